@@ -13,9 +13,24 @@ relays rank 0's single JSON line and exits with the worst child's return code (l
 
 Prints ONE JSON line (rank 0).  `value` = samples all ranks processed / max-over-ranks time of
 exactly K steps bracketed by barrier + synchronize; inputs are resident in HBM before the timed
-region.  `roofline` is measured live with HIP events around every launch of the dominant kernel
-family (the fp32-MFMA implicit-GEMM convolutions) in extra, separately run profiled steps;
-`cpu_baseline` times the CPU oracle (a port of the reference path) on this box's host cores.
+region; `ms_per_step` = that time / K.  A plain run does nothing else: it sets up, warms up, times
+the K steps, writes the last step's outputs (--dump-outputs DIR) and prints the line.
+
+--full adds the secondary figures, each in runs of its own after the timed steps: `roofline` is
+measured live with HIP events around every launch of the dominant kernel family (the implicit-GEMM
+convolutions) in extra, separately run profiled steps (with `roofline_fusion` and `kernel_families`);
+`cpu_baseline` times the CPU oracle (a port of the reference path) on the host's cores.
+
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
+    python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
+
+--dump-outputs DIR writes what the timed path handed its caller in the last timed step as
+DIR/<name>.npy (float32): the loss, the model's outputs (pred_gaze, the per-iteration predictions
+`preds`, img_feat, initial_rot_feat, the fused features `feats`), and in training a sample of every
+parameter's gradient (`grad_sample`) and, after the Adam step, of every parameter (`param_sample`).
+Arrays above DUMP_MAX_ELEMS elements, and the per-parameter samples, are fixed, seeded samples (the
+indices depend only on the array's name and size), so two builds run with the same arguments can be
+compared file by file; the inputs and weights are seeded as well.
 """
 import argparse
 import json
@@ -41,6 +56,9 @@ BF16_WORKLOADS = {"c5"}
 PEAK_BF16_MFMA_TFLOPS = 2500.0     # MI355X_MICROARCH.md: dense bf16 / fp16 MFMA (the 5 PF headline includes 2:1 sparsity)
 PEAK_FP32_MFMA_TFLOPS = 157.3      # MI355X_MICROARCH.md: v_mfma_f32_32x32x2_f32, dense
 PEAK_HBM_GBS = 8000.0
+DUMP_MAX_ELEMS = 2 << 20           # --dump-outputs: larger arrays are written as a seeded sample of this many elements
+DUMP_PARAM_SAMPLE = 4096           # ... and this many elements of each parameter / gradient
+DUMP_BUDGET_BYTES = 64_000_000
 
 
 def sample_flops(depth, views):
@@ -205,16 +223,70 @@ def launch_ranks(world, argv, script=None, extra_env=None, timeout=None, python=
     return worst, (out0[0] if out0 else "")
 
 
-def main():
+def _dump_sample(name, n, k):
+    """Sorted indices of a fixed sample of k of n elements: a function of (name, n, k) alone."""
+    import zlib
+    import numpy as np
+    rng = np.random.default_rng(zlib.crc32(f"{name}:{n}".encode()))
+    return np.sort(rng.choice(n, size=k, replace=False))
+
+
+def dump_outputs(out_dir, arrays, params=(), grads=()):
+    """Write `arrays` (name -> tensor) as out_dir/<name>.npy in float32, arrays above DUMP_MAX_ELEMS elements as a
+    seeded sample; `params` / `grads` ((name, tensor) in model order) as one `param_sample` / `grad_sample` array of
+    up to DUMP_PARAM_SAMPLE seeded elements per tensor.  Returns the names written."""
+    import numpy as np
+    import torch
+
+    def flat_sample(name, t, k):
+        t = t.detach().reshape(-1)
+        if t.numel() <= k:
+            return t.float().cpu().numpy()
+        idx = torch.from_numpy(_dump_sample(name, t.numel(), k)).to(t.device)
+        return t.index_select(0, idx).float().cpu().numpy()
+
+    files = {}
+    for name, t in arrays.items():
+        a = flat_sample(name, t, DUMP_MAX_ELEMS) if t.numel() > DUMP_MAX_ELEMS else t.detach().float().cpu().numpy()
+        files[name] = a
+    for key, seq in (("param_sample", params), ("grad_sample", grads)):
+        parts = [flat_sample(n, t, DUMP_PARAM_SAMPLE) for n, t in seq]
+        if parts:
+            files[key] = np.concatenate(parts)
+    total = sum(a.nbytes for a in files.values())
+    assert total <= DUMP_BUDGET_BYTES, f"--dump-outputs: {total} bytes exceed the {DUMP_BUDGET_BYTES}-byte budget"
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in files.items():
+        np.save(os.path.join(out_dir, f"{name}.npy"), np.ascontiguousarray(a, dtype=np.float32))
+    return sorted(files)
+
+
+def build_parser():
     ap = argparse.ArgumentParser()
+
+    def positive(v):
+        if int(v) < 1:
+            raise argparse.ArgumentTypeError(f"must be >= 1, got {v}")
+        return int(v)
+
+    def non_negative(v):
+        if int(v) < 0:
+            raise argparse.ArgumentTypeError(f"must be >= 0, got {v}")
+        return int(v)
+
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
-    ap.add_argument("--warmup", type=int, default=5)
+    ap.add_argument("--steps", type=positive, default=20, help="timed steps (ms_per_step = their time / steps)")
+    ap.add_argument("--warmup", type=non_negative, default=5)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the secondary figures after the timed steps: roofline, roofline_fusion and kernel_families "
+                         "(extra profiled steps) and cpu_baseline (the CPU oracle); a plain run reports them as null")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (float32, seeded samples of large arrays)")
     ap.add_argument("--workload", default="c3", choices=sorted(WORKLOADS),
                     help="default: the largest single-GPU configuration of BASELINE.json (C3)")
     ap.add_argument("--batch", type=int, default=0, help="override the per-GPU batch")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip roofline, roofline_fusion and kernel_families")
     ap.add_argument("--bucket-mb", type=float, default=25.0, help="data-parallel gradient bucket size")
     # one-rank RCCL rehearsal at C3 (MVG_FORCE_DIST=1, profiles/README.md): plain 159.2 ms; 0 reserved CUs / 4 channels
     # 163.3; 4 / 4 165.0; 8 / 8 165.3; 12 / 8 166.1.  The gradient stream is 358 MB per ~160 ms step: a few GB/s, far
@@ -228,14 +300,18 @@ def main():
                     help="N = 1 training: capture zero_grad + forward + loss + backward + Adam once in a hipGraph and replay it "
                          "(rot_mvgaze_amd/graph.py).  Host time per step drops from ~20 ms to 0.15 ms; the GPU time does not (the eager "
                          "step is GPU-bound) and the capture is single-stream - a captured side stream replays 1.4-1.7x slower on "
-                         "ROCm 7.0 - so the weight-gradient overlap (+6 %) is lost: off by default (profiles/README.md, round 4)")
+                         "ROCm 7.0 - so the weight-gradient overlap (+6 %%) is lost: off by default (profiles/README.md, round 4)")
     ap.add_argument("--no-overlap", action="store_true",
                     help="run the backward-weight kernels on the compute stream (per-kernel profiling: rocprofv3 --stats)")
     ap.add_argument("--dtype", default=None, choices=["f32", "bf16"],
                     help="backbone storage / matrix-core type (default: f32, bf16 for --workload c5)")
     ap.add_argument("--mode", default="train", choices=["train", "eval"],
                     help="eval = inference forward only (model.eval(), BN folded into the convs; SURVEY §8(f) rank 2)")
-    args = ap.parse_args()
+    return ap
+
+
+def main():
+    args = build_parser().parse_args()
 
     if args.gpus > 1 and "RANK" not in os.environ:
         # bare `python bench.py --gpus N`: become the launcher (no torch / HIP in this process)
@@ -322,13 +398,19 @@ def main():
         model.ensure_layout()
         model._backbone.overlap_wgrad = False
 
+    last = {}            # --dump-outputs: the latest step's output dict (its tape is released by backward)
+
     def step():
         if args.mode == "eval":
             with torch.no_grad():
                 out = model.forward_multiview(img, rot)
+            if args.dump_outputs:
+                last["out"] = out
             return out["pred_gaze"].sum()
         model.zero_grad(set_to_none=True)
         out = model.forward_multiview(img, rot)
+        if args.dump_outputs:
+            last["out"] = out
         loss = criterion(out, gt)
         loss.backward()
         if optimizer is not None:
@@ -370,9 +452,25 @@ def main():
     value = world * B * args.steps / elapsed
     loss_val = float(loss.item())
 
-    # ---- roofline of the dominant kernel family (separate, event-instrumented steps)
+    # ---- what the last timed step handed its caller (before any --full step touches the model again)
+    if args.dump_outputs and rank == 0:
+        out = last["out"]
+        pairs = list(out["pairs"].values())
+        arrays = {"pred_gaze": out["pred_gaze"], "preds": out["_mvg_preds"], "img_feat": out["img_feat"],
+                  "initial_rot_feat": out["initial_rot_feat"],
+                  "feats": torch.stack([torch.stack([pd[f"iter_{it}"][f"feat_{s}"] for pd in pairs for s in (0, 1)])
+                                        for it in range(pairs[0]["num_iter"])])}
+        named = list(model.named_parameters())
+        if args.mode == "train":
+            arrays["loss"] = loss
+        dump_outputs(args.dump_outputs, arrays,
+                     params=named if optimizer is not None else (),
+                     grads=[(n, p.grad) for n, p in named if p.grad is not None] if args.mode == "train" else ())
+        del out, pairs, arrays
+
+    # ---- --full only: roofline of the dominant kernel family (separate, event-instrumented steps)
     roofline, families = None, None
-    if not args.no_roofline:
+    if args.full and not args.no_roofline:
         nprof = min(args.steps, 3)
         # per-kernel durations are taken with the kernels alone on the GPU: the timed region overlaps the
         # backward-weight kernels (side stream) with the rest of backward, which stretches every
@@ -468,7 +566,7 @@ def main():
                         "builders (rotcat) + the gradient splits (colsum) + loss + geometry launches"}
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         cpu = cpu_baseline(depth, V)
 
     if rank == 0:

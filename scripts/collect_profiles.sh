@@ -7,11 +7,11 @@ TAG=${1:-r03}
 O=gpurun_out
 cd "$(dirname "$0")/.." || exit 1
 export TMPDIR=/tmp
-( time python3 bench.py > $O/${TAG}_bench_c3.json 2> $O/${TAG}_bench.err ) 2> $O/${TAG}_bench_c3_walltime.txt || exit 1; echo "c3 bench done"
-for w in c2 c4 c5 r50v2 c5fp32; do python3 bench.py --workload $w --no-cpu-baseline > $O/${TAG}_bench_$w.json 2>> $O/${TAG}_bench.err || exit 1; done
-python3 bench.py --mode eval --workload c2 --no-cpu-baseline > $O/${TAG}_bench_c2_eval.json 2>> $O/${TAG}_bench.err || exit 1
-python3 bench.py --mode eval --no-cpu-baseline > $O/${TAG}_bench_c3_eval.json 2>> $O/${TAG}_bench.err || exit 1
-MVG_SPLIT=0 python3 bench.py --no-cpu-baseline > $O/${TAG}_bench_c3_fp32mfma.json 2>> $O/${TAG}_bench.err || exit 1
+( time python3 bench.py --full > $O/${TAG}_bench_c3.json 2> $O/${TAG}_bench.err ) 2> $O/${TAG}_bench_c3_walltime.txt || exit 1; echo "c3 bench done"
+for w in c2 c4 c5 r50v2 c5fp32; do python3 bench.py --full --workload $w --no-cpu-baseline > $O/${TAG}_bench_$w.json 2>> $O/${TAG}_bench.err || exit 1; done
+python3 bench.py --full --mode eval --workload c2 --no-cpu-baseline > $O/${TAG}_bench_c2_eval.json 2>> $O/${TAG}_bench.err || exit 1
+python3 bench.py --full --mode eval --no-cpu-baseline > $O/${TAG}_bench_c3_eval.json 2>> $O/${TAG}_bench.err || exit 1
+MVG_SPLIT=0 python3 bench.py --full --no-cpu-baseline > $O/${TAG}_bench_c3_fp32mfma.json 2>> $O/${TAG}_bench.err || exit 1
 # the captured step (single-stream hipGraph replay): host time per step vs the eager step
 for w in c3 c4 c2; do python3 bench.py --workload $w --graph --no-cpu-baseline --no-roofline > $O/${TAG}_bench_${w}_graph.json 2>> $O/${TAG}_bench.err || exit 1; done
 python3 scripts/graph_probe.py c4 2>&1 | grep -v amdgpu.ids > $O/${TAG}_graph_probe_c4.txt
