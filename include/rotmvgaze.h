@@ -223,6 +223,21 @@ int mvg_bn_bwd_apply(const float *g, const float *act, const float *y, const flo
                      const float *invstd, const float *gamma, const float *s1, const float *s2,
                      const float *relu_scale, const float *relu_shift, int groups,
                      int64_t rows_per_group, int c, float *dy, float *dz_out, void *stream);
+/* Eval mode (model.eval() with gradients): backward of BatchNorm2d on its RUNNING statistics - what autograd
+ * differentiates for F.batch_norm(training=False) in resnet.py:84,88,132,136,140 (:91,143: the downsample
+ * BatchNorm) - in ONE pass, since nothing depends on batch sums:
+ *   dz = g masked by the unit's ReLU,  dy = gamma*invstd_r*dz,  invstd_r = 1/sqrt(running_var + eps),
+ *   dbeta[c] (+)= sum dz,  dgamma[c] (+)= sum dz*(y - running_mean)*invstd_r  (over every row of every group).
+ * The mask, as the forward decided it: act > 0, relu_bits (mvg_bn_apply_bits' layout), or fma(y, relu_scale,
+ * relu_shift) > 0 with the [groups][c] scale / shift of mvg_bn_eval_affine; all NULL: no ReLU (downsample branch).
+ * dy may alias g; dz_out (optional, may alias g, not dy) receives dz for the residual branch.  The sums are left
+ * per (group, chunk, channel) in `workspace` and a second launch adds them in a fixed order (reproducible);
+ * dgamma / dbeta NULL: no sums.  workspace: mvg_bn_eval_bwd_workspace_floats() floats (both entry points). */
+int mvg_bn_eval_bwd(const float *g, const float *act, const uint8_t *relu_bits, const float *y, const float *relu_scale,
+                    const float *relu_shift, const float *gamma, const float *running_mean, const float *running_var,
+                    float eps, int groups, int64_t rows_per_group, int c, float *dy, float *dz_out, float *dgamma,
+                    float *dbeta, int accumulate, float *workspace, void *stream);
+size_t mvg_bn_eval_bwd_workspace_floats(int groups, int64_t rows_per_group, int c);
 
 /* ---------------------------------------------------------------- pooling / layout
  * nn.MaxPool2d(3,2,1) resnet.py:189; nn.AdaptiveAvgPool2d((1,1)) resnet.py:200 + rot_mv.py:126;
@@ -250,6 +265,15 @@ int mvg_bn_relu_maxpool_bwd_apply(const float *g_pooled, const uint8_t *argmax, 
                                   const float *scale, const float *shift, const float *s1,
                                   const float *s2, int groups, int n_per_group, int h, int w, int c,
                                   int ho, int wo, float *dy, void *stream);
+/* The stem tail in eval mode (resnet.py:262-265 with bn1 on its running statistics): max-pool backward through
+ * argmax, the ReLU mask fma(y, scale, shift) > 0 (scale / shift [groups][c] of mvg_bn_eval_affine), and
+ * dy = gamma*invstd_r*dz in one pass that writes dy [groups][n_per_group][h][w][c] once; dgamma / dbeta as
+ * mvg_bn_eval_bwd.  c/4 must divide 256. */
+int mvg_bn_relu_maxpool_eval_bwd(const float *g_pooled, const uint8_t *argmax, const float *y, const float *scale,
+                                 const float *shift, const float *gamma, const float *running_mean,
+                                 const float *running_var, float eps, int groups, int n_per_group, int h, int w,
+                                 int c, int ho, int wo, float *dy, float *dgamma, float *dbeta, int accumulate,
+                                 float *workspace, void *stream);
 int mvg_avgpool_fwd(const float *x, float *y, int n, int hw, int c, void *stream);
 int mvg_avgpool_bwd(const float *dy, float *dx, int n, int hw, int c, void *stream);
 int mvg_nchw_to_nhwc4(const float *src, float *dst, int n, int c, int h, int w, void *stream);

@@ -108,6 +108,11 @@ SIGNATURES = {
     "mvg_bn_relu_maxpool_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P,
                                             _P]),
     "mvg_bn_relu_maxpool_bwd_apply": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    # eval mode (running statistics): one-pass BatchNorm backward, and its stem-tail form
+    "mvg_bn_eval_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I64, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "mvg_bn_eval_bwd_workspace_floats": (C.c_size_t, [_I, _I64, _I]),
+    "mvg_bn_relu_maxpool_eval_bwd": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P,
+                                          _P]),
     "mvg_avgpool_fwd": (_I, [_P, _P, _I, _I, _I, _P]),
     "mvg_avgpool_bwd": (_I, [_P, _P, _I, _I, _I, _P]),
     "mvg_nchw_to_nhwc4": (_I, [_P, _P, _I, _I, _I, _I, _P]),

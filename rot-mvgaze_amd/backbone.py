@@ -448,6 +448,8 @@ class Backbone:
     def _bn_bwd(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink):
         """g = grad wrt the unit's output.  Returns (dy, dz): dy = grad wrt the conv output;
         dz = g masked by the unit's ReLU (written in place into g) when the residual branch needs it."""
+        if not u.trained:
+            return self._bn_bwd_eval(u, g, need_dz, sink)
         c = u.spec
         G = u.y.shape[0]
         gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
@@ -498,6 +500,30 @@ class Backbone:
                           acc, ra)
         ops.bn_bwd_apply(g, act, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, g, None, ra)
         return g, None
+
+    def _bn_bwd_eval(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink):
+        """_bn_bwd for a unit whose forward normalised with the running statistics (eval mode, fp32-MFMA kernels): one
+        pass (ops.bn_eval_bwd) - dy needs no batch sums.  The tape's mean / invstd were never filled and are not read:
+        the kernel takes the running statistics, and the ReLU mask from where the forward left it."""
+        c = u.spec
+        G = u.y.shape[0]
+        gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
+        rm, rv = self.p[c.bn + ".running_mean"], self.p[c.bn + ".running_var"]
+        acc = sink.accumulate(gp)
+        assert acc == sink.accumulate(bp)
+        if u.relu_bits is not None:
+            mask = {"relu_bits": u.relu_bits}
+        elif u.relu_affine is not None:
+            mask = {"relu_affine": u.relu_affine}
+        elif u.relu:
+            mask = {"act": u.out}
+        else:
+            mask = {}
+        # the residual branch needs dz: it stays in g, dy goes to a new buffer; otherwise dy overwrites g
+        dy = torch.empty_like(g) if need_dz else g
+        ops.bn_eval_bwd(g, u.y, gp.detach(), rm, rv, BN_EPS, G, u.rows, c.cout, dy, sink.view(gp), sink.view(bp), acc,
+                        dz_out=g if need_dz else None, **mask)
+        return dy, (g if need_dz else None)
 
     def _side(self, dev) -> "torch.cuda.Stream":
         if self._wg_stream is None or self._wg_stream.device != dev or self._wg_low != self.wgrad_low_priority:
@@ -618,9 +644,9 @@ class Backbone:
         order they become final); returns d(img) as V NCHW tensors when need_dimg."""
         V, B = tape["V"], tape["B"]
         units: List[_Unit] = tape["units"]
-        if not all(u.trained for u in units):
-            raise NotImplementedError("backward through eval-mode BatchNorm (running statistics) is not implemented: "
-                                      "call model.train() for gradient steps")
+        if self.bf16 and not all(u.trained for u in units):
+            raise NotImplementedError("backward through eval-mode BatchNorm (running statistics) is not implemented on the "
+                                      "bf16 path: call model.train() for gradient steps, or use the fp32 model")
         Hc, Wc = tape["final_hw"]
         if need_dimg and self.bf16:
             raise NotImplementedError("d(loss)/d(img) is not produced by the bf16 path")
@@ -678,7 +704,13 @@ class Backbone:
         s12 = torch.empty(3 if stem_sp else 2, V, sc.cout, dtype=torch.float32, device=g.device)
         acc = sink.accumulate(gp)
         assert acc == sink.accumulate(bp)
-        if stem_sp:
+        if not stem.trained:
+            # eval mode: max pool + ReLU + BatchNorm on the running statistics, one pass (no batch sums to wait for)
+            dy = torch.empty_like(stem.y)
+            ops.bn_relu_maxpool_eval_bwd(g, argmax, stem.y, scale, shift, gp.detach(), P[sc.bn + ".running_mean"],
+                                         P[sc.bn + ".running_var"], BN_EPS, V, B, H1, W1, sc.cout, Hp, Wp, dy, sink.view(gp),
+                                         sink.view(bp), acc)
+        elif stem_sp:
             # the stem's weight gradient runs on the split kernels: dy goes out in sp, scaled by a bound from the reduce pass
             sinv = torch.empty(1, dtype=torch.float32, device=g.device)
             ops.bn_relu_maxpool_bwd_reduce_split(g, argmax, stem.y, stem.mean, stem.invstd, scale, shift, V, B, H1, W1, sc.cout, Hp, Wp,

@@ -1081,6 +1081,243 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const T *__restr
     }
 }
 
+// ---- eval mode: BatchNorm on the running statistics, backward in ONE streaming pass -----------------------------
+// With x-hat = (y - running_mean) * invstd_r, invstd_r = 1 / sqrt(running_var + eps) and dz = g masked by the ReLU:
+//   dy = gamma * invstd_r * dz,   dbeta = sum dz,   dgamma = sum dz * x-hat
+// dy needs no sum, so the train-mode pair (reduce, then an apply that waits for it) becomes one pass reading g, y (and
+// the mask) and writing dy; the sums leave per-(group, chunk, channel) partials in bn_bwd_reduce_kernel's layout
+// ([groups][chunks][2][c]) and bn_eval_bwd_finalize_kernel adds them in a fixed order.  The mask is the forward's:
+// relu_bits (bn_apply_bits), act > 0, or fma(y, mscale, mshift) > 0 with bn_eval_affine's scale / shift (bn_apply_kernel's
+// expression); none of them: no ReLU.  dy and dz_out may alias g (every element is read, then written, by one lane).
+__device__ __forceinline__ void bn_eval_factors(const float *gamma, const float *rmean, const float *rvar, float eps, int cq,
+                                                float4 &mu, float4 &is, float4 &k) {
+  const float4 ga = reinterpret_cast<const float4 *>(gamma)[cq], rm = reinterpret_cast<const float4 *>(rmean)[cq];
+  const float4 rv = reinterpret_cast<const float4 *>(rvar)[cq];
+  const float4 sd = make_float4(sqrtf(rv.x + eps), sqrtf(rv.y + eps), sqrtf(rv.z + eps), sqrtf(rv.w + eps));
+  mu = rm;
+  is = make_float4(1.f / sd.x, 1.f / sd.y, 1.f / sd.z, 1.f / sd.w);
+  k = make_float4(ga.x / sd.x, ga.y / sd.y, ga.z / sd.z, ga.w / sd.w);     // = bn_eval_affine_kernel's scale
+}
+
+// grid = (chunks, column blocks, groups); thread = one float4 column group x one row lane (bn_bwd_reduce_kernel's shape)
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float *g, const float *__restrict__ act, const float *__restrict__ y,
+                                                          const unsigned char *__restrict__ relu_bits,
+                                                          const float *__restrict__ mscale, const float *__restrict__ mshift,
+                                                          const float *__restrict__ gamma, const float *__restrict__ rmean,
+                                                          const float *__restrict__ rvar, float eps, long long rows,
+                                                          long long rows_per_chunk, int c, int cwn, int cw, float *dy, float *dz_out,
+                                                          float *__restrict__ partial, int chunks) {
+  __shared__ float4 sh[2][256];
+  const int grp = blockIdx.z;
+  const int rl = threadIdx.x / cw, cl = threadIdx.x % cw;
+  const int nrl = 256 / cw;
+  const int cq = blockIdx.y * cw + cl;
+  const bool cok = cq < cwn;
+  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+  if (cok) {
+    float4 mu, is, k, ma = s1, mb = s1;
+    bn_eval_factors(gamma, rmean, rvar, eps, cq, mu, is, k);
+    if (mscale) {
+      ma = reinterpret_cast<const float4 *>(mscale + (long long)grp * c)[cq];
+      mb = reinterpret_cast<const float4 *>(mshift + (long long)grp * c)[cq];
+    }
+    const long long r0 = (long long)blockIdx.x * rows_per_chunk;
+    long long r1 = r0 + rows_per_chunk;
+    if (r1 > rows) r1 = rows;
+    const long long gbase = (long long)grp * rows * cwn;
+    auto row = [&](long long r, float4 &a1, float4 &a2) {
+      const long long off = gbase + r * cwn + cq;
+      float4 d = reinterpret_cast<const float4 *>(g)[off];
+      const float4 v = reinterpret_cast<const float4 *>(y)[off];
+      if (relu_bits) {
+        const unsigned m4 = relu_bits[off];
+        d.x = (m4 & 1u) ? d.x : 0.f;
+        d.y = (m4 & 2u) ? d.y : 0.f;
+        d.z = (m4 & 4u) ? d.z : 0.f;
+        d.w = (m4 & 8u) ? d.w : 0.f;
+      } else if (act) {
+        const float4 a = reinterpret_cast<const float4 *>(act)[off];
+        d.x = a.x > 0.f ? d.x : 0.f;
+        d.y = a.y > 0.f ? d.y : 0.f;
+        d.z = a.z > 0.f ? d.z : 0.f;
+        d.w = a.w > 0.f ? d.w : 0.f;
+      } else if (mscale) {
+        d.x = __builtin_fmaf(v.x, ma.x, mb.x) > 0.f ? d.x : 0.f;
+        d.y = __builtin_fmaf(v.y, ma.y, mb.y) > 0.f ? d.y : 0.f;
+        d.z = __builtin_fmaf(v.z, ma.z, mb.z) > 0.f ? d.z : 0.f;
+        d.w = __builtin_fmaf(v.w, ma.w, mb.w) > 0.f ? d.w : 0.f;
+      }
+      a1.x += d.x; a1.y += d.y; a1.z += d.z; a1.w += d.w;
+      a2.x += d.x * ((v.x - mu.x) * is.x);
+      a2.y += d.y * ((v.y - mu.y) * is.y);
+      a2.z += d.z * ((v.z - mu.z) * is.z);
+      a2.w += d.w * ((v.w - mu.w) * is.w);
+      if (dz_out) reinterpret_cast<float4 *>(dz_out)[off] = d;
+      reinterpret_cast<float4 *>(dy)[off] = make_float4(k.x * d.x, k.y * d.y, k.z * d.z, k.w * d.w);
+    };
+    constexpr int U = 4;          // rows in flight per thread (bn_bwd_reduce_kernel's count for fp32)
+    float4 t1[U - 1], t2[U - 1];
+#pragma unroll
+    for (int u = 0; u < U - 1; ++u) t1[u] = t2[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    long long r = r0 + rl;
+    for (; r + (U - 1) * (long long)nrl < r1; r += U * (long long)nrl) {
+      row(r, s1, s2);
+#pragma unroll
+      for (int u = 1; u < U; ++u) row(r + u * (long long)nrl, t1[u - 1], t2[u - 1]);
+    }
+    for (; r < r1; r += nrl) row(r, s1, s2);
+    s1.x += t1[0].x + (t1[1].x + t1[2].x); s1.y += t1[0].y + (t1[1].y + t1[2].y);
+    s1.z += t1[0].z + (t1[1].z + t1[2].z); s1.w += t1[0].w + (t1[1].w + t1[2].w);
+    s2.x += t2[0].x + (t2[1].x + t2[2].x); s2.y += t2[0].y + (t2[1].y + t2[2].y);
+    s2.z += t2[0].z + (t2[1].z + t2[2].z); s2.w += t2[0].w + (t2[1].w + t2[2].w);
+  }
+  sh[0][threadIdx.x] = s1;
+  sh[1][threadIdx.x] = s2;
+  __syncthreads();
+  if (rl == 0 && cok) {
+    for (int j = 1; j < nrl; ++j) {
+      const float4 a = sh[0][j * cw + cl], b = sh[1][j * cw + cl];
+      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
+      s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
+    }
+    float4 *p = reinterpret_cast<float4 *>(partial + (((long long)grp * chunks + blockIdx.x) * 2) * c);
+    p[cq] = s1;
+    p[c / 4 + cq] = s2;
+  }
+}
+
+// The stem tail in eval mode: max-pool backward through argmax, the ReLU mask from y, then dy = gamma invstd_r dz - the
+// quad gather of bn_pool_bwd_apply_kernel (a lane owns a 2 x 2 pixel quad x 4 channels and deals out the four windows that
+// quad can have won), so the 112 x 112 gradient map is written once, as dy.  grid = (chunks, groups), a grid-stride loop
+// over the group's (image, quad row, quad column, channel group) items; c/4 divides 256, so a lane keeps its channels and
+// the workgroup's partial sums go to partial[group][blockIdx.x] ([groups][chunks][2][c], as above).
+__global__ __launch_bounds__(256) void bn_pool_eval_bwd_kernel(const float *__restrict__ gp, const uchar4 *__restrict__ am,
+                                                               const float *__restrict__ y, const float *__restrict__ mscale,
+                                                               const float *__restrict__ mshift, const float *__restrict__ gamma,
+                                                               const float *__restrict__ rmean, const float *__restrict__ rvar,
+                                                               float eps, int n_per_group, int h, int w, int ho, int wo, int c4n,
+                                                               float *__restrict__ dy, float *__restrict__ partial) {
+  __shared__ float4 sh[2][256];
+  const int hq = (h + 1) >> 1, wq = (w + 1) >> 1;
+  const int grp = blockIdx.y;
+  const int cq = threadIdx.x % c4n;            // 256 % c4n == 0 and the grid stride is a multiple of 256
+  float4 mu, is, k;
+  bn_eval_factors(gamma, rmean, rvar, eps, cq, mu, is, k);
+  const float4 sa = reinterpret_cast<const float4 *>(mscale)[(long long)grp * c4n + cq];
+  const float4 sb = reinterpret_cast<const float4 *>(mshift)[(long long)grp * c4n + cq];
+  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+  const long long items = (long long)n_per_group * hq * wq * c4n;
+  const long long stride = (long long)gridDim.x * 256;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += stride) {
+    const long long q = i / c4n;
+    const int qb = (int)(q % wq);
+    const long long line = q / wq;
+    const int qa = (int)(line % hq);
+    const long long n = (long long)grp * n_per_group + line / hq;
+    uchar4 wk[2][2];
+    float4 wg[2][2];
+#pragma unroll
+    for (int a = 0; a < 2; ++a)
+#pragma unroll
+      for (int b = 0; b < 2; ++b) {
+        const bool ok = qa + a < ho && qb + b < wo;
+        const long long o = ((n * ho + qa + a) * wo + qb + b) * c4n + cq;
+        wk[a][b] = ok ? am[o] : make_uchar4(255, 255, 255, 255);
+        wg[a][b] = ok ? reinterpret_cast<const float4 *>(gp)[o] : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+    float4 v[2][2];
+    bool pok[2][2];
+#pragma unroll
+    for (int pi = 0; pi < 2; ++pi)
+#pragma unroll
+      for (int pj = 0; pj < 2; ++pj) {
+        pok[pi][pj] = 2 * qa + pi < h && 2 * qb + pj < w;
+        v[pi][pj] = pok[pi][pj] ? reinterpret_cast<const float4 *>(y)[((n * h + 2 * qa + pi) * w + 2 * qb + pj) * c4n + cq]
+                                : make_float4(0.f, 0.f, 0.f, 0.f);
+      }
+#pragma unroll
+    for (int pi = 0; pi < 2; ++pi)
+#pragma unroll
+      for (int pj = 0; pj < 2; ++pj) {
+        if (!pok[pi][pj]) continue;
+        // pixel (2 qa + pi, 2 qb + pj) inside window (qa + a, qb + b): kh = pi + 1 - 2 a, kw = pj + 1 - 2 b
+        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+        for (int a = 0; a < 2; ++a) {
+          const int kh = pi + 1 - 2 * a;
+          if (kh < 0) continue;
+#pragma unroll
+          for (int b = 0; b < 2; ++b) {
+            const int kw = pj + 1 - 2 * b;
+            if (kw < 0) continue;
+            const unsigned char me = (unsigned char)(kh * 3 + kw);
+            const uchar4 kk = wk[a][b];
+            const float4 gg = wg[a][b];
+            if (kk.x == me) d.x += gg.x;
+            if (kk.y == me) d.y += gg.y;
+            if (kk.z == me) d.z += gg.z;
+            if (kk.w == me) d.w += gg.w;
+          }
+        }
+        const float4 vv = v[pi][pj];
+        d.x = __builtin_fmaf(vv.x, sa.x, sb.x) > 0.f ? d.x : 0.f;
+        d.y = __builtin_fmaf(vv.y, sa.y, sb.y) > 0.f ? d.y : 0.f;
+        d.z = __builtin_fmaf(vv.z, sa.z, sb.z) > 0.f ? d.z : 0.f;
+        d.w = __builtin_fmaf(vv.w, sa.w, sb.w) > 0.f ? d.w : 0.f;
+        s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
+        s2.x += d.x * ((vv.x - mu.x) * is.x);
+        s2.y += d.y * ((vv.y - mu.y) * is.y);
+        s2.z += d.z * ((vv.z - mu.z) * is.z);
+        s2.w += d.w * ((vv.w - mu.w) * is.w);
+        reinterpret_cast<float4 *>(dy)[((n * h + 2 * qa + pi) * w + 2 * qb + pj) * c4n + cq] =
+            make_float4(k.x * d.x, k.y * d.y, k.z * d.z, k.w * d.w);
+      }
+  }
+  sh[0][threadIdx.x] = s1;
+  sh[1][threadIdx.x] = s2;
+  __syncthreads();
+  if (threadIdx.x < c4n) {
+    for (int j = threadIdx.x + c4n; j < 256; j += c4n) {
+      const float4 a = sh[0][j], b = sh[1][j];
+      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
+      s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
+    }
+    float4 *p = reinterpret_cast<float4 *>(partial + (((long long)grp * gridDim.x + blockIdx.x) * 2) * (4 * c4n));
+    p[cq] = s1;
+    p[c4n + cq] = s2;
+  }
+}
+
+// dgamma (+)= the sum of every (group, chunk) partial's s2 row, dbeta (+)= ... of the s1 rows.  grid = c/16 workgroups of
+// 1024 lanes = 16 channels x 64 partial-lanes; every lane adds a fixed stride of the partials in fp64 (groups in order),
+// then a fixed tree: the same sums every run.
+__global__ __launch_bounds__(1024) void bn_eval_bwd_finalize_kernel(const float *__restrict__ partial, int n_partials, int c,
+                                                                    float *dgamma, float *dbeta, int accumulate) {
+  __shared__ double sh[2][64][16];
+  const int cl = threadIdx.x & 15, pl = threadIdx.x >> 4;
+  const int ch = blockIdx.x * 16 + cl;
+  double a = 0.0, b = 0.0;
+  if (ch < c)
+    for (int k = pl; k < n_partials; k += 64) {
+      a += partial[(long long)k * 2 * c + ch];
+      b += partial[((long long)k * 2 + 1) * c + ch];
+    }
+  sh[0][pl][cl] = a;
+  sh[1][pl][cl] = b;
+  __syncthreads();
+  for (int o = 32; o > 0; o >>= 1) {
+    if (pl < o) {
+      sh[0][pl][cl] += sh[0][pl + o][cl];
+      sh[1][pl][cl] += sh[1][pl + o][cl];
+    }
+    __syncthreads();
+  }
+  if (pl == 0 && ch < c) {
+    if (dbeta) dbeta[ch] = (accumulate ? dbeta[ch] : 0.f) + (float)sh[0][0][cl];
+    if (dgamma) dgamma[ch] = (accumulate ? dgamma[ch] : 0.f) + (float)sh[1][0][cl];
+  }
+}
+
 static int bwd_chunks(int groups, long long rows, int c) {
   // at least 64 rows per chunk
   const int c4n = c / 4;
@@ -1096,6 +1333,12 @@ static int bwd_chunks(int groups, long long rows, int c) {
   long long maxc = (rows + 63) / 64;
   if (want > maxc) want = maxc;
   return (int)want;
+}
+
+// workgroups per group of bn_pool_eval_bwd_kernel's grid-stride loop (= its partials per group): four per CU in all
+static int eval_pool_chunks(int groups) {
+  const int b = 4 * compute_cus() / groups;
+  return b > 1 ? b : 1;
 }
 
 static int grid_for(long long n4) {
@@ -1470,5 +1713,66 @@ int mvg_bn_relu_maxpool_bwd_apply_split(const float *g_pooled, const uint8_t *ar
 MVG_BN_BITS_FACES(, float)
 MVG_BN_BITS_FACES(_bf16, uint16_t)
 #undef MVG_BN_BITS_FACES
+
+// ---- eval mode (running statistics): the one-pass backward and its stem-tail form ---------------------------------
+size_t mvg_bn_eval_bwd_workspace_floats(int groups, int64_t rows_per_group, int c) {
+  const int a = bwd_chunks(groups, rows_per_group, c), b = eval_pool_chunks(groups);
+  return (size_t)groups * (a > b ? a : b) * 2 * c;
+}
+
+int mvg_bn_eval_bwd(const float *g, const float *act, const uint8_t *relu_bits, const float *y, const float *relu_scale,
+                    const float *relu_shift, const float *gamma, const float *running_mean, const float *running_var, float eps,
+                    int groups, int64_t rows_per_group, int c, float *dy, float *dz_out, float *dgamma, float *dbeta,
+                    int accumulate, float *workspace, void *stream) {
+  MVG_REQUIRE((act ? 1 : 0) + (relu_bits ? 1 : 0) + (relu_scale ? 1 : 0) <= 1,
+              "bn_eval_bwd: give the ReLU mask ONE way: act, relu_bits or (relu_scale, relu_shift)");
+  MVG_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "bn_eval_bwd: relu_scale and relu_shift go together");
+  MVG_REQUIRE(g && y && dy && gamma && running_mean && running_var && workspace,
+              "bn_eval_bwd: g, y, dy, gamma, running_mean, running_var and workspace are required");
+  MVG_REQUIRE(dz_out == nullptr || dz_out != dy, "bn_eval_bwd: dz_out and dy must be different buffers");
+  MVG_REQUIRE(groups > 0 && groups < 65536 && rows_per_group > 0 && c > 0 && c % 4 == 0, "bn_eval_bwd: bad sizes");
+  const int c4n = c / 4;
+  const int cw = c4n < 256 ? c4n : 256;
+  MVG_REQUIRE(256 % cw == 0, "bn_eval_bwd: c/4 must divide 256 or be a multiple of it (c=%d)", c);
+  hipStream_t st = (hipStream_t)stream;
+  const int chunks = bwd_chunks(groups, rows_per_group, c);
+  const long long rpc = (rows_per_group + chunks - 1) / chunks;
+  ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0,
+               4.0 * groups * (double)rows_per_group * c * (3 + (act ? 1 : 0) + (dz_out ? 1 : 0)) +
+                   (relu_bits ? groups * (double)rows_per_group * c4n : 0.0));
+  hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(chunks, ceil_div(c4n, cw), groups), dim3(256), 0, st, g, act, y, relu_bits, relu_scale,
+                     relu_shift, gamma, running_mean, running_var, eps, (long long)rows_per_group, rpc, c, c4n, cw, dy, dz_out, workspace,
+                     chunks);
+  if (check_launch("bn_eval_bwd")) return 1;
+  if (!dgamma && !dbeta) return 0;
+  hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(1024), 0, st, workspace, groups * chunks, c, dgamma, dbeta,
+                     accumulate);
+  return check_launch("bn_eval_bwd_finalize");
+}
+
+int mvg_bn_relu_maxpool_eval_bwd(const float *g_pooled, const uint8_t *argmax, const float *y, const float *scale, const float *shift,
+                                 const float *gamma, const float *running_mean, const float *running_var, float eps, int groups,
+                                 int n_per_group, int h, int w, int c, int ho, int wo, float *dy, float *dgamma, float *dbeta,
+                                 int accumulate, float *workspace, void *stream) {
+  MVG_REQUIRE(g_pooled && argmax && y && scale && shift && gamma && running_mean && running_var && dy && workspace,
+              "bn_relu_maxpool_eval_bwd: every pointer but dgamma / dbeta is required");
+  MVG_REQUIRE(groups > 0 && groups < 65536 && n_per_group > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && 256 % (c / 4) == 0,
+              "bn_relu_maxpool_eval_bwd: bad sizes (c/4 must divide 256, c=%d)", c);
+  MVG_REQUIRE(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1, "bn_relu_maxpool_eval_bwd: bad output size");
+  hipStream_t st = (hipStream_t)stream;
+  const int c4n = c / 4;
+  const long long items = (long long)n_per_group * ((h + 1) / 2) * ((w + 1) / 2) * c4n;
+  long long chunks = (items + 255) / 256;
+  if (chunks > eval_pool_chunks(groups)) chunks = eval_pool_chunks(groups);
+  ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0,
+               4.0 * groups * ((double)n_per_group * h * w * c * 2 + (double)n_per_group * ho * wo * c * 1.25));
+  hipLaunchKernelGGL(bn_pool_eval_bwd_kernel, dim3((int)chunks, groups), dim3(256), 0, st, g_pooled, (const uchar4 *)argmax, y, scale,
+                     shift, gamma, running_mean, running_var, eps, n_per_group, h, w, ho, wo, c4n, dy, workspace);
+  if (check_launch("bn_relu_maxpool_eval_bwd")) return 1;
+  if (!dgamma && !dbeta) return 0;
+  hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(1024), 0, st, workspace, groups * (int)chunks, c, dgamma,
+                     dbeta, accumulate);
+  return check_launch("bn_eval_bwd_finalize");
+}
 
 }  // extern "C"

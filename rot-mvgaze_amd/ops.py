@@ -516,6 +516,30 @@ def bn_bwd_apply(g, act, y, mean, invstd, gamma, s1, s2, groups, rows_per_group,
                                  groups, rows_per_group, c, _p(dy), _p(dz_out), _s()), "bn_bwd_apply")
 
 
+def bn_eval_bwd(g, y, gamma, running_mean, running_var, eps, groups, rows_per_group, c, dy, dgamma, dbeta, accumulate,
+                act=None, relu_bits=None, relu_affine=None, dz_out=None):
+    """Eval-mode BatchNorm backward (running statistics) in one pass: dy = gamma * invstd_r * dz, dgamma / dbeta (+)= the
+    sums over every group.  The ReLU mask from ONE of act, relu_bits, relu_affine = (scale, shift) of bn_eval_affine, or
+    none.  dy may be g itself; dz_out (may be g, not dy) receives the masked gradient."""
+    n = lib().mvg_bn_eval_bwd_workspace_floats(groups, rows_per_group, c)
+    ws = torch.empty(n, dtype=torch.float32, device=g.device)
+    rs, rh = relu_affine if relu_affine is not None else (None, None)
+    check(lib().mvg_bn_eval_bwd(_p(_f32c(g)), _p(act), _p(relu_bits), _p(_f32c(y)), _p(rs), _p(rh), _p(gamma), _p(running_mean),
+                                _p(running_var), eps, groups, rows_per_group, c, _p(_f32c(dy)), _p(dz_out), _p(dgamma), _p(dbeta),
+                                int(accumulate), _p(ws), _s()), "bn_eval_bwd")
+
+
+def bn_relu_maxpool_eval_bwd(g_pooled, argmax, y, scale, shift, gamma, running_mean, running_var, eps, groups, n_per_group, h, w,
+                             c, ho, wo, dy, dgamma, dbeta, accumulate):
+    """The stem tail in eval mode: max-pool backward + ReLU + BatchNorm on the running statistics, dy written once."""
+    n = lib().mvg_bn_eval_bwd_workspace_floats(groups, n_per_group * h * w, c)
+    ws = torch.empty(n, dtype=torch.float32, device=y.device)
+    check(lib().mvg_bn_relu_maxpool_eval_bwd(_p(_f32c(g_pooled)), _p(argmax), _p(_f32c(y)), _p(scale), _p(shift), _p(gamma),
+                                             _p(running_mean), _p(running_var), eps, groups, n_per_group, h, w, c, ho, wo,
+                                             _p(_f32c(dy)), _p(dgamma), _p(dbeta), int(accumulate), _p(ws), _s()),
+          "bn_relu_maxpool_eval_bwd")
+
+
 # ---------------------------------------------------------------- pooling / layout
 def maxpool_fwd(x, y, argmax, n, h, w, c, ho, wo):
     check(lib().mvg_maxpool3x3s2_fwd(_p(x), _p(y), _p(argmax), n, h, w, c, ho, wo, _s()), "maxpool_fwd")
