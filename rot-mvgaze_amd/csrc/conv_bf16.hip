@@ -641,24 +641,6 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(WgradParams p) {
     }
 }
 
-// A stride-2 parity class without taps: dx = addend (or zero) on that class's pixels (16-byte vectors of 8 bf16).
-__global__ __launch_bounds__(256) void dgrad_empty_class_bf16_kernel(u32x4 *__restrict__ dx, const u32x4 *__restrict__ addend,
-                                                                     long long n, int sub_h, int sub_w, int full_h, int full_w,
-                                                                     int c8, int py, int px) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int cc = (int)(i % c8);
-    long long t = i / c8;
-    const int x2 = (int)(t % sub_w);
-    t /= sub_w;
-    const int y2 = (int)(t % sub_h);
-    const long long img = t / sub_h;
-    const long long off = ((img * full_h + 2 * y2 + py) * full_w + 2 * x2 + px) * c8 + cc;
-    u32x4 z = {0u, 0u, 0u, 0u};
-    dx[off] = addend ? addend[off] : z;
-  }
-}
-
 // The stem's folded row-window operand (mvg_stem_fprop_bf16): window m of an image row holds image columns 4 m - 4 ..
 // 4 m + 11 x 4 channels (3 real) in bf16 - 64 values, the K-step of the LDS-DMA kernel - straight from the NCHW fp32
 // input.  One thread per 8-value chunk = two columns.
@@ -790,7 +772,6 @@ int mvg_cast_weights_bf16(const mvg_conv_desc *d, const float *w, int cin_src, v
 static int fprop_bf16_impl(const mvg_conv_desc *d, const void *x, const void *wgt, void *y, const float *bias, int relu,
                            float *stats, void *stream, bool f32io, int stride_w = -1, int pad_w = -1) {
   if (stride_w < 0 && validate_bf16(d)) return 2;
-  const long long EA = f32io ? 4 : 2;
   IgemmParams p;
   memset(&p, 0, sizeof(p));
   p.a = (const float *)x;
@@ -799,47 +780,15 @@ static int fprop_bf16_impl(const mvg_conv_desc *d, const void *x, const void *wg
   p.bias = bias;
   p.relu = relu;
   p.stats = stats;
-  p.groups = d->groups;
-  p.out_h = d->ho;
-  p.out_w = d->wo;
-  p.src_h = d->h;
-  p.src_w = d->w;
-  p.src_c = d->cin;
-  p.src_c_shift = (d->r * d->s > 1) ? ilog2_exact(d->cin) : 0;
-  p.ncols = d->cout;
-  p.r = d->r;
-  p.s = d->s;
-  p.rs = d->r * d->s;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.stride_w = stride_w >= 0 ? stride_w : d->stride;
-  p.pad_w = stride_w >= 0 ? pad_w : d->pad;
   p.stats_fold = stride_w >= 0 ? 1 : 0;
-  p.ktotal = d->r * d->s * d->cin;
-  p.b_row_len = p.ktotal;
-  p.cin = d->cin;
-  p.rows_per_group = (long long)d->n * d->ho * d->wo;
-  p.src_img_stride = (long long)d->h * d->w * d->cin;
-  p.imgs_per_group = d->n;
-  p.ntaps = d->r * d->s;
-  p.tap_ns = d->s;
-  p.tap_step = 1;
-  p.cls_step = 1;
-  p.a_group_bytes = EA * d->n * p.src_img_stride;
-  p.b_bytes = 2ll * d->cout * p.ktotal;
-  MVG_REQUIRE(p.a_group_bytes < 0x7FFFFFF0ll && p.b_bytes < 0x7FFFFFF0ll, "bf16 conv: a group / the weights exceed 2 GiB");
+  if (fprop_geometry(p, d, f32io ? 4 : 2, 2, "bf16 conv", stride_w, pad_w)) return 2;
   MVG_REQUIRE(p.rows_per_group * (long long)d->cout < (1ll << 31), "bf16 conv: a group of the output exceeds 2^31 elements");
-  p.tap_ns_div = make_fastdiv((unsigned)p.tap_ns);
-  p.ohw_div = make_fastdiv((unsigned)(p.out_h * p.out_w));
-  p.ow_div = make_fastdiv((unsigned)p.out_w);
   const double acin = d->cin == 8 && d->r == 7 ? 3.0 : (double)d->cin;       // the stem's channels 3..7 are zero padding
   const double flops = 2.0 * d->groups * (double)p.rows_per_group * d->cout * d->r * d->s * acin * (stride_w >= 0 ? 147.0 / 448.0 : 1.0);
   const double bytes = 2.0 * (d->groups * (double)d->n * d->h * d->w * acin + (double)d->cout * d->r * d->s * acin +
                               d->groups * (double)p.rows_per_group * d->cout);
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_FPROP : MVG_K_CONV_FPROP, (hipStream_t)stream, flops, bytes);
-  p.ncls = 1;
-  class_from_params(p.cls[0], p);
   return launch_igemm_bf16<false>(p, (hipStream_t)stream, f32io);
 }
 
@@ -858,7 +807,6 @@ struct Bf16BnFuse {        // fused BatchNorm-backward reduce of the unit whose 
 static int dgrad_bf16_impl(const mvg_conv_desc *d, const void *dy, const void *wgt_crsk, void *dx, const void *mask,
                            const void *addend, void *stream, bool f32io, const Bf16BnFuse *bnf = nullptr) {
   if (validate_bf16(d)) return 2;
-  const long long EA = f32io ? 4 : 2;
   MVG_REQUIRE(!f32io || d->stride == 1, "bf16 dgrad with fp32 operands: stride 1 only");
   IgemmParams p;
   memset(&p, 0, sizeof(p));
@@ -877,98 +825,16 @@ static int dgrad_bf16_impl(const mvg_conv_desc *d, const void *dy, const void *w
     p.bn_part = bnf->part;
     p.bn_part_rows = 2;
   }
-  p.groups = d->groups;
-  p.out_h = d->h;
-  p.out_w = d->w;
-  p.src_h = d->ho;
-  p.src_w = d->wo;
-  p.src_c = d->cout;
-  p.src_c_shift = (d->r * d->s > 1) ? ilog2_exact(d->cout) : 0;
-  p.ncols = d->cin;
-  p.r = d->r;
-  p.s = d->s;
-  p.rs = d->r * d->s;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.ktotal = d->r * d->s * d->cout;
-  p.b_row_len = d->r * d->s * d->cout;
-  p.cin = d->cin;
-  p.src_img_stride = (long long)d->ho * d->wo * d->cout;
-  p.imgs_per_group = d->n;
-  p.full_h = d->h;
-  p.full_w = d->w;
-  p.a_group_bytes = EA * d->n * p.src_img_stride;
-  p.b_bytes = 2ll * d->cin * p.b_row_len;
-  MVG_REQUIRE(p.a_group_bytes < 0x7FFFFFF0ll && p.b_bytes < 0x7FFFFFF0ll, "bf16 conv: a group / the weights exceed 2 GiB");
+  if (dgrad_geometry(p, d, f32io ? 4 : 2, 2, "bf16 conv")) return 2;
   MVG_REQUIRE((long long)d->n * d->h * d->w * d->cin < (1ll << 31), "bf16 conv: a group of dx exceeds 2^31 elements");
   const double flops = 2.0 * d->groups * (double)d->n * d->ho * d->wo * d->cout * d->r * d->s * d->cin;
   const double bytes = 2.0 * (d->groups * (double)d->n * d->ho * d->wo * d->cout + (double)d->cout * d->r * d->s * d->cin) +
                        (bnf ? 4.125 : 2.0) * d->groups * (double)d->n * d->h * d->w * d->cin;      // (fused reduce: + y and the mask bits)
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_DGRAD : MVG_K_CONV_DGRAD, (hipStream_t)stream, flops, bytes);
-  const int step = d->stride;
-  IgemmParams m = p;
-  m.ncls = 0;
-  int cls_k[4];
-  for (int py = 0; py < step; ++py)
-    for (int px = 0; px < step; ++px) {
-      const int sub_h = (d->h - py + step - 1) / step, sub_w = (d->w - px + step - 1) / step;
-      if (sub_h <= 0 || sub_w <= 0) continue;
-      const int r0 = (py + d->pad) % step, s0 = (px + d->pad) % step;
-      const int nr = r0 < d->r ? (d->r - r0 + step - 1) / step : 0;
-      const int ns = s0 < d->s ? (d->s - s0 + step - 1) / step : 0;
-      IgemmParams q = p;
-      q.out_h = sub_h;
-      q.out_w = sub_w;
-      q.rows_per_group = (long long)d->n * sub_h * sub_w;
-      q.ntaps = nr * ns;
-      q.tap_ns = ns > 0 ? ns : 1;
-      q.tap_ns_div = make_fastdiv((unsigned)q.tap_ns);
-      q.ohw_div = make_fastdiv((unsigned)(sub_h * sub_w));
-      q.ow_div = make_fastdiv((unsigned)sub_w);
-      q.tap_r0 = r0;
-      q.tap_s0 = s0;
-      q.tap_step = step;
-      q.ktotal = nr * ns * d->cout;
-      q.cls_step = step;
-      q.cls_py = py;
-      q.cls_px = px;
-      q.cls_cy = (py + d->pad - r0) / step;
-      q.cls_cx = (px + d->pad - s0) / step;
-      if (q.ntaps == 0 && !bnf) {
-        if (addend != dx || !addend) {                 // nothing to do when the caller accumulates in place
-          const long long n = (long long)d->groups * d->n * sub_h * sub_w * (d->cin / 8);
-          long long blocks = (n + 255) / 256;
-          if (blocks > 4096) blocks = 4096;
-          hipLaunchKernelGGL(dgrad_empty_class_bf16_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (u32x4 *)dx,
-                             (const u32x4 *)addend, n, sub_h, sub_w, d->h, d->w, d->cin / 8, py, px);
-          if (check_launch("dgrad_bf16(empty class)")) return 1;
-        }
-        continue;
-      }
-      if (m.ncls == 0) {
-        m.tap_step = step;
-        m.cls_step = step;
-        m.rows_per_group = q.rows_per_group;
-        m.ktotal = q.ktotal;
-        m.out_h = q.out_h;
-        m.out_w = q.out_w;
-      }
-      cls_k[m.ncls] = q.ktotal;
-      class_from_params(m.cls[m.ncls++], q);
-    }
-  if (m.ncls == 0) return 0;
-  for (int i = 1; i < m.ncls; ++i)                       // longest class first
-    for (int j = i; j > 0 && cls_k[j] > cls_k[j - 1]; --j) {
-      const IgemmClass tc = m.cls[j];
-      m.cls[j] = m.cls[j - 1];
-      m.cls[j - 1] = tc;
-      const int tk = cls_k[j];
-      cls_k[j] = cls_k[j - 1];
-      cls_k[j - 1] = tk;
-    }
-  m.no_remap = m.ncls > 1;
-  return launch_igemm_bf16<true>(m, (hipStream_t)stream, f32io);
+  if (int e = dgrad_classes(p, d, bnf != nullptr, f32io ? 4 : 2, dx, addend, (hipStream_t)stream)) return e;
+  if (p.ncls == 0) return 0;
+  return launch_igemm_bf16<true>(p, (hipStream_t)stream, f32io);
 }
 
 int mvg_conv_dgrad_bf16(const mvg_conv_desc *d, const void *dy, const void *wgt_crsk, void *dx, const void *mask,
@@ -1063,61 +929,24 @@ int mvg_conv_wgrad_splits_bf16(const mvg_conv_desc *d) {
   if (validate_bf16(d)) return -1;
   int bm, bn;
   wgrad_bf16_tile(d, bm, bn);
-  const int ncols = d->r * d->s * d->cin;
-  const long long tiles = (long long)ceil_div(d->cout, bm) * ceil_div(ncols, bn);
-  const long long pixels = (long long)d->groups * d->n * d->ho * d->wo;
-  const int cus = compute_cus();
-  long long want = (2LL * cus) / tiles;                    // one resident round at two workgroups per CU
-  long long maxs = pixels / 512;                           // at least 512 pixels (8 K-steps) per split
-  if (maxs < 1) maxs = 1;
-  if (want > maxs) want = maxs;
-  if (want < 1) want = 1;
-  if (want > 1024) want = 1024;
-  return (int)want;
+  const long long tiles = (long long)ceil_div(d->cout, bm) * ceil_div(d->r * d->s * d->cin, bn);
+  // one resident round at two workgroups per CU, at least 512 pixels (8 K-steps) per split
+  return wgrad_split_count(tiles, (long long)d->groups * d->n * d->ho * d->wo, 2, 512);
 }
 
 static int wgrad_bf16_impl(const mvg_conv_desc *d, const void *x, const void *dy, float *dw, float *db, float *workspace,
                            int splits, int accumulate, void *stream, bool f32in, int stride_w = -1, int pad_w = -1, bool slabs_only = false) {
   if (stride_w < 0 && validate_bf16(d)) return 2;
-  const long long EB = f32in ? 4 : 2;
   MVG_REQUIRE(!db || f32in, "wgrad_bf16: the bias gradient rides on the fp32-operand form only");
-  MVG_REQUIRE(splits >= 1, "wgrad_bf16: splits < 1");
-  MVG_REQUIRE(splits == 1 || workspace != nullptr, "wgrad_bf16: workspace required for splits > 1");
   WgradParams p;
   memset(&p, 0, sizeof(p));
   p.x = (const float *)x;
   p.dy = (const float *)dy;
-  p.h = d->h;
-  p.w = d->w;
-  p.cin = d->cin;
-  p.cout = d->cout;
-  p.r = d->r;
-  p.s = d->s;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.stride_w = stride_w >= 0 ? stride_w : d->stride;
-  p.pad_w = stride_w >= 0 ? pad_w : d->pad;
-  p.ho = d->ho;
-  p.wo = d->wo;
-  p.ncols = d->r * d->s * d->cin;
-  p.pixels = (long long)d->groups * d->n * d->ho * d->wo;
-  p.pixels_per_split = ((p.pixels + splits - 1) / splits + 63) / 64 * 64;
-  p.x_bytes = EB * d->groups * d->n * d->h * d->w * d->cin;
-  p.ohw_div = make_fastdiv((unsigned)(d->ho * d->wo));
-  p.wo_div = make_fastdiv((unsigned)d->wo);
-  p.cin_div = make_fastdiv((unsigned)d->cin);
-  p.s_div = make_fastdiv((unsigned)d->s);
-  MVG_REQUIRE(p.pixels_per_split * d->cout * EB < 0x7FFFFFF0ll, "wgrad_bf16: split too large for 32-bit offsets");
-  MVG_REQUIRE(EB * (p.pixels_per_split / (d->ho * d->wo) + 2) * d->h * d->w * d->cin < 0x7FFFFFF0ll,
-              "wgrad_bf16: split too large for 32-bit offsets");
+  if (wgrad_geometry(p, d, f32in ? 4 : 2, 64, dw, db, workspace, splits, accumulate, "wgrad_bf16", stride_w, pad_w)) return 2;
   int bm, bn;
   wgrad_bf16_tile(d, bm, bn);
   p.mtiles = ceil_div(d->cout, bm);
   p.ntiles = ceil_div(p.ncols, bn);
-  p.out = splits == 1 ? dw : workspace;
-  p.accumulate = (splits == 1) ? accumulate : 0;
-  float *db_slab = workspace ? workspace + (size_t)splits * d->cout * p.ncols : nullptr;
-  p.db = db ? (splits == 1 ? db : db_slab) : nullptr;
   hipStream_t st = (hipStream_t)stream;
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   {
@@ -1142,24 +971,7 @@ static int wgrad_bf16_impl(const mvg_conv_desc *d, const void *x, const void *dy
 #undef MVG_WGRAD_BF16
     if (check_launch("conv_wgrad_bf16")) return 1;
   }
-  if (splits > 1 && !slabs_only) {
-    const long long n = (long long)d->cout * p.ncols;
-    MVG_REQUIRE(n % 4 == 0, "wgrad_bf16: weight elements %% 4 != 0");
-    ProfScope ps(MVG_K_WGRAD_REDUCE, st, 0.0, 4.0 * n * (splits + 1));
-    const int lanes = splits >= 32 ? 16 : (splits >= 8 ? 4 : 1);
-    const long long blocks = (n / 4 + 256 / lanes - 1) / (256 / lanes);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, workspace, dw, n / 4, splits, accumulate,
-                       lanes);
-    if (check_launch("wgrad_reduce")) return 1;
-    if (db) {
-      const long long nb = d->cout;
-      const long long bblocks = (nb / 4 + 256 / lanes - 1) / (256 / lanes);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)bblocks), dim3(256), 0, st, db_slab, db, nb / 4, splits, accumulate,
-                         lanes);
-      if (check_launch("wgrad_reduce(bias)")) return 1;
-    }
-  }
-  return 0;
+  return splits > 1 && !slabs_only ? wgrad_reduce_slabs(p, workspace, dw, db, splits, accumulate, st, "wgrad_bf16") : 0;
 }
 
 int mvg_conv_wgrad_bf16(const mvg_conv_desc *d, const void *x, const void *dy, float *dw, float *workspace, int splits,
@@ -1176,13 +988,7 @@ int mvg_stem_wgrad_splits_bf16(const mvg_conv_desc *d) {
   mvg_conv_desc rw;
   if (stem_fold_desc(d, &rw)) return -1;
   const long long tiles = (long long)ceil_div(rw.cout, 128) * ceil_div(7 * 64, 128);
-  const long long pixels = (long long)rw.groups * rw.n * rw.ho * rw.wo;
-  long long want = (2LL * compute_cus()) / tiles, maxs = pixels / 512;
-  if (maxs < 1) maxs = 1;
-  if (want > maxs) want = maxs;
-  if (want < 1) want = 1;
-  if (want > 1024) want = 1024;
-  return (int)want;
+  return wgrad_split_count(tiles, (long long)rw.groups * rw.n * rw.ho * rw.wo, 2, 512);
 }
 
 int mvg_stem_wgrad_bf16(const mvg_conv_desc *d, const void *xw, const void *dy, float *dw_fold, float *workspace, int splits,

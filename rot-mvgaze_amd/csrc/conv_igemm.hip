@@ -995,24 +995,6 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
     }
 }
 
-// A stride-2 parity class without taps (e.g. three of the four classes of a 1x1 stride-2 conv):
-// dx = 0 there, plus the addend.
-__global__ __launch_bounds__(256) void dgrad_empty_class_kernel(float4 *__restrict__ dx, const float4 *__restrict__ addend,
-                                                                long long n, int sub_h, int sub_w, int full_h, int full_w,
-                                                                int c4, int py, int px) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int cc = (int)(i % c4);
-    long long t = i / c4;
-    const int x2 = (int)(t % sub_w);
-    t /= sub_w;
-    const int y2 = (int)(t % sub_h);
-    const long long img = t / sub_h;
-    const long long off = ((img * full_h + 2 * y2 + py) * full_w + 2 * x2 + px) * c4 + cc;
-    dx[off] = addend ? addend[off] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -1268,43 +1250,13 @@ static int fprop_impl(const mvg_conv_desc *d, const float *x, const float *wgt, 
   p.addend = residual;
   p.relu = relu;
   p.stats = stats;
-  p.groups = d->groups;
-  p.out_h = d->ho;
-  p.out_w = d->wo;
-  p.src_h = d->h;
-  p.src_w = d->w;
-  p.src_c = d->cin;
-  p.src_c_shift = (d->r * d->s > 1) ? ilog2_exact(d->cin) : 0;
-  p.ncols = d->cout;
-  p.r = d->r;
-  p.s = d->s;
-  p.rs = d->r * d->s;
-  p.stride = d->stride;
-  p.stride_shift = d->stride == 2 ? 1 : 0;
-  p.pad = d->pad;
-  p.ktotal = d->r * d->s * d->cin;
-  p.cin = d->cin;
-  p.rows_per_group = (long long)d->n * d->ho * d->wo;
-  p.src_img_stride = (long long)d->h * d->w * d->cin;
-  p.imgs_per_group = d->n;
-  p.ntaps = d->r * d->s;
-  p.tap_ns = d->s;
-  p.tap_step = 1;
-  p.cls_step = 1;
-  p.a_group_bytes = 4ll * d->n * p.src_img_stride;
-  p.b_bytes = 4ll * d->cout * p.ktotal;
-  MVG_REQUIRE(p.a_group_bytes < 0x7FFFFFF0ll && p.b_bytes < 0x7FFFFFF0ll, "conv: a group / the weights exceed 2 GiB");
-  p.tap_ns_div = make_fastdiv((unsigned)p.tap_ns);
-  p.ohw_div = make_fastdiv((unsigned)(p.out_h * p.out_w));
-  p.ow_div = make_fastdiv((unsigned)p.out_w);
+  if (fprop_geometry(p, d, 4, 4, "conv")) return 2;
   const TileChoice t = choose_tile(p.rows_per_group, d->groups, d->cout, p.ktotal, false);
   const double flops = 2.0 * d->groups * (double)p.rows_per_group * d->cout * d->r * d->s * alg_cin(d);
   const double bytes = 4.0 * (d->groups * (double)d->n * d->h * d->w * alg_cin(d) + (double)d->cout * d->r * d->s * alg_cin(d) +
                               d->groups * (double)p.rows_per_group * d->cout);
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_FPROP : MVG_K_CONV_FPROP, (hipStream_t)stream, flops, bytes);
-  p.ncls = 1;
-  class_from_params(p.cls[0], p);
   if (!stats && plan_splitk(p, t, ws ? ws_floats : 0, false) > 1) {
     p.slab = ws;
     if (launch_igemm<false>(p, t, (hipStream_t)stream)) return 1;
@@ -1324,112 +1276,28 @@ static int dgrad_impl(const mvg_conv_desc *d, const float *dy, const float *wgt,
   p.out = dx;
   p.mask = mask;
   p.addend = addend;
-  p.groups = d->groups;
-  p.out_h = d->h;
-  p.out_w = d->w;
-  p.src_h = d->ho;
-  p.src_w = d->wo;
-  p.src_c = d->cout;
-  p.src_c_shift = (d->r * d->s > 1) ? ilog2_exact(d->cout) : 0;
-  p.ncols = d->cin;
-  p.r = d->r;
-  p.s = d->s;
-  p.rs = d->r * d->s;
-  p.stride = d->stride;
-  p.stride_shift = d->stride == 2 ? 1 : 0;
-  p.pad = d->pad;
-  p.ktotal = d->r * d->s * d->cout;
-  p.cin = d->cin;
-  p.src_img_stride = (long long)d->ho * d->wo * d->cout;
-  p.imgs_per_group = d->n;
-  p.full_h = d->h;
-  p.full_w = d->w;
-  p.a_group_bytes = 4ll * d->n * p.src_img_stride;
-  p.b_bytes = 4ll * d->cout * d->r * d->s * d->cin;
-  MVG_REQUIRE(p.a_group_bytes < 0x7FFFFFF0ll && p.b_bytes < 0x7FFFFFF0ll, "conv: a group / the weights exceed 2 GiB");
+  if (dgrad_geometry(p, d, 4, 4, "conv")) return 2;
   // algorithmic flops: the transposed conv touches each (output pixel, tap) pair of the fprop once
   const double flops = 2.0 * d->groups * (double)d->n * d->ho * d->wo * d->cout * d->r * d->s * alg_cin(d);
   const double bytes = 4.0 * (d->groups * (double)d->n * d->ho * d->wo * d->cout + (double)d->cout * d->r * d->s * alg_cin(d) +
                               d->groups * (double)d->n * d->h * d->w * alg_cin(d));
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_DGRAD : MVG_K_CONV_DGRAD, (hipStream_t)stream, flops, bytes);
-  const int step = d->stride;
-  IgemmParams m = p;                   // the merged fp32 launch: every parity class in one grid
-  m.ncls = 0;
+  if (int e = dgrad_classes(p, d, false, 4, dx, addend, (hipStream_t)stream)) return e;
+  if (p.ncls == 0) return 0;
   long long cls_rows[4];
   int cls_k[4];
-  for (int py = 0; py < step; ++py)
-    for (int px = 0; px < step; ++px) {
-      const int sub_h = (d->h - py + step - 1) / step, sub_w = (d->w - px + step - 1) / step;
-      if (sub_h <= 0 || sub_w <= 0) continue;
-      const int r0 = (py + d->pad) % step, s0 = (px + d->pad) % step;
-      const int nr = r0 < d->r ? (d->r - r0 + step - 1) / step : 0;
-      const int ns = s0 < d->s ? (d->s - s0 + step - 1) / step : 0;
-      IgemmParams q = p;
-      q.out_h = sub_h;
-      q.out_w = sub_w;
-      q.rows_per_group = (long long)d->n * sub_h * sub_w;
-      q.ntaps = nr * ns;
-      q.tap_ns = ns > 0 ? ns : 1;
-      q.tap_ns_div = make_fastdiv((unsigned)q.tap_ns);
-      q.ohw_div = make_fastdiv((unsigned)(sub_h * sub_w));
-      q.ow_div = make_fastdiv((unsigned)sub_w);
-      q.tap_r0 = r0;
-      q.tap_s0 = s0;
-      q.tap_step = step;
-      q.ktotal = nr * ns * d->cout;
-      q.cls_step = step;
-      q.cls_py = py;
-      q.cls_px = px;
-      q.cls_cy = (py + d->pad - r0) / step;
-      q.cls_cx = (px + d->pad - s0) / step;
-      if (q.ntaps == 0) {
-        // no tap reaches this class: dx = addend (nothing to do when the caller accumulates in place)
-        if (addend != dx || !addend) {
-          MVG_REQUIRE(d->cin % 4 == 0, "dgrad: cin %% 4 != 0");
-          const long long n = (long long)d->groups * d->n * sub_h * sub_w * (d->cin / 4);
-          long long blocks = (n + 255) / 256;
-          if (blocks > 4096) blocks = 4096;
-          hipLaunchKernelGGL(dgrad_empty_class_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float4 *)dx,
-                             (const float4 *)addend, n, sub_h, sub_w, d->h, d->w, d->cin / 4, py, px);
-          if (check_launch("dgrad(empty class)")) return 1;
-        }
-        continue;
-      }
-      if (m.ncls == 0) {               // launch-wide fields that depend on the stride
-        m.tap_step = step;
-        m.cls_step = step;
-        m.rows_per_group = q.rows_per_group;
-        m.ktotal = q.ktotal;
-        m.out_h = q.out_h;
-        m.out_w = q.out_w;
-      }
-      cls_rows[m.ncls] = q.rows_per_group;
-      cls_k[m.ncls] = q.ktotal;
-      class_from_params(m.cls[m.ncls++], q);
-    }
-  if (m.ncls == 0) return 0;
-  // longest class first: with one tile per workgroup the short tiles then fill the tail
-  for (int i = 1; i < m.ncls; ++i)
-    for (int j = i; j > 0 && cls_k[j] > cls_k[j - 1]; --j) {
-      const IgemmClass tc = m.cls[j];
-      m.cls[j] = m.cls[j - 1];
-      m.cls[j - 1] = tc;
-      const long long tr = cls_rows[j];
-      cls_rows[j] = cls_rows[j - 1];
-      cls_rows[j - 1] = tr;
-      const int tk = cls_k[j];
-      cls_k[j] = cls_k[j - 1];
-      cls_k[j - 1] = tk;
-    }
-  m.no_remap = m.ncls > 1;
-  const TileChoice t = choose_tile_multi(cls_rows, cls_k, m.ncls, d->groups, d->cin, true);
-  if (m.ncls == 1 && step == 1 && plan_splitk(m, t, ws ? ws_floats : 0, true) > 1) {
-    m.slab = ws;
-    if (launch_igemm<true>(m, t, (hipStream_t)stream)) return 1;
-    return launch_splitk_reduce(m, (hipStream_t)stream);
+  for (int i = 0; i < p.ncls; ++i) {
+    cls_rows[i] = p.cls[i].rows_per_group;
+    cls_k[i] = p.cls[i].ktotal;
   }
-  return launch_igemm<true>(m, t, (hipStream_t)stream);
+  const TileChoice t = choose_tile_multi(cls_rows, cls_k, p.ncls, d->groups, d->cin, true);
+  if (p.ncls == 1 && d->stride == 1 && plan_splitk(p, t, ws ? ws_floats : 0, true) > 1) {
+    p.slab = ws;
+    if (launch_igemm<true>(p, t, (hipStream_t)stream)) return 1;
+    return launch_splitk_reduce(p, (hipStream_t)stream);
+  }
+  return launch_igemm<true>(p, t, (hipStream_t)stream);
 }
 
 static mvg_conv_desc linear_desc(int rows, int fin, int fout) {
@@ -1512,59 +1380,23 @@ extern "C" {
 int mvg_conv_wgrad_splits(const mvg_conv_desc *d) {
   if (validate(d)) return -1;
   const TileChoice t = wgrad_tile(d);
-  const int ncols = d->r * d->s * d->cin;
-  const long long tiles = (long long)ceil_div(d->cout, t.bm) * ceil_div(ncols, t.bn);
-  const long long pixels = (long long)d->groups * d->n * d->ho * d->wo;
-  const int cus = compute_cus();
-  // one resident round: tiles x splits <= CUs x workgroups-per-CU (rounding the split count UP puts a
-  // handful of workgroups into a second round that costs as much as the first)
-  int wpc = wgrad_occupancy(t);
-  if (wpc > 4) wpc = 4;
-  long long want = ((long long)wpc * cus) / tiles;
-  long long maxs = pixels / 256;                           // at least 256 pixels (16 K-steps) per split
-  if (maxs < 1) maxs = 1;
-  if (want > maxs) want = maxs;
-  if (want < 1) want = 1;
-  if (want > 1024) want = 1024;
-  return (int)want;
+  const long long tiles = (long long)ceil_div(d->cout, t.bm) * ceil_div(d->r * d->s * d->cin, t.bn);
+  const int wpc = wgrad_occupancy(t);
+  return wgrad_split_count(tiles, (long long)d->groups * d->n * d->ho * d->wo, wpc > 4 ? 4 : wpc, 256);   // 16 K-steps per split
 }
 
 static int wgrad_impl(const mvg_conv_desc *d, const float *x, const float *dy, float *dw, float *db, float *workspace,
                       int splits, int accumulate, void *stream, const RotCat *rc = nullptr) {
   if (validate(d)) return 2;
   MVG_REQUIRE(d->cout % 4 == 0, "wgrad: cout %% 4 != 0 (%d)", d->cout);
-  MVG_REQUIRE(splits >= 1, "wgrad: splits < 1");
-  MVG_REQUIRE(splits == 1 || workspace != nullptr, "wgrad: workspace required for splits > 1");
   WgradParams p;
   memset(&p, 0, sizeof(p));
   p.x = x;
   p.dy = dy;
-  p.h = d->h;
-  p.w = d->w;
-  p.cin = d->cin;
-  p.cout = d->cout;
-  p.r = d->r;
-  p.s = d->s;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.ho = d->ho;
-  p.wo = d->wo;
-  p.ncols = d->r * d->s * d->cin;
-  p.pixels = (long long)d->groups * d->n * d->ho * d->wo;
-  p.pixels_per_split = ((p.pixels + splits - 1) / splits + 15) / 16 * 16;
-  p.x_bytes = 4ll * d->groups * d->n * d->h * d->w * d->cin;
-  p.ohw_div = make_fastdiv((unsigned)(d->ho * d->wo));
-  p.wo_div = make_fastdiv((unsigned)d->wo);
-  p.cin_div = make_fastdiv((unsigned)d->cin);
-  p.s_div = make_fastdiv((unsigned)d->s);
-  MVG_REQUIRE(p.pixels_per_split * d->cout * 4ll < 0x7FFFFFF0ll, "wgrad: split too large for 32-bit offsets");
-  MVG_REQUIRE(4ll * (p.pixels_per_split / (d->ho * d->wo) + 2) * d->h * d->w * d->cin < 0x7FFFFFF0ll,
-              "wgrad: split too large for 32-bit offsets");
+  if (wgrad_geometry(p, d, 4, 16, dw, db, workspace, splits, accumulate, "wgrad")) return 2;
   const TileChoice t = wgrad_tile(d);
   p.mtiles = ceil_div(d->cout, t.bm);
   p.ntiles = ceil_div(p.ncols, t.bn);
-  p.out = splits == 1 ? dw : workspace;
-  p.accumulate = (splits == 1) ? accumulate : 0;
   if (rc) {
     p.rc_feat = rc->feat;
     p.rc_rel = rc->rel;
@@ -1575,8 +1407,6 @@ static int wgrad_impl(const mvg_conv_desc *d, const float *x, const float *dy, f
     p.rc_img_bytes = 4ll * rc->img_rows * rc->cf;
     p.rc_feat_bytes = 4ll * rc->feat_rows * 3 * rc->nvec;
   }
-  float *db_slab = workspace ? workspace + (size_t)splits * d->cout * p.ncols : nullptr;     // after the dw slabs
-  p.db = db ? (splits == 1 ? db : db_slab) : nullptr;
   hipStream_t st = (hipStream_t)stream;
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   {
@@ -1607,24 +1437,7 @@ static int wgrad_impl(const mvg_conv_desc *d, const float *x, const float *dy, f
 #undef MVG_WGRAD_LAUNCH
     if (check_launch("conv_wgrad")) return 1;
   }
-  if (splits > 1) {
-    const long long n = (long long)d->cout * p.ncols;
-    MVG_REQUIRE(n % 4 == 0, "wgrad: weight elements %% 4 != 0");
-    ProfScope ps(MVG_K_WGRAD_REDUCE, st, 0.0, 4.0 * n * (splits + 1));
-    const int lanes = splits >= 32 ? 16 : (splits >= 8 ? 4 : 1);
-    const long long blocks = (n / 4 + 256 / lanes - 1) / (256 / lanes);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, workspace, dw, n / 4, splits, accumulate,
-                       lanes);
-    if (check_launch("wgrad_reduce")) return 1;
-    if (db) {
-      const long long nb = d->cout;
-      const long long bblocks = (nb / 4 + 256 / lanes - 1) / (256 / lanes);
-      hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)bblocks), dim3(256), 0, st, db_slab, db, nb / 4, splits, accumulate,
-                         lanes);
-      if (check_launch("wgrad_reduce(bias)")) return 1;
-    }
-  }
-  return 0;
+  return splits > 1 ? wgrad_reduce_slabs(p, workspace, dw, db, splits, accumulate, st, "wgrad") : 0;
 }
 
 int mvg_conv_wgrad(const mvg_conv_desc *d, const float *x, const float *dy, float *dw, float *workspace, int splits,

@@ -1,5 +1,7 @@
 // Types and helpers shared by the implicit-GEMM translation units (conv_igemm.hip: fp32 MFMA,
-// conv_bf16.hip: bf16 MFMA).  Everything here is static / inline: the library is built without
+// conv_split.hip: split-operand fp16 MFMA, conv_bf16.hip: bf16 MFMA): the kernels' parameter blocks and the host
+// planning every family does alike - descriptor -> launch geometry, backward-data parity classes, weight-gradient
+// pixel splits and their slab reduce.  Everything here is static / inline: the library is built without
 // relocatable device code, so a kernel must be defined in the translation unit that launches it.
 #pragma once
 #include <stdlib.h>
@@ -270,28 +272,238 @@ static int validate(const mvg_conv_desc *d) {
   return parts;
 }
 
-// the class view of the top-level fields (single-class launches)
-static void class_from_params(IgemmClass &c, const IgemmParams &p) {
+// One class of a launch: rows are the n images' out_h x out_w pixels, K is ntaps taps (tap_ns per filter row, the first
+// at (tap_r0, tap_s0)) x src_c channels.  Tile and unit offsets are the launcher's.
+static IgemmClass make_class(int n, int out_h, int out_w, int ntaps, int tap_ns, int tap_r0, int tap_s0, int src_c) {
+  IgemmClass c;
   memset(&c, 0, sizeof(c));
-  c.out_h = p.out_h;
-  c.out_w = p.out_w;
-  c.ntaps = p.ntaps;
-  c.tap_ns = p.tap_ns;
-  c.tap_r0 = p.tap_r0;
-  c.tap_s0 = p.tap_s0;
-  c.ktotal = p.ktotal;
-  c.cls_py = p.cls_py;
-  c.cls_px = p.cls_px;
-  c.cls_cy = p.cls_cy;
-  c.cls_cx = p.cls_cx;
-  c.mtiles_per_group = p.mtiles_per_group;
-  c.rows_per_group = p.rows_per_group;
-  c.tap_ns_div = p.tap_ns_div;
-  c.ohw_div = p.ohw_div;
-  c.ow_div = p.ow_div;
-  c.KT = p.ktotal > 0 ? ceil_div(p.ktotal, 16) : 1;
-  c.korder = (p.ntaps > 1 && p.src_c % 32 == 0) ? 1 : 0;
-  c.per_div = make_fastdiv((unsigned)(p.ntaps > 0 ? 2 * p.ntaps : 1));      // for BK = 16; launch_igemm resets it
+  c.out_h = out_h;
+  c.out_w = out_w;
+  c.ntaps = ntaps;
+  c.tap_ns = tap_ns;
+  c.tap_r0 = tap_r0;
+  c.tap_s0 = tap_s0;
+  c.ktotal = ntaps * src_c;
+  c.rows_per_group = (long long)n * out_h * out_w;
+  c.tap_ns_div = make_fastdiv((unsigned)tap_ns);
+  c.ohw_div = make_fastdiv((unsigned)(out_h * out_w));
+  c.ow_div = make_fastdiv((unsigned)out_w);
+  c.KT = c.ktotal > 0 ? ceil_div(c.ktotal, 16) : 1;
+  c.korder = (ntaps > 1 && src_c % 32 == 0) ? 1 : 0;
+  c.per_div = make_fastdiv((unsigned)(ntaps > 0 ? 2 * ntaps : 1));      // for BK = 16; the launchers reset it
+  return c;
+}
+
+// The descriptor's fields of a forward launch (one class): a_elem / b_elem bytes per element of the gathered operand and
+// of the weights.  stride_w >= 0: the horizontal stride / padding differ from d->stride / d->pad (the stems' row-window
+// forms, whose descriptors their callers check).  `what` prefixes the error messages.
+static int fprop_geometry(IgemmParams &p, const mvg_conv_desc *d, int a_elem, int b_elem, const char *what, int stride_w = -1,
+                          int pad_w = -1) {
+  p.groups = d->groups;
+  p.out_h = d->ho;
+  p.out_w = d->wo;
+  p.src_h = d->h;
+  p.src_w = d->w;
+  p.src_c = d->cin;
+  p.src_c_shift = (d->r * d->s > 1) ? ilog2_exact(d->cin) : 0;
+  p.ncols = d->cout;
+  p.r = d->r;
+  p.s = d->s;
+  p.rs = d->r * d->s;
+  p.stride = d->stride;
+  p.stride_shift = d->stride == 2 ? 1 : 0;
+  p.pad = d->pad;
+  p.stride_w = stride_w >= 0 ? stride_w : d->stride;
+  p.pad_w = stride_w >= 0 ? pad_w : d->pad;
+  p.ktotal = d->r * d->s * d->cin;
+  p.b_row_len = p.ktotal;
+  p.cin = d->cin;
+  p.rows_per_group = (long long)d->n * d->ho * d->wo;
+  p.src_img_stride = (long long)d->h * d->w * d->cin;
+  p.imgs_per_group = d->n;
+  p.ntaps = d->r * d->s;
+  p.tap_ns = d->s;
+  p.tap_step = 1;
+  p.cls_step = 1;
+  p.a_group_bytes = (long long)a_elem * d->n * p.src_img_stride;
+  p.b_bytes = (long long)b_elem * d->cout * p.ktotal;
+  MVG_REQUIRE(p.a_group_bytes < 0x7FFFFFF0ll && p.b_bytes < 0x7FFFFFF0ll, "%s: a group / the weights exceed 2 GiB", what);
+  p.ncls = 1;
+  p.cls[0] = make_class(d->n, d->ho, d->wo, p.ntaps, d->s, 0, 0, d->cin);
+  p.tap_ns_div = p.cls[0].tap_ns_div;
+  p.ohw_div = p.cls[0].ohw_div;
+  p.ow_div = p.cls[0].ow_div;
+  return 0;
+}
+
+// The descriptor's fields of a backward-data launch (dx = dy (*) w^T: dy gathered, the CRSK weights' rows of r*s*cout),
+// before dgrad_classes splits it: a_elem / b_elem as in fprop_geometry.
+static int dgrad_geometry(IgemmParams &p, const mvg_conv_desc *d, int a_elem, int b_elem, const char *what) {
+  p.groups = d->groups;
+  p.out_h = d->h;
+  p.out_w = d->w;
+  p.src_h = d->ho;
+  p.src_w = d->wo;
+  p.src_c = d->cout;
+  p.src_c_shift = (d->r * d->s > 1) ? ilog2_exact(d->cout) : 0;
+  p.ncols = d->cin;
+  p.r = d->r;
+  p.s = d->s;
+  p.rs = d->r * d->s;
+  p.stride = d->stride;
+  p.stride_shift = d->stride == 2 ? 1 : 0;
+  p.pad = d->pad;
+  p.ktotal = d->r * d->s * d->cout;
+  p.b_row_len = p.ktotal;
+  p.cin = d->cin;
+  p.src_img_stride = (long long)d->ho * d->wo * d->cout;
+  p.imgs_per_group = d->n;
+  p.full_h = d->h;
+  p.full_w = d->w;
+  p.a_group_bytes = (long long)a_elem * d->n * p.src_img_stride;
+  p.b_bytes = (long long)b_elem * d->cin * p.b_row_len;
+  MVG_REQUIRE(p.a_group_bytes < 0x7FFFFFF0ll && p.b_bytes < 0x7FFFFFF0ll, "%s: a group / the weights exceed 2 GiB", what);
+  return 0;
+}
+
+// A stride-2 parity class without taps (e.g. three of the four classes of a 1x1 stride-2 conv): dx = addend, or 0, on
+// that class's pixels; cv 16-byte vectors per pixel.
+static __global__ __launch_bounds__(256) void dgrad_empty_class_kernel(uint4 *__restrict__ dx, const uint4 *__restrict__ addend,
+                                                                       long long n, int sub_h, int sub_w, int full_h, int full_w,
+                                                                       int cv, int py, int px) {
+  const long long stride = (long long)gridDim.x * blockDim.x;
+  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
+    const int cc = (int)(i % cv);
+    long long t = i / cv;
+    const int x2 = (int)(t % sub_w);
+    t /= sub_w;
+    const int y2 = (int)(t % sub_h);
+    const long long img = t / sub_h;
+    const long long off = ((img * full_h + 2 * y2 + py) * full_w + 2 * x2 + px) * cv + cc;
+    dx[off] = addend ? addend[off] : make_uint4(0u, 0u, 0u, 0u);
+  }
+}
+
+// The classes of a backward-data launch (p from dgrad_geometry): one at stride 1; at stride 2 one per output-pixel parity
+// (py, px) - each a dense sub-convolution over its own taps - all merged into p.cls, longest first (with one tile per
+// workgroup the short tiles then fill the tail); the launch-wide fields are the first class's.  A class without taps is a
+// class of its own when keep_tapless (a fused BatchNorm reduce: its tiles run the epilogue only); otherwise
+// dgrad_empty_class_kernel writes dx = addend there now (nothing when the caller accumulates in place; dx_elem bytes per
+// element).  p.ncls == 0 on return: nothing left to launch.
+static int dgrad_classes(IgemmParams &p, const mvg_conv_desc *d, bool keep_tapless, int dx_elem, void *dx, const void *addend,
+                         hipStream_t st) {
+  const int step = d->stride;
+  p.ncls = 0;
+  for (int py = 0; py < step; ++py)
+    for (int px = 0; px < step; ++px) {
+      const int sub_h = (d->h - py + step - 1) / step, sub_w = (d->w - px + step - 1) / step;
+      if (sub_h <= 0 || sub_w <= 0) continue;
+      const int r0 = (py + d->pad) % step, s0 = (px + d->pad) % step;
+      const int nr = r0 < d->r ? (d->r - r0 + step - 1) / step : 0;
+      const int ns = s0 < d->s ? (d->s - s0 + step - 1) / step : 0;
+      if (nr * ns == 0 && !keep_tapless) {
+        if (addend != dx || !addend) {
+          const int cv = d->cin * dx_elem / 16;
+          const long long n = (long long)d->groups * d->n * sub_h * sub_w * cv;
+          long long blocks = (n + 255) / 256;
+          if (blocks > 4096) blocks = 4096;
+          hipLaunchKernelGGL(dgrad_empty_class_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (uint4 *)dx, (const uint4 *)addend, n,
+                             sub_h, sub_w, d->h, d->w, cv, py, px);
+          if (check_launch("dgrad(empty class)")) return 1;
+        }
+        continue;
+      }
+      IgemmClass &c = p.cls[p.ncls++];
+      c = make_class(d->n, sub_h, sub_w, nr * ns, ns > 0 ? ns : 1, r0, s0, d->cout);
+      c.cls_py = py;
+      c.cls_px = px;
+      c.cls_cy = (py + d->pad - r0) / step;
+      c.cls_cx = (px + d->pad - s0) / step;
+      if (p.ncls == 1) {
+        p.tap_step = step;
+        p.cls_step = step;
+        p.rows_per_group = c.rows_per_group;
+        p.ktotal = c.ktotal;
+        p.out_h = sub_h;
+        p.out_w = sub_w;
+      }
+    }
+  for (int i = 1; i < p.ncls; ++i)
+    for (int j = i; j > 0 && p.cls[j].ktotal > p.cls[j - 1].ktotal; --j) {
+      const IgemmClass t = p.cls[j];
+      p.cls[j] = p.cls[j - 1];
+      p.cls[j - 1] = t;
+    }
+  p.no_remap = p.ncls > 1;
+  return 0;
+}
+
+// The descriptor's fields of a weight-gradient launch and where its result goes: elem bytes per element of x and dy, each
+// of the `splits` pixel ranges a multiple of px_align pixels (the kernel's K-step), stride_w / pad_w as in fprop_geometry.
+// With splits > 1 the kernel writes fp32 slabs [splits][cout][r*s*cin] (then [splits][cout] of db) to the workspace and
+// wgrad_reduce_slabs sums them.  The tile is the family's.
+static int wgrad_geometry(WgradParams &p, const mvg_conv_desc *d, int elem, int px_align, float *dw, float *db, float *workspace,
+                          int splits, int accumulate, const char *what, int stride_w = -1, int pad_w = -1) {
+  MVG_REQUIRE(splits >= 1, "%s: splits < 1", what);
+  MVG_REQUIRE(splits == 1 || workspace != nullptr, "%s: workspace required for splits > 1", what);
+  p.h = d->h;
+  p.w = d->w;
+  p.cin = d->cin;
+  p.cout = d->cout;
+  p.r = d->r;
+  p.s = d->s;
+  p.stride = d->stride;
+  p.pad = d->pad;
+  p.stride_w = stride_w >= 0 ? stride_w : d->stride;
+  p.pad_w = stride_w >= 0 ? pad_w : d->pad;
+  p.ho = d->ho;
+  p.wo = d->wo;
+  p.ncols = d->r * d->s * d->cin;
+  p.pixels = (long long)d->groups * d->n * d->ho * d->wo;
+  p.pixels_per_split = ((p.pixels + splits - 1) / splits + px_align - 1) / px_align * px_align;
+  p.x_bytes = (long long)elem * d->groups * d->n * d->h * d->w * d->cin;
+  p.ohw_div = make_fastdiv((unsigned)(d->ho * d->wo));
+  p.wo_div = make_fastdiv((unsigned)d->wo);
+  p.cin_div = make_fastdiv((unsigned)d->cin);
+  p.s_div = make_fastdiv((unsigned)d->s);
+  MVG_REQUIRE(p.pixels_per_split * d->cout * elem < 0x7FFFFFF0ll, "%s: split too large for 32-bit offsets", what);
+  MVG_REQUIRE((long long)elem * (p.pixels_per_split / (d->ho * d->wo) + 2) * d->h * d->w * d->cin < 0x7FFFFFF0ll,
+              "%s: split too large for 32-bit offsets", what);
+  p.out = splits == 1 ? dw : workspace;
+  p.accumulate = (splits == 1) ? accumulate : 0;
+  p.db = db ? (splits == 1 ? db : workspace + (size_t)splits * d->cout * p.ncols) : nullptr;
+  return 0;
+}
+
+// The sums of a pixel-split weight gradient's slabs into dw (and of the bias slabs after them into db, when given).
+static int wgrad_reduce_slabs(const WgradParams &p, float *workspace, float *dw, float *db, int splits, int accumulate, hipStream_t st,
+                              const char *what) {
+  const long long n = (long long)p.cout * p.ncols;
+  MVG_REQUIRE(n % 4 == 0, "%s: weight elements %% 4 != 0", what);
+  ProfScope ps(MVG_K_WGRAD_REDUCE, st, 0.0, 4.0 * n * (splits + 1));
+  const int lanes = splits >= 32 ? 16 : (splits >= 8 ? 4 : 1);
+  const long long blocks = (n / 4 + 256 / lanes - 1) / (256 / lanes);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, workspace, dw, n / 4, splits, accumulate, lanes);
+  if (check_launch("wgrad_reduce")) return 1;
+  if (!db) return 0;
+  const long long nb = p.cout;
+  const long long bblocks = (nb / 4 + 256 / lanes - 1) / (256 / lanes);
+  hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)bblocks), dim3(256), 0, st, workspace + (size_t)splits * n, db, nb / 4, splits,
+                     accumulate, lanes);
+  return check_launch("wgrad_reduce(bias)");
+}
+
+// Pixel splits of a weight gradient over `tiles` output tiles: one resident round of workgroups_per_cu per CU (rounding
+// the split count UP puts a handful of workgroups into a second round that costs as much as the first), at least
+// min_pixels pixels per split, at most 1024 splits.
+static int wgrad_split_count(long long tiles, long long pixels, int workgroups_per_cu, int min_pixels) {
+  long long want = ((long long)workgroups_per_cu * compute_cus()) / tiles;
+  long long maxs = pixels / min_pixels;
+  if (maxs < 1) maxs = 1;
+  if (want > maxs) want = maxs;
+  if (want < 1) want = 1;
+  if (want > 1024) want = 1024;
+  return (int)want;
 }
 
 }  // namespace mvg

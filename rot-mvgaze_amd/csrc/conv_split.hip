@@ -778,23 +778,6 @@ __global__ __launch_bounds__(256) void stem_rowwindow_nchw_kernel(const float *_
   }
 }
 
-// A stride-2 parity class without taps: dx = addend (or zero) on that class's pixels (float4 vectors)
-__global__ __launch_bounds__(256) void dgrad_empty_class_split_kernel(float4 *__restrict__ dx, const float4 *__restrict__ addend,
-                                                                      long long n, int sub_h, int sub_w, int full_h, int full_w,
-                                                                      int c4, int py, int px) {
-  const long long stride = (long long)gridDim.x * blockDim.x;
-  for (long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += stride) {
-    const int cc = (int)(i % c4);
-    long long t = i / c4;
-    const int x2 = (int)(t % sub_w);
-    t /= sub_w;
-    const int y2 = (int)(t % sub_h);
-    const long long img = t / sub_h;
-    const long long off = ((img * full_h + 2 * y2 + py) * full_w + 2 * x2 + px) * c4 + cc;
-    dx[off] = addend ? addend[off] : make_float4(0.f, 0.f, 0.f, 0.f);
-  }
-}
-
 // ------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------
@@ -988,38 +971,8 @@ static int fprop_split_impl(const mvg_conv_desc *d, const void *x_sp, const floa
     p.out_sinv = aff->out_sinv;
     p.bias_absmax = aff->bias_absmax;
   }
-  p.groups = d->groups;
-  p.out_h = d->ho;
-  p.out_w = d->wo;
-  p.src_h = d->h;
-  p.src_w = d->w;
-  p.src_c = d->cin;
-  p.src_c_shift = (d->r * d->s > 1) ? ilog2_exact(d->cin) : 0;
-  p.ncols = d->cout;
-  p.r = d->r;
-  p.s = d->s;
-  p.rs = d->r * d->s;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.stride_w = stride_w >= 0 ? stride_w : d->stride;
-  p.pad_w = stride_w >= 0 ? pad_w : d->pad;
-  p.ktotal = d->r * d->s * d->cin;
-  p.b_row_len = p.ktotal;
-  p.cin = d->cin;
-  p.rows_per_group = (long long)d->n * d->ho * d->wo;
-  p.src_img_stride = (long long)d->h * d->w * d->cin;
-  p.imgs_per_group = d->n;
-  p.ntaps = d->r * d->s;
-  p.tap_ns = d->s;
-  p.tap_step = 1;
-  p.cls_step = 1;
-  p.a_group_bytes = (long long)SP_BYTES * d->n * p.src_img_stride;
-  p.b_bytes = (long long)SP_BYTES * d->cout * p.ktotal;
-  MVG_REQUIRE(p.a_group_bytes < 0x7FFFFFF0ll && p.b_bytes < 0x7FFFFFF0ll, "split conv: a group / the weights exceed 2 GiB");
+  if (fprop_geometry(p, d, SP_BYTES, SP_BYTES, "split conv", stride_w, pad_w)) return 2;
   MVG_REQUIRE(p.rows_per_group * (long long)d->cout < (1ll << 31), "split conv: a group of the output exceeds 2^31 elements");
-  p.tap_ns_div = make_fastdiv((unsigned)p.tap_ns);
-  p.ohw_div = make_fastdiv((unsigned)(p.out_h * p.out_w));
-  p.ow_div = make_fastdiv((unsigned)p.out_w);
   // (the stem's row-window form multiplies 7 x 32 values per output where the filter has 7 x 7 x 3: count the filter's)
   const double flops = 2.0 * d->groups * (double)p.rows_per_group * d->cout * d->r * d->s * d->cin * (stride_w >= 0 ? 147.0 / 224.0 : 1.0);
   const double bytes = (double)SP_BYTES * (d->groups * (double)d->n * d->h * d->w * d->cin + (double)d->cout * d->r * d->s * d->cin) +
@@ -1027,8 +980,6 @@ static int fprop_split_impl(const mvg_conv_desc *d, const void *x_sp, const floa
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_FPROP : MVG_K_CONV_FPROP, (hipStream_t)stream, flops, bytes);
   p.stats_partials = ceil_div(p.rows_per_group, SP_BM) * 2;    // = mvg_conv_stats_partials_split
-  p.ncls = 1;
-  class_from_params(p.cls[0], p);
   const bool lin_k = aff && aff->lin;
   return launch_igemm_split<false>(p, (hipStream_t)stream, lin_k, lin_k ? SP_BM : split_tile_rows(d->cout, d->r * d->s, p.rows_per_group));
 }
@@ -1079,29 +1030,7 @@ static int dgrad_split_impl(const mvg_conv_desc *d, const void *dy_sp, const flo
     p.bn_part = bnf->part;
     p.bn_part_rows = bnf->part_rows;
   }
-  p.groups = d->groups;
-  p.out_h = d->h;
-  p.out_w = d->w;
-  p.src_h = d->ho;
-  p.src_w = d->wo;
-  p.src_c = d->cout;
-  p.src_c_shift = (d->r * d->s > 1) ? ilog2_exact(d->cout) : 0;
-  p.ncols = d->cin;
-  p.r = d->r;
-  p.s = d->s;
-  p.rs = d->r * d->s;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.ktotal = d->r * d->s * d->cout;
-  p.b_row_len = d->r * d->s * d->cout;
-  p.cin = d->cin;
-  p.src_img_stride = (long long)d->ho * d->wo * d->cout;
-  p.imgs_per_group = d->n;
-  p.full_h = d->h;
-  p.full_w = d->w;
-  p.a_group_bytes = (long long)SP_BYTES * d->n * p.src_img_stride;
-  p.b_bytes = (long long)SP_BYTES * d->cin * p.b_row_len;
-  MVG_REQUIRE(p.a_group_bytes < 0x7FFFFFF0ll && p.b_bytes < 0x7FFFFFF0ll, "split conv: a group / the weights exceed 2 GiB");
+  if (dgrad_geometry(p, d, SP_BYTES, SP_BYTES, "split conv")) return 2;
   MVG_REQUIRE((long long)d->n * d->h * d->w * d->cin < (1ll << 31), "split conv: a group of dx exceeds 2^31 elements");
   const double flops = 2.0 * d->groups * (double)d->n * d->ho * d->wo * d->cout * d->r * d->s * d->cin;
   // (with the BatchNorm reduce on board the launch also reads that unit's y and mask bits: its algorithmic bytes)
@@ -1109,69 +1038,9 @@ static int dgrad_split_impl(const mvg_conv_desc *d, const void *dy_sp, const flo
                        (bnf ? 8.25 : 4.0) * d->groups * (double)d->n * d->h * d->w * d->cin;
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_DGRAD : MVG_K_CONV_DGRAD, (hipStream_t)stream, flops, bytes);
-  const int step = d->stride;
-  IgemmParams m = p;
-  m.ncls = 0;
-  int cls_k[4];
-  for (int py = 0; py < step; ++py)
-    for (int px = 0; px < step; ++px) {
-      const int sub_h = (d->h - py + step - 1) / step, sub_w = (d->w - px + step - 1) / step;
-      if (sub_h <= 0 || sub_w <= 0) continue;
-      const int r0 = (py + d->pad) % step, s0 = (px + d->pad) % step;
-      const int nr = r0 < d->r ? (d->r - r0 + step - 1) / step : 0;
-      const int ns = s0 < d->s ? (d->s - s0 + step - 1) / step : 0;
-      IgemmParams q = p;
-      q.out_h = sub_h;
-      q.out_w = sub_w;
-      q.rows_per_group = (long long)d->n * sub_h * sub_w;
-      q.ntaps = nr * ns;
-      q.tap_ns = ns > 0 ? ns : 1;
-      q.tap_ns_div = make_fastdiv((unsigned)q.tap_ns);
-      q.ohw_div = make_fastdiv((unsigned)(sub_h * sub_w));
-      q.ow_div = make_fastdiv((unsigned)sub_w);
-      q.tap_r0 = r0;
-      q.tap_s0 = s0;
-      q.tap_step = step;
-      q.ktotal = nr * ns * d->cout;
-      q.cls_step = step;
-      q.cls_py = py;
-      q.cls_px = px;
-      q.cls_cy = (py + d->pad - r0) / step;
-      q.cls_cx = (px + d->pad - s0) / step;
-      if (q.ntaps == 0 && !bnf) {
-        if (addend != dx || !addend) {                 // nothing to do when the caller accumulates in place
-          const long long n = (long long)d->groups * d->n * sub_h * sub_w * (d->cin / 4);
-          long long blocks = (n + 255) / 256;
-          if (blocks > 4096) blocks = 4096;
-          hipLaunchKernelGGL(dgrad_empty_class_split_kernel, dim3((unsigned)blocks), dim3(256), 0, (hipStream_t)stream, (float4 *)dx,
-                             (const float4 *)addend, n, sub_h, sub_w, d->h, d->w, d->cin / 4, py, px);
-          if (check_launch("dgrad_split(empty class)")) return 1;
-        }
-        continue;
-      }
-      if (m.ncls == 0) {
-        m.tap_step = step;
-        m.cls_step = step;
-        m.rows_per_group = q.rows_per_group;
-        m.ktotal = q.ktotal;
-        m.out_h = q.out_h;
-        m.out_w = q.out_w;
-      }
-      cls_k[m.ncls] = q.ktotal;
-      class_from_params(m.cls[m.ncls++], q);
-    }
-  if (m.ncls == 0) return 0;
-  for (int i = 1; i < m.ncls; ++i)                       // longest class first
-    for (int j = i; j > 0 && cls_k[j] > cls_k[j - 1]; --j) {
-      const IgemmClass tc = m.cls[j];
-      m.cls[j] = m.cls[j - 1];
-      m.cls[j - 1] = tc;
-      const int tk = cls_k[j];
-      cls_k[j] = cls_k[j - 1];
-      cls_k[j - 1] = tk;
-    }
-  m.no_remap = m.ncls > 1;
-  return launch_igemm_split<true>(m, (hipStream_t)stream, lin_kernel,
+  if (int e = dgrad_classes(p, d, bnf != nullptr, 4, dx, addend, (hipStream_t)stream)) return e;
+  if (p.ncls == 0) return 0;
+  return launch_igemm_split<true>(p, (hipStream_t)stream, lin_kernel,
                                   lin_kernel ? SP_BM : split_tile_rows(d->cin, d->r * d->s, (long long)d->n * d->h * d->w));
 }
 
@@ -1223,62 +1092,27 @@ int mvg_conv_wgrad_splits_split(const mvg_conv_desc *d) {
   if (validate_split(d)) return -1;
   int bm, bn;
   wgrad_split_tile(d, bm, bn);
-  const int ncols = d->r * d->s * d->cin;
-  const long long tiles = (long long)ceil_div(d->cout, bm) * ceil_div(ncols, bn);
-  const long long pixels = (long long)d->groups * d->n * d->ho * d->wo;
-  const int cus = compute_cus();
+  const long long tiles = (long long)ceil_div(d->cout, bm) * ceil_div(d->r * d->s * d->cin, bn);
   // one resident round: three workgroups per CU (128-column tiles; measured at C3: 2 / 3 / 4 / 6 per CU -> 17.8 / 16.8 / 16.7 /
-  // 17.7 ms of wgrad per step), two with the 256-column tiles (2 / 3 / 4 / 6 -> 15.6 / 16.8 / 16.4 / 17.3 ms)
-  long long want = ((bn == 256 ? 2LL : 3LL) * cus) / tiles;
-  long long maxs = pixels / 256;                           // at least 256 pixels (16 K-steps) per split
-  if (maxs < 1) maxs = 1;
-  if (want > maxs) want = maxs;
-  if (want < 1) want = 1;
-  if (want > 1024) want = 1024;
-  return (int)want;
+  // 17.7 ms of wgrad per step), two with the 256-column tiles (2 / 3 / 4 / 6 -> 15.6 / 16.8 / 16.4 / 17.3 ms); 16 K-steps per split
+  return wgrad_split_count(tiles, (long long)d->groups * d->n * d->ho * d->wo, bn == 256 ? 2 : 3, 256);
 }
 
 static int wgrad_split_impl(const mvg_conv_desc *d, const void *x_sp, const void *dy_sp, const float *dy_sinv, float *dw, float *workspace,
                             int splits, int accumulate, void *stream, int stride_w = -1, int pad_w = -1, const float *x_sinv = nullptr,
                             bool slabs_only = false) {
   if (stride_w < 0 && validate_split(d)) return 2;
-  MVG_REQUIRE(splits >= 1, "wgrad_split: splits < 1");
-  MVG_REQUIRE(splits == 1 || workspace != nullptr, "wgrad_split: workspace required for splits > 1");
   WgradParams p;
   memset(&p, 0, sizeof(p));
   p.x = (const float *)x_sp;
   p.dy = (const float *)dy_sp;
   p.dy_sinv = dy_sinv;
   p.x_sinv = x_sinv;
-  p.h = d->h;
-  p.w = d->w;
-  p.cin = d->cin;
-  p.cout = d->cout;
-  p.r = d->r;
-  p.s = d->s;
-  p.stride = d->stride;
-  p.pad = d->pad;
-  p.stride_w = stride_w >= 0 ? stride_w : d->stride;
-  p.pad_w = stride_w >= 0 ? pad_w : d->pad;
-  p.ho = d->ho;
-  p.wo = d->wo;
-  p.ncols = d->r * d->s * d->cin;
-  p.pixels = (long long)d->groups * d->n * d->ho * d->wo;
-  p.pixels_per_split = ((p.pixels + splits - 1) / splits + 15) / 16 * 16;
-  p.x_bytes = (long long)SP_BYTES * d->groups * d->n * d->h * d->w * d->cin;
-  p.ohw_div = make_fastdiv((unsigned)(d->ho * d->wo));
-  p.wo_div = make_fastdiv((unsigned)d->wo);
-  p.cin_div = make_fastdiv((unsigned)d->cin);
-  p.s_div = make_fastdiv((unsigned)d->s);
-  MVG_REQUIRE(p.pixels_per_split * d->cout * SP_BYTES < 0x7FFFFFF0ll, "wgrad_split: split too large for 32-bit offsets");
-  MVG_REQUIRE((long long)SP_BYTES * (p.pixels_per_split / (d->ho * d->wo) + 2) * d->h * d->w * d->cin < 0x7FFFFFF0ll,
-              "wgrad_split: split too large for 32-bit offsets");
+  if (wgrad_geometry(p, d, SP_BYTES, 16, dw, nullptr, workspace, splits, accumulate, "wgrad_split", stride_w, pad_w)) return 2;
   int bm, bn;
   wgrad_split_tile(d, bm, bn);
   p.mtiles = ceil_div(d->cout, bm);
   p.ntiles = ceil_div(p.ncols, bn);
-  p.out = splits == 1 ? dw : workspace;
-  p.accumulate = (splits == 1) ? accumulate : 0;
   hipStream_t st = (hipStream_t)stream;
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   {
@@ -1304,15 +1138,7 @@ static int wgrad_split_impl(const mvg_conv_desc *d, const void *x_sp, const void
 #undef MVG_WGRAD_SPLIT
     if (check_launch("conv_wgrad_split")) return 1;
   }
-  if (splits > 1 && !slabs_only) {
-    const long long n = (long long)d->cout * p.ncols;
-    ProfScope ps(MVG_K_WGRAD_REDUCE, st, 0.0, 4.0 * n * (splits + 1));
-    const int lanes = splits >= 32 ? 16 : (splits >= 8 ? 4 : 1);
-    const long long blocks = (n / 4 + 256 / lanes - 1) / (256 / lanes);
-    hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, workspace, dw, n / 4, splits, accumulate, lanes);
-    if (check_launch("wgrad_reduce")) return 1;
-  }
-  return 0;
+  return splits > 1 && !slabs_only ? wgrad_reduce_slabs(p, workspace, dw, nullptr, splits, accumulate, st, "wgrad_split") : 0;
 }
 
 int mvg_conv_wgrad_split(const mvg_conv_desc *d, const void *x_sp, const void *dy_sp, const float *dy_sinv, float *dw, float *workspace,
@@ -1447,13 +1273,7 @@ int mvg_stem_wgrad_splits_split(const mvg_conv_desc *d) {
   mvg_conv_desc rw;
   if (stem_desc(d, &rw)) return -1;
   const long long tiles = (long long)ceil_div(rw.cout, rw.cout >= 128 ? 128 : 64) * ceil_div(7 * 32, 128);
-  const long long pixels = (long long)rw.groups * rw.n * rw.ho * rw.wo;
-  long long want = (3LL * compute_cus()) / tiles, maxs = pixels / 256;
-  if (maxs < 1) maxs = 1;
-  if (want > maxs) want = maxs;
-  if (want < 1) want = 1;
-  if (want > 1024) want = 1024;
-  return (int)want;
+  return wgrad_split_count(tiles, (long long)rw.groups * rw.n * rw.ho * rw.wo, 3, 256);
 }
 
 int mvg_stem_wgrad_split(const mvg_conv_desc *d, const void *xw_sp, const void *dy_sp, const float *dy_sinv, float *dw_rw, float *workspace,

@@ -110,14 +110,18 @@ def cast_weights_bf16(d: ConvDesc, w: Tensor, cin_src: int, need_transposed: boo
     return wk, wt
 
 
+def _wgrad_slabs(splits_fn, what: str, d: ConvDesc, n: int, device):
+    """(splits, workspace) of a weight gradient with n elements per slab: splits_fn (an mvg_*wgrad_splits* entry point) plans
+    the pixel splits; more than one needs fp32 slabs [splits][n] for the library's fixed-order reduce."""
+    splits = splits_fn(C.byref(d))
+    if splits < 1:
+        check(1, what)
+    return splits, (torch.empty(splits * n, dtype=torch.float32, device=device) if splits > 1 else None)
+
+
 def conv_wgrad(d: ConvDesc, x: Tensor, dy: Tensor, dw: Tensor, accumulate: bool = False, defer: Optional[list] = None):
     """defer (bf16 storage only): see conv_wgrad_split - slabs now, their sums in one wgrad_reduce_batch launch per residual block."""
-    splits = _fn("mvg_conv_wgrad_splits", x)(C.byref(d))
-    if splits < 1:
-        check(1, "conv_wgrad_splits")
-    ws = None
-    if splits > 1:
-        ws = torch.empty(splits * d.cout * d.r * d.s * d.cin, dtype=torch.float32, device=x.device)
+    splits, ws = _wgrad_slabs(_fn("mvg_conv_wgrad_splits", x), "conv_wgrad_splits", d, d.cout * d.r * d.s * d.cin, x.device)
     if defer is not None and splits > 1 and x.dtype == torch.bfloat16 and dw.numel() == d.cout * d.r * d.s * d.cin and dw.numel() % 4 == 0:
         check(lib().mvg_conv_wgrad_bf16_slabs(C.byref(d), _p(x), _p(dy), _p(ws), splits, _s()), "conv_wgrad_bf16_slabs")
         defer.append((ws, dw, splits, bool(accumulate)))
@@ -128,10 +132,7 @@ def conv_wgrad(d: ConvDesc, x: Tensor, dy: Tensor, dw: Tensor, accumulate: bool 
 def linear_wgrad(x: Tensor, dy: Tensor, dw: Tensor, db: Optional[Tensor], rows: int, fin: int, fout: int, accumulate: bool = False):
     """dw (+)= dy^T x and db (+)= column sums of dy in one launch (+ the fixed-order slab reduce)."""
     d = ConvDesc.linear(rows, fin, fout)
-    splits = lib().mvg_conv_wgrad_splits(C.byref(d))
-    if splits < 1:
-        check(1, "conv_wgrad_splits")
-    ws = torch.empty(splits * (fout * fin + fout), dtype=torch.float32, device=x.device) if splits > 1 else None
+    splits, ws = _wgrad_slabs(lib().mvg_conv_wgrad_splits, "conv_wgrad_splits", d, fout * fin + fout, x.device)
     check(lib().mvg_linear_wgrad(_p(x), _p(dy), _p(dw), _p(db), rows, fin, fout, _p(ws), splits, int(accumulate), _s()),
           "linear_wgrad")
 
@@ -147,10 +148,7 @@ def fuser_fprop(img_feat, feat, rel, row_img, row_src, w, bias, relu, y, rows, c
 def fuser_wgrad(img_feat, feat, rel, row_img, row_src, dy, dw, db, rows, cf, nvec, fout, accumulate=False):
     fin = cf + 3 * nvec
     d = ConvDesc.linear(rows, fin, fout)
-    splits = lib().mvg_conv_wgrad_splits(C.byref(d))
-    if splits < 1:
-        check(1, "conv_wgrad_splits")
-    ws = torch.empty(splits * (fout * fin + fout), dtype=torch.float32, device=dy.device) if splits > 1 else None
+    splits, ws = _wgrad_slabs(lib().mvg_conv_wgrad_splits, "conv_wgrad_splits", d, fout * fin + fout, dy.device)
     check(lib().mvg_fuser_wgrad(_p(img_feat), _p(feat), _p(rel), _p(row_img), _p(row_src), _p(dy), _p(dw), _p(db), rows, cf, nvec,
                                 fout, img_feat.numel() // cf, feat.numel() // (3 * nvec), _p(ws), splits, int(accumulate), _s()),
           "fuser_wgrad")
@@ -270,10 +268,7 @@ def stem_fprop_split(d: ConvDesc, xw: Tensor, w_sp: Tensor, y: Tensor, stats: Op
 
 def stem_wgrad_split(d: ConvDesc, xw: Tensor, dy_sp: Tensor, dw_rw: Tensor, accumulate: bool = False):
     """dw_rw [cout, 7, 8, 4] fp32 (+)= the stem's weight gradient in the row-window tap layout."""
-    splits = lib().mvg_stem_wgrad_splits_split(C.byref(d))
-    if splits < 1:
-        check(1, "stem_wgrad_splits_split")
-    ws = torch.empty(splits * d.cout * 224, dtype=torch.float32, device=xw.device) if splits > 1 else None
+    splits, ws = _wgrad_slabs(lib().mvg_stem_wgrad_splits_split, "stem_wgrad_splits_split", d, d.cout * 224, xw.device)
     check(lib().mvg_stem_wgrad_split(C.byref(d), _p(xw), _p(dy_sp), _sinv(dy_sp), _p(dw_rw), _p(ws), splits, int(accumulate), _s()),
           "stem_wgrad_split")
 
@@ -312,10 +307,7 @@ def stem_fprop_bf16(d: ConvDesc, xw: Tensor, w_fold: Tensor, y: Tensor, stats: O
 
 def stem_wgrad_bf16(d: ConvDesc, xw: Tensor, dy: Tensor, dw_fold: Tensor, accumulate: bool = False):
     """dw_fold [2 cout, 7, 16, 4] fp32 (+)= the stem's weight gradient in the folded-window tap layout."""
-    splits = lib().mvg_stem_wgrad_splits_bf16(C.byref(d))
-    if splits < 1:
-        check(1, "stem_wgrad_splits_bf16")
-    ws = torch.empty(splits * 2 * d.cout * 448, dtype=torch.float32, device=xw.device) if splits > 1 else None
+    splits, ws = _wgrad_slabs(lib().mvg_stem_wgrad_splits_bf16, "stem_wgrad_splits_bf16", d, 2 * d.cout * 448, xw.device)
     check(lib().mvg_stem_wgrad_bf16(C.byref(d), _p(xw), _p(dy), _p(dw_fold), _p(ws), splits, int(accumulate), _s()), "stem_wgrad_bf16")
 
 
@@ -356,10 +348,7 @@ def conv_dgrad_bf16_bnreduce(d: ConvDesc, dy, wt, dx, addend, bn_y, bn_bits, bn_
 def conv_wgrad_split(d: ConvDesc, x_sp: Tensor, dy_sp: Tensor, dw: Tensor, accumulate: bool = False, defer: Optional[list] = None):
     """defer (a list): with more than one pixel split, only the slabs are written and (slabs, dw, splits, accumulate) is appended
     for ONE wgrad_reduce_batch launch over the list (the caller's: at the end of a residual block, on the same stream)."""
-    splits = lib().mvg_conv_wgrad_splits_split(C.byref(d))
-    if splits < 1:
-        check(1, "conv_wgrad_splits_split")
-    ws = torch.empty(splits * dw.numel(), dtype=torch.float32, device=dw.device) if splits > 1 else None
+    splits, ws = _wgrad_slabs(lib().mvg_conv_wgrad_splits_split, "conv_wgrad_splits_split", d, dw.numel(), dw.device)
     assert getattr(x_sp, "sinv", None) is None, "conv_wgrad_split: the activation operand is stored unscaled"
     if defer is not None and splits > 1:
         check(lib().mvg_conv_wgrad_split_slabs(C.byref(d), _p(x_sp), _p(dy_sp), _sinv(dy_sp), _p(ws), splits, _s()), "conv_wgrad_split_slabs")
@@ -436,10 +425,7 @@ def linear_dgrad_mixed(dy, wt_bf16, mask, addend, dx, rows, fin, fout):
 
 def linear_wgrad_mixed(x, dy, dw, db, rows, fin, fout, accumulate=False):
     d = ConvDesc.linear(rows, fin, fout)
-    splits = lib().mvg_conv_wgrad_splits_bf16(C.byref(d))
-    if splits < 1:
-        check(1, "conv_wgrad_splits_bf16")
-    ws = torch.empty(splits * (fout * fin + fout), dtype=torch.float32, device=x.device) if splits > 1 else None
+    splits, ws = _wgrad_slabs(lib().mvg_conv_wgrad_splits_bf16, "conv_wgrad_splits_bf16", d, fout * fin + fout, x.device)
     check(lib().mvg_linear_wgrad_mixed(_p(x), _p(dy), _p(dw), _p(db), rows, fin, fout, _p(ws), splits, int(accumulate), _s()),
           "linear_wgrad_mixed")
 
@@ -739,10 +725,7 @@ def linear_dgrad_split(dy_sp, wt_sp, dx, rows, fin, fout, addend=None, relu_mask
 
 def linear_wgrad_split(x_sp, dy_sp, dw, rows, fin, fout, accumulate=False):
     d = ConvDesc.make(1, rows, 1, 1, fin, fout, 1, 1, 0)
-    splits = lib().mvg_conv_wgrad_splits_split(C.byref(d))
-    if splits < 1:
-        check(1, "conv_wgrad_splits_split")
-    ws = torch.empty(splits * dw.numel(), dtype=torch.float32, device=dw.device) if splits > 1 else None
+    splits, ws = _wgrad_slabs(lib().mvg_conv_wgrad_splits_split, "conv_wgrad_splits_split", d, dw.numel(), dw.device)
     check(lib().mvg_linear_wgrad_split(rows, fin, fout, _p(x_sp), _sinv(x_sp), _p(dy_sp), _sinv(dy_sp), _p(dw), _p(ws), splits,
                                        int(accumulate), _s()), "linear_wgrad_split")
 
