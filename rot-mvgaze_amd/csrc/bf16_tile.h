@@ -2,6 +2,7 @@
 // bf16 pieces): vector types, packing, and the LDS-staged tile epilogue.  Static / inline only (conv_shared.h).
 #pragma once
 #include "conv_shared.h"
+#include "bn_math.h"
 #include "elem.h"
 
 namespace mvg {
@@ -271,7 +272,7 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
           ld8(bnc + 2 * BN + cv * 8, bn_ra);
           ld8(bnc + 3 * BN + cv * 8, bn_rb);
 #pragma unroll
-          for (int k = 0; k < 8; ++k) bits = (bits & ~(1u << k)) | ((__builtin_fmaf(yy[k], bn_ra[k], bn_rb[k]) > 0.f ? 1u : 0u) << k);
+          for (int k = 0; k < 8; ++k) bits = (bits & ~(1u << k)) | ((relu_on(yy[k], bn_ra[k], bn_rb[k]) ? 1u : 0u) << k);
         }
         float bn_mu[8], bn_is[8];
         ld8(bnc + cv * 8, bn_mu);
@@ -281,7 +282,7 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
           x[k] = ((bits >> k) & 1u) != 0u ? x[k] : 0.f;
           bn_mx[k] = fmaxf(bn_mx[k], fabsf(x[k]));
           bn_s1[k] += x[k];
-          bn_s2[k] += x[k] * ((yy[k] - bn_mu[k]) * bn_is[k]);
+          bn_s2[k] += x[k] * xhat(yy[k], bn_mu[k], bn_is[k]);
         }
       }
       if constexpr (LIN) {
@@ -330,8 +331,8 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
         bits = 0u;
 #pragma unroll
         for (int k = 0; k < 4; ++k) {
-          bits |= (__builtin_fmaf(bf_lo(yw[k]), bn_ra[2 * k], bn_rb[2 * k]) > 0.f ? 1u : 0u) << (2 * k);
-          bits |= (__builtin_fmaf(bf_hi(yw[k]), bn_ra[2 * k + 1], bn_rb[2 * k + 1]) > 0.f ? 1u : 0u) << (2 * k + 1);
+          bits |= (relu_on(bf_lo(yw[k]), bn_ra[2 * k], bn_rb[2 * k]) ? 1u : 0u) << (2 * k);
+          bits |= (relu_on(bf_hi(yw[k]), bn_ra[2 * k + 1], bn_rb[2 * k + 1]) ? 1u : 0u) << (2 * k + 1);
         }
       }
       // the second sum stays UNCENTRED here - sum(dz * y); bn_bwd_finalize turns the totals into s2 = invstd * (sum(dz * y)
@@ -404,7 +405,7 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
           ld44(bnc + 2 * BN, bn_ra);
           ld44(bnc + 3 * BN, bn_rb);
 #pragma unroll
-          for (int k = 0; k < 8; ++k) bits = (bits & ~(1u << k)) | ((__builtin_fmaf(yy[k], bn_ra[k], bn_rb[k]) > 0.f ? 1u : 0u) << k);
+          for (int k = 0; k < 8; ++k) bits = (bits & ~(1u << k)) | ((relu_on(yy[k], bn_ra[k], bn_rb[k]) ? 1u : 0u) << k);
         }
         float bn_mu[8], bn_is[8];
         ld44(bnc, bn_mu);
@@ -414,7 +415,7 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
           x[k] = ((bits >> k) & 1u) != 0u ? x[k] : 0.f;
           bn_mx[k] = fmaxf(bn_mx[k], fabsf(x[k]));
           bn_s1[k] += x[k];
-          bn_s2[k] += x[k] * ((yy[k] - bn_mu[k]) * bn_is[k]);
+          bn_s2[k] += x[k] * xhat(yy[k], bn_mu[k], bn_is[k]);
         }
       }
       if (p.nt_out) {

@@ -4,6 +4,7 @@
 
 #include "common.h"
 #include "elem.h"
+#include "bn_math.h"
 
 namespace mvg {
 
@@ -395,35 +396,16 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T *__restrict__ y, 
     if (residual) Elem<TR>::ldw(residual, base + i, r);
 #pragma unroll
     for (int w = 0; w < W; ++w) {
-      const float4 a = pa[w], b = pb[w];
-      // explicit fma: the backward kernels rebuild the ReLU mask from y with the same expression
-      o[w] = make_float4(__builtin_fmaf(v[w].x, a.x, b.x), __builtin_fmaf(v[w].y, a.y, b.y), __builtin_fmaf(v[w].z, a.z, b.z),
-                         __builtin_fmaf(v[w].w, a.w, b.w));
-      if (residual) {
-        float4 rr = r[w];
-        if (rs4) {
-          const float4 ra = pra[w], rb = prb[w];
-          rr = make_float4(__builtin_fmaf(rr.x, ra.x, rb.x), __builtin_fmaf(rr.y, ra.y, rb.y), __builtin_fmaf(rr.z, ra.z, rb.z),
-                           __builtin_fmaf(rr.w, ra.w, rb.w));
-        }
-        o[w].x += rr.x;
-        o[w].y += rr.y;
-        o[w].z += rr.z;
-        o[w].w += rr.w;
-      }
-      if (relu) {
-        o[w].x = fmaxf(o[w].x, 0.f);
-        o[w].y = fmaxf(o[w].y, 0.f);
-        o[w].z = fmaxf(o[w].z, 0.f);
-        o[w].w = fmaxf(o[w].w, 0.f);
-      }
+      o[w] = bn_fwd(v[w], pa[w], pb[w]);      // bn_math.h: the backward kernels rebuild the ReLU mask from y with relu_on
+      if (residual) acc4(o[w], rs4 ? bn_fwd(r[w], pra[w], prb[w]) : r[w]);
+      if (relu) o[w] = relu4(o[w]);
     }
     Elem<TO>::stw(out, base + i, o);
     if (relu_bits) {
       unsigned m = 0;
 #pragma unroll
       for (int w = 0; w < W; ++w)
-        m |= ((o[w].x > 0.f ? 1u : 0u) | (o[w].y > 0.f ? 2u : 0u) | (o[w].z > 0.f ? 4u : 0u) | (o[w].w > 0.f ? 8u : 0u)) << (4 * w);
+        m |= relu_nibble(o[w]) << (4 * w);
       relu_bits[base + i] = (unsigned char)m;
     }
     cq += step;
@@ -432,6 +414,43 @@ __global__ __launch_bounds__(256) void bn_apply_kernel(const T *__restrict__ y, 
 }
 
 // ---- backward reduce ------------------------------------------------------------------------
+// The tail of every reduce-type kernel.  256 lanes = nrl row lanes x cw columns (lane = rl * cw + cl), column group cq
+// of the row, valid when cok: the row lanes' sums meet in LDS and row lane 0 folds them in row-lane order - s1 and s2 by
+// addition, mx (max |dz|, R == 3 only) by maximum - and stores rows 0 .. prows - 1 of partial record grp * chunks +
+// blockIdx.x ([prows][c] floats, row4 float4 per row; the third row times mx_scale).  s1 / s2 / mx: W float4 each.
+// (The record's address is formed here, after the barrier, from its ingredients: formed at the call it compiles to
+// vector instead of scalar arithmetic.)
+template <int R, int W>
+__device__ __forceinline__ void bn_reduce_tail(float4 (&sh)[R][256][W], float4 *s1, float4 *s2, float4 *mx, bool cok, int nrl, int cw, int rl,
+                                               int cl, int cq, float *partial, int grp, int chunks, int c, int row4, int prows = 2,
+                                               float mx_scale = 1.f) {
+#pragma unroll
+  for (int w = 0; w < W; ++w) {
+    sh[0][threadIdx.x][w] = s1[w];
+    sh[1][threadIdx.x][w] = s2[w];
+    if constexpr (R == 3) sh[2][threadIdx.x][w] = mx[w];
+  }
+  __syncthreads();
+  if (rl == 0 && cok) {
+    for (int k = 1; k < nrl; ++k) {
+#pragma unroll
+      for (int w = 0; w < W; ++w) {
+        acc4(s1[w], sh[0][k * cw + cl][w]);
+        acc4(s2[w], sh[1][k * cw + cl][w]);
+        if constexpr (R == 3) max4(mx[w], sh[2][k * cw + cl][w]);
+      }
+    }
+    float4 *p = reinterpret_cast<float4 *>(partial + (((long long)grp * chunks + blockIdx.x) * prows) * c);
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      p[cq * W + w] = s1[w];
+      p[row4 + cq * W + w] = s2[w];
+      if constexpr (R == 3)
+        if (prows == 3) p[2 * row4 + cq * W + w] = mul4(mx[w], mx_scale);
+    }
+  }
+}
+
 // grid = (chunks, column blocks, groups); thread = one float4 column group x one row lane.
 template <typename T>
 __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T *g, const T *__restrict__ act,
@@ -455,14 +474,14 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T *g, const T 
   const bool cok = cq < cwn;
   float4 s1[W], s2[W], mx[W];
 #pragma unroll
-  for (int w = 0; w < W; ++w) s1[w] = s2[w] = mx[w] = make_float4(0.f, 0.f, 0.f, 0.f);
+  for (int w = 0; w < W; ++w) s1[w] = s2[w] = mx[w] = zero4();
   if (cok) {
     float4 mu[W], is[W], ma[W], mb[W];
 #pragma unroll
     for (int w = 0; w < W; ++w) {
       mu[w] = reinterpret_cast<const float4 *>(mean + (long long)grp * c)[cq * W + w];
       is[w] = reinterpret_cast<const float4 *>(invstd + (long long)grp * c)[cq * W + w];
-      ma[w] = mb[w] = make_float4(0.f, 0.f, 0.f, 0.f);
+      ma[w] = mb[w] = zero4();
       if (mscale) {
         ma[w] = reinterpret_cast<const float4 *>(mscale + (long long)grp * c)[cq * W + w];
         mb[w] = reinterpret_cast<const float4 *>(mshift + (long long)grp * c)[cq * W + w];
@@ -483,35 +502,12 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T *g, const T 
       const unsigned mb8 = relu_bits ? (unsigned)relu_bits[off] : 0u;
 #pragma unroll
       for (int w = 0; w < W; ++w) {
-        if (relu_bits) {               // the mask bn_apply recorded (bit k of the byte = element k of this access > 0)
-          const unsigned m4 = mb8 >> (4 * w);
-          d[w].x = (m4 & 1u) ? d[w].x : 0.f;
-          d[w].y = (m4 & 2u) ? d[w].y : 0.f;
-          d[w].z = (m4 & 4u) ? d[w].z : 0.f;
-          d[w].w = (m4 & 8u) ? d[w].w : 0.f;
-        } else if (act) {
-          d[w].x = a[w].x > 0.f ? d[w].x : 0.f;
-          d[w].y = a[w].y > 0.f ? d[w].y : 0.f;
-          d[w].z = a[w].z > 0.f ? d[w].z : 0.f;
-          d[w].w = a[w].w > 0.f ? d[w].w : 0.f;
-        } else if (mscale) {       // ReLU without residual: out > 0 <=> fma(y, scale, shift) > 0 (bn_apply_kernel)
-          d[w].x = __builtin_fmaf(v[w].x, ma[w].x, mb[w].x) > 0.f ? d[w].x : 0.f;
-          d[w].y = __builtin_fmaf(v[w].y, ma[w].y, mb[w].y) > 0.f ? d[w].y : 0.f;
-          d[w].z = __builtin_fmaf(v[w].z, ma[w].z, mb[w].z) > 0.f ? d[w].z : 0.f;
-          d[w].w = __builtin_fmaf(v[w].w, ma[w].w, mb[w].w) > 0.f ? d[w].w : 0.f;
-        }
-        mx[w].x = fmaxf(mx[w].x, fabsf(d[w].x));
-        mx[w].y = fmaxf(mx[w].y, fabsf(d[w].y));
-        mx[w].z = fmaxf(mx[w].z, fabsf(d[w].z));
-        mx[w].w = fmaxf(mx[w].w, fabsf(d[w].w));
-        a1[w].x += d[w].x;
-        a1[w].y += d[w].y;
-        a1[w].z += d[w].z;
-        a1[w].w += d[w].w;
-        a2[w].x += d[w].x * ((v[w].x - mu[w].x) * is[w].x);
-        a2[w].y += d[w].y * ((v[w].y - mu[w].y) * is[w].y);
-        a2[w].z += d[w].z * ((v[w].z - mu[w].z) * is[w].z);
-        a2[w].w += d[w].w * ((v[w].w - mu[w].w) * is[w].w);
+        if (relu_bits) d[w] = mask_bits4(d[w], mb8 >> (4 * w));      // the mask bn_apply recorded (bit k of the byte = element k of this access > 0)
+        else if (act) d[w] = mask_act4(d[w], a[w]);
+        else if (mscale) d[w] = mask_affine4(d[w], v[w], ma[w], mb[w]);   // ReLU without residual (bn_math.h: relu_on)
+        max4(mx[w], abs4(d[w]));
+        acc4(a1[w], d[w]);
+        acc4_xhat(a2[w], d[w], v[w], mu[w], is[w]);
       }
       if (dz_out) E::stw(dz_out, off, d);      // the masked gradient (may alias g): the apply pass then needs no mask
     };
@@ -520,7 +516,7 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T *g, const T 
 #pragma unroll
     for (int u = 0; u < U - 1; ++u)
 #pragma unroll
-      for (int w = 0; w < W; ++w) t1[u][w] = t2[u][w] = make_float4(0.f, 0.f, 0.f, 0.f);
+      for (int w = 0; w < W; ++w) t1[u][w] = t2[u][w] = zero4();
     long long r = r0 + rl;
     for (; r + (U - 1) * (long long)nrl < r1; r += U * (long long)nrl) {
       row(r, s1, s2);
@@ -531,41 +527,15 @@ __global__ __launch_bounds__(256) void bn_bwd_reduce_kernel(const T *g, const T 
 #pragma unroll
     for (int w = 0; w < W; ++w) {
       if constexpr (U == 4) {
-        s1[w].x += t1[0][w].x + (t1[1][w].x + t1[2][w].x); s1[w].y += t1[0][w].y + (t1[1][w].y + t1[2][w].y);
-        s1[w].z += t1[0][w].z + (t1[1][w].z + t1[2][w].z); s1[w].w += t1[0][w].w + (t1[1][w].w + t1[2][w].w);
-        s2[w].x += t2[0][w].x + (t2[1][w].x + t2[2][w].x); s2[w].y += t2[0][w].y + (t2[1][w].y + t2[2][w].y);
-        s2[w].z += t2[0][w].z + (t2[1][w].z + t2[2][w].z); s2[w].w += t2[0][w].w + (t2[1][w].w + t2[2][w].w);
+        acc4(s1[w], add4(t1[0][w], add4(t1[1][w], t1[2][w])));
+        acc4(s2[w], add4(t2[0][w], add4(t2[1][w], t2[2][w])));
       } else {
-        s1[w].x += t1[0][w].x; s1[w].y += t1[0][w].y; s1[w].z += t1[0][w].z; s1[w].w += t1[0][w].w;
-        s2[w].x += t2[0][w].x; s2[w].y += t2[0][w].y; s2[w].z += t2[0][w].z; s2[w].w += t2[0][w].w;
+        acc4(s1[w], t1[0][w]);
+        acc4(s2[w], t2[0][w]);
       }
     }
   }
-#pragma unroll
-  for (int w = 0; w < W; ++w) {
-    sh[0][threadIdx.x][w] = s1[w];
-    sh[1][threadIdx.x][w] = s2[w];
-    sh[2][threadIdx.x][w] = mx[w];
-  }
-  __syncthreads();
-  if (rl == 0 && cok) {
-    for (int k = 1; k < nrl; ++k) {
-#pragma unroll
-      for (int w = 0; w < W; ++w) {
-        const float4 a = sh[0][k * cw + cl][w], b = sh[1][k * cw + cl][w], m = sh[2][k * cw + cl][w];
-        s1[w].x += a.x; s1[w].y += a.y; s1[w].z += a.z; s1[w].w += a.w;
-        s2[w].x += b.x; s2[w].y += b.y; s2[w].z += b.z; s2[w].w += b.w;
-        mx[w].x = fmaxf(mx[w].x, m.x); mx[w].y = fmaxf(mx[w].y, m.y); mx[w].z = fmaxf(mx[w].z, m.z); mx[w].w = fmaxf(mx[w].w, m.w);
-      }
-    }
-    float4 *p = reinterpret_cast<float4 *>(partial + (((long long)grp * chunks + blockIdx.x) * prows) * c);
-#pragma unroll
-    for (int w = 0; w < W; ++w) {
-      p[cq * W + w] = s1[w];
-      p[c / 4 + cq * W + w] = s2[w];
-      if (prows == 3) p[2 * (c / 4) + cq * W + w] = mx[w];
-    }
-  }
+  bn_reduce_tail(sh, s1, s2, mx, cok, nrl, cw, rl, cl, cq, partial, grp, chunks, c, c / 4, prows);
 }
 
 // grid = (c/16, groups) blocks, 1024 threads = 16 channels x 64 chunk-lanes: one (view) group per workgroup (a 64-channel
@@ -704,23 +674,9 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_kernel(const T *__restrict__
     if (act) E::ldw(act, base + i, a);
 #pragma unroll
     for (int w = 0; w < W; ++w) {
-      if (act) {
-        d[w].x = a[w].x > 0.f ? d[w].x : 0.f;
-        d[w].y = a[w].y > 0.f ? d[w].y : 0.f;
-        d[w].z = a[w].z > 0.f ? d[w].z : 0.f;
-        d[w].w = a[w].w > 0.f ? d[w].w : 0.f;
-      } else if (mscale) {
-        const float4 ma = pma[w], mb = pmb[w];
-        d[w].x = __builtin_fmaf(v[w].x, ma.x, mb.x) > 0.f ? d[w].x : 0.f;
-        d[w].y = __builtin_fmaf(v[w].y, ma.y, mb.y) > 0.f ? d[w].y : 0.f;
-        d[w].z = __builtin_fmaf(v[w].z, ma.z, mb.z) > 0.f ? d[w].z : 0.f;
-        d[w].w = __builtin_fmaf(v[w].w, ma.w, mb.w) > 0.f ? d[w].w : 0.f;
-      }
-      const float4 mu = pmu[w], is = pis[w], ga = pga[w], sa = psa[w], sb = psb[w];
-      o[w].x = ga.x * is.x * (d[w].x - sa.x * inv_rows - (v[w].x - mu.x) * is.x * (sb.x * inv_rows));
-      o[w].y = ga.y * is.y * (d[w].y - sa.y * inv_rows - (v[w].y - mu.y) * is.y * (sb.y * inv_rows));
-      o[w].z = ga.z * is.z * (d[w].z - sa.z * inv_rows - (v[w].z - mu.z) * is.z * (sb.z * inv_rows));
-      o[w].w = ga.w * is.w * (d[w].w - sa.w * inv_rows - (v[w].w - mu.w) * is.w * (sb.w * inv_rows));
+      if (act) d[w] = mask_act4(d[w], a[w]);
+      else if (mscale) d[w] = mask_affine4(d[w], v[w], pma[w], pmb[w]);
+      o[w] = bn_dy(d[w], v[w], pmu[w], pis[w], pga[w], psa[w], psb[w], inv_rows);
     }
     if (dz_out) E::stw(dz_out, base + i, d);
     Elem<TO>::stw(dy, base + i, o);
@@ -788,8 +744,8 @@ __global__ __launch_bounds__(256) void bn_apply_sp_kernel(const float *__restric
     unsigned m = 0;
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
-      float x = __builtin_fmaf(v.v[k], sc.v[k], sh.v[k]);      // the same expressions as bn_apply_kernel (mask rebuild in the backward)
-      if (residual) x += raff ? __builtin_fmaf(r.v[k], rs.v[k], rh.v[k]) : r.v[k];
+      float x = bn_fwd(v.v[k], sc.v[k], sh.v[k]);              // bn_math.h, as bn_apply_kernel (mask rebuild in the backward)
+      if (residual) x += raff ? bn_fwd(r.v[k], rs.v[k], rh.v[k]) : r.v[k];
       if (relu) x = fmaxf(x, 0.f);
       o.v[k] = x;
       m |= (x > 0.f ? 1u : 0u) << (k + (k >= 4 ? 4 : 0));    // two bytes, low nibbles: one byte per 4 channels (bn_bwd_reduce_bits)
@@ -856,8 +812,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_sp_kernel(const float *__res
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float dd = d.v[k];
-      if (mscale) dd = __builtin_fmaf(v.v[k], ma.v[k], mb.v[k]) > 0.f ? dd : 0.f;
-      o.v[k] = (ga.v[k] * is.v[k] * (dd - sa.v[k] * inv_rows - (v.v[k] - mu.v[k]) * is.v[k] * (sb.v[k] * inv_rows))) * dsc;
+      if (mscale) dd = relu_mask(relu_on(v.v[k], ma.v[k], mb.v[k]), dd);
+      o.v[k] = bn_dy(dd, v.v[k], mu.v[k], is.v[k], ga.v[k], sa.v[k], sb.v[k], inv_rows) * dsc;
     }
     st8_sp(dy, base + i, o);
     cq += step;
@@ -869,12 +825,7 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_sp_kernel(const float *__res
 // The normalised stem activation (B*V x 112 x 112 x 64 floats, 411 MB at C2) is never written:
 // forward reads the conv output once and writes the pooled map + argmax; backward rebuilds the
 // gradient of the BN output on the fly (gather over the <= 4 pooling windows a pixel can win) and
-// the ReLU mask from y (mask = fma(y, scale, shift) > 0, the same expression as the forward).
-__device__ __forceinline__ float4 bn_relu4(float4 v, float4 a, float4 b) {
-  return make_float4(fmaxf(__builtin_fmaf(v.x, a.x, b.x), 0.f), fmaxf(__builtin_fmaf(v.y, a.y, b.y), 0.f),
-                     fmaxf(__builtin_fmaf(v.z, a.z, b.z), 0.f), fmaxf(__builtin_fmaf(v.w, a.w, b.w), 0.f));
-}
-
+// the ReLU mask from y (bn_math.h: relu_on, the forward's own expression).
 // grid = (ceil(wo*c4n / 256), images*ho): one thread = one (image, oy, ox, 4 channels), no per-thread
 // divisions by runtime values except ox/cq.  First maximum in (kh, kw) scan order (ATen's rule).
 template <typename T, typename TO = T>
@@ -934,7 +885,7 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const T *__rest
                                                                  int cw, float *__restrict__ partial, int chunks, int prows) {
   // prows == 3 (split path): a third partial row bounds max |gradient of a pixel| per channel - 4 x the largest masked
   // window gradient (a pixel wins at most four of the 3x3 stride-2 windows) - for the sp scale of dy
-  __shared__ float4 sh[3][256];
+  __shared__ float4 sh[3][256][1];
   const int grp = blockIdx.z;
   const int rl = threadIdx.x / cw, cl = threadIdx.x % cw;
   const int nrl = 256 / cw;
@@ -966,31 +917,69 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_reduce_kernel(const T *__rest
           const int kh = (k[j] * 11) >> 5, kw = k[j] - 3 * kh;          // k / 3, k % 3 for k < 9
           const int iy = 2 * oy - 1 + kh, ix = 2 * ox - 1 + kw;          // the winner is an in-bounds pixel
           const float v = Elem<T>::ld1(yimg, ((long long)iy * w + ix) * c + j);
-          const float d = __builtin_fmaf(v, sa[j], sb[j]) > 0.f ? g[j] : 0.f;
+          const float d = relu_mask(relu_on(v, sa[j], sb[j]), g[j]);
           mxv[j] = fmaxf(mxv[j], fabsf(d));
           s1[j] += d;
-          s2[j] += d * ((v - mu[j]) * is[j]);
+          s2[j] += d * xhat(v, mu[j], is[j]);
         }
       }
     }
   }
-  sh[0][threadIdx.x] = make_float4(s1[0], s1[1], s1[2], s1[3]);
-  sh[1][threadIdx.x] = make_float4(s2[0], s2[1], s2[2], s2[3]);
-  sh[2][threadIdx.x] = make_float4(mxv[0], mxv[1], mxv[2], mxv[3]);
-  __syncthreads();
-  if (rl == 0 && cok) {
-    float4 t1 = sh[0][threadIdx.x], t2 = sh[1][threadIdx.x], t3 = sh[2][threadIdx.x];
-    for (int k = 1; k < nrl; ++k) {
-      const float4 a = sh[0][k * cw + cl], b = sh[1][k * cw + cl], m = sh[2][k * cw + cl];
-      t1.x += a.x; t1.y += a.y; t1.z += a.z; t1.w += a.w;
-      t2.x += b.x; t2.y += b.y; t2.z += b.z; t2.w += b.w;
-      t3.x = fmaxf(t3.x, m.x); t3.y = fmaxf(t3.y, m.y); t3.z = fmaxf(t3.z, m.z); t3.w = fmaxf(t3.w, m.w);
+  float4 t1[1] = {make_float4(s1[0], s1[1], s1[2], s1[3])}, t2[1] = {make_float4(s2[0], s2[1], s2[2], s2[3])};
+  float4 t3[1] = {make_float4(mxv[0], mxv[1], mxv[2], mxv[3])};
+  bn_reduce_tail(sh, t1, t2, t3, cok, nrl, cw, rl, cl, cq, partial, grp, chunks, c, c4n, prows, 4.f);
+}
+
+// The quad gather of the stem tail's backward passes: the 2 x 2 pixel quad (rows 2 qa, 2 qa + 1, columns 2 qb, 2 qb + 1) x 4
+// channels of image n can only have won the pooling windows (qa, qa + 1) x (qb, qb + 1): their four (argmax, gradient)
+// records and the quad's four y are loaded once, and pixel(px, d, v) is called for every pixel inside the image with its
+// float4 index px, the sum d of the gradients of the windows it won - added in the order (qa, qb), (qa, qb + 1),
+// (qa + 1, qb), (qa + 1, qb + 1), ReLU mask not applied yet - and its y.  `pixel` captures BY VALUE and receives what it
+// accumulates into as `sums`: values reached through a closure of references are promoted to registers only after the
+// loop optimisations have run, and the per-channel products of bn_dy then contract differently (other roundings).
+template <typename T, typename F, typename... S>
+__device__ __forceinline__ void pool_quad_gather(const T *__restrict__ gp, const uchar4 *__restrict__ am, const T *__restrict__ y, long long n,
+                                                 int qa, int qb, int cq, int h, int w, int ho, int wo, int c4n, F pixel, S &...sums) {
+  uchar4 wk[2][2];
+  float4 wg[2][2];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+      const bool ok = qa + i < ho && qb + j < wo;
+      const long long o = ((n * ho + qa + i) * wo + qb + j) * c4n + cq;
+      wk[i][j] = ok ? am[o] : make_uchar4(255, 255, 255, 255);
+      wg[i][j] = ok ? Elem<T>::ld4(gp, o) : zero4();
     }
-    float4 *p = reinterpret_cast<float4 *>(partial + (((long long)grp * chunks + blockIdx.x) * prows) * c);
-    p[cq] = t1;
-    p[c4n + cq] = t2;
-    if (prows == 3) p[2 * c4n + cq] = make_float4(4.f * t3.x, 4.f * t3.y, 4.f * t3.z, 4.f * t3.w);
-  }
+  float4 v[2][2];
+  bool pok[2][2];
+#pragma unroll
+  for (int pi = 0; pi < 2; ++pi)
+#pragma unroll
+    for (int pj = 0; pj < 2; ++pj) {
+      pok[pi][pj] = 2 * qa + pi < h && 2 * qb + pj < w;
+      v[pi][pj] = pok[pi][pj] ? Elem<T>::ld4(y, ((n * h + 2 * qa + pi) * w + 2 * qb + pj) * c4n + cq) : zero4();
+    }
+#pragma unroll
+  for (int pi = 0; pi < 2; ++pi)
+#pragma unroll
+    for (int pj = 0; pj < 2; ++pj) {
+      if (!pok[pi][pj]) continue;
+      // pixel (2 qa + pi, 2 qb + pj) inside window (qa + i, qb + j): kh = pi + 1 - 2 i, kw = pj + 1 - 2 j (in 0..2)
+      float4 d = zero4();
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const int kh = pi + 1 - 2 * i;
+        if (kh < 0) continue;
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+          const int kw = pj + 1 - 2 * j;
+          if (kw < 0) continue;
+          d = map4([](float d, unsigned k, float g, unsigned me) { return k == me ? d + g : d; }, d, wk[i][j], wg[i][j], (unsigned)(kh * 3 + kw));
+        }
+      }
+      pixel(((n * h + 2 * qa + pi) * w + 2 * qb + pj) * c4n + cq, d, v[pi][pj], sums...);
+    }
 }
 
 // grid = (ceil(ceil(w/2)*c4n / 256), images*ceil(h/2)): one thread = one 2 x 2 pixel quad (rows 2a, 2a+1, columns 2b, 2b+1)
@@ -1018,67 +1007,14 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const T *__restr
   const float4 sa = reinterpret_cast<const float4 *>(scale)[gq], sb = reinterpret_cast<const float4 *>(shift)[gq];
   const float4 a1 = reinterpret_cast<const float4 *>(s1)[gq], a2 = reinterpret_cast<const float4 *>(s2)[gq];
   const float4 ga = reinterpret_cast<const float4 *>(gamma)[cq];
-  const float dsc = dy_sinv ? 1.f / *dy_sinv : 1.f;         // sp result: times 2^k (bn_dy_scale_kernel; exact)
-  // the four windows
-  uchar4 wk[2][2];
-  float4 wg[2][2];
-#pragma unroll
-  for (int i = 0; i < 2; ++i)
-#pragma unroll
-    for (int j = 0; j < 2; ++j) {
-      const bool ok = qa + i < ho && qb + j < wo;
-      const long long o = (((long long)n * ho + qa + i) * wo + qb + j) * c4n + cq;
-      wk[i][j] = ok ? am[o] : make_uchar4(255, 255, 255, 255);
-      wg[i][j] = ok ? Elem<T>::ld4(gp, o) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-  float4 v[2][2];
-  bool pok[2][2];
-#pragma unroll
-  for (int pi = 0; pi < 2; ++pi)
-#pragma unroll
-    for (int pj = 0; pj < 2; ++pj) {
-      pok[pi][pj] = 2 * qa + pi < h && 2 * qb + pj < w;
-      v[pi][pj] = pok[pi][pj] ? Elem<T>::ld4(y, (((long long)n * h + 2 * qa + pi) * w + 2 * qb + pj) * c4n + cq) : make_float4(0.f, 0.f, 0.f, 0.f);
-    }
-#pragma unroll
-  for (int pi = 0; pi < 2; ++pi)
-#pragma unroll
-    for (int pj = 0; pj < 2; ++pj) {
-      if (!pok[pi][pj]) continue;
-      // pixel (2 qa + pi, 2 qb + pj) inside window (qa + i, qb + j): kh = pi + 1 - 2 i, kw = pj + 1 - 2 j (in 0..2)
-      float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const int kh = pi + 1 - 2 * i;
-        if (kh < 0) continue;
-#pragma unroll
-        for (int j = 0; j < 2; ++j) {
-          const int kw = pj + 1 - 2 * j;
-          if (kw < 0) continue;
-          const unsigned char me = (unsigned char)(kh * 3 + kw);
-          const uchar4 k = wk[i][j];
-          const float4 g = wg[i][j];
-          if (k.x == me) d.x += g.x;
-          if (k.y == me) d.y += g.y;
-          if (k.z == me) d.z += g.z;
-          if (k.w == me) d.w += g.w;
-        }
-      }
-      const float4 vv = v[pi][pj];
-      d.x = __builtin_fmaf(vv.x, sa.x, sb.x) > 0.f ? d.x : 0.f;
-      d.y = __builtin_fmaf(vv.y, sa.y, sb.y) > 0.f ? d.y : 0.f;
-      d.z = __builtin_fmaf(vv.z, sa.z, sb.z) > 0.f ? d.z : 0.f;
-      d.w = __builtin_fmaf(vv.w, sa.w, sb.w) > 0.f ? d.w : 0.f;
-      float4 o;
-      o.x = ga.x * is.x * (d.x - a1.x * inv_rows - (vv.x - mu.x) * is.x * (a2.x * inv_rows));
-      o.y = ga.y * is.y * (d.y - a1.y * inv_rows - (vv.y - mu.y) * is.y * (a2.y * inv_rows));
-      o.z = ga.z * is.z * (d.z - a1.z * inv_rows - (vv.z - mu.z) * is.z * (a2.z * inv_rows));
-      o.w = ga.w * is.w * (d.w - a1.w * inv_rows - (vv.w - mu.w) * is.w * (a2.w * inv_rows));
-      if (dy_sinv) {
-        o.x *= dsc; o.y *= dsc; o.z *= dsc; o.w *= dsc;
-      }
-      Elem<TO>::st4(dy, (((long long)n * h + 2 * qa + pi) * w + 2 * qb + pj) * c4n + cq, o);
-    }
+  const bool scaled = dy_sinv != nullptr;                   // sp result: times 2^k (bn_dy_scale_kernel; exact)
+  const float dsc = scaled ? 1.f / *dy_sinv : 1.f;
+  pool_quad_gather(gp, am, y, n, qa, qb, cq, h, w, ho, wo, c4n, [=](long long px, float4 d, float4 v) {
+    d = mask_affine4(d, v, sa, sb);
+    float4 o = bn_dy(d, v, mu, is, ga, a1, a2, inv_rows);
+    if (scaled) o = mul4(o, dsc);
+    Elem<TO>::st4(dy, px, o);
+  });
 }
 
 // ---- eval mode: BatchNorm on the running statistics, backward in ONE streaming pass -----------------------------
@@ -1087,16 +1023,16 @@ __global__ __launch_bounds__(256) void bn_pool_bwd_apply_kernel(const T *__restr
 // dy needs no sum, so the train-mode pair (reduce, then an apply that waits for it) becomes one pass reading g, y (and
 // the mask) and writing dy; the sums leave per-(group, chunk, channel) partials in bn_bwd_reduce_kernel's layout
 // ([groups][chunks][2][c]) and bn_eval_bwd_finalize_kernel adds them in a fixed order.  The mask is the forward's:
-// relu_bits (bn_apply_bits), act > 0, or fma(y, mscale, mshift) > 0 with bn_eval_affine's scale / shift (bn_apply_kernel's
-// expression); none of them: no ReLU.  dy and dz_out may alias g (every element is read, then written, by one lane).
+// relu_bits (bn_apply_bits), act > 0, or relu_on(y, mscale, mshift) with bn_eval_affine's scale / shift (bn_math.h);
+// none of them: no ReLU.  dy and dz_out may alias g (every element is read, then written, by one lane).
 __device__ __forceinline__ void bn_eval_factors(const float *gamma, const float *rmean, const float *rvar, float eps, int cq,
                                                 float4 &mu, float4 &is, float4 &k) {
   const float4 ga = reinterpret_cast<const float4 *>(gamma)[cq], rm = reinterpret_cast<const float4 *>(rmean)[cq];
   const float4 rv = reinterpret_cast<const float4 *>(rvar)[cq];
-  const float4 sd = make_float4(sqrtf(rv.x + eps), sqrtf(rv.y + eps), sqrtf(rv.z + eps), sqrtf(rv.w + eps));
+  const float4 sd = map4([](float rv, float eps) { return sqrtf(rv + eps); }, rv, eps);
   mu = rm;
-  is = make_float4(1.f / sd.x, 1.f / sd.y, 1.f / sd.z, 1.f / sd.w);
-  k = make_float4(ga.x / sd.x, ga.y / sd.y, ga.z / sd.z, ga.w / sd.w);     // = bn_eval_affine_kernel's scale
+  is = map4([](float sd) { return 1.f / sd; }, sd);
+  k = map4([](float ga, float sd) { return ga / sd; }, ga, sd);     // = bn_eval_affine_kernel's scale
 }
 
 // grid = (chunks, column blocks, groups); thread = one float4 column group x one row lane (bn_bwd_reduce_kernel's shape)
@@ -1107,13 +1043,13 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float *g, const 
                                                           const float *__restrict__ rvar, float eps, long long rows,
                                                           long long rows_per_chunk, int c, int cwn, int cw, float *dy, float *dz_out,
                                                           float *__restrict__ partial, int chunks) {
-  __shared__ float4 sh[2][256];
+  __shared__ float4 sh[2][256][1];
   const int grp = blockIdx.z;
   const int rl = threadIdx.x / cw, cl = threadIdx.x % cw;
   const int nrl = 256 / cw;
   const int cq = blockIdx.y * cw + cl;
   const bool cok = cq < cwn;
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+  float4 s1 = zero4(), s2 = s1;
   if (cok) {
     float4 mu, is, k, ma = s1, mb = s1;
     bn_eval_factors(gamma, rmean, rvar, eps, cq, mu, is, k);
@@ -1129,36 +1065,18 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float *g, const 
       const long long off = gbase + r * cwn + cq;
       float4 d = reinterpret_cast<const float4 *>(g)[off];
       const float4 v = reinterpret_cast<const float4 *>(y)[off];
-      if (relu_bits) {
-        const unsigned m4 = relu_bits[off];
-        d.x = (m4 & 1u) ? d.x : 0.f;
-        d.y = (m4 & 2u) ? d.y : 0.f;
-        d.z = (m4 & 4u) ? d.z : 0.f;
-        d.w = (m4 & 8u) ? d.w : 0.f;
-      } else if (act) {
-        const float4 a = reinterpret_cast<const float4 *>(act)[off];
-        d.x = a.x > 0.f ? d.x : 0.f;
-        d.y = a.y > 0.f ? d.y : 0.f;
-        d.z = a.z > 0.f ? d.z : 0.f;
-        d.w = a.w > 0.f ? d.w : 0.f;
-      } else if (mscale) {
-        d.x = __builtin_fmaf(v.x, ma.x, mb.x) > 0.f ? d.x : 0.f;
-        d.y = __builtin_fmaf(v.y, ma.y, mb.y) > 0.f ? d.y : 0.f;
-        d.z = __builtin_fmaf(v.z, ma.z, mb.z) > 0.f ? d.z : 0.f;
-        d.w = __builtin_fmaf(v.w, ma.w, mb.w) > 0.f ? d.w : 0.f;
-      }
-      a1.x += d.x; a1.y += d.y; a1.z += d.z; a1.w += d.w;
-      a2.x += d.x * ((v.x - mu.x) * is.x);
-      a2.y += d.y * ((v.y - mu.y) * is.y);
-      a2.z += d.z * ((v.z - mu.z) * is.z);
-      a2.w += d.w * ((v.w - mu.w) * is.w);
+      if (relu_bits) d = mask_bits4(d, relu_bits[off]);
+      else if (act) d = mask_act4(d, reinterpret_cast<const float4 *>(act)[off]);
+      else if (mscale) d = mask_affine4(d, v, ma, mb);
+      acc4(a1, d);
+      acc4_xhat(a2, d, v, mu, is);
       if (dz_out) reinterpret_cast<float4 *>(dz_out)[off] = d;
-      reinterpret_cast<float4 *>(dy)[off] = make_float4(k.x * d.x, k.y * d.y, k.z * d.z, k.w * d.w);
+      reinterpret_cast<float4 *>(dy)[off] = mul4(k, d);
     };
     constexpr int U = 4;          // rows in flight per thread (bn_bwd_reduce_kernel's count for fp32)
     float4 t1[U - 1], t2[U - 1];
 #pragma unroll
-    for (int u = 0; u < U - 1; ++u) t1[u] = t2[u] = make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int u = 0; u < U - 1; ++u) t1[u] = t2[u] = zero4();
     long long r = r0 + rl;
     for (; r + (U - 1) * (long long)nrl < r1; r += U * (long long)nrl) {
       row(r, s1, s2);
@@ -1166,24 +1084,10 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float *g, const 
       for (int u = 1; u < U; ++u) row(r + u * (long long)nrl, t1[u - 1], t2[u - 1]);
     }
     for (; r < r1; r += nrl) row(r, s1, s2);
-    s1.x += t1[0].x + (t1[1].x + t1[2].x); s1.y += t1[0].y + (t1[1].y + t1[2].y);
-    s1.z += t1[0].z + (t1[1].z + t1[2].z); s1.w += t1[0].w + (t1[1].w + t1[2].w);
-    s2.x += t2[0].x + (t2[1].x + t2[2].x); s2.y += t2[0].y + (t2[1].y + t2[2].y);
-    s2.z += t2[0].z + (t2[1].z + t2[2].z); s2.w += t2[0].w + (t2[1].w + t2[2].w);
+    acc4(s1, add4(t1[0], add4(t1[1], t1[2])));
+    acc4(s2, add4(t2[0], add4(t2[1], t2[2])));
   }
-  sh[0][threadIdx.x] = s1;
-  sh[1][threadIdx.x] = s2;
-  __syncthreads();
-  if (rl == 0 && cok) {
-    for (int j = 1; j < nrl; ++j) {
-      const float4 a = sh[0][j * cw + cl], b = sh[1][j * cw + cl];
-      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
-      s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
-    }
-    float4 *p = reinterpret_cast<float4 *>(partial + (((long long)grp * chunks + blockIdx.x) * 2) * c);
-    p[cq] = s1;
-    p[c / 4 + cq] = s2;
-  }
+  bn_reduce_tail(sh, &s1, &s2, nullptr, cok, nrl, cw, rl, cl, cq, partial, grp, chunks, c, c / 4);
 }
 
 // The stem tail in eval mode: max-pool backward through argmax, the ReLU mask from y, then dy = gamma invstd_r dz - the
@@ -1205,7 +1109,7 @@ __global__ __launch_bounds__(256) void bn_pool_eval_bwd_kernel(const float *__re
   bn_eval_factors(gamma, rmean, rvar, eps, cq, mu, is, k);
   const float4 sa = reinterpret_cast<const float4 *>(mscale)[(long long)grp * c4n + cq];
   const float4 sb = reinterpret_cast<const float4 *>(mshift)[(long long)grp * c4n + cq];
-  float4 s1 = make_float4(0.f, 0.f, 0.f, 0.f), s2 = s1;
+  float4 s1 = zero4(), s2 = s1;
   const long long items = (long long)n_per_group * hq * wq * c4n;
   const long long stride = (long long)gridDim.x * 256;
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < items; i += stride) {
@@ -1214,73 +1118,21 @@ __global__ __launch_bounds__(256) void bn_pool_eval_bwd_kernel(const float *__re
     const long long line = q / wq;
     const int qa = (int)(line % hq);
     const long long n = (long long)grp * n_per_group + line / hq;
-    uchar4 wk[2][2];
-    float4 wg[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; ++a)
-#pragma unroll
-      for (int b = 0; b < 2; ++b) {
-        const bool ok = qa + a < ho && qb + b < wo;
-        const long long o = ((n * ho + qa + a) * wo + qb + b) * c4n + cq;
-        wk[a][b] = ok ? am[o] : make_uchar4(255, 255, 255, 255);
-        wg[a][b] = ok ? reinterpret_cast<const float4 *>(gp)[o] : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-    float4 v[2][2];
-    bool pok[2][2];
-#pragma unroll
-    for (int pi = 0; pi < 2; ++pi)
-#pragma unroll
-      for (int pj = 0; pj < 2; ++pj) {
-        pok[pi][pj] = 2 * qa + pi < h && 2 * qb + pj < w;
-        v[pi][pj] = pok[pi][pj] ? reinterpret_cast<const float4 *>(y)[((n * h + 2 * qa + pi) * w + 2 * qb + pj) * c4n + cq]
-                                : make_float4(0.f, 0.f, 0.f, 0.f);
-      }
-#pragma unroll
-    for (int pi = 0; pi < 2; ++pi)
-#pragma unroll
-      for (int pj = 0; pj < 2; ++pj) {
-        if (!pok[pi][pj]) continue;
-        // pixel (2 qa + pi, 2 qb + pj) inside window (qa + a, qb + b): kh = pi + 1 - 2 a, kw = pj + 1 - 2 b
-        float4 d = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-        for (int a = 0; a < 2; ++a) {
-          const int kh = pi + 1 - 2 * a;
-          if (kh < 0) continue;
-#pragma unroll
-          for (int b = 0; b < 2; ++b) {
-            const int kw = pj + 1 - 2 * b;
-            if (kw < 0) continue;
-            const unsigned char me = (unsigned char)(kh * 3 + kw);
-            const uchar4 kk = wk[a][b];
-            const float4 gg = wg[a][b];
-            if (kk.x == me) d.x += gg.x;
-            if (kk.y == me) d.y += gg.y;
-            if (kk.z == me) d.z += gg.z;
-            if (kk.w == me) d.w += gg.w;
-          }
-        }
-        const float4 vv = v[pi][pj];
-        d.x = __builtin_fmaf(vv.x, sa.x, sb.x) > 0.f ? d.x : 0.f;
-        d.y = __builtin_fmaf(vv.y, sa.y, sb.y) > 0.f ? d.y : 0.f;
-        d.z = __builtin_fmaf(vv.z, sa.z, sb.z) > 0.f ? d.z : 0.f;
-        d.w = __builtin_fmaf(vv.w, sa.w, sb.w) > 0.f ? d.w : 0.f;
-        s1.x += d.x; s1.y += d.y; s1.z += d.z; s1.w += d.w;
-        s2.x += d.x * ((vv.x - mu.x) * is.x);
-        s2.y += d.y * ((vv.y - mu.y) * is.y);
-        s2.z += d.z * ((vv.z - mu.z) * is.z);
-        s2.w += d.w * ((vv.w - mu.w) * is.w);
-        reinterpret_cast<float4 *>(dy)[((n * h + 2 * qa + pi) * w + 2 * qb + pj) * c4n + cq] =
-            make_float4(k.x * d.x, k.y * d.y, k.z * d.z, k.w * d.w);
-      }
+    pool_quad_gather(gp, am, y, n, qa, qb, cq, h, w, ho, wo, c4n, [=](long long px, float4 d, float4 v, float4 &s1, float4 &s2) {
+      d = mask_affine4(d, v, sa, sb);
+      acc4(s1, d);
+      acc4_xhat(s2, d, v, mu, is);
+      reinterpret_cast<float4 *>(dy)[px] = mul4(k, d);
+    }, s1, s2);
   }
+  // (not bn_reduce_tail: this kernel has no 256 / c4n, and a strided fold over the lanes j = lane + c4n, + 2 c4n, ...)
   sh[0][threadIdx.x] = s1;
   sh[1][threadIdx.x] = s2;
   __syncthreads();
   if (threadIdx.x < c4n) {
     for (int j = threadIdx.x + c4n; j < 256; j += c4n) {
-      const float4 a = sh[0][j], b = sh[1][j];
-      s1.x += a.x; s1.y += a.y; s1.z += a.z; s1.w += a.w;
-      s2.x += b.x; s2.y += b.y; s2.z += b.z; s2.w += b.w;
+      acc4(s1, sh[0][j]);
+      acc4(s2, sh[1][j]);
     }
     float4 *p = reinterpret_cast<float4 *>(partial + (((long long)grp * gridDim.x + blockIdx.x) * 2) * (4 * c4n));
     p[cq] = s1;
@@ -1346,6 +1198,40 @@ static int grid_for(long long n4) {
   if (b > 4096) b = 4096;      // thinner grids (1024 / 2048) were tried to leave wave slots to the wgrad stream: no gain
   if (b < 1) b = 1;
   return (int)b;
+}
+
+// The geometry of the reduce-type passes over [rows][c]: cwn 16-byte column groups per row (W float4 each), column
+// blocks of cw = min(cwn, 256) of them - 256 / cw row lanes per workgroup, so cw must divide 256 - and the rows cut
+// into `chunks` ranges of rows_per_chunk.
+struct ReduceGeom {
+  int cwn, cw, chunks;
+  long long rows_per_chunk;
+};
+static int reduce_geometry(const char *who, int groups, long long rows, int c, int W, ReduceGeom &g) {
+  g.cwn = c / 4 / W;
+  g.cw = g.cwn < 256 ? g.cwn : 256;
+  MVG_REQUIRE(256 % g.cw == 0, "%s: c/%d must divide 256 or be a multiple of it (c=%d)", who, 4 * W, c);
+  g.chunks = bwd_chunks(groups, rows, c);
+  g.rows_per_chunk = (rows + g.chunks - 1) / g.chunks;
+  return 0;
+}
+
+// The ReLU mask of a backward pass comes ONE way: the activation, the bits bn_apply recorded, or y with (scale, shift).
+static int require_one_mask(const char *who, const char *ways, const void *act, const void *relu_bits, const float *relu_scale,
+                            const float *relu_shift) {
+  MVG_REQUIRE((act ? 1 : 0) + (relu_bits ? 1 : 0) + (relu_scale ? 1 : 0) <= 1, "%s: give the ReLU mask %s", who, ways);
+  MVG_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "%s: relu_scale and relu_shift go together", who);
+  return 0;
+}
+
+// *dy_sinv of a unit whose dy goes out in sp, unless the reduce pass / the fused backward-data launch left it already
+// (they do when they are given gamma)
+static int ensure_dy_scale(int ready, const float *gamma, const float *invstd, const float *s1, const float *s2, const float *mx, int groups,
+                           int c, long long rows, float *dy_sinv, hipStream_t st) {
+  if (ready) return 0;
+  hipLaunchKernelGGL(bn_dy_scale_kernel, dim3(1), dim3(1024), 0, st, gamma, invstd, s1, s2, mx, groups, c, 1.0f / (float)rows,
+                     sqrtf((float)rows), dy_sinv);
+  return check_launch("bn_dy_scale");
 }
 
 int bn_bwd_finalize_launch(const float *partial, int groups, int chunks, int c, float *s1, float *s2, float *dgamma,
@@ -1457,24 +1343,21 @@ static int bn_bwd_reduce_impl(const T *g, const T *act, const T *y, const float 
                               float *s1, float *s2, float *dgamma, float *dbeta, int accumulate, float *workspace, T *dz_out,
                               void *stream, const uint8_t *relu_bits = nullptr, float *mx = nullptr, const float *gamma = nullptr,
                               float *dy_sinv = nullptr) {
-  MVG_REQUIRE(!(act && relu_scale) && !(relu_bits && (act || relu_scale)),
-              "bn_bwd_reduce: give the ReLU mask ONE way: act, (relu_scale, relu_shift) or relu_bits");
-  MVG_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "bn_bwd_reduce: relu_scale and relu_shift go together");
+  if (int e = require_one_mask("bn_bwd_reduce", "ONE way: act, (relu_scale, relu_shift) or relu_bits", act, relu_bits, relu_scale, relu_shift))
+    return e;
   MVG_REQUIRE(c % 4 == 0, "bn_bwd_reduce: c %% 4 != 0");
   MVG_REQUIRE(workspace != nullptr, "bn_bwd_reduce: workspace required");
   hipStream_t st = (hipStream_t)stream;
   constexpr int W = Elem<T>::W;
   MVG_REQUIRE(c % (4 * W) == 0, "bn_bwd_reduce: c must be a multiple of %d", 4 * W);
-  const int c4n = c / 4 / W;                 // 16-byte column groups per row
-  const int cw = c4n < 256 ? c4n : 256;
-  MVG_REQUIRE(256 % cw == 0, "bn_bwd_reduce: c/%d must divide 256 or be a multiple of it (c=%d)", 4 * W, c);
-  const int chunks = bwd_chunks(groups, rows_per_group, c);
-  const long long rpc = (rows_per_group + chunks - 1) / chunks;
+  ReduceGeom q;
+  if (int e = reduce_geometry("bn_bwd_reduce", groups, rows_per_group, c, W, q)) return e;
   ProfScope ps(MVG_K_BN_BWD_REDUCE, st, 0.0, Elem<T>::kBytes * groups * (double)rows_per_group * c * ((act ? 3 : 2) + (dz_out ? 1 : 0)));
-  hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(chunks, ceil_div(c4n, cw), groups), dim3(256), 0, st, g, act, y, mean, invstd,
-                     relu_scale, relu_shift, (long long)rows_per_group, rpc, c, c4n, cw, workspace, chunks, dz_out, relu_bits, mx ? 3 : 2);
+  hipLaunchKernelGGL(bn_bwd_reduce_kernel<T>, dim3(q.chunks, ceil_div(q.cwn, q.cw), groups), dim3(256), 0, st, g, act, y, mean, invstd,
+                     relu_scale, relu_shift, (long long)rows_per_group, q.rows_per_chunk, c, q.cwn, q.cw, workspace, q.chunks, dz_out, relu_bits,
+                     mx ? 3 : 2);
   if (check_launch("bn_bwd_reduce")) return 1;
-  return bn_bwd_finalize_launch(workspace, groups, chunks, c, s1, s2, dgamma, dbeta, accumulate, st, mx, nullptr, nullptr, gamma, invstd,
+  return bn_bwd_finalize_launch(workspace, groups, q.chunks, c, s1, s2, dgamma, dbeta, accumulate, st, mx, nullptr, nullptr, gamma, invstd,
                                 (long long)rows_per_group, dy_sinv);
 }
 
@@ -1482,8 +1365,7 @@ template <typename T, typename TO = T>
 static int bn_bwd_apply_impl(const T *g, const T *act, const T *y, const float *mean, const float *invstd, const float *gamma,
                              const float *s1, const float *s2, const float *relu_scale, const float *relu_shift, int groups,
                              int64_t rows_per_group, int c, TO *dy, T *dz_out, void *stream) {
-  MVG_REQUIRE(!(act && relu_scale), "bn_bwd_apply: give the ReLU mask either as act or as (relu_scale, relu_shift)");
-  MVG_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "bn_bwd_apply: relu_scale and relu_shift go together");
+  if (int e = require_one_mask("bn_bwd_apply", "either as act or as (relu_scale, relu_shift)", act, nullptr, relu_scale, relu_shift)) return e;
   MVG_REQUIRE(c % 4 == 0, "bn_bwd_apply: c %% 4 != 0");
   hipStream_t st = (hipStream_t)stream;
   const long long n4 = rows_per_group * (c / 4);
@@ -1521,12 +1403,12 @@ static int bn_relu_maxpool_bwd_reduce_impl(const T *g_pooled, const uint8_t *arg
   MVG_REQUIRE(workspace != nullptr, "bn_relu_maxpool_bwd_reduce: workspace required");
   hipStream_t st = (hipStream_t)stream;
   const long long rows = (long long)n_per_group * h * w;
-  const int c4n = c / 4;
-  const int cw = c4n < 256 ? c4n : 256;
-  MVG_REQUIRE(256 % cw == 0, "bn_relu_maxpool_bwd_reduce: c/4 must divide 256 or be a multiple of it (c=%d)", c);
+  ReduceGeom q;
+  if (int e = reduce_geometry("bn_relu_maxpool_bwd_reduce", groups, rows, c, 1, q)) return e;
+  const int c4n = q.cwn, cw = q.cw;
   // chunk = whole image lines; never more chunks than mvg_bn_bwd_workspace_floats(groups, rows, c) sizes
   const int lines = n_per_group * ho;                 // pooled lines
-  int chunks = bwd_chunks(groups, rows, c);
+  int chunks = q.chunks;
   if (chunks > lines) chunks = lines;
   const int lpc = (lines + chunks - 1) / chunks;
   chunks = (lines + lpc - 1) / lpc;
@@ -1666,11 +1548,7 @@ int mvg_bn_bwd_apply_split(const float *g, const float *y, const float *mean, co
   hipStream_t st = (hipStream_t)stream;
   const long long n8 = rows_per_group * (c / 8);
   ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0, 8.0 * groups * (double)n8 * (8.0 + SP_BYTES));
-  if (!dy_sinv_ready) {          // (the reduce pass / the fused backward-data launch left *dy_sinv when it was given gamma)
-    hipLaunchKernelGGL(bn_dy_scale_kernel, dim3(1), dim3(1024), 0, st, gamma, invstd, s1, s2, mx, groups, c, 1.0f / (float)rows_per_group,
-                       sqrtf((float)rows_per_group), dy_sinv);
-    if (check_launch("bn_dy_scale")) return 1;
-  }
+  if (ensure_dy_scale(dy_sinv_ready, gamma, invstd, s1, s2, mx, groups, c, rows_per_group, dy_sinv, st)) return 1;
   hipLaunchKernelGGL(bn_bwd_apply_sp_kernel, dim3(grid_for(n8), groups), dim3(256), 0, st, g, y, mean, invstd, gamma, s1, s2,
                      relu_scale, relu_shift, n8, 1.0f / (float)rows_per_group, c / 8, c, (sp_t *)dy_sp, dy_sinv);
   return check_launch("bn_bwd_apply_split");
@@ -1700,12 +1578,7 @@ int mvg_bn_relu_maxpool_bwd_apply_split(const float *g_pooled, const uint8_t *ar
                                         const float *s1, const float *s2, int groups, int n_per_group, int h, int w, int c, int ho,
                                         int wo, void *dy_sp, const float *mx, float *dy_sinv, int dy_sinv_ready, void *stream) {
   MVG_REQUIRE(c % 8 == 0 && mx && dy_sinv, "bn_relu_maxpool_bwd_apply_split: c %% 8 != 0, or mx / dy_sinv missing");
-  const long long rows = (long long)n_per_group * h * w;
-  if (!dy_sinv_ready) {
-    hipLaunchKernelGGL(bn_dy_scale_kernel, dim3(1), dim3(1024), 0, (hipStream_t)stream, gamma, invstd, s1, s2, mx, groups, c,
-                       1.0f / (float)rows, sqrtf((float)rows), dy_sinv);
-    if (check_launch("bn_dy_scale")) return 1;
-  }
+  if (ensure_dy_scale(dy_sinv_ready, gamma, invstd, s1, s2, mx, groups, c, (long long)n_per_group * h * w, dy_sinv, (hipStream_t)stream)) return 1;
   return bn_relu_maxpool_bwd_apply_impl<float, sp_t>(g_pooled, argmax, y, mean, invstd, gamma, scale, shift, s1, s2, groups,
                                                      n_per_group, h, w, c, ho, wo, (sp_t *)dy_sp, stream, dy_sinv);
 }
@@ -1724,24 +1597,21 @@ int mvg_bn_eval_bwd(const float *g, const float *act, const uint8_t *relu_bits, 
                     const float *relu_shift, const float *gamma, const float *running_mean, const float *running_var, float eps,
                     int groups, int64_t rows_per_group, int c, float *dy, float *dz_out, float *dgamma, float *dbeta,
                     int accumulate, float *workspace, void *stream) {
-  MVG_REQUIRE((act ? 1 : 0) + (relu_bits ? 1 : 0) + (relu_scale ? 1 : 0) <= 1,
-              "bn_eval_bwd: give the ReLU mask ONE way: act, relu_bits or (relu_scale, relu_shift)");
-  MVG_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "bn_eval_bwd: relu_scale and relu_shift go together");
+  if (int e = require_one_mask("bn_eval_bwd", "ONE way: act, relu_bits or (relu_scale, relu_shift)", act, relu_bits, relu_scale, relu_shift))
+    return e;
   MVG_REQUIRE(g && y && dy && gamma && running_mean && running_var && workspace,
               "bn_eval_bwd: g, y, dy, gamma, running_mean, running_var and workspace are required");
   MVG_REQUIRE(dz_out == nullptr || dz_out != dy, "bn_eval_bwd: dz_out and dy must be different buffers");
   MVG_REQUIRE(groups > 0 && groups < 65536 && rows_per_group > 0 && c > 0 && c % 4 == 0, "bn_eval_bwd: bad sizes");
-  const int c4n = c / 4;
-  const int cw = c4n < 256 ? c4n : 256;
-  MVG_REQUIRE(256 % cw == 0, "bn_eval_bwd: c/4 must divide 256 or be a multiple of it (c=%d)", c);
+  ReduceGeom q;
+  if (int e = reduce_geometry("bn_eval_bwd", groups, rows_per_group, c, 1, q)) return e;
+  const int c4n = q.cwn, cw = q.cw, chunks = q.chunks;
   hipStream_t st = (hipStream_t)stream;
-  const int chunks = bwd_chunks(groups, rows_per_group, c);
-  const long long rpc = (rows_per_group + chunks - 1) / chunks;
   ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0,
                4.0 * groups * (double)rows_per_group * c * (3 + (act ? 1 : 0) + (dz_out ? 1 : 0)) +
                    (relu_bits ? groups * (double)rows_per_group * c4n : 0.0));
   hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(chunks, ceil_div(c4n, cw), groups), dim3(256), 0, st, g, act, y, relu_bits, relu_scale,
-                     relu_shift, gamma, running_mean, running_var, eps, (long long)rows_per_group, rpc, c, c4n, cw, dy, dz_out, workspace,
+                     relu_shift, gamma, running_mean, running_var, eps, (long long)rows_per_group, q.rows_per_chunk, c, c4n, cw, dy, dz_out, workspace,
                      chunks);
   if (check_launch("bn_eval_bwd")) return 1;
   if (!dgamma && !dbeta) return 0;
