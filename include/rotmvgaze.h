@@ -424,6 +424,16 @@ int mvg_cast_weights_bf16(const mvg_conv_desc *d, const float *w, int cin_src, v
 int mvg_conv_fprop_bf16(const mvg_conv_desc *d, const void *x, const void *wgt, void *y, const float *bias,
                         int relu, float *stats, void *stream);
 int mvg_conv_stats_partials_bf16(const mvg_conv_desc *d, int32_t *out_rows_per_partial);
+/* Inference on the bf16 storage path (like mvg_conv_fprop_affine / mvg_conv_fprop_split_affine): BatchNorm on its running
+ * statistics folded into the conv epilogue,
+ *     out = bf16( [relu]( acc * scale[cout] + shift[cout] [+ residual] ) )
+ * acc = the fp32 accumulator; scale / shift fp32 from mvg_bn_eval_affine (one row: every group uses the same); residual
+ * (may be NULL) bf16, shaped like out; the ReLU follows the add; ONE rounding, at the store - no raw conv output, no
+ * mvg_bn_apply_bf16 pass.  Same shapes and kernel choice as mvg_conv_fprop_bf16, in instantiations of their own (the
+ * training kernels are unchanged).  With scale = 1, shift = 0, no residual, no ReLU the result equals
+ * mvg_conv_fprop_bf16's as values. */
+int mvg_conv_fprop_bf16_affine(const mvg_conv_desc *d, const void *x, const void *wgt, void *out, const float *scale,
+                               const float *shift, const void *residual, int relu, void *stream);
 /* like mvg_conv_dgrad; wgt_crsk = the transposed bf16 weights; mask/addend (bf16) like dx */
 int mvg_conv_dgrad_bf16(const mvg_conv_desc *d, const void *dy, const void *wgt_crsk, void *dx,
                         const void *mask, const void *addend, void *stream);
@@ -501,6 +511,12 @@ int mvg_avgpool_fwd_bf16(const uint16_t *x, float *y, int n, int hw, int c, void
 int mvg_avgpool_bwd_bf16(const float *dy, uint16_t *dx, int n, int hw, int c, void *stream);
 /* fp32 NCHW images (rot_mv.py:188-189) -> bf16 NHWC with the channels zero-padded to 8 */
 int mvg_nchw_to_nhwc8_bf16(const float *src, uint16_t *dst, int n, int c, int h, int w, void *stream);
+/* mvg_preprocess_u8hwc_resize (h == oh && w == ow: mvg_preprocess_u8hwc) straight to the bf16 stem's input: the same
+ * arithmetic (one device function serves both), the result rounded once to bf16 and stored NHWC8, dst [n][oh][ow][8] with
+ * channels 3..7 zero - bit for bit what mvg_nchw_to_nhwc8_bf16 makes of the fp32 kernel's output.  One launch per view. */
+int mvg_preprocess_u8hwc_resize_bf16(const uint8_t *src, uint16_t *dst, int n, int h, int w, int oh, int ow, float mean0,
+                                     float mean1, float mean2, float std0, float std1, float std2, int swap_rb,
+                                     void *stream);
 
 /* ---- "split" operands: fp32-accurate convolutions on the fp16 matrix cores (csrc/conv_split.hip) ----------------
  * An fp32 tensor in "sp" format holds every value v - times a per-tensor power-of-two scale 2^k chosen by its producer -

@@ -151,6 +151,7 @@ SIGNATURES = {
     "mvg_cast_weights_bf16": (_I, [_D, _P, _I, _P, _P, _P]),
     "mvg_conv_fprop_bf16": (_I, [_D, _P, _P, _P, _P, _I, _P, _P]),
     "mvg_conv_stats_partials_bf16": (_I, [_D, C.POINTER(C.c_int32)]),
+    "mvg_conv_fprop_bf16_affine": (_I, [_D, _P, _P, _P, _P, _P, _P, _I, _P]),
     "mvg_conv_dgrad_bf16": (_I, [_D, _P, _P, _P, _P, _P, _P]),
     "mvg_conv_dgrad_bn_partials_bf16": (_I, [_D]),
     "mvg_conv_dgrad_bf16_bnreduce": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P]),
@@ -174,6 +175,7 @@ SIGNATURES = {
     "mvg_avgpool_fwd_bf16": (_I, [_P, _P, _I, _I, _I, _P]),
     "mvg_avgpool_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _P]),
     "mvg_nchw_to_nhwc8_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "mvg_preprocess_u8hwc_resize_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mvg_mt19937_seed": (_I, [_P, C.c_uint64]),
     "mvg_pair_index_build": (_I64, [_P, _P, _I, _I, _P, _I64]),
 }

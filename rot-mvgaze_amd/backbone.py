@@ -55,6 +55,9 @@ class _Unit:
 
 class Backbone:
     _guard_scale = 1          # tests raise it to exercise the 2 GiB guard of the split path without a 2 GiB tensor
+    # tests: a list here makes an inference forward (no tape) append, per unit, (spec name, input, residual, output) - for the
+    # stem (spec name, input, raw conv output y, pooled map) - references, no copies
+    _debug_units: Optional[list] = None
 
     def __init__(self, depth: int, params: Dict[str, Tensor], prefix: str = "_feat_extractor.0."):
         self.spec: BackboneSpec = backbone_spec(depth, prefix)
@@ -93,6 +96,12 @@ class Backbone:
         # d(loss)/d(img) (the backward-data launch runs on the fp32 kernel) or the width is odd.
         self.stem_rowwindow = True
         self.split_eval = True      # inference forward on the split kernels too
+        # bf16 path, inference (no tape): BatchNorm on the running statistics, the residual and the ReLU folded into the conv
+        # epilogue (mvg_conv_fprop_bf16_affine) - every activation written once and rounded once - the downsample branch
+        # stored normalised, and the bf16 weight copies kept between calls.  (attribute False: the training-shaped launches -
+        # conv, bn_apply - and a weight cast per call.)
+        self.bf16_fold_eval = True
+        self._wprep_infer_ok = False          # the persistent bf16 copies hold _wprep_versions and may serve the next inference call
         self._wk_cache: Dict[str, tuple] = {}     # inference: conv name -> (data_ptr, version, sp weights)
         # training: one launch per step makes every conv's bf16 / sp weight copies
         self.batch_weight_prep = True
@@ -120,10 +129,13 @@ class Backbone:
             f"{c.name}.weight must be channels_last (KRSC)"
         return w.detach()
 
-    def _prepare_weights(self, dev) -> Dict[str, tuple]:
+    def _prepare_weights(self, dev, reuse: bool = False) -> Dict[str, tuple]:
         """The per-step copies of every conv's weights the bf16 / split kernels read (KRSC for fprop, CRSK for
         backward-data), made by ONE launch: destination buffers and the launch's device-resident table of
-        (source, destinations, shape) records are built once per parameter placement and reused every step."""
+        (source, destinations, shape) records are built once per parameter placement and reused every step.
+        reuse (bf16 inference): no launch when the buffers already hold these parameters - same placement, same version
+        counters as _wprep_versions, and nothing invalidated them since (invalidate_weight_cache, train(), any other
+        forward).  The buffers then hold exactly what _wprep_versions says, as the tapes that point into them expect."""
         mode = 0 if self.bf16 else 1
         stem_rw = self._stem_rw
         convs = [c for c in self.spec.all_convs() if not (mode == 1 and c.cin == 3 and not stem_rw)]
@@ -169,7 +181,11 @@ class Backbone:
                              c.cin | (cin_pad << 32), wstat[ci].data_ptr()])
             table = torch.tensor(rows, dtype=torch.int64).to(dev)            # once per placement (a host-to-device copy)
             self._wprep_state = (key, out, table, len(rows), mode, wstat)
+        elif (reuse and self._wprep_infer_ok and
+              self._wprep_versions == tuple(self.p[c.name + ".weight"]._version for c in self.spec.all_convs())):
+            return self._wprep_state[1]
         _, out, table, n, mode, wstat = self._wprep_state
+        self._wprep_infer_ok = reuse
         if mode == 1:
             wstat.zero_()                                  # the max |w| slots are atomicMax targets
             if self._stem_w8 is not None:
@@ -185,12 +201,13 @@ class Backbone:
         return out
 
     def invalidate_weight_cache(self):
-        """Forget the inference path's cached sp copies of the conv weights.  The cache is keyed on each parameter's
+        """Forget the inference path's cached sp (bf16 path: bf16) copies of the conv weights.  The cache is keyed on each parameter's
         (data_ptr, version counter); writes that bypass the counter - ``p.data.copy_()`` / ``p.data.mul_()`` (EMA,
         clipping) or writes to ``model.param_arena()`` - must be followed by this call (or by
         ``torch.autograd.graph.increment_version(p)``), otherwise ``torch.no_grad()`` inference keeps using the old
         weights.  ``model.train()`` and every training forward clear it too."""
         self._wk_cache.clear()
+        self._wprep_infer_ok = False          # bf16 path: the next inference call casts the weights again
 
     def bn_count_buffers(self) -> List[Tensor]:
         return [self.p[c.bn + ".num_batches_tracked"] for c in self.spec.all_convs()]
@@ -279,6 +296,13 @@ class Backbone:
                 pooled, am = self._pool_plain(y, G, N, d.ho, d.wo, c.cout)
                 return (ops.split_f32(pooled), am) if sp_eval else (pooled, am)
             return y
+        elif tape is None and bf and self.bf16_fold_eval and not pool:
+            # bf16 inference: the same fold on the bf16 kernels - y is the unit's output, written once, rounded once
+            ops.bn_eval_affine(1, c.cout, gamma, beta, rm, rv, BN_EPS, scale[:1], shift[:1])
+            ops.conv_fprop_bf16_affine(d, x, w, y, scale[0], shift[0], residual, relu)
+            if self._debug_units is not None:
+                self._debug_units.append((c.name, x, residual, y))
+            return y
         else:
             fprop(None)
             ops.bn_eval_affine(G, c.cout, gamma, beta, rm, rv, BN_EPS, scale, shift)
@@ -304,6 +328,8 @@ class Backbone:
             else:
                 out = torch.empty(G, N, hp, wp_, c.cout, dtype=self.act_dtype, device=dev)
                 ops.bn_relu_maxpool_fwd(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
+            if self._debug_units is not None and tape is None and not training:
+                self._debug_units.append((c.name, x, y, out))
         elif sp_out:
             out = ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev)
             bits = ops.bn_apply_split(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine,
@@ -354,8 +380,9 @@ class Backbone:
             B, C, H, W = imgs[0].shape
         assert C == 3
         dev = imgs[0].device
-        if self.bf16 and raw:
-            raise NotImplementedError("raw uint8 input with the bf16 path: normalise to fp32 NCHW first")
+        if self.bf16 and raw and (training or keep_tape):
+            raise NotImplementedError("raw uint8 input with the bf16 path is served for inference only (model.eval() under "
+                                      "torch.no_grad()): for training steps normalise to fp32 NCHW first")
         # The split kernels address one view of an sp tensor (4 bytes per element) with 32-bit offsets: the largest one
         # (layer1's output: (H/4) x (W/4) x 64 or 256 channels per image) must stay below 2 GiB, or this call runs on the
         # fp32-MFMA kernels (64-bit row offsets there; B < 668 per view at 224 x 224 with ResNet-50)
@@ -385,6 +412,8 @@ class Backbone:
                     ops.stem_rowwindow_bf16(im.detach().contiguous(), x0[v])
                 else:
                     ops.stem_rowwindow_split_nchw(im.detach().contiguous(), x0[v])
+            elif self.bf16 and raw:             # inference: one launch per view, no fp32 image in between
+                ops.preprocess_u8hwc_resize_bf16(im.contiguous(), x0[v], B, Hin, Win, H, W, IMAGE_MEAN, IMAGE_STD, input_bgr)
             elif self.bf16:
                 assert im.dtype == torch.float32
                 ops.nchw_to_nhwc8_bf16(im.detach().contiguous(), x0[v], B, 3, H, W)
@@ -397,9 +426,9 @@ class Backbone:
             x0 = ops.stem_rowwindow_split(x0)
         self._wprep = None
         if training:
-            self._wk_cache.clear()               # the weights are about to change: drop the inference copies
+            self.invalidate_weight_cache()       # the weights are about to change: drop the inference copies
         if self.batch_weight_prep and (self.bf16 or (self._split_now and training)):
-            self._wprep = self._prepare_weights(dev)
+            self._wprep = self._prepare_weights(dev, reuse=self.bf16 and self.bf16_fold_eval and not training and not keep_tape)
         tape: Optional[dict] = {"units": [], "blocks": [], "V": V, "B": B} if keep_tape else None
         if keep_tape and self._wprep is not None:
             tape["wprep_versions"] = self._wprep_versions
@@ -420,7 +449,7 @@ class Backbone:
             ds_idx = None
             ident_affine = None
             if blk.downsample is not None:
-                if training or keep_tape or self.bf16:
+                if training or keep_tape or (self.bf16 and not self.bf16_fold_eval):
                     # raw downsample conv output + its (scale, shift): normalised inside the last unit's bn_apply
                     identity, ident_affine = self._unit_fwd(blk.downsample, x, V, B, Hc, Wc, training, False, None, ulist,
                                                             defer_apply=True)

@@ -32,9 +32,10 @@ __device__ __forceinline__ void ld8(const float *p, float (&v)[8]) {       // 8 
 // column = lane & 31, row = (e & 3) + 8 * (e >> 2) + 4 * (lane >> 5)).
 // BNF: the kernel carries the fused BatchNorm-backward reduce (IgemmParams::bn_*); its shared memory then holds
 // bf16_epilogue_bytes<...>() bytes: the staging tile, the row offsets and 4 * BN floats of per-channel constants.
-template <int BM, int BN, int PASSES, bool BNF>
+// AFF: the inference form of the bf16 storage kernels (below); the per-channel scale and shift wait behind the row offsets.
+template <int BM, int BN, int PASSES, bool BNF, bool AFF = false>
 constexpr int bf16_epilogue_bytes() {
-  return (BM / PASSES) * (BN + 4) * 4 + BM * 4 + (BNF ? 4 * BN * 4 : 0);
+  return (BM / PASSES) * (BN + 4) * 4 + BM * 4 + (BNF ? 4 * BN * 4 : 0) + (AFF ? 2 * BN * 4 : 0);
 }
 
 // LIN (split kernels running a Linear layer of the fusion block): the epilogue can also (i) leave max |stored value| of an
@@ -43,8 +44,12 @@ constexpr int bf16_epilogue_bytes() {
 // |acc| <= ktotal * 2^30 in the operands' scaled units, so |result| <= ktotal * 2^30 * osc + max |bias| - with
 // *p.out_sinv = 2^-k for the consumers (IgemmParams::out_sinv / bias_absmax).
 // WGN: waves along the tile's columns (2; 1 for the 256 x 64 tile of the split kernels: four wave rows of 64 x 64).
+// AFF (bf16 storage, forward, inference): out = bf16([relu](acc * scale[c] + shift[c] [+ residual])) with p.scale, p.bias as
+// scale / shift and p.addend as the bf16 residual - the ReLU FOLLOWS the add and the only rounding is the store's.  Its own
+// instantiations: the training kernels carry none of it.  The 2 * BN constants wait in LDS behind the row offsets
+// (bf16_epilogue_bytes<.., AFF>) and are re-read per iteration, like the fused reduce's, not held across the store loop.
 template <int BM, int BN, int WGM, bool DGRAD, bool F32IO, int PASSES = 1, bool ACC16 = false, bool BNF = false, bool LIN = false, int WGN = 2,
-          class AccT>
+          bool AFF = false, class AccT>
 __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmClass &c, AccT &acc,
                                               unsigned short *smem, int tid, int g, int mtile, int ntile) {
   constexpr int NT = WGM * WGN * 64;
@@ -69,7 +74,7 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
       if (tid == 0 && mtile == 0 && ntile == 0 && g == 0) *p.out_sinv = 1.f / lin_scale;
     }
   }
-  if (!DGRAD && p.stats) {
+  if (!DGRAD && !AFF && p.stats) {
     // per-wave partial over its WTM rows: column sum and sum of squares centred on the partial's own mean
     long long cnt_ll = c.rows_per_group - row_base;
     const int cnt = cnt_ll <= 0 ? 0 : (cnt_ll > WTM ? WTM : (int)cnt_ll);
@@ -171,6 +176,16 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
 #pragma unroll
     for (int k = 0; k < 8; ++k) bn_s1[k] = bn_s2[k] = bn_mx[k] = 0.f;
   }
+  float *affc = reinterpret_cast<float *>(smem) + (BM / PASSES) * LDO + BM;     // AFF: [2][BN] scale, shift (the first barrier below publishes them)
+  if constexpr (AFF) {
+    static_assert(!DGRAD && !F32IO && !BNF && !LIN, "bf16_epilogue: AFF is the forward form of the bf16 storage kernels");
+    for (int cc = tid; cc < BN; cc += NT) {
+      const int colc = ntile * BN + cc;
+      const bool ok = colc < p.ncols;
+      affc[cc] = ok ? p.scale[colc] : 0.f;
+      affc[BN + cc] = ok ? p.bias[colc] : 0.f;
+    }
+  }
 #pragma unroll
   for (int ph = 0; ph < PASSES; ++ph) {
   if (PASSES > 1 && ph > 0) __syncthreads();                  // the previous pass's rows have been read
@@ -199,6 +214,34 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
     if constexpr (F32IO) {
 #pragma unroll
       for (int k = 0; k < 8; ++k) x[k] *= osc;
+    }
+    if constexpr (AFF) {
+      asm volatile("" ::: "memory");           // re-read the constants here (not hoisted into 16 live registers)
+      float sa[8], sb[8];
+      ld8(affc + cv * 8, sa);
+      ld8(affc + BN + cv * 8, sb);
+#pragma unroll
+      for (int k = 0; k < 8; ++k) x[k] = __builtin_fmaf(x[k], sa[k], sb[k]);
+      if (add_g) {                             // the block's identity (bf16), then the ReLU
+        const u32x4 a = *reinterpret_cast<const u32x4 *>(add_g + off + col);
+        const unsigned aa[4] = {a.x, a.y, a.z, a.w};
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+          x[2 * k] += bf_lo(aa[k]);
+          x[2 * k + 1] += bf_hi(aa[k]);
+        }
+      }
+      if (p.relu) {
+#pragma unroll
+        for (int k = 0; k < 8; ++k) x[k] = fmaxf(x[k], 0.f);
+      }
+      u32x4 o;
+      o.x = pack_bf2(x[0], x[1]);
+      o.y = pack_bf2(x[2], x[3]);
+      o.z = pack_bf2(x[4], x[5]);
+      o.w = pack_bf2(x[6], x[7]);
+      *reinterpret_cast<u32x4 *>(out_g + off + col) = o;
+      return;
     }
     if (!DGRAD && F32IO && p.scale) {          // inference: BatchNorm folded into a per-channel affine
       const float4 s0 = *reinterpret_cast<const float4 *>(p.scale + col), s1 = *reinterpret_cast<const float4 *>(p.scale + col + 4);

@@ -149,18 +149,36 @@ __global__ __launch_bounds__(256) void nhwc4_to_nchw_kernel(const float4 *__rest
 
 // uint8 HWC face patch -> normalised fp32 NHWC4: the deterministic part of the reference's input
 // pipeline (dataset/gaze.py:106-111 BGR->RGB; main.py:50-55 ToTensor = /255, Normalize(mean, std)).
+// The per-pixel arithmetic is ONE device function for the fp32 (NHWC4) and the bf16 (NHWC8) kernels: the same
+// source, the same contractions, so the bf16 output is the fp32 output rounded once.
+__device__ __forceinline__ void preprocess_u8_px(const unsigned char *__restrict__ src, long long i, float m0, float m1, float m2,
+                                                 float s0, float s1, float s2, int swap_rb, float &c0, float &c1, float &c2) {
+  const unsigned char *p = src + 3 * i;
+  c0 = (float)p[swap_rb ? 2 : 0], c1 = (float)p[1], c2 = (float)p[swap_rb ? 0 : 2];
+  c0 = (c0 / 255.0f - m0) / s0;
+  c1 = (c1 / 255.0f - m1) / s1;
+  c2 = (c2 / 255.0f - m2) / s2;
+}
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char *__restrict__ src,
                                                             float4 *__restrict__ dst, long long pixels, float m0,
                                                             float m1, float m2, float s0, float s1, float s2,
                                                             int swap_rb) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= pixels) return;
-  const unsigned char *p = src + 3 * i;
-  float c0 = (float)p[swap_rb ? 2 : 0], c1 = (float)p[1], c2 = (float)p[swap_rb ? 0 : 2];
-  c0 = (c0 / 255.0f - m0) / s0;
-  c1 = (c1 / 255.0f - m1) / s1;
-  c2 = (c2 / 255.0f - m2) / s2;
+  float c0, c1, c2;
+  preprocess_u8_px(src, i, m0, m1, m2, s0, s1, s2, swap_rb, c0, c1, c2);
   dst[i] = make_float4(c0, c1, c2, 0.f);
+}
+// ... straight to the bf16 stem's input: NHWC8 (channels 3..7 zero), one 16-byte store per pixel, no fp32 image in between
+__global__ __launch_bounds__(256) void preprocess_u8_bf16_kernel(const unsigned char *__restrict__ src,
+                                                                 uint4 *__restrict__ dst, long long pixels, float m0,
+                                                                 float m1, float m2, float s0, float s1, float s2,
+                                                                 int swap_rb) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= pixels) return;
+  float c0, c1, c2;
+  preprocess_u8_px(src, i, m0, m1, m2, s0, s1, s2, swap_rb, c0, c1, c2);
+  dst[i] = make_uint4(bf16_pack2(c0, c1), bf16_pack2(c2, 0.f), 0u, 0u);
 }
 
 // test_transform of main.py:50-55 for patches that are not already S x S: ToTensor (/255) ->
@@ -199,12 +217,10 @@ __device__ __forceinline__ float aa_weight(const AaAxis &a, int j, int x0, float
   const float w = fmaxf(0.f, 1.f - fabsf(t));
   return total != 0.f ? w / total : w;
 }
-__global__ __launch_bounds__(256) void preprocess_u8_resize_kernel(const unsigned char *__restrict__ src,
-                                                                   float4 *__restrict__ dst, int n, int h, int w, int oh,
-                                                                   int ow, AaAxis ay, AaAxis ax, float m0, float m1,
-                                                                   float m2, float s0, float s1, float s2, int swap_rb) {
-  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= (long long)n * oh * ow) return;
+// (one device function for the fp32 and the bf16 kernel, like preprocess_u8_px)
+__device__ __forceinline__ void preprocess_u8_resize_px(const unsigned char *__restrict__ src, long long i, int h, int w, int oh, int ow,
+                                                        const AaAxis &ay, const AaAxis &ax, float m0, float m1, float m2, float s0,
+                                                        float s1, float s2, int swap_rb, float &c0, float &c1, float &c2) {
   const int ox = (int)(i % ow);
   const long long r = i / ow;
   const int oy = (int)(r % oh), img = (int)(r / oh);
@@ -233,7 +249,29 @@ __global__ __launch_bounds__(256) void preprocess_u8_resize_kernel(const unsigne
     o0 = o2;
     o2 = t;
   }
-  dst[i] = make_float4((o0 - m0) / s0, (o1 - m1) / s1, (o2 - m2) / s2, 0.f);
+  c0 = (o0 - m0) / s0;
+  c1 = (o1 - m1) / s1;
+  c2 = (o2 - m2) / s2;
+}
+__global__ __launch_bounds__(256) void preprocess_u8_resize_kernel(const unsigned char *__restrict__ src,
+                                                                   float4 *__restrict__ dst, int n, int h, int w, int oh,
+                                                                   int ow, AaAxis ay, AaAxis ax, float m0, float m1,
+                                                                   float m2, float s0, float s1, float s2, int swap_rb) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)n * oh * ow) return;
+  float c0, c1, c2;
+  preprocess_u8_resize_px(src, i, h, w, oh, ow, ay, ax, m0, m1, m2, s0, s1, s2, swap_rb, c0, c1, c2);
+  dst[i] = make_float4(c0, c1, c2, 0.f);
+}
+__global__ __launch_bounds__(256) void preprocess_u8_resize_bf16_kernel(const unsigned char *__restrict__ src,
+                                                                        uint4 *__restrict__ dst, int n, int h, int w, int oh,
+                                                                        int ow, AaAxis ay, AaAxis ax, float m0, float m1,
+                                                                        float m2, float s0, float s1, float s2, int swap_rb) {
+  const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (i >= (long long)n * oh * ow) return;
+  float c0, c1, c2;
+  preprocess_u8_resize_px(src, i, h, w, oh, ow, ay, ax, m0, m1, m2, s0, s1, s2, swap_rb, c0, c1, c2);
+  dst[i] = make_uint4(bf16_pack2(c0, c1), bf16_pack2(c2, 0.f), 0u, 0u);
 }
 
 // RandomMultiErasing (utils/augment.py:10-47): img *= nearest-neighbour upsampling of a per-image
@@ -370,6 +408,25 @@ int mvg_preprocess_u8hwc_resize(const uint8_t *src, float *dst, int n, int h, in
   hipLaunchKernelGGL(preprocess_u8_resize_kernel, dim3(ceil_div(pixels, 256)), dim3(256), 0, st, src, (float4 *)dst, n, h, w,
                      oh, ow, aa_axis(h, oh), aa_axis(w, ow), mean0, mean1, mean2, std0, std1, std2, swap_rb);
   return check_launch("preprocess_u8hwc_resize");
+}
+
+int mvg_preprocess_u8hwc_resize_bf16(const uint8_t *src, uint16_t *dst, int n, int h, int w, int oh, int ow, float mean0,
+                                     float mean1, float mean2, float std0, float std1, float std2, int swap_rb, void *stream) {
+  MVG_REQUIRE(src && dst, "preprocess_resize_bf16: null argument");
+  MVG_REQUIRE(std0 > 0.f && std1 > 0.f && std2 > 0.f, "preprocess: std must be positive");
+  MVG_REQUIRE(n > 0 && h > 0 && w > 0 && oh > 0 && ow > 0, "preprocess_resize_bf16: bad sizes");
+  hipStream_t st = (hipStream_t)stream;
+  const long long pixels = (long long)n * oh * ow;
+  if (h == oh && w == ow) {    // torchvision's resize returns the input unchanged
+    ProfScope ps(MVG_K_LAYOUT, st, 0.0, 19.0 * (double)pixels);
+    hipLaunchKernelGGL(preprocess_u8_bf16_kernel, dim3(ceil_div(pixels, 256)), dim3(256), 0, st, src, (uint4 *)dst, pixels, mean0,
+                       mean1, mean2, std0, std1, std2, swap_rb);
+    return check_launch("preprocess_u8hwc_bf16");
+  }
+  ProfScope ps(MVG_K_LAYOUT, st, 0.0, 3.0 * (double)n * h * w + 16.0 * (double)pixels);
+  hipLaunchKernelGGL(preprocess_u8_resize_bf16_kernel, dim3(ceil_div(pixels, 256)), dim3(256), 0, st, src, (uint4 *)dst, n, h, w,
+                     oh, ow, aa_axis(h, oh), aa_axis(w, ow), mean0, mean1, mean2, std0, std1, std2, swap_rb);
+  return check_launch("preprocess_u8hwc_resize_bf16");
 }
 
 int mvg_multi_erase_nchw(float *img, const float *masks, const int32_t *grid, int gmax, int n, int c, int h, int w,

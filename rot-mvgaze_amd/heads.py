@@ -261,8 +261,14 @@ class FusionHead:
         self._idx_cache: Dict[Tuple[int, str], dict] = {}
         self._wprep_state = None
         self._wsp_versions = None
+        self.keep_infer_copies = True             # bf16 path: inference calls reuse the bf16 copies while the weights are unchanged
+        self._wbf_infer_ok = False                # the persistent bf16 copies hold _wsp_versions and may serve the next inference call
 
-    def _prepare_split_weights(self, rows: int, dev, mixed: bool = False):
+    def invalidate_weight_cache(self):
+        """The next inference call of the bf16 path casts the Linear weights again (see Backbone.invalidate_weight_cache)."""
+        self._wbf_infer_ok = False
+
+    def _prepare_split_weights(self, rows: int, dev, mixed: bool = False, reuse: bool = False):
         """The sp copies (KRSC for fprop, CRSK for backward-data) of every fuser / head Linear that runs on the split
         kernels this step - or, mixed (the bf16 path), their bf16 copies - made by ONE batched launch pair (like
         Backbone._prepare_weights: persistent destination buffers and a device-resident record table built once per
@@ -289,12 +295,20 @@ class FusionHead:
                 rows_t.append([m.w[l].data_ptr(), wk.data_ptr(), wt.data_ptr(), fout | (1 << 32), fin | (fin << 32), wstat[i].data_ptr()])
             table = torch.tensor(rows_t, dtype=torch.int64).to(dev) if rows_t else None
             self._wprep_state = (key, bufs, table, wstat)
+            self._wbf_infer_ok = False
         _, bufs, table, wstat = self._wprep_state
         for m in mods:
             m._wsp = [None] * m.n
             m._wbf = [None] * m.n
         if table is None:
             return
+        # reuse (bf16 inference): the buffers already hold these parameters (same placement, same version counters, nothing
+        # invalidated since) - no cast launch
+        if mixed and reuse and self._wbf_infer_ok and self._wsp_versions == tuple(m.w[l]._version for m, l, _, _ in bufs):
+            for m, l, wk, wt in bufs:
+                m._wbf[l] = (wk, wt)
+            return
+        self._wbf_infer_ok = mixed and reuse
         if not mixed:
             wstat.zero_()
         ops.weights_prep_batch(table, len(bufs), 0 if mixed else 1, 256)
@@ -379,7 +393,7 @@ class FusionHead:
         if split_on:
             return self._forward_split(img_feat, rot, keep_tape, ix)
         if self.mixed:
-            self._prepare_split_weights(D * B, dev, mixed=True)
+            self._prepare_split_weights(D * B, dev, mixed=True, reuse=self.keep_infer_copies and not keep_tape and not training)
         hl, lifted = self.lifter.forward(img_feat.reshape(V * B, cf))
         rel = torch.empty(D, B, 3, 3, dtype=torch.float32, device=dev)
         ops.relative_rotation(rot.detach().to(torch.float32).contiguous(), ix["vi"], ix["vj"], rel, B, V, D)

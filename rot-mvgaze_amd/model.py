@@ -297,13 +297,14 @@ class MultiViewGaze(nn.Module):
         return self._grad_arena, [(p, self._grad_offsets[id(p)], p.numel()) for p in self._grad_order]
 
     def invalidate_weight_cache(self) -> None:
-        """``torch.no_grad()`` inference keeps sp copies of the conv weights between calls, keyed on every parameter's
-        version counter.  The counter misses writes through ``p.data`` (``p.data.copy_`` / ``mul_``: EMA, clipping) and
+        """``torch.no_grad()`` inference keeps sp copies of the conv weights (bf16 path: the bf16 copies of the conv and Linear
+        weights) between calls, keyed on every parameter's version counter.  The counter misses writes through ``p.data`` (``p.data.copy_`` / ``mul_``: EMA, clipping) and
         writes to ``param_arena()``: call this after such a write (or ``torch.autograd.graph.increment_version(p)``).
         ``load_state_dict``, the fused Adam, the data-parallel broadcast, ``train()`` and training forwards are covered."""
         bb = getattr(self, "_backbone", None)
         if bb is not None:
             bb.invalidate_weight_cache()
+            self._head.invalidate_weight_cache()   # bf16 path: the Linear layers' bf16 copies
 
     def train(self, mode: bool = True):
         if mode:                                   # weights are about to change; eval() keeps the cache (it is what uses it)

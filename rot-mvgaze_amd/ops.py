@@ -97,6 +97,16 @@ def conv_fprop_affine(d: ConvDesc, x: Tensor, w: Tensor, out: Tensor, scale: Ten
                                       _s(True)), "conv_fprop_affine")
 
 
+def conv_fprop_bf16_affine(d: ConvDesc, x: Tensor, w: Tensor, out: Tensor, scale: Tensor, shift: Tensor,
+                           residual: Optional[Tensor], relu: bool):
+    """Inference forward of the bf16 storage path, BatchNorm folded: out = bf16(relu?(conv * scale + shift (+ residual)))."""
+    assert x.dtype == w.dtype == out.dtype == torch.bfloat16 and (residual is None or (residual.dtype == torch.bfloat16 and
+                                                                                       residual.shape == out.shape))
+    assert scale.numel() == d.cout and shift.numel() == d.cout and out.is_contiguous()
+    check(lib().mvg_conv_fprop_bf16_affine(C.byref(d), _p(x), _p(w), _p(out), _p(_f32c(scale)), _p(_f32c(shift)), _p(residual),
+                                           int(relu), _s()), "conv_fprop_bf16_affine")
+
+
 def conv_dgrad(d: ConvDesc, dy: Tensor, w: Tensor, dx: Tensor, mask: Optional[Tensor] = None,
                addend: Optional[Tensor] = None):
     check(_fn("mvg_conv_dgrad", dy)(C.byref(d), _p(dy), _p(w), _p(dx), _p(mask), _p(addend), _s(True)), "conv_dgrad")
@@ -596,6 +606,14 @@ def multi_erase_nchw(img, masks, grid, gmax, n, c, h, w):
 def preprocess_u8hwc_resize(src, dst, n, h, w, oh, ow, mean, std, swap_rb):
     check(lib().mvg_preprocess_u8hwc_resize(_p(src), _p(dst), n, h, w, oh, ow, mean[0], mean[1], mean[2], std[0], std[1],
                                             std[2], int(swap_rb), _s()), "preprocess_u8hwc_resize")
+
+
+def preprocess_u8hwc_resize_bf16(src, dst, n, h, w, oh, ow, mean, std, swap_rb):
+    """uint8 [n, h, w, 3] -> dst bf16 [n, oh, ow, 8] (channels 3..7 zero): preprocess_u8hwc[_resize] rounded once, the stem's input."""
+    assert src.dtype == torch.uint8 and src.is_contiguous() and dst.dtype == torch.bfloat16 and dst.is_contiguous()
+    assert src.numel() == n * h * w * 3 and dst.numel() == n * oh * ow * 8
+    check(lib().mvg_preprocess_u8hwc_resize_bf16(_p(src), _p(dst), n, h, w, oh, ow, mean[0], mean[1], mean[2], std[0], std[1],
+                                                 std[2], int(swap_rb), _s()), "preprocess_u8hwc_resize_bf16")
 
 
 def preprocess_u8hwc(src, dst, n, h, w, mean, std, swap_rb):
