@@ -584,6 +584,33 @@ int mvg_bn_relu_maxpool_fwd_split(const float *y, const float *scale, const floa
                                   uint8_t *argmax, int groups, int n_per_group, int h, int w, int c, int ho, int wo,
                                   void *stream);
 int mvg_avgpool_fwd_split(const void *x_sp, float *y, int n, int hw, int c, void *stream);
+/* Backbone activations of a TRAINING step carry a per-tensor power-of-two scale too (the reference - resnet.py:60-75,
+ * 113-133,261-275 - computes them in plain fp32 and has no range limit; fp16 pieces overflow at 65 520 and lose small
+ * values absolutely).  The scale comes from a bound that needs no pass over any activation: a unit writes
+ * [relu](gamma xhat + beta [+ identity]) with xhat a z-score of n = B Ho Wo samples per view, |xhat| <= sqrt(n - 1), so
+ *   bound(unit) = max_c (|gamma_c| sqrt(n - 1) + |beta_c|),  bound(block output) = bound(last unit) + bound(identity),
+ * identity = the previous block's output (first block: the stem's pooled map, bound(stem unit)) or the downsample
+ * BatchNorm's output.  2^k = 1 while 1 <= bound < 2^15 (every value fits unscaled: the stored bits are those of an
+ * unscaled tensor), else the power of two that maps the bound just below 2^15; a zero, infinite or NaN bound gives 1.
+ *   mvg_act_scales: ONE single-workgroup launch for a whole step.  items_dev: n <= 256 records in DEVICE memory of
+ *     { const float *gamma, *beta; int32 c; float sqrt(n - 1); int32 ident; int32 slot; }  (32 bytes) in forward order;
+ *     ident = an EARLIER record whose (chained) bound is added, or -1; slots[slot] receives 2^-k (slot -1: none).
+ *   The _scaled / _xs entry points are the ones above with those device scalars (NULL = unscaled: the results of the old
+ *   entry point, bit for bit; the new ones also reject null required pointers and non-positive sizes, the old ones keep
+ *   exactly the argument checks they had): out_sinv / pooled_sinv of the tensor written, res_sinv of an sp identity, x_sinv of the tensor read
+ *   (the conv forward takes it as mvg_conv_fprop_split's x_sinv).  The ReLU mask bits are decided on the unscaled value.
+ *   Readers that use an sp activation only for its SIGN (relu_mask_sp, the backward's mask forms) need no scale.
+ * Inference on the split kernels (mvg_conv_fprop_split_affine) has no z-score bound - running statistics - and stays
+ * unscaled: |activation| must stay below 65 504 there. */
+int mvg_act_scales(const void *items_dev, int n, float *slots, int n_slots, void *stream);
+int mvg_bn_apply_split_scaled(const float *y, const float *scale, const float *shift, const void *residual, int residual_sp,
+                              const float *res_scale, const float *res_shift, const float *res_sinv, int relu, void *out_sp,
+                              const float *out_sinv, uint8_t *relu_bits, int groups, int64_t rows_per_group, int c,
+                              void *stream);
+int mvg_bn_relu_maxpool_fwd_split_scaled(const float *y, const float *scale, const float *shift, void *pooled_sp,
+                                         const float *pooled_sinv, uint8_t *argmax, int groups, int n_per_group, int h, int w,
+                                         int c, int ho, int wo, void *stream);
+int mvg_avgpool_fwd_split_scaled(const void *x_sp, const float *x_sinv, float *y, int n, int hw, int c, void *stream);
 /* mvg_conv_dgrad_split fused with the BatchNorm-backward reduce pass of the unit whose output gradient dx is (stride 1
  * or 2: a stride-2 launch's parity classes - those a 1x1 filter never touches included - each bring their partials): dx is stored masked by that unit's ReLU (bn_bits from mvg_bn_apply_split, or fma(bn_y, relu_scale,
  * relu_shift) > 0, or no mask) and s1 / s2 / dgamma / dbeta come out of the same launch + a finalize; mx [groups][cin] (may be
@@ -631,6 +658,11 @@ int mvg_conv_wgrad_split(const mvg_conv_desc *d, const void *x_sp, const void *d
  * host_n[i] floats, fixed order.  Host arrays; the launch copies them. */
 int mvg_conv_wgrad_split_slabs(const mvg_conv_desc *d, const void *x_sp, const void *dy_sp, const float *dy_sinv, float *workspace,
                                int splits, void *stream);
+/* ... with x_sinv, the 2^-k of a scaled activation operand (mvg_act_scales; NULL = unscaled) */
+int mvg_conv_wgrad_split_xs(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *dy_sp, const float *dy_sinv,
+                            float *dw, float *workspace, int splits, int accumulate, void *stream);
+int mvg_conv_wgrad_split_slabs_xs(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *dy_sp,
+                                  const float *dy_sinv, float *workspace, int splits, void *stream);
 int mvg_wgrad_reduce_batch(const float *const *host_slabs, float *const *host_dw, const int64_t *host_n, const int32_t *host_splits,
                            const int32_t *host_accumulate, int n, void *stream);
 

@@ -82,6 +82,13 @@ SIGNATURES = {
     "mvg_bn_bwd_reduce_split": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P, _P]),
     "mvg_bn_relu_maxpool_fwd_split": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mvg_avgpool_fwd_split": (_I, [_P, _P, _I, _I, _I, _P]),
+    # per-tensor scales of the backbone's sp activations (training steps)
+    "mvg_act_scales": (_I, [_P, _I, _P, _I, _P]),
+    "mvg_bn_apply_split_scaled": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I64, _I, _P]),
+    "mvg_bn_relu_maxpool_fwd_split_scaled": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
+    "mvg_avgpool_fwd_split_scaled": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "mvg_conv_wgrad_split_xs": (_I, [_D, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "mvg_conv_wgrad_split_slabs_xs": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
     "mvg_stem_rowwindow_split": (_I, [_P, _P, _I64, _I, _I, _P]),
     "mvg_stem_rowwindow_split_nchw": (_I, [_P, _P, _I64, _I, _I, _P]),
     "mvg_stem_fprop_split": (_I, [_D, _P, _P, _P, _P, _P, _P]),

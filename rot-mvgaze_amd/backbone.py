@@ -12,9 +12,11 @@ input, ReLU mask); weights are the PyTorch parameters themselves in channels_las
 """
 from __future__ import annotations
 
+import math
 import os
 from typing import Callable, Dict, List, Optional
 
+import numpy as np
 import torch
 
 from . import ops
@@ -108,6 +110,9 @@ class Backbone:
         self._wprep: Optional[Dict[str, tuple]] = None
         self._wprep_state = None
         self._wprep_versions = None
+        # split path, training: per-tensor scales of the sp activations (one launch per step: _prepare_act_scales)
+        self._ascale_state = None             # (key, device table, records, conv name -> slot, slots)
+        self._act_sinv: Optional[Dict[str, Tensor]] = None    # per forward call: conv name -> its output's 1-element slot
         self._wg_defer: Optional[list] = None # backward: (slabs, dw, splits, accumulate) of the split wgrads whose reduce is pending
         self._split_now = self.split          # per forward call: off when a view's largest sp tensor would exceed 2 GiB
         self._stem_rw = False                 # per forward call: the stem runs in row-window form on the split kernels
@@ -199,6 +204,55 @@ class Backbone:
         # they hold, so that the backward of an OLDER tape can tell (tapes keep pointers into these buffers)
         self._wprep_versions = tuple(self.p[c.name + ".weight"]._version for c in self.spec.all_convs())
         return out
+
+    def _prepare_act_scales(self, dev, B: int, H: int, W: int) -> Dict[str, Tensor]:
+        """The 2^-k of every sp activation this training step stores (each unit's output, the stem's pooled map), by ONE
+        single-workgroup launch (ops.act_scales) from a bound that depends on parameters and shapes only:
+            bound(unit) = max_c(|gamma_c| sqrt(n - 1) + |beta_c|),   n = B Ho Wo  (a z-score of n samples is <= sqrt(n - 1)),
+            bound(block output) = bound(last unit) + bound(identity: previous block's output, or the downsample BatchNorm).
+        The device table of (gamma, beta, channels, sqrt(n - 1), identity record, slot) records is built once per
+        (placement, B, H, W); the slots are a fresh tensor per step, kept alive by the sp tensors that carry its 1-element
+        views as ``.sinv``.  Returns conv name -> slot view.  No pass over an activation, no atomics, no host synchronisation."""
+        s = self.spec
+        convs = s.all_convs()
+        key = (str(dev), B, H, W, tuple((self.p[c.bn + ".weight"].data_ptr(), self.p[c.bn + ".bias"].data_ptr()) for c in convs))
+        if self._ascale_state is None or self._ascale_state[0] != key:
+            rec, slot_of = [], {}
+
+            def size(h, c):
+                return (h + 2 * c.pad - c.k) // c.stride + 1
+
+            def add(c, n, ident, has_slot):
+                slot = -1
+                if has_slot:
+                    slot = slot_of[c.name] = len(slot_of)
+                rec.append((self.p[c.bn + ".weight"].data_ptr(), self.p[c.bn + ".bias"].data_ptr(), c.cout,
+                            math.sqrt(max(n - 1, 0)), ident, slot))
+                return len(rec) - 1
+            h, w = size(H, s.stem), size(W, s.stem)
+            prev = add(s.stem, B * h * w, -1, True)          # the pooled map: max pool and ReLU do not raise the unit's bound
+            h, w = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+            for blk in s.blocks:
+                hb, wb = h, w
+                for c in blk.convs[:-1]:
+                    hb, wb = size(hb, c), size(wb, c)
+                    add(c, B * hb * wb, -1, True)
+                ident = prev
+                if blk.downsample is not None:           # its normalised map is never stored: a bound, no slot
+                    ident = add(blk.downsample, B * size(h, blk.downsample) * size(w, blk.downsample), -1, False)
+                c = blk.convs[-1]
+                hb, wb = size(hb, c), size(wb, c)
+                prev = add(c, B * hb * wb, ident, True)
+                h, w = hb, wb
+            items = np.array(rec, dtype=np.dtype([("gamma", "<i8"), ("beta", "<i8"), ("c", "<i4"), ("sqrt_n1", "<f4"),
+                                                  ("ident", "<i4"), ("slot", "<i4")]))
+            table = torch.from_numpy(items.view("<i8").reshape(len(rec), 4).copy()).to(dev)   # once per placement and shape
+            self._ascale_state = (key, table, len(rec), slot_of, len(slot_of))
+        _, table, n, slot_of, n_slots = self._ascale_state
+        slots = torch.empty(n_slots, dtype=torch.float32, device=dev)
+        ops.act_scales(table, n, slots)
+        views = slots.split(1)
+        return {name: views[i] for name, i in slot_of.items()}
 
     def invalidate_weight_cache(self):
         """Forget the inference path's cached sp (bf16 path: bf16) copies of the conv weights.  The cache is keyed on each parameter's
@@ -324,6 +378,7 @@ class Backbone:
             argmax = torch.empty(G, N, hp, wp_, c.cout, dtype=torch.uint8, device=dev)
             if sp_out:
                 out = ops.sp_empty(G, N, hp, wp_, c.cout, device=dev)
+                out.sinv = self._act_sinv[c.name]
                 ops.bn_relu_maxpool_fwd_split(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
             else:
                 out = torch.empty(G, N, hp, wp_, c.cout, dtype=self.act_dtype, device=dev)
@@ -332,6 +387,7 @@ class Backbone:
                 self._debug_units.append((c.name, x, y, out))
         elif sp_out:
             out = ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev)
+            out.sinv = self._act_sinv[c.name]       # this step's 2^-k of the unit's output (an sp identity brings its own)
             bits = ops.bn_apply_split(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine,
                                       want_bits=keep and relu and residual is not None)
         else:
@@ -429,6 +485,9 @@ class Backbone:
             self.invalidate_weight_cache()       # the weights are about to change: drop the inference copies
         if self.batch_weight_prep and (self.bf16 or (self._split_now and training)):
             self._wprep = self._prepare_weights(dev, reuse=self.bf16 and self.bf16_fold_eval and not training and not keep_tape)
+        # ... and one launch gives every sp activation of the step its scale (x, out and identity carry it as .sinv; the
+        # tape's x_in / out keep it for the backward's weight gradients)
+        self._act_sinv = self._prepare_act_scales(dev, B, H, W) if (self._split_now and training and not self.bf16) else None
         tape: Optional[dict] = {"units": [], "blocks": [], "V": V, "B": B} if keep_tape else None
         if keep_tape and self._wprep is not None:
             tape["wprep_versions"] = self._wprep_versions
@@ -500,7 +559,9 @@ class Backbone:
         acc = sink.accumulate(gp)
         assert acc == sink.accumulate(bp)
         if u.split:
-            # split path: g and y are fp32, dy goes to the conv kernels in sp; residual units carry their mask as bits
+            # split path: g and y are fp32, dy goes to the conv kernels in sp; residual units carry their mask as bits.
+            # No pass here reads the (scaled) sp activation: the mask comes from the bits or from fma(y, scale, shift) > 0,
+            # both decided on the unscaled value
             assert not (u.relu and ra is None) or u.relu_bits is not None
             sinv = torch.empty(1, dtype=torch.float32, device=g.device)       # dy's 2^-k: left by the reduce pass's finalize launch
             if u.relu_bits is not None:
@@ -580,6 +641,8 @@ class Backbone:
                 dy.sinv.record_stream(side)
             dy.record_stream(side)                                # the allocator must not recycle these while
             u.x_in.record_stream(side)                            # the side stream still reads them
+            if getattr(u.x_in, "sinv", None) is not None:         # (a scaled sp activation: its slot too)
+                u.x_in.sinv.record_stream(side)
         else:
             self._wgrad(u, dy, sink)
         dx = None
@@ -592,7 +655,8 @@ class Backbone:
         c = u.spec
         wp = self.p[c.name + ".weight"]
         if u.split:
-            # (slabs now, their sums in ONE launch per residual block: _flush_wgrad_reduces)
+            # (slabs now, their sums in ONE launch per residual block: _flush_wgrad_reduces); x_in is read by VALUE: its
+            # .sinv goes into the launch's output scale
             ops.conv_wgrad_split(u.desc, u.x_in, dy, sink.view(wp), sink.accumulate(wp), defer=self._wg_defer)
         elif u.stem_rw and self.bf16:
             dw16 = torch.empty(2 * c.cout, 7, 16, 4, dtype=torch.float32, device=dy.device)
@@ -657,6 +721,7 @@ class Backbone:
                 gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
                 acc = sink.accumulate(gp)
                 assert acc == sink.accumulate(bp)
+                # (the fused reduce epilogue masks with U's bits or fma(U.y, scale, shift) > 0: no sp activation is read)
                 s12 = torch.empty(3, dx.shape[0], c.cout, dtype=torch.float32, device=dx.device)     # s1, s2, max |dz| per channel
                 sinv = torch.empty(1, dtype=torch.float32, device=dx.device)      # 2^-k of the dy that U's apply pass will write
                 ops.conv_dgrad_split_bnreduce(u.desc, dy, u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd,

@@ -2,6 +2,8 @@
 // float4 accesses, channel index carried incrementally (no per-element division).
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "common.h"
 #include "elem.h"
 #include "bn_math.h"
@@ -716,7 +718,14 @@ __global__ __launch_bounds__(256) void bn_apply_sp_kernel(const float *__restric
                                                           const float *__restrict__ res_scale,
                                                           const float *__restrict__ res_shift, int relu, sp_t *__restrict__ out,
                                                           long long n8_per_group, int c8n, int c,
-                                                          unsigned short *__restrict__ relu_bits) {
+                                                          unsigned short *__restrict__ relu_bits,
+                                                          const float *__restrict__ out_sinv,
+                                                          const float *__restrict__ res_sinv) {
+  // out is stored times 2^k = 1 / *out_sinv (act_scales_kernel; exact: a power of two), an sp identity comes back times
+  // its own 2^-k; null = unscaled.  Multiplying by 1.0f changes no bit: the unscaled entry point is this kernel with nulls.
+  // (both uniform: kept in scalar registers, so the row loop holds no more vector registers than the unscaled kernel did)
+  const float osc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(out_sinv ? 1.f / *out_sinv : 1.f)));
+  const float rsi = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((RES_SP && res_sinv) ? *res_sinv : 1.f)));
   const int g = blockIdx.y;
   const long long base = (long long)g * n8_per_group;
   const long long stride = (long long)gridDim.x * 256;
@@ -745,15 +754,61 @@ __global__ __launch_bounds__(256) void bn_apply_sp_kernel(const float *__restric
 #pragma unroll
     for (int k = 0; k < 8; ++k) {
       float x = bn_fwd(v.v[k], sc.v[k], sh.v[k]);              // bn_math.h, as bn_apply_kernel (mask rebuild in the backward)
-      if (residual) x += raff ? bn_fwd(r.v[k], rs.v[k], rh.v[k]) : r.v[k];
+      if (residual) x += raff ? bn_fwd(r.v[k], rs.v[k], rh.v[k]) : (RES_SP ? r.v[k] * rsi : r.v[k]);
       if (relu) x = fmaxf(x, 0.f);
-      o.v[k] = x;
       m |= (x > 0.f ? 1u : 0u) << (k + (k >= 4 ? 4 : 0));    // two bytes, low nibbles: one byte per 4 channels (bn_bwd_reduce_bits)
+      o.v[k] = x * osc;                                      // after the mask decision: the bits come from the unscaled value
     }
     st8_sp(out, base + i, o);
     if (relu_bits) relu_bits[base + i] = (unsigned short)m;
     cq += step;
     if (cq >= c8n) cq -= c8n;
+  }
+}
+
+// ---- the scales of a training step's sp activations, from parameters and shapes alone ---------------------------------
+// A unit in training mode writes [relu](gamma xhat + beta [+ identity]) with xhat a z-score of n = B Ho Wo samples, so
+// |xhat| <= sqrt(n - 1) whatever eps is, and
+//   bound(unit) = max_c (|gamma_c| sqrt(n - 1) + |beta_c|),   bound(block output) = bound(last unit) + bound(identity),
+// the identity being the previous block's output (the stem's pooled map: max pool and ReLU do not raise a bound) or the
+// downsample BatchNorm's output.  No activation is read: ONE workgroup serves every unit of the step.  A wave takes a
+// record's channels (plain multiply and add, fixed order of the maximum: the host can evaluate the same fp32 expression),
+// then one lane walks the chain over the blocks in record order and writes slots[slot] = 2^-k (elem.h:
+// sp_scale_for_banded; a NaN or infinite parameter makes the bound infinite and the scale 1).
+struct ActScaleItem {
+  const float *gamma, *beta;
+  int32_t c;            // channels
+  float sqrt_n1;        // sqrt(n - 1), rounded to fp32 by the host
+  int32_t ident;        // record whose chained bound is added (an EARLIER record), or -1
+  int32_t slot;         // where 2^-k goes, or -1: the unit writes no sp tensor (a downsample branch)
+};
+constexpr int ACT_SCALE_MAX_ITEMS = 256;
+
+__global__ __launch_bounds__(1024) void act_scales_kernel(const ActScaleItem *__restrict__ items, int n, float *__restrict__ slots,
+                                                          int n_slots) {
+  __shared__ float bound[ACT_SCALE_MAX_ITEMS];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  for (int r = wave; r < n; r += 16) {
+    const ActScaleItem it = items[r];
+    float b = 0.f;
+    for (int ch = lane; ch < it.c; ch += 64) {
+      float v = __fadd_rn(__fmul_rn(fabsf(it.gamma[ch]), it.sqrt_n1), fabsf(it.beta[ch]));
+      if (!(v <= 3.0e38f)) v = INFINITY;         // NaN too: fmaxf would drop it
+      b = fmaxf(b, v);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) b = fmaxf(b, __shfl_xor(b, o, 64));
+    if (lane == 0) bound[r] = b;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    for (int r = 0; r < n; ++r) {
+      const int id = items[r].ident, slot = items[r].slot;
+      float b = bound[r];
+      if (id >= 0 && id < r) b = __fadd_rn(b, bound[id]);
+      bound[r] = b;
+      if (slot >= 0 && slot < n_slots) slots[slot] = 1.f / sp_scale_for_banded(b);
+    }
   }
 }
 
@@ -832,7 +887,7 @@ template <typename T, typename TO = T>
 __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T *__restrict__ y, const float *__restrict__ scale,
                                                                   const float *__restrict__ shift, TO *__restrict__ pooled,
                                                                   uchar4 *__restrict__ argmax, int n_per_group, int h, int w,
-                                                                  int c4n, int ho, int wo) {
+                                                                  int c4n, int ho, int wo, const float *__restrict__ out_sinv) {
   const int t = blockIdx.x * 256 + threadIdx.x;
   if (t >= wo * c4n) return;
   const int ox = t / c4n, cq = t - ox * c4n;
@@ -866,6 +921,10 @@ __global__ __launch_bounds__(256) void bn_relu_maxpool_fwd_kernel(const T *__res
     }
   }
   const long long o = (((long long)n * ho + oy) * wo + ox) * c4n + cq;
+  if constexpr (std::is_same<TO, sp_t>::value) {
+    // sp: the pooled map times 2^k = 1 / *out_sinv (act_scales_kernel; null = unscaled, and x 1.0f changes no bit)
+    if (out_sinv) best = mul4(best, 1.f / *out_sinv);
+  }
   Elem<TO>::st4(pooled, o, best);
   argmax[o] = idx;
 }
@@ -1380,7 +1439,8 @@ static int bn_bwd_apply_impl(const T *g, const T *act, const T *y, const float *
 
 template <typename T, typename TO = T>
 static int bn_relu_maxpool_fwd_impl(const T *y, const float *scale, const float *shift, TO *pooled, uint8_t *argmax, int groups,
-                                    int n_per_group, int h, int w, int c, int ho, int wo, void *stream) {
+                                    int n_per_group, int h, int w, int c, int ho, int wo, void *stream,
+                                    const float *out_sinv = nullptr) {
   MVG_REQUIRE(c % 4 == 0, "bn_relu_maxpool: c %% 4 != 0");
   MVG_REQUIRE(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1, "bn_relu_maxpool: bad output size");
   const long long total = (long long)groups * n_per_group * ho * wo * (c / 4);
@@ -1389,7 +1449,7 @@ static int bn_relu_maxpool_fwd_impl(const T *y, const float *scale, const float 
                Elem<T>::kBytes * (double)groups * n_per_group * h * w * c + Elem<TO>::kBytes * (double)total * 4 + (double)total * 4);
   MVG_REQUIRE((long long)groups * n_per_group * ho < 65536, "bn_relu_maxpool: images*ho must fit grid.y");
   hipLaunchKernelGGL((bn_relu_maxpool_fwd_kernel<T, TO>), dim3(ceil_div((long long)wo * (c / 4), 256), groups * n_per_group * ho),
-                     dim3(256), 0, st, y, scale, shift, pooled, (uchar4 *)argmax, n_per_group, h, w, c / 4, ho, wo);
+                     dim3(256), 0, st, y, scale, shift, pooled, (uchar4 *)argmax, n_per_group, h, w, c / 4, ho, wo, out_sinv);
   return check_launch("bn_relu_maxpool_fwd");
 }
 
@@ -1519,9 +1579,10 @@ int mvg_bn_bwd_reduce_split(const float *g, const uint8_t *relu_bits, const floa
                                    dbeta, accumulate, workspace, dz_out, stream, relu_bits, mx, gamma, dy_sinv);
 }
 
-int mvg_bn_apply_split(const float *y, const float *scale, const float *shift, const void *residual, int residual_sp,
-                       const float *res_scale, const float *res_shift, int relu, void *out_sp, uint8_t *relu_bits, int groups,
-                       int64_t rows_per_group, int c, void *stream) {
+// shared by the unscaled entry point (null scales: its behaviour and its argument checks are what they were) and the scaled one
+static int bn_apply_split_impl(const float *y, const float *scale, const float *shift, const void *residual, int residual_sp,
+                               const float *res_scale, const float *res_shift, const float *res_sinv, int relu, void *out_sp,
+                               const float *out_sinv, uint8_t *relu_bits, int groups, int64_t rows_per_group, int c, void *stream) {
   MVG_REQUIRE(c % 8 == 0, "bn_apply_split: c %% 8 != 0");
   MVG_REQUIRE(!(residual_sp && res_scale), "bn_apply_split: an sp residual is already normalised (no res_scale / res_shift)");
   MVG_REQUIRE((res_scale == nullptr) == (res_shift == nullptr) && (residual || !res_scale),
@@ -1532,11 +1593,41 @@ int mvg_bn_apply_split(const float *y, const float *scale, const float *shift, c
   const dim3 grid(grid_for(n8), groups), block(256);
   if (residual && residual_sp)
     hipLaunchKernelGGL(bn_apply_sp_kernel<true>, grid, block, 0, st, y, scale, shift, residual, res_scale, res_shift, relu,
-                       (sp_t *)out_sp, n8, c / 8, c, (unsigned short *)relu_bits);
+                       (sp_t *)out_sp, n8, c / 8, c, (unsigned short *)relu_bits, out_sinv, res_sinv);
   else
     hipLaunchKernelGGL(bn_apply_sp_kernel<false>, grid, block, 0, st, y, scale, shift, residual, res_scale, res_shift, relu,
-                       (sp_t *)out_sp, n8, c / 8, c, (unsigned short *)relu_bits);
+                       (sp_t *)out_sp, n8, c / 8, c, (unsigned short *)relu_bits, out_sinv, res_sinv);
   return check_launch("bn_apply_split");
+}
+
+// out_sinv / res_sinv (device scalars from mvg_act_scales, or NULL = unscaled): the 2^-k of the sp output and of an sp identity
+int mvg_bn_apply_split_scaled(const float *y, const float *scale, const float *shift, const void *residual, int residual_sp,
+                              const float *res_scale, const float *res_shift, const float *res_sinv, int relu, void *out_sp,
+                              const float *out_sinv, uint8_t *relu_bits, int groups, int64_t rows_per_group, int c, void *stream) {
+  MVG_REQUIRE(y && scale && shift && out_sp, "bn_apply_split: y, scale, shift and out_sp are required");
+  MVG_REQUIRE(groups > 0 && groups < 65536 && rows_per_group > 0 && c > 0, "bn_apply_split: bad sizes");
+  MVG_REQUIRE(!res_sinv || (residual && residual_sp), "bn_apply_split: res_sinv is the scale of an sp residual");
+  return bn_apply_split_impl(y, scale, shift, residual, residual_sp, res_scale, res_shift, res_sinv, relu, out_sp, out_sinv, relu_bits,
+                             groups, rows_per_group, c, stream);
+}
+
+int mvg_bn_apply_split(const float *y, const float *scale, const float *shift, const void *residual, int residual_sp,
+                       const float *res_scale, const float *res_shift, int relu, void *out_sp, uint8_t *relu_bits, int groups,
+                       int64_t rows_per_group, int c, void *stream) {
+  return bn_apply_split_impl(y, scale, shift, residual, residual_sp, res_scale, res_shift, nullptr, relu, out_sp, nullptr, relu_bits,
+                             groups, rows_per_group, c, stream);
+}
+
+// Every sp activation scale of a training step in one single-workgroup launch (act_scales_kernel).  items_dev: n records in
+// DEVICE memory of { const float *gamma, *beta; int32 c; float sqrt(n - 1); int32 ident; int32 slot; } (32 bytes).
+int mvg_act_scales(const void *items_dev, int n, float *slots, int n_slots, void *stream) {
+  static_assert(sizeof(ActScaleItem) == 32, "ActScaleItem: the callers build 32-byte records");
+  MVG_REQUIRE(items_dev && slots, "act_scales: items_dev and slots are required");
+  MVG_REQUIRE(n >= 1 && n <= ACT_SCALE_MAX_ITEMS && n_slots >= 1, "act_scales: 1..%d records and at least one slot", ACT_SCALE_MAX_ITEMS);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_LAYOUT, st, 0.0, 0.0);
+  hipLaunchKernelGGL(act_scales_kernel, dim3(1), dim3(1024), 0, st, (const ActScaleItem *)items_dev, n, slots, n_slots);
+  return check_launch("act_scales");
 }
 
 int mvg_bn_bwd_apply_split(const float *g, const float *y, const float *mean, const float *invstd, const float *gamma,
@@ -1552,6 +1643,15 @@ int mvg_bn_bwd_apply_split(const float *g, const float *y, const float *mean, co
   hipLaunchKernelGGL(bn_bwd_apply_sp_kernel, dim3(grid_for(n8), groups), dim3(256), 0, st, g, y, mean, invstd, gamma, s1, s2,
                      relu_scale, relu_shift, n8, 1.0f / (float)rows_per_group, c / 8, c, (sp_t *)dy_sp, dy_sinv);
   return check_launch("bn_bwd_apply_split");
+}
+
+int mvg_bn_relu_maxpool_fwd_split_scaled(const float *y, const float *scale, const float *shift, void *pooled_sp,
+                                         const float *pooled_sinv, uint8_t *argmax, int groups, int n_per_group, int h, int w, int c,
+                                         int ho, int wo, void *stream) {
+  MVG_REQUIRE(y && scale && shift && pooled_sp && argmax, "bn_relu_maxpool_fwd_split: y, scale, shift, pooled_sp and argmax are required");
+  MVG_REQUIRE(c % 8 == 0, "bn_relu_maxpool_fwd_split: c %% 8 != 0");
+  return bn_relu_maxpool_fwd_impl<float, sp_t>(y, scale, shift, (sp_t *)pooled_sp, argmax, groups, n_per_group, h, w, c, ho, wo,
+                                               stream, pooled_sinv);
 }
 
 int mvg_bn_relu_maxpool_fwd_split(const float *y, const float *scale, const float *shift, void *pooled_sp, uint8_t *argmax,

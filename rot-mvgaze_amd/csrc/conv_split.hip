@@ -1141,9 +1141,23 @@ static int wgrad_split_impl(const mvg_conv_desc *d, const void *x_sp, const void
   return splits > 1 && !slabs_only ? wgrad_reduce_slabs(p, workspace, dw, nullptr, splits, accumulate, st, "wgrad_split") : 0;
 }
 
+// x_sinv (may be NULL = unscaled): the 2^-k of an activation operand stored times 2^k (bn.hip: act_scales_kernel)
+int mvg_conv_wgrad_split_xs(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *dy_sp, const float *dy_sinv,
+                            float *dw, float *workspace, int splits, int accumulate, void *stream) {
+  MVG_REQUIRE(d && x_sp && dy_sp && dw, "wgrad_split: d, x_sp, dy_sp and dw are required");
+  return wgrad_split_impl(d, x_sp, dy_sp, dy_sinv, dw, workspace, splits, accumulate, stream, -1, -1, x_sinv);
+}
+
 int mvg_conv_wgrad_split(const mvg_conv_desc *d, const void *x_sp, const void *dy_sp, const float *dy_sinv, float *dw, float *workspace,
                          int splits, int accumulate, void *stream) {
   return wgrad_split_impl(d, x_sp, dy_sp, dy_sinv, dw, workspace, splits, accumulate, stream);
+}
+
+int mvg_conv_wgrad_split_slabs_xs(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *dy_sp, const float *dy_sinv,
+                                  float *workspace, int splits, void *stream) {
+  MVG_REQUIRE(d && x_sp && dy_sp, "wgrad_split_slabs: d, x_sp and dy_sp are required");
+  MVG_REQUIRE(splits > 1 && workspace, "wgrad_split_slabs: splits > 1 and a workspace (the slabs ARE the result)");
+  return wgrad_split_impl(d, x_sp, dy_sp, dy_sinv, workspace, workspace, splits, 0, stream, -1, -1, x_sinv, true);
 }
 
 int mvg_conv_wgrad_split_slabs(const mvg_conv_desc *d, const void *x_sp, const void *dy_sp, const float *dy_sinv, float *workspace, int splits,

@@ -107,6 +107,12 @@ __device__ __forceinline__ float sp_scale_for(float bound) {
   return ldexpf(1.f, k);
 }
 
+// The scale of a backbone activation, from a parameter-only bound (bn.hip: act_scales_kernel): 1 while the bound lies in
+// [1, 2^15) - every value then fits fp16's range unscaled and keeps the bits an unscaled store gives - sp_scale_for outside.
+__device__ __forceinline__ float sp_scale_for_banded(float bound) {
+  return (bound >= 1.f && bound < 32768.f) ? 1.f : sp_scale_for(bound);
+}
+
 template <>
 struct Elem<sp_t> {
   static constexpr double kBytes = (double)SP_BYTES;

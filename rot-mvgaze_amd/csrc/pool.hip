@@ -1,4 +1,6 @@
 // MaxPool2d(3,2,1), global average pool, and the NCHW <-> NHWC4 boundary repack.  HBM-bound.
+#include <type_traits>
+
 #include "common.h"
 #include "elem.h"
 
@@ -86,7 +88,7 @@ __global__ __launch_bounds__(256) void maxpool_bwd_kernel(const float4 *__restri
 
 template <typename T>
 __global__ __launch_bounds__(256) void avgpool_fwd_kernel(const T *__restrict__ x, float4 *__restrict__ y, int n,
-                                                          int hw, int c4n) {
+                                                          int hw, int c4n, const float *__restrict__ x_sinv) {
   const long long i = (long long)blockIdx.x * 256 + threadIdx.x;
   if (i >= (long long)n * c4n) return;
   const int cq = (int)(i % c4n);
@@ -97,7 +99,15 @@ __global__ __launch_bounds__(256) void avgpool_fwd_kernel(const T *__restrict__ 
     s.x += v.x; s.y += v.y; s.z += v.z; s.w += v.w;
   }
   const float inv = 1.f / (float)hw;
-  y[i] = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+  float4 o = make_float4(s.x * inv, s.y * inv, s.z * inv, s.w * inv);
+  if constexpr (std::is_same<T, sp_t>::value) {
+    // an sp map stored times 2^k: the mean comes back times its 2^-k (null = unscaled, and x 1.0f changes no bit)
+    if (x_sinv) {
+      const float k = *x_sinv;
+      o = make_float4(o.x * k, o.y * k, o.z * k, o.w * k);
+    }
+  }
+  y[i] = o;
 }
 
 template <typename T>
@@ -330,7 +340,7 @@ int mvg_maxpool3x3s2_bwd(const float *dy, const uint8_t *argmax, float *dx, int 
     hipStream_t st = (hipStream_t)stream;                                                                             \
     ProfScope ps(MVG_K_POOL, st, 0.0, (double)n * (Elem<T>::kBytes * hw + 4.0) * c);                                  \
     hipLaunchKernelGGL(avgpool_fwd_kernel<T>, dim3(ceil_div((long long)n * (c / 4), 256)), dim3(256), 0, st, x,       \
-                       (float4 *)y, n, hw, c / 4);                                                                    \
+                       (float4 *)y, n, hw, c / 4, (const float *)nullptr);                                            \
     return check_launch("avgpool_fwd");                                                                               \
   }                                                                                                                    \
   int mvg_avgpool_bwd##SUFFIX(const float *dy, T *dx, int n, int hw, int c, void *stream) {                           \
@@ -346,13 +356,22 @@ MVG_AVGPOOL_FACES(, float)
 MVG_AVGPOOL_FACES(_bf16, uint16_t)
 #undef MVG_AVGPOOL_FACES
 
-int mvg_avgpool_fwd_split(const void *x_sp, float *y, int n, int hw, int c, void *stream) {
+static int avgpool_fwd_split_impl(const void *x_sp, const float *x_sinv, float *y, int n, int hw, int c, void *stream) {
   MVG_REQUIRE(c % 8 == 0, "avgpool_split: c %% 8 != 0");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_POOL, st, 0.0, (double)n * (6.0 * hw + 4.0) * c);
   hipLaunchKernelGGL(avgpool_fwd_kernel<sp_t>, dim3(ceil_div((long long)n * (c / 4), 256)), dim3(256), 0, st, (const sp_t *)x_sp,
-                     (float4 *)y, n, hw, c / 4);
+                     (float4 *)y, n, hw, c / 4, x_sinv);
   return check_launch("avgpool_fwd_split");
+}
+
+int mvg_avgpool_fwd_split_scaled(const void *x_sp, const float *x_sinv, float *y, int n, int hw, int c, void *stream) {
+  MVG_REQUIRE(x_sp && y && n > 0 && hw > 0 && c > 0, "avgpool_split: x_sp and y are required, sizes positive");
+  return avgpool_fwd_split_impl(x_sp, x_sinv, y, n, hw, c, stream);
+}
+
+int mvg_avgpool_fwd_split(const void *x_sp, float *y, int n, int hw, int c, void *stream) {
+  return avgpool_fwd_split_impl(x_sp, nullptr, y, n, hw, c, stream);
 }
 
 int mvg_nchw_to_nhwc8_bf16(const float *src, uint16_t *dst, int n, int c, int h, int w, void *stream) {

@@ -166,7 +166,8 @@ def fuser_wgrad(img_feat, feat, rel, row_img, row_src, dy, dw, db, rows, cf, nve
 
 # ---- "split" operands: fp32 values as two fp16 pieces (+ a per-tensor power-of-two scale), fp32-accurate products on
 # the fp16 matrix cores.  An sp tensor is a float16 tensor [..., C/8, 2, 8]; its scale travels as the attribute
-# ``sinv`` - a 1-element fp32 DEVICE tensor holding 2^-k, or absent / None for unscaled tensors (activations).
+# ``sinv`` - a 1-element fp32 DEVICE tensor holding 2^-k, or absent / None for unscaled tensors (the image operand,
+# inference activations).  A view (``x[v]``) drops Python attributes: pass the whole tensor, or set ``sinv`` on the view.
 def _sinv(t: Optional[Tensor]):
     return _p(getattr(t, "sinv", None)) if t is not None else None
 
@@ -242,14 +243,20 @@ def conv_fprop_split(d: ConvDesc, x_sp: Tensor, w_sp: Tensor, y: Tensor, stats: 
 def conv_fprop_split_affine(d: ConvDesc, x_sp: Tensor, w_sp: Tensor, out: Tensor, scale: Tensor, shift: Tensor,
                             residual: Optional[Tensor], relu: bool):
     """Inference forward on the split kernels, BatchNorm folded: out = relu?(conv * scale + shift (+ residual)).
-    out / residual: fp32 tensors or (unscaled) sp tensors."""
+    out / residual: fp32 tensors or (unscaled) sp tensors - unscaled because running statistics give no z-score bound to
+    derive a scale from (act_scales serves training steps only): |activation| must stay below 65 504 on this path."""
+    assert getattr(residual, "sinv", None) is None, "conv_fprop_split_affine: the residual is read unscaled"
     check(lib().mvg_conv_fprop_split_affine(C.byref(d), _p(x_sp), _sinv(x_sp), _p(w_sp), _sinv(w_sp), _p(out), int(is_sp(out)), _p(scale),
                                             _p(shift), _p(residual), int(is_sp(residual)), int(relu), _s()), "conv_fprop_split_affine")
 
 
 def conv_dgrad_split(d: ConvDesc, dy_sp: Tensor, wt_sp: Tensor, dx: Tensor, addend: Optional[Tensor] = None,
                      relu_mask_sp: Optional[Tensor] = None):
-    assert relu_mask_sp is None or (is_sp(relu_mask_sp) and getattr(relu_mask_sp, "sinv", None) is None)
+    # relu_mask_sp is read for its SIGN only, so its (positive) scale is not needed - up to the format's flush: a positive value
+    # below fp16's smallest subnormal in the stored units (outside the dead band: below ~2^-39 of the tensor's bound) is stored as
+    # 0 and reads as "off", where mask bits taken in the forward would say "on".  The backbone does not use this form (it
+    # masks with bits or fma(y, scale, shift) > 0); the fusion block's hidden activations do, with a producer-side scale.
+    assert relu_mask_sp is None or is_sp(relu_mask_sp)
     check(lib().mvg_conv_dgrad_split(C.byref(d), _p(dy_sp), _sinv(dy_sp), _p(wt_sp), _sinv(wt_sp), _p(dx), _p(addend), _p(relu_mask_sp),
                                      _s()), "conv_dgrad_split")
 
@@ -359,13 +366,14 @@ def conv_wgrad_split(d: ConvDesc, x_sp: Tensor, dy_sp: Tensor, dw: Tensor, accum
     """defer (a list): with more than one pixel split, only the slabs are written and (slabs, dw, splits, accumulate) is appended
     for ONE wgrad_reduce_batch launch over the list (the caller's: at the end of a residual block, on the same stream)."""
     splits, ws = _wgrad_slabs(lib().mvg_conv_wgrad_splits_split, "conv_wgrad_splits_split", d, dw.numel(), dw.device)
-    assert getattr(x_sp, "sinv", None) is None, "conv_wgrad_split: the activation operand is stored unscaled"
+    # x_sp is read by VALUE: its 2^-k (a backbone activation's act_scales slot; None = unscaled) goes into the output scale
     if defer is not None and splits > 1:
-        check(lib().mvg_conv_wgrad_split_slabs(C.byref(d), _p(x_sp), _p(dy_sp), _sinv(dy_sp), _p(ws), splits, _s()), "conv_wgrad_split_slabs")
+        check(lib().mvg_conv_wgrad_split_slabs_xs(C.byref(d), _p(x_sp), _sinv(x_sp), _p(dy_sp), _sinv(dy_sp), _p(ws), splits, _s()),
+              "conv_wgrad_split_slabs")
         defer.append((ws, dw, splits, bool(accumulate)))
         return
-    check(lib().mvg_conv_wgrad_split(C.byref(d), _p(x_sp), _p(dy_sp), _sinv(dy_sp), _p(dw), _p(ws), splits, int(accumulate), _s()),
-          "conv_wgrad_split")
+    check(lib().mvg_conv_wgrad_split_xs(C.byref(d), _p(x_sp), _sinv(x_sp), _p(dy_sp), _sinv(dy_sp), _p(dw), _p(ws), splits,
+                                        int(accumulate), _s()), "conv_wgrad_split")
 
 
 def wgrad_reduce_batch(items: list):
@@ -387,9 +395,21 @@ def bn_apply_split(y, scale, shift, residual, relu, out_sp, groups, rows_per_gro
     bits = torch.empty(groups * rows_per_group * c // 4, dtype=torch.uint8, device=y.device) if want_bits else None
     rs, rh = residual_affine if residual_affine is not None else (None, None)
     res_sp = is_sp(residual)
-    check(lib().mvg_bn_apply_split(_p(y), _p(scale), _p(shift), _p(residual), int(res_sp), _p(rs), _p(rh), int(relu), _p(out_sp),
-                                   _p(bits), groups, rows_per_group, c, _s()), "bn_apply_split")
+    # out_sp.sinv / an sp residual's sinv (act_scales slots, or None = unscaled): the output is stored times its 2^k, the
+    # identity read back by value times its 2^-k; the mask bits come from the unscaled value
+    check(lib().mvg_bn_apply_split_scaled(_p(y), _p(scale), _p(shift), _p(residual), int(res_sp), _p(rs), _p(rh),
+                                          _sinv(residual) if res_sp else None, int(relu), _p(out_sp), _sinv(out_sp), _p(bits), groups,
+                                          rows_per_group, c, _s()), "bn_apply_split")
     return bits
+
+
+def act_scales(table: Tensor, n: int, slots: Tensor):
+    """slots[i] <- 2^-k of a training step's i-th sp activation, all from one single-workgroup launch.  table: [n, 4] int64
+    DEVICE tensor holding n 32-byte records {gamma, beta: pointers; c: int32; sqrt(n - 1): float32; ident, slot: int32, -1 =
+    none} - see mvg_act_scales."""
+    assert table.is_cuda and table.dtype == torch.int64 and table.is_contiguous() and table.shape == (n, 4)
+    assert slots.dtype == torch.float32 and slots.is_contiguous()
+    check(lib().mvg_act_scales(C.c_void_p(table.data_ptr()), n, _p(slots), slots.numel(), _s()), "act_scales")
 
 
 def bn_bwd_reduce_split(g, relu_bits, y, mean, invstd, groups, rows_per_group, c, s1, s2, dgamma, dbeta, accumulate, mx,
@@ -416,12 +436,14 @@ def bn_bwd_apply_split(g, y, mean, invstd, gamma, s1, s2, groups, rows_per_group
 
 
 def bn_relu_maxpool_fwd_split(y, scale, shift, pooled_sp, argmax, groups, n_per_group, h, w, c, ho, wo):
-    check(lib().mvg_bn_relu_maxpool_fwd_split(_p(y), _p(scale), _p(shift), _p(pooled_sp), _p(argmax), groups, n_per_group, h, w, c,
-                                              ho, wo, _s()), "bn_relu_maxpool_fwd_split")
+    """pooled_sp.sinv (an act_scales slot, or None = unscaled): the pooled map is stored times its 2^k."""
+    check(lib().mvg_bn_relu_maxpool_fwd_split_scaled(_p(y), _p(scale), _p(shift), _p(pooled_sp), _sinv(pooled_sp), _p(argmax), groups,
+                                                     n_per_group, h, w, c, ho, wo, _s()), "bn_relu_maxpool_fwd_split")
 
 
 def avgpool_fwd_split(x_sp, y, n, hw, c):
-    check(lib().mvg_avgpool_fwd_split(_p(x_sp), _p(y), n, hw, c, _s()), "avgpool_fwd_split")
+    """x_sp is read by value: the mean comes back times x_sp.sinv."""
+    check(lib().mvg_avgpool_fwd_split_scaled(_p(x_sp), _sinv(x_sp), _p(y), n, hw, c, _s()), "avgpool_fwd_split")
 
 
 # ---- Linear layers of the fusion block in the bf16 path: fp32 tensors, bf16 matrix product (weights = bf16 copies)
