@@ -621,6 +621,19 @@ int mvg_conv_dgrad_split_bnreduce(const mvg_conv_desc *d, const void *dy_sp, con
                                   const float *bn_mean, const float *bn_invstd, const float *relu_scale, const float *relu_shift,
                                   float *partials, float *s1, float *s2, float *dgamma, float *dbeta, int accumulate,
                                   float *mx, const float *bn_gamma, float *dx_dy_sinv, void *stream);
+/* mvg_bn_bwd_apply_split (g already masked, dy_sinv ready) and mvg_conv_dgrad_split_bnreduce of the same unit in ONE launch, for a
+ * 1x1 / stride 1 / pad 0 unit with cin = 64 or 128 (one column tile of backward-data: every dy element is consumed by exactly one
+ * workgroup) and cout % 32 == 0, cout <= 512: the loader forms dy = BatchNorm backward of (dz, y) with the unit's mean / invstd
+ * [groups][cout], gamma [cout] and sums un_s1 / un_s2 [groups][cout] over rows_per_group = n * ho * wo rows, times 2^k = 1 / *dy_sinv,
+ * multiplies it and WRITES it to dy_sp (an output here: the weight gradient reads it afterwards).  Everything from w_crsk_sp on is
+ * mvg_conv_dgrad_split_bnreduce's.  dy_sp, dx, the sums and mx hold the bits the two calls leave. */
+int mvg_conv_dgrad_split_bnapply_bnreduce(const mvg_conv_desc *d, void *dy_sp, const float *dy_sinv, const float *dz, const float *y,
+                                          const float *mean, const float *invstd, const float *gamma, const float *un_s1,
+                                          const float *un_s2, int64_t rows_per_group, const void *w_crsk_sp, const float *w_sinv,
+                                          float *dx, const float *addend, const float *bn_y, const uint8_t *bn_bits,
+                                          const float *bn_mean, const float *bn_invstd, const float *relu_scale,
+                                          const float *relu_shift, float *partials, float *s1, float *s2, float *dgamma, float *dbeta,
+                                          int accumulate, float *mx, const float *bn_gamma, float *dx_dy_sinv, void *stream);
 /* The 7x7 stride-2 stem (resnet.py:184, ResNet.forward :262) on the split kernels, "row-window" form: the 3-channel image
  * (stored NHWC with 4 channels) is rewritten as xw [images][h][w/2][8][4] in sp - window ox holds image columns 2 ox - 4 ..
  * 2 ox + 3, zero outside the image - and the stem becomes a 7 x 1 filter over 32 "channels" (vertical stride 2 / pad 3,

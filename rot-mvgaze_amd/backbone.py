@@ -28,6 +28,36 @@ BN_EPS, BN_MOMENTUM = 1e-5, 0.1          # nn.BatchNorm2d defaults (resnet.py:18
 IMAGE_MEAN, IMAGE_STD = (0.485, 0.456, 0.406), (0.229, 0.224, 0.225)      # main.py:38-39
 
 
+BN_APPLY_DGRAD_MAX_COUT = 512      # the merged launch keeps the unit's 5 x cout BatchNorm constants in LDS
+
+
+def bn_apply_dgrad_eligible(c: ConvSpec, *, split: bool, trained: bool, fused_in: bool, carries_reduce: bool,
+                            need_dimg: bool = False) -> bool:
+    """Whether unit ``c``'s BatchNorm-backward apply pass is formed inside its own backward-data launch
+    (mvg_conv_dgrad_split_bnapply_bnreduce) instead of running as a pass of its own.  All of:
+    split path and a training tape (not bf16, not MVG_SPLIT=0, not eval-mode BatchNorm, not a d(img) backward);
+    a 1x1 / stride 1 / pad 0 unit whose backward-data GEMM has ONE column tile (cin 64 or 128: every dy element is then
+    consumed by exactly one workgroup) and whose constants fit the kernel's table;
+    ``fused_in``: its gradient arrived masked, with the fused sums and a ready dy scale (``_Unit.fused_s12``);
+    ``carries_reduce``: its backward-data launch carries the fused reduce of the unit below."""
+    return bool(split and trained and not need_dimg and fused_in and carries_reduce
+                and c.k == 1 and c.stride == 1 and c.pad == 0 and c.cin in (64, 128)
+                and c.cout % 32 == 0 and c.cout <= BN_APPLY_DGRAD_MAX_COUT)
+
+
+def bn_apply_dgrad_units(spec: BackboneSpec, *, split: bool = True, bf16: bool = False, training: bool = True,
+                         need_dimg: bool = False, fuse_bn_split: bool = True, enabled: bool = True) -> List[str]:
+    """The conv names of ``spec`` that take the merged launch, in backward order: Backbone.backward's decision over the
+    architecture plan alone (no GPU).  It is taken for a block's LAST unit: that unit receives a fused gradient from the block
+    above (its first conv's backward-data launch, or its downsample branch's) - the network's last block gets its gradient
+    from the average pool - and its own launch carries the reduce of the unit below it."""
+    on = enabled and split and not bf16 and fuse_bn_split
+    nb = len(spec.blocks)
+    return [blk.convs[-1].name for bi, blk in reversed(list(enumerate(spec.blocks)))
+            if bn_apply_dgrad_eligible(blk.convs[-1], split=on, trained=training, fused_in=bi < nb - 1,
+                                       carries_reduce=len(blk.convs) > 1, need_dimg=need_dimg)]
+
+
 class GradSink:
     """Where parameter gradients go.  ``view(p)`` returns the tensor the kernels write into and
     ``accumulate(p)`` says whether they must add to it; ``publish(ps)`` is called once a group of
@@ -92,6 +122,11 @@ class Backbone:
         # stride-2 filter never touches as epilogue-only tiles.  (attribute False: separate reduce passes - the tests
         # compare the two.)
         self.fuse_bn_split = True
+        # split path, training: a 1x1 stride-1 unit whose backward-data GEMM has one column tile (ResNet-50's layer1 / layer2
+        # conv3) forms its dy in that launch's loader (bn_apply_dgrad_eligible; mvg_conv_dgrad_split_bnapply_bnreduce): no
+        # apply pass, the sp dy written once for the weight gradient.  (attribute False: the apply pass and the plain launch -
+        # the same bits; the tests and the A/B runs compare the two.)
+        self.fuse_bn_apply_dgrad = True
         # split path, training: the 7x7 stem on the split kernels too, in its "row-window" form (mvg_stem_fprop_split: the
         # image rewritten as [.., W/2, 8 columns x 4 channels] windows, a 7 x 1 filter over 32 channels, K = 224) instead
         # of the fp32-MFMA kernel on 4-channel taps (K = 196 at a fifth of the matrix rate).  Not when the caller wants
@@ -533,9 +568,11 @@ class Backbone:
         return feat, tape
 
     # ---------------------------------------------------------------- backward
-    def _bn_bwd(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink):
+    def _bn_bwd(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink, defer_apply: bool = False):
         """g = grad wrt the unit's output.  Returns (dy, dz): dy = grad wrt the conv output;
-        dz = g masked by the unit's ReLU (written in place into g) when the residual branch needs it."""
+        dz = g masked by the unit's ReLU (written in place into g) when the residual branch needs it.
+        defer_apply (a unit that bn_apply_dgrad_eligible accepted): dy is only allocated - the unit's backward-data launch
+        forms and writes it (dy.bn_apply holds what that launch needs)."""
         if not u.trained:
             return self._bn_bwd_eval(u, g, need_dz, sink)
         c = u.spec
@@ -545,6 +582,10 @@ class Backbone:
             # split path, fused: g arrived masked and the sums came with it; dy goes out in sp
             (s12, sinv), u.fused_s12 = u.fused_s12, None
             dy = ops.sp_empty(*u.y.shape, device=g.device)
+            if defer_apply:
+                dy.sinv = sinv
+                dy.bn_apply = (g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], u.rows)
+                return dy, (g if need_dz else None)
             ops.bn_bwd_apply_split(g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, None, s12[2], sinv)
             return dy, (g if need_dz else None)
         if u.fused_s12 is not None:
@@ -632,6 +673,13 @@ class Backbone:
 
     def _conv_bwd(self, u: _Unit, dy: Tensor, need_dx: bool, addend: Optional[Tensor], sink: GradSink,
                   fuse_for: Optional[_Unit] = None):
+        if getattr(dy, "bn_apply", None) is not None:
+            # dy does not exist yet: the backward-data launch forms it and writes it, then the weight gradient reads it
+            dx = torch.empty(ops.sp_shape(u.x_in), dtype=torch.float32, device=dy.device)
+            self._dgrad(u, dy, dx, addend, fuse_for, sink)
+            need_dx = False
+        else:
+            dx = None
         if self.overlap_wgrad and dy.is_cuda:
             side = self._side(dy.device)
             side.wait_stream(torch.cuda.current_stream())         # dy (and everything before it) is ready
@@ -645,7 +693,6 @@ class Backbone:
                 u.x_in.sinv.record_stream(side)
         else:
             self._wgrad(u, dy, sink)
-        dx = None
         if need_dx:
             dx = torch.empty(ops.sp_shape(u.x_in), dtype=torch.float32, device=dy.device) if u.split else torch.empty_like(u.x_in)
             self._dgrad(u, dy, dx, addend, fuse_for, sink)
@@ -724,6 +771,16 @@ class Backbone:
                 # (the fused reduce epilogue masks with U's bits or fma(U.y, scale, shift) > 0: no sp activation is read)
                 s12 = torch.empty(3, dx.shape[0], c.cout, dtype=torch.float32, device=dx.device)     # s1, s2, max |dz| per channel
                 sinv = torch.empty(1, dtype=torch.float32, device=dx.device)      # 2^-k of the dy that U's apply pass will write
+                pend = getattr(dy, "bn_apply", None)
+                if pend is not None:
+                    dz, y, mean, invstd, gamma, us1, us2, rows = pend
+                    dy.bn_apply = None
+                    ops.conv_dgrad_split_bnapply_bnreduce(u.desc, dy, dy.sinv, dz, y, mean, invstd, gamma, us1, us2, rows, u.w, dx,
+                                                          addend, U.y, U.relu_bits, U.mean, U.invstd,
+                                                          None if U.relu_bits is not None else U.relu_affine, s12[0], s12[1],
+                                                          sink.view(gp), sink.view(bp), acc, s12[2], gp.detach(), sinv)
+                    U.fused_s12 = (s12, sinv)
+                    return
                 ops.conv_dgrad_split_bnreduce(u.desc, dy, u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd,
                                               None if U.relu_bits is not None else U.relu_affine, s12[0], s12[1], sink.view(gp),
                                               sink.view(bp), acc, s12[2], gp.detach(), sinv)
@@ -761,8 +818,12 @@ class Backbone:
             # fused pool backward takes it for the first block)
             prev_last = units[blocks[bi - 1][0][-1]] if bi > 0 else None
             done: List[torch.nn.Parameter] = []
-            dy, dz = self._bn_bwd(last, g, True, sink)
-            d = self._conv_bwd(last, dy, True, None, sink, fuse_for=units[idx[-2]])
+            below = units[idx[-2]]
+            merge = self.fuse_bn_apply_dgrad and bn_apply_dgrad_eligible(
+                last.spec, split=last.split and not self.bf16, trained=last.trained, fused_in=last.fused_s12 is not None,
+                carries_reduce=below.split and self.fuse_bn_split, need_dimg=need_dimg)
+            dy, dz = self._bn_bwd(last, g, True, sink, defer_apply=merge)
+            d = self._conv_bwd(last, dy, True, None, sink, fuse_for=below)
             done += [P[last.spec.name + ".weight"], P[last.spec.bn + ".weight"], P[last.spec.bn + ".bias"]]
             last.y = last.out = None
             del dy

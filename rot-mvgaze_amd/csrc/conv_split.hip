@@ -292,11 +292,23 @@ __device__ __forceinline__ int sp_row_swz(int R) { return ((R >> 1) & 1) | (((R 
 //
 // STAGES = 2 (launches that leave a CU one or two workgroups - the fusion block's Linears, 48 - 336 tiles of up to 112 K-steps on
 // 256 CUs; every conv of a small batch - so that nobody covers a workgroup's waits): an explicit software pipeline, see the K loop.
-template <int BN, bool DGRAD, bool LIN = false, int WGM = 2, int STAGES = 1>
+//
+// BNA (backward-data of a 1x1 stride-1 unit whose GEMM has ONE column tile - ResNet-50's layer1 / layer2 conv3: K = cout wide,
+// N = cin <= 128 - with the fused reduce on board; IgemmParams::bna_*): the A operand dy does not exist yet.  The loader forms it
+// per K-step in registers - thread t: chunk t & 3 of rows t >> 2 and 64 + (t >> 2), so four lanes cover a row's 128-byte line of
+// dz and of y; dy = bn_dy(...) * 2^k exactly as bn_bwd_apply_sp_kernel (bn.hip) computes it; the unit's 5 x cout per-channel
+// constants wait in LDS behind the row table - writes the two fp16 pieces into the slots the fragment reads expect, and stores the
+// same 32 bytes to the global sp dy for the weight gradient.  Every dy element belongs to exactly one workgroup and one K-step:
+// the apply pass's 3 passes over the map (read dz, read y, write dy) and this launch's read of dy become read dz, read y, write
+// dy.  The weights keep their DMA path.  The A fragments
+// hold the bits the two-launch form reads back from memory, in the same K order: results are those of that form, bit for bit.
+constexpr int BNA_MAX_C = 512;                                  // channels of the constants' LDS table
+template <int BN, bool DGRAD, bool LIN = false, int WGM = 2, int STAGES = 1, bool BNA = false>
 __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4) void igemm_split16_kernel(IgemmParams p) {
   constexpr int BM = 64 * WGM, WGN = 4 / WGM, NW = 4;
   static_assert(WGM == 2 || (WGM == 4 && BN == 64), "tiles: 128 x BN (2 x 2 waves) or 256 x 64 (4 x 1)");
   static_assert(STAGES == 1 || STAGES == 2, "one LDS stage, or the two-stage pipeline");
+  static_assert(!BNA || (DGRAD && !LIN && WGM == 2 && STAGES == 1), "the dy-forming loader: backward-data, 128-row tiles, one stage");
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
   constexpr int TM = WTM / 16, TN = WTN / 16;
   constexpr int SLOTS = 4 * SP_NP;                            // 16-byte slots per LDS row (8)
@@ -307,7 +319,8 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4)
   static_assert(QA % NW == 0 && (NQ - QA) % NW == 0, "whole instructions per wave");
   constexpr int EPI_B = bf16_epilogue_bytes<BM, BN, WGM, DGRAD>();          // one wave row (64 tile rows) per staging pass
   constexpr int INFO_OFF = STAGES * STAGE_B > EPI_B ? STAGES * STAGE_B : EPI_B;  // row table behind the stages / the epilogue tile
-  constexpr int SMEM_B = INFO_OFF + BM * 8;
+  constexpr int BNK_OFF = INFO_OFF + BM * 8;                  // BNA: [5][src_c] mean, invstd, gamma, s1, s2 of this group
+  constexpr int SMEM_B = BNK_OFF + (BNA ? 5 * BNA_MAX_C * 4 : 0);
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_B];
 
   const int tid = threadIdx.x;
@@ -346,6 +359,18 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4)
       msk |= (unsigned)(((unsigned)iy < (unsigned)p.src_h) & ((unsigned)ix < (unsigned)p.src_w)) << t;
     }
     rowinfo[tid] = make_uint2(base, ok ? msk : 0u);
+  }
+  if constexpr (BNA) {
+    float *bnk = reinterpret_cast<float *>(smem + BNK_OFF);
+    const int C = p.src_c;
+    for (int i = tid; i < C; i += 256) {
+      const long long gc = (long long)g * C + i;
+      bnk[i] = p.bna_mean[gc];
+      bnk[C + i] = p.bna_invstd[gc];
+      bnk[2 * C + i] = p.bna_gamma[i];
+      bnk[3 * C + i] = p.bna_s1[gc];
+      bnk[4 * C + i] = p.bna_s2[gc];
+    }
   }
   __syncthreads();
   // ---- the instructions this wave issues: Q = wave + 4 i; lane -> linear slot 64 Q + lane -> (row, slot in row);
@@ -388,10 +413,12 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4)
       const int btap = (c.tap_r0 + p.tap_step * fru) * p.s + c.tap_s0 + p.tap_step * fsu;
       kb = (unsigned)(btap * p.src_c + chb) * (unsigned)SP_BYTES;
     }
+    if constexpr (!BNA) {
 #pragma unroll
-    for (int i = 0; i < A_PER; ++i) {
-      const bool ok = ((a_vmask[i] >> tap_u) & 1u) != 0u;
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_vp)(smem + stage_off + (wave + NW * i) * 1024), 16, (int)pred_off(a_base[i] + sdelta, ok), 0, 0, 0);
+      for (int i = 0; i < A_PER; ++i) {
+        const bool ok = ((a_vmask[i] >> tap_u) & 1u) != 0u;
+        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_vp)(smem + stage_off + (wave + NW * i) * 1024), 16, (int)pred_off(a_base[i] + sdelta, ok), 0, 0, 0);
+      }
     }
 #pragma unroll
     for (int i = 0; i < B_PER; ++i)
@@ -433,7 +460,86 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4)
   };
   // smallest terms first: (a1 b2, a2 b1), a1 b1
   auto products = [&](const f16x8 (&av)[SP_NP][TM], const f16x8 (&bv)[SP_NP][TN]) { SPLIT16_ONE(0, 1) SPLIT16_ONE(1, 0) SPLIT16_ONE(0, 0) };
-  if constexpr (STAGES == 1) {
+  if constexpr (BNA) {
+    // (1x1, stride 1: the GEMM's rows are dy's pixels, K-step kt = channels 32 kt .. 32 kt + 31)
+    const int C = p.src_c;
+    const int a_cc = tid & 3, a_r0 = tid >> 2;
+    const long long grow0 = (long long)g * c.rows_per_group;
+    const __amdgpu_buffer_rsrc_t rs_dz = make_rsrc(p.bna_dz + grow0 * C, 4ll * c.rows_per_group * C);
+    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(p.bna_y + grow0 * C, 4ll * c.rows_per_group * C);
+    uint4 *dy_out = reinterpret_cast<uint4 *>(const_cast<float *>(p.a)) + grow0 * C / 4;      // 4 bytes per element
+    const float inv_rows = p.bna_inv_rows;
+    const float dsc = 1.f / *p.a_sinv;                        // 2^k (exact: a power of two)
+    bool a_ok[2];
+    unsigned a_goff[2];                                        // byte offset of (row, chunk) in the group's fp32 maps = in its sp dy
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const long long m = (long long)mtile * BM + a_r0 + 64 * i;
+      a_ok[i] = m < c.rows_per_group;
+      a_goff[i] = pred_off((unsigned)m * (unsigned)C * 4u + 32u * (unsigned)a_cc, a_ok[i]);
+    }
+    float4 dzv[2][2], yv[2][2];
+    auto a_load = [&](int kt) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const unsigned off = a_goff[i] + 128u * (unsigned)kt;
+        dzv[i][0] = buf_ld16(rs_dz, off);
+        dzv[i][1] = buf_ld16(rs_dz, off + 16u);
+        yv[i][0] = buf_ld16(rs_y, off);
+        yv[i][1] = buf_ld16(rs_y, off + 16u);
+      }
+    };
+    // the next K-step's dz and y in flight while this one is multiplied: 32 more live registers, which the 128-column tile
+    // (64 accumulators, 64 fragment registers) does not have at three workgroups per CU (168) - it loads at the top instead
+    constexpr bool PREFETCH = BN == 64;
+    if (PREFETCH) a_load(0);
+    for (int kt = 0; kt < KT; ++kt) {
+      issue(kt, 0);                                            // the weights: DMA
+      if (!PREFETCH) a_load(kt);
+      uint4 q[2][SP_NP];
+      {
+        const float *kc = reinterpret_cast<const float *>(smem + BNK_OFF) + kt * SP_BK + a_cc * 8;
+        float mu[8], is[8], ga[8], sa[8], sb[8];
+        ld8(kc, mu);
+        ld8(kc + C, is);
+        ld8(kc + 2 * C, ga);
+        ld8(kc + 3 * C, sa);
+        ld8(kc + 4 * C, sb);
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const float d[8] = {dzv[i][0].x, dzv[i][0].y, dzv[i][0].z, dzv[i][0].w, dzv[i][1].x, dzv[i][1].y, dzv[i][1].z, dzv[i][1].w};
+          const float v[8] = {yv[i][0].x, yv[i][0].y, yv[i][0].z, yv[i][0].w, yv[i][1].x, yv[i][1].y, yv[i][1].z, yv[i][1].w};
+          float o[8];
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            const float t = bn_dy(d[k], v[k], mu[k], is[k], ga[k], sa[k], sb[k], inv_rows) * dsc;
+            o[k] = a_ok[i] ? t : 0.f;                          // rows beyond the group: the zeros the DMA loader reads there
+          }
+          split2_chunk(o, q[i][0], q[i][1]);
+          const int R = a_r0 + 64 * i;
+#pragma unroll
+          for (int pc = 0; pc < SP_NP; ++pc)
+            *reinterpret_cast<uint4 *>(smem + R * ROWB + (((2 * a_cc + pc) ^ sp_row_swz(R)) << 4)) = q[i][pc];
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        if (a_ok[i]) {
+          uint4 *dst = dy_out + ((a_goff[i] + 128u * (unsigned)kt) >> 4);
+          dst[0] = q[i][0];
+          dst[1] = q[i][1];
+        }
+      if (PREFETCH && kt + 1 < KT) a_load(kt + 1);             // in flight while this K-step is multiplied
+      {
+        f16x8 av[SP_NP][TM], bv[SP_NP][TN];
+        load_frags(smem, av, bv);
+        products(av, bv);
+      }
+      __syncthreads();                                         // everyone is done reading before the next K-step is written
+    }
+  } else if constexpr (STAGES == 1) {
     for (int kt = 0; kt < KT; ++kt) {
       issue(kt, 0);
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -795,7 +901,7 @@ static int validate_split(const mvg_conv_desc *d) {
 static int split_tile_rows(int ncols, int taps, long long rows) { return (ncols < 128 && taps > 1 && rows >= 65536) ? 256 : SP_BM; }
 
 template <bool DGRAD>
-static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin = false, int bm = SP_BM) {
+static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin = false, int bm = SP_BM, bool bna = false) {
   // (128 x 64 tiles for the short-K, write-heavy 1x1 layers - 64 -> 256 at 56 x 56 and the like - were measured in round 4:
   // within 2 % of 128 x 128 on every such shape, forward and backward-data)
   int bn = p.ncols >= 128 ? 128 : 64;
@@ -845,6 +951,14 @@ static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin = false, 
   int kt_max = 0;
   for (int i = 0; i < p.ncls; ++i) kt_max = p.cls[i].KT > kt_max ? p.cls[i].KT : kt_max;
   const bool pipelined = tiles <= 2LL * compute_cus() || (tiles <= 4LL * compute_cus() && kt_max >= 48);
+  if constexpr (DGRAD) {
+    if (bna) {               // dy formed in the loader (same tiles as the DMA kernels: the fused reduce's partials are theirs)
+      MVG_REQUIRE(!lin && bm == SP_BM && p.ntiles == 1 && p.ncls == 1, "split conv: the dy-forming loader takes one column tile");
+      if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, true, false, 2, 1, true>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((igemm_split16_kernel<64, true, false, 2, 1, true>), grid, block, 0, st, p);
+      return check_launch("conv_dgrad_split_bnapply");
+    }
+  }
   if (lin) {                 // a Linear of the fusion block: the epilogue's scale / abs-max features compiled in
     if (bn == 128 && pipelined) hipLaunchKernelGGL((igemm_split16_kernel<128, DGRAD, true, 2, 2>), grid, block, 0, st, p);
     else if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, DGRAD, true>), grid, block, 0, st, p);
@@ -1005,9 +1119,14 @@ struct SplitBnFuse {       // fused BatchNorm-backward reduce of the unit whose 
   int part_rows;
 };
 
+struct SplitBnApply {      // the launch forms its own dy (IgemmParams::bna_*): the unit's BatchNorm-backward apply pass
+  const float *dz, *y, *mean, *invstd, *gamma, *s1, *s2;
+  long long rows_per_group;
+};
+
 static int dgrad_split_impl(const mvg_conv_desc *d, const void *dy_sp, const float *dy_sinv, const void *w_crsk_sp, const float *w_sinv,
                             float *dx, const float *addend, void *stream, const SplitBnFuse *bnf, const void *relu_mask_sp = nullptr,
-                            bool lin_kernel = false, float *out_absmax = nullptr) {
+                            bool lin_kernel = false, float *out_absmax = nullptr, const SplitBnApply *bna = nullptr) {
   if (validate_split(d)) return 2;
   IgemmParams p;
   memset(&p, 0, sizeof(p));
@@ -1030,18 +1149,29 @@ static int dgrad_split_impl(const mvg_conv_desc *d, const void *dy_sp, const flo
     p.bn_part = bnf->part;
     p.bn_part_rows = bnf->part_rows;
   }
+  if (bna) {
+    p.bna_dz = bna->dz;
+    p.bna_y = bna->y;
+    p.bna_mean = bna->mean;
+    p.bna_invstd = bna->invstd;
+    p.bna_gamma = bna->gamma;
+    p.bna_s1 = bna->s1;
+    p.bna_s2 = bna->s2;
+    p.bna_inv_rows = 1.0f / (float)bna->rows_per_group;       // mvg_bn_bwd_apply_split's
+  }
   if (dgrad_geometry(p, d, SP_BYTES, SP_BYTES, "split conv")) return 2;
   MVG_REQUIRE((long long)d->n * d->h * d->w * d->cin < (1ll << 31), "split conv: a group of dx exceeds 2^31 elements");
   const double flops = 2.0 * d->groups * (double)d->n * d->ho * d->wo * d->cout * d->r * d->s * d->cin;
   // (with the BatchNorm reduce on board the launch also reads that unit's y and mask bits: its algorithmic bytes)
   const double bytes = (double)SP_BYTES * (d->groups * (double)d->n * d->ho * d->wo * d->cout + (double)d->cout * d->r * d->s * d->cin) +
-                       (bnf ? 8.25 : 4.0) * d->groups * (double)d->n * d->h * d->w * d->cin;
+                       (bnf ? 8.25 : 4.0) * d->groups * (double)d->n * d->h * d->w * d->cin +
+                       (bna ? 8.0 : 0.0) * d->groups * (double)d->n * d->ho * d->wo * d->cout;       // dz and y read, dy written not read
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_DGRAD : MVG_K_CONV_DGRAD, (hipStream_t)stream, flops, bytes);
   if (int e = dgrad_classes(p, d, bnf != nullptr, 4, dx, addend, (hipStream_t)stream)) return e;
   if (p.ncls == 0) return 0;
   return launch_igemm_split<true>(p, (hipStream_t)stream, lin_kernel,
-                                  lin_kernel ? SP_BM : split_tile_rows(d->cin, d->r * d->s, (long long)d->n * d->h * d->w));
+                                  lin_kernel ? SP_BM : split_tile_rows(d->cin, d->r * d->s, (long long)d->n * d->h * d->w), bna != nullptr);
 }
 
 int mvg_conv_dgrad_split(const mvg_conv_desc *d, const void *dy_sp, const float *dy_sinv, const void *w_crsk_sp, const float *w_sinv,
@@ -1069,6 +1199,36 @@ int mvg_conv_dgrad_split_bnreduce(const mvg_conv_desc *d, const void *dy_sp, con
   MVG_REQUIRE(P > 0, "dgrad_split_bnreduce: bad descriptor");
   const SplitBnFuse f = {bn_y, bn_bits, bn_mean, bn_invstd, relu_scale, relu_shift, partials, mx ? 3 : 2};
   if (dgrad_split_impl(d, dy_sp, dy_sinv, w_crsk_sp, w_sinv, dx, addend, stream, &f)) return 1;
+  ProfScope ps(MVG_K_BN_BWD_REDUCE, (hipStream_t)stream, 0.0, 8.0 * d->groups * (double)P * d->cin);
+  return bn_bwd_finalize_launch(partials, d->groups, P, d->cin, s1, s2, dgamma, dbeta, accumulate, (hipStream_t)stream, mx, nullptr, nullptr,
+                                bn_gamma, bn_invstd, (long long)d->n * d->h * d->w, dx_dy_sinv);
+}
+
+int mvg_conv_dgrad_split_bnapply_bnreduce(const mvg_conv_desc *d, void *dy_sp, const float *dy_sinv, const float *dz, const float *y,
+                                          const float *mean, const float *invstd, const float *gamma, const float *un_s1,
+                                          const float *un_s2, int64_t rows_per_group, const void *w_crsk_sp, const float *w_sinv,
+                                          float *dx, const float *addend, const float *bn_y, const uint8_t *bn_bits,
+                                          const float *bn_mean, const float *bn_invstd, const float *relu_scale,
+                                          const float *relu_shift, float *partials, float *s1, float *s2, float *dgamma, float *dbeta,
+                                          int accumulate, float *mx, const float *bn_gamma, float *dx_dy_sinv, void *stream) {
+  MVG_REQUIRE(d && dy_sp && dz && y && mean && invstd && gamma && un_s1 && un_s2 && w_crsk_sp && dx,
+              "dgrad_split_bnapply_bnreduce: null argument");
+  MVG_REQUIRE(dy_sinv, "dgrad_split_bnapply_bnreduce: dy_sinv (the 2^-k the reduce pass left for this unit's dy) is required");
+  MVG_REQUIRE(d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0, "dgrad_split_bnapply_bnreduce: 1x1, stride 1, pad 0 only");
+  MVG_REQUIRE(d->cin == 64 || d->cin == 128, "dgrad_split_bnapply_bnreduce: cin must be 64 or 128 (one column tile; got %d)", d->cin);
+  MVG_REQUIRE(d->cout % 32 == 0 && d->cout <= BNA_MAX_C, "dgrad_split_bnapply_bnreduce: cout must be a multiple of 32, at most %d (got %d)",
+              BNA_MAX_C, d->cout);
+  MVG_REQUIRE(rows_per_group == (int64_t)d->n * d->ho * d->wo, "dgrad_split_bnapply_bnreduce: rows_per_group is not n * ho * wo");
+  MVG_REQUIRE(bn_y && bn_mean && bn_invstd && partials && s1 && s2, "dgrad_split_bnapply_bnreduce: null argument");
+  MVG_REQUIRE((bn_gamma == nullptr) == (dx_dy_sinv == nullptr) && (!dx_dy_sinv || mx),
+              "dgrad_split_bnapply_bnreduce: bn_gamma, dx_dy_sinv (and mx) go together");
+  MVG_REQUIRE(!(bn_bits && relu_scale) && ((relu_scale == nullptr) == (relu_shift == nullptr)),
+              "dgrad_split_bnapply_bnreduce: give the ReLU mask either as bits or as (relu_scale, relu_shift)");
+  const int P = mvg_conv_dgrad_bn_partials_split(d);
+  MVG_REQUIRE(P > 0, "dgrad_split_bnapply_bnreduce: bad descriptor");
+  const SplitBnFuse f = {bn_y, bn_bits, bn_mean, bn_invstd, relu_scale, relu_shift, partials, mx ? 3 : 2};
+  const SplitBnApply a = {dz, y, mean, invstd, gamma, un_s1, un_s2, (long long)rows_per_group};
+  if (dgrad_split_impl(d, dy_sp, dy_sinv, w_crsk_sp, w_sinv, dx, addend, stream, &f, nullptr, false, nullptr, &a)) return 1;
   ProfScope ps(MVG_K_BN_BWD_REDUCE, (hipStream_t)stream, 0.0, 8.0 * d->groups * (double)P * d->cin);
   return bn_bwd_finalize_launch(partials, d->groups, P, d->cin, s1, s2, dgamma, dbeta, accumulate, (hipStream_t)stream, mx, nullptr, nullptr,
                                 bn_gamma, bn_invstd, (long long)d->n * d->h * d->w, dx_dy_sinv);

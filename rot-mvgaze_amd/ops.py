@@ -349,6 +349,24 @@ def conv_dgrad_split_bnreduce(d: ConvDesc, dy_sp, wt_sp, dx, addend, bn_y, bn_bi
           "conv_dgrad_split_bnreduce")
 
 
+def conv_dgrad_split_bnapply_bnreduce(d: ConvDesc, dy_sp, dy_sinv, dz, y, mean, invstd, gamma, un_s1, un_s2, rows_per_group, wt_sp, dx,
+                                      addend, bn_y, bn_bits, bn_mean, bn_invstd, relu_affine, s1, s2, dgamma, dbeta, accumulate: bool,
+                                      mx: Optional[Tensor] = None, bn_gamma: Optional[Tensor] = None,
+                                      dx_dy_sinv: Optional[Tensor] = None):
+    """bn_bwd_apply_split (dz already masked, ``dy_sinv`` left by the reduce pass) + conv_dgrad_split_bnreduce of a 1x1 stride-1
+    unit with cin 64 / 128 in ONE launch: the backward-data loader forms dy, uses it and writes it to ``dy_sp`` (an output:
+    the weight gradient's operand; dy_sp.sinv = dy_sinv)."""
+    P = conv_dgrad_bn_partials_split(d)
+    part = torch.empty(d.groups * P * 3 * d.cin, dtype=torch.float32, device=dx.device)
+    rs, rh = relu_affine if relu_affine is not None else (None, None)
+    dy_sp.sinv = dy_sinv
+    check(lib().mvg_conv_dgrad_split_bnapply_bnreduce(C.byref(d), _p(dy_sp), _p(dy_sinv), _p(dz), _p(y), _p(mean), _p(invstd), _p(gamma),
+                                                      _p(un_s1), _p(un_s2), rows_per_group, _p(wt_sp), _sinv(wt_sp), _p(dx), _p(addend),
+                                                      _p(bn_y), _p(bn_bits), _p(bn_mean), _p(bn_invstd), _p(rs), _p(rh), _p(part), _p(s1),
+                                                      _p(s2), _p(dgamma), _p(dbeta), int(accumulate), _p(mx), _p(bn_gamma),
+                                                      _p(dx_dy_sinv), _s(True)), "conv_dgrad_split_bnapply_bnreduce")
+
+
 def conv_dgrad_bf16_bnreduce(d: ConvDesc, dy, wt, dx, addend, bn_y, bn_bits, bn_mean, bn_invstd, relu_affine, s1, s2, dgamma, dbeta,
                              accumulate: bool):
     """conv_dgrad (bf16 storage) + the BatchNorm-backward reduce pass of the unit whose output gradient dx is, in one launch."""

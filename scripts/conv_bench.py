@@ -90,6 +90,17 @@ for (cin, cout, k, st, pad, h), cnt in shapes.items():
         mx = torch.empty(G, cin, device=dev)
         tdf = timeit(lambda: ops.conv_dgrad_split_bnreduce(d, gys, wts, dx, None, x, bits, mean, invstd, None, s12[0], s12[1], dgb[0], dgb[1], False, mx))
         fbytes = 4.0 * (gy.numel() + 2 * x.numel()) + bits.numel()
+        if k == 1 and st == 1 and cin in (64, 128) and cout <= 512:
+            # the units whose backward-data loader forms dy (mvg_conv_dgrad_split_bnapply_bnreduce): the pair it replaces
+            # - the unit's BatchNorm apply pass, then backward-data + reduce - against the merged launch
+            uc = [torch.rand(G, cout, device=dev) + 0.5 for _ in range(4)]
+            gam, us, sv, dys = torch.rand(cout, device=dev) + 0.5, torch.rand(G, cout, device=dev), torch.ones(1, device=dev), ops.sp_empty(G, rows, cout, device=dev)
+            def pair():
+                ops.bn_bwd_apply_split(gy, y, uc[0], uc[1], gam, uc[2], uc[3], G, rows, cout, dys, None, us, sv)
+                ops.conv_dgrad_split_bnreduce(d, dys, wts, dx, None, x, bits, mean, invstd, None, s12[0], s12[1], dgb[0], dgb[1], False, mx)
+            tp = timeit(pair)
+            tm = timeit(lambda: ops.conv_dgrad_split_bnapply_bnreduce(d, dys, sv, gy, y, uc[0], uc[1], gam, uc[2], uc[3], rows, wts, dx, None, x, bits, mean, invstd, None, s12[0], s12[1], dgb[0], dgb[1], False, mx))
+            print(f"{cin:5d} {cout:5d} {k} {st} {h:4d} {cnt:3d} | BN apply + dgrad + reduce {tp*1e3:.3f} ms -> dy formed in the dgrad loader {tm*1e3:.3f} ms ({4.0*(3*gy.numel()+2*x.numel())/tm/1e9:.0f} GB/s of dz, y, dy, dx, y')")
     else:
         tf = timeit(lambda: ops.conv_fprop(d, x, w, y, None, False, stats))
         td = timeit(lambda: ops.conv_dgrad(d, gy, wt, dx)) if cin > 8 else float("nan")
