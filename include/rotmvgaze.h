@@ -634,6 +634,20 @@ int mvg_conv_dgrad_split_bnapply_bnreduce(const mvg_conv_desc *d, void *dy_sp, c
                                           const float *bn_mean, const float *bn_invstd, const float *relu_scale,
                                           const float *relu_shift, float *partials, float *s1, float *s2, float *dgamma, float *dbeta,
                                           int accumulate, float *mx, const float *bn_gamma, float *dx_dy_sinv, void *stream);
+/* mvg_bn_apply_split_scaled (residual + ReLU) of the unit that PRODUCES a conv's input and mvg_conv_fprop_split of that conv in ONE
+ * launch, for a 1x1 / stride 1 / pad 0 conv with cout = 64 or 128 (one column tile of the forward GEMM: every input element is
+ * consumed by exactly one workgroup) and cin % 32 == 0, cin <= 512 - a residual block's first conv after a bottleneck: the loader
+ * forms relu(bn_y * scale + shift + residual) with the producer's scale / shift [groups][cin]; the residual [groups][n][h][w][cin] is
+ * an sp identity (residual_sp = 1; read times *res_sinv, NULL = 1) or the raw fp32 downsample output with res_scale / res_shift
+ * [groups][cin]; multiplies it and WRITES it times 1 / *out_sinv to out_sp (an output here: later readers find it as the apply pass
+ * leaves it), and the ReLU mask to relu_bits (may be NULL).  Everything from w_sp on is mvg_conv_fprop_split's.  out_sp, relu_bits,
+ * y and stats hold the bits the two calls leave.  The launch runs the single-stage K loop: mvg_conv_fprop_split_stages tells which
+ * form mvg_conv_fprop_split picks for a descriptor on this device (1 = single-stage, 2 = two-stage pipeline, -1 = bad descriptor). */
+int mvg_conv_fprop_split_stages(const mvg_conv_desc *d);
+int mvg_conv_fprop_split_bnapply(const mvg_conv_desc *d, void *out_sp, const float *out_sinv, const float *bn_y, const float *scale,
+                                 const float *shift, const void *residual, int residual_sp, const float *res_scale,
+                                 const float *res_shift, const float *res_sinv, uint8_t *relu_bits, const void *w_sp,
+                                 const float *w_sinv, float *y, float *stats, void *stream);
 /* The 7x7 stride-2 stem (resnet.py:184, ResNet.forward :262) on the split kernels, "row-window" form: the 3-channel image
  * (stored NHWC with 4 channels) is rewritten as xw [images][h][w/2][8][4] in sp - window ox holds image columns 2 ox - 4 ..
  * 2 ox + 3, zero outside the image - and the stem becomes a 7 x 1 filter over 32 "channels" (vertical stride 2 / pad 3,

@@ -99,6 +99,8 @@ SIGNATURES = {
     "mvg_conv_dgrad_bn_partials_split": (_I, [_D]),
     "mvg_conv_dgrad_split_bnreduce": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mvg_conv_dgrad_split_bnapply_bnreduce": (_I, [_D] + [_P] * 9 + [_I64] + [_P] * 15 + [_I, _P, _P, _P, _P]),
+    "mvg_conv_fprop_split_stages": (_I, [_D]),
+    "mvg_conv_fprop_split_bnapply": (_I, [_D] + [_P] * 6 + [_I] + [_P] * 9),
     "mvg_conv_wgrad_splits_split": (_I, [_D]),
     "mvg_conv_wgrad_split": (_I, [_D, _P, _P, _P, _P, _P, _I, _I, _P]),
     "mvg_conv_wgrad_split_slabs": (_I, [_D, _P, _P, _P, _P, _I, _P]),

@@ -58,6 +58,35 @@ def bn_apply_dgrad_units(spec: BackboneSpec, *, split: bool = True, bf16: bool =
                                        carries_reduce=len(blk.convs) > 1, need_dimg=need_dimg)]
 
 
+BN_APPLY_FPROP_MAX_CIN = 512       # the merged forward launch keeps the producer's (and the residual's) scale / shift in LDS
+
+
+def bn_apply_fprop_eligible(producer: ConvSpec, consumer: ConvSpec, *, split: bool, trained: bool, residual: bool = True,
+                            relu: bool = True, single_stage: bool = True) -> bool:
+    """Whether the BatchNorm apply pass of ``producer`` - a residual block's LAST unit - is formed inside the forward launch of
+    ``consumer`` - the NEXT block's first conv (mvg_conv_fprop_split_bnapply) - instead of running as a pass of its own.  All of:
+    split path and a training forward on batch statistics (not bf16, not MVG_SPLIT=0, not eval-mode BatchNorm);
+    the producer adds a residual and applies the ReLU;
+    the consumer is 1x1 / stride 1 / pad 0 with cout 64 or 128: its forward GEMM has ONE column tile, so every element of the
+    block output is consumed by exactly one workgroup; cin <= 512: the constants fit the kernel's table;
+    ``single_stage``: the launch plan gives the consumer the single-stage K loop (ops.conv_fprop_split_stages: the merged launch
+    has no two-stage form)."""
+    return bool(split and trained and residual and relu and single_stage
+                and consumer.k == 1 and consumer.stride == 1 and consumer.pad == 0 and consumer.cout in (64, 128)
+                and consumer.cin == producer.cout and consumer.cin % 32 == 0 and consumer.cin <= BN_APPLY_FPROP_MAX_CIN)
+
+
+def bn_apply_fprop_pairs(spec: BackboneSpec, *, split: bool = True, bf16: bool = False, training: bool = True, enabled: bool = True,
+                         single_stage: Optional[Callable[[ConvSpec], bool]] = None) -> List[tuple]:
+    """The (producer, consumer) conv names of ``spec`` that take the merged forward launch, in forward order: Backbone.forward's
+    decision over the architecture plan alone (no GPU).  single_stage(consumer) answers the launch-plan condition, which
+    depends on the batch and the device (None: met - every such launch of a C3 / C4 step is single-stage)."""
+    on = enabled and split and not bf16
+    return [(a.convs[-1].name, b.convs[0].name) for a, b in zip(spec.blocks[:-1], spec.blocks[1:])
+            if bn_apply_fprop_eligible(a.convs[-1], b.convs[0], split=on, trained=training,
+                                       single_stage=True if single_stage is None else single_stage(b.convs[0]))]
+
+
 class GradSink:
     """Where parameter gradients go.  ``view(p)`` returns the tensor the kernels write into and
     ``accumulate(p)`` says whether they must add to it; ``publish(ps)`` is called once a group of
@@ -127,6 +156,11 @@ class Backbone:
         # apply pass, the sp dy written once for the weight gradient.  (attribute False: the apply pass and the plain launch -
         # the same bits; the tests and the A/B runs compare the two.)
         self.fuse_bn_apply_dgrad = True
+        # split path, training: a residual block's output whose first reader is the next block's 1x1 stride-1 conv1 with one column
+        # tile (ResNet-50's layer1 / layer2: six block outputs) is formed by that conv's forward loader (bn_apply_fprop_eligible;
+        # mvg_conv_fprop_split_bnapply): no apply pass, the sp output written once for its later readers.  (attribute False: the
+        # apply pass and the plain launch - the same bits; the tests and the A/B runs compare the two.)
+        self.fuse_bn_apply_fprop = True
         # split path, training: the 7x7 stem on the split kernels too, in its "row-window" form (mvg_stem_fprop_split: the
         # image rewritten as [.., W/2, 8 columns x 4 channels] windows, a 7 x 1 filter over 32 channels, K = 224) instead
         # of the fp32-MFMA kernel on 4-channel taps (K = 196 at a fifth of the matrix rate).  Not when the caller wants
@@ -304,12 +338,15 @@ class Backbone:
     # ---------------------------------------------------------------- forward
     def _unit_fwd(self, c: ConvSpec, x: Tensor, G: int, N: int, H: int, W: int, training: bool, relu: bool,
                   residual: Optional[Tensor], tape: Optional[list], pool: bool = False, residual_affine=None,
-                  defer_apply: bool = False):
+                  defer_apply: bool = False, next_conv: Optional[ConvSpec] = None, pending_apply: Optional[tuple] = None):
         """conv -> BatchNorm (-> + residual) (-> ReLU).  pool=True (the stem): the 3x3/2 max pool is
         fused behind the ReLU and (pooled, argmax) is returned; the normalised map is not stored.
         defer_apply (the downsample branch): stop after the statistics and return (y, (scale, shift)) - the
         normalisation is applied by the consumer, the block's last unit, which takes them as
-        residual / residual_affine; the normalised downsample map is never written."""
+        residual / residual_affine; the normalised downsample map is never written.
+        next_conv (a block's last unit: the next block's first conv): when bn_apply_fprop_eligible accepts the pair, this unit's
+        apply pass is NOT launched - (out, pending) is returned, out allocated and recorded on the tape as usual, and the next
+        block's first unit takes ``pending`` as pending_apply: its forward launch forms, uses and writes ``x`` (= that out)."""
         bf = self.bf16
         cin = (8 if bf else 4) if c.cin == 3 else c.cin
         d = ConvDesc.make(G, N, H, W, cin, c.cout, c.k, c.stride, c.pad)
@@ -344,10 +381,15 @@ class Backbone:
                 ops.stem_fprop_bf16(d, x, w, y, stats_buf)
             elif stem_rw:
                 ops.stem_fprop_split(d, x, w, y, stats_buf)
+            elif sp_in and pending_apply is not None:
+                # x does not exist yet: this launch forms it from the previous block's last unit, then every later reader finds it
+                py, pscale, pshift, pres, pres_affine, pbits = pending_apply
+                ops.conv_fprop_split_bnapply(d, x, py, pscale, pshift, pres, w, y, stats_buf, pres_affine, pbits)
             elif sp_in:
                 ops.conv_fprop_split(d, x, w, y, stats_buf)
             else:
                 ops.conv_fprop(d, x, w, y, None, False, stats_buf)
+        assert pending_apply is None or (sp_in and training and not stem_rw)
         if training:
             if stem_rw and bf:   # two output columns per GEMM row: twice the partials of a forward over n x ho x wo/2 rows
                 P, rpp = ops.conv_stats_partials(ConvDesc.make(G, N, d.ho, d.wo // 2, 64, 2 * c.cout, 1, 1, 0), True)
@@ -423,8 +465,15 @@ class Backbone:
         elif sp_out:
             out = ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev)
             out.sinv = self._act_sinv[c.name]       # this step's 2^-k of the unit's output (an sp identity brings its own)
-            bits = ops.bn_apply_split(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine,
-                                      want_bits=keep and relu and residual is not None)
+            want_bits = keep and relu and residual is not None
+            handed = (next_conv is not None and self.fuse_bn_apply_fprop
+                      and bn_apply_fprop_eligible(c, next_conv, split=sp_in, trained=training, residual=residual is not None, relu=relu)
+                      and ops.conv_fprop_split_stages(ConvDesc.make(G, N, d.ho, d.wo, next_conv.cin, next_conv.cout, 1, 1, 0)) == 1)
+            if handed:
+                bits = torch.empty(G * rows * c.cout // 4, dtype=torch.uint8, device=dev) if want_bits else None
+                handed = (y, scale, shift, residual, residual_affine, bits)
+            else:
+                bits = ops.bn_apply_split(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine, want_bits=want_bits)
         else:
             out = torch.empty_like(y) if keep else y            # inference: normalise in place
             bits = None
@@ -446,6 +495,8 @@ class Backbone:
             else:
                 u.relu_bits = bits
             tape.append(u)
+        if next_conv is not None:
+            return out, ((handed or None) if sp_out else None)
         return (out, argmax) if pool else out
 
     @staticmethod
@@ -532,13 +583,16 @@ class Backbone:
         s = self.spec
         x, argmax = self._unit_fwd(s.stem, x0, V, B, H, W, training, True, None, ulist, pool=True)
         Hc, Wc = x.shape[2], x.shape[3]
-        for blk in s.blocks:
+        pending = None        # the previous block's apply pass, when this block's first conv forms its own input
+        for bi, blk in enumerate(s.blocks):
             first = len(ulist) if keep_tape else 0
             identity = x
             out = x
             h, w = Hc, Wc
             for c in blk.convs[:-1]:
-                out = self._unit_fwd(c, out, V, B, h, w, training, True, None, ulist)
+                # (conv1 runs before the downsample branch and before anything else that reads the block input)
+                out = self._unit_fwd(c, out, V, B, h, w, training, True, None, ulist, pending_apply=pending)
+                pending = None
                 h, w = out.shape[2], out.shape[3]
             ds_idx = None
             ident_affine = None
@@ -550,8 +604,13 @@ class Backbone:
                 else:
                     identity = self._unit_fwd(blk.downsample, x, V, B, Hc, Wc, training, False, None, ulist)
                 ds_idx = len(ulist) - 1 if keep_tape else None
-            out = self._unit_fwd(blk.convs[-1], out, V, B, h, w, training, True, identity, ulist,
-                                 residual_affine=ident_affine)
+            nxt = s.blocks[bi + 1].convs[0] if bi + 1 < len(s.blocks) else None
+            if nxt is not None and training and not self.bf16:
+                out, pending = self._unit_fwd(blk.convs[-1], out, V, B, h, w, training, True, identity, ulist,
+                                              residual_affine=ident_affine, next_conv=nxt)
+            else:
+                out = self._unit_fwd(blk.convs[-1], out, V, B, h, w, training, True, identity, ulist,
+                                     residual_affine=ident_affine)
             if keep_tape:
                 n_main = len(blk.convs)
                 idx = list(range(first, first + n_main - 1)) + [len(ulist) - 1]

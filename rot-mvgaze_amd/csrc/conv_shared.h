@@ -172,6 +172,15 @@ struct IgemmParams {
   // it and stores it ONCE in sp to `a` (written here, read later by the weight gradient).
   const float *bna_dz, *bna_y, *bna_mean, *bna_invstd, *bna_gamma, *bna_s1, *bna_s2;
   float bna_inv_rows;             // 1 / rows per group of the unit's BatchNorm
+  // Split kernels, forward of a residual block's first conv (1x1, stride 1, ONE column tile; igemm_split16_kernel<.., FAP>): the A
+  // operand - the previous block's output - is not read: the loader forms it, relu(fap_y * fap_scale + fap_shift + residual) * 2^k
+  // with 2^-k = *a_sinv (that block's BatchNorm apply pass: scale / shift [groups][src_c]; the residual fap_res is the sp identity,
+  // read times *fap_res_sinv (null = 1), or with fap_res_scale / fap_res_shift the raw fp32 downsample output), multiplies it
+  // and stores it ONCE in sp to `a`, and the ReLU mask to fap_bits (one unsigned short per 8-channel chunk, bn_apply_sp_kernel's layout;
+  // null = not wanted).
+  const float *fap_y, *fap_scale, *fap_shift, *fap_res_scale, *fap_res_shift, *fap_res_sinv;
+  const void *fap_res;
+  unsigned short *fap_bits;
 };
 
 // bijective XCD-aware remap of a 1-D grid (cdna_hip_programming.md §5 "XCD swizzle must be

@@ -302,13 +302,23 @@ __device__ __forceinline__ int sp_row_swz(int R) { return ((R >> 1) & 1) | (((R 
 // the apply pass's 3 passes over the map (read dz, read y, write dy) and this launch's read of dy become read dz, read y, write
 // dy.  The weights keep their DMA path.  The A fragments
 // hold the bits the two-launch form reads back from memory, in the same K order: results are those of that form, bit for bit.
+//
+// FAP (forward of a residual block's FIRST conv - 1x1, stride 1, cout 64 / 128: one column tile - in ResNet-50's layer1 / layer2;
+// IgemmParams::fap_*): the forward twin of BNA.  The A operand is the previous block's output, which does not exist yet: the loader
+// forms it per K-step with the same thread -> (row, chunk) map - out = relu(bn_fwd(y, scale, shift) + residual) * 2^k, expression
+// for expression what bn_apply_sp_kernel (bn.hip) computes, the residual being the sp identity times its 2^-k (FAP = 1) or the raw
+// fp32 downsample output through its own (scale, shift) (FAP = 2) - stores the two pieces into the fragment slots, writes the same
+// 32 bytes ONCE to the global sp `out` (plain stores: the downsample conv, the next apply and the weight gradients re-read it)
+// and the chunk's ReLU mask bits.  The producer's scale / shift (and the residual's) of this group wait in LDS behind the row
+// table.  The apply pass's three passes over the map plus this launch's read become three.  Three workgroups per CU (168 registers).
 constexpr int BNA_MAX_C = 512;                                  // channels of the constants' LDS table
-template <int BN, bool DGRAD, bool LIN = false, int WGM = 2, int STAGES = 1, bool BNA = false>
-__global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4) void igemm_split16_kernel(IgemmParams p) {
+template <int BN, bool DGRAD, bool LIN = false, int WGM = 2, int STAGES = 1, bool BNA = false, int FAP = 0>
+__global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || FAP != 0) ? 3 : 4) void igemm_split16_kernel(IgemmParams p) {
   constexpr int BM = 64 * WGM, WGN = 4 / WGM, NW = 4;
   static_assert(WGM == 2 || (WGM == 4 && BN == 64), "tiles: 128 x BN (2 x 2 waves) or 256 x 64 (4 x 1)");
   static_assert(STAGES == 1 || STAGES == 2, "one LDS stage, or the two-stage pipeline");
   static_assert(!BNA || (DGRAD && !LIN && WGM == 2 && STAGES == 1), "the dy-forming loader: backward-data, 128-row tiles, one stage");
+  static_assert(FAP == 0 || (FAP <= 2 && !BNA && !DGRAD && !LIN && WGM == 2 && STAGES == 1), "the block-output-forming loader: forward, 128-row tiles, one stage");
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
   constexpr int TM = WTM / 16, TN = WTN / 16;
   constexpr int SLOTS = 4 * SP_NP;                            // 16-byte slots per LDS row (8)
@@ -320,7 +330,7 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4)
   constexpr int EPI_B = bf16_epilogue_bytes<BM, BN, WGM, DGRAD>();          // one wave row (64 tile rows) per staging pass
   constexpr int INFO_OFF = STAGES * STAGE_B > EPI_B ? STAGES * STAGE_B : EPI_B;  // row table behind the stages / the epilogue tile
   constexpr int BNK_OFF = INFO_OFF + BM * 8;                  // BNA: [5][src_c] mean, invstd, gamma, s1, s2 of this group
-  constexpr int SMEM_B = BNK_OFF + (BNA ? 5 * BNA_MAX_C * 4 : 0);
+  constexpr int SMEM_B = BNK_OFF + (BNA ? 5 : 2 * FAP) * BNA_MAX_C * 4;      // FAP: [2 FAP][src_c] scale, shift (, res_scale, res_shift)
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_B];
 
   const int tid = threadIdx.x;
@@ -372,6 +382,19 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4)
       bnk[4 * C + i] = p.bna_s2[gc];
     }
   }
+  if constexpr (FAP != 0) {
+    float *fk = reinterpret_cast<float *>(smem + BNK_OFF);
+    const int C = p.src_c;
+    for (int i = tid; i < C; i += 256) {
+      const long long gc = (long long)g * C + i;
+      fk[i] = p.fap_scale[gc];
+      fk[C + i] = p.fap_shift[gc];
+      if constexpr (FAP == 2) {
+        fk[2 * C + i] = p.fap_res_scale[gc];
+        fk[3 * C + i] = p.fap_res_shift[gc];
+      }
+    }
+  }
   __syncthreads();
   // ---- the instructions this wave issues: Q = wave + 4 i; lane -> linear slot 64 Q + lane -> (row, slot in row);
   // the slot holds source slot j = slot ^ h(row) of the row's 128-byte span (j = 2 cc + pc: the memory order)
@@ -413,7 +436,7 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4)
       const int btap = (c.tap_r0 + p.tap_step * fru) * p.s + c.tap_s0 + p.tap_step * fsu;
       kb = (unsigned)(btap * p.src_c + chb) * (unsigned)SP_BYTES;
     }
-    if constexpr (!BNA) {
+    if constexpr (!BNA && FAP == 0) {
 #pragma unroll
       for (int i = 0; i < A_PER; ++i) {
         const bool ok = ((a_vmask[i] >> tap_u) & 1u) != 0u;
@@ -530,6 +553,103 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4) ? 3 : 4)
           uint4 *dst = dy_out + ((a_goff[i] + 128u * (unsigned)kt) >> 4);
           dst[0] = q[i][0];
           dst[1] = q[i][1];
+        }
+      if (PREFETCH && kt + 1 < KT) a_load(kt + 1);             // in flight while this K-step is multiplied
+      {
+        f16x8 av[SP_NP][TM], bv[SP_NP][TN];
+        load_frags(smem, av, bv);
+        products(av, bv);
+      }
+      __syncthreads();                                         // everyone is done reading before the next K-step is written
+    }
+  } else if constexpr (FAP != 0) {
+    // (1x1, stride 1: the GEMM's rows are the block output's pixels, K-step kt = channels 32 kt .. 32 kt + 31)
+    const int C = p.src_c;
+    const int a_cc = tid & 3, a_r0 = tid >> 2;
+    const long long grow0 = (long long)g * c.rows_per_group;
+    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(p.fap_y + grow0 * C, 4ll * c.rows_per_group * C);
+    const __amdgpu_buffer_rsrc_t rs_r = make_rsrc(reinterpret_cast<const float *>(p.fap_res) + grow0 * C, 4ll * c.rows_per_group * C);
+    uint4 *a_out = reinterpret_cast<uint4 *>(const_cast<float *>(p.a)) + grow0 * C / 4;       // 4 bytes per element
+    unsigned short *bits_out = p.fap_bits ? p.fap_bits + grow0 * (C >> 3) : nullptr;           // one per chunk
+    // 2^k of out, 2^-k of the identity (exact: powers of two; uniform: scalar registers)
+    const float osc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p.a_sinv ? 1.f / *p.a_sinv : 1.f)));
+    const float rsi = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((FAP == 1 && p.fap_res_sinv) ? *p.fap_res_sinv : 1.f)));
+    bool a_ok[2];
+    unsigned a_goff[2];                                        // byte offset of (row, chunk) in the group's fp32 maps = in its sp maps
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const long long m = (long long)mtile * BM + a_r0 + 64 * i;
+      a_ok[i] = m < c.rows_per_group;
+      a_goff[i] = pred_off((unsigned)m * (unsigned)C * 4u + 32u * (unsigned)a_cc, a_ok[i]);
+    }
+    float4 yv[2][2], rv[2][2];                                 // rv: FAP = 1 the identity's two pieces (bits), FAP = 2 fp32
+    auto a_load = [&](int kt) {
+#pragma unroll
+      for (int i = 0; i < 2; ++i) {
+        const unsigned off = a_goff[i] + 128u * (unsigned)kt;
+        yv[i][0] = buf_ld16(rs_y, off);
+        yv[i][1] = buf_ld16(rs_y, off + 16u);
+        rv[i][0] = buf_ld16(rs_r, off);
+        rv[i][1] = buf_ld16(rs_r, off + 16u);
+      }
+    };
+    // the next K-step's y and residual in flight while this one is multiplied: as BNA, where the registers allow (BN = 64)
+    constexpr bool PREFETCH = BN == 64;
+    if (PREFETCH) a_load(0);
+    for (int kt = 0; kt < KT; ++kt) {
+      issue(kt, 0);                                            // the weights: DMA
+      if (!PREFETCH) a_load(kt);
+      uint4 q[2][SP_NP];
+      unsigned mb[2];
+      {
+        const float *kc = reinterpret_cast<const float *>(smem + BNK_OFF) + kt * SP_BK + a_cc * 8;
+        float sc[8], sh[8], rs[8], rh[8];
+        ld8(kc, sc);
+        ld8(kc + C, sh);
+        if constexpr (FAP == 2) {
+          ld8(kc + 2 * C, rs);
+          ld8(kc + 3 * C, rh);
+        }
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+          const float v[8] = {yv[i][0].x, yv[i][0].y, yv[i][0].z, yv[i][0].w, yv[i][1].x, yv[i][1].y, yv[i][1].z, yv[i][1].w};
+          float r[8];
+          if constexpr (FAP == 1) {
+            const uint4 r1 = make_uint4(__float_as_uint(rv[i][0].x), __float_as_uint(rv[i][0].y), __float_as_uint(rv[i][0].z), __float_as_uint(rv[i][0].w));
+            const uint4 r2 = make_uint4(__float_as_uint(rv[i][1].x), __float_as_uint(rv[i][1].y), __float_as_uint(rv[i][1].z), __float_as_uint(rv[i][1].w));
+            merge2_chunk(r1, r2, r);
+          } else {
+            r[0] = rv[i][0].x; r[1] = rv[i][0].y; r[2] = rv[i][0].z; r[3] = rv[i][0].w;
+            r[4] = rv[i][1].x; r[5] = rv[i][1].y; r[6] = rv[i][1].z; r[7] = rv[i][1].w;
+          }
+          float o[8];
+          unsigned m = 0;
+#pragma unroll
+          for (int k = 0; k < 8; ++k) {
+            float x = bn_fwd(v[k], sc[k], sh[k]);              // bn_apply_sp_kernel's expressions, in its order
+            x += FAP == 2 ? bn_fwd(r[k], rs[k], rh[k]) : r[k] * rsi;
+            x = fmaxf(x, 0.f);
+            m |= (x > 0.f ? 1u : 0u) << (k + (k >= 4 ? 4 : 0));
+            o[k] = a_ok[i] ? x * osc : 0.f;                    // rows beyond the group: the zeros the DMA loader reads there
+          }
+          mb[i] = m;
+          split2_chunk(o, q[i][0], q[i][1]);
+          const int R = a_r0 + 64 * i;
+#pragma unroll
+          for (int pc = 0; pc < SP_NP; ++pc)
+            *reinterpret_cast<uint4 *>(smem + R * ROWB + (((2 * a_cc + pc) ^ sp_row_swz(R)) << 4)) = q[i][pc];
+        }
+      }
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+#pragma unroll
+      for (int i = 0; i < 2; ++i)
+        if (a_ok[i]) {
+          const unsigned off = a_goff[i] + 128u * (unsigned)kt;
+          uint4 *dst = a_out + (off >> 4);
+          dst[0] = q[i][0];
+          dst[1] = q[i][1];
+          if (bits_out) bits_out[off >> 5] = (unsigned short)mb[i];
         }
       if (PREFETCH && kt + 1 < KT) a_load(kt + 1);             // in flight while this K-step is multiplied
       {
@@ -901,7 +1021,7 @@ static int validate_split(const mvg_conv_desc *d) {
 static int split_tile_rows(int ncols, int taps, long long rows) { return (ncols < 128 && taps > 1 && rows >= 65536) ? 256 : SP_BM; }
 
 template <bool DGRAD>
-static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin = false, int bm = SP_BM, bool bna = false) {
+static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin = false, int bm = SP_BM, bool bna = false, int fap = 0) {
   // (128 x 64 tiles for the short-K, write-heavy 1x1 layers - 64 -> 256 at 56 x 56 and the like - were measured in round 4:
   // within 2 % of 128 x 128 on every such shape, forward and backward-data)
   int bn = p.ncols >= 128 ? 128 : 64;
@@ -957,6 +1077,16 @@ static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin = false, 
       if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, true, false, 2, 1, true>), grid, block, 0, st, p);
       else hipLaunchKernelGGL((igemm_split16_kernel<64, true, false, 2, 1, true>), grid, block, 0, st, p);
       return check_launch("conv_dgrad_split_bnapply");
+    }
+  }
+  if constexpr (!DGRAD) {
+    if (fap) {               // the block output formed in the loader (same tiles, K order and epilogue as the DMA kernels)
+      MVG_REQUIRE(!lin && bm == SP_BM && p.ntiles == 1 && p.ncls == 1, "split conv: the block-output-forming loader takes one column tile");
+      if (bn == 128 && fap == 2) hipLaunchKernelGGL((igemm_split16_kernel<128, false, false, 2, 1, false, 2>), grid, block, 0, st, p);
+      else if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, false, false, 2, 1, false, 1>), grid, block, 0, st, p);
+      else if (fap == 2) hipLaunchKernelGGL((igemm_split16_kernel<64, false, false, 2, 1, false, 2>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((igemm_split16_kernel<64, false, false, 2, 1, false, 1>), grid, block, 0, st, p);
+      return check_launch("conv_fprop_split_bnapply");
     }
   }
   if (lin) {                 // a Linear of the fusion block: the epilogue's scale / abs-max features compiled in
@@ -1063,8 +1193,15 @@ struct SplitAffine {       // inference forward: y = acc * scale + shift (+ resi
 
 // stride_w / pad_w >= 0: the horizontal stride / padding differ from d->stride / d->pad (the stem's row-window form, whose
 // descriptor the caller has checked itself)
+struct SplitFwdApply {     // the launch forms its own input (IgemmParams::fap_*): the previous block's BatchNorm apply pass
+  const float *y, *scale, *shift, *res_scale, *res_shift, *res_sinv;
+  const void *res;
+  uint8_t *bits;
+};
+
 static int fprop_split_impl(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *w_sp, const float *w_sinv,
-                            void *y, float *stats, void *stream, const SplitAffine *aff, int stride_w = -1, int pad_w = -1) {
+                            void *y, float *stats, void *stream, const SplitAffine *aff, int stride_w = -1, int pad_w = -1,
+                            const SplitFwdApply *fap = nullptr) {
   if (stride_w < 0 && validate_split(d)) return 2;
   IgemmParams p;
   memset(&p, 0, sizeof(p));
@@ -1085,22 +1222,67 @@ static int fprop_split_impl(const mvg_conv_desc *d, const void *x_sp, const floa
     p.out_sinv = aff->out_sinv;
     p.bias_absmax = aff->bias_absmax;
   }
+  if (fap) {
+    p.fap_y = fap->y;
+    p.fap_scale = fap->scale;
+    p.fap_shift = fap->shift;
+    p.fap_res = fap->res;
+    p.fap_res_scale = fap->res_scale;
+    p.fap_res_shift = fap->res_shift;
+    p.fap_res_sinv = fap->res_sinv;
+    p.fap_bits = (unsigned short *)fap->bits;
+  }
   if (fprop_geometry(p, d, SP_BYTES, SP_BYTES, "split conv", stride_w, pad_w)) return 2;
   MVG_REQUIRE(p.rows_per_group * (long long)d->cout < (1ll << 31), "split conv: a group of the output exceeds 2^31 elements");
   // (the stem's row-window form multiplies 7 x 32 values per output where the filter has 7 x 7 x 3: count the filter's)
   const double flops = 2.0 * d->groups * (double)p.rows_per_group * d->cout * d->r * d->s * d->cin * (stride_w >= 0 ? 147.0 / 224.0 : 1.0);
+  // (with the apply pass on board the launch reads y and the residual and writes the input instead of reading it: its algorithmic bytes)
   const double bytes = (double)SP_BYTES * (d->groups * (double)d->n * d->h * d->w * d->cin + (double)d->cout * d->r * d->s * d->cin) +
-                       4.0 * d->groups * (double)p.rows_per_group * d->cout;
+                       4.0 * d->groups * (double)p.rows_per_group * d->cout +
+                       (fap ? 8.0 + 1.0 / 4.0 : 0.0) * d->groups * (double)d->n * d->h * d->w * d->cin;
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_FPROP : MVG_K_CONV_FPROP, (hipStream_t)stream, flops, bytes);
   p.stats_partials = ceil_div(p.rows_per_group, SP_BM) * 2;    // = mvg_conv_stats_partials_split
   const bool lin_k = aff && aff->lin;
-  return launch_igemm_split<false>(p, (hipStream_t)stream, lin_k, lin_k ? SP_BM : split_tile_rows(d->cout, d->r * d->s, p.rows_per_group));
+  return launch_igemm_split<false>(p, (hipStream_t)stream, lin_k, lin_k ? SP_BM : split_tile_rows(d->cout, d->r * d->s, p.rows_per_group), false,
+                                   fap ? (fap->res_scale ? 2 : 1) : 0);
 }
 
 int mvg_conv_fprop_split(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *w_sp, const float *w_sinv, float *y,
                          float *stats, void *stream) {
   return fprop_split_impl(d, x_sp, x_sinv, w_sp, w_sinv, y, stats, stream, nullptr);
+}
+
+int mvg_conv_fprop_split_stages(const mvg_conv_desc *d) {
+  // 1 / 2: the K loop launch_igemm_split picks for this forward (single-stage / the two-stage pipeline); -1: bad descriptor.
+  // (mvg_conv_fprop_split_bnapply exists in the single-stage form only: the caller's eligibility rule asks here.)
+  if (validate_split(d)) return -1;
+  const long long rows = (long long)d->n * d->ho * d->wo;
+  const int bm = split_tile_rows(d->cout, d->r * d->s, rows);
+  const long long tiles = (long long)d->groups * ceil_div(rows, bm) * ceil_div(d->cout, d->cout >= 128 ? 128 : 64);
+  const int kt = ceil_div(d->r * d->s * d->cin, SP_BK);
+  const bool pipelined = tiles <= 2LL * compute_cus() || (tiles <= 4LL * compute_cus() && kt >= 48);
+  return (pipelined && d->cout >= 128 && bm == SP_BM) ? 2 : 1;
+}
+
+int mvg_conv_fprop_split_bnapply(const mvg_conv_desc *d, void *out_sp, const float *out_sinv, const float *bn_y, const float *scale,
+                                 const float *shift, const void *residual, int residual_sp, const float *res_scale,
+                                 const float *res_shift, const float *res_sinv, uint8_t *relu_bits, const void *w_sp,
+                                 const float *w_sinv, float *y, float *stats, void *stream) {
+  // mvg_bn_apply_split_scaled (residual + ReLU) of the unit that PRODUCES this conv's input, and mvg_conv_fprop_split, in ONE
+  // launch: out_sp (an output: the conv's input, written once in sp times 1 / *out_sinv) = relu(bn_y * scale + shift + residual),
+  // the residual an sp identity (read times *res_sinv) or the raw fp32 downsample output with (res_scale, res_shift);
+  // relu_bits (optional) receives the mask as mvg_bn_apply_split_scaled writes it.  Same bits as the two launches.
+  MVG_REQUIRE(d && out_sp && bn_y && scale && shift && residual && w_sp && y, "fprop_split_bnapply: null argument");
+  MVG_REQUIRE(d->r == 1 && d->s == 1 && d->stride == 1 && d->pad == 0, "fprop_split_bnapply: 1x1, stride 1, pad 0 only");
+  MVG_REQUIRE(d->cout == 64 || d->cout == 128, "fprop_split_bnapply: cout must be 64 or 128 (one column tile; got %d)", d->cout);
+  MVG_REQUIRE(d->cin % 32 == 0 && d->cin <= BNA_MAX_C, "fprop_split_bnapply: cin must be a multiple of 32, at most %d (got %d)", BNA_MAX_C,
+              d->cin);
+  MVG_REQUIRE(residual_sp ? (!res_scale && !res_shift) : (res_scale && res_shift && !res_sinv),
+              "fprop_split_bnapply: the residual is an sp identity (no res_scale / res_shift) or fp32 with res_scale and res_shift");
+  MVG_REQUIRE((long long)d->n * d->h * d->w * d->cin < (1ll << 29), "fprop_split_bnapply: a group of the input exceeds 2 GiB");
+  const SplitFwdApply a = {bn_y, scale, shift, res_scale, res_shift, res_sinv, residual, relu_bits};
+  return fprop_split_impl(d, out_sp, out_sinv, w_sp, w_sinv, y, stats, stream, nullptr, -1, -1, &a);
 }
 
 int mvg_conv_fprop_split_affine(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *w_sp, const float *w_sinv,

@@ -240,6 +240,28 @@ def conv_fprop_split(d: ConvDesc, x_sp: Tensor, w_sp: Tensor, y: Tensor, stats: 
     check(lib().mvg_conv_fprop_split(C.byref(d), _p(x_sp), _sinv(x_sp), _p(w_sp), _sinv(w_sp), _p(y), _p(stats), _s()), "conv_fprop_split")
 
 
+def conv_fprop_split_stages(d: ConvDesc) -> int:
+    """1 / 2: the K loop conv_fprop_split takes for ``d`` on this device (single-stage / two-stage pipeline)."""
+    n = lib().mvg_conv_fprop_split_stages(C.byref(d))
+    if n < 0:
+        check(1, "conv_fprop_split_stages")
+    return n
+
+
+def conv_fprop_split_bnapply(d: ConvDesc, out_sp: Tensor, bn_y, scale, shift, residual, w_sp: Tensor, y: Tensor,
+                             stats: Optional[Tensor] = None, residual_affine=None, bits: Optional[Tensor] = None):
+    """bn_apply_split (residual, ReLU) of the unit whose output ``out_sp`` is + conv_fprop_split of the 1x1 stride-1 conv (cout 64 /
+    128) that reads it, in ONE launch: the forward loader forms out_sp, uses it and writes it (an output: out_sp.sinv is its scale).
+    residual: an sp identity, or the raw fp32 downsample output with residual_affine = its (scale, shift).  bits (optional, uint8
+    [groups * rows * cin / 4]): receives the ReLU mask bytes as bn_apply_split returns them."""
+    assert bits is None or (bits.dtype == torch.uint8 and bits.numel() == d.groups * d.n * d.h * d.w * d.cin // 4)
+    rs, rh = residual_affine if residual_affine is not None else (None, None)
+    res_sp = is_sp(residual)
+    check(lib().mvg_conv_fprop_split_bnapply(C.byref(d), _p(out_sp), _sinv(out_sp), _p(bn_y), _p(scale), _p(shift), _p(residual), int(res_sp),
+                                             _p(rs), _p(rh), _sinv(residual) if res_sp else None, _p(bits), _p(w_sp), _sinv(w_sp), _p(y),
+                                             _p(stats), _s()), "conv_fprop_split_bnapply")
+
+
 def conv_fprop_split_affine(d: ConvDesc, x_sp: Tensor, w_sp: Tensor, out: Tensor, scale: Tensor, shift: Tensor,
                             residual: Optional[Tensor], relu: bool):
     """Inference forward on the split kernels, BatchNorm folded: out = relu?(conv * scale + shift (+ residual)).

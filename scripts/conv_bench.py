@@ -86,6 +86,19 @@ for (cin, cout, k, st, pad, h), cnt in shapes.items():
         tf = timeit(lambda: ops.conv_fprop_split(d, xs, wk, y, stats_s))
         td = timeit(lambda: ops.conv_dgrad_split(d, gys, wts, dx))
         tw = timeit(lambda: ops.conv_wgrad_split(d, xs, gys, dw))
+        if k == 1 and st == 1 and cout in (64, 128) and cin in (256, 512):
+            # a residual block's first conv whose forward loader forms its own input (mvg_conv_fprop_split_bnapply): the pair it
+            # replaces - the previous block's BatchNorm apply pass (sp identity / raw downsample residual), then the forward -
+            # against the merged launch
+            py, pc = torch.randn(G, rows, cin, device=dev), [torch.rand(G, cin, device=dev) + 0.5 for _ in range(4)]
+            outs, fb = ops.sp_empty(G, N, h, h, cin, device=dev), torch.empty(G * rows * cin // 4, dtype=torch.uint8, device=dev)
+            for form, res, ra in (("sp identity", xs, None), ("fp32 affine residual", x, (pc[2], pc[3]))):
+                def fpair():
+                    ops.bn_apply_split(py, pc[0], pc[1], res, True, outs, G, rows, cin, ra, want_bits=True)
+                    ops.conv_fprop_split(d, outs, wk, y, stats_s)
+                tp = timeit(fpair)
+                tm = timeit(lambda: ops.conv_fprop_split_bnapply(d, outs, py, pc[0], pc[1], res, wk, y, stats_s, ra, fb))
+                print(f"{cin:5d} {cout:5d} {k} {st} {h:4d} {cnt:3d} | BN apply ({form}) + fprop {tp*1e3:.3f} ms -> block output formed in the fprop loader {tm*1e3:.3f} ms ({4.0*(3*x.numel()+y.numel())/tm/1e9:.0f} GB/s of y, residual, out, y')")
         bits = torch.randint(0, 16, (G * rows * cin // 4,), dtype=torch.uint8, device=dev)
         mx = torch.empty(G, cin, device=dev)
         tdf = timeit(lambda: ops.conv_dgrad_split_bnreduce(d, gys, wts, dx, None, x, bits, mean, invstd, None, s12[0], s12[1], dgb[0], dgb[1], False, mx))
