@@ -750,15 +750,8 @@ __global__ __launch_bounds__(256) void bn_apply_sp_kernel(const float *__restric
     const F8 v = ld8(y, base + i);
     F8 r, o;
     if (residual) r = RES_SP ? ld8_sp(reinterpret_cast<const sp_t *>(residual), base + i) : ld8(reinterpret_cast<const float *>(residual), base + i);
-    unsigned m = 0;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float x = bn_fwd(v.v[k], sc.v[k], sh.v[k]);              // bn_math.h, as bn_apply_kernel (mask rebuild in the backward)
-      if (residual) x += raff ? bn_fwd(r.v[k], rs.v[k], rh.v[k]) : (RES_SP ? r.v[k] * rsi : r.v[k]);
-      if (relu) x = fmaxf(x, 0.f);
-      m |= (x > 0.f ? 1u : 0u) << (k + (k >= 4 ? 4 : 0));    // two bytes, low nibbles: one byte per 4 channels (bn_bwd_reduce_bits)
-      o.v[k] = x * osc;                                      // after the mask decision: the bits come from the unscaled value
-    }
+    // (bn_math.h; conv_split.hip's block-output former calls the same function: one launch or two, the same bits)
+    const unsigned m = bn_apply_chunk(v.v, sc.v, sh.v, residual != nullptr, r.v, raff, rs.v, rh.v, RES_SP, rsi, relu != 0, osc, o.v);
     st8_sp(out, base + i, o);
     if (relu_bits) relu_bits[base + i] = (unsigned short)m;
     cq += step;
@@ -864,12 +857,8 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_sp_kernel(const float *__res
     }
     const F8 d = ld8(g, base + i), v = ld8(y, base + i);
     F8 o;
-#pragma unroll
-    for (int k = 0; k < 8; ++k) {
-      float dd = d.v[k];
-      if (mscale) dd = relu_mask(relu_on(v.v[k], ma.v[k], mb.v[k]), dd);
-      o.v[k] = bn_dy(dd, v.v[k], mu.v[k], is.v[k], ga.v[k], sa.v[k], sb.v[k], inv_rows) * dsc;
-    }
+    // (bn_math.h; conv_split.hip's dy former calls the same function: one launch or two, the same bits)
+    bn_dy_chunk(d.v, v.v, mu.v, is.v, ga.v, sa.v, sb.v, inv_rows, dsc, o.v, mscale != nullptr, ma.v, mb.v);
     st8_sp(dy, base + i, o);
     cq += step;
     if (cq >= c8n) cq -= c8n;

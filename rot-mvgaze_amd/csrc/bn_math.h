@@ -1,7 +1,8 @@
 // The BatchNorm element math, written ONCE: the forward affine and the ReLU-mask rule built on it, x-hat, the backward
-// expression, and their lane-wise forms over a float4 (4 consecutive channels).  Every kernel that normalises, masks a
-// gradient or forms dy - bn.hip's passes, and the BatchNorm reduce that rides on the backward-data epilogue
-// (bf16_tile.h) - calls these, so the forward pass and every backward pass take the SAME bit decision for the mask.
+// expression, their lane-wise forms over a float4 (4 consecutive channels) and the sp passes' 8-channel chunk forms.  Every
+// kernel that normalises, masks a gradient or forms dy - bn.hip's passes, the BatchNorm reduce that rides on the backward-data
+// epilogue (bf16_tile.h), the operand-forming conv loaders (conv_split.hip) - calls these, so the forward pass and every
+// backward pass take the SAME bit decision for the mask.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -69,6 +70,36 @@ __device__ __forceinline__ void acc4_xhat(float4 &s, float4 d, float4 y, float4 
 }
 __device__ __forceinline__ float4 bn_dy(float4 dz, float4 y, float4 mean, float4 invstd, float4 gamma, float4 s1, float4 s2, float inv_rows) {
   return map4([](auto... s) { return bn_dy(s...); }, dz, y, mean, invstd, gamma, s1, s2, inv_rows);
+}
+
+// ---- one 8-channel chunk: bn.hip's sp passes and the operand-forming loaders of conv_split.hip ------------------------
+// The apply pass: o = [relu](bn_fwd(y, sc, sh) + residual) * osc, the residual (has_res) being r through its own affine
+// (res_affine: bn_fwd(r, rs, rh)), r times rsi (res_scaled: an sp identity and its 2^-k) or r as it is.  Returns the ReLU
+// mask as two bytes, low nibbles: one byte per 4 channels (bn_bwd_reduce_bits), taken from the unscaled value.
+__device__ __forceinline__ unsigned bn_apply_chunk(const float (&y)[8], const float (&sc)[8], const float (&sh)[8], bool has_res,
+                                                   const float (&r)[8], bool res_affine, const float (&rs)[8], const float (&rh)[8],
+                                                   bool res_scaled, float rsi, bool relu, float osc, float (&o)[8]) {
+  unsigned m = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    float x = bn_fwd(y[k], sc[k], sh[k]);                    // as bn_apply_kernel (mask rebuild in the backward)
+    if (has_res) x += res_affine ? bn_fwd(r[k], rs[k], rh[k]) : (res_scaled ? r[k] * rsi : r[k]);
+    if (relu) x = fmaxf(x, 0.f);
+    m |= (x > 0.f ? 1u : 0u) << (k + (k >= 4 ? 4 : 0));
+    o[k] = x * osc;                                          // after the mask decision
+  }
+  return m;
+}
+// The backward apply pass: o = bn_dy(dz, y, ...) * dsc; masked: dz first goes through the unit's ReLU mask, rebuilt from y (ms, mh)
+__device__ __forceinline__ void bn_dy_chunk(const float (&dz)[8], const float (&y)[8], const float (&mean)[8], const float (&invstd)[8],
+                                            const float (&gamma)[8], const float (&s1)[8], const float (&s2)[8], float inv_rows, float dsc,
+                                            float (&o)[8], bool masked, const float (&ms)[8], const float (&mh)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    float d = dz[k];
+    if (masked) d = relu_mask(relu_on(y[k], ms[k], mh[k]), d);
+    o[k] = bn_dy(d, y[k], mean[k], invstd[k], gamma[k], s1[k], s2[k], inv_rows) * dsc;
+  }
 }
 
 }  // namespace mvg

@@ -166,13 +166,13 @@ struct IgemmParams {
   const int *rc_row_img, *rc_row_src;
   int rc_cf, rc_nvec, rc_nvec_shift;
   long long rc_img_bytes, rc_feat_bytes;
-  // Split kernels, backward-data of a 1x1 stride-1 unit with ONE column tile (igemm_split16_kernel<.., BNA = true>): the A
+  // Split kernels, backward-data of a 1x1 stride-1 unit with ONE column tile (igemm_split16_kernel<.., AF = A_DY>): the A
   // operand dy is not read - the loader forms it, dy = bn_dy(dz, y, ...) * 2^k with 2^-k = *a_sinv (the unit's own
   // BatchNorm-backward apply pass: bna_dz already masked; mean / invstd / s1 / s2 [groups][src_c], gamma [src_c]), multiplies
   // it and stores it ONCE in sp to `a` (written here, read later by the weight gradient).
   const float *bna_dz, *bna_y, *bna_mean, *bna_invstd, *bna_gamma, *bna_s1, *bna_s2;
   float bna_inv_rows;             // 1 / rows per group of the unit's BatchNorm
-  // Split kernels, forward of a residual block's first conv (1x1, stride 1, ONE column tile; igemm_split16_kernel<.., FAP>): the A
+  // Split kernels, forward of a residual block's first conv (1x1, stride 1, ONE column tile; igemm_split16_kernel<.., AF = A_OUT_SP | A_OUT_AFFINE>): the A
   // operand - the previous block's output - is not read: the loader forms it, relu(fap_y * fap_scale + fap_shift + residual) * 2^k
   // with 2^-k = *a_sinv (that block's BatchNorm apply pass: scale / shift [groups][src_c]; the residual fap_res is the sp identity,
   // read times *fap_res_sinv (null = 1), or with fap_res_scale / fap_res_shift the raw fp32 downsample output), multiplies it

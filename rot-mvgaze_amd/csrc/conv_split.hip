@@ -293,32 +293,143 @@ __device__ __forceinline__ int sp_row_swz(int R) { return ((R >> 1) & 1) | (((R 
 // STAGES = 2 (launches that leave a CU one or two workgroups - the fusion block's Linears, 48 - 336 tiles of up to 112 K-steps on
 // 256 CUs; every conv of a small batch - so that nobody covers a workgroup's waits): an explicit software pipeline, see the K loop.
 //
-// BNA (backward-data of a 1x1 stride-1 unit whose GEMM has ONE column tile - ResNet-50's layer1 / layer2 conv3: K = cout wide,
-// N = cin <= 128 - with the fused reduce on board; IgemmParams::bna_*): the A operand dy does not exist yet.  The loader forms it
-// per K-step in registers - thread t: chunk t & 3 of rows t >> 2 and 64 + (t >> 2), so four lanes cover a row's 128-byte line of
-// dz and of y; dy = bn_dy(...) * 2^k exactly as bn_bwd_apply_sp_kernel (bn.hip) computes it; the unit's 5 x cout per-channel
-// constants wait in LDS behind the row table - writes the two fp16 pieces into the slots the fragment reads expect, and stores the
-// same 32 bytes to the global sp dy for the weight gradient.  Every dy element belongs to exactly one workgroup and one K-step:
-// the apply pass's 3 passes over the map (read dz, read y, write dy) and this launch's read of dy become read dz, read y, write
-// dy.  The weights keep their DMA path.  The A fragments
-// hold the bits the two-launch form reads back from memory, in the same K order: results are those of that form, bit for bit.
-//
-// FAP (forward of a residual block's FIRST conv - 1x1, stride 1, cout 64 / 128: one column tile - in ResNet-50's layer1 / layer2;
-// IgemmParams::fap_*): the forward twin of BNA.  The A operand is the previous block's output, which does not exist yet: the loader
-// forms it per K-step with the same thread -> (row, chunk) map - out = relu(bn_fwd(y, scale, shift) + residual) * 2^k, expression
-// for expression what bn_apply_sp_kernel (bn.hip) computes, the residual being the sp identity times its 2^-k (FAP = 1) or the raw
-// fp32 downsample output through its own (scale, shift) (FAP = 2) - stores the two pieces into the fragment slots, writes the same
-// 32 bytes ONCE to the global sp `out` (plain stores: the downsample conv, the next apply and the weight gradients re-read it)
-// and the chunk's ReLU mask bits.  The producer's scale / shift (and the residual's) of this group wait in LDS behind the row
-// table.  The apply pass's three passes over the map plus this launch's read become three.  Three workgroups per CU (168 registers).
+// AF != A_DMA (1x1, stride 1, ONE column tile, one stage): the A operand does not exist yet - a launch that would follow a BatchNorm
+// pass forms that pass's result in its own loader.  Thread t takes chunk t & 3 of rows t >> 2 and 64 + (t >> 2), so four lanes cover
+// a row's 128-byte line of each fp32 map; per K-step it loads its two chunks' inputs into registers, forms the 8 values with the
+// pass's own function (bn_math.h: the sp pass of bn.hip calls the same one), writes the two fp16 pieces into the slots the fragment
+// reads expect and stores the same 32 bytes ONCE to the global sp operand `a` (plain stores: later launches re-read it).  Every
+// element belongs to exactly one workgroup and one K-step: the pass's three trips over the map (two reads, one write) plus this
+// launch's read become three.  The weights keep their DMA path.  The A fragments hold the bits the two-launch form reads back from
+// memory, in the same K order, and tiles and epilogue are the DMA kernels': results are those of that form, bit for bit.  The group's
+// per-channel constants wait in LDS behind the row table.  Three workgroups per CU (168 registers).
+// What differs between the passes is a "former" (below): which maps it reads, which constants it stages, the chunk function.
+//   * A_DY (backward-data of ResNet-50's layer1 / layer2 conv3 - K = cout wide, N = cin <= 128 - with the fused reduce on board;
+//     IgemmParams::bna_*): dy = bn_dy(dz, y, ...) * 2^k as bn_bwd_apply_sp_kernel; 5 x cout constants; dy is re-read by the weight
+//     gradient.
+//   * A_OUT_SP / A_OUT_AFFINE (forward of a residual block's FIRST conv, cout 64 / 128, in ResNet-50's layer1 / layer2;
+//     IgemmParams::fap_*): the previous block's output, out = relu(bn_fwd(y, scale, shift) + residual) * 2^k as bn_apply_sp_kernel,
+//     the residual being the sp identity times its 2^-k or the raw fp32 downsample output through its own (scale, shift); 2 / 4 x cin
+//     constants; also stores the chunk's ReLU mask bits; out is re-read by the downsample conv, the next apply and the weight gradients.
+enum AForm : int { A_DMA = 0, A_DY = 1, A_OUT_SP = 2, A_OUT_AFFINE = 3 };
 constexpr int BNA_MAX_C = 512;                                  // channels of the constants' LDS table
-template <int BN, bool DGRAD, bool LIN = false, int WGM = 2, int STAGES = 1, bool BNA = false, int FAP = 0>
-__global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || FAP != 0) ? 3 : 4) void igemm_split16_kernel(IgemmParams p) {
+
+__device__ __forceinline__ void unpack8(const float4 (&v)[2], float (&o)[8]) {
+  o[0] = v[0].x; o[1] = v[0].y; o[2] = v[0].z; o[3] = v[0].w; o[4] = v[1].x; o[5] = v[1].y; o[6] = v[1].z; o[7] = v[1].w;
+}
+
+// A former: stage() the group's constants into the LDS table, once per tile; load(i, byte_off) issues row half i's loads into member
+// registers; consts(kc, C) this K-step's 8 channels' constants; form(i, ok, o) the chunk; store_extra(i, byte_off) what leaves with it.
+struct DyFormer {
+  static constexpr int TABLES = 5;                            // [5][C] mean, invstd, gamma, s1, s2 of this group
+  __amdgpu_buffer_rsrc_t rs_dz, rs_y;
+  float inv_rows, dsc;
+  float4 dzv[2][2], yv[2][2];
+  float mu[8], is[8], ga[8], sa[8], sb[8];
+  static __device__ __forceinline__ void stage(float *t, const IgemmParams &p, int g, int C, int tid) {
+    for (int i = tid; i < C; i += 256) {
+      const long long gc = (long long)g * C + i;
+      t[i] = p.bna_mean[gc];
+      t[C + i] = p.bna_invstd[gc];
+      t[2 * C + i] = p.bna_gamma[i];
+      t[3 * C + i] = p.bna_s1[gc];
+      t[4 * C + i] = p.bna_s2[gc];
+    }
+  }
+  __device__ __forceinline__ DyFormer(const IgemmParams &p, long long grow0, long long rows_per_group, int C)
+      : rs_dz(make_rsrc(p.bna_dz + grow0 * C, 4ll * rows_per_group * C)), rs_y(make_rsrc(p.bna_y + grow0 * C, 4ll * rows_per_group * C)),
+        inv_rows(p.bna_inv_rows), dsc(1.f / *p.a_sinv) {}      // 2^k (exact: a power of two)
+  __device__ __forceinline__ void load(int i, unsigned off) {
+    dzv[i][0] = buf_ld16(rs_dz, off);
+    dzv[i][1] = buf_ld16(rs_dz, off + 16u);
+    yv[i][0] = buf_ld16(rs_y, off);
+    yv[i][1] = buf_ld16(rs_y, off + 16u);
+  }
+  __device__ __forceinline__ void consts(const float *kc, int C) {
+    ld8(kc, mu);
+    ld8(kc + C, is);
+    ld8(kc + 2 * C, ga);
+    ld8(kc + 3 * C, sa);
+    ld8(kc + 4 * C, sb);
+  }
+  __device__ __forceinline__ void form(int i, bool ok, float (&o)[8]) {
+    float d[8], v[8];
+    unpack8(dzv[i], d);
+    unpack8(yv[i], v);
+    bn_dy_chunk(d, v, mu, is, ga, sa, sb, inv_rows, dsc, o, false, mu, mu);          // (dz arrives masked)
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = ok ? o[k] : 0.f;        // rows beyond the group: the zeros the DMA loader reads there
+  }
+  __device__ __forceinline__ void store_extra(int, unsigned) {}
+};
+
+template <bool AFFINE>
+struct OutFormer {
+  static constexpr int TABLES = AFFINE ? 4 : 2;                // [2 | 4][C] scale, shift (, res_scale, res_shift) of this group
+  __amdgpu_buffer_rsrc_t rs_y, rs_r;
+  float osc, rsi;
+  unsigned short *bits_out;
+  float4 yv[2][2], rv[2][2];                                   // rv: the identity's two pieces (bits), or fp32
+  float sc[8], sh[8], rs[8], rh[8];
+  unsigned mb[2];
+  static __device__ __forceinline__ void stage(float *t, const IgemmParams &p, int g, int C, int tid) {
+    for (int i = tid; i < C; i += 256) {
+      const long long gc = (long long)g * C + i;
+      t[i] = p.fap_scale[gc];
+      t[C + i] = p.fap_shift[gc];
+      if constexpr (AFFINE) {
+        t[2 * C + i] = p.fap_res_scale[gc];
+        t[3 * C + i] = p.fap_res_shift[gc];
+      }
+    }
+  }
+  // osc: 2^k of out, rsi: 2^-k of the identity (exact: powers of two; uniform: scalar registers)
+  __device__ __forceinline__ OutFormer(const IgemmParams &p, long long grow0, long long rows_per_group, int C)
+      : rs_y(make_rsrc(p.fap_y + grow0 * C, 4ll * rows_per_group * C)),
+        rs_r(make_rsrc(reinterpret_cast<const float *>(p.fap_res) + grow0 * C, 4ll * rows_per_group * C)),
+        osc(__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p.a_sinv ? 1.f / *p.a_sinv : 1.f)))),
+        rsi(__uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((!AFFINE && p.fap_res_sinv) ? *p.fap_res_sinv : 1.f)))),
+        bits_out(p.fap_bits ? p.fap_bits + grow0 * (C >> 3) : nullptr) {}                       // one per chunk
+  __device__ __forceinline__ void load(int i, unsigned off) {
+    yv[i][0] = buf_ld16(rs_y, off);
+    yv[i][1] = buf_ld16(rs_y, off + 16u);
+    rv[i][0] = buf_ld16(rs_r, off);
+    rv[i][1] = buf_ld16(rs_r, off + 16u);
+  }
+  __device__ __forceinline__ void consts(const float *kc, int C) {
+    ld8(kc, sc);
+    ld8(kc + C, sh);
+    if constexpr (AFFINE) {
+      ld8(kc + 2 * C, rs);
+      ld8(kc + 3 * C, rh);
+    }
+  }
+  __device__ __forceinline__ void form(int i, bool ok, float (&o)[8]) {
+    float v[8], r[8];
+    unpack8(yv[i], v);
+    if constexpr (AFFINE) {
+      unpack8(rv[i], r);
+    } else {
+      const uint4 r1 = make_uint4(__float_as_uint(rv[i][0].x), __float_as_uint(rv[i][0].y), __float_as_uint(rv[i][0].z), __float_as_uint(rv[i][0].w));
+      const uint4 r2 = make_uint4(__float_as_uint(rv[i][1].x), __float_as_uint(rv[i][1].y), __float_as_uint(rv[i][1].z), __float_as_uint(rv[i][1].w));
+      merge2_chunk(r1, r2, r);
+    }
+    mb[i] = bn_apply_chunk(v, sc, sh, true, r, AFFINE, rs, rh, !AFFINE, rsi, true, osc, o);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) o[k] = ok ? o[k] : 0.f;        // rows beyond the group: the zeros the DMA loader reads there
+  }
+  __device__ __forceinline__ void store_extra(int i, unsigned off) {
+    if (bits_out) bits_out[off >> 5] = (unsigned short)mb[i];
+  }
+};
+
+template <int BN, bool DGRAD, bool LIN = false, int WGM = 2, int STAGES = 1, AForm AF = A_DMA>
+__global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || AF != A_DMA) ? 3 : 4) void igemm_split16_kernel(IgemmParams p) {
   constexpr int BM = 64 * WGM, WGN = 4 / WGM, NW = 4;
   static_assert(WGM == 2 || (WGM == 4 && BN == 64), "tiles: 128 x BN (2 x 2 waves) or 256 x 64 (4 x 1)");
   static_assert(STAGES == 1 || STAGES == 2, "one LDS stage, or the two-stage pipeline");
-  static_assert(!BNA || (DGRAD && !LIN && WGM == 2 && STAGES == 1), "the dy-forming loader: backward-data, 128-row tiles, one stage");
-  static_assert(FAP == 0 || (FAP <= 2 && !BNA && !DGRAD && !LIN && WGM == 2 && STAGES == 1), "the block-output-forming loader: forward, 128-row tiles, one stage");
+  static_assert(AF == A_DMA || (DGRAD == (AF == A_DY) && !LIN && WGM == 2 && STAGES == 1),
+                "operand-forming loaders: dy in backward-data, the block output in forward; 128-row tiles, one stage");
+  using Former = std::conditional_t<AF == A_DY, DyFormer, OutFormer<AF == A_OUT_AFFINE>>;
   constexpr int WTM = BM / WGM, WTN = BN / WGN;
   constexpr int TM = WTM / 16, TN = WTN / 16;
   constexpr int SLOTS = 4 * SP_NP;                            // 16-byte slots per LDS row (8)
@@ -329,8 +440,8 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || FAP !=
   static_assert(QA % NW == 0 && (NQ - QA) % NW == 0, "whole instructions per wave");
   constexpr int EPI_B = bf16_epilogue_bytes<BM, BN, WGM, DGRAD>();          // one wave row (64 tile rows) per staging pass
   constexpr int INFO_OFF = STAGES * STAGE_B > EPI_B ? STAGES * STAGE_B : EPI_B;  // row table behind the stages / the epilogue tile
-  constexpr int BNK_OFF = INFO_OFF + BM * 8;                  // BNA: [5][src_c] mean, invstd, gamma, s1, s2 of this group
-  constexpr int SMEM_B = BNK_OFF + (BNA ? 5 : 2 * FAP) * BNA_MAX_C * 4;      // FAP: [2 FAP][src_c] scale, shift (, res_scale, res_shift)
+  constexpr int BNK_OFF = INFO_OFF + BM * 8;                  // the former's per-channel constants: [TABLES][src_c]
+  constexpr int SMEM_B = BNK_OFF + (AF != A_DMA ? Former::TABLES : 0) * BNA_MAX_C * 4;
   __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_B];
 
   const int tid = threadIdx.x;
@@ -370,31 +481,7 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || FAP !=
     }
     rowinfo[tid] = make_uint2(base, ok ? msk : 0u);
   }
-  if constexpr (BNA) {
-    float *bnk = reinterpret_cast<float *>(smem + BNK_OFF);
-    const int C = p.src_c;
-    for (int i = tid; i < C; i += 256) {
-      const long long gc = (long long)g * C + i;
-      bnk[i] = p.bna_mean[gc];
-      bnk[C + i] = p.bna_invstd[gc];
-      bnk[2 * C + i] = p.bna_gamma[i];
-      bnk[3 * C + i] = p.bna_s1[gc];
-      bnk[4 * C + i] = p.bna_s2[gc];
-    }
-  }
-  if constexpr (FAP != 0) {
-    float *fk = reinterpret_cast<float *>(smem + BNK_OFF);
-    const int C = p.src_c;
-    for (int i = tid; i < C; i += 256) {
-      const long long gc = (long long)g * C + i;
-      fk[i] = p.fap_scale[gc];
-      fk[C + i] = p.fap_shift[gc];
-      if constexpr (FAP == 2) {
-        fk[2 * C + i] = p.fap_res_scale[gc];
-        fk[3 * C + i] = p.fap_res_shift[gc];
-      }
-    }
-  }
+  if constexpr (AF != A_DMA) Former::stage(reinterpret_cast<float *>(smem + BNK_OFF), p, g, p.src_c, tid);
   __syncthreads();
   // ---- the instructions this wave issues: Q = wave + 4 i; lane -> linear slot 64 Q + lane -> (row, slot in row);
   // the slot holds source slot j = slot ^ h(row) of the row's 128-byte span (j = 2 cc + pc: the memory order)
@@ -436,7 +523,7 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || FAP !=
       const int btap = (c.tap_r0 + p.tap_step * fru) * p.s + c.tap_s0 + p.tap_step * fsu;
       kb = (unsigned)(btap * p.src_c + chb) * (unsigned)SP_BYTES;
     }
-    if constexpr (!BNA && FAP == 0) {
+    if constexpr (AF == A_DMA) {
 #pragma unroll
       for (int i = 0; i < A_PER; ++i) {
         const bool ok = ((a_vmask[i] >> tap_u) & 1u) != 0u;
@@ -483,97 +570,13 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || FAP !=
   };
   // smallest terms first: (a1 b2, a2 b1), a1 b1
   auto products = [&](const f16x8 (&av)[SP_NP][TM], const f16x8 (&bv)[SP_NP][TN]) { SPLIT16_ONE(0, 1) SPLIT16_ONE(1, 0) SPLIT16_ONE(0, 0) };
-  if constexpr (BNA) {
-    // (1x1, stride 1: the GEMM's rows are dy's pixels, K-step kt = channels 32 kt .. 32 kt + 31)
+  if constexpr (AF != A_DMA) {
+    // (1x1, stride 1: the GEMM's rows are the formed map's pixels, K-step kt = channels 32 kt .. 32 kt + 31)
     const int C = p.src_c;
     const int a_cc = tid & 3, a_r0 = tid >> 2;
     const long long grow0 = (long long)g * c.rows_per_group;
-    const __amdgpu_buffer_rsrc_t rs_dz = make_rsrc(p.bna_dz + grow0 * C, 4ll * c.rows_per_group * C);
-    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(p.bna_y + grow0 * C, 4ll * c.rows_per_group * C);
-    uint4 *dy_out = reinterpret_cast<uint4 *>(const_cast<float *>(p.a)) + grow0 * C / 4;      // 4 bytes per element
-    const float inv_rows = p.bna_inv_rows;
-    const float dsc = 1.f / *p.a_sinv;                        // 2^k (exact: a power of two)
-    bool a_ok[2];
-    unsigned a_goff[2];                                        // byte offset of (row, chunk) in the group's fp32 maps = in its sp dy
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long long m = (long long)mtile * BM + a_r0 + 64 * i;
-      a_ok[i] = m < c.rows_per_group;
-      a_goff[i] = pred_off((unsigned)m * (unsigned)C * 4u + 32u * (unsigned)a_cc, a_ok[i]);
-    }
-    float4 dzv[2][2], yv[2][2];
-    auto a_load = [&](int kt) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const unsigned off = a_goff[i] + 128u * (unsigned)kt;
-        dzv[i][0] = buf_ld16(rs_dz, off);
-        dzv[i][1] = buf_ld16(rs_dz, off + 16u);
-        yv[i][0] = buf_ld16(rs_y, off);
-        yv[i][1] = buf_ld16(rs_y, off + 16u);
-      }
-    };
-    // the next K-step's dz and y in flight while this one is multiplied: 32 more live registers, which the 128-column tile
-    // (64 accumulators, 64 fragment registers) does not have at three workgroups per CU (168) - it loads at the top instead
-    constexpr bool PREFETCH = BN == 64;
-    if (PREFETCH) a_load(0);
-    for (int kt = 0; kt < KT; ++kt) {
-      issue(kt, 0);                                            // the weights: DMA
-      if (!PREFETCH) a_load(kt);
-      uint4 q[2][SP_NP];
-      {
-        const float *kc = reinterpret_cast<const float *>(smem + BNK_OFF) + kt * SP_BK + a_cc * 8;
-        float mu[8], is[8], ga[8], sa[8], sb[8];
-        ld8(kc, mu);
-        ld8(kc + C, is);
-        ld8(kc + 2 * C, ga);
-        ld8(kc + 3 * C, sa);
-        ld8(kc + 4 * C, sb);
-#pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const float d[8] = {dzv[i][0].x, dzv[i][0].y, dzv[i][0].z, dzv[i][0].w, dzv[i][1].x, dzv[i][1].y, dzv[i][1].z, dzv[i][1].w};
-          const float v[8] = {yv[i][0].x, yv[i][0].y, yv[i][0].z, yv[i][0].w, yv[i][1].x, yv[i][1].y, yv[i][1].z, yv[i][1].w};
-          float o[8];
-#pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            const float t = bn_dy(d[k], v[k], mu[k], is[k], ga[k], sa[k], sb[k], inv_rows) * dsc;
-            o[k] = a_ok[i] ? t : 0.f;                          // rows beyond the group: the zeros the DMA loader reads there
-          }
-          split2_chunk(o, q[i][0], q[i][1]);
-          const int R = a_r0 + 64 * i;
-#pragma unroll
-          for (int pc = 0; pc < SP_NP; ++pc)
-            *reinterpret_cast<uint4 *>(smem + R * ROWB + (((2 * a_cc + pc) ^ sp_row_swz(R)) << 4)) = q[i][pc];
-        }
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        if (a_ok[i]) {
-          uint4 *dst = dy_out + ((a_goff[i] + 128u * (unsigned)kt) >> 4);
-          dst[0] = q[i][0];
-          dst[1] = q[i][1];
-        }
-      if (PREFETCH && kt + 1 < KT) a_load(kt + 1);             // in flight while this K-step is multiplied
-      {
-        f16x8 av[SP_NP][TM], bv[SP_NP][TN];
-        load_frags(smem, av, bv);
-        products(av, bv);
-      }
-      __syncthreads();                                         // everyone is done reading before the next K-step is written
-    }
-  } else if constexpr (FAP != 0) {
-    // (1x1, stride 1: the GEMM's rows are the block output's pixels, K-step kt = channels 32 kt .. 32 kt + 31)
-    const int C = p.src_c;
-    const int a_cc = tid & 3, a_r0 = tid >> 2;
-    const long long grow0 = (long long)g * c.rows_per_group;
-    const __amdgpu_buffer_rsrc_t rs_y = make_rsrc(p.fap_y + grow0 * C, 4ll * c.rows_per_group * C);
-    const __amdgpu_buffer_rsrc_t rs_r = make_rsrc(reinterpret_cast<const float *>(p.fap_res) + grow0 * C, 4ll * c.rows_per_group * C);
+    Former f(p, grow0, c.rows_per_group, C);
     uint4 *a_out = reinterpret_cast<uint4 *>(const_cast<float *>(p.a)) + grow0 * C / 4;       // 4 bytes per element
-    unsigned short *bits_out = p.fap_bits ? p.fap_bits + grow0 * (C >> 3) : nullptr;           // one per chunk
-    // 2^k of out, 2^-k of the identity (exact: powers of two; uniform: scalar registers)
-    const float osc = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(p.a_sinv ? 1.f / *p.a_sinv : 1.f)));
-    const float rsi = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint((FAP == 1 && p.fap_res_sinv) ? *p.fap_res_sinv : 1.f)));
     bool a_ok[2];
     unsigned a_goff[2];                                        // byte offset of (row, chunk) in the group's fp32 maps = in its sp maps
 #pragma unroll
@@ -582,63 +585,28 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || FAP !=
       a_ok[i] = m < c.rows_per_group;
       a_goff[i] = pred_off((unsigned)m * (unsigned)C * 4u + 32u * (unsigned)a_cc, a_ok[i]);
     }
-    float4 yv[2][2], rv[2][2];                                 // rv: FAP = 1 the identity's two pieces (bits), FAP = 2 fp32
     auto a_load = [&](int kt) {
 #pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        const unsigned off = a_goff[i] + 128u * (unsigned)kt;
-        yv[i][0] = buf_ld16(rs_y, off);
-        yv[i][1] = buf_ld16(rs_y, off + 16u);
-        rv[i][0] = buf_ld16(rs_r, off);
-        rv[i][1] = buf_ld16(rs_r, off + 16u);
-      }
+      for (int i = 0; i < 2; ++i) f.load(i, a_goff[i] + 128u * (unsigned)kt);
     };
-    // the next K-step's y and residual in flight while this one is multiplied: as BNA, where the registers allow (BN = 64)
+    // the next K-step's inputs in flight while this one is multiplied: 32 more live registers, which the 128-column tile
+    // (64 accumulators, 64 fragment registers) does not have at three workgroups per CU (168) - it loads at the top instead
     constexpr bool PREFETCH = BN == 64;
     if (PREFETCH) a_load(0);
     for (int kt = 0; kt < KT; ++kt) {
       issue(kt, 0);                                            // the weights: DMA
       if (!PREFETCH) a_load(kt);
       uint4 q[2][SP_NP];
-      unsigned mb[2];
-      {
-        const float *kc = reinterpret_cast<const float *>(smem + BNK_OFF) + kt * SP_BK + a_cc * 8;
-        float sc[8], sh[8], rs[8], rh[8];
-        ld8(kc, sc);
-        ld8(kc + C, sh);
-        if constexpr (FAP == 2) {
-          ld8(kc + 2 * C, rs);
-          ld8(kc + 3 * C, rh);
-        }
+      f.consts(reinterpret_cast<const float *>(smem + BNK_OFF) + kt * SP_BK + a_cc * 8, C);
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
-          const float v[8] = {yv[i][0].x, yv[i][0].y, yv[i][0].z, yv[i][0].w, yv[i][1].x, yv[i][1].y, yv[i][1].z, yv[i][1].w};
-          float r[8];
-          if constexpr (FAP == 1) {
-            const uint4 r1 = make_uint4(__float_as_uint(rv[i][0].x), __float_as_uint(rv[i][0].y), __float_as_uint(rv[i][0].z), __float_as_uint(rv[i][0].w));
-            const uint4 r2 = make_uint4(__float_as_uint(rv[i][1].x), __float_as_uint(rv[i][1].y), __float_as_uint(rv[i][1].z), __float_as_uint(rv[i][1].w));
-            merge2_chunk(r1, r2, r);
-          } else {
-            r[0] = rv[i][0].x; r[1] = rv[i][0].y; r[2] = rv[i][0].z; r[3] = rv[i][0].w;
-            r[4] = rv[i][1].x; r[5] = rv[i][1].y; r[6] = rv[i][1].z; r[7] = rv[i][1].w;
-          }
-          float o[8];
-          unsigned m = 0;
+      for (int i = 0; i < 2; ++i) {
+        float o[8];
+        f.form(i, a_ok[i], o);
+        split2_chunk(o, q[i][0], q[i][1]);
+        const int R = a_r0 + 64 * i;
 #pragma unroll
-          for (int k = 0; k < 8; ++k) {
-            float x = bn_fwd(v[k], sc[k], sh[k]);              // bn_apply_sp_kernel's expressions, in its order
-            x += FAP == 2 ? bn_fwd(r[k], rs[k], rh[k]) : r[k] * rsi;
-            x = fmaxf(x, 0.f);
-            m |= (x > 0.f ? 1u : 0u) << (k + (k >= 4 ? 4 : 0));
-            o[k] = a_ok[i] ? x * osc : 0.f;                    // rows beyond the group: the zeros the DMA loader reads there
-          }
-          mb[i] = m;
-          split2_chunk(o, q[i][0], q[i][1]);
-          const int R = a_r0 + 64 * i;
-#pragma unroll
-          for (int pc = 0; pc < SP_NP; ++pc)
-            *reinterpret_cast<uint4 *>(smem + R * ROWB + (((2 * a_cc + pc) ^ sp_row_swz(R)) << 4)) = q[i][pc];
-        }
+        for (int pc = 0; pc < SP_NP; ++pc)
+          *reinterpret_cast<uint4 *>(smem + R * ROWB + (((2 * a_cc + pc) ^ sp_row_swz(R)) << 4)) = q[i][pc];
       }
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
@@ -649,7 +617,7 @@ __global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || FAP !=
           uint4 *dst = a_out + (off >> 4);
           dst[0] = q[i][0];
           dst[1] = q[i][1];
-          if (bits_out) bits_out[off >> 5] = (unsigned short)mb[i];
+          f.store_extra(i, off);
         }
       if (PREFETCH && kt + 1 < KT) a_load(kt + 1);             // in flight while this K-step is multiplied
       {
@@ -1020,46 +988,32 @@ static int validate_split(const mvg_conv_desc *d) {
 // tiles.  A function of the descriptor alone: mvg_conv_dgrad_bn_partials_split sizes the fused reduce's partials with it.
 static int split_tile_rows(int ncols, int taps, long long rows) { return (ncols < 128 && taps > 1 && rows >= 65536) ? 256 : SP_BM; }
 
-template <bool DGRAD>
-static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin = false, int bm = SP_BM, bool bna = false, int fap = 0) {
+// The tiling of an igemm_split16_kernel launch and the K loop it gets: a function of (columns, taps, rows of the whole map, groups,
+// each class's rows per group and K, lin) - launch_igemm_split launches by it, mvg_conv_fprop_split_stages answers from it.  Writes
+// every class's mtiles_per_group, KT and tile0.  (256-row tiles come with 64 columns and never with lin: by construction.)
+struct SplitPlan { int bm, bn, kt_max; long long tiles; bool pipelined; };
+static SplitPlan split_plan(int ncols, int taps, long long rows, int groups, bool lin, IgemmClass *cls, int ncls) {
+  SplitPlan pl;
+  pl.bm = lin ? SP_BM : split_tile_rows(ncols, taps, rows);
   // (128 x 64 tiles for the short-K, write-heavy 1x1 layers - 64 -> 256 at 56 x 56 and the like - were measured in round 4:
   // within 2 % of 128 x 128 on every such shape, forward and backward-data)
-  int bn = p.ncols >= 128 ? 128 : 64;
-  if (lin && bn == 128 && p.ncls == 1) {
+  pl.bn = ncols >= 128 ? 128 : 64;
+  if (lin && pl.bn == 128 && ncls == 1) {
     // a Linear whose 128 x 128 tiles would leave most CUs idle (C3's head layer: 48 tiles; C4's per-GPU share: 12 - 84):
     // a lone workgroup takes in ~41 GB/s, so the launch is as fast as its busiest CU's operand bytes - 128 x 64 tiles
     // (24 KB instead of 32 KB per K-step) on twice the CUs
-    const long long t128 = (long long)p.groups * ceil_div(p.cls[0].rows_per_group, bm) * ceil_div(p.ncols, 128);
-    if (2 * t128 <= compute_cus()) bn = 64;
+    const long long t128 = (long long)groups * ceil_div(cls[0].rows_per_group, pl.bm) * ceil_div(ncols, 128);
+    if (2 * t128 <= compute_cus()) pl.bn = 64;
   }
-  MVG_REQUIRE(bm == SP_BM || (bm == 256 && bn == 64 && !lin), "split conv: 256-row tiles go with 64 columns");
-  p.ntiles = ceil_div(p.ncols, bn);
-  p.splits = 1;
-  p.sk_tiles = 0;
-  long long tiles = 0;
-  p.bn_parts = 0;
-  for (int i = 0; i < p.ncls; ++i) {
-    IgemmClass &c = p.cls[i];
-    c.mtiles_per_group = ceil_div(c.rows_per_group, bm);
+  pl.tiles = 0, pl.kt_max = 0;
+  for (int i = 0; i < ncls; ++i) {
+    IgemmClass &c = cls[i];
+    c.mtiles_per_group = ceil_div(c.rows_per_group, pl.bm);
     c.KT = ceil_div(c.ktotal, SP_BK);              // 0: a class without taps (fused reduce only) - its tiles are epilogue only
-    c.korder = c.ntaps > 1 ? 1 : 0;
-    c.per_div = make_fastdiv((unsigned)(c.ntaps > 0 ? c.ntaps : 1));
-    c.tile0 = (int)tiles;
-    c.unit0 = 0;
-    c.part0 = p.bn_parts;
-    p.bn_parts += c.mtiles_per_group;
-    tiles += (long long)p.groups * c.mtiles_per_group * p.ntiles;
-    MVG_REQUIRE((c.ntaps >= 1 || (DGRAD && p.bn_part)) && c.ntaps <= 32 && c.ktotal % SP_BK == 0, "split conv: class shape not covered");
+    c.tile0 = (int)pl.tiles;
+    pl.tiles += (long long)groups * c.mtiles_per_group * ceil_div(ncols, pl.bn);
+    pl.kt_max = c.KT > pl.kt_max ? c.KT : pl.kt_max;
   }
-  MVG_REQUIRE(tiles < (1LL << 31), "split conv: grid too large");
-  if (tiles <= 0) return 0;
-  // The backbone's fp32 results (y, dx: 0.2 - 1.7 GB per launch, next read by a BatchNorm pass that streams them once) leave
-  // with non-temporal stores: C3 81.4 -> 80.9 ms per step on one box (the passes that follow find more of their other
-  // operand in the Infinity Cache: bn_apply 8.8 -> 8.4 ms).  Not the stride-2 parity classes - they write every other pixel,
-  // which wants the cache to merge lines (0.96 -> 1.01 ms on 256 -> 512 at 56 x 56) - and not the fusion block's Linears,
-  // whose results are re-read at once.
-  p.nt_out = (!lin && !(DGRAD && p.cls_step == 2)) ? 1 : 0;
-  dim3 grid((unsigned)tiles), block(256);
   // At most two workgroups per CU: nobody covers a workgroup's waits - the two-stage software pipeline.  Measured per shape
   // (scripts/linear_split_bench.py, C3's fusion rows: fprop 431 -> 320 us per iteration, dgrad 246 -> 210;
   // scripts/conv_bench.py 50 32 4, C4's per-GPU share: 15.2 -> 14.6 ms over the net, 512-channel 3x3 at 7x7 0.169 -> 0.127 ms;
@@ -1068,24 +1022,49 @@ static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin = false, 
   // Up to four per CU it still wins where the K loop is long (ResNet-50's 7x7 stage at C3, 784 tiles: 512-channel 3x3
   // backward-data + reduce 0.399 -> 0.322 ms, 2048 <- 512 backward-data 0.218 -> 0.185); with every slot filled the
   // single-stage loop at four workgroups per CU is faster (17.4 vs 19.5 ms over the forward net).
-  int kt_max = 0;
-  for (int i = 0; i < p.ncls; ++i) kt_max = p.cls[i].KT > kt_max ? p.cls[i].KT : kt_max;
-  const bool pipelined = tiles <= 2LL * compute_cus() || (tiles <= 4LL * compute_cus() && kt_max >= 48);
-  if constexpr (DGRAD) {
-    if (bna) {               // dy formed in the loader (same tiles as the DMA kernels: the fused reduce's partials are theirs)
-      MVG_REQUIRE(!lin && bm == SP_BM && p.ntiles == 1 && p.ncls == 1, "split conv: the dy-forming loader takes one column tile");
-      if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, true, false, 2, 1, true>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((igemm_split16_kernel<64, true, false, 2, 1, true>), grid, block, 0, st, p);
-      return check_launch("conv_dgrad_split_bnapply");
-    }
+  pl.pipelined = pl.tiles <= 2LL * compute_cus() || (pl.tiles <= 4LL * compute_cus() && pl.kt_max >= 48);
+  return pl;
+}
+
+// taps, rows: the filter's taps and the rows of the whole map (the row-tile height's arguments); af: the loader forms the A operand
+template <bool DGRAD>
+static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin, int taps, long long rows, AForm af = A_DMA) {
+  const SplitPlan pl = split_plan(p.ncols, taps, rows, p.groups, lin, p.cls, p.ncls);
+  const int bm = pl.bm, bn = pl.bn;
+  const bool pipelined = pl.pipelined;
+  p.ntiles = ceil_div(p.ncols, bn);
+  p.splits = 1;
+  p.sk_tiles = 0;
+  p.bn_parts = 0;
+  for (int i = 0; i < p.ncls; ++i) {
+    IgemmClass &c = p.cls[i];
+    c.korder = c.ntaps > 1 ? 1 : 0;
+    c.per_div = make_fastdiv((unsigned)(c.ntaps > 0 ? c.ntaps : 1));
+    c.unit0 = 0;
+    c.part0 = p.bn_parts;
+    p.bn_parts += c.mtiles_per_group;
+    MVG_REQUIRE((c.ntaps >= 1 || (DGRAD && p.bn_part)) && c.ntaps <= 32 && c.ktotal % SP_BK == 0, "split conv: class shape not covered");
   }
-  if constexpr (!DGRAD) {
-    if (fap) {               // the block output formed in the loader (same tiles, K order and epilogue as the DMA kernels)
-      MVG_REQUIRE(!lin && bm == SP_BM && p.ntiles == 1 && p.ncls == 1, "split conv: the block-output-forming loader takes one column tile");
-      if (bn == 128 && fap == 2) hipLaunchKernelGGL((igemm_split16_kernel<128, false, false, 2, 1, false, 2>), grid, block, 0, st, p);
-      else if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, false, false, 2, 1, false, 1>), grid, block, 0, st, p);
-      else if (fap == 2) hipLaunchKernelGGL((igemm_split16_kernel<64, false, false, 2, 1, false, 2>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((igemm_split16_kernel<64, false, false, 2, 1, false, 1>), grid, block, 0, st, p);
+  MVG_REQUIRE(pl.tiles < (1LL << 31), "split conv: grid too large");
+  if (pl.tiles <= 0) return 0;
+  // The backbone's fp32 results (y, dx: 0.2 - 1.7 GB per launch, next read by a BatchNorm pass that streams them once) leave
+  // with non-temporal stores: C3 81.4 -> 80.9 ms per step on one box (the passes that follow find more of their other
+  // operand in the Infinity Cache: bn_apply 8.8 -> 8.4 ms).  Not the stride-2 parity classes - they write every other pixel,
+  // which wants the cache to merge lines (0.96 -> 1.01 ms on 256 -> 512 at 56 x 56) - and not the fusion block's Linears,
+  // whose results are re-read at once.
+  p.nt_out = (!lin && !(DGRAD && p.cls_step == 2)) ? 1 : 0;
+  dim3 grid((unsigned)pl.tiles), block(256);
+  if (af != A_DMA) {         // the A operand formed in the loader (tiles, K order, epilogue - the fused reduce's partials - as the DMA kernels)
+    MVG_REQUIRE(!lin && bm == SP_BM && p.ntiles == 1 && p.ncls == 1 && DGRAD == (af == A_DY), "split conv: the operand-forming loaders take one column tile");
+    if constexpr (DGRAD) {
+      if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, true, false, 2, 1, A_DY>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((igemm_split16_kernel<64, true, false, 2, 1, A_DY>), grid, block, 0, st, p);
+      return check_launch("conv_dgrad_split_bnapply");
+    } else {
+      if (bn == 128 && af == A_OUT_AFFINE) hipLaunchKernelGGL((igemm_split16_kernel<128, false, false, 2, 1, A_OUT_AFFINE>), grid, block, 0, st, p);
+      else if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, false, false, 2, 1, A_OUT_SP>), grid, block, 0, st, p);
+      else if (af == A_OUT_AFFINE) hipLaunchKernelGGL((igemm_split16_kernel<64, false, false, 2, 1, A_OUT_AFFINE>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((igemm_split16_kernel<64, false, false, 2, 1, A_OUT_SP>), grid, block, 0, st, p);
       return check_launch("conv_fprop_split_bnapply");
     }
   }
@@ -1243,9 +1222,8 @@ static int fprop_split_impl(const mvg_conv_desc *d, const void *x_sp, const floa
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
   ProfScope ps(lin ? MVG_K_LINEAR_FPROP : MVG_K_CONV_FPROP, (hipStream_t)stream, flops, bytes);
   p.stats_partials = ceil_div(p.rows_per_group, SP_BM) * 2;    // = mvg_conv_stats_partials_split
-  const bool lin_k = aff && aff->lin;
-  return launch_igemm_split<false>(p, (hipStream_t)stream, lin_k, lin_k ? SP_BM : split_tile_rows(d->cout, d->r * d->s, p.rows_per_group), false,
-                                   fap ? (fap->res_scale ? 2 : 1) : 0);
+  return launch_igemm_split<false>(p, (hipStream_t)stream, aff && aff->lin, d->r * d->s, p.rows_per_group,
+                                   fap ? (fap->res_scale ? A_OUT_AFFINE : A_OUT_SP) : A_DMA);
 }
 
 int mvg_conv_fprop_split(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *w_sp, const float *w_sinv, float *y,
@@ -1257,12 +1235,12 @@ int mvg_conv_fprop_split_stages(const mvg_conv_desc *d) {
   // 1 / 2: the K loop launch_igemm_split picks for this forward (single-stage / the two-stage pipeline); -1: bad descriptor.
   // (mvg_conv_fprop_split_bnapply exists in the single-stage form only: the caller's eligibility rule asks here.)
   if (validate_split(d)) return -1;
-  const long long rows = (long long)d->n * d->ho * d->wo;
-  const int bm = split_tile_rows(d->cout, d->r * d->s, rows);
-  const long long tiles = (long long)d->groups * ceil_div(rows, bm) * ceil_div(d->cout, d->cout >= 128 ? 128 : 64);
-  const int kt = ceil_div(d->r * d->s * d->cin, SP_BK);
-  const bool pipelined = tiles <= 2LL * compute_cus() || (tiles <= 4LL * compute_cus() && kt >= 48);
-  return (pipelined && d->cout >= 128 && bm == SP_BM) ? 2 : 1;
+  IgemmClass c;
+  memset(&c, 0, sizeof(c));
+  c.rows_per_group = (long long)d->n * d->ho * d->wo;
+  c.ktotal = d->r * d->s * d->cin;
+  const SplitPlan pl = split_plan(d->cout, d->r * d->s, c.rows_per_group, d->groups, false, &c, 1);
+  return (pl.pipelined && pl.bn == 128 && pl.bm == SP_BM) ? 2 : 1;         // launch_igemm_split's dispatch for a conv
 }
 
 int mvg_conv_fprop_split_bnapply(const mvg_conv_desc *d, void *out_sp, const float *out_sinv, const float *bn_y, const float *scale,
@@ -1352,8 +1330,7 @@ static int dgrad_split_impl(const mvg_conv_desc *d, const void *dy_sp, const flo
   ProfScope ps(lin ? MVG_K_LINEAR_DGRAD : MVG_K_CONV_DGRAD, (hipStream_t)stream, flops, bytes);
   if (int e = dgrad_classes(p, d, bnf != nullptr, 4, dx, addend, (hipStream_t)stream)) return e;
   if (p.ncls == 0) return 0;
-  return launch_igemm_split<true>(p, (hipStream_t)stream, lin_kernel,
-                                  lin_kernel ? SP_BM : split_tile_rows(d->cin, d->r * d->s, (long long)d->n * d->h * d->w), bna != nullptr);
+  return launch_igemm_split<true>(p, (hipStream_t)stream, lin_kernel, d->r * d->s, (long long)d->n * d->h * d->w, bna ? A_DY : A_DMA);
 }
 
 int mvg_conv_dgrad_split(const mvg_conv_desc *d, const void *dy_sp, const float *dy_sinv, const void *w_crsk_sp, const float *w_sinv,
@@ -1367,23 +1344,34 @@ int mvg_conv_dgrad_bn_partials_split(const mvg_conv_desc *d) {
   return dgrad_bn_partials(d, split_tile_rows(d->cin, d->r * d->s, (long long)d->n * d->h * d->w));
 }
 
+// Backward-data with the BatchNorm-backward reduce pass of the unit it feeds on board, then that pass's finalize: the tail of both
+// entries below (who: the entry's name in the messages; bna: the launch also forms its own dy)
+static int dgrad_split_bnreduce_impl(const char *who, const mvg_conv_desc *d, const void *dy_sp, const float *dy_sinv, const void *w_crsk_sp,
+                                     const float *w_sinv, float *dx, const float *addend, const float *bn_y, const uint8_t *bn_bits,
+                                     const float *bn_mean, const float *bn_invstd, const float *relu_scale, const float *relu_shift,
+                                     float *partials, float *s1, float *s2, float *dgamma, float *dbeta, int accumulate, float *mx,
+                                     const float *bn_gamma, float *dx_dy_sinv, void *stream, const SplitBnApply *bna) {
+  MVG_REQUIRE(bn_y && bn_mean && bn_invstd && partials && s1 && s2, "%s: null argument", who);
+  MVG_REQUIRE((bn_gamma == nullptr) == (dx_dy_sinv == nullptr) && (!dx_dy_sinv || mx), "%s: bn_gamma, dx_dy_sinv (and mx) go together", who);
+  MVG_REQUIRE(!(bn_bits && relu_scale) && ((relu_scale == nullptr) == (relu_shift == nullptr)),
+              "%s: give the ReLU mask either as bits or as (relu_scale, relu_shift)", who);
+  const int P = mvg_conv_dgrad_bn_partials_split(d);
+  MVG_REQUIRE(P > 0, "%s: bad descriptor", who);
+  const SplitBnFuse f = {bn_y, bn_bits, bn_mean, bn_invstd, relu_scale, relu_shift, partials, mx ? 3 : 2};
+  if (dgrad_split_impl(d, dy_sp, dy_sinv, w_crsk_sp, w_sinv, dx, addend, stream, &f, nullptr, false, nullptr, bna)) return 1;
+  ProfScope ps(MVG_K_BN_BWD_REDUCE, (hipStream_t)stream, 0.0, 8.0 * d->groups * (double)P * d->cin);
+  return bn_bwd_finalize_launch(partials, d->groups, P, d->cin, s1, s2, dgamma, dbeta, accumulate, (hipStream_t)stream, mx, nullptr, nullptr,
+                                bn_gamma, bn_invstd, (long long)d->n * d->h * d->w, dx_dy_sinv);
+}
+
 int mvg_conv_dgrad_split_bnreduce(const mvg_conv_desc *d, const void *dy_sp, const float *dy_sinv, const void *w_crsk_sp,
                                   const float *w_sinv, float *dx, const float *addend, const float *bn_y, const uint8_t *bn_bits,
                                   const float *bn_mean, const float *bn_invstd, const float *relu_scale, const float *relu_shift,
                                   float *partials, float *s1, float *s2, float *dgamma, float *dbeta, int accumulate,
                                   float *mx, const float *bn_gamma, float *dx_dy_sinv, void *stream) {
   // (dx_dy_sinv: receives the 2^-k of the dy that mvg_bn_bwd_apply_split will make from dx - the NEXT unit down the chain)
-  MVG_REQUIRE(bn_y && bn_mean && bn_invstd && partials && s1 && s2, "dgrad_split_bnreduce: null argument");
-  MVG_REQUIRE((bn_gamma == nullptr) == (dx_dy_sinv == nullptr) && (!dx_dy_sinv || mx), "dgrad_split_bnreduce: bn_gamma, dx_dy_sinv (and mx) go together");
-  MVG_REQUIRE(!(bn_bits && relu_scale) && ((relu_scale == nullptr) == (relu_shift == nullptr)),
-              "dgrad_split_bnreduce: give the ReLU mask either as bits or as (relu_scale, relu_shift)");
-  const int P = mvg_conv_dgrad_bn_partials_split(d);
-  MVG_REQUIRE(P > 0, "dgrad_split_bnreduce: bad descriptor");
-  const SplitBnFuse f = {bn_y, bn_bits, bn_mean, bn_invstd, relu_scale, relu_shift, partials, mx ? 3 : 2};
-  if (dgrad_split_impl(d, dy_sp, dy_sinv, w_crsk_sp, w_sinv, dx, addend, stream, &f)) return 1;
-  ProfScope ps(MVG_K_BN_BWD_REDUCE, (hipStream_t)stream, 0.0, 8.0 * d->groups * (double)P * d->cin);
-  return bn_bwd_finalize_launch(partials, d->groups, P, d->cin, s1, s2, dgamma, dbeta, accumulate, (hipStream_t)stream, mx, nullptr, nullptr,
-                                bn_gamma, bn_invstd, (long long)d->n * d->h * d->w, dx_dy_sinv);
+  return dgrad_split_bnreduce_impl("dgrad_split_bnreduce", d, dy_sp, dy_sinv, w_crsk_sp, w_sinv, dx, addend, bn_y, bn_bits, bn_mean, bn_invstd,
+                                   relu_scale, relu_shift, partials, s1, s2, dgamma, dbeta, accumulate, mx, bn_gamma, dx_dy_sinv, stream, nullptr);
 }
 
 int mvg_conv_dgrad_split_bnapply_bnreduce(const mvg_conv_desc *d, void *dy_sp, const float *dy_sinv, const float *dz, const float *y,
@@ -1401,19 +1389,9 @@ int mvg_conv_dgrad_split_bnapply_bnreduce(const mvg_conv_desc *d, void *dy_sp, c
   MVG_REQUIRE(d->cout % 32 == 0 && d->cout <= BNA_MAX_C, "dgrad_split_bnapply_bnreduce: cout must be a multiple of 32, at most %d (got %d)",
               BNA_MAX_C, d->cout);
   MVG_REQUIRE(rows_per_group == (int64_t)d->n * d->ho * d->wo, "dgrad_split_bnapply_bnreduce: rows_per_group is not n * ho * wo");
-  MVG_REQUIRE(bn_y && bn_mean && bn_invstd && partials && s1 && s2, "dgrad_split_bnapply_bnreduce: null argument");
-  MVG_REQUIRE((bn_gamma == nullptr) == (dx_dy_sinv == nullptr) && (!dx_dy_sinv || mx),
-              "dgrad_split_bnapply_bnreduce: bn_gamma, dx_dy_sinv (and mx) go together");
-  MVG_REQUIRE(!(bn_bits && relu_scale) && ((relu_scale == nullptr) == (relu_shift == nullptr)),
-              "dgrad_split_bnapply_bnreduce: give the ReLU mask either as bits or as (relu_scale, relu_shift)");
-  const int P = mvg_conv_dgrad_bn_partials_split(d);
-  MVG_REQUIRE(P > 0, "dgrad_split_bnapply_bnreduce: bad descriptor");
-  const SplitBnFuse f = {bn_y, bn_bits, bn_mean, bn_invstd, relu_scale, relu_shift, partials, mx ? 3 : 2};
   const SplitBnApply a = {dz, y, mean, invstd, gamma, un_s1, un_s2, (long long)rows_per_group};
-  if (dgrad_split_impl(d, dy_sp, dy_sinv, w_crsk_sp, w_sinv, dx, addend, stream, &f, nullptr, false, nullptr, &a)) return 1;
-  ProfScope ps(MVG_K_BN_BWD_REDUCE, (hipStream_t)stream, 0.0, 8.0 * d->groups * (double)P * d->cin);
-  return bn_bwd_finalize_launch(partials, d->groups, P, d->cin, s1, s2, dgamma, dbeta, accumulate, (hipStream_t)stream, mx, nullptr, nullptr,
-                                bn_gamma, bn_invstd, (long long)d->n * d->h * d->w, dx_dy_sinv);
+  return dgrad_split_bnreduce_impl("dgrad_split_bnapply_bnreduce", d, dy_sp, dy_sinv, w_crsk_sp, w_sinv, dx, addend, bn_y, bn_bits, bn_mean,
+                                   bn_invstd, relu_scale, relu_shift, partials, s1, s2, dgamma, dbeta, accumulate, mx, bn_gamma, dx_dy_sinv, stream, &a);
 }
 
 static void wgrad_split_tile(const mvg_conv_desc *d, int &bm, int &bn) {

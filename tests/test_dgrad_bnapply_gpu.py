@@ -12,7 +12,7 @@ pytestmark = pytest.mark.gpu
 
 # (G, N, h, cin, cout): 75 rows - one ragged tile; 162 rows - a full tile and a ragged one; two K-steps; five K-steps with
 # cout not a multiple of 64; 49 tiles
-SHAPES = [(2, 3, 5, 64, 256), (1, 2, 9, 128, 512), (3, 2, 14, 64, 64), (2, 5, 9, 128, 160), (1, 2, 56, 64, 256)]
+SHAPES = [(2, 3, 5, 64, 256), (1, 2, 9, 128, 512), (3, 2, 14, 64, 64), (2, 5, 9, 128, 160), (1, 2, 56, 64, 256), (1, 1, 3, 64, 32)]
 SENTINEL = 1234.0
 
 

@@ -11,7 +11,7 @@ pytestmark = pytest.mark.gpu
 
 # (G, N, h, cin, cout): 75 rows - one ragged tile, two groups; 162 rows - a full tile and a ragged one, 16 K-steps, 128
 # columns; two K-steps, three groups; 13 tiles
-SHAPES = [(2, 3, 5, 256, 64), (1, 2, 9, 512, 128), (3, 2, 14, 64, 64), (1, 2, 28, 256, 128)]
+SHAPES = [(2, 3, 5, 256, 64), (1, 2, 9, 512, 128), (3, 2, 14, 64, 64), (1, 2, 28, 256, 128), (1, 1, 3, 32, 64)]
 SENTINEL = 1234.0
 
 
