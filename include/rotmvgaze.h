@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MVG_ABI_VERSION 10
+#define MVG_ABI_VERSION 11
 
 /* ---------------------------------------------------------------- library */
 int mvg_abi_version(void);
@@ -642,8 +642,13 @@ int mvg_conv_dgrad_split_bnapply_bnreduce(const mvg_conv_desc *d, void *dy_sp, c
  * [groups][cin]; multiplies it and WRITES it times 1 / *out_sinv to out_sp (an output here: later readers find it as the apply pass
  * leaves it), and the ReLU mask to relu_bits (may be NULL).  Everything from w_sp on is mvg_conv_fprop_split's.  out_sp, relu_bits,
  * y and stats hold the bits the two calls leave.  The launch runs the single-stage K loop: mvg_conv_fprop_split_stages tells which
- * form mvg_conv_fprop_split picks for a descriptor on this device (1 = single-stage, 2 = two-stage pipeline, -1 = bad descriptor). */
+ * form mvg_conv_fprop_split picks for a descriptor on this device (1 = single-stage, 2 = two-stage pipeline, -1 = bad descriptor).
+ * mvg_conv_dgrad_split_stages answers the same for mvg_conv_dgrad_split (fused_reduce = 0) and mvg_conv_dgrad_split_bnreduce
+ * (fused_reduce != 0: the launch keeps the stride-2 parity classes without taps, so it has more tiles).  Both are host arithmetic
+ * by the launch's own plan - device CUs minus mvg_set_reserved_cus - and launch nothing: a test asserts with them which kernel
+ * form a shape ran. */
 int mvg_conv_fprop_split_stages(const mvg_conv_desc *d);
+int mvg_conv_dgrad_split_stages(const mvg_conv_desc *d, int fused_reduce);
 int mvg_conv_fprop_split_bnapply(const mvg_conv_desc *d, void *out_sp, const float *out_sinv, const float *bn_y, const float *scale,
                                  const float *shift, const void *residual, int residual_sp, const float *res_scale,
                                  const float *res_shift, const float *res_sinv, uint8_t *relu_bits, const void *w_sp,
@@ -678,6 +683,10 @@ int mvg_bn_relu_maxpool_bwd_apply_split(const float *g_pooled, const uint8_t *ar
                                         const float *s1, const float *s2, int groups, int n_per_group, int h, int w, int c,
                                         int ho, int wo, void *dy_sp, const float *mx, float *dy_sinv, int dy_sinv_ready, void *stream);
 int mvg_conv_wgrad_splits_split(const mvg_conv_desc *d);   /* pixel-split count; workspace = splits * cout*r*s*cin floats */
+/* The tile mvg_conv_wgrad_split runs a descriptor on: *bm x *bn (cout rows x r*s*cin columns; 128 x 256, 128 x 192, 128 x 128,
+ * 128 x 64, 64 x 192, 64 x 128 or 64 x 64) and *incremental = 1 when the kernel addresses pixels incrementally (ho * wo >= 32).
+ * Each pointer may be NULL.  Host arithmetic by the launch's own choice, launches nothing; 0, or -1 for a bad descriptor. */
+int mvg_conv_wgrad_split_tile(const mvg_conv_desc *d, int32_t *bm, int32_t *bn, int32_t *incremental);
 int mvg_conv_wgrad_split(const mvg_conv_desc *d, const void *x_sp, const void *dy_sp, const float *dy_sinv, float *dw,
                          float *workspace, int splits, int accumulate, void *stream);
 /* The same launch WITHOUT its slab reduce (splits > 1: workspace receives the per-split partial gradients), and the reduces

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "librotmvgaze_hip.so")
 
 K_FAMILIES = 18
-ABI_VERSION = 10
+ABI_VERSION = 11
 
 
 class ConvDesc(C.Structure):
@@ -100,8 +100,10 @@ SIGNATURES = {
     "mvg_conv_dgrad_split_bnreduce": (_I, [_D, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _P, _P, _P, _P]),
     "mvg_conv_dgrad_split_bnapply_bnreduce": (_I, [_D] + [_P] * 9 + [_I64] + [_P] * 15 + [_I, _P, _P, _P, _P]),
     "mvg_conv_fprop_split_stages": (_I, [_D]),
+    "mvg_conv_dgrad_split_stages": (_I, [_D, _I]),
     "mvg_conv_fprop_split_bnapply": (_I, [_D] + [_P] * 6 + [_I] + [_P] * 9),
     "mvg_conv_wgrad_splits_split": (_I, [_D]),
+    "mvg_conv_wgrad_split_tile": (_I, [_D, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mvg_conv_wgrad_split": (_I, [_D, _P, _P, _P, _P, _P, _I, _I, _P]),
     "mvg_conv_wgrad_split_slabs": (_I, [_D, _P, _P, _P, _P, _I, _P]),
     "mvg_wgrad_reduce_batch": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_int32),

@@ -402,13 +402,17 @@ static __global__ __launch_bounds__(256) void dgrad_empty_class_kernel(uint4 *__
 // The classes of a backward-data launch (p from dgrad_geometry): one at stride 1; at stride 2 one per output-pixel parity
 // (py, px) - each a dense sub-convolution over its own taps - all merged into p.cls, longest first (with one tile per
 // workgroup the short tiles then fill the tail); the launch-wide fields are the first class's.  A class without taps is a
-// class of its own when keep_tapless (a fused BatchNorm reduce: its tiles run the epilogue only); otherwise
-// dgrad_empty_class_kernel writes dx = addend there now (nothing when the caller accumulates in place; dx_elem bytes per
-// element).  p.ncls == 0 on return: nothing left to launch.
-static int dgrad_classes(IgemmParams &p, const mvg_conv_desc *d, bool keep_tapless, int dx_elem, void *dx, const void *addend,
-                         hipStream_t st) {
+// class of its own when keep_tapless (a fused BatchNorm reduce: its tiles run the epilogue only); otherwise it is left
+// out of p.cls and listed in `dropped` (dgrad_classes fills it).  Host arithmetic only: nothing is launched, so the
+// families' plan queries (mvg_conv_dgrad_split_stages) build the same table.  p.ncls == 0 on return: no class has taps.
+struct DgradDropped {
+  int n;
+  struct { int py, px, sub_h, sub_w; } c[4];
+};
+static void dgrad_plan_classes(IgemmParams &p, const mvg_conv_desc *d, bool keep_tapless, DgradDropped &dropped) {
   const int step = d->stride;
   p.ncls = 0;
+  dropped.n = 0;
   for (int py = 0; py < step; ++py)
     for (int px = 0; px < step; ++px) {
       const int sub_h = (d->h - py + step - 1) / step, sub_w = (d->w - px + step - 1) / step;
@@ -417,15 +421,7 @@ static int dgrad_classes(IgemmParams &p, const mvg_conv_desc *d, bool keep_taple
       const int nr = r0 < d->r ? (d->r - r0 + step - 1) / step : 0;
       const int ns = s0 < d->s ? (d->s - s0 + step - 1) / step : 0;
       if (nr * ns == 0 && !keep_tapless) {
-        if (addend != dx || !addend) {
-          const int cv = d->cin * dx_elem / 16;
-          const long long n = (long long)d->groups * d->n * sub_h * sub_w * cv;
-          long long blocks = (n + 255) / 256;
-          if (blocks > 4096) blocks = 4096;
-          hipLaunchKernelGGL(dgrad_empty_class_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (uint4 *)dx, (const uint4 *)addend, n,
-                             sub_h, sub_w, d->h, d->w, cv, py, px);
-          if (check_launch("dgrad(empty class)")) return 1;
-        }
+        dropped.c[dropped.n++] = {py, px, sub_h, sub_w};
         continue;
       }
       IgemmClass &c = p.cls[p.ncls++];
@@ -450,6 +446,24 @@ static int dgrad_classes(IgemmParams &p, const mvg_conv_desc *d, bool keep_taple
       p.cls[j - 1] = t;
     }
   p.no_remap = p.ncls > 1;
+}
+
+// dgrad_plan_classes, and dgrad_empty_class_kernel over every dropped class: dx = addend there (nothing when the caller
+// accumulates in place; dx_elem bytes per element).  p.ncls == 0 on return: nothing left to launch.
+static int dgrad_classes(IgemmParams &p, const mvg_conv_desc *d, bool keep_tapless, int dx_elem, void *dx, const void *addend,
+                         hipStream_t st) {
+  DgradDropped dropped;
+  dgrad_plan_classes(p, d, keep_tapless, dropped);
+  if (addend == dx && addend) return 0;
+  for (int i = 0; i < dropped.n; ++i) {
+    const int cv = d->cin * dx_elem / 16;
+    const long long n = (long long)d->groups * d->n * dropped.c[i].sub_h * dropped.c[i].sub_w * cv;
+    long long blocks = (n + 255) / 256;
+    if (blocks > 4096) blocks = 4096;
+    hipLaunchKernelGGL(dgrad_empty_class_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (uint4 *)dx, (const uint4 *)addend, n,
+                       dropped.c[i].sub_h, dropped.c[i].sub_w, d->h, d->w, cv, dropped.c[i].py, dropped.c[i].px);
+    if (check_launch("dgrad(empty class)")) return 1;
+  }
   return 0;
 }
 

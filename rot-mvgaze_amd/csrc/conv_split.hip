@@ -989,9 +989,12 @@ static int validate_split(const mvg_conv_desc *d) {
 static int split_tile_rows(int ncols, int taps, long long rows) { return (ncols < 128 && taps > 1 && rows >= 65536) ? 256 : SP_BM; }
 
 // The tiling of an igemm_split16_kernel launch and the K loop it gets: a function of (columns, taps, rows of the whole map, groups,
-// each class's rows per group and K, lin) - launch_igemm_split launches by it, mvg_conv_fprop_split_stages answers from it.  Writes
-// every class's mtiles_per_group, KT and tile0.  (256-row tiles come with 64 columns and never with lin: by construction.)
+// each class's rows per group and K, lin) - launch_igemm_split launches by it, mvg_conv_fprop_split_stages and
+// mvg_conv_dgrad_split_stages answer from it.  Writes every class's mtiles_per_group, KT and tile0.  (256-row tiles come with 64
+// columns and never with lin: by construction.)
 struct SplitPlan { int bm, bn, kt_max; long long tiles; bool pipelined; };
+// K-loop stages of a conv's DMA-loader launch under a plan: the two-stage pipeline exists for 128 x 128 tiles only
+static int split_conv_stages(const SplitPlan &pl) { return (pl.pipelined && pl.bn == 128 && pl.bm == SP_BM) ? 2 : 1; }
 static SplitPlan split_plan(int ncols, int taps, long long rows, int groups, bool lin, IgemmClass *cls, int ncls) {
   SplitPlan pl;
   pl.bm = lin ? SP_BM : split_tile_rows(ncols, taps, rows);
@@ -1074,7 +1077,7 @@ static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin, int taps
     else if (pipelined) hipLaunchKernelGGL((igemm_split16_kernel<64, DGRAD, true, 2, 2>), grid, block, 0, st, p);
     else hipLaunchKernelGGL((igemm_split16_kernel<64, DGRAD, true>), grid, block, 0, st, p);
   } else if (bm == 256) hipLaunchKernelGGL((igemm_split16_kernel<64, DGRAD, false, 4>), grid, block, 0, st, p);
-  else if (bn == 128 && pipelined) hipLaunchKernelGGL((igemm_split16_kernel<128, DGRAD, false, 2, 2>), grid, block, 0, st, p);
+  else if (split_conv_stages(pl) == 2) hipLaunchKernelGGL((igemm_split16_kernel<128, DGRAD, false, 2, 2>), grid, block, 0, st, p);
   else if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, DGRAD>), grid, block, 0, st, p);
   else hipLaunchKernelGGL((igemm_split16_kernel<64, DGRAD>), grid, block, 0, st, p);
   return check_launch(DGRAD ? "conv_dgrad_split" : "conv_fprop_split");
@@ -1240,7 +1243,7 @@ int mvg_conv_fprop_split_stages(const mvg_conv_desc *d) {
   c.rows_per_group = (long long)d->n * d->ho * d->wo;
   c.ktotal = d->r * d->s * d->cin;
   const SplitPlan pl = split_plan(d->cout, d->r * d->s, c.rows_per_group, d->groups, false, &c, 1);
-  return (pl.pipelined && pl.bn == 128 && pl.bm == SP_BM) ? 2 : 1;         // launch_igemm_split's dispatch for a conv
+  return split_conv_stages(pl);
 }
 
 int mvg_conv_fprop_split_bnapply(const mvg_conv_desc *d, void *out_sp, const float *out_sinv, const float *bn_y, const float *scale,
@@ -1339,6 +1342,18 @@ int mvg_conv_dgrad_split(const mvg_conv_desc *d, const void *dy_sp, const float 
   return dgrad_split_impl(d, dy_sp, dy_sinv, w_crsk_sp, w_sinv, dx, addend, stream, nullptr, relu_mask_sp);
 }
 
+int mvg_conv_dgrad_split_stages(const mvg_conv_desc *d, int fused_reduce) {
+  // 1 / 2: the K loop launch_igemm_split picks for this backward-data (mvg_conv_dgrad_split; fused_reduce != 0:
+  // mvg_conv_dgrad_split_bnreduce, whose launch keeps the parity classes without taps); -1: bad descriptor.  Launches nothing.
+  if (validate_split(d)) return -1;
+  IgemmParams p;
+  memset(&p, 0, sizeof(p));
+  if (dgrad_geometry(p, d, SP_BYTES, SP_BYTES, "split conv")) return -1;
+  DgradDropped dropped;
+  dgrad_plan_classes(p, d, fused_reduce != 0, dropped);
+  return split_conv_stages(split_plan(p.ncols, d->r * d->s, (long long)d->n * d->h * d->w, p.groups, false, p.cls, p.ncls));
+}
+
 int mvg_conv_dgrad_bn_partials_split(const mvg_conv_desc *d) {
   if (validate_split(d)) return -1;
   return dgrad_bn_partials(d, split_tile_rows(d->cin, d->r * d->s, (long long)d->n * d->h * d->w));
@@ -1394,7 +1409,10 @@ int mvg_conv_dgrad_split_bnapply_bnreduce(const mvg_conv_desc *d, void *dy_sp, c
                                    bn_invstd, relu_scale, relu_shift, partials, s1, s2, dgamma, dbeta, accumulate, mx, bn_gamma, dx_dy_sinv, stream, &a);
 }
 
-static void wgrad_split_tile(const mvg_conv_desc *d, int &bm, int &bn) {
+// The tile of a weight-gradient launch and its pixel addressing (incr: wgrad_split_kernel's incremental form, at most one image
+// wrap per 16-pixel step): wgrad_split_impl dispatches by it, mvg_conv_wgrad_split_tile answers from it.
+static void wgrad_split_tile(const mvg_conv_desc *d, int &bm, int &bn, bool &incr) {
+  incr = (long long)d->ho * d->wo >= 32;
   const int ncols = d->r * d->s * d->cin;
   bm = d->cout >= 128 ? 128 : 64;
   bn = ncols >= 128 ? 128 : 64;
@@ -1411,11 +1429,23 @@ static void wgrad_split_tile(const mvg_conv_desc *d, int &bm, int &bn) {
 int mvg_conv_wgrad_splits_split(const mvg_conv_desc *d) {
   if (validate_split(d)) return -1;
   int bm, bn;
-  wgrad_split_tile(d, bm, bn);
+  bool incr;
+  wgrad_split_tile(d, bm, bn, incr);
   const long long tiles = (long long)ceil_div(d->cout, bm) * ceil_div(d->r * d->s * d->cin, bn);
   // one resident round: three workgroups per CU (128-column tiles; measured at C3: 2 / 3 / 4 / 6 per CU -> 17.8 / 16.8 / 16.7 /
   // 17.7 ms of wgrad per step), two with the 256-column tiles (2 / 3 / 4 / 6 -> 15.6 / 16.8 / 16.4 / 17.3 ms); 16 K-steps per split
   return wgrad_split_count(tiles, (long long)d->groups * d->n * d->ho * d->wo, bn == 256 ? 2 : 3, 256);
+}
+
+int mvg_conv_wgrad_split_tile(const mvg_conv_desc *d, int32_t *bm, int32_t *bn, int32_t *incremental) {
+  if (validate_split(d)) return -1;
+  int tm, tn;
+  bool incr;
+  wgrad_split_tile(d, tm, tn, incr);
+  if (bm) *bm = tm;
+  if (bn) *bn = tn;
+  if (incremental) *incremental = incr ? 1 : 0;
+  return 0;
 }
 
 static int wgrad_split_impl(const mvg_conv_desc *d, const void *x_sp, const void *dy_sp, const float *dy_sinv, float *dw, float *workspace,
@@ -1430,7 +1460,8 @@ static int wgrad_split_impl(const mvg_conv_desc *d, const void *x_sp, const void
   p.x_sinv = x_sinv;
   if (wgrad_geometry(p, d, SP_BYTES, 16, dw, nullptr, workspace, splits, accumulate, "wgrad_split", stride_w, pad_w)) return 2;
   int bm, bn;
-  wgrad_split_tile(d, bm, bn);
+  bool incr;
+  wgrad_split_tile(d, bm, bn, incr);
   p.mtiles = ceil_div(d->cout, bm);
   p.ntiles = ceil_div(p.ncols, bn);
   hipStream_t st = (hipStream_t)stream;
@@ -1442,7 +1473,6 @@ static int wgrad_split_impl(const mvg_conv_desc *d, const void *x_sp, const void
     ProfScope ps(lin ? MVG_K_LINEAR_WGRAD : MVG_K_CONV_WGRAD, st, flops, bytes);
     MVG_REQUIRE((long long)p.mtiles * p.ntiles * splits < (1LL << 31), "wgrad_split: grid too large");
     dim3 grid(p.mtiles * p.ntiles * splits), block(256);
-    const bool incr = (long long)d->ho * d->wo >= 32;        // at most one image wrap per 16-pixel step
 #define MVG_WGRAD_SPLIT(BM_, BN_)                                                                  \
   do {                                                                                             \
     if (incr) hipLaunchKernelGGL((wgrad_split_kernel<BM_, BN_, true>), grid, block, 0, st, p);     \

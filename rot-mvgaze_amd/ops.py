@@ -248,6 +248,23 @@ def conv_fprop_split_stages(d: ConvDesc) -> int:
     return n
 
 
+def conv_dgrad_split_stages(d: ConvDesc, fused_reduce: bool = False) -> int:
+    """1 / 2: the K loop conv_dgrad_split (fused_reduce: conv_dgrad_split_bnreduce, which keeps the parity classes without
+    taps) takes for ``d`` on this device.  Host arithmetic: nothing is launched."""
+    n = lib().mvg_conv_dgrad_split_stages(C.byref(d), int(fused_reduce))
+    if n < 0:
+        check(1, "conv_dgrad_split_stages")
+    return n
+
+
+def conv_wgrad_split_tile(d: ConvDesc):
+    """(bm, bn, incremental): the tile conv_wgrad_split runs ``d`` on and whether the kernel addresses pixels incrementally."""
+    bm, bn, incr = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if lib().mvg_conv_wgrad_split_tile(C.byref(d), C.byref(bm), C.byref(bn), C.byref(incr)) != 0:
+        check(1, "conv_wgrad_split_tile")
+    return bm.value, bn.value, bool(incr.value)
+
+
 def conv_fprop_split_bnapply(d: ConvDesc, out_sp: Tensor, bn_y, scale, shift, residual, w_sp: Tensor, y: Tensor,
                              stats: Optional[Tensor] = None, residual_affine=None, bits: Optional[Tensor] = None):
     """bn_apply_split (residual, ReLU) of the unit whose output ``out_sp`` is + conv_fprop_split of the 1x1 stride-1 conv (cout 64 /

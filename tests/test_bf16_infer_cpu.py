@@ -46,11 +46,11 @@ def test_affine_signature_mirrors_the_fp32_one():
     assert names(_header_args("mvg_preprocess_u8hwc_resize_bf16")) == names(_header_args("mvg_preprocess_u8hwc_resize"))
 
 
-def test_abi_version_stays_10(built_lib):
+def test_abi_version_in_header_binding_and_library_agree(built_lib):
     from rot_mvgaze_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+10\b", hdr)
-    assert _lib.ABI_VERSION == 10 == built_lib.mvg_abi_version()
+    assert re.search(r"#define\s+MVG_ABI_VERSION\s+11\b", hdr)
+    assert _lib.ABI_VERSION == 11 == built_lib.mvg_abi_version()
 
 
 def test_backbone_switch_and_debug_hook_defaults():
