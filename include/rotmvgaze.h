@@ -180,6 +180,12 @@ int mvg_bn_finalize(const float *stats, int groups, int partials, int rows_per_p
 int mvg_bn_eval_affine(int groups, int c, const float *gamma, const float *beta,
                        const float *running_mean, const float *running_var, float eps,
                        float *scale, float *shift, void *stream);
+/* Every BatchNorm of a network folded by ONE launch (the inference session's bind; 20 / 53 records for ResNet-18 / -50).
+ * items_dev: n records in DEVICE memory of
+ *   { const float *gamma, *beta, *running_mean, *running_var; float *scale, *shift; int32 c; int32 pad; }  (56 bytes);
+ * scale[c] / shift[c] of every record receive the bits mvg_bn_eval_affine(1, c, ...) leaves (one device function serves
+ * both kernels).  max_c: the widest record's channel count (it sizes the grid). */
+int mvg_bn_eval_affine_batch(const void *items_dev, int n, int max_c, float eps, void *stream);
 /* out = [relu]( y*scale[g] + shift[g] [+ residual] );  y,out,residual: [groups][rows][c].
  * res_scale/res_shift ([groups][c], both or neither): the residual is the RAW output of the block's
  * downsample conv and its BatchNorm (residual*res_scale + res_shift) is applied here, so the normalised
@@ -737,6 +743,65 @@ int mvg_linear_wgrad_split(int rows, int fin, int fout, const void *x_sp, const 
                            float *dw, float *workspace, int splits, int accumulate, void *stream);
 int mvg_split_colsum(const float *g, int rows, int cols, const float *absmax, void *out_sp, float *out_sinv, float *db, int accumulate,
                      void *stream);
+
+/* ---------------------------------------------------------------- inference session (no Python needed)
+ * An opaque handle, made for ONE (architecture, views, batch, height, width) shape, that queues the complete eval-mode
+ * forward of the fp32 model - input layout, backbone with BatchNorm folded into the conv epilogues (trainer.py:164-199
+ * under model.eval()), pools, lifter, fusion iterations, gaze heads (rot_mv.py:188-263) - from one call.  It calls the
+ * entry points above, in the order and with the arguments the Python module uses, so the results are bit-identical.
+ *
+ * Ownership: the caller owns the workspace, the model tensors, the inputs and the outputs; the session keeps pointers
+ * only.  mvg_session_forward allocates nothing, never synchronises and touches no host memory after its launches are
+ * queued.  The workspace holds the sp copies of the conv / Linear weights (KRSC only), the folded (scale, shift) of every
+ * BatchNorm, the pair / row index tables, the split head path's 64 scale slots, the activation arena (buffers share
+ * bytes when their live ranges do not intersect; create verifies that plan and fails if it is unsound) and a scratch
+ * region of mvg_scratch_bytes() that the launches of a forward use instead of the mvg_set_scratch registry.
+ *
+ * split: 1 = the kernels the fp32 module runs by default (split-operand convs unless a view's largest sp tensor would reach
+ * 2 GiB - decided from the cfg's real sizes -, split-operand fuser / head Linears from 1024 rows), 0 = the fp32-MFMA kernels
+ * everywhere (MVG_SPLIT=0).  raw_u8: the views are uint8 [batch][in_h][in_w][3] patches put through
+ * mvg_preprocess_u8hwc_resize (mean / std of main.py:38-39) instead of fp32 [batch][3][height][width] images.
+ * Not representable: the encode_rotmat and share_feature variants, the bf16 storage path, training. */
+typedef struct mvg_session mvg_session;
+typedef struct {
+  int32_t depth;          /* 18 | 50 */
+  int32_t num_iter;       /* >= 1 (reference: 3); at most 5 when the head runs on the split kernels */
+  int32_t views, batch;   /* 2 <= views <= 8, batch >= 1 */
+  int32_t height, width;  /* network input size, >= 32 */
+  int32_t share_weights, ignore_rotmat;
+  int32_t split;
+  int32_t raw_u8;
+  int32_t in_h, in_w, input_bgr;          /* raw_u8 only */
+} mvg_session_cfg;
+
+/* HOST ONLY (no HIP call: runs on a machine without a GPU): builds the layer table, the conv descriptors, the kernel-family
+ * decisions and the buffer plan, and checks the plan.  Non-zero + mvg_last_error() for a configuration outside the scope;
+ * *out is NULL then. */
+int mvg_session_create(const mvg_session_cfg *cfg, mvg_session **out);
+/* Frees the handle (host memory only; the workspace is the caller's).  NULL is allowed. */
+void mvg_session_destroy(mvg_session *s);
+/* The model tensors the session reads, by state_dict key, in the order mvg_session_bind takes their pointers: per conv
+ * weight (KRSC), BatchNorm weight, bias, running_mean, running_var; then the lifter, fuser and head Linears (weight, bias).
+ * With share_weights only iteration 0's fuser / head appear. */
+int mvg_session_num_tensors(const mvg_session *s);
+const char *mvg_session_tensor_name(const mvg_session *s, int i);
+int64_t mvg_session_tensor_numel(const mvg_session *s, int i);
+/* Bytes of the workspace mvg_session_bind wants (host only). */
+size_t mvg_session_workspace_bytes(const mvg_session *s);
+/* Library calls one mvg_session_forward queues (host only; a stream-K / split-K GEMM adds its fix-up kernel on the device). */
+int mvg_session_launches(const mvg_session *s);
+/* host_tensor_ptrs: a HOST array of mvg_session_num_tensors() device pointers (fp32, contiguous; conv weights KRSC).
+ * workspace: 256-byte aligned device memory of at least mvg_session_workspace_bytes().  Queues on `stream` the work that
+ * depends on the weights only: the index tables, the stem filter padded to 4 channels, every sp weight copy (two
+ * mvg_weights_prep_batch calls) and every BatchNorm fold (one mvg_bn_eval_affine_batch).  Call it again after the
+ * weights changed (same or new pointers).  Forwards must be ordered after it (same stream, or an event). */
+int mvg_session_bind(mvg_session *s, const void *const *host_tensor_ptrs, void *workspace, size_t bytes, void *stream);
+/* Queues one forward on `stream`: only the launches that depend on the input.  host_view_ptrs: a HOST array of `views`
+ * device pointers (fp32 NCHW images, or uint8 HWC patches with raw_u8); rot fp32 [batch][views][3][3].  Outputs (device,
+ * fp32, D = views (views - 1) directed pairs, I = num_iter, Cf = 512 | 2048): img_feat [views][batch][Cf], lifted
+ * [views][batch][3][512], feats [I][D][batch][3][512], preds [I][D][batch][2]. */
+int mvg_session_forward(mvg_session *s, const void *const *host_view_ptrs, const float *rot, float *img_feat, float *lifted,
+                        float *feats, float *preds, void *stream);
 
 #ifdef __cplusplus
 }

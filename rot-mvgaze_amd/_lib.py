@@ -34,6 +34,13 @@ class ProfEntry(C.Structure):
     _fields_ = [("launches", C.c_int64), ("ms", C.c_double), ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class SessionCfg(C.Structure):
+    """mvg_session_cfg (include/rotmvgaze.h)."""
+    _fields_ = [(n, C.c_int32) for n in
+                ("depth", "num_iter", "views", "batch", "height", "width", "share_weights", "ignore_rotmat", "split", "raw_u8",
+                 "in_h", "in_w", "input_bgr")]
+
+
 _P = C.c_void_p
 _I = C.c_int
 _I64 = C.c_int64
@@ -67,6 +74,7 @@ SIGNATURES = {
     "mvg_linear_dgrad": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P, C.c_size_t, _P]),
     "mvg_bn_finalize": (_I, [_P, _I, _I, _I, _I64, _I, _P, _P, _P, _P, _F, _F, _P, _P, _P, _P, _P]),
     "mvg_bn_eval_affine": (_I, [_I, _I, _P, _P, _P, _P, _F, _P, _P, _P]),
+    "mvg_bn_eval_affine_batch": (_I, [_P, _I, _I, _F, _P]),
     "mvg_bn_apply": (_I, [_P, _P, _P, _P, _P, _P, _I, _P, _I, _I64, _I, _P]),
     "mvg_bn_bwd_reduce": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _P, _P, _I, _P, _P, _P]),
     "mvg_split_f32": (_I, [_P, _P, _I64, _F, _P]),
@@ -190,6 +198,16 @@ SIGNATURES = {
     "mvg_preprocess_u8hwc_resize_bf16": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mvg_mt19937_seed": (_I, [_P, C.c_uint64]),
     "mvg_pair_index_build": (_I64, [_P, _P, _I, _I, _P, _I64]),
+    # inference session: one call queues the whole eval-mode forward (session.py)
+    "mvg_session_create": (_I, [C.POINTER(SessionCfg), C.POINTER(_P)]),
+    "mvg_session_destroy": (None, [_P]),
+    "mvg_session_num_tensors": (_I, [_P]),
+    "mvg_session_tensor_name": (C.c_char_p, [_P, _I]),
+    "mvg_session_tensor_numel": (_I64, [_P, _I]),
+    "mvg_session_workspace_bytes": (C.c_size_t, [_P]),
+    "mvg_session_launches": (_I, [_P]),
+    "mvg_session_bind": (_I, [_P, C.POINTER(_P), _P, C.c_size_t, _P]),
+    "mvg_session_forward": (_I, [_P, C.POINTER(_P), _P, _P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -36,7 +36,25 @@ struct Scratch {
 };
 static std::mutex g_scratch_mu;
 static Scratch g_scratch[32];
+// The inference session brings its own scratch region: while a ScratchScope is alive on this thread, launches on its stream
+// find that region and the registry below is neither read nor changed for them.
+static thread_local Scratch t_scope = {0, nullptr, nullptr, 0};
+ScratchScope::ScratchScope(hipStream_t st, float *ptr, size_t floats) {
+  prev_st = t_scope.st;
+  prev_ptr = t_scope.ptr;
+  prev_floats = t_scope.floats;
+  t_scope.st = st;
+  t_scope.ptr = ptr;
+  t_scope.floats = floats;
+}
+ScratchScope::~ScratchScope() {
+  t_scope.st = prev_st;
+  t_scope.ptr = prev_ptr;
+  t_scope.floats = prev_floats;
+}
+
 float *stream_scratch(hipStream_t st, size_t floats) {
+  if (t_scope.ptr && t_scope.st == st) return t_scope.floats >= floats ? t_scope.ptr : nullptr;
   std::lock_guard<std::mutex> lk(g_scratch_mu);
   int dev = 0;
   if (hipGetDevice(&dev) != hipSuccess) return nullptr;

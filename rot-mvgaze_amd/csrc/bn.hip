@@ -342,9 +342,21 @@ __global__ void bn_eval_affine_kernel(int groups, int c, const float *gamma, con
   const int i = blockIdx.x * blockDim.x + threadIdx.x;
   if (i >= groups * c) return;
   const int ch = i % c;
-  const float sc = gamma[ch] / sqrtf(rv[ch] + eps);
-  scale[i] = sc;
-  shift[i] = beta[ch] - rm[ch] * sc;
+  bn_eval_affine_ch(gamma[ch], beta[ch], rm[ch], rv[ch], eps, scale[i], shift[i]);
+}
+
+// Every BatchNorm of a network folded by ONE launch (the inference session's bind): blockIdx.y = the record, the x
+// dimension covers the widest record's channels.  One row per record: eval-mode (scale, shift) do not depend on the group.
+struct BnEvalItem {
+  const float *gamma, *beta, *rm, *rv;
+  float *scale, *shift;
+  int32_t c;
+  int32_t pad;
+};
+__global__ __launch_bounds__(256) void bn_eval_affine_batch_kernel(const BnEvalItem *__restrict__ items, float eps) {
+  const BnEvalItem it = items[blockIdx.y];
+  for (int ch = blockIdx.x * 256 + threadIdx.x; ch < it.c; ch += gridDim.x * 256)
+    bn_eval_affine_ch(it.gamma[ch], it.beta[ch], it.rm[ch], it.rv[ch], eps, it.scale[ch], it.shift[ch]);
 }
 
 // ---- apply: out = [relu](y*scale + shift [+ residual]) -------------------------------------
@@ -1363,6 +1375,18 @@ int mvg_bn_eval_affine(int groups, int c, const float *gamma, const float *beta,
   hipLaunchKernelGGL(bn_eval_affine_kernel, dim3(ceil_div((long long)groups * c, 256)), dim3(256), 0, st, groups, c, gamma,
                      beta, running_mean, running_var, eps, scale, shift);
   return check_launch("bn_eval_affine");
+}
+
+// items_dev: n records in DEVICE memory of { const float *gamma, *beta, *running_mean, *running_var; float *scale, *shift;
+// int32 c; int32 pad; } (56 bytes): scale[c], shift[c] of every record as mvg_bn_eval_affine(1, c, ...) leaves them.
+int mvg_bn_eval_affine_batch(const void *items_dev, int n, int max_c, float eps, void *stream) {
+  static_assert(sizeof(BnEvalItem) == 56, "BnEvalItem: the callers build 56-byte records");
+  MVG_REQUIRE(items_dev != nullptr && n >= 1 && n <= 65535 && max_c >= 1, "bn_eval_affine_batch: null table, or n / max_c out of range");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_BN_FINALIZE, st, 0.0, 4.0 * 6 * max_c * n);
+  hipLaunchKernelGGL(bn_eval_affine_batch_kernel, dim3((unsigned)ceil_div(max_c, 256), (unsigned)n), dim3(256), 0, st,
+                     (const BnEvalItem *)items_dev, eps);
+  return check_launch("bn_eval_affine_batch");
 }
 
 }  // extern "C" (templated implementations below)

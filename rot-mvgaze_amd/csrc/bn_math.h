@@ -14,6 +14,13 @@ __device__ __forceinline__ float bn_fwd(float y, float scale, float shift) { ret
 // The ReLU mask without the activation: out > 0 <=> bn_fwd(y, scale, shift) > 0 (no residual on that unit).
 __device__ __forceinline__ bool relu_on(float y, float scale, float shift) { return bn_fwd(y, scale, shift) > 0.f; }
 __device__ __forceinline__ float relu_mask(bool on, float d) { return on ? d : 0.f; }
+// Eval mode: one channel's (scale, shift) from the running statistics.  bn_eval_affine_kernel and its batched form
+// (bn_eval_affine_batch_kernel: every BatchNorm of a network in one launch) both call this, so they leave the same bits.
+__device__ __forceinline__ void bn_eval_affine_ch(float gamma, float beta, float rm, float rv, float eps, float &scale, float &shift) {
+  const float sc = gamma / sqrtf(rv + eps);
+  scale = sc;
+  shift = beta - rm * sc;
+}
 __device__ __forceinline__ float xhat(float y, float mean, float invstd) { return (y - mean) * invstd; }
 // dy = gamma invstd (dz - s1/n - x-hat s2/n).  The association is part of the definition: the build contracts
 // multiply-adds, and the shape of this expression decides which ones.

@@ -20,6 +20,19 @@ void prof_end(int family, hipStream_t s);
 // ordered by the stream, so every kernel sequence that finishes with its scratch before the next launch on that
 // stream may share it (stream-K pieces, bn_finalize slices).  The library allocates nothing.
 float *stream_scratch(hipStream_t st, size_t floats);
+// A caller-owned scratch region for the launches this thread queues on `st` while the object lives (session.hip: the
+// session's workspace holds one); stream_scratch answers from it instead of the mvg_set_scratch registry.
+struct ScratchScope {
+  ScratchScope(hipStream_t st, float *ptr, size_t floats);
+  ~ScratchScope();
+  ScratchScope(const ScratchScope &) = delete;
+  ScratchScope &operator=(const ScratchScope &) = delete;
+
+ private:
+  hipStream_t prev_st;
+  float *prev_ptr;
+  size_t prev_floats;
+};
 // device CUs minus mvg_set_reserved_cus(): what stream-K grids, wgrad splits and split-K plan for
 int compute_cus();
 

@@ -1,0 +1,738 @@
+// The inference session's plan builder and its host-only entry points (mvg_session_create / _destroy and the queries).
+// No HIP here, like pair_index.cpp: this file compiles and runs stand-alone (tests/native/session_plan_check.cpp).
+//
+// The plan restates, as data, what the Python module decides per call for model.eval() under torch.no_grad() on the fp32
+// path: arch.py's layer table, Backbone.forward's 2 GiB guard and unit order (backbone.py: conv1.., downsample, last conv with
+// the residual), FusionHead.forward's choice between the generated-input fp32-MFMA Linears and _forward_split (heads.py:
+// D * B >= 1024 rows).  Every step is one call of an existing entry point; session.hip executes them.
+#include <limits.h>
+#include <stdio.h>
+#include <string.h>
+
+#include <algorithm>
+#include <new>
+
+#include "session_plan.h"
+
+namespace {
+using namespace mvg;
+
+constexpr int NVEC = 512, ROT_DIM = 3 * NVEC, HEAD_HID = 512;
+constexpr int SPLIT_MIN_ROWS = 1024;             // heads.SPLIT_MIN_ROWS
+constexpr int64_t ALIGN = 256;
+
+struct ConvSpec {
+  std::string name, bn;
+  int cin, cout, k, stride, pad;
+};
+struct BlockSpec {
+  std::vector<ConvSpec> convs;
+  bool has_ds = false;
+  ConvSpec ds;
+};
+
+// arch.backbone_spec
+void backbone_spec(int depth, ConvSpec &stem, std::vector<BlockSpec> &blocks, int &fc_dim) {
+  const std::string pre = "_feat_extractor.0.";
+  const bool bottleneck = depth == 50;
+  const int counts18[4] = {2, 2, 2, 2}, counts50[4] = {3, 4, 6, 3}, planes_of[4] = {64, 128, 256, 512};
+  const int expansion = bottleneck ? 4 : 1;
+  stem = {pre + "conv1", pre + "bn1", 3, 64, 7, 2, 3};
+  fc_dim = 512 * expansion;
+  int inplanes = 64;
+  for (int li = 1; li <= 4; ++li) {
+    const int planes = planes_of[li - 1], nblk = bottleneck ? counts50[li - 1] : counts18[li - 1];
+    for (int bi = 0; bi < nblk; ++bi) {
+      const int stride = (bi == 0 && li > 1) ? 2 : 1, outplanes = planes * expansion;
+      const std::string p = pre + "layer" + std::to_string(li) + "." + std::to_string(bi) + ".";
+      BlockSpec b;
+      if (bottleneck) {
+        b.convs.push_back({p + "conv1", p + "bn1", inplanes, planes, 1, 1, 0});
+        b.convs.push_back({p + "conv2", p + "bn2", planes, planes, 3, stride, 1});
+        b.convs.push_back({p + "conv3", p + "bn3", planes, outplanes, 1, 1, 0});
+      } else {
+        b.convs.push_back({p + "conv1", p + "bn1", inplanes, planes, 3, stride, 1});
+        b.convs.push_back({p + "conv2", p + "bn2", planes, planes, 3, 1, 1});
+      }
+      if (stride != 1 || inplanes != outplanes) {
+        b.has_ds = true;
+        b.ds = {p + "downsample.0", p + "downsample.1", inplanes, outplanes, 1, stride, 0};
+      }
+      blocks.push_back(b);
+      inplanes = outplanes;
+    }
+  }
+}
+
+mvg_conv_desc make_desc(int groups, int n, int h, int w, int cin, int cout, int k, int stride, int pad) {
+  mvg_conv_desc d;
+  d.groups = groups;
+  d.n = n;
+  d.h = h;
+  d.w = w;
+  d.cin = cin;
+  d.cout = cout;
+  d.r = d.s = k;
+  d.stride = stride;
+  d.pad = pad;
+  d.ho = (h + 2 * pad - k) / stride + 1;
+  d.wo = (w + 2 * pad - k) / stride + 1;
+  return d;
+}
+
+int64_t align_up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
+
+struct Act {               // an activation of the backbone: a buffer holding [V][B][h][w][c], 4 bytes per element in fp32 and in sp
+  int buf = -1;
+  bool sp = false;
+  int h = 0, w = 0, c = 0;
+};
+
+struct Builder {
+  SessionPlan &p;
+  explicit Builder(SessionPlan &plan) : p(plan) {}
+
+  int new_buf(int64_t bytes, const char *what, bool persistent = false) {
+    SBuf b;
+    b.bytes = bytes;
+    b.what = what;
+    b.first = persistent ? -1 : INT32_MAX;
+    b.last = persistent ? INT32_MAX : -1;
+    p.bufs.push_back(b);
+    return (int)p.bufs.size() - 1;
+  }
+  // a reference from the step being built (its index = steps.size()): extends the buffer's live range to it
+  SRef buf(int id, int64_t off = 0) {
+    SBuf &b = p.bufs[id];
+    if (b.first != -1) {
+      const int s = (int)p.steps.size();
+      b.first = std::min(b.first, s);
+      b.last = std::max(b.last, s);
+    }
+    SRef r;
+    r.space = SR_BUF;
+    r.idx = id;
+    r.off = off;
+    return r;
+  }
+  static SRef ref(int space, int idx = 0, int64_t off = 0) {
+    SRef r;
+    r.space = space;
+    r.idx = idx;
+    r.off = off;
+    return r;
+  }
+  static SRef tensor(int idx) { return ref(SR_TENSOR, idx); }
+  int add_tensor(const std::string &name, int64_t numel) {
+    STensor t;
+    t.name = name;
+    t.numel = numel;
+    p.tensors.push_back(t);
+    return (int)p.tensors.size() - 1;
+  }
+  void push(const SStep &s) { p.steps.push_back(s); }
+};
+
+// Offsets for every buffer: in order of first use, each at the lowest offset where it overlaps no placed buffer whose live
+// range intersects its own (persistent buffers come first and so sit at the bottom).
+void allocate(SessionPlan &p) {
+  std::vector<int> order;
+  for (int i = 0; i < (int)p.bufs.size(); ++i) {
+    if (p.bufs[i].first != -1 && p.bufs[i].last < 0) {      // planned but never referenced
+      p.bufs[i].bytes = 0;
+      p.bufs[i].first = p.bufs[i].last = 0;
+    }
+    order.push_back(i);
+  }
+  std::stable_sort(order.begin(), order.end(), [&](int a, int b) { return p.bufs[a].first < p.bufs[b].first; });
+  std::vector<int> placed;
+  int64_t top = 0;
+  for (int id : order) {
+    SBuf &b = p.bufs[id];
+    const int64_t need = align_up(b.bytes);
+    std::vector<std::pair<int64_t, int64_t>> busy;
+    for (int q : placed) {
+      const SBuf &o = p.bufs[q];
+      if (o.bytes > 0 && std::max(o.first, b.first) <= std::min(o.last, b.last)) busy.push_back({o.off, o.off + align_up(o.bytes)});
+    }
+    std::sort(busy.begin(), busy.end());
+    int64_t at = 0;
+    for (const auto &iv : busy) {
+      if (at + need <= iv.first) break;
+      at = std::max(at, iv.second);
+    }
+    b.off = at;
+    top = std::max(top, at + need);
+    placed.push_back(id);
+  }
+  p.workspace_bytes = top;
+}
+
+// The guard against a stray pointer: no two buffers that are live together may share a byte, and every range ends inside the
+// workspace.  Runs on every create.
+bool self_check(const SessionPlan &p, char *why, size_t n) {
+  const int nb = (int)p.bufs.size();
+  for (int i = 0; i < nb; ++i) {
+    const SBuf &a = p.bufs[i];
+    if (a.off < 0 || a.off % ALIGN != 0 || a.bytes < 0 || a.off + a.bytes > p.workspace_bytes) {
+      snprintf(why, n, "buffer %d (%s) [%lld, +%lld) leaves the workspace of %lld bytes", i, a.what, (long long)a.off,
+               (long long)a.bytes, (long long)p.workspace_bytes);
+      return false;
+    }
+    if (a.bytes == 0) continue;
+    for (int j = i + 1; j < nb; ++j) {
+      const SBuf &b = p.bufs[j];
+      if (b.bytes == 0 || std::max(a.first, b.first) > std::min(a.last, b.last)) continue;
+      if (a.off < b.off + b.bytes && b.off < a.off + a.bytes) {
+        snprintf(why, n, "buffers %d (%s) and %d (%s) are live together and overlap", i, a.what, j, b.what);
+        return false;
+      }
+    }
+  }
+  // every reference of every step stays inside its buffer and is live at that step
+  for (int s = 0; s < (int)p.steps.size(); ++s)
+    for (const SRef &r : p.steps[s].r) {
+      if (r.space != SR_BUF) continue;
+      if (r.idx < 0 || r.idx >= nb) {
+        snprintf(why, n, "step %d names buffer %d of %d", s, r.idx, nb);
+        return false;
+      }
+      const SBuf &b = p.bufs[r.idx];
+      if (r.off < 0 || r.off >= std::max<int64_t>(b.bytes, 1) || s < b.first || s > b.last) {
+        snprintf(why, n, "step %d reads buffer %d (%s) outside its bytes or its live range", s, r.idx, b.what);
+        return false;
+      }
+    }
+  return true;
+}
+
+int build(const mvg_session_cfg &c, SessionPlan &p) {
+  Builder B(p);
+  const int V = c.views, N = c.batch, H = c.height, W = c.width, I = c.num_iter;
+  ConvSpec stem;
+  std::vector<BlockSpec> blocks;
+  int cf = 0;
+  backbone_spec(c.depth, stem, blocks, cf);
+  p.fc_dim = cf;
+
+  // Backbone.forward: one view of the largest sp tensor (layer1's output) is addressed with 32-bit offsets
+  const int64_t biggest_view = (int64_t)N * ((H + 3) / 4) * ((W + 3) / 4) * blocks[0].convs.back().cout;
+  p.split_now = (c.split != 0 && 4 * biggest_view < 0x7FFFFFF0LL) ? 1 : 0;
+  const int D = V * (V - 1), rows = D * N;
+  p.dirs = D;
+  p.head_rows = rows;
+  p.head_split = (c.split != 0 && rows >= SPLIT_MIN_ROWS) ? 1 : 0;      // model.run_views: head.split = backbone.split
+  if (p.head_split && !(2 + I <= 8 && 11 * I + 2 <= SESSION_SLOTS)) {
+    set_error("session_create: num_iter %d is more than the split head path's slot arena serves (at most 5)", I);
+    return 2;
+  }
+
+  // ---- tensors, in state_dict order
+  struct ConvT {
+    ConvSpec s;
+    int t = 0, fold = -1, wprep = -1;
+  };
+  std::vector<ConvT> convs;
+  int64_t aff_bytes = 0, wk_bytes = 0;
+  auto add_conv = [&](const ConvSpec &s) {
+    ConvT ct;
+    ct.s = s;
+    ct.t = B.add_tensor(s.name + ".weight", (int64_t)s.cout * s.cin * s.k * s.k);
+    B.add_tensor(s.bn + ".weight", s.cout);
+    B.add_tensor(s.bn + ".bias", s.cout);
+    B.add_tensor(s.bn + ".running_mean", s.cout);
+    B.add_tensor(s.bn + ".running_var", s.cout);
+    SBnFold f;
+    f.gamma = ct.t + 1;
+    f.c = s.cout;
+    f.aff_off = aff_bytes;
+    aff_bytes += align_up(2LL * s.cout * 4);
+    p.max_c = std::max(p.max_c, s.cout);
+    ct.fold = (int)p.folds.size();
+    p.folds.push_back(f);
+    if (p.split_now && s.cin != 3) {
+      SWPrep w;
+      w.tensor = ct.t;
+      w.cout = s.cout;
+      w.rs = s.k * s.k;
+      w.cin = s.cin;
+      w.wk_off = wk_bytes;
+      wk_bytes += align_up((int64_t)s.cout * s.k * s.k * s.cin * 4);
+      ct.wprep = (int)p.wprep_backbone.size();
+      p.wprep_backbone.push_back(w);
+    }
+    convs.push_back(ct);
+    return (int)convs.size() - 1;
+  };
+  const int ci_stem = add_conv(stem);
+  std::vector<std::vector<int>> blk_convs(blocks.size());
+  std::vector<int> blk_ds(blocks.size(), -1);
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    for (const ConvSpec &s : blocks[b].convs) blk_convs[b].push_back(add_conv(s));
+    if (blocks[b].has_ds) blk_ds[b] = add_conv(blocks[b].ds);
+  }
+  p.stem_weight = convs[ci_stem].t;
+  p.stem_cout = stem.cout;
+  struct Lin {
+    int w = 0, b = 0, fin = 0, fout = 0, wprep = -1;
+  };
+  auto add_lin = [&](const std::string &name, int fin, int fout) {
+    Lin l;
+    l.fin = fin;
+    l.fout = fout;
+    l.w = B.add_tensor(name + ".weight", (int64_t)fout * fin);
+    l.b = B.add_tensor(name + ".bias", fout);
+    return l;
+  };
+  const int kin = cf + ROT_DIM;                   // arch.head_dims, default / ignore_rotmat variants: ImageFeatFuser
+  Lin lift0 = add_lin("_lifter._lifter.blocks.0.0", cf, ROT_DIM), lift1 = add_lin("_lifter._lifter.blocks.1.0", ROT_DIM, ROT_DIM);
+  const int nmod = c.share_weights ? 1 : I;
+  std::vector<Lin> fu0(nmod), fu1(nmod), hd0(nmod), hd1(nmod);
+  for (int i = 0; i < nmod; ++i) {
+    const std::string pre = "_img_fusers." + std::to_string(i) + "._fuser.blocks.";
+    fu0[i] = add_lin(pre + "0.0", kin, kin);
+    fu1[i] = add_lin(pre + "1.0", kin, ROT_DIM);
+  }
+  for (int i = 0; i < nmod; ++i) {
+    const std::string pre = "_gaze_estimators." + std::to_string(i) + ".blocks.";
+    hd0[i] = add_lin(pre + "0.0", kin, HEAD_HID);
+    hd1[i] = add_lin(pre + "1.0", HEAD_HID, 2);
+  }
+  if (p.head_split) {
+    // FusionHead._prepare_split_weights: heads and fusers from the last iteration down, every layer with fin, fout % 32 == 0
+    auto prep = [&](Lin &l) {
+      SWPrep w;
+      w.tensor = l.w;
+      w.cout = l.fout;
+      w.rs = 1;
+      w.cin = l.fin;
+      w.wk_off = wk_bytes;
+      wk_bytes += align_up((int64_t)l.fout * l.fin * 4);
+      l.wprep = (int)p.wprep_head.size();
+      p.wprep_head.push_back(w);
+    };
+    for (int i = nmod - 1; i >= 0; --i) {
+      prep(hd0[i]);
+      prep(fu0[i]);
+      prep(fu1[i]);
+    }
+  }
+  for (size_t k = 0; k < p.wprep_backbone.size(); ++k) p.wprep_backbone[k].stat = (int)k;
+  for (size_t k = 0; k < p.wprep_head.size(); ++k) p.wprep_head[k].stat = (int)(p.wprep_backbone.size() + k);
+  const int nstat = (int)(p.wprep_backbone.size() + p.wprep_head.size());
+
+  // ---- persistent buffers (bind writes them)
+  p.tab_folds = 0;
+  p.tab_wprep_backbone = align_up((int64_t)p.folds.size() * 56);
+  p.tab_wprep_head = p.tab_wprep_backbone + align_up((int64_t)p.wprep_backbone.size() * 48);
+  p.tab_bytes = p.tab_wprep_head + align_up((int64_t)p.wprep_head.size() * 48);
+  p.buf_tables = B.new_buf(p.tab_bytes, "record tables", true);
+  const int64_t rt = align_up((int64_t)rows * 4), dt = align_up((int64_t)D * 4);
+  p.rows_vi = 0;
+  p.rows_vj = dt;
+  p.rows_img = 2 * dt;
+  p.rows_view = 2 * dt + rt;
+  p.rows_partner = 2 * dt + 2 * rt;
+  p.rows_ident = 2 * dt + 3 * rt;
+  p.buf_rows = B.new_buf(2 * dt + 4 * rt, "pair / row tables", true);
+  p.buf_affine = B.new_buf(aff_bytes, "folded BatchNorm (scale, shift)", true);
+  p.buf_wstat = B.new_buf(std::max(nstat, 1) * 8LL, "weight copy scales", true);
+  p.buf_wk = B.new_buf(wk_bytes, "sp weight copies (KRSC)", true);
+  p.buf_w4 = B.new_buf((int64_t)stem.cout * stem.k * stem.k * 4 * 4, "stem filter, 4 channels", true);
+  p.buf_slots = B.new_buf(SESSION_SLOTS * 4, "head scale slots", true);
+  p.buf_scratch = B.new_buf((int64_t)SESSION_SCRATCH_BYTES, "scratch", true);
+
+  auto scale_of = [&](int ci) { return B.ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].aff_off); };
+  auto shift_of = [&](int ci) { return B.ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].aff_off + 4LL * convs[ci].s.cout); };
+  auto wk_of = [&](const SWPrep &w) { return B.ref(SR_BUF, p.buf_wk, w.wk_off); };
+  auto sinv_of = [&](const SWPrep &w) { return B.ref(SR_BUF, p.buf_wstat, 8LL * w.stat + 4); };
+  auto act_bytes = [&](int h, int w, int ch) { return (int64_t)V * N * h * w * ch * 4; };
+
+  // ---- input layout: V launches into x0 [V][B][H][W][4]
+  const int x0 = B.new_buf(act_bytes(H, W, 4), "input NHWC4");
+  for (int v = 0; v < V; ++v) {
+    SStep s;
+    s.op = c.raw_u8 ? SOP_PREPROCESS_U8 : SOP_NCHW_TO_NHWC4;
+    s.r[0] = B.ref(SR_VIEW, v);
+    s.r[1] = B.buf(x0, (int64_t)v * N * H * W * 4 * 4);
+    if (c.raw_u8) {
+      s.i[0] = N; s.i[1] = c.in_h; s.i[2] = c.in_w; s.i[3] = H; s.i[4] = W; s.i[5] = c.input_bgr ? 1 : 0;
+    } else {
+      s.i[0] = N; s.i[1] = 3; s.i[2] = H; s.i[3] = W;
+    }
+    B.push(s);
+  }
+
+  // ---- stem: fp32-MFMA kernel on the 4-channel image (also on the split path), plain max pool, split of the pooled map
+  const mvg_conv_desc dstem = make_desc(V, N, H, W, 4, stem.cout, stem.k, stem.stride, stem.pad);
+  if (dstem.ho < 1 || dstem.wo < 1) {
+    set_error("session_create: %d x %d is too small for the stem", H, W);
+    return 2;
+  }
+  const int ystem = B.new_buf(act_bytes(dstem.ho, dstem.wo, stem.cout), "stem output");
+  {
+    SStep s;
+    s.op = SOP_CONV_AFFINE;
+    s.d = dstem;
+    s.r[0] = B.buf(x0);
+    s.r[1] = B.ref(SR_BUF, p.buf_w4);
+    s.r[2] = B.buf(ystem);
+    s.r[3] = scale_of(ci_stem);
+    s.r[4] = shift_of(ci_stem);
+    s.i[0] = 1;
+    B.push(s);
+  }
+  const int hp = (dstem.ho + 2 - 3) / 2 + 1, wp = (dstem.wo + 2 - 3) / 2 + 1;
+  Act x;
+  x.h = hp;
+  x.w = wp;
+  x.c = stem.cout;
+  {
+    const int pooled = B.new_buf(act_bytes(hp, wp, stem.cout), "pooled map");
+    const int argmax = B.new_buf((int64_t)V * N * hp * wp * stem.cout, "pool argmax");
+    SStep s;
+    s.op = SOP_MAXPOOL;
+    s.r[0] = B.buf(ystem);
+    s.r[1] = B.buf(pooled);
+    s.r[2] = B.buf(argmax);
+    s.i[0] = V * N; s.i[1] = dstem.ho; s.i[2] = dstem.wo; s.i[3] = stem.cout; s.i[4] = hp; s.i[5] = wp;
+    B.push(s);
+    x.buf = pooled;
+    if (p.split_now) {
+      const int pooled_sp = B.new_buf(act_bytes(hp, wp, stem.cout), "pooled map (sp)");
+      SStep t;
+      t.op = SOP_SPLIT_F32;
+      t.r[0] = B.buf(pooled);
+      t.r[1] = B.buf(pooled_sp);
+      t.n = (int64_t)V * N * hp * wp * stem.cout;
+      B.push(t);
+      x.buf = pooled_sp;
+      x.sp = true;
+    }
+  }
+
+  // ---- residual blocks.  unit(): conv + folded BatchNorm (+ residual) (+ ReLU) in one launch
+  bool bad_size = false;
+  auto unit = [&](int ci, const Act &in, bool relu, const Act *residual) {
+    const ConvSpec &cs = convs[ci].s;
+    const mvg_conv_desc d = make_desc(V, N, in.h, in.w, cs.cin, cs.cout, cs.k, cs.stride, cs.pad);
+    if (d.ho < 1 || d.wo < 1) bad_size = true;
+    Act out;
+    out.h = std::max(d.ho, 1);
+    out.w = std::max(d.wo, 1);
+    out.c = cs.cout;
+    out.buf = B.new_buf(act_bytes(out.h, out.w, out.c), "unit output");
+    SStep s;
+    s.d = d;
+    if (p.split_now) {
+      // the epilogue writes the next conv's sp operand; the downsample branch (no ReLU), read only as a residual, stays fp32
+      const SWPrep &w = p.wprep_backbone[convs[ci].wprep];
+      out.sp = relu;
+      s.op = SOP_CONV_SPLIT_AFFINE;
+      s.r[0] = B.buf(in.buf);
+      s.r[1] = wk_of(w);
+      s.r[2] = sinv_of(w);
+      s.r[3] = B.buf(out.buf);
+      s.r[4] = scale_of(ci);
+      s.r[5] = shift_of(ci);
+      if (residual) s.r[6] = B.buf(residual->buf);
+      s.i[0] = out.sp ? 1 : 0;
+      s.i[1] = (residual && residual->sp) ? 1 : 0;
+      s.i[2] = relu ? 1 : 0;
+    } else {
+      s.op = SOP_CONV_AFFINE;
+      s.r[0] = B.buf(in.buf);
+      s.r[1] = B.tensor(convs[ci].t);
+      s.r[2] = B.buf(out.buf);
+      s.r[3] = scale_of(ci);
+      s.r[4] = shift_of(ci);
+      if (residual) s.r[5] = B.buf(residual->buf);
+      s.i[0] = relu ? 1 : 0;
+    }
+    B.push(s);
+    return out;
+  };
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    Act identity = x, out = x;
+    const std::vector<int> &cv = blk_convs[b];
+    for (size_t k = 0; k + 1 < cv.size(); ++k) out = unit(cv[k], out, true, nullptr);
+    if (blk_ds[b] >= 0) identity = unit(blk_ds[b], x, false, nullptr);
+    x = unit(cv.back(), out, true, &identity);
+  }
+  if (bad_size) {
+    set_error("session_create: %d x %d is too small for ResNet-%d (a layer's map would be empty)", H, W, c.depth);
+    return 2;
+  }
+  {
+    SStep s;
+    s.op = x.sp ? SOP_AVGPOOL_SPLIT : SOP_AVGPOOL;
+    s.r[0] = B.buf(x.buf);
+    s.r[1] = B.ref(SR_IMG_FEAT);
+    s.i[0] = V * N; s.i[1] = x.h * x.w; s.i[2] = cf;
+    B.push(s);
+  }
+
+  // ---- lifter, relative rotations (both head paths)
+  int64_t lin_ws_floats = 0;
+  auto lin_ws = [&](int r, int fin, int fout) {       // mvg_linear_workspace_floats (session_bind verifies the match)
+    const int64_t n = 16LL * r * std::max(fin, fout);
+    lin_ws_floats = std::max(lin_ws_floats, n);
+    return n;
+  };
+  lin_ws(V * N, cf, ROT_DIM);
+  lin_ws(V * N, ROT_DIM, ROT_DIM);
+  if (!p.head_split) {
+    lin_ws(rows, kin, kin);
+    lin_ws(rows, kin, ROT_DIM);
+    lin_ws(rows, kin, HEAD_HID);
+  }
+  const int ws = B.new_buf(lin_ws_floats * 4, "Linear split-K workspace");
+  auto linear = [&](const SRef &xin, const Lin &l, bool relu, const SRef &y, int r) {
+    SStep s;
+    s.op = SOP_LINEAR;
+    s.r[0] = xin;
+    s.r[1] = B.tensor(l.w);
+    s.r[2] = B.tensor(l.b);
+    s.r[3] = y;
+    s.r[4] = B.buf(ws);
+    s.i[0] = relu ? 1 : 0; s.i[1] = r; s.i[2] = l.fin; s.i[3] = l.fout;
+    s.n = lin_ws(r, l.fin, l.fout);
+    B.push(s);
+  };
+  const int hl = B.new_buf((int64_t)V * N * ROT_DIM * 4, "lifter hidden");
+  linear(B.ref(SR_IMG_FEAT), lift0, true, B.buf(hl), V * N);
+  linear(B.buf(hl), lift1, false, B.ref(SR_LIFTED), V * N);
+  const int rel = B.new_buf((int64_t)rows * 9 * 4, "relative rotations");
+  {
+    SStep s;
+    s.op = SOP_RELROT;
+    s.r[0] = B.ref(SR_ROT);
+    s.r[1] = B.ref(SR_BUF, p.buf_rows, p.rows_vi);
+    s.r[2] = B.ref(SR_BUF, p.buf_rows, p.rows_vj);
+    s.r[3] = B.buf(rel);
+    s.i[0] = N; s.i[1] = V; s.i[2] = D;
+    B.push(s);
+  }
+  const SRef t_img = B.ref(SR_BUF, p.buf_rows, p.rows_img), t_view = B.ref(SR_BUF, p.buf_rows, p.rows_view),
+             t_partner = B.ref(SR_BUF, p.buf_rows, p.rows_partner), t_ident = B.ref(SR_BUF, p.buf_rows, p.rows_ident);
+  const int64_t feat_it = (int64_t)rows * ROT_DIM * 4, pred_it = (int64_t)rows * 2 * 4;
+  auto skinny = [&](const SRef &xin, const Lin &l, int it) {
+    SStep s;
+    s.op = SOP_SKINNY;
+    s.r[0] = xin;
+    s.r[1] = B.tensor(l.w);
+    s.r[2] = B.tensor(l.b);
+    s.r[3] = B.ref(SR_PREDS, 0, it * pred_it);
+    s.i[0] = rows; s.i[1] = HEAD_HID; s.i[2] = 2;
+    B.push(s);
+  };
+
+  if (!p.head_split) {
+    // FusionHead.forward, fused_in: [img_feat | R @ F] is generated inside the first Linear's operand loader
+    auto fuser = [&](const SRef &feat, int feat_rows, bool rotate, const SRef &row_src, const Lin &l, const SRef &y) {
+      SStep s;
+      s.op = SOP_FUSER;
+      s.r[0] = B.ref(SR_IMG_FEAT);
+      s.r[1] = feat;
+      if (rotate) s.r[2] = B.buf(rel);
+      s.r[3] = t_img;
+      s.r[4] = row_src;
+      s.r[5] = B.tensor(l.w);
+      s.r[6] = B.tensor(l.b);
+      s.r[7] = y;
+      s.r[8] = B.buf(ws);
+      s.i[0] = 1; s.i[1] = rows; s.i[2] = cf; s.i[3] = l.fout; s.i[4] = V * N; s.i[5] = feat_rows;
+      s.n = lin_ws(rows, cf + ROT_DIM, l.fout);
+      B.push(s);
+    };
+    for (int it = 0; it < I; ++it) {
+      const int m = c.share_weights ? 0 : it;
+      const int hf = B.new_buf((int64_t)rows * kin * 4, "fuser hidden"), hh = B.new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
+      const SRef src = it == 0 ? B.ref(SR_LIFTED) : B.ref(SR_FEATS, 0, (it - 1) * feat_it);
+      fuser(src, it == 0 ? V * N : rows, !c.ignore_rotmat, it == 0 ? t_view : t_partner, fu0[m], B.buf(hf));
+      linear(B.buf(hf), fu1[m], false, B.ref(SR_FEATS, 0, it * feat_it), rows);
+      fuser(B.ref(SR_FEATS, 0, it * feat_it), rows, false, t_ident, hd0[m], B.buf(hh));
+      skinny(B.buf(hh), hd1[m], it);
+    }
+  } else {
+    // FusionHead._forward_split: every operand of a split Linear with its own power-of-two scale, found without extra passes
+    int nslot = 0;
+    auto slot = [&]() { return B.ref(SR_BUF, p.buf_slots, 4LL * nslot++); };
+    const SRef am_img = slot(), am_lift = slot();
+    std::vector<SRef> bam(I), am_f(I);
+    for (int it = 0; it < I; ++it) bam[it] = slot();
+    for (int it = 0; it < I; ++it) am_f[it] = slot();
+    {
+      SStep s;                               // abs-max slots start at zero, every forward
+      s.op = SOP_CLEAR;
+      s.r[0] = B.ref(SR_BUF, p.buf_slots);
+      s.n = SESSION_SLOTS * 4;
+      B.push(s);
+    }
+    {
+      SStep s;
+      s.op = SOP_ABSMAX;
+      s.i[0] = 2 + I;
+      s.r[0] = B.ref(SR_IMG_FEAT);
+      s.cnt[0] = (int64_t)V * N * cf;
+      s.r[8] = am_img;
+      s.r[1] = B.ref(SR_LIFTED);
+      s.cnt[1] = (int64_t)V * N * ROT_DIM;
+      s.r[9] = am_lift;
+      for (int it = 0; it < I; ++it) {
+        s.r[2 + it] = B.tensor(fu0[c.share_weights ? 0 : it].b);
+        s.cnt[2 + it] = kin;
+        s.r[10 + it] = bam[it];
+      }
+      B.push(s);
+    }
+    auto build_inputs = [&](const SRef &feat, const SRef &am_feat, const SRef &row_src_f, int xf, const SRef &xf_sinv, int xh,
+                            const SRef &xh_sinv) {
+      SStep s;
+      s.op = SOP_FUSE_BUILD;
+      s.r[0] = B.ref(SR_IMG_FEAT);
+      s.r[1] = feat;
+      if (!c.ignore_rotmat) s.r[2] = B.buf(rel);
+      s.r[3] = t_img;
+      s.r[4] = row_src_f;
+      if (xh >= 0) s.r[5] = t_ident;
+      if (xf >= 0) {
+        s.r[6] = B.buf(xf);
+        s.r[10] = xf_sinv;
+      }
+      if (xh >= 0) {
+        s.r[7] = B.buf(xh);
+        s.r[11] = xh_sinv;
+      }
+      s.r[8] = am_img;
+      s.r[9] = am_feat;
+      s.i[0] = rows; s.i[1] = cf;
+      B.push(s);
+    };
+    auto linear_split = [&](int xin, const SRef &x_sinv, const Lin &l, bool relu, const SRef &out, bool out_sp, const SRef &out_sinv,
+                            const SRef &bias_absmax, const SRef &out_absmax) {
+      const SWPrep &w = p.wprep_head[l.wprep];
+      SStep s;
+      s.op = SOP_LINEAR_SPLIT;
+      s.r[0] = B.buf(xin);
+      s.r[1] = x_sinv;
+      s.r[2] = wk_of(w);
+      s.r[3] = sinv_of(w);
+      s.r[4] = B.tensor(l.b);
+      s.r[5] = out;
+      s.r[6] = out_sinv;
+      s.r[7] = bias_absmax;
+      s.r[8] = out_absmax;
+      s.i[0] = rows; s.i[1] = l.fin; s.i[2] = l.fout; s.i[3] = relu ? 1 : 0; s.i[4] = out_sp ? 1 : 0;
+      B.push(s);
+    };
+    const SRef none;
+    const int64_t xbytes = (int64_t)rows * kin * 4;
+    int xf = B.new_buf(xbytes, "fuser input (sp)");
+    SRef xf_sinv = slot();
+    build_inputs(B.ref(SR_LIFTED), am_lift, t_view, xf, xf_sinv, -1, none);
+    for (int it = 0; it < I; ++it) {
+      const int m = c.share_weights ? 0 : it;
+      const int h = B.new_buf(xbytes, "fuser hidden (sp)");
+      const SRef h_sinv = slot();
+      linear_split(xf, xf_sinv, fu0[m], true, B.buf(h), true, h_sinv, bam[it], none);
+      linear_split(h, h_sinv, fu1[m], false, B.ref(SR_FEATS, 0, it * feat_it), false, none, none, am_f[it]);
+      const int xh = B.new_buf(xbytes, "head input (sp)");
+      const SRef xh_sinv = slot();
+      int xf_next = -1;
+      SRef xf_next_sinv;
+      if (it + 1 < I) {
+        xf_next = B.new_buf(xbytes, "fuser input (sp)");
+        xf_next_sinv = slot();
+      }
+      build_inputs(B.ref(SR_FEATS, 0, it * feat_it), am_f[it], t_partner, xf_next, xf_next_sinv, xh, xh_sinv);
+      const int hh = B.new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
+      linear_split(xh, xh_sinv, hd0[m], true, B.buf(hh), false, none, none, none);
+      skinny(B.buf(hh), hd1[m], it);
+      xf = xf_next;
+      xf_sinv = xf_next_sinv;
+    }
+    if (nslot > SESSION_SLOTS) {
+      set_error("session_create: the split head path needs %d slots (%d available)", nslot, SESSION_SLOTS);
+      return 2;
+    }
+  }
+
+  allocate(p);
+  char why[256];
+  if (!self_check(p, why, sizeof(why))) {
+    set_error("session_create: the buffer plan failed its self-check: %s", why);
+    return 3;
+  }
+  return 0;
+}
+
+}  // namespace
+
+extern "C" {
+
+int mvg_session_create(const mvg_session_cfg *cfg, mvg_session **out) {
+  if (out) *out = nullptr;
+  if (!cfg || !out) {
+    mvg::set_error("session_create: cfg and out are required");
+    return 2;
+  }
+  const mvg_session_cfg &c = *cfg;
+  if (c.depth != 18 && c.depth != 50) {
+    mvg::set_error("session_create: depth %d (the hot path covers ResNet-18 and ResNet-50)", c.depth);
+    return 2;
+  }
+  if (c.views < 2 || c.views > mvg::SESSION_MAX_VIEWS) {
+    mvg::set_error("session_create: views %d (2 .. %d)", c.views, mvg::SESSION_MAX_VIEWS);
+    return 2;
+  }
+  if (c.batch < 1 || c.batch > 65536 || c.num_iter < 1 || c.num_iter > 64) {
+    mvg::set_error("session_create: batch %d (1 .. 65536) or num_iter %d (1 .. 64) out of range", c.batch, c.num_iter);
+    return 2;
+  }
+  if (c.height < 32 || c.width < 32 || c.height > 4096 || c.width > 4096) {
+    mvg::set_error("session_create: input size %d x %d (32 .. 4096 per side: the backbone halves it five times)", c.height, c.width);
+    return 2;
+  }
+  if (c.raw_u8 && (c.in_h < 1 || c.in_w < 1 || c.in_h > 16384 || c.in_w > 16384)) {
+    mvg::set_error("session_create: raw_u8 needs the patch size (in_h %d, in_w %d)", c.in_h, c.in_w);
+    return 2;
+  }
+  if ((int64_t)c.views * (c.views - 1) * c.batch > (1 << 24) || (int64_t)c.views * c.batch * c.height * c.width * 64 / 4 > (1LL << 40)) {
+    mvg::set_error("session_create: views x batch x size is beyond what one forward addresses");
+    return 2;
+  }
+  mvg_session *s = new (std::nothrow) mvg_session();
+  if (!s) {
+    mvg::set_error("session_create: out of host memory");
+    return 1;
+  }
+  s->cfg = c;
+  const int rc = build(c, s->plan);
+  if (rc != 0) {
+    delete s;
+    return rc;
+  }
+  *out = s;
+  return 0;
+}
+
+void mvg_session_destroy(mvg_session *s) { delete s; }
+
+int mvg_session_num_tensors(const mvg_session *s) { return s ? (int)s->plan.tensors.size() : -1; }
+
+const char *mvg_session_tensor_name(const mvg_session *s, int i) {
+  if (!s || i < 0 || i >= (int)s->plan.tensors.size()) return nullptr;
+  return s->plan.tensors[i].name.c_str();
+}
+
+int64_t mvg_session_tensor_numel(const mvg_session *s, int i) {
+  if (!s || i < 0 || i >= (int)s->plan.tensors.size()) return -1;
+  return s->plan.tensors[i].numel;
+}
+
+size_t mvg_session_workspace_bytes(const mvg_session *s) { return s ? (size_t)s->plan.workspace_bytes : 0; }
+
+int mvg_session_launches(const mvg_session *s) { return s ? (int)s->plan.steps.size() : -1; }
+
+}  // extern "C"

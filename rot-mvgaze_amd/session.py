@@ -1,0 +1,145 @@
+"""Inference session: the whole eval-mode forward queued by ONE call into librotmvgaze_hip.so.
+
+``InferenceSession`` is the Python face of the handle-level C ABI (``mvg_session_*`` in include/rotmvgaze.h): a plan built
+on the host for one (architecture, V, B, H, W) shape, a caller-owned workspace, and a forward that queues the same entry
+points ``MultiViewGaze.run_views`` calls under ``model.eval()`` / ``torch.no_grad()`` - input layout, backbone with
+BatchNorm folded, pools, lifter, fusion iterations, gaze heads - so its four outputs are bit-identical to the module's.
+What depends on the weights only (sp weight copies, BatchNorm folds, index tables) is queued once by ``bind`` /
+``refresh``; ``run`` queues the per-input launches, allocates nothing when given its outputs and never synchronises.
+
+The model's own ``forward`` / ``forward_multiview`` do not route through a session.
+"""
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, Optional, Sequence, Tuple
+
+import torch
+
+from . import ops
+from ._lib import SessionCfg, check, lib
+from .arch import NUM_FEAT_VEC
+
+Tensor = torch.Tensor
+
+
+class InferenceSession:
+    """``InferenceSession(model, views, batch, height, width, raw_hw=None, input_bgr=False)``.
+
+    model: a ``MultiViewGaze`` / ``FeatRotationSymm`` on the GPU (default, ``share_weights`` or ``ignore_rotmat`` variant,
+    ``compute_dtype`` float32).  height / width: the network's input size.  raw_hw = (h, w): the views are raw uint8
+    ``[B, h, w, 3]`` patches, resized and normalised on the GPU (``input_bgr``: swap B and R first); otherwise fp32
+    ``[B, 3, height, width]``.  The kernel family follows ``model._backbone.split`` (MVG_SPLIT); the 2 GiB guard of the split
+    path is evaluated from the real sizes.  Several sessions may share one model."""
+
+    def __init__(self, model, views: int, batch: int, height: int, width: int, raw_hw: Optional[Tuple[int, int]] = None,
+                 input_bgr: bool = False) -> None:
+        v = model._variant
+        if v.encode_rotmat or v.share_feature:
+            raise ValueError("InferenceSession: the encode_rotmat and share_feature variants are not served by the native session")
+        if model.compute_dtype != torch.float32:
+            raise ValueError("InferenceSession: compute_dtype must be torch.float32 (the bf16 inference form is not served)")
+        self._h = None
+        self.model = model
+        model.ensure_layout()
+        self.views, self.batch, self.height, self.width = int(views), int(batch), int(height), int(width)
+        self.raw_hw = tuple(raw_hw) if raw_hw is not None else None
+        in_h, in_w = self.raw_hw if self.raw_hw is not None else (0, 0)
+        cfg = SessionCfg(depth=model._depth, num_iter=model._num_iter, views=self.views, batch=self.batch, height=self.height,
+                         width=self.width, share_weights=int(v.share_weights), ignore_rotmat=int(v.ignore_rotmat),
+                         split=int(model._backbone.split), raw_u8=int(self.raw_hw is not None), in_h=int(in_h), in_w=int(in_w),
+                         input_bgr=int(bool(input_bgr)))
+        h = C.c_void_p()
+        check(lib().mvg_session_create(C.byref(cfg), C.byref(h)), "session_create")
+        self._h = h
+        self.tensor_names: List[str] = [lib().mvg_session_tensor_name(h, i).decode() for i in range(lib().mvg_session_num_tensors(h))]
+        self.workspace_bytes = int(lib().mvg_session_workspace_bytes(h))
+        self.launches = int(lib().mvg_session_launches(h))
+        self.device = next(model.parameters()).device
+        self.fc_dim, self.num_iter, self.dirs = model._fc_dim, model._num_iter, self.views * (self.views - 1)
+        with torch.cuda.device(self.device):
+            self._workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
+        self._views_arr = (C.c_void_p * self.views)()
+        self.refresh()
+
+    # ---------------------------------------------------------------- weights
+    def refresh(self) -> None:
+        """(Re)bind the model's parameters and BatchNorm buffers and queue the once-per-weights work on the current stream.
+        Call it after the weights changed (an optimizer step, ``load_state_dict``, a write to the arena)."""
+        if self._h is None:
+            raise RuntimeError("InferenceSession is closed")
+        self.model.ensure_layout()
+        named = self.model._named_tensors()
+        ptrs = (C.c_void_p * len(self.tensor_names))()
+        for i, name in enumerate(self.tensor_names):
+            t = named[name].detach()
+            if t.dtype != torch.float32 or t.device != self.device:
+                raise RuntimeError(f"InferenceSession: {name} must be an fp32 tensor on {self.device}")
+            if t.numel() != lib().mvg_session_tensor_numel(self._h, i):
+                raise RuntimeError(f"InferenceSession: {name} has {t.numel()} elements, the session expects "
+                                   f"{lib().mvg_session_tensor_numel(self._h, i)}")
+            if not (t.is_contiguous(memory_format=torch.channels_last) if (t.dim() == 4 and t.shape[2] > 1) else
+                    (t.is_contiguous() or t.is_contiguous(memory_format=torch.channels_last))):
+                raise RuntimeError(f"InferenceSession: {name} must be contiguous (conv weights channels_last = KRSC)")
+            ptrs[i] = t.data_ptr()
+        with torch.cuda.device(self.device):
+            check(lib().mvg_session_bind(self._h, ptrs, C.c_void_p(self._workspace.data_ptr()), self.workspace_bytes,
+                                         C.c_void_p(ops._s())), "session_bind")
+
+    # ---------------------------------------------------------------- forward
+    def empty_outputs(self):
+        """Uninitialised (img_feat, lifted, feats, preds) of this session's shape, for ``run(..., out=...)``."""
+        V, B, I, D, dev = self.views, self.batch, self.num_iter, self.dirs, self.device
+        mk = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+        return mk(V, B, self.fc_dim), mk(V, B, 3, NUM_FEAT_VEC), mk(I, D, B, 3, NUM_FEAT_VEC), mk(I, D, B, 2)
+
+    def run(self, imgs: Sequence[Tensor], rot: Tensor, out=None):
+        """imgs: V tensors (fp32 ``[B,3,H,W]``, or uint8 ``[B,h,w,3]`` with ``raw_hw``); rot fp32 ``[B,V,3,3]``.  Returns
+        ``(img_feat [V,B,Cf], lifted [V,B,3,512], feats [I,D,B,3,512], preds [I,D,B,2])`` as ``run_views`` does; ``out``
+        (from ``empty_outputs``) receives them without any allocation.  Queued on the current stream."""
+        if self._h is None:
+            raise RuntimeError("InferenceSession is closed")
+        V, B = self.views, self.batch
+        if len(imgs) != V:
+            raise ValueError(f"InferenceSession.run: {len(imgs)} views, the session was made for {V}")
+        want = (B, self.raw_hw[0], self.raw_hw[1], 3) if self.raw_hw is not None else (B, 3, self.height, self.width)
+        dt = torch.uint8 if self.raw_hw is not None else torch.float32
+        for v, im in enumerate(imgs):
+            if tuple(im.shape) != want or im.dtype != dt or im.device != self.device or not im.is_contiguous():
+                raise ValueError(f"InferenceSession.run: view {v} must be a contiguous {dt} tensor of shape {want} on {self.device}")
+            self._views_arr[v] = im.data_ptr()
+        if tuple(rot.shape) != (B, V, 3, 3) or rot.dtype != torch.float32 or rot.device != self.device or not rot.is_contiguous():
+            raise ValueError(f"InferenceSession.run: rot must be a contiguous fp32 tensor of shape {(B, V, 3, 3)} on {self.device}")
+        if out is None:
+            out = self.empty_outputs()
+        else:
+            for o, ref in zip(out, ((V, B, self.fc_dim), (V, B, 3, NUM_FEAT_VEC), (self.num_iter, self.dirs, B, 3, NUM_FEAT_VEC),
+                                    (self.num_iter, self.dirs, B, 2))):
+                if tuple(o.shape) != ref or o.dtype != torch.float32 or o.device != self.device or not o.is_contiguous():
+                    raise ValueError(f"InferenceSession.run: an output must be a contiguous fp32 tensor of shape {ref}")
+        img_feat, lifted, feats, preds = out
+        with torch.cuda.device(self.device):
+            check(lib().mvg_session_forward(self._h, self._views_arr, C.c_void_p(rot.data_ptr()), C.c_void_p(img_feat.data_ptr()),
+                                            C.c_void_p(lifted.data_ptr()), C.c_void_p(feats.data_ptr()), C.c_void_p(preds.data_ptr()),
+                                            C.c_void_p(ops._s())), "session_forward")
+        return img_feat, lifted, feats, preds
+
+    # ---------------------------------------------------------------- lifetime
+    def close(self) -> None:
+        """Destroy the handle and drop the workspace (stream-ordered: queued forwards still finish)."""
+        if self._h is not None:
+            lib().mvg_session_destroy(self._h)
+            self._h = None
+            self._workspace = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()

@@ -1,0 +1,166 @@
+"""The inference session's host side (no GPU): the ABI additions, the tensor list against the module's state_dict, the
+buffer plan's reuse, where the head path switches, the rejected configurations, and the plan builder compiled stand-alone
+under AddressSanitizer + UBSan (a plain executable: nothing is loaded into Python and nothing is preloaded)."""
+import ctypes as C
+import os
+import re
+import shutil
+import subprocess
+
+import pytest
+
+import rot_mvgaze_amd  # noqa: F401
+from rot_mvgaze_amd import arch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SESSION_ENTRY_POINTS = ("mvg_session_create", "mvg_session_destroy", "mvg_session_num_tensors", "mvg_session_tensor_name",
+                        "mvg_session_tensor_numel", "mvg_session_workspace_bytes", "mvg_session_launches", "mvg_session_bind",
+                        "mvg_session_forward", "mvg_bn_eval_affine_batch")
+
+
+@pytest.fixture(scope="module")
+def L():
+    import __graft_entry__ as ge
+    ge.build()
+    from rot_mvgaze_amd import _lib
+    return _lib.lib()
+
+
+def _cfg(**kw):
+    from rot_mvgaze_amd._lib import SessionCfg
+    d = dict(depth=50, num_iter=3, views=2, batch=2, height=64, width=64, share_weights=0, ignore_rotmat=0, split=1, raw_u8=0,
+             in_h=0, in_w=0, input_bgr=0)
+    d.update(kw)
+    return SessionCfg(**d)
+
+
+class _Session:
+    def __init__(self, L, **kw):
+        self.L, self.h = L, C.c_void_p()
+        self.rc = L.mvg_session_create(C.byref(_cfg(**kw)), C.byref(self.h))
+
+    def __enter__(self):
+        assert self.rc == 0, self.L.mvg_last_error()
+        return self
+
+    def __exit__(self, *exc):
+        self.L.mvg_session_destroy(self.h)
+
+    def names(self):
+        return [self.L.mvg_session_tensor_name(self.h, i).decode() for i in range(self.L.mvg_session_num_tensors(self.h))]
+
+    def numels(self):
+        return [self.L.mvg_session_tensor_numel(self.h, i) for i in range(self.L.mvg_session_num_tensors(self.h))]
+
+    def workspace(self):
+        return self.L.mvg_session_workspace_bytes(self.h)
+
+    def launches(self):
+        return self.L.mvg_session_launches(self.h)
+
+
+def test_abi_additions(L):
+    from rot_mvgaze_amd import _lib
+    hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
+    assert re.search(r"#define\s+MVG_ABI_VERSION\s+11\b", hdr)
+    assert L.mvg_abi_version() == _lib.ABI_VERSION == 11
+    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    for name in SESSION_ENTRY_POINTS:
+        m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", code, flags=re.S)
+        assert m, f"{name} is not declared in include/rotmvgaze.h"
+        args = m.group(1).strip()
+        arity = 0 if args in ("", "void") else args.count(",") + 1
+        assert hasattr(L, name), f"{name} is not exported"
+        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == arity, (name, arity)
+    # the cfg struct the binding passes is the header's: 13 int32 fields, in order
+    m = re.search(r"typedef struct \{([^{}]*)\} mvg_session_cfg;", code)
+    fields = [f.strip() for decl in re.findall(r"int32_t\s+([^;]+);", m.group(1)) for f in decl.split(",")]
+    assert fields == [n for n, _ in _lib.SessionCfg._fields_] and C.sizeof(_lib.SessionCfg) == 4 * len(fields)
+
+
+@pytest.mark.parametrize("depth", [18, 50])
+def test_tensor_names_match_the_state_dict(L, depth):
+    from rot_mvgaze_amd.model import FeatRotationSymm
+    sd = FeatRotationSymm(depth, 3).state_dict()
+    want = [k for k in sd if not k.startswith("_feat_extractor.0.fc.") and not k.endswith("num_batches_tracked")]
+    shared = [k for k in FeatRotationSymm(depth, 3, share_weights=True).state_dict()
+              if not k.startswith("_feat_extractor.0.fc.") and not k.endswith("num_batches_tracked")
+              and not re.match(r"_(img_fusers|gaze_estimators)\.[12]\.", k)]
+    assert len(shared) == len(want) - 16
+    n = 0
+    for views in (2, 3, 4):
+        for batch in (1, 3, 86):
+            for hw in (64, 224):
+                for split in (0, 1):
+                    for raw in (0, 1):
+                        with _Session(L, depth=depth, views=views, batch=batch, height=hw, width=hw, split=split, raw_u8=raw,
+                                      in_h=80 * raw, in_w=72 * raw) as s:
+                            assert s.names() == want
+                            assert s.numels() == [sd[k].numel() for k in want]
+                            n += 1
+    assert n == 72
+    with _Session(L, depth=depth, share_weights=1) as s:
+        assert s.names() == shared
+        assert s.numels() == [sd[k].numel() for k in shared]
+
+
+def _unit_output_elems_per_image(depth, hw):
+    """Every conv + BatchNorm unit's output elements for one image (the no-reuse yardstick)."""
+    spec = arch.backbone_spec(depth)
+    size = lambda h, c: (h + 2 * c.pad - c.k) // c.stride + 1
+    h = size(hw, spec.stem)
+    total = h * h * spec.stem.cout
+    h = (h + 2 - 3) // 2 + 1
+    for blk in spec.blocks:
+        hb = h
+        for c in blk.convs:
+            hb = size(hb, c)
+            total += hb * hb * c.cout
+        if blk.downsample is not None:
+            hd = size(h, blk.downsample)
+            total += hd * hd * blk.downsample.cout
+        h = hb
+    return total
+
+
+def test_workspace_reuses_buffers(L):
+    sizes = []
+    for batch in (1, 2, 8, 32, 85, 86, 128):
+        with _Session(L, depth=50, views=4, batch=batch, height=224, width=224) as s:
+            sizes.append(s.workspace())
+    assert sizes == sorted(sizes) and sizes[0] > 0
+    per_image = _unit_output_elems_per_image(50, 224)
+    assert abs(per_image - 11.114e6) < 0.001e6
+    no_reuse = per_image * 4 * 128 * 4                       # C3 eval: R50, V = 4, B = 128, fp32 / sp = 4 bytes per element
+    assert sizes[-1] <= no_reuse / 2, (sizes[-1], no_reuse)
+
+
+def test_head_path_switches_at_1024_rows(L):
+    with _Session(L, depth=18, views=4, batch=85) as a, _Session(L, depth=18, views=4, batch=86) as b:
+        assert a.launches() > 0 and b.launches() > 0
+        assert a.launches() != b.launches()                  # 1020 rows: generated-input fp32-MFMA Linears; 1032: the split Linears
+    with _Session(L, depth=18, views=4, batch=85, split=0) as a, _Session(L, depth=18, views=4, batch=86, split=0) as b:
+        assert a.launches() == b.launches()                  # MVG_SPLIT=0: one head path at every row count
+
+
+@pytest.mark.parametrize("bad", [dict(depth=34), dict(views=1), dict(batch=0), dict(raw_u8=1, in_h=0, in_w=72), None])
+def test_rejected_configurations(L, bad):
+    h = C.c_void_p(1)
+    rc = L.mvg_session_create(C.byref(_cfg(**bad)) if bad is not None else None, C.byref(h))
+    assert rc != 0 and h.value is None
+    assert L.mvg_last_error()
+
+
+def test_plan_builder_standalone_under_sanitizers(tmp_path):
+    cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
+    assert cxx, "a host C++ compiler is needed to build tests/native/session_plan_check.cpp"
+    exe = str(tmp_path / "session_plan_check")
+    # the sanitizer runtimes are linked into the executable: it runs as it is, with nothing preloaded
+    static = ["-static-libasan", "-static-libubsan"] if "clang" not in os.path.basename(cxx) else ["-static-libsan"]
+    subprocess.run([cxx, "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + static + ["-o", exe,
+                    os.path.join(ROOT, "tests", "native", "session_plan_check.cpp"),
+                    os.path.join(ROOT, "rot-mvgaze_amd", "csrc", "session_plan.cpp")], check=True)
+    r = subprocess.run([exe], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    assert "session_plan_check: ok" in r.stdout
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr
