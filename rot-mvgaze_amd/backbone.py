@@ -14,7 +14,8 @@ from __future__ import annotations
 
 import math
 import os
-from typing import Callable, Dict, List, Optional
+from dataclasses import dataclass
+from typing import Callable, Dict, List, NamedTuple, Optional
 
 import numpy as np
 import torch
@@ -102,16 +103,33 @@ class GradSink:
         raise NotImplementedError
 
 
+@dataclass(slots=True)
 class _Unit:
     """Saved state of one conv + BN (+ReLU) (+residual) for the backward pass."""
-    __slots__ = ("spec", "desc", "x_in", "y", "out", "mean", "invstd", "relu", "rows", "w", "trained", "pool",
-                 "relu_affine", "fused_s12", "relu_bits", "split", "stem_rw")
+    spec: Optional[ConvSpec] = None
+    desc: Optional[ConvDesc] = None
+    x_in: Optional[Tensor] = None
+    y: Optional[Tensor] = None        # the raw conv output (BatchNorm backward needs x-hat)
+    out: Optional[Tensor] = None      # the post-activation map (None: never stored - the stem, a deferred downsample branch)
+    mean: Optional[Tensor] = None
+    invstd: Optional[Tensor] = None
+    relu: bool = False
+    rows: int = 0
+    w: Optional[Tensor] = None        # the backward-data operand: the transposed copy on the bf16 / split kernels
+    trained: bool = True              # normalised with batch statistics (False: eval mode, running statistics)
+    pool: Optional[tuple] = None      # the stem: (argmax, scale, shift, ho, wo, hp, wp) of the fused max pool
+    relu_affine: Optional[tuple] = None   # ReLU without residual: (scale, shift) - the backward rebuilds the mask from y
+    fused_s12: Optional[object] = None    # BatchNorm-backward sums delivered by the backward-data launch that produced this unit's gradient
+    relu_bits: Optional[Tensor] = None    # residual units: the ReLU mask as one byte per 16-byte access (ops.bn_apply_bits)
+    split: bool = False       # conv operands (x_in, out, dy, w) in sp (two fp16 pieces), split-operand kernels (conv_split.hip)
+    stem_rw: bool = False     # the stem in row-window form: x_in is the window operand, dy goes out in sp
 
-    def __init__(self):
-        self.split = False        # conv operands (x_in, out, dy, w) in sp (two fp16 pieces), split-operand kernels (conv_split.hip)
-        self.stem_rw = False      # the stem in row-window form: x_in is the window operand, dy goes out in sp
-        self.relu_bits = None     # residual units: the ReLU mask as one byte per 16-byte access (ops.bn_apply_bits)
-        self.fused_s12 = None     # BatchNorm-backward sums delivered by the backward-data launch that produced this unit's gradient
+
+class _Fwd(NamedTuple):
+    """What Backbone._unit_fwd returns, whatever its mode (members a mode does not produce are None)."""
+    out: Tensor                       # the unit's output; the pooled map (pool); the raw conv output y (defer_apply)
+    affine: Optional[tuple] = None    # defer_apply: the (scale, shift) the consumer normalises ``out`` with
+    pending: Optional[tuple] = None   # the apply pass handed to next_conv's forward launch (bn_apply_fprop_eligible)
 
 
 class Backbone:
@@ -192,17 +210,6 @@ class Backbone:
         return self.act_dtype == torch.bfloat16
 
     # ---------------------------------------------------------------- helpers
-    def _weight(self, c: ConvSpec) -> Tensor:
-        """KRSC device tensor the kernels read.  The 3-channel stem is padded to 4 channels."""
-        w = self.p[c.name + ".weight"]
-        if c.cin == 3:
-            w4 = torch.zeros(c.cout, c.k, c.k, 4, dtype=torch.float32, device=w.device)
-            w4[..., :3].copy_(w.detach().permute(0, 2, 3, 1))          # 9408 floats: layout plumbing
-            return w4
-        assert w.is_contiguous(memory_format=torch.channels_last) or (c.k == 1 and w.is_contiguous()), \
-            f"{c.name}.weight must be channels_last (KRSC)"
-        return w.detach()
-
     def _prepare_weights(self, dev, reuse: bool = False) -> Dict[str, tuple]:
         """The per-step copies of every conv's weights the bf16 / split kernels read (KRSC for fprop, CRSK for
         backward-data), made by ONE launch: destination buffers and the launch's device-resident table of
@@ -336,176 +343,214 @@ class Backbone:
         return [self.p[c.bn + ".num_batches_tracked"] for c in self.spec.all_convs()]
 
     # ---------------------------------------------------------------- forward
+    def _conv_weights(self, c: ConvSpec, d: ConvDesc, sp: bool, need_transposed: bool):
+        """(w, w_t): the KRSC weight operand of conv ``c`` and its transposed copy for backward-data (or None).  sp: the launch
+        reads sp operands (split kernels; the stem in row-window form).  sp / bf16: this step's copies when ONE launch at the
+        start of forward() made them (_wprep), else a split / cast per call; otherwise the fp32 parameter itself."""
+        if (sp or self.bf16) and self._wprep is not None:
+            return self._wprep[c.name]
+        wsrc = self.p[c.name + ".weight"].detach()
+        if c.cin == 3 and not (sp or self.bf16):                          # the 3-channel stem padded to 4 channels
+            w4 = torch.zeros(c.cout, c.k, c.k, 4, dtype=torch.float32, device=wsrc.device)
+            w4[..., :3].copy_(wsrc.permute(0, 2, 3, 1))                   # 9408 floats: layout plumbing
+            return w4, None
+        assert wsrc.is_contiguous(memory_format=torch.channels_last) or (c.k == 1 and wsrc.is_contiguous()), \
+            f"{c.name}.weight must be channels_last (KRSC)"
+        if not (sp or self.bf16):
+            return wsrc, None
+        if sp:
+            return ops.split_weights(d, wsrc, need_transposed=need_transposed)
+        # one cast of the fp32 master weights per step: KRSC for fprop, CRSK (transposed) for backward-data
+        return ops.cast_weights_bf16(d, wsrc, c.cin, need_transposed=need_transposed and c.cin != 3)
+
+    def _unit_infer(self, c: ConvSpec, x: Tensor, G: int, N: int, H: int, W: int, relu: bool, residual: Optional[Tensor],
+                    pool: bool = False) -> Tensor:
+        """Folded inference unit (no tape, not training, not the unfolded bf16 form): conv with BatchNorm on the running
+        statistics (+ residual) (+ ReLU) in its epilogue - ONE launch, the output written once.  Returns the unit's output;
+        pool (the fp32 stem): the max-pooled map, in sp when the split kernels serve the call.
+        csrc/session_plan.cpp restates this method (its unit()) and _forward_infer (its block loop) as data for the fp32
+        model: a change to the launches here must be made there too."""
+        bf = self.bf16
+        assert not (bf and pool)                 # the bf16 stem goes through _unit_fwd
+        d = ConvDesc.make(G, N, H, W, 4 if c.cin == 3 else c.cin, c.cout, c.k, c.stride, c.pad)
+        dev = x.device
+        sp_eval = self._split_now and self.split_eval and not bf
+        sp = sp_eval and c.cin != 3              # this conv on the split kernels (the 3-channel stem: fp32-MFMA)
+        if not sp:
+            w, _ = self._conv_weights(c, d, False, False)
+        aff = torch.empty(2, 1, c.cout, dtype=torch.float32, device=dev)
+        ops.bn_eval_affine(1, c.cout, self.p[c.bn + ".weight"].detach(), self.p[c.bn + ".bias"].detach(),
+                           self.p[c.bn + ".running_mean"], self.p[c.bn + ".running_var"], BN_EPS, aff[0], aff[1])
+        scale, shift = aff[0, 0], aff[1, 0]
+        if sp:
+            # the epilogue writes the next conv's sp operand directly (the downsample branch, read only as a residual, stays
+            # fp32).  The sp copy of the weights is kept between calls while the parameter is unchanged (its version counter:
+            # load_state_dict, optimizer steps - the fused Adam bumps it explicitly - and broadcasts all move it)
+            wsrc = self.p[c.name + ".weight"]
+            hit = self._wk_cache.get(c.name)
+            if hit is not None and hit[0] == wsrc.data_ptr() and hit[1] == wsrc._version:
+                wk = hit[2]
+            else:
+                wk, _ = self._conv_weights(c, d, True, False)
+                self._wk_cache[c.name] = (wsrc.data_ptr(), wsrc._version, wk)
+            out = (ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev) if relu
+                   else torch.empty(G, N, d.ho, d.wo, c.cout, dtype=torch.float32, device=dev))
+            ops.conv_fprop_split_affine(d, x, wk, out, scale, shift, residual, relu)
+            return out
+        y = torch.empty(G, N, d.ho, d.wo, c.cout, dtype=self.act_dtype, device=dev)
+        if bf:                                   # y is the unit's output, written once, rounded once
+            ops.conv_fprop_bf16_affine(d, x, w, y, scale, shift, residual, relu)
+            if self._debug_units is not None:
+                self._debug_units.append((c.name, x, residual, y))
+            return y
+        ops.conv_fprop_affine(d, x, w, y, scale, shift, residual, relu)
+        if not pool:
+            return y
+        pooled = self._pool_plain(y, G, N, d.ho, d.wo, c.cout)
+        return ops.split_f32(pooled) if sp_eval else pooled
+
+    @staticmethod
+    def _pool_plain(a0: Tensor, G: int, N: int, h: int, w: int, c: int) -> Tensor:
+        hp, wp_ = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
+        x = torch.empty(G, N, hp, wp_, c, dtype=torch.float32, device=a0.device)
+        argmax = torch.empty(G, N, hp, wp_, c, dtype=torch.uint8, device=a0.device)       # (written, never read: no backward)
+        ops.maxpool_fwd(a0, x, argmax, G * N, h, w, c, hp, wp_)
+        return x
+
+    def _stats_partials(self, c: ConvSpec, d: ConvDesc, sp_in: bool, stem_rw: bool):
+        """(partials per group, rows per partial) of the batch statistics that the unit's forward launch leaves."""
+        if stem_rw and self.bf16:   # two output columns per GEMM row: twice the partials of a forward over n x ho x wo/2 rows
+            P, rpp = ops.conv_stats_partials(ConvDesc.make(d.groups, d.n, d.ho, d.wo // 2, 64, 2 * c.cout, 1, 1, 0), True)
+            return 2 * P, rpp
+        if stem_rw:                 # the same row tiles as any split forward with these n, ho, wo
+            return ops.conv_stats_partials_split(ConvDesc.make(d.groups, d.n, d.ho, d.wo, 32, c.cout, 1, 1, 0))
+        return ops.conv_stats_partials_split(d) if sp_in else ops.conv_stats_partials(d, self.bf16)
+
     def _unit_fwd(self, c: ConvSpec, x: Tensor, G: int, N: int, H: int, W: int, training: bool, relu: bool,
                   residual: Optional[Tensor], tape: Optional[list], pool: bool = False, residual_affine=None,
-                  defer_apply: bool = False, next_conv: Optional[ConvSpec] = None, pending_apply: Optional[tuple] = None):
-        """conv -> BatchNorm (-> + residual) (-> ReLU).  pool=True (the stem): the 3x3/2 max pool is
-        fused behind the ReLU and (pooled, argmax) is returned; the normalised map is not stored.
-        defer_apply (the downsample branch): stop after the statistics and return (y, (scale, shift)) - the
-        normalisation is applied by the consumer, the block's last unit, which takes them as
+                  defer_apply: bool = False, next_conv: Optional[ConvSpec] = None, pending_apply: Optional[tuple] = None) -> _Fwd:
+        """conv -> BatchNorm (-> + residual) (-> ReLU), the BatchNorm as passes of its own: batch statistics (training) or
+        the running ones (eval mode with a tape; bf16 inference that is not folded; the bf16 inference stem).  Returns _Fwd.
+        pool=True (the stem): the 3x3/2 max pool is fused behind the ReLU - out is the pooled map; the normalised map is not stored.
+        defer_apply (the downsample branch): stop after the statistics - out is the raw conv output y and affine its
+        (scale, shift): the normalisation is applied by the consumer, the block's last unit, which takes them as
         residual / residual_affine; the normalised downsample map is never written.
         next_conv (a block's last unit: the next block's first conv): when bn_apply_fprop_eligible accepts the pair, this unit's
-        apply pass is NOT launched - (out, pending) is returned, out allocated and recorded on the tape as usual, and the next
-        block's first unit takes ``pending`` as pending_apply: its forward launch forms, uses and writes ``x`` (= that out)."""
+        apply pass is NOT launched - out is allocated and recorded on the tape as usual, and the next block's first unit
+        takes ``pending`` as pending_apply: its forward launch forms, uses and writes ``x`` (= that out)."""
         bf = self.bf16
-        cin = (8 if bf else 4) if c.cin == 3 else c.cin
-        d = ConvDesc.make(G, N, H, W, cin, c.cout, c.k, c.stride, c.pad)
+        d = ConvDesc.make(G, N, H, W, (8 if bf else 4) if c.cin == 3 else c.cin, c.cout, c.k, c.stride, c.pad)
         dev = x.device
         # split path: training steps of the fp32 model; sp_in = this conv reads sp operands (all but the stem),
         # sp_out = its consumers do (every unit: the stem's pooled map feeds layer1)
         sp_out = self._split_now and training and not bf
         sp_in = sp_out and c.cin != 3
         stem_rw = c.cin == 3 and self._stem_rw and (sp_out or bf)  # x is then the row-window operand (ops.stem_rowwindow_split / _bf16)
-        if (sp_in or bf or stem_rw) and self._wprep is not None:
-            w, w_t = self._wprep[c.name]         # this step's copies, made by ONE launch at the start of forward()
-        elif sp_in:
-            wsrc = self.p[c.name + ".weight"].detach()
-            assert wsrc.is_contiguous(memory_format=torch.channels_last) or (c.k == 1 and wsrc.is_contiguous())
-            w, w_t = ops.split_weights(d, wsrc, need_transposed=tape is not None)
-        elif bf:
-            # one cast of the fp32 master weights per step: KRSC for fprop, CRSK (transposed) for backward-data
-            wsrc = self.p[c.name + ".weight"].detach()
-            assert wsrc.is_contiguous(memory_format=torch.channels_last) or (c.k == 1 and wsrc.is_contiguous())
-            w, w_t = ops.cast_weights_bf16(d, wsrc, c.cin, need_transposed=(tape is not None and c.cin != 3))
-        else:
-            w, w_t = self._weight(c), None
+        assert pending_apply is None or (sp_in and not stem_rw)
+        assert not stem_rw or self._wprep is not None               # the row-window filter comes from the batched weight prep only
+        keep = tape is not None
+        w, w_t = self._conv_weights(c, d, sp_in or stem_rw, keep)
         y = torch.empty(G, N, d.ho, d.wo, c.cout, dtype=self.act_dtype, device=dev)
         rows = N * d.ho * d.wo
         gamma, beta = self.p[c.bn + ".weight"].detach(), self.p[c.bn + ".bias"].detach()
         rm, rv = self.p[c.bn + ".running_mean"], self.p[c.bn + ".running_var"]
-        aff = torch.empty(4, G, c.cout, dtype=torch.float32, device=dev)
-        mean, invstd, scale, shift = aff[0], aff[1], aff[2], aff[3]
-
-        def fprop(stats_buf):
-            if stem_rw and bf:
-                ops.stem_fprop_bf16(d, x, w, y, stats_buf)
-            elif stem_rw:
-                ops.stem_fprop_split(d, x, w, y, stats_buf)
-            elif sp_in and pending_apply is not None:
-                # x does not exist yet: this launch forms it from the previous block's last unit, then every later reader finds it
-                py, pscale, pshift, pres, pres_affine, pbits = pending_apply
-                ops.conv_fprop_split_bnapply(d, x, py, pscale, pshift, pres, w, y, stats_buf, pres_affine, pbits)
-            elif sp_in:
-                ops.conv_fprop_split(d, x, w, y, stats_buf)
-            else:
-                ops.conv_fprop(d, x, w, y, None, False, stats_buf)
-        assert pending_apply is None or (sp_in and training and not stem_rw)
+        mean, invstd, scale, shift = torch.empty(4, G, c.cout, dtype=torch.float32, device=dev)
+        stats = None                             # training: the launch leaves partial batch statistics per row tile
         if training:
-            if stem_rw and bf:   # two output columns per GEMM row: twice the partials of a forward over n x ho x wo/2 rows
-                P, rpp = ops.conv_stats_partials(ConvDesc.make(G, N, d.ho, d.wo // 2, 64, 2 * c.cout, 1, 1, 0), True)
-                P *= 2
-            elif stem_rw:    # the same row tiles as any split forward with these n, ho, wo
-                P, rpp = ops.conv_stats_partials_split(ConvDesc.make(G, N, d.ho, d.wo, 32, c.cout, 1, 1, 0))
-            else:
-                P, rpp = ops.conv_stats_partials_split(d) if sp_in else ops.conv_stats_partials(d, bf)
+            P, rpp = self._stats_partials(c, d, sp_in, stem_rw)
             stats = torch.empty(G, P, 2, c.cout, dtype=torch.float32, device=dev)
-            fprop(stats)
+        if stem_rw and bf:
+            ops.stem_fprop_bf16(d, x, w, y, stats)
+        elif stem_rw:
+            ops.stem_fprop_split(d, x, w, y, stats)
+        elif pending_apply is not None:
+            # x does not exist yet: this launch forms it from the previous block's last unit, then every later reader finds it
+            py, pscale, pshift, pres, pres_affine, pbits = pending_apply
+            ops.conv_fprop_split_bnapply(d, x, py, pscale, pshift, pres, w, y, stats, pres_affine, pbits)
+        elif sp_in:
+            ops.conv_fprop_split(d, x, w, y, stats)
+        else:
+            ops.conv_fprop(d, x, w, y, None, False, stats)
+        if training:
             ops.bn_finalize(stats, G, P, rpp, rows, c.cout, gamma, beta, rm, rv, BN_MOMENTUM, BN_EPS, mean, invstd,
                             scale, shift)
-        elif tape is None and not bf:
-            # inference: BN (running statistics) + residual + ReLU folded into the conv epilogue
-            ops.bn_eval_affine(1, c.cout, gamma, beta, rm, rv, BN_EPS, scale[:1], shift[:1])
-            sp_eval = self._split_now and self.split_eval
-            if sp_eval and c.cin != 3:
-                # ... on the split kernels: the epilogue writes the next conv's sp operand directly (the downsample
-                # branch, read only as a residual, stays fp32)
-                wsrc = self.p[c.name + ".weight"].detach()
-                assert wsrc.is_contiguous(memory_format=torch.channels_last) or (c.k == 1 and wsrc.is_contiguous())
-                # the sp copy of the weights is kept between calls while the parameter is unchanged (its version counter:
-                # load_state_dict, optimizer steps - the fused Adam bumps it explicitly - and broadcasts all move it)
-                hit = self._wk_cache.get(c.name)
-                if hit is not None and hit[0] == wsrc.data_ptr() and hit[1] == wsrc._version:
-                    wk = hit[2]
-                else:
-                    wk, _ = ops.split_weights(d, wsrc, need_transposed=False)
-                    self._wk_cache[c.name] = (wsrc.data_ptr(), wsrc._version, wk)
-                out = ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev) if relu else y
-                ops.conv_fprop_split_affine(d, x, wk, out, scale[0], shift[0], residual, relu)
-                return out
-            ops.conv_fprop_affine(d, x, w, y, scale[0], shift[0], residual, relu)
-            if pool:
-                pooled, am = self._pool_plain(y, G, N, d.ho, d.wo, c.cout)
-                return (ops.split_f32(pooled), am) if sp_eval else (pooled, am)
-            return y
-        elif tape is None and bf and self.bf16_fold_eval and not pool:
-            # bf16 inference: the same fold on the bf16 kernels - y is the unit's output, written once, rounded once
-            ops.bn_eval_affine(1, c.cout, gamma, beta, rm, rv, BN_EPS, scale[:1], shift[:1])
-            ops.conv_fprop_bf16_affine(d, x, w, y, scale[0], shift[0], residual, relu)
-            if self._debug_units is not None:
-                self._debug_units.append((c.name, x, residual, y))
-            return y
         else:
-            fprop(None)
             ops.bn_eval_affine(G, c.cout, gamma, beta, rm, rv, BN_EPS, scale, shift)
-        keep = tape is not None
+        out = bits = pool_rec = handed = None
         if defer_apply:
             assert not relu and residual is None and not pool
-            if keep:
-                u = _Unit()
-                u.spec, u.desc, u.x_in, u.y, u.out, u.mean, u.invstd, u.relu, u.rows, u.w = \
-                    c, d, x, y, None, mean, invstd, False, rows, (w_t if (bf or sp_in) else w)
-                u.trained = training
-                u.split = sp_in
-                u.relu_affine = None
-                tape.append(u)
-            return y, (scale, shift)
-        if pool:
+        elif pool:
             assert relu and residual is None
-            hp, wp_ = (d.ho + 2 - 3) // 2 + 1, (d.wo + 2 - 3) // 2 + 1
-            argmax = torch.empty(G, N, hp, wp_, c.cout, dtype=torch.uint8, device=dev)
-            if sp_out:
-                out = ops.sp_empty(G, N, hp, wp_, c.cout, device=dev)
-                out.sinv = self._act_sinv[c.name]
-                ops.bn_relu_maxpool_fwd_split(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
-            else:
-                out = torch.empty(G, N, hp, wp_, c.cout, dtype=self.act_dtype, device=dev)
-                ops.bn_relu_maxpool_fwd(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
-            if self._debug_units is not None and tape is None and not training:
+            out, pool_rec = self._stem_tail(c, d, y, scale, shift, sp_out)
+            if self._debug_units is not None and not keep and not training:
                 self._debug_units.append((c.name, x, y, out))
         elif sp_out:
             out = ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev)
             out.sinv = self._act_sinv[c.name]       # this step's 2^-k of the unit's output (an sp identity brings its own)
             want_bits = keep and relu and residual is not None
-            handed = (next_conv is not None and self.fuse_bn_apply_fprop
-                      and bn_apply_fprop_eligible(c, next_conv, split=sp_in, trained=training, residual=residual is not None, relu=relu)
-                      and ops.conv_fprop_split_stages(ConvDesc.make(G, N, d.ho, d.wo, next_conv.cin, next_conv.cout, 1, 1, 0)) == 1)
-            if handed:
+            if (next_conv is not None and self.fuse_bn_apply_fprop
+                    and bn_apply_fprop_eligible(c, next_conv, split=sp_in, trained=training, residual=residual is not None, relu=relu)
+                    and ops.conv_fprop_split_stages(ConvDesc.make(G, N, d.ho, d.wo, next_conv.cin, next_conv.cout, 1, 1, 0)) == 1):
                 bits = torch.empty(G * rows * c.cout // 4, dtype=torch.uint8, device=dev) if want_bits else None
                 handed = (y, scale, shift, residual, residual_affine, bits)
             else:
                 bits = ops.bn_apply_split(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine, want_bits=want_bits)
         else:
             out = torch.empty_like(y) if keep else y            # inference: normalise in place
-            bits = None
             if keep and relu and residual is not None and self.relu_bits:
                 bits = ops.bn_apply_bits(y, scale, shift, residual, out, G, rows, c.cout, residual_affine)
             else:
                 ops.bn_apply(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine)
         if keep:
-            u = _Unit()
-            u.spec, u.desc, u.x_in, u.y, u.out, u.mean, u.invstd, u.relu, u.rows, u.w = \
-                c, d, x, y, (None if pool else out), mean, invstd, relu, rows, (w_t if (bf or sp_in) else w)
-            u.trained = training
-            u.split = sp_in
-            u.stem_rw = stem_rw
-            # ReLU without residual: the backward rebuilds the mask from y (saves reading `out` twice)
-            u.relu_affine = (scale, shift) if (relu and residual is None and not pool) else None
-            if pool:
-                u.pool = (argmax, scale, shift, d.ho, d.wo, hp, wp_)
-            else:
-                u.relu_bits = bits
-            tape.append(u)
-        if next_conv is not None:
-            return out, ((handed or None) if sp_out else None)
-        return (out, argmax) if pool else out
+            # (ReLU without residual: the backward rebuilds the mask from y - saves reading `out` twice)
+            tape.append(_Unit(spec=c, desc=d, x_in=x, y=y, out=None if pool else out, mean=mean, invstd=invstd, relu=relu,
+                              rows=rows, w=w_t if (bf or sp_in) else w, trained=training, split=sp_in, stem_rw=stem_rw,
+                              relu_affine=(scale, shift) if (relu and residual is None and not pool) else None,
+                              pool=pool_rec, relu_bits=bits))
+        return _Fwd(y, affine=(scale, shift)) if defer_apply else _Fwd(out, pending=handed)
 
-    @staticmethod
-    def _pool_plain(a0: Tensor, G: int, N: int, h: int, w: int, c: int):
-        hp, wp_ = (h + 2 - 3) // 2 + 1, (w + 2 - 3) // 2 + 1
-        x = torch.empty(G, N, hp, wp_, c, dtype=torch.float32, device=a0.device)
-        argmax = torch.empty(G, N, hp, wp_, c, dtype=torch.uint8, device=a0.device)
-        ops.maxpool_fwd(a0, x, argmax, G * N, h, w, c, hp, wp_)
-        return x, argmax
+    def _stem_tail(self, c: ConvSpec, d: ConvDesc, y: Tensor, scale: Tensor, shift: Tensor, sp_out: bool):
+        """BatchNorm apply + ReLU + 3x3/2 max pool of the stem in one pass.  Returns (pooled map, the _Unit.pool record)."""
+        G, N = y.shape[0], y.shape[1]
+        hp, wp_ = (d.ho + 2 - 3) // 2 + 1, (d.wo + 2 - 3) // 2 + 1
+        argmax = torch.empty(G, N, hp, wp_, c.cout, dtype=torch.uint8, device=y.device)
+        if sp_out:
+            out = ops.sp_empty(G, N, hp, wp_, c.cout, device=y.device)
+            out.sinv = self._act_sinv[c.name]
+            ops.bn_relu_maxpool_fwd_split(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
+        else:
+            out = torch.empty(G, N, hp, wp_, c.cout, dtype=self.act_dtype, device=y.device)
+            ops.bn_relu_maxpool_fwd(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
+        return out, (argmax, scale, shift, d.ho, d.wo, hp, wp_)
+
+    def _input_layout(self, imgs: List[Tensor], B: int, H: int, W: int, input_bgr: bool) -> Tensor:
+        """x0, the stem's input operand, one launch per view: row windows straight from the NCHW input when the stem runs in
+        row-window form (no NHWC image is built); else the NHWC image padded to 4 (bf16: 8) channels, from raw uint8 patches
+        or NCHW fp32 - and the windows from that image for raw input with a row-window stem."""
+        V, dev, bf = len(imgs), imgs[0].device, self.bf16
+        raw = imgs[0].dtype == torch.uint8
+        direct = self._stem_rw and not raw
+        if direct and bf:
+            x0 = torch.empty(V, B, H, W // 4, 64, dtype=self.act_dtype, device=dev)
+        elif direct:
+            x0 = ops.sp_empty(V, B, H, W // 2, 32, device=dev)
+            x0.sinv = None
+        else:
+            x0 = torch.empty(V, B, H, W, 8 if bf else 4, dtype=self.act_dtype, device=dev)
+        for v, im in enumerate(imgs):
+            assert im.shape == imgs[0].shape and im.is_cuda and im.dtype == imgs[0].dtype
+            if raw:                             # (bf16: inference only - no fp32 image in between)
+                prep = ops.preprocess_u8hwc_resize_bf16 if bf else ops.preprocess_u8hwc_resize
+                prep(im.contiguous(), x0[v], B, im.shape[1], im.shape[2], H, W, IMAGE_MEAN, IMAGE_STD, input_bgr)
+                continue
+            assert im.dtype == torch.float32
+            if direct:
+                (ops.stem_rowwindow_bf16 if bf else ops.stem_rowwindow_split_nchw)(im.detach().contiguous(), x0[v])
+            else:
+                (ops.nchw_to_nhwc8_bf16 if bf else ops.nchw_to_nhwc4)(im.detach().contiguous(), x0[v], B, 3, H, W)
+        if self._stem_rw and not direct:                # raw uint8 input: windows from the normalised NHWC4 image
+            x0 = ops.stem_rowwindow_split(x0)
+        return x0
 
     def forward(self, imgs: List[Tensor], training: bool, keep_tape: bool, input_bgr: bool = False,
                 input_size: Optional[int] = None, need_dimg: bool = False):
@@ -538,34 +583,7 @@ class Backbone:
         else:
             self._stem_rw = (self._split_now and self.stem_rowwindow and training and not need_dimg and W % 2 == 0
                              and self.batch_weight_prep and 32 * B * H * (W // 2) * 4 < 0x7FFFFFF0)
-        direct = self._stem_rw and not raw              # windows straight from the NCHW input: no NHWC image is built
-        if direct and self.bf16:
-            x0 = torch.empty(V, B, H, W // 4, 64, dtype=self.act_dtype, device=dev)
-        elif direct:
-            x0 = ops.sp_empty(V, B, H, W // 2, 32, device=dev)
-            x0.sinv = None
-        else:
-            x0 = torch.empty(V, B, H, W, 8 if self.bf16 else 4, dtype=self.act_dtype, device=dev)
-        for v, im in enumerate(imgs):
-            assert im.shape == imgs[0].shape and im.is_cuda and im.dtype == imgs[0].dtype
-            if direct:
-                assert im.dtype == torch.float32
-                if self.bf16:
-                    ops.stem_rowwindow_bf16(im.detach().contiguous(), x0[v])
-                else:
-                    ops.stem_rowwindow_split_nchw(im.detach().contiguous(), x0[v])
-            elif self.bf16 and raw:             # inference: one launch per view, no fp32 image in between
-                ops.preprocess_u8hwc_resize_bf16(im.contiguous(), x0[v], B, Hin, Win, H, W, IMAGE_MEAN, IMAGE_STD, input_bgr)
-            elif self.bf16:
-                assert im.dtype == torch.float32
-                ops.nchw_to_nhwc8_bf16(im.detach().contiguous(), x0[v], B, 3, H, W)
-            elif raw:
-                ops.preprocess_u8hwc_resize(im.contiguous(), x0[v], B, Hin, Win, H, W, IMAGE_MEAN, IMAGE_STD, input_bgr)
-            else:
-                assert im.dtype == torch.float32
-                ops.nchw_to_nhwc4(im.detach().contiguous(), x0[v], B, 3, H, W)
-        if self._stem_rw and not direct:                # raw uint8 input: windows from the normalised NHWC4 image
-            x0 = ops.stem_rowwindow_split(x0)
+        x0 = self._input_layout(imgs, B, H, W, input_bgr)
         self._wprep = None
         if training:
             self.invalidate_weight_cache()       # the weights are about to change: drop the inference copies
@@ -577,46 +595,13 @@ class Backbone:
         tape: Optional[dict] = {"units": [], "blocks": [], "V": V, "B": B} if keep_tape else None
         if keep_tape and self._wprep is not None:
             tape["wprep_versions"] = self._wprep_versions
-        ulist = tape["units"] if keep_tape else None
         if training:
             torch._foreach_add_(self.bn_count_buffers(), V)       # num_batches_tracked += 1 per view call
-        s = self.spec
-        x, argmax = self._unit_fwd(s.stem, x0, V, B, H, W, training, True, None, ulist, pool=True)
+        if training or keep_tape or (self.bf16 and not self.bf16_fold_eval):
+            x = self._forward_taped(x0, V, B, H, W, training, tape)
+        else:
+            x = self._forward_infer(x0, V, B, H, W)
         Hc, Wc = x.shape[2], x.shape[3]
-        pending = None        # the previous block's apply pass, when this block's first conv forms its own input
-        for bi, blk in enumerate(s.blocks):
-            first = len(ulist) if keep_tape else 0
-            identity = x
-            out = x
-            h, w = Hc, Wc
-            for c in blk.convs[:-1]:
-                # (conv1 runs before the downsample branch and before anything else that reads the block input)
-                out = self._unit_fwd(c, out, V, B, h, w, training, True, None, ulist, pending_apply=pending)
-                pending = None
-                h, w = out.shape[2], out.shape[3]
-            ds_idx = None
-            ident_affine = None
-            if blk.downsample is not None:
-                if training or keep_tape or (self.bf16 and not self.bf16_fold_eval):
-                    # raw downsample conv output + its (scale, shift): normalised inside the last unit's bn_apply
-                    identity, ident_affine = self._unit_fwd(blk.downsample, x, V, B, Hc, Wc, training, False, None, ulist,
-                                                            defer_apply=True)
-                else:
-                    identity = self._unit_fwd(blk.downsample, x, V, B, Hc, Wc, training, False, None, ulist)
-                ds_idx = len(ulist) - 1 if keep_tape else None
-            nxt = s.blocks[bi + 1].convs[0] if bi + 1 < len(s.blocks) else None
-            if nxt is not None and training and not self.bf16:
-                out, pending = self._unit_fwd(blk.convs[-1], out, V, B, h, w, training, True, identity, ulist,
-                                              residual_affine=ident_affine, next_conv=nxt)
-            else:
-                out = self._unit_fwd(blk.convs[-1], out, V, B, h, w, training, True, identity, ulist,
-                                     residual_affine=ident_affine)
-            if keep_tape:
-                n_main = len(blk.convs)
-                idx = list(range(first, first + n_main - 1)) + [len(ulist) - 1]
-                tape["blocks"].append((idx, ds_idx))
-            x = out
-            Hc, Wc = out.shape[2], out.shape[3]
         feat = torch.empty(V, B, self.fc_dim, dtype=torch.float32, device=dev)
         if x.dtype == torch.float16:                                # sp activation of the split path
             ops.avgpool_fwd_split(x, feat, V * B, Hc * Wc, self.fc_dim)
@@ -626,7 +611,63 @@ class Backbone:
             tape["final_hw"] = (Hc, Wc)
         return feat, tape
 
+    def _forward_infer(self, x0: Tensor, V: int, B: int, H: int, W: int) -> Tensor:
+        """Stem and residual blocks of the folded inference forward (see _unit_infer), in the order csrc/session_plan.cpp
+        states: conv1 up to the last conv, the downsample branch as a normalised residual, the last conv with residual + ReLU."""
+        s = self.spec
+        if self.bf16:         # the bf16 stem keeps the training-shaped launches: conv, then BatchNorm + ReLU + max pool in one pass
+            x = self._unit_fwd(s.stem, x0, V, B, H, W, False, True, None, None, pool=True).out
+        else:
+            x = self._unit_infer(s.stem, x0, V, B, H, W, True, None, pool=True)
+        for blk in s.blocks:
+            out = x
+            for c in blk.convs[:-1]:
+                out = self._unit_infer(c, out, V, B, out.shape[2], out.shape[3], True, None)
+            identity = x
+            if blk.downsample is not None:
+                identity = self._unit_infer(blk.downsample, x, V, B, x.shape[2], x.shape[3], False, None)
+            x = self._unit_infer(blk.convs[-1], out, V, B, out.shape[2], out.shape[3], True, identity)
+        return x
+
+    def _forward_taped(self, x0: Tensor, V: int, B: int, H: int, W: int, training: bool, tape: Optional[dict]) -> Tensor:
+        """Stem and residual blocks through _unit_fwd: training, eval mode with a tape, and (tape None) unfolded bf16
+        inference.  Fills tape["units"] / tape["blocks"]."""
+        s = self.spec
+        ulist = tape["units"] if tape is not None else None
+        x = self._unit_fwd(s.stem, x0, V, B, H, W, training, True, None, ulist, pool=True).out
+        pending = None        # the previous block's apply pass, when this block's first conv forms its own input
+        for bi, blk in enumerate(s.blocks):
+            first = len(ulist) if ulist is not None else 0
+            identity, ident_affine, ds_idx = x, None, None
+            out = x
+            for c in blk.convs[:-1]:
+                # (conv1 runs before the downsample branch and before anything else that reads the block input)
+                out = self._unit_fwd(c, out, V, B, out.shape[2], out.shape[3], training, True, None, ulist, pending_apply=pending).out
+                pending = None
+            if blk.downsample is not None:
+                # raw downsample conv output + its (scale, shift): normalised inside the last unit's bn_apply
+                identity, ident_affine, _ = self._unit_fwd(blk.downsample, x, V, B, x.shape[2], x.shape[3], training, False,
+                                                           None, ulist, defer_apply=True)
+                ds_idx = len(ulist) - 1 if ulist is not None else None
+            nxt = s.blocks[bi + 1].convs[0] if (bi + 1 < len(s.blocks) and training and not self.bf16) else None
+            x, _, pending = self._unit_fwd(blk.convs[-1], out, V, B, out.shape[2], out.shape[3], training, True, identity, ulist,
+                                           residual_affine=ident_affine, next_conv=nxt)
+            if ulist is not None:
+                tape["blocks"].append((list(range(first, first + len(blk.convs) - 1)) + [len(ulist) - 1], ds_idx))
+        return x
+
     # ---------------------------------------------------------------- backward
+    def _bn_params(self, c: ConvSpec, sink: GradSink):
+        """(gamma, beta, accumulate): the BatchNorm parameters of unit ``c`` and whether their gradients are added to."""
+        gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
+        acc = sink.accumulate(gp)
+        assert acc == sink.accumulate(bp)
+        return gp, bp, acc
+
+    def _unit_params(self, c: ConvSpec) -> List[torch.nn.Parameter]:
+        """The parameters whose gradients are final once unit ``c``'s backward is queued (GradSink.publish)."""
+        return [self.p[c.name + ".weight"], self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]]
+
     def _bn_bwd(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink, defer_apply: bool = False):
         """g = grad wrt the unit's output.  Returns (dy, dz): dy = grad wrt the conv output;
         dz = g masked by the unit's ReLU (written in place into g) when the residual branch needs it.
@@ -636,7 +677,7 @@ class Backbone:
             return self._bn_bwd_eval(u, g, need_dz, sink)
         c = u.spec
         G = u.y.shape[0]
-        gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
+        gp, bp, acc = self._bn_params(c, sink)
         if u.fused_s12 is not None and u.split:
             # split path, fused: g arrived masked and the sums came with it; dy goes out in sp
             (s12, sinv), u.fused_s12 = u.fused_s12, None
@@ -644,8 +685,8 @@ class Backbone:
             if defer_apply:
                 dy.sinv = sinv
                 dy.bn_apply = (g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], u.rows)
-                return dy, (g if need_dz else None)
-            ops.bn_bwd_apply_split(g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, None, s12[2], sinv)
+            else:
+                ops.bn_bwd_apply_split(g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, None, s12[2], sinv)
             return dy, (g if need_dz else None)
         if u.fused_s12 is not None:
             # g arrived masked by this unit's ReLU and its sums (incl. dgamma / dbeta) came with it
@@ -656,38 +697,31 @@ class Backbone:
         s12 = torch.empty(3 if u.split else 2, G, c.cout, dtype=torch.float32, device=g.device)     # s1, s2 (, max |dz| per channel)
         ra = u.relu_affine
         act = u.out if (u.relu and ra is None) else None
-        acc = sink.accumulate(gp)
-        assert acc == sink.accumulate(bp)
         if u.split:
             # split path: g and y are fp32, dy goes to the conv kernels in sp; residual units carry their mask as bits.
             # No pass here reads the (scaled) sp activation: the mask comes from the bits or from fma(y, scale, shift) > 0,
             # both decided on the unscaled value
             assert not (u.relu and ra is None) or u.relu_bits is not None
             sinv = torch.empty(1, dtype=torch.float32, device=g.device)       # dy's 2^-k: left by the reduce pass's finalize launch
-            if u.relu_bits is not None:
-                ops.bn_bwd_reduce_split(g, u.relu_bits, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp),
-                                        sink.view(bp), acc, s12[2], None, dz_out=g, gamma=gp.detach(), dy_sinv=sinv)
-            else:
-                ops.bn_bwd_reduce_split(g, None, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp),
-                                        sink.view(bp), acc, s12[2], ra, gamma=gp.detach(), dy_sinv=sinv)
+            bits = u.relu_bits
+            ra = None if bits is not None else ra                 # one mask source; with bits the reduce pass leaves dz in g
+            ops.bn_bwd_reduce_split(g, bits, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp), sink.view(bp),
+                                    acc, s12[2], ra, dz_out=g if bits is not None else None, gamma=gp.detach(), dy_sinv=sinv)
             dy = ops.sp_empty(*u.y.shape, device=g.device)
-            ops.bn_bwd_apply_split(g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy,
-                                   None if u.relu_bits is not None else ra, s12[2], sinv)
+            ops.bn_bwd_apply_split(g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, ra, s12[2], sinv)
             return dy, (g if need_dz else None)
+        # need_dz: the reduce pass writes the masked gradient dz over g: the apply pass then reads (dz, y) only - no
+        # second look at the ReLU mask, no second dz store - and the residual branch takes dz from g
+        if need_dz and u.relu_bits is not None:
+            ops.bn_bwd_reduce_bits(g, u.relu_bits, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp),
+                                   sink.view(bp), acc, dz_out=g)
+        else:
+            ops.bn_bwd_reduce(g, act, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp), sink.view(bp),
+                              acc, ra, dz_out=g if need_dz else None)
         if need_dz:
-            # the reduce pass writes the masked gradient dz over g: the apply pass then reads (dz, y) only - no
-            # second look at the ReLU mask, no second dz store - and the residual branch takes dz from g
-            if u.relu_bits is not None:
-                ops.bn_bwd_reduce_bits(g, u.relu_bits, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp),
-                                       sink.view(bp), acc, dz_out=g)
-            else:
-                ops.bn_bwd_reduce(g, act, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp),
-                                  sink.view(bp), acc, ra, dz_out=g)
             dy = torch.empty_like(g)
             ops.bn_bwd_apply(g, None, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, None, None)
             return dy, g
-        ops.bn_bwd_reduce(g, act, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp), sink.view(bp),
-                          acc, ra)
         ops.bn_bwd_apply(g, act, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, g, None, ra)
         return g, None
 
@@ -697,10 +731,8 @@ class Backbone:
         the kernel takes the running statistics, and the ReLU mask from where the forward left it."""
         c = u.spec
         G = u.y.shape[0]
-        gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
+        gp, bp, acc = self._bn_params(c, sink)
         rm, rv = self.p[c.bn + ".running_mean"], self.p[c.bn + ".running_var"]
-        acc = sink.accumulate(gp)
-        assert acc == sink.accumulate(bp)
         if u.relu_bits is not None:
             mask = {"relu_bits": u.relu_bits}
         elif u.relu_affine is not None:
@@ -732,13 +764,12 @@ class Backbone:
 
     def _conv_bwd(self, u: _Unit, dy: Tensor, need_dx: bool, addend: Optional[Tensor], sink: GradSink,
                   fuse_for: Optional[_Unit] = None):
+        dx = None
         if getattr(dy, "bn_apply", None) is not None:
             # dy does not exist yet: the backward-data launch forms it and writes it, then the weight gradient reads it
             dx = torch.empty(ops.sp_shape(u.x_in), dtype=torch.float32, device=dy.device)
             self._dgrad(u, dy, dx, addend, fuse_for, sink)
             need_dx = False
-        else:
-            dx = None
         if self.overlap_wgrad and dy.is_cuda:
             side = self._side(dy.device)
             side.wait_stream(torch.cuda.current_stream())         # dy (and everything before it) is ready
@@ -767,30 +798,29 @@ class Backbone:
         elif u.stem_rw and self.bf16:
             dw16 = torch.empty(2 * c.cout, 7, 16, 4, dtype=torch.float32, device=dy.device)
             ops.stem_wgrad_bf16(u.desc, u.x_in, dy, dw16, False)
-            gv = sink.view(wp).permute(0, 2, 3, 1)                    # [cout, 7, 7, 3] view of the gradient
-            if sink.accumulate(wp):
-                gv.add_(dw16[:c.cout, :, 1:8, :3])
-            else:
-                gv.copy_(dw16[:c.cout, :, 1:8, :3])
-            gv.add_(dw16[c.cout:, :, 3:10, :3])                       # the odd output columns' taps
+            self._stem_grad(wp, sink, dw16[:c.cout, :, 1:8, :3], dw16[c.cout:, :, 3:10, :3])    # (second: the odd output columns' taps)
         elif u.stem_rw:
             dw8 = torch.empty(c.cout, 7, 8, 4, dtype=torch.float32, device=dy.device)
             ops.stem_wgrad_split(u.desc, u.x_in, dy, dw8, False)
-            gv = sink.view(wp).permute(0, 2, 3, 1)                    # [cout, 7, 7, 3] view of the gradient
-            if sink.accumulate(wp):
-                gv.add_(dw8[:, :, 1:, :3])
-            else:
-                gv.copy_(dw8[:, :, 1:, :3])
+            self._stem_grad(wp, sink, dw8[:, :, 1:, :3])
         elif c.cin == 3:
             dw4 = torch.empty(c.cout, c.k, c.k, u.desc.cin, dtype=torch.float32, device=dy.device)
             ops.conv_wgrad(u.desc, u.x_in, dy, dw4, False)
-            gv = sink.view(wp).permute(0, 2, 3, 1)
-            if sink.accumulate(wp):
-                gv.add_(dw4[..., :3])
-            else:
-                gv.copy_(dw4[..., :3])
+            self._stem_grad(wp, sink, dw4[..., :3])
         else:
             ops.conv_wgrad(u.desc, u.x_in, dy, sink.view(wp), sink.accumulate(wp), defer=self._wg_defer if self.bf16 else None)
+
+    @staticmethod
+    def _stem_grad(wp: torch.nn.Parameter, sink: GradSink, dw: Tensor, dw_odd: Optional[Tensor] = None):
+        """The stem's weight gradient, computed into a padded buffer, into the parameter's gradient: ``dw`` (and ``dw_odd``,
+        the second filter copy of the bf16 two-parity form) are [cout, 7, 7, 3] slices of that buffer."""
+        gv = sink.view(wp).permute(0, 2, 3, 1)                        # [cout, 7, 7, 3] view of the gradient
+        if sink.accumulate(wp):
+            gv.add_(dw)
+        else:
+            gv.copy_(dw)
+        if dw_odd is not None:
+            gv.add_(dw_odd)
 
     def _flush_wgrad_reduces(self, dev):
         """The slab sums of the weight gradients launched since the last flush, in one launch on the stream that wrote the slabs."""
@@ -812,9 +842,7 @@ class Backbone:
         if (self.bf16 and U is not None and self.fuse_bn_split and u.spec.cin != 3 and u.desc.cin % 64 == 0 and u.desc.cout % 64 == 0
                 and (not U.relu or U.relu_bits is not None or U.relu_affine is not None)):     # (relu_bits off: mask from the activation)
             c = U.spec
-            gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
-            acc = sink.accumulate(gp)
-            assert acc == sink.accumulate(bp)
+            gp, bp, acc = self._bn_params(c, sink)
             s12 = torch.empty(2, dx.shape[0], c.cout, dtype=torch.float32, device=dx.device)
             ops.conv_dgrad_bf16_bnreduce(u.desc, dy, u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd,
                                          None if U.relu_bits is not None else U.relu_affine, s12[0], s12[1], sink.view(gp),
@@ -824,100 +852,36 @@ class Backbone:
         if u.split:
             if U is not None and U.split and self.fuse_bn_split:
                 c = U.spec
-                gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
-                acc = sink.accumulate(gp)
-                assert acc == sink.accumulate(bp)
+                gp, bp, acc = self._bn_params(c, sink)
                 # (the fused reduce epilogue masks with U's bits or fma(U.y, scale, shift) > 0: no sp activation is read)
                 s12 = torch.empty(3, dx.shape[0], c.cout, dtype=torch.float32, device=dx.device)     # s1, s2, max |dz| per channel
                 sinv = torch.empty(1, dtype=torch.float32, device=dx.device)      # 2^-k of the dy that U's apply pass will write
+                ra = None if U.relu_bits is not None else U.relu_affine
                 pend = getattr(dy, "bn_apply", None)
                 if pend is not None:
                     dz, y, mean, invstd, gamma, us1, us2, rows = pend
                     dy.bn_apply = None
                     ops.conv_dgrad_split_bnapply_bnreduce(u.desc, dy, dy.sinv, dz, y, mean, invstd, gamma, us1, us2, rows, u.w, dx,
-                                                          addend, U.y, U.relu_bits, U.mean, U.invstd,
-                                                          None if U.relu_bits is not None else U.relu_affine, s12[0], s12[1],
+                                                          addend, U.y, U.relu_bits, U.mean, U.invstd, ra, s12[0], s12[1],
                                                           sink.view(gp), sink.view(bp), acc, s12[2], gp.detach(), sinv)
-                    U.fused_s12 = (s12, sinv)
-                    return
-                ops.conv_dgrad_split_bnreduce(u.desc, dy, u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd,
-                                              None if U.relu_bits is not None else U.relu_affine, s12[0], s12[1], sink.view(gp),
-                                              sink.view(bp), acc, s12[2], gp.detach(), sinv)
-                U.fused_s12 = (s12, sinv)
-                return
-            ops.conv_dgrad_split(u.desc, dy, u.w, dx, addend)
-            return
-        ops.conv_dgrad(u.desc, dy, u.w, dx, None, addend)
-
-    def backward(self, tape: dict, dfeat: Tensor, sink: GradSink, need_dimg: bool = False):
-        """dfeat [V,B,fc_dim] -> parameter gradients into ``sink`` (published layer4 ... stem, the
-        order they become final); returns d(img) as V NCHW tensors when need_dimg."""
-        V, B = tape["V"], tape["B"]
-        units: List[_Unit] = tape["units"]
-        if self.bf16 and not all(u.trained for u in units):
-            raise NotImplementedError("backward through eval-mode BatchNorm (running statistics) is not implemented on the "
-                                      "bf16 path: call model.train() for gradient steps, or use the fp32 model")
-        Hc, Wc = tape["final_hw"]
-        if need_dimg and self.bf16:
-            raise NotImplementedError("d(loss)/d(img) is not produced by the bf16 path")
-        if tape.get("wprep_versions") is not None and tape["wprep_versions"] != getattr(self, "_wprep_versions", None):
-            raise RuntimeError("backward of a tape whose bf16 / sp weight copies were overwritten by a later forward with "
-                               "DIFFERENT weights (forward, optimizer step, forward, then backward of the first call): "
-                               "backward-data would run with the new weights.  Run backward before the weights change "
-                               "(PyTorch raises its version-counter error in the same situation)")
-        g = torch.empty(V, B, Hc, Wc, self.fc_dim, dtype=self.act_dtype, device=dfeat.device)
-        ops.avgpool_bwd(dfeat.contiguous(), g, V * B, Hc * Wc, self.fc_dim)
-        self._wg_defer = []
-        P = self.p
-        blocks = tape["blocks"]
-        for bi in range(len(blocks) - 1, -1, -1):
-            idx, ds_idx = blocks[bi]
-            last = units[idx[-1]]
-            # the unit that receives this block's input gradient: the previous block's last unit (the stem's
-            # fused pool backward takes it for the first block)
-            prev_last = units[blocks[bi - 1][0][-1]] if bi > 0 else None
-            done: List[torch.nn.Parameter] = []
-            below = units[idx[-2]]
-            merge = self.fuse_bn_apply_dgrad and bn_apply_dgrad_eligible(
-                last.spec, split=last.split and not self.bf16, trained=last.trained, fused_in=last.fused_s12 is not None,
-                carries_reduce=below.split and self.fuse_bn_split, need_dimg=need_dimg)
-            dy, dz = self._bn_bwd(last, g, True, sink, defer_apply=merge)
-            d = self._conv_bwd(last, dy, True, None, sink, fuse_for=below)
-            done += [P[last.spec.name + ".weight"], P[last.spec.bn + ".weight"], P[last.spec.bn + ".bias"]]
-            last.y = last.out = None
-            del dy
-            for k in range(len(idx) - 2, -1, -1):
-                u = units[idx[k]]
-                dy, _ = self._bn_bwd(u, d, False, sink)
-                if k == 0:
-                    # with a downsample branch the block-input gradient is final only after that branch's launch
-                    d = self._conv_bwd(u, dy, True, dz if ds_idx is None else None, sink,
-                                       fuse_for=prev_last if ds_idx is None else None)
                 else:
-                    d = self._conv_bwd(u, dy, True, None, sink, fuse_for=units[idx[k - 1]])
-                done += [P[u.spec.name + ".weight"], P[u.spec.bn + ".weight"], P[u.spec.bn + ".bias"]]
-                u.y = u.out = None
-            if ds_idx is not None:
-                ud = units[ds_idx]
-                dyd, _ = self._bn_bwd(ud, dz, False, sink)
-                self._conv_bwd(ud, dyd, False, None, sink)                # wgrad only
-                self._dgrad(ud, dyd, d, d, prev_last, sink)               # d += dgrad (aliasing addend): now final
-                done += [P[ud.spec.name + ".weight"], P[ud.spec.bn + ".weight"], P[ud.spec.bn + ".bias"]]
-                ud.y = ud.out = None
-            self._flush_wgrad_reduces(g.device)               # this block's weight gradients are final once their slabs are summed
-            sink.publish(done)
-            g = d
-            if "debug" in tape:
-                tape["debug"].append(g.clone())
-        # stem: max pool + ReLU + BatchNorm backward fused (the 112x112 gradient map is never built)
-        stem = units[0]
+                    ops.conv_dgrad_split_bnreduce(u.desc, dy, u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd, ra, s12[0], s12[1],
+                                                  sink.view(gp), sink.view(bp), acc, s12[2], gp.detach(), sinv)
+                U.fused_s12 = (s12, sinv)
+            else:
+                ops.conv_dgrad_split(u.desc, dy, u.w, dx, addend)
+        else:
+            ops.conv_dgrad(u.desc, dy, u.w, dx, None, addend)
+
+    def _stem_bn_bwd(self, stem: _Unit, g: Tensor, V: int, B: int, sink: GradSink) -> Tensor:
+        """The stem's max pool + ReLU + BatchNorm backward, fused (the 112x112 gradient map is never built): g = grad wrt
+        the pooled map; returns dy = grad wrt the stem conv's output."""
         argmax, scale, shift, H1, W1, Hp, Wp = stem.pool
         sc = stem.spec
-        gp, bp = P[sc.bn + ".weight"], P[sc.bn + ".bias"]
+        P = self.p
+        gp, bp, acc = self._bn_params(sc, sink)
         stem_sp = stem.stem_rw and not self.bf16
         s12 = torch.empty(3 if stem_sp else 2, V, sc.cout, dtype=torch.float32, device=g.device)
-        acc = sink.accumulate(gp)
-        assert acc == sink.accumulate(bp)
         if not stem.trained:
             # eval mode: max pool + ReLU + BatchNorm on the running statistics, one pass (no batch sums to wait for)
             dy = torch.empty_like(stem.y)
@@ -938,10 +902,73 @@ class Backbone:
             dy = torch.empty_like(stem.y)
             ops.bn_relu_maxpool_bwd_apply(g, argmax, stem.y, stem.mean, stem.invstd, gp.detach(), scale, shift, s12[0], s12[1],
                                           V, B, H1, W1, sc.cout, Hp, Wp, dy)
+        return dy
+
+    def backward(self, tape: dict, dfeat: Tensor, sink: GradSink, need_dimg: bool = False):
+        """dfeat [V,B,fc_dim] -> parameter gradients into ``sink`` (published layer4 ... stem, the
+        order they become final); returns d(img) as V NCHW tensors when need_dimg."""
+        V, B = tape["V"], tape["B"]
+        units: List[_Unit] = tape["units"]
+        if self.bf16 and not all(u.trained for u in units):
+            raise NotImplementedError("backward through eval-mode BatchNorm (running statistics) is not implemented on the "
+                                      "bf16 path: call model.train() for gradient steps, or use the fp32 model")
+        Hc, Wc = tape["final_hw"]
+        if need_dimg and self.bf16:
+            raise NotImplementedError("d(loss)/d(img) is not produced by the bf16 path")
+        if tape.get("wprep_versions") is not None and tape["wprep_versions"] != getattr(self, "_wprep_versions", None):
+            raise RuntimeError("backward of a tape whose bf16 / sp weight copies were overwritten by a later forward with "
+                               "DIFFERENT weights (forward, optimizer step, forward, then backward of the first call): "
+                               "backward-data would run with the new weights.  Run backward before the weights change "
+                               "(PyTorch raises its version-counter error in the same situation)")
+        g = torch.empty(V, B, Hc, Wc, self.fc_dim, dtype=self.act_dtype, device=dfeat.device)
+        ops.avgpool_bwd(dfeat.contiguous(), g, V * B, Hc * Wc, self.fc_dim)
+        self._wg_defer = []
+        blocks = tape["blocks"]
+        for bi in range(len(blocks) - 1, -1, -1):
+            idx, ds_idx = blocks[bi]
+            last = units[idx[-1]]
+            # the unit that receives this block's input gradient: the previous block's last unit (the stem's
+            # fused pool backward takes it for the first block)
+            prev_last = units[blocks[bi - 1][0][-1]] if bi > 0 else None
+            done: List[torch.nn.Parameter] = []
+            below = units[idx[-2]]
+            merge = self.fuse_bn_apply_dgrad and bn_apply_dgrad_eligible(
+                last.spec, split=last.split and not self.bf16, trained=last.trained, fused_in=last.fused_s12 is not None,
+                carries_reduce=below.split and self.fuse_bn_split, need_dimg=need_dimg)
+            dy, dz = self._bn_bwd(last, g, True, sink, defer_apply=merge)
+            d = self._conv_bwd(last, dy, True, None, sink, fuse_for=below)
+            done += self._unit_params(last.spec)
+            last.y = last.out = None
+            del dy
+            for k in range(len(idx) - 2, -1, -1):
+                u = units[idx[k]]
+                dy, _ = self._bn_bwd(u, d, False, sink)
+                if k == 0:
+                    # with a downsample branch the block-input gradient is final only after that branch's launch
+                    d = self._conv_bwd(u, dy, True, dz if ds_idx is None else None, sink,
+                                       fuse_for=prev_last if ds_idx is None else None)
+                else:
+                    d = self._conv_bwd(u, dy, True, None, sink, fuse_for=units[idx[k - 1]])
+                done += self._unit_params(u.spec)
+                u.y = u.out = None
+            if ds_idx is not None:
+                ud = units[ds_idx]
+                dyd, _ = self._bn_bwd(ud, dz, False, sink)
+                self._conv_bwd(ud, dyd, False, None, sink)                # wgrad only
+                self._dgrad(ud, dyd, d, d, prev_last, sink)               # d += dgrad (aliasing addend): now final
+                done += self._unit_params(ud.spec)
+                ud.y = ud.out = None
+            self._flush_wgrad_reduces(g.device)               # this block's weight gradients are final once their slabs are summed
+            sink.publish(done)
+            g = d
+            if "debug" in tape:
+                tape["debug"].append(g.clone())
+        stem = units[0]
+        dy = self._stem_bn_bwd(stem, g, V, B, sink)
         dx0 = self._conv_bwd(stem, dy, need_dimg, None, sink)
         self._flush_wgrad_reduces(g.device)
         self._wg_defer = None
-        sink.publish([P[stem.spec.name + ".weight"], P[stem.spec.bn + ".weight"], P[stem.spec.bn + ".bias"]])
+        sink.publish(self._unit_params(stem.spec))
         if self._wg_stream is not None and dy.is_cuda and (self.overlap_wgrad or not torch.cuda.is_current_stream_capturing()):
             torch.cuda.current_stream().wait_stream(self._wg_stream)      # gradients complete for the optimizer
         if not need_dimg:

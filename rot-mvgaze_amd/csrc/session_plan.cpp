@@ -2,9 +2,10 @@
 // No HIP here, like pair_index.cpp: this file compiles and runs stand-alone (tests/native/session_plan_check.cpp).
 //
 // The plan restates, as data, what the Python module decides per call for model.eval() under torch.no_grad() on the fp32
-// path: arch.py's layer table, Backbone.forward's 2 GiB guard and unit order (backbone.py: conv1.., downsample, last conv with
-// the residual), FusionHead.forward's choice between the generated-input fp32-MFMA Linears and _forward_split (heads.py:
-// D * B >= 1024 rows).  Every step is one call of an existing entry point; session.hip executes them.
+// path: arch.py's layer table, Backbone.forward's 2 GiB guard, Backbone._unit_infer's launches per unit and
+// Backbone._forward_infer's unit order (backbone.py: conv1.., downsample, last conv with the residual), FusionHead.forward's
+// choice between the generated-input fp32-MFMA Linears and _forward_split (heads.py: D * B >= 1024 rows).  Every step is one
+// call of an existing entry point; session.hip executes them.
 #include <limits.h>
 #include <stdio.h>
 #include <string.h>
@@ -411,7 +412,8 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
     }
   }
 
-  // ---- residual blocks.  unit(): conv + folded BatchNorm (+ residual) (+ ReLU) in one launch
+  // ---- residual blocks.  unit(): conv + folded BatchNorm (+ residual) (+ ReLU) in one launch = Backbone._unit_infer (fp32-MFMA
+  // and split forms); the block loop below = Backbone._forward_infer.  A change to either is made in backbone.py too
   bool bad_size = false;
   auto unit = [&](int ci, const Act &in, bool relu, const Act *residual) {
     const ConvSpec &cs = convs[ci].s;
