@@ -560,6 +560,18 @@ int mvg_conv_fprop_split(const mvg_conv_desc *d, const void *x_sp, const float *
 int mvg_conv_fprop_split_affine(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *w_sp, const float *w_sinv,
                                 void *out, int out_sp, const float *scale, const float *shift, const void *residual,
                                 int residual_sp, int relu, void *stream);
+/* The guarded inference forward (see "Inference on the split kernels" below): the launch above with an sp output
+ * (out_sp != 0 is required) plus the activation RANGE RECORD of what it stores.  *range_word (required; device memory;
+ * cleared by the caller before the forward) receives, by an unsigned-integer atomic max, the largest bit pattern of |v|
+ * over the stored elements, v being the fp32 value handed to the fp16 split - after scale, shift, residual and ReLU.  The
+ * integer order is the float order for non-negative floats and ranks inf / NaN above every finite value.  The tensor has
+ * overflowed iff the word is >= 0x477FF000 (|v| >= 65520.0f: where fp16 round-to-nearest-even gives inf).  Rows and columns
+ * beyond the map's edge take no part.  Same tiles, launch plan and output bits as mvg_conv_fprop_split_affine.
+ * mvg_split_f32_ranged: mvg_split_f32 plus the same record (the stem's pooled map). */
+int mvg_conv_fprop_split_affine_ranged(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *w_sp,
+                                       const float *w_sinv, void *out, int out_sp, const float *scale, const float *shift,
+                                       const void *residual, int residual_sp, int relu, uint32_t *range_word, void *stream);
+int mvg_split_f32_ranged(const float *x, void *out_sp, int64_t n, float scale, uint32_t *range_word, void *stream);
 /* relu_mask_sp (may be NULL; stride-1 launches): an sp tensor shaped like dx - dx is zeroed where it is <= 0 (the ReLU of a
  * Linear's hidden layer, whose activation the forward wrote in sp) */
 int mvg_conv_dgrad_split(const mvg_conv_desc *d, const void *dy_sp, const float *dy_sinv, const void *w_crsk_sp,
@@ -606,8 +618,12 @@ int mvg_avgpool_fwd_split(const void *x_sp, float *y, int n, int hw, int c, void
  *   exactly the argument checks they had): out_sinv / pooled_sinv of the tensor written, res_sinv of an sp identity, x_sinv of the tensor read
  *   (the conv forward takes it as mvg_conv_fprop_split's x_sinv).  The ReLU mask bits are decided on the unscaled value.
  *   Readers that use an sp activation only for its SIGN (relu_mask_sp, the backward's mask forms) need no scale.
- * Inference on the split kernels (mvg_conv_fprop_split_affine) has no z-score bound - running statistics - and stays
- * unscaled: |activation| must stay below 65 504 there. */
+ * Inference on the split kernels (mvg_conv_fprop_split_affine) has no z-score bound - running statistics give none, and a
+ * bound chained from the input grows by every layer's L1 gain - and stays unscaled: an activation that reaches 65 520 is
+ * stored as inf and merges to NaN, which a later ReLU can turn into 0.  The caller who cannot vouch for the checkpoint
+ * runs the guarded forward instead: mvg_conv_fprop_split_affine_ranged / mvg_split_f32_ranged leave one range word per sp
+ * tensor (same launches, same output bits), and a word >= 0x477FF000 says that tensor overflowed - rerun on the fp32-MFMA
+ * kernels (mvg_conv_fprop_affine; Backbone.split_eval_guard = "fallback" does that, mvg_session_set_range_record reports). */
 int mvg_act_scales(const void *items_dev, int n, float *slots, int n_slots, void *stream);
 int mvg_bn_apply_split_scaled(const float *y, const float *scale, const float *shift, const void *residual, int residual_sp,
                               const float *res_scale, const float *res_shift, const float *res_sinv, int relu, void *out_sp,
@@ -802,6 +818,18 @@ int mvg_session_bind(mvg_session *s, const void *const *host_tensor_ptrs, void *
  * [views][batch][3][512], feats [I][D][batch][3][512], preds [I][D][batch][2]. */
 int mvg_session_forward(mvg_session *s, const void *const *host_view_ptrs, const float *rot, float *img_feat, float *lifted,
                         float *feats, float *preds, void *stream);
+/* The activation range record of a session whose backbone runs on the split kernels (mvg_conv_fprop_split_affine_ranged):
+ * one 32-bit word per sp tensor the forward stores - the stem's pooled map (named by the stem's conv), then every block
+ * conv in forward order; the downsample branches stay fp32 and have none.  _num_range_units (host only): how many, 0 when
+ * the backbone is not on the split kernels (split = 0, or the 2 GiB guard); _range_unit_name (host only): the conv's
+ * state_dict prefix, NULL out of range.  _set_range_record (host only: the pointer is only stored): record_dev = device
+ * memory of _num_range_units words, or NULL (the default) for no record.  With a record mvg_session_forward clears it with
+ * one stream-ordered memset and calls the ranged entry points: same mvg_session_launches, same outputs, still no
+ * synchronisation and no allocation.  There is no fallback inside a session: a caller who reads a word >= 0x477FF000
+ * builds a split = 0 session. */
+int mvg_session_num_range_units(const mvg_session *s);
+const char *mvg_session_range_unit_name(const mvg_session *s, int i);
+int mvg_session_set_range_record(mvg_session *s, uint32_t *record_dev);
 
 #ifdef __cplusplus
 }

@@ -208,6 +208,12 @@ SIGNATURES = {
     "mvg_session_launches": (_I, [_P]),
     "mvg_session_bind": (_I, [_P, C.POINTER(_P), _P, C.c_size_t, _P]),
     "mvg_session_forward": (_I, [_P, C.POINTER(_P), _P, _P, _P, _P, _P, _P]),
+    # activation range record of the guarded inference forward (Backbone.split_eval_guard, InferenceSession(range_record=True))
+    "mvg_conv_fprop_split_affine_ranged": (_I, [_D, _P, _P, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
+    "mvg_split_f32_ranged": (_I, [_P, _P, _I64, _F, _P, _P]),
+    "mvg_session_num_range_units": (_I, [_P]),
+    "mvg_session_range_unit_name": (C.c_char_p, [_P, _I]),
+    "mvg_session_set_range_record": (_I, [_P, _P]),
 }
 
 _lib = None

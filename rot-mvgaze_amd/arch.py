@@ -87,6 +87,17 @@ def backbone_spec(depth: int, prefix: str = "_feat_extractor.0.") -> BackboneSpe
     return spec
 
 
+def range_unit_names(depth: int, prefix: str = "_feat_extractor.0.") -> List[str]:
+    """The sp tensors the folded inference forward stores on the split kernels, in forward order, each named by the conv whose
+    unit writes it: the stem's conv for the pooled map, then every block conv.  The downsample branches stay fp32 and are
+    not listed.  One word of the activation range record each (Backbone.split_eval_guard, mvg_session_range_unit_name)."""
+    spec = backbone_spec(depth, prefix)
+    return [spec.stem.name] + [c.name for b in spec.blocks for c in b.convs]
+
+
+RANGE_OVER_BITS = 0x477FF000      # bits of 65520.0f: from here fp16 round-to-nearest-even gives inf
+
+
 def mlp_names(prefix: str, n_layers: int) -> List[str]:
     return [f"{prefix}blocks.{i}.0" for i in range(n_layers)]
 

@@ -22,7 +22,7 @@ import torch
 
 from . import ops
 from ._lib import ConvDesc
-from .arch import BackboneSpec, ConvSpec, backbone_spec
+from .arch import RANGE_OVER_BITS, BackboneSpec, ConvSpec, backbone_spec, range_unit_names
 
 Tensor = torch.Tensor
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1          # nn.BatchNorm2d defaults (resnet.py:185)
@@ -185,6 +185,22 @@ class Backbone:
         # d(loss)/d(img) (the backward-data launch runs on the fp32 kernel) or the width is odd.
         self.stem_rowwindow = True
         self.split_eval = True      # inference forward on the split kernels too
+        # Inference on the split kernels stores every activation as two UNSCALED fp16 pieces, and running statistics bound
+        # nothing: a checkpoint whose activation reaches 65 520 stores inf, merges to NaN, and a later ReLU can turn that into 0.
+        # The guard (folded fp32 inference only; the taped paths and the bf16 path ignore it) makes every sp-producing launch
+        # leave max |stored value| - as float bits, an integer atomic max: inf / NaN rank on top - in its word of a record
+        # (arch.range_unit_names; same launches, same output bits):
+        #   None        today's launches exactly;
+        #   "record"    the ranged launches; range_report() / overflowed() read the record (they synchronise, the forward never
+        #               does: it can be captured in a graph);
+        #   "fallback"  also reads the record after the backbone (one small copy + a synchronisation; not under stream capture) and,
+        #               if a tensor overflowed, reruns the call on the fp32-MFMA kernels - the result of split_eval = False, bit
+        #               for bit - and stays on them for later inference calls until invalidate_weight_cache() / train().
+        self.split_eval_guard: Optional[str] = None
+        self._range_record: Optional[Tensor] = None       # int32 [len(range_unit_names)]: a plain attribute, not a buffer
+        self._range_slot: Dict[str, int] = {n: i for i, n in enumerate(range_unit_names(depth, prefix))}
+        self._range_live = False              # per forward call: the ranged launches are in use
+        self._range_tripped = False           # "fallback" saw an overflow: inference stays on the fp32-MFMA kernels
         # bf16 path, inference (no tape): BatchNorm on the running statistics, the residual and the ReLU folded into the conv
         # epilogue (mvg_conv_fprop_bf16_affine) - every activation written once and rounded once - the downsample branch
         # stored normalised, and the bf16 weight copies kept between calls.  (attribute False: the training-shaped launches -
@@ -338,6 +354,23 @@ class Backbone:
         weights.  ``model.train()`` and every training forward clear it too."""
         self._wk_cache.clear()
         self._wprep_infer_ok = False          # bf16 path: the next inference call casts the weights again
+        self._range_tripped = False           # new weights: the guarded forward tries the split kernels again
+
+    def _range_words(self) -> Tensor:
+        if self.split_eval_guard is None or self._range_record is None:
+            raise RuntimeError("no activation range record: set split_eval_guard to 'record' or 'fallback' and run an inference forward")
+        return self._range_record.cpu()        # (synchronises)
+
+    def range_report(self) -> Dict[str, float]:
+        """{conv name: max |activation| of the sp tensor its unit stored} of the last guarded inference forward, in forward
+        order (inf / nan when the fp32 value was); all zeros when that call did not run on the split kernels.  Synchronises."""
+        vals = self._range_words().view(torch.float32).tolist()
+        return {n: vals[i] for n, i in self._range_slot.items()}
+
+    def overflowed(self) -> List[str]:
+        """The units of range_report() whose tensor reached 65 520 (an fp16 piece became inf), in forward order.  Synchronises."""
+        words = self._range_words().tolist()
+        return [n for n, i in self._range_slot.items() if words[i] >= RANGE_OVER_BITS]
 
     def bn_count_buffers(self) -> List[Tensor]:
         return [self.p[c.bn + ".num_batches_tracked"] for c in self.spec.all_convs()]
@@ -395,7 +428,10 @@ class Backbone:
                 self._wk_cache[c.name] = (wsrc.data_ptr(), wsrc._version, wk)
             out = (ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev) if relu
                    else torch.empty(G, N, d.ho, d.wo, c.cout, dtype=torch.float32, device=dev))
-            ops.conv_fprop_split_affine(d, x, wk, out, scale, shift, residual, relu)
+            if self._range_live and relu:        # (an sp output: every unit but the downsample branches)
+                ops.conv_fprop_split_affine_ranged(d, x, wk, out, scale, shift, residual, relu, self._range_word(c))
+            else:
+                ops.conv_fprop_split_affine(d, x, wk, out, scale, shift, residual, relu)
             return out
         y = torch.empty(G, N, d.ho, d.wo, c.cout, dtype=self.act_dtype, device=dev)
         if bf:                                   # y is the unit's output, written once, rounded once
@@ -407,7 +443,13 @@ class Backbone:
         if not pool:
             return y
         pooled = self._pool_plain(y, G, N, d.ho, d.wo, c.cout)
+        if sp_eval and self._range_live:
+            return ops.split_f32_ranged(pooled, self._range_word(c))
         return ops.split_f32(pooled) if sp_eval else pooled
+
+    def _range_word(self, c: ConvSpec) -> Tensor:
+        i = self._range_slot[c.name]
+        return self._range_record[i:i + 1]
 
     @staticmethod
     def _pool_plain(a0: Tensor, G: int, N: int, h: int, w: int, c: int) -> Tensor:
@@ -575,6 +617,15 @@ class Backbone:
         # fp32-MFMA kernels (64-bit row offsets there; B < 668 per view at 224 x 224 with ResNet-50)
         biggest_view_elems = B * ((H + 3) // 4) * ((W + 3) // 4) * self.spec.blocks[0].convs[-1].cout
         self._split_now = self.split and 4 * biggest_view_elems * self._guard_scale < 0x7FFFFFF0
+        infer = not (training or keep_tape or self.bf16)         # the folded fp32 inference forward: what split_eval_guard covers
+        if self.split_eval_guard not in (None, "record", "fallback"):
+            raise ValueError(f"split_eval_guard must be None, 'record' or 'fallback' (got {self.split_eval_guard!r})")
+        guard = self.split_eval_guard if infer else None
+        if guard == "fallback" and torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("split_eval_guard = 'fallback' reads the range record on the host and cannot run while the stream "
+                               "is capturing: capture with 'record' and check overflowed() after the replay")
+        if guard == "fallback" and self._range_tripped:
+            self._split_now = False              # an earlier call overflowed: fp32-MFMA kernels until the weights change
         # the stem's form for this call (see stem_rowwindow)
         if self.bf16:        # folded windows: width % 4, whole 64-row partials (n * ho * wo / 2), the stem's weights through the batch
             ho, wo = (H - 1) // 2 + 1, W // 2
@@ -600,7 +651,19 @@ class Backbone:
         if training or keep_tape or (self.bf16 and not self.bf16_fold_eval):
             x = self._forward_taped(x0, V, B, H, W, training, tape)
         else:
+            self._range_live = guard is not None and self._split_now and self.split_eval
+            if guard is not None:
+                if self._range_record is None or self._range_record.device != dev:
+                    self._range_record = torch.zeros(len(self._range_slot), dtype=torch.int32, device=dev)
+                else:
+                    self._range_record.zero_()
             x = self._forward_infer(x0, V, B, H, W)
+            if guard == "fallback" and self._range_live:
+                if max(self._range_record.tolist()) >= RANGE_OVER_BITS:      # one small copy + a synchronisation (|v|: sign bit clear)
+                    self._range_tripped = True
+                    self._split_now = self._range_live = False
+                    x = self._forward_infer(x0, V, B, H, W)
+            self._range_live = False
         Hc, Wc = x.shape[2], x.shape[3]
         feat = torch.empty(V, B, self.fc_dim, dtype=torch.float32, device=dev)
         if x.dtype == torch.float16:                                # sp activation of the split path

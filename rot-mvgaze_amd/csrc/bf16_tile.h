@@ -22,6 +22,33 @@ __device__ __forceinline__ void ld8(const float *p, float (&v)[8]) {       // 8 
   v[0] = a.x; v[1] = a.y; v[2] = a.z; v[3] = a.w; v[4] = b.x; v[5] = b.y; v[6] = b.z; v[7] = b.w;
 }
 
+// The activation range record of the guarded inference forward: *word = max over a tensor's stored elements of the bits of |v|
+// (an UNSIGNED-INTEGER max on the float's bits: monotone for non-negative floats, inf / NaN rank above every finite value, where
+// fmaxf would drop a NaN).  range_bits: one value's contribution.  range_commit: every thread of a 256-thread workgroup calls it
+// with its own maximum after the workgroup is done with `lds` (4 words; a barrier precedes the write) - wave reduce, cross-wave
+// reduce, ONE plain load of the word (a stale value only costs a redundant atomic) and an atomicMax only when the workgroup's value
+// is larger: a handful of atomics per launch, not one per workgroup (same-address atomics serialise at ~12 ns each).
+constexpr unsigned RANGE_OVER_BITS = 0x477FF000u;              // 65520.0f: from here fp16 round-to-nearest-even gives inf
+__device__ __forceinline__ unsigned range_bits(unsigned mx, float v) {
+  const unsigned b = __float_as_uint(v) & 0x7FFFFFFFu;
+  return b > mx ? b : mx;
+}
+__device__ __forceinline__ void range_commit(unsigned mx, unsigned *lds, unsigned *__restrict__ word, int tid) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) {
+    const unsigned other = (unsigned)__shfl_xor((int)mx, o, 64);
+    mx = other > mx ? other : mx;
+  }
+  __syncthreads();                             // `lds` is free: everyone is done with what it held
+  if ((tid & 63) == 0) lds[tid >> 6] = mx;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned m = lds[0];
+    for (int k = 1; k < 4; ++k) m = lds[k] > m ? lds[k] : m;
+    if (m > *word) atomicMax(word, m);
+  }
+}
+
 // Epilogue shared by the bf16 GEMM kernels: BN partial statistics from the fp32 accumulators, then the tile goes
 // through LDS (fp32, the operand buffers are free after the K loop) so that global stores are 16-byte vectors along
 // the channel axis, with bias / ReLU / mask / addend applied in fp32 and ONE rounding to bf16 (F32IO: fp32 stores).
@@ -48,8 +75,11 @@ constexpr int bf16_epilogue_bytes() {
 // scale / shift and p.addend as the bf16 residual - the ReLU FOLLOWS the add and the only rounding is the store's.  Its own
 // instantiations: the training kernels carry none of it.  The 2 * BN constants wait in LDS behind the row offsets
 // (bf16_epilogue_bytes<.., AFF>) and are re-read per iteration, like the fused reduce's, not held across the store loop.
+// RNG (split kernels, forward, sp output, not LIN; its own instantiations): the launch also leaves the range record of what it
+// stores in *p.out_absmax (range_commit above).  A lane takes the maximum over the values it hands to split2_chunk - after scale,
+// shift, residual and ReLU; rows and columns beyond the map's edge never reach that line - and the stored bits are the unranged kernel's.
 template <int BM, int BN, int WGM, bool DGRAD, bool F32IO, int PASSES = 1, bool ACC16 = false, bool BNF = false, bool LIN = false, int WGN = 2,
-          bool AFF = false, class AccT>
+          bool AFF = false, bool RNG = false, class AccT>
 __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmClass &c, AccT &acc,
                                               unsigned short *smem, int tid, int g, int mtile, int ntile) {
   constexpr int NT = WGM * WGN * 64;
@@ -67,6 +97,8 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
   // split operands carry per-tensor power-of-two scales: exact to undo on the accumulators
   const float osc = F32IO ? (p.a_sinv ? *p.a_sinv : 1.f) * (p.b_sinv ? *p.b_sinv : 1.f) : 1.f;
   float lin_scale = 1.f, lin_max = 0.f;
+  unsigned rng_max = 0u;
+  static_assert(!RNG || (F32IO && !DGRAD && !LIN && !BNF && !AFF && WGM * WGN == 4), "bf16_epilogue: RNG is a forward form of the split conv kernels");
   if constexpr (LIN && F32IO) {
     if (!DGRAD && p.out_sp && p.out_sinv) {
       const float bound = (float)p.ktotal * 1073741824.f * osc + (p.bias_absmax ? *p.bias_absmax : 0.f);
@@ -276,6 +308,10 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
         if constexpr (LIN) {
 #pragma unroll
           for (int k = 0; k < 8; ++k) x[k] *= lin_scale;
+        }
+        if constexpr (RNG) {
+#pragma unroll
+          for (int k = 0; k < 8; ++k) rng_max = range_bits(rng_max, x[k]);
         }
         uint4 q1, q2;
         split2_chunk(x, q1, q2);
@@ -497,6 +533,7 @@ __device__ __forceinline__ void bf16_epilogue(const IgemmParams &p, const IgemmC
     for (int it = 0; it < PR * CV / NT; ++it) store_rows(it);
   }
   }  // passes
+  if constexpr (RNG) range_commit(rng_max, reinterpret_cast<unsigned *>(smem), p.out_absmax, tid);     // (the staging tile has been read out)
   if constexpr (LIN && F32IO) {
     if (p.out_absmax) {                        // ONE atomic per workgroup (atomics on one address serialise at ~12 ns each)
 #pragma unroll

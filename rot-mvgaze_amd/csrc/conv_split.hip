@@ -52,6 +52,26 @@ __global__ __launch_bounds__(256) void split_f32_kernel(const float4 *__restrict
   }
 }
 
+// split_f32_kernel plus the activation range record of what it stores (bf16_tile.h: range_commit) - the stem's pooled map, the
+// only sp tensor of the guarded inference forward that no conv epilogue writes
+__global__ __launch_bounds__(256) void split_f32_ranged_kernel(const float4 *__restrict__ x, uint4 *__restrict__ out, long long n8, float scale,
+                                                               unsigned *__restrict__ range_word) {
+  __shared__ unsigned red[4];
+  const long long stride = (long long)gridDim.x * 256;
+  unsigned mx = 0u;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n8; i += stride) {
+    const float4 lo = x[2 * i], hi = x[2 * i + 1];
+    const float v[8] = {lo.x * scale, lo.y * scale, lo.z * scale, lo.w * scale, hi.x * scale, hi.y * scale, hi.z * scale, hi.w * scale};
+#pragma unroll
+    for (int k = 0; k < 8; ++k) mx = range_bits(mx, v[k]);
+    uint4 q1, q2;
+    split2_chunk(v, q1, q2);
+    out[2 * i] = q1;
+    out[2 * i + 1] = q2;
+  }
+  range_commit(mx, red, range_word, (int)threadIdx.x);
+}
+
 // sp -> fp32: (piece 1 + piece 2) * inv_scale
 __global__ __launch_bounds__(256) void merge_sp_kernel(const uint4 *__restrict__ x, float4 *__restrict__ out, long long n8, float inv_scale) {
   const long long stride = (long long)gridDim.x * 256;
@@ -422,259 +442,15 @@ struct OutFormer {
   }
 };
 
-template <int BN, bool DGRAD, bool LIN = false, int WGM = 2, int STAGES = 1, AForm AF = A_DMA>
-__global__ __launch_bounds__(256, STAGES == 2 ? 2 : (DGRAD || WGM == 4 || AF != A_DMA) ? 3 : 4) void igemm_split16_kernel(IgemmParams p) {
-  constexpr int BM = 64 * WGM, WGN = 4 / WGM, NW = 4;
-  static_assert(WGM == 2 || (WGM == 4 && BN == 64), "tiles: 128 x BN (2 x 2 waves) or 256 x 64 (4 x 1)");
-  static_assert(STAGES == 1 || STAGES == 2, "one LDS stage, or the two-stage pipeline");
-  static_assert(AF == A_DMA || (DGRAD == (AF == A_DY) && !LIN && WGM == 2 && STAGES == 1),
-                "operand-forming loaders: dy in backward-data, the block output in forward; 128-row tiles, one stage");
-  using Former = std::conditional_t<AF == A_DY, DyFormer, OutFormer<AF == A_OUT_AFFINE>>;
-  constexpr int WTM = BM / WGM, WTN = BN / WGN;
-  constexpr int TM = WTM / 16, TN = WTN / 16;
-  constexpr int SLOTS = 4 * SP_NP;                            // 16-byte slots per LDS row (8)
-  constexpr int ROWB = 16 * SLOTS, ROWS = BM + BN, STAGE_B = ROWS * ROWB;
-  constexpr int NQ = ROWS * SLOTS / 64;                       // DMA wave-instructions per stage (32 / 24)
-  constexpr int QA = BM * SLOTS / 64;                         // ... of which the first 16 fill the A rows
-  constexpr int A_PER = QA / NW, B_PER = (NQ - QA) / NW;      // per wave: 4 and 4 / 2
-  static_assert(QA % NW == 0 && (NQ - QA) % NW == 0, "whole instructions per wave");
-  constexpr int EPI_B = bf16_epilogue_bytes<BM, BN, WGM, DGRAD>();          // one wave row (64 tile rows) per staging pass
-  constexpr int INFO_OFF = STAGES * STAGE_B > EPI_B ? STAGES * STAGE_B : EPI_B;  // row table behind the stages / the epilogue tile
-  constexpr int BNK_OFF = INFO_OFF + BM * 8;                  // the former's per-channel constants: [TABLES][src_c]
-  constexpr int SMEM_B = BNK_OFF + (AF != A_DMA ? Former::TABLES : 0) * BNA_MAX_C * 4;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[SMEM_B];
-
-  const int tid = threadIdx.x;
-  const int lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int wm = wave / WGN, wn = wave % WGN;
-  const int nwg = gridDim.x;
-  const int wg_all = p.no_remap ? (int)blockIdx.x : xcd_remap(blockIdx.x, nwg);
-  int ci = 0;
-  for (int i = 1; i < p.ncls; ++i) ci += wg_all >= p.cls[i].tile0;
-  const IgemmClass &c = p.cls[ci];
-  const int wg = wg_all - c.tile0;
-  const int ntile = wg % p.ntiles;
-  const int mt_all = wg / p.ntiles;
-  const int g = mt_all / c.mtiles_per_group;
-  const int mtile = mt_all - g * c.mtiles_per_group;
-  const int KT = c.KT;
-  const int ohw = c.out_h * c.out_w;
-
-  // ---- row table: thread r < 128 -> (byte offset of row r's pixel at tap (0,0) channel 0, bit t = tap t in range)
-  uint2 *rowinfo = reinterpret_cast<uint2 *>(smem + INFO_OFF);
-  if (tid < BM) {
-    const long long m = (long long)mtile * BM + tid;
-    const bool ok = m < c.rows_per_group;
-    const int mm = ok ? (int)m : 0;
-    const int img = (int)fdiv((unsigned)mm, c.ohw_div);
-    const int rem = mm - img * ohw;
-    const int oy = (int)fdiv((unsigned)rem, c.ow_div), ox = rem - oy * c.out_w;
-    const int y0 = DGRAD ? oy + c.cls_cy : oy * p.stride - p.pad;
-    const int x0 = DGRAD ? ox + c.cls_cx : ox * p.stride_w - p.pad_w;
-    const unsigned base = (unsigned)(img * p.src_img_stride * SP_BYTES) + (unsigned)((y0 * p.src_w + x0) * p.src_c) * (unsigned)SP_BYTES;
-    unsigned msk = 0;
-    for (int t = 0; t < c.ntaps; ++t) {
-      const int fr = (int)fdiv((unsigned)t, c.tap_ns_div), fs = t - fr * c.tap_ns;
-      const int iy = DGRAD ? y0 - fr : y0 + fr;
-      const int ix = DGRAD ? x0 - fs : x0 + fs;
-      msk |= (unsigned)(((unsigned)iy < (unsigned)p.src_h) & ((unsigned)ix < (unsigned)p.src_w)) << t;
-    }
-    rowinfo[tid] = make_uint2(base, ok ? msk : 0u);
-  }
-  if constexpr (AF != A_DMA) Former::stage(reinterpret_cast<float *>(smem + BNK_OFF), p, g, p.src_c, tid);
-  __syncthreads();
-  // ---- the instructions this wave issues: Q = wave + 4 i; lane -> linear slot 64 Q + lane -> (row, slot in row);
-  // the slot holds source slot j = slot ^ h(row) of the row's 128-byte span (j = 2 cc + pc: the memory order)
-  unsigned a_base[A_PER], a_vmask[A_PER], b_base[B_PER];
-#pragma unroll
-  for (int i = 0; i < A_PER; ++i) {
-    const int sl = (wave + NW * i) * 64 + lane;
-    const int row = sl / SLOTS, j = (sl % SLOTS) ^ sp_row_swz(row);
-    const uint2 ri = rowinfo[row];
-    a_base[i] = ri.x + 16u * (unsigned)j;
-    a_vmask[i] = ri.y;
-  }
-#pragma unroll
-  for (int i = 0; i < B_PER; ++i) {
-    const int sl = (wave + NW * (A_PER + i)) * 64 + lane - BM * SLOTS;
-    const int row = sl / SLOTS, j = (sl % SLOTS) ^ sp_row_swz(row);        // h(BM + row) == h(row): BM is a multiple of 8
-    const int n = ntile * BN + row;
-    b_base[i] = pred_off(((unsigned)n * (unsigned)p.b_row_len) * (unsigned)SP_BYTES + 16u * (unsigned)j, n < p.ncols);
-  }
-  const __amdgpu_buffer_rsrc_t rs_a =
-      make_rsrc(reinterpret_cast<const char *>(p.a) + (long long)g * p.imgs_per_group * p.src_img_stride * SP_BYTES, p.a_group_bytes);
-  const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(p.b, p.b_bytes);
-  typedef __attribute__((address_space(3))) void *lds_vp;
-
-  auto issue = [&](int kt, int stage_off) {
-    int kstart = kt * SP_BK;
-    if (c.korder) {
-      const int cblk = (int)fdiv((unsigned)kt, c.per_div), rem = kt - cblk * c.ntaps;
-      kstart = (rem << p.src_c_shift) + cblk * SP_BK;
-    }
-    const int ks = __builtin_amdgcn_readfirstlane(kstart);
-    const int tap_u = c.ntaps > 1 ? (ks >> p.src_c_shift) : 0;
-    const int chb = ks - (tap_u << p.src_c_shift);
-    const int fru = (int)fdiv((unsigned)tap_u, c.tap_ns_div), fsu = tap_u - fru * c.tap_ns;
-    const int disp = (fru * p.src_w + fsu) * p.src_c;
-    const unsigned sdelta = (unsigned)(((DGRAD ? -disp : disp) + chb) * SP_BYTES);
-    unsigned kb = (unsigned)ks * (unsigned)SP_BYTES;
-    if (DGRAD) {
-      const int btap = (c.tap_r0 + p.tap_step * fru) * p.s + c.tap_s0 + p.tap_step * fsu;
-      kb = (unsigned)(btap * p.src_c + chb) * (unsigned)SP_BYTES;
-    }
-    if constexpr (AF == A_DMA) {
-#pragma unroll
-      for (int i = 0; i < A_PER; ++i) {
-        const bool ok = ((a_vmask[i] >> tap_u) & 1u) != 0u;
-        __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_a, (lds_vp)(smem + stage_off + (wave + NW * i) * 1024), 16, (int)pred_off(a_base[i] + sdelta, ok), 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int i = 0; i < B_PER; ++i)
-      __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_b, (lds_vp)(smem + stage_off + (wave + NW * (A_PER + i)) * 1024), 16, (int)(b_base[i] + kb), 0, 0, 0);
-  };
-
-  f32x4 acc[TM][TN];
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int e = 0; e < 4; ++e) acc[i][j][e] = 0.f;
-
-  // fragment addresses: lane -> row (l & 15) of a 16-row tile, chunk cc = l >> 4, piece pc -> slot (2 cc + pc) ^ h(row)
-  const int cc_l = lane >> 4;
-  int a_off[TM][SP_NP], b_off[TN][SP_NP];
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    const int R = wm * WTM + i * 16 + (lane & 15);
-#pragma unroll
-    for (int pc = 0; pc < SP_NP; ++pc) a_off[i][pc] = R * ROWB + (((2 * cc_l + pc) ^ sp_row_swz(R)) << 4);
-  }
-#pragma unroll
-  for (int j = 0; j < TN; ++j) {
-    const int R = wn * WTN + j * 16 + (lane & 15);
-#pragma unroll
-    for (int pc = 0; pc < SP_NP; ++pc) b_off[j][pc] = (BM + R) * ROWB + (((2 * cc_l + pc) ^ sp_row_swz(R)) << 4);
-  }
-
-  auto load_frags = [&](const unsigned char *stage, f16x8 (&av)[SP_NP][TM], f16x8 (&bv)[SP_NP][TN]) {
-#pragma unroll
-    for (int pc = 0; pc < SP_NP; ++pc) {
-#pragma unroll
-      for (int i = 0; i < TM; ++i) av[pc][i] = *reinterpret_cast<const f16x8 *>(stage + a_off[i][pc]);
-#pragma unroll
-      for (int j = 0; j < TN; ++j) bv[pc][j] = *reinterpret_cast<const f16x8 *>(stage + b_off[j][pc]);
-    }
-  };
-  // smallest terms first: (a1 b2, a2 b1), a1 b1
-  auto products = [&](const f16x8 (&av)[SP_NP][TM], const f16x8 (&bv)[SP_NP][TN]) { SPLIT16_ONE(0, 1) SPLIT16_ONE(1, 0) SPLIT16_ONE(0, 0) };
-  if constexpr (AF != A_DMA) {
-    // (1x1, stride 1: the GEMM's rows are the formed map's pixels, K-step kt = channels 32 kt .. 32 kt + 31)
-    const int C = p.src_c;
-    const int a_cc = tid & 3, a_r0 = tid >> 2;
-    const long long grow0 = (long long)g * c.rows_per_group;
-    Former f(p, grow0, c.rows_per_group, C);
-    uint4 *a_out = reinterpret_cast<uint4 *>(const_cast<float *>(p.a)) + grow0 * C / 4;       // 4 bytes per element
-    bool a_ok[2];
-    unsigned a_goff[2];                                        // byte offset of (row, chunk) in the group's fp32 maps = in its sp maps
-#pragma unroll
-    for (int i = 0; i < 2; ++i) {
-      const long long m = (long long)mtile * BM + a_r0 + 64 * i;
-      a_ok[i] = m < c.rows_per_group;
-      a_goff[i] = pred_off((unsigned)m * (unsigned)C * 4u + 32u * (unsigned)a_cc, a_ok[i]);
-    }
-    auto a_load = [&](int kt) {
-#pragma unroll
-      for (int i = 0; i < 2; ++i) f.load(i, a_goff[i] + 128u * (unsigned)kt);
-    };
-    // the next K-step's inputs in flight while this one is multiplied: 32 more live registers, which the 128-column tile
-    // (64 accumulators, 64 fragment registers) does not have at three workgroups per CU (168) - it loads at the top instead
-    constexpr bool PREFETCH = BN == 64;
-    if (PREFETCH) a_load(0);
-    for (int kt = 0; kt < KT; ++kt) {
-      issue(kt, 0);                                            // the weights: DMA
-      if (!PREFETCH) a_load(kt);
-      uint4 q[2][SP_NP];
-      f.consts(reinterpret_cast<const float *>(smem + BNK_OFF) + kt * SP_BK + a_cc * 8, C);
-#pragma unroll
-      for (int i = 0; i < 2; ++i) {
-        float o[8];
-        f.form(i, a_ok[i], o);
-        split2_chunk(o, q[i][0], q[i][1]);
-        const int R = a_r0 + 64 * i;
-#pragma unroll
-        for (int pc = 0; pc < SP_NP; ++pc)
-          *reinterpret_cast<uint4 *>(smem + R * ROWB + (((2 * a_cc + pc) ^ sp_row_swz(R)) << 4)) = q[i][pc];
-      }
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-#pragma unroll
-      for (int i = 0; i < 2; ++i)
-        if (a_ok[i]) {
-          const unsigned off = a_goff[i] + 128u * (unsigned)kt;
-          uint4 *dst = a_out + (off >> 4);
-          dst[0] = q[i][0];
-          dst[1] = q[i][1];
-          f.store_extra(i, off);
-        }
-      if (PREFETCH && kt + 1 < KT) a_load(kt + 1);             // in flight while this K-step is multiplied
-      {
-        f16x8 av[SP_NP][TM], bv[SP_NP][TN];
-        load_frags(smem, av, bv);
-        products(av, bv);
-      }
-      __syncthreads();                                         // everyone is done reading before the next K-step is written
-    }
-  } else if constexpr (STAGES == 1) {
-    for (int kt = 0; kt < KT; ++kt) {
-      issue(kt, 0);
-      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-      __syncthreads();
-      {
-        f16x8 av[SP_NP][TM], bv[SP_NP][TN];
-        load_frags(smem, av, bv);
-        products(av, bv);
-      }
-      __syncthreads();                                         // everyone is done reading before the next DMA lands
-    }
-  } else {
-    // Software pipeline, two levels: two K-steps of DMA in LDS / in flight, and the fragments of K-step kt + 1 read into a second
-    // register set while K-step kt's MFMAs run (with one wave per SIMD nothing else overlaps the LDS reads with the matrix
-    // pipe).  At the top of K-step kt: wait until K-step kt + 1 has landed (the only group in flight: vmcnt(0)) and this wave's
-    // fragment reads of K-step kt are complete (lgkmcnt(0)), barrier - now K-step kt's stage is free for every wave and K-step
-    // kt + 2 goes into it.  A bare s_barrier: __syncthreads() carries a fence that the compiler turns into s_waitcnt vmcnt(0)
-    // wherever an LDS-DMA is pending, which in the prologue would wait for BOTH stages before the first multiply.  (Three and
-    // four stages with counted vmcnt waits - one workgroup per CU - measured the same as two: profiles/r04_lin_kloop_stages_ab.txt.)
-    constexpr int G = A_PER + B_PER;                           // DMA instructions per wave and K-step
-    if (KT > 0) issue(0, 0);                                   // (KT = 0: a tap-less class of a fused-reduce launch, epilogue only)
-    if (KT > 1) {
-      issue(1, STAGE_B);
-      asm volatile("s_waitcnt vmcnt(%0)\n\ts_barrier" ::"n"(G) : "memory");     // K-step 0 has landed, K-step 1 is in flight
-    } else {
-      asm volatile("s_waitcnt vmcnt(0)\n\ts_barrier" ::: "memory");
-    }
-    f16x8 a0[SP_NP][TM], b0[SP_NP][TN], a1[SP_NP][TM], b1[SP_NP][TN];
-    load_frags(smem, a0, b0);
-    int cur = 0;                                               // byte offset of K-step kt's stage
-    auto step = [&](int kt, const f16x8 (&ca)[SP_NP][TM], const f16x8 (&cb)[SP_NP][TN], f16x8 (&na)[SP_NP][TM], f16x8 (&nb)[SP_NP][TN]) {
-      if (kt + 1 < KT) {
-        asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)\n\ts_barrier" ::: "memory");
-        if (kt + 2 < KT) issue(kt + 2, cur);
-        cur ^= STAGE_B;
-        load_frags(smem + cur, na, nb);
-      }
-      products(ca, cb);
-    };
-    for (int kt = 0; kt < KT; kt += 2) {
-      step(kt, a0, b0, a1, b1);
-      if (kt + 1 < KT) step(kt + 1, a1, b1, a0, b0);
-    }
-    __syncthreads();                                           // the epilogue reuses the stages
-  }
-  bf16_epilogue<BM, BN, WGM, DGRAD, true, WGM, true, DGRAD, LIN, WGN>(p, c, acc, reinterpret_cast<unsigned short *>(smem), tid, g, mtile, ntile);
-}
+//
+// The kernel itself lives in conv_split_igemm.inc: once as igemm_split16_kernel, once as igemm_split16_ranged_kernel, the guarded
+// inference forward's form with the activation range record in its epilogue (mvg_conv_fprop_split_affine_ranged).
+#define MVG_SPLIT_RNG 0
+#include "conv_split_igemm.inc"
+#undef MVG_SPLIT_RNG
+#define MVG_SPLIT_RNG 1
+#include "conv_split_igemm.inc"
+#undef MVG_SPLIT_RNG
 
 // ------------------------------------------------------------------------------------------
 // wgrad: dw[o][tap][c] = sum over pixels of dy[pix][o] * x[pix at tap][c] with both operands in sp.  Like the bf16
@@ -1031,7 +807,7 @@ static SplitPlan split_plan(int ncols, int taps, long long rows, int groups, boo
 
 // taps, rows: the filter's taps and the rows of the whole map (the row-tile height's arguments); af: the loader forms the A operand
 template <bool DGRAD>
-static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin, int taps, long long rows, AForm af = A_DMA) {
+static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin, int taps, long long rows, AForm af = A_DMA, bool ranged = false) {
   const SplitPlan pl = split_plan(p.ncols, taps, rows, p.groups, lin, p.cls, p.ncls);
   const int bm = pl.bm, bn = pl.bn;
   const bool pipelined = pl.pipelined;
@@ -1071,6 +847,16 @@ static int launch_igemm_split(IgemmParams &p, hipStream_t st, bool lin, int taps
       return check_launch("conv_fprop_split_bnapply");
     }
   }
+  if (ranged) {              // the guarded inference forward: the plain forward's four forms with the range record in the epilogue
+    MVG_REQUIRE(!DGRAD && !lin && p.out_sp && p.out_absmax, "split conv: the range record goes with a forward that stores sp");
+    if constexpr (!DGRAD) {
+      if (bm == 256) hipLaunchKernelGGL((igemm_split16_ranged_kernel<64, 4>), grid, block, 0, st, p);
+      else if (split_conv_stages(pl) == 2) hipLaunchKernelGGL((igemm_split16_ranged_kernel<128, 2, 2>), grid, block, 0, st, p);
+      else if (bn == 128) hipLaunchKernelGGL((igemm_split16_ranged_kernel<128>), grid, block, 0, st, p);
+      else hipLaunchKernelGGL((igemm_split16_ranged_kernel<64>), grid, block, 0, st, p);
+    }
+    return check_launch("conv_fprop_split_ranged");
+  }
   if (lin) {                 // a Linear of the fusion block: the epilogue's scale / abs-max features compiled in
     if (bn == 128 && pipelined) hipLaunchKernelGGL((igemm_split16_kernel<128, DGRAD, true, 2, 2>), grid, block, 0, st, p);
     else if (bn == 128) hipLaunchKernelGGL((igemm_split16_kernel<128, DGRAD, true>), grid, block, 0, st, p);
@@ -1099,6 +885,19 @@ int mvg_split_f32(const float *x, void *out_sp, int64_t n, float scale, void *st
   if (blocks > 8192) blocks = 8192;
   hipLaunchKernelGGL(split_f32_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float4 *)x, (uint4 *)out_sp, (long long)(n / 8), scale);
   return check_launch("split_f32");
+}
+
+int mvg_split_f32_ranged(const float *x, void *out_sp, int64_t n, float scale, uint32_t *range_word, void *stream) {
+  MVG_REQUIRE(x && out_sp && range_word && n >= 0 && n % 8 == 0, "split_f32_ranged: null argument or n %% 8 != 0");
+  MVG_REQUIRE(scale > 0.f, "split_f32_ranged: scale must be positive (a power of two keeps the round trip exact)");
+  if (n == 0) return 0;
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_LAYOUT, st, 0.0, (4.0 + SP_BYTES) * (double)n);
+  long long blocks = (n / 8 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(split_f32_ranged_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float4 *)x, (uint4 *)out_sp, (long long)(n / 8), scale,
+                     (unsigned *)range_word);
+  return check_launch("split_f32_ranged");
 }
 
 int mvg_merge_sp(const void *x_sp, float *out, int64_t n, float inv_scale, void *stream) {
@@ -1171,6 +970,7 @@ struct SplitAffine {       // inference forward: y = acc * scale + shift (+ resi
   int lin;
   float *out_absmax, *out_sinv;
   const float *bias_absmax;
+  uint32_t *range_word;    // the guarded inference forward's record of this launch's sp output (travels as IgemmParams::out_absmax)
 };
 
 // stride_w / pad_w >= 0: the horizontal stride / padding differ from d->stride / d->pad (the stem's row-window form, whose
@@ -1200,7 +1000,7 @@ static int fprop_split_impl(const mvg_conv_desc *d, const void *x_sp, const floa
     p.addend_sp = aff->residual_sp;
     p.relu = aff->relu;
     p.out_sp = aff->out_sp;
-    p.out_absmax = (unsigned *)aff->out_absmax;
+    p.out_absmax = aff->range_word ? (unsigned *)aff->range_word : (unsigned *)aff->out_absmax;
     p.out_sinv = aff->out_sinv;
     p.bias_absmax = aff->bias_absmax;
   }
@@ -1226,7 +1026,7 @@ static int fprop_split_impl(const mvg_conv_desc *d, const void *x_sp, const floa
   ProfScope ps(lin ? MVG_K_LINEAR_FPROP : MVG_K_CONV_FPROP, (hipStream_t)stream, flops, bytes);
   p.stats_partials = ceil_div(p.rows_per_group, SP_BM) * 2;    // = mvg_conv_stats_partials_split
   return launch_igemm_split<false>(p, (hipStream_t)stream, aff && aff->lin, d->r * d->s, p.rows_per_group,
-                                   fap ? (fap->res_scale ? A_OUT_AFFINE : A_OUT_SP) : A_DMA);
+                                   fap ? (fap->res_scale ? A_OUT_AFFINE : A_OUT_SP) : A_DMA, aff && aff->range_word);
 }
 
 int mvg_conv_fprop_split(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *w_sp, const float *w_sinv, float *y,
@@ -1270,7 +1070,16 @@ int mvg_conv_fprop_split_affine(const mvg_conv_desc *d, const void *x_sp, const 
                                 void *out, int out_sp, const float *scale, const float *shift, const void *residual, int residual_sp,
                                 int relu, void *stream) {
   MVG_REQUIRE(scale && shift && out, "fprop_split_affine: scale, shift and out are required");
-  const SplitAffine a = {scale, shift, residual, residual_sp, relu, out_sp, 0, nullptr, nullptr, nullptr};
+  const SplitAffine a = {scale, shift, residual, residual_sp, relu, out_sp, 0, nullptr, nullptr, nullptr, nullptr};
+  return fprop_split_impl(d, x_sp, x_sinv, w_sp, w_sinv, out, nullptr, stream, &a);
+}
+
+int mvg_conv_fprop_split_affine_ranged(const mvg_conv_desc *d, const void *x_sp, const float *x_sinv, const void *w_sp, const float *w_sinv,
+                                       void *out, int out_sp, const float *scale, const float *shift, const void *residual,
+                                       int residual_sp, int relu, uint32_t *range_word, void *stream) {
+  MVG_REQUIRE(scale && shift && out, "fprop_split_affine_ranged: scale, shift and out are required");
+  MVG_REQUIRE(range_word && out_sp, "fprop_split_affine_ranged: range_word is required and the output must be sp (out_sp != 0)");
+  const SplitAffine a = {scale, shift, residual, residual_sp, relu, out_sp, 0, nullptr, nullptr, nullptr, range_word};
   return fprop_split_impl(d, x_sp, x_sinv, w_sp, w_sinv, out, nullptr, stream, &a);
 }
 
@@ -1569,7 +1378,7 @@ int mvg_linear_fprop_split(int rows, int fin, int fout, const void *x_sp, const 
   MVG_REQUIRE(!out_sp || out_sinv, "linear_fprop_split: an sp result needs out_sinv (it is stored scaled)");
   MVG_REQUIRE(!(out_sp && out_absmax), "linear_fprop_split: out_absmax is for fp32 results");
   const mvg_conv_desc d = linear_desc(rows, fin, fout);
-  const SplitAffine a = {nullptr, bias, nullptr, 0, relu, out_sp, 1, out_absmax, out_sinv, bias_absmax};
+  const SplitAffine a = {nullptr, bias, nullptr, 0, relu, out_sp, 1, out_absmax, out_sinv, bias_absmax, nullptr};
   return fprop_split_impl(&d, x_sp, x_sinv, w_sp, w_sinv, out, nullptr, stream, &a);
 }
 

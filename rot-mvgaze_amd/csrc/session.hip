@@ -111,9 +111,14 @@ static int run_step(const mvg_session *s, const FwdArgs &a, const SStep &t, void
                                          IMAGE_MEAN[2], IMAGE_STD[0], IMAGE_STD[1], IMAGE_STD[2], i[5], stream);
     case SOP_CONV_AFFINE: return mvg_conv_fprop_affine(&t.d, F(0), F(1), F(2), F(3), F(4), F(5), i[0], stream);
     case SOP_CONV_SPLIT_AFFINE:
+      if (s->range_record && t.range >= 0)
+        return mvg_conv_fprop_split_affine_ranged(&t.d, p[0], nullptr, p[1], F(2), p[3], i[0], F(4), F(5), p[6], i[1], i[2],
+                                                  s->range_record + t.range, stream);
       return mvg_conv_fprop_split_affine(&t.d, p[0], nullptr, p[1], F(2), p[3], i[0], F(4), F(5), p[6], i[1], i[2], stream);
     case SOP_MAXPOOL: return mvg_maxpool3x3s2_fwd(F(0), F(1), (uint8_t *)p[2], i[0], i[1], i[2], i[3], i[4], i[5], stream);
-    case SOP_SPLIT_F32: return mvg_split_f32(F(0), p[1], t.n, 1.0f, stream);
+    case SOP_SPLIT_F32:
+      if (s->range_record && t.range >= 0) return mvg_split_f32_ranged(F(0), p[1], t.n, 1.0f, s->range_record + t.range, stream);
+      return mvg_split_f32(F(0), p[1], t.n, 1.0f, stream);
     case SOP_AVGPOOL: return mvg_avgpool_fwd(F(0), F(1), i[0], i[1], i[2], stream);
     case SOP_AVGPOOL_SPLIT: return mvg_avgpool_fwd_split_scaled(p[0], nullptr, F(1), i[0], i[1], i[2], stream);
     case SOP_LINEAR: return mvg_linear_fprop(F(0), F(1), F(2), i[0], F(3), i[1], i[2], i[3], F(4), (size_t)t.n, stream);
@@ -250,6 +255,13 @@ int mvg_session_forward(mvg_session *s, const void *const *host_view_ptrs, const
   // the launches that can use scratch find the session's region (their stream-K / split forms, as under Python's registered
   // workspace), whatever mvg_set_scratch holds for this stream
   ScratchScope scope((hipStream_t)stream, (float *)buf_ptr(s, s->plan.buf_scratch), SESSION_SCRATCH_BYTES / sizeof(float));
+  if (s->range_record && !s->plan.range_units.empty()) {     // the range record starts every forward at zero (atomicMax targets)
+    if (hipMemsetAsync(s->range_record, 0, s->plan.range_units.size() * sizeof(uint32_t), (hipStream_t)stream) != hipSuccess) {
+      (void)hipGetLastError();
+      set_error("session_forward: clearing the range record failed");
+      return 1;
+    }
+  }
   for (const SStep &t : s->plan.steps)
     if (int e = run_step(s, a, t, stream)) return e;
   return 0;

@@ -406,6 +406,8 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
       t.r[0] = B.buf(pooled);
       t.r[1] = B.buf(pooled_sp);
       t.n = (int64_t)V * N * hp * wp * stem.cout;
+      t.range = (int32_t)p.range_units.size();
+      p.range_units.push_back(stem.name);
       B.push(t);
       x.buf = pooled_sp;
       x.sp = true;
@@ -441,6 +443,10 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
       s.i[0] = out.sp ? 1 : 0;
       s.i[1] = (residual && residual->sp) ? 1 : 0;
       s.i[2] = relu ? 1 : 0;
+      if (out.sp) {
+        s.range = (int32_t)p.range_units.size();
+        p.range_units.push_back(cs.name);
+      }
     } else {
       s.op = SOP_CONV_AFFINE;
       s.r[0] = B.buf(in.buf);
@@ -736,5 +742,25 @@ int64_t mvg_session_tensor_numel(const mvg_session *s, int i) {
 size_t mvg_session_workspace_bytes(const mvg_session *s) { return s ? (size_t)s->plan.workspace_bytes : 0; }
 
 int mvg_session_launches(const mvg_session *s) { return s ? (int)s->plan.steps.size() : -1; }
+
+int mvg_session_num_range_units(const mvg_session *s) { return s ? (int)s->plan.range_units.size() : -1; }
+
+const char *mvg_session_range_unit_name(const mvg_session *s, int i) {
+  if (!s || i < 0 || i >= (int)s->plan.range_units.size()) return nullptr;
+  return s->plan.range_units[i].c_str();
+}
+
+int mvg_session_set_range_record(mvg_session *s, uint32_t *record_dev) {
+  if (!s) {
+    mvg::set_error("session_set_range_record: null session");
+    return 2;
+  }
+  if (record_dev && s->plan.range_units.empty()) {
+    mvg::set_error("session_set_range_record: this session's backbone is not on the split kernels (no range units)");
+    return 2;
+  }
+  s->range_record = record_dev;
+  return 0;
+}
 
 }  // extern "C"

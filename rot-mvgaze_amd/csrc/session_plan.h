@@ -34,6 +34,7 @@ struct SStep {
   int32_t i[6] = {0, 0, 0, 0, 0, 0};
   int64_t n = 0;             // element / byte count, or the floats of the Linear workspace in r[..]
   int64_t cnt[8] = {0, 0, 0, 0, 0, 0, 0, 0};
+  int32_t range = -1;        // SOP_SPLIT_F32 / an sp-writing SOP_CONV_SPLIT_AFFINE: the step's word of the range record; else -1
 };
 
 // A byte range of the workspace, live from step `first` to step `last` (inclusive).  Persistent buffers (what bind
@@ -79,6 +80,7 @@ struct SessionPlan {
   int32_t split_now = 0;                        // the backbone runs on the split kernels (cfg.split and the 2 GiB guard)
   int32_t head_split = 0;                       // the fuser / head Linears run on the split kernels (>= 1024 rows)
   int32_t fc_dim = 0;
+  std::vector<std::string> range_units;         // range record: word -> the conv whose unit writes that sp tensor (forward order)
   int64_t workspace_bytes = 0;
 };
 
@@ -93,4 +95,5 @@ struct mvg_session {
   size_t workspace_bytes = 0;
   void *bound_stream = nullptr;
   bool bound = false;
+  uint32_t *range_record = nullptr;             // mvg_session_set_range_record: device words, or null (no record)
 };

@@ -217,6 +217,17 @@ class MultiViewGaze(nn.Module):
         # storage / matrix-core type of the backbone: torch.float32 (default: the path held to 1e-4 against the
         # reference) or torch.bfloat16 (BASELINE config C5: bf16 activations + weights copies, fp32 everything else)
         self.compute_dtype = torch.float32
+        # fp32 inference on the split kernels: the activation range guard (Backbone.split_eval_guard) - None (default),
+        # "record" (range_report() / overflowed() tell) or "fallback" (an overflowing checkpoint runs on the fp32-MFMA kernels)
+        self.split_eval_guard: Optional[str] = None
+
+    def range_report(self) -> Dict[str, float]:
+        """Backbone.range_report() of the last guarded inference forward: {conv name: max |activation| stored in sp}."""
+        return self._backbone.range_report()
+
+    def overflowed(self) -> List[str]:
+        """Backbone.overflowed(): the units whose sp tensor reached fp16's overflow point in the last guarded inference forward."""
+        return self._backbone.overflowed()
 
     # ---------------------------------------------------------------- plumbing
     def _named_tensors(self) -> Dict[str, Tensor]:
@@ -333,6 +344,7 @@ class MultiViewGaze(nn.Module):
         if self.compute_dtype not in (torch.float32, torch.bfloat16):
             raise ValueError("compute_dtype must be torch.float32 or torch.bfloat16")
         self._backbone.act_dtype = self.compute_dtype
+        self._backbone.split_eval_guard = self.split_eval_guard
         self._head.mixed = self.compute_dtype == torch.bfloat16
         self._head.split = self._backbone.split          # one switch (MVG_SPLIT) selects the kernel family everywhere
         self._sink.active = False

@@ -195,6 +195,17 @@ def split_f32(x: Tensor, scale: float = 1.0) -> Tensor:
     return out
 
 
+def split_f32_ranged(x: Tensor, range_word: Tensor, scale: float = 1.0) -> Tensor:
+    """split_f32 plus the activation range record: ``range_word`` (1-element int32 device tensor, cleared by the caller) receives
+    max over the stored elements of the bits of |x * scale| (integer atomic max; >= 0x477FF000: an fp16 piece overflowed)."""
+    assert x.dtype == torch.float32 and x.is_contiguous() and x.shape[-1] % 8 == 0
+    assert range_word.dtype == torch.int32 and range_word.numel() == 1
+    out = sp_empty(*x.shape, device=x.device)
+    check(lib().mvg_split_f32_ranged(_p(x), _p(out), x.numel(), float(scale), _p(range_word), _s()), "split_f32_ranged")
+    out.sinv = None if scale == 1.0 else torch.full((1,), 1.0 / scale, dtype=torch.float32, device=x.device)
+    return out
+
+
 def merge_sp(x: Tensor) -> Tensor:
     """sp -> fp32 (the sum of the pieces times the tensor's 2^-k; test plumbing: reads sinv on the host)."""
     assert is_sp(x) and x.is_contiguous() and x.shape[-1] == 8 and x.shape[-2] == 2
@@ -287,6 +298,17 @@ def conv_fprop_split_affine(d: ConvDesc, x_sp: Tensor, w_sp: Tensor, out: Tensor
     assert getattr(residual, "sinv", None) is None, "conv_fprop_split_affine: the residual is read unscaled"
     check(lib().mvg_conv_fprop_split_affine(C.byref(d), _p(x_sp), _sinv(x_sp), _p(w_sp), _sinv(w_sp), _p(out), int(is_sp(out)), _p(scale),
                                             _p(shift), _p(residual), int(is_sp(residual)), int(relu), _s()), "conv_fprop_split_affine")
+
+
+def conv_fprop_split_affine_ranged(d: ConvDesc, x_sp: Tensor, w_sp: Tensor, out: Tensor, scale: Tensor, shift: Tensor,
+                                   residual: Optional[Tensor], relu: bool, range_word: Tensor):
+    """conv_fprop_split_affine with an sp ``out`` plus the activation range record: ``range_word`` (1-element int32 device tensor,
+    cleared by the caller) receives max over the stored elements of the bits of |value| (see split_f32_ranged).  Same output bits."""
+    assert getattr(residual, "sinv", None) is None, "conv_fprop_split_affine_ranged: the residual is read unscaled"
+    assert is_sp(out) and range_word.dtype == torch.int32 and range_word.numel() == 1
+    check(lib().mvg_conv_fprop_split_affine_ranged(C.byref(d), _p(x_sp), _sinv(x_sp), _p(w_sp), _sinv(w_sp), _p(out), 1, _p(scale), _p(shift),
+                                                   _p(residual), int(is_sp(residual)), int(relu), _p(range_word), _s()),
+          "conv_fprop_split_affine_ranged")
 
 
 def conv_dgrad_split(d: ConvDesc, dy_sp: Tensor, wt_sp: Tensor, dx: Tensor, addend: Optional[Tensor] = None,

@@ -18,7 +18,7 @@ import torch
 
 from . import ops
 from ._lib import SessionCfg, check, lib
-from .arch import NUM_FEAT_VEC
+from .arch import NUM_FEAT_VEC, RANGE_OVER_BITS
 
 Tensor = torch.Tensor
 
@@ -30,10 +30,14 @@ class InferenceSession:
     ``compute_dtype`` float32).  height / width: the network's input size.  raw_hw = (h, w): the views are raw uint8
     ``[B, h, w, 3]`` patches, resized and normalised on the GPU (``input_bgr``: swap B and R first); otherwise fp32
     ``[B, 3, height, width]``.  The kernel family follows ``model._backbone.split`` (MVG_SPLIT); the 2 GiB guard of the split
-    path is evaluated from the real sizes.  Several sessions may share one model."""
+    path is evaluated from the real sizes.  Several sessions may share one model.
+
+    range_record=True: every forward also leaves the activation range record of the backbone's sp tensors (one word per name in
+    ``range_unit_names``; same launches, same outputs, still no synchronisation) for ``range_report()`` / ``overflowed()``.  A
+    session has no fallback: on an overflow build one over a model with ``_backbone.split = False``."""
 
     def __init__(self, model, views: int, batch: int, height: int, width: int, raw_hw: Optional[Tuple[int, int]] = None,
-                 input_bgr: bool = False) -> None:
+                 input_bgr: bool = False, range_record: bool = False) -> None:
         v = model._variant
         if v.encode_rotmat or v.share_feature:
             raise ValueError("InferenceSession: the encode_rotmat and share_feature variants are not served by the native session")
@@ -60,6 +64,13 @@ class InferenceSession:
         with torch.cuda.device(self.device):
             self._workspace = torch.empty(self.workspace_bytes, dtype=torch.uint8, device=self.device)
         self._views_arr = (C.c_void_p * self.views)()
+        self.range_unit_names: List[str] = [lib().mvg_session_range_unit_name(h, i).decode()
+                                            for i in range(lib().mvg_session_num_range_units(h))]
+        self._range_record: Optional[Tensor] = None
+        if range_record and self.range_unit_names:
+            with torch.cuda.device(self.device):
+                self._range_record = torch.zeros(len(self.range_unit_names), dtype=torch.int32, device=self.device)
+            check(lib().mvg_session_set_range_record(h, C.c_void_p(self._range_record.data_ptr())), "session_set_range_record")
         self.refresh()
 
     # ---------------------------------------------------------------- weights
@@ -124,6 +135,25 @@ class InferenceSession:
                                             C.c_void_p(ops._s())), "session_forward")
         return img_feat, lifted, feats, preds
 
+    # ---------------------------------------------------------------- activation range record
+    def range_report(self):
+        """{conv name: max |activation| of the sp tensor its unit stored} in the last forward, in forward order; empty when the
+        backbone is not on the split kernels.  Needs ``range_record=True``.  Synchronises."""
+        if self._range_record is None:
+            if self.range_unit_names:
+                raise RuntimeError("InferenceSession: made without range_record=True")
+            return {}
+        vals = self._range_record.cpu().view(torch.float32).tolist()
+        return dict(zip(self.range_unit_names, vals))
+
+    def overflowed(self) -> List[str]:
+        """The units of ``range_report()`` whose tensor reached 65 520 (an fp16 piece became inf), in forward order.  Synchronises."""
+        if self._range_record is None:
+            if self.range_unit_names:
+                raise RuntimeError("InferenceSession: made without range_record=True")
+            return []
+        return [n for n, w in zip(self.range_unit_names, self._range_record.tolist()) if w >= RANGE_OVER_BITS]
+
     # ---------------------------------------------------------------- lifetime
     def close(self) -> None:
         """Destroy the handle and drop the workspace (stream-ordered: queued forwards still finish)."""
@@ -131,6 +161,7 @@ class InferenceSession:
             lib().mvg_session_destroy(self._h)
             self._h = None
             self._workspace = None
+            self._range_record = None
 
     def __del__(self):
         try:
