@@ -777,7 +777,14 @@ int mvg_split_colsum(const float *g, int rows, int cols, const float *absmax, vo
  * 2 GiB - decided from the cfg's real sizes -, split-operand fuser / head Linears from 1024 rows), 0 = the fp32-MFMA kernels
  * everywhere (MVG_SPLIT=0).  raw_u8: the views are uint8 [batch][in_h][in_w][3] patches put through
  * mvg_preprocess_u8hwc_resize (mean / std of main.py:38-39) instead of fp32 [batch][3][height][width] images.
- * Not representable: the encode_rotmat and share_feature variants, the bf16 storage path, training. */
+ *
+ * Two compute forms (mvg_session_create_ex): MVG_SESSION_FP32, the above, and MVG_SESSION_BF16, the eval-mode forward of the
+ * bf16 storage path as the module queues it with compute_dtype = bfloat16 - uint8 patches or fp32 images straight to the bf16
+ * NHWC8 stem input, the stem as mvg_conv_fprop_bf16 + mvg_bn_relu_maxpool_fwd_bf16, every residual unit one
+ * mvg_conv_fprop_bf16_affine, mvg_avgpool_fwd_bf16, and the lifter / fuser / head Linears on mvg_linear_fprop_mixed over
+ * materialised mvg_rotcat_fwd inputs.  Its workspace holds bf16 weight copies (KRSC only, the stem's 3 channels padded to 8)
+ * and a 2-byte activation arena; split is ignored; there are no range units.  Bit-identical to the module, like the fp32 form.
+ * Not representable: the encode_rotmat and share_feature variants, training. */
 typedef struct mvg_session mvg_session;
 typedef struct {
   int32_t depth;          /* 18 | 50 */
@@ -794,6 +801,14 @@ typedef struct {
  * decisions and the buffer plan, and checks the plan.  Non-zero + mvg_last_error() for a configuration outside the scope;
  * *out is NULL then. */
 int mvg_session_create(const mvg_session_cfg *cfg, mvg_session **out);
+/* HOST ONLY.  mvg_session_create with the compute form chosen: mvg_session_create(cfg, out) is
+ * mvg_session_create_ex(cfg, MVG_SESSION_FP32, out).  MVG_SESSION_BF16 accepts and ignores cfg->split, and also rejects here
+ * every shape one of the bf16 entry points would reject in mvg_session_forward.  Any other `compute` is rejected.
+ * mvg_session_compute returns the form a handle was made for (-1 for NULL). */
+#define MVG_SESSION_FP32 0
+#define MVG_SESSION_BF16 1
+int mvg_session_create_ex(const mvg_session_cfg *cfg, int32_t compute, mvg_session **out);
+int mvg_session_compute(const mvg_session *s);
 /* Frees the handle (host memory only; the workspace is the caller's).  NULL is allowed. */
 void mvg_session_destroy(mvg_session *s);
 /* The model tensors the session reads, by state_dict key, in the order mvg_session_bind takes their pointers: per conv
@@ -806,10 +821,16 @@ int64_t mvg_session_tensor_numel(const mvg_session *s, int i);
 size_t mvg_session_workspace_bytes(const mvg_session *s);
 /* Library calls one mvg_session_forward queues (host only; a stream-K / split-K GEMM adds its fix-up kernel on the device). */
 int mvg_session_launches(const mvg_session *s);
+/* The plan's steps in the order mvg_session_forward queues them (host only, both forms): how many, and the entry point step
+ * i calls, without the "mvg_" prefix, e.g. "conv_fprop_bf16_affine" (a step that records ranges still names the plain entry
+ * point; the split head path's slot clear is "memset").  NULL out of range. */
+int mvg_session_num_steps(const mvg_session *s);
+const char *mvg_session_step_name(const mvg_session *s, int i);
 /* host_tensor_ptrs: a HOST array of mvg_session_num_tensors() device pointers (fp32, contiguous; conv weights KRSC).
  * workspace: 256-byte aligned device memory of at least mvg_session_workspace_bytes().  Queues on `stream` the work that
  * depends on the weights only: the index tables, the stem filter padded to 4 channels, every sp weight copy (two
- * mvg_weights_prep_batch calls) and every BatchNorm fold (one mvg_bn_eval_affine_batch).  Call it again after the
+ * mvg_weights_prep_batch calls; MVG_SESSION_BF16: the bf16 copies, mode 0, and no padded stem filter) and every BatchNorm
+ * fold (one mvg_bn_eval_affine_batch).  Call it again after the
  * weights changed (same or new pointers).  Forwards must be ordered after it (same stream, or an event). */
 int mvg_session_bind(mvg_session *s, const void *const *host_tensor_ptrs, void *workspace, size_t bytes, void *stream);
 /* Queues one forward on `stream`: only the launches that depend on the input.  host_view_ptrs: a HOST array of `views`
@@ -821,7 +842,7 @@ int mvg_session_forward(mvg_session *s, const void *const *host_view_ptrs, const
 /* The activation range record of a session whose backbone runs on the split kernels (mvg_conv_fprop_split_affine_ranged):
  * one 32-bit word per sp tensor the forward stores - the stem's pooled map (named by the stem's conv), then every block
  * conv in forward order; the downsample branches stay fp32 and have none.  _num_range_units (host only): how many, 0 when
- * the backbone is not on the split kernels (split = 0, or the 2 GiB guard); _range_unit_name (host only): the conv's
+ * the backbone is not on the split kernels (split = 0, the 2 GiB guard, or MVG_SESSION_BF16); _range_unit_name (host only): the conv's
  * state_dict prefix, NULL out of range.  _set_range_record (host only: the pointer is only stored): record_dev = device
  * memory of _num_range_units words, or NULL (the default) for no record.  With a record mvg_session_forward clears it with
  * one stream-ordered memset and calls the ranged entry points: same mvg_session_launches, same outputs, still no

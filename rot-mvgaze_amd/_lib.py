@@ -13,6 +13,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "librotmvgaze_hip.so")
 
 K_FAMILIES = 18
 ABI_VERSION = 11
+SESSION_FP32, SESSION_BF16 = 0, 1         # MVG_SESSION_FP32 / MVG_SESSION_BF16 (mvg_session_create_ex)
 
 
 class ConvDesc(C.Structure):
@@ -214,6 +215,11 @@ SIGNATURES = {
     "mvg_session_num_range_units": (_I, [_P]),
     "mvg_session_range_unit_name": (C.c_char_p, [_P, _I]),
     "mvg_session_set_range_record": (_I, [_P, _P]),
+    # the session's compute forms (fp32 | bf16) and its step list
+    "mvg_session_create_ex": (_I, [C.POINTER(SessionCfg), C.c_int32, C.POINTER(_P)]),
+    "mvg_session_compute": (_I, [_P]),
+    "mvg_session_num_steps": (_I, [_P]),
+    "mvg_session_step_name": (C.c_char_p, [_P, _I]),
 }
 
 _lib = None

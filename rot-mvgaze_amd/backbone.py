@@ -401,8 +401,8 @@ class Backbone:
         """Folded inference unit (no tape, not training, not the unfolded bf16 form): conv with BatchNorm on the running
         statistics (+ residual) (+ ReLU) in its epilogue - ONE launch, the output written once.  Returns the unit's output;
         pool (the fp32 stem): the max-pooled map, in sp when the split kernels serve the call.
-        csrc/session_plan.cpp restates this method (its unit()) and _forward_infer (its block loop) as data for the fp32
-        model: a change to the launches here must be made there too."""
+        csrc/session_plan.cpp restates this method (its unit()) and _forward_infer (its block loop) as data, for the fp32
+        model (build) and for the bf16 branch (build_bf16): a change to the launches here must be made there too."""
         bf = self.bf16
         assert not (bf and pool)                 # the bf16 stem goes through _unit_fwd
         d = ConvDesc.make(G, N, H, W, 4 if c.cin == 3 else c.cin, c.cout, c.k, c.stride, c.pad)
@@ -474,6 +474,8 @@ class Backbone:
         """conv -> BatchNorm (-> + residual) (-> ReLU), the BatchNorm as passes of its own: batch statistics (training) or
         the running ones (eval mode with a tape; bf16 inference that is not folded; the bf16 inference stem).  Returns _Fwd.
         pool=True (the stem): the 3x3/2 max pool is fused behind the ReLU - out is the pooled map; the normalised map is not stored.
+        The non-training pool=True branch on the bf16 path - conv_fprop without statistics, bn_eval_affine over G rows,
+        _stem_tail - is restated as the stem of csrc/session_plan.cpp's build_bf16: a change here is made there too.
         defer_apply (the downsample branch): stop after the statistics - out is the raw conv output y and affine its
         (scale, shift): the normalisation is applied by the consumer, the block's last unit, which takes them as
         residual / residual_affine; the normalised downsample map is never written.
@@ -568,7 +570,8 @@ class Backbone:
     def _input_layout(self, imgs: List[Tensor], B: int, H: int, W: int, input_bgr: bool) -> Tensor:
         """x0, the stem's input operand, one launch per view: row windows straight from the NCHW input when the stem runs in
         row-window form (no NHWC image is built); else the NHWC image padded to 4 (bf16: 8) channels, from raw uint8 patches
-        or NCHW fp32 - and the windows from that image for raw input with a row-window stem."""
+        or NCHW fp32 - and the windows from that image for raw input with a row-window stem.
+        (The bf16 branch without a row-window stem is restated by csrc/session_plan.cpp's build_bf16.)"""
         V, dev, bf = len(imgs), imgs[0].device, self.bf16
         raw = imgs[0].dtype == torch.uint8
         direct = self._stem_rw and not raw
@@ -676,7 +679,8 @@ class Backbone:
 
     def _forward_infer(self, x0: Tensor, V: int, B: int, H: int, W: int) -> Tensor:
         """Stem and residual blocks of the folded inference forward (see _unit_infer), in the order csrc/session_plan.cpp
-        states: conv1 up to the last conv, the downsample branch as a normalised residual, the last conv with residual + ReLU."""
+        states (build for the fp32 model, build_bf16 for the bf16 path): conv1 up to the last conv, the downsample branch as a
+        normalised residual, the last conv with residual + ReLU."""
         s = self.spec
         if self.bf16:         # the bf16 stem keeps the training-shaped launches: conv, then BatchNorm + ReLU + max pool in one pass
             x = self._unit_fwd(s.stem, x0, V, B, H, W, False, True, None, None, pool=True).out

@@ -1,7 +1,8 @@
 // The inference session's executor: mvg_session_bind queues what depends on the weights only, mvg_session_forward walks the
 // plan (session_plan.cpp) and queues one existing entry point per step - the same functions, with the same arguments, the
 // Python module calls, so launch plans, stream-K decisions and ProfScope accounting are theirs.  No launch logic lives here;
-// the three kernels below are table / layout plumbing of bind.
+// the three kernels below are table / layout plumbing of bind.  Both compute forms of the plan (fp32, bf16) run through the same
+// executor: the form only decides which steps the plan holds and which weight copies bind queues.
 #include "common.h"
 #include "session_plan.h"
 
@@ -148,6 +149,20 @@ static int run_step(const mvg_session *s, const FwdArgs &a, const SStep &t, void
                                   F(9), F(10), F(11), i[0], i[1], 512, stream);
     case SOP_LINEAR_SPLIT:
       return mvg_linear_fprop_split(i[0], i[1], i[2], p[0], F(1), p[2], F(3), F(4), i[3], p[5], i[4], F(6), F(7), F(8), stream);
+    // ---- the bf16 form
+    case SOP_NCHW_TO_NHWC8_BF16: return mvg_nchw_to_nhwc8_bf16(F(0), (uint16_t *)p[1], i[0], i[1], i[2], i[3], stream);
+    case SOP_PREPROCESS_U8_BF16:
+      return mvg_preprocess_u8hwc_resize_bf16((const uint8_t *)p[0], (uint16_t *)p[1], i[0], i[1], i[2], i[3], i[4], IMAGE_MEAN[0],
+                                              IMAGE_MEAN[1], IMAGE_MEAN[2], IMAGE_STD[0], IMAGE_STD[1], IMAGE_STD[2], i[5], stream);
+    case SOP_CONV_BF16: return mvg_conv_fprop_bf16(&t.d, p[0], p[1], p[2], nullptr, 0, nullptr, stream);
+    case SOP_BN_RELU_MAXPOOL_BF16:
+      return mvg_bn_relu_maxpool_fwd_bf16((const uint16_t *)p[0], F(1), F(2), (uint16_t *)p[3], (uint8_t *)p[4], i[0], i[1], i[2], i[3],
+                                          i[4], (int)t.cnt[0], (int)t.cnt[1], stream);
+    case SOP_CONV_BF16_AFFINE: return mvg_conv_fprop_bf16_affine(&t.d, p[0], p[1], p[2], F(3), F(4), p[5], i[0], stream);
+    case SOP_AVGPOOL_BF16: return mvg_avgpool_fwd_bf16((const uint16_t *)p[0], F(1), i[0], i[1], i[2], stream);
+    case SOP_LINEAR_MIXED: return mvg_linear_fprop_mixed(F(0), p[1], F(2), i[0], F(3), i[1], i[2], i[3], stream);
+    case SOP_ROTCAT:
+      return mvg_rotcat_fwd(F(0), F(1), F(2), (const int32_t *)p[3], (const int32_t *)p[4], F(5), i[0], i[1], i[2], i[3], stream);
   }
   set_error("session_forward: unknown step %d", t.op);
   return 2;
@@ -181,19 +196,23 @@ int mvg_session_bind(mvg_session *s, const void *const *host_tensor_ptrs, void *
   s->bound_stream = stream;
   hipStream_t st = (hipStream_t)stream;
   auto T = [&](int k) { return (const float *)s->tensor_ptrs[k]; };
+  const bool bf16 = pl.compute == MVG_SESSION_BF16;
 
   // the record tables
   std::vector<BnEvalRecord> folds(pl.folds.size());
   for (size_t k = 0; k < folds.size(); ++k) {
     const SBnFold &f = pl.folds[k];
     float *aff = (float *)buf_ptr(s, pl.buf_affine, f.aff_off);
-    folds[k] = {T(f.gamma), T(f.gamma + 1), T(f.gamma + 2), T(f.gamma + 3), aff, aff + f.c, f.c, 0};
+    float *shift = f.shift_off >= 0 ? (float *)buf_ptr(s, pl.buf_affine, f.shift_off) : aff + f.c;
+    folds[k] = {T(f.gamma), T(f.gamma + 1), T(f.gamma + 2), T(f.gamma + 3), aff, shift, f.c, 0};
   }
   auto records = [&](const std::vector<SWPrep> &src) {
     std::vector<WPrepRecord> out(src.size());
     for (size_t k = 0; k < src.size(); ++k) {
       const SWPrep &w = src[k];
-      out[k] = {T(w.tensor), buf_ptr(s, pl.buf_wk, w.wk_off), nullptr, w.cout, w.rs, w.cin, w.cin, (float *)buf_ptr(s, pl.buf_wstat, 8LL * w.stat)};
+      // (bf16 form, mode 0: cin zero-padded to cin_pad, no statistics)
+      out[k] = {T(w.tensor), buf_ptr(s, pl.buf_wk, w.wk_off), nullptr, w.cout, w.rs, w.cin, w.cin_pad ? w.cin_pad : w.cin,
+                bf16 ? nullptr : (float *)buf_ptr(s, pl.buf_wstat, 8LL * w.stat)};
     }
     return out;
   };
@@ -221,15 +240,29 @@ int mvg_session_bind(mvg_session *s, const void *const *host_tensor_ptrs, void *
                        R(pl.rows_view), R(pl.rows_partner), R(pl.rows_ident));
     if (check_launch("session_bind: row tables")) return 1;
   }
+  if (bf16) {
+    // mvg_rotcat_fwd's per-direction source tables (FusionHead._indices: partner = d ^ 1, ident = d); then the bf16 weight
+    // copies as Backbone._prepare_weights / FusionHead._prepare_split_weights(mixed=True) make them (mode 0; KRSC only:
+    // weights_prep_batch_kernel skips a null transposed pointer in both of its mode-0 branches)
+    int32_t partner[SESSION_MAX_VIEWS * (SESSION_MAX_VIEWS - 1)], ident[SESSION_MAX_VIEWS * (SESSION_MAX_VIEWS - 1)];
+    for (int k = 0; k < pl.dirs; ++k) {
+      partner[k] = k ^ 1;
+      ident[k] = k;
+    }
+    if (stage(partner, (size_t)pl.dirs * 4, buf_ptr(s, pl.buf_dirs, pl.dirs_partner), st)) return 1;
+    if (stage(ident, (size_t)pl.dirs * 4, buf_ptr(s, pl.buf_dirs, pl.dirs_ident), st)) return 1;
+    if (int e = mvg_weights_prep_batch(buf_ptr(s, pl.buf_tables, pl.tab_wprep_backbone), (int)wb.size(), 0, 0, stream)) return e;
+    if (int e = mvg_weights_prep_batch(buf_ptr(s, pl.buf_tables, pl.tab_wprep_head), (int)wh.size(), 0, 256, stream)) return e;
+  }
   // the stem's filter, 3 -> 4 channels
-  {
+  if (!bf16) {
     const int taps = pl.stem_cout * 49;
     hipLaunchKernelGGL(session_pad_stem_kernel, dim3((unsigned)ceil_div(taps, 256)), dim3(256), 0, st, T(pl.stem_weight),
                        (float *)buf_ptr(s, pl.buf_w4), taps);
     if (check_launch("session_bind: stem filter")) return 1;
   }
   // sp weight copies: the max |w| slots are atomicMax targets and start at zero
-  if (!wb.empty() || !wh.empty()) {
+  if (!bf16 && (!wb.empty() || !wh.empty())) {
     if (hipMemsetAsync(buf_ptr(s, pl.buf_wstat), 0, (size_t)pl.bufs[pl.buf_wstat].bytes, st) != hipSuccess) {
       (void)hipGetLastError();
       set_error("session_bind: clearing the weight statistics failed");

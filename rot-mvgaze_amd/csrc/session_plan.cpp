@@ -6,6 +6,10 @@
 // Backbone._forward_infer's unit order (backbone.py: conv1.., downsample, last conv with the residual), FusionHead.forward's
 // choice between the generated-input fp32-MFMA Linears and _forward_split (heads.py: D * B >= 1024 rows).  Every step is one
 // call of an existing entry point; session.hip executes them.
+//
+// build_bf16 below restates the same forward for the bf16 storage path (MVG_SESSION_BF16): the bf16 branches of
+// Backbone._input_layout, _forward_infer, _unit_infer and the non-training pool=True branch of _unit_fwd (backbone.py), and the
+// `mixed` branch of FusionHead.forward with Mlp._use_mixed per layer (heads.py).
 #include <limits.h>
 #include <stdio.h>
 #include <string.h>
@@ -675,14 +679,361 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
   return 0;
 }
 
+// ---- the bf16 form.  What the bf16 entry points require of a launch, restated so that create rejects what forward would
+// (conv_shared.h: validate, fprop_geometry; conv_bf16.hip: validate_bf16, fprop_bf16_impl, launch_igemm_bf16).  a_elem: bytes
+// per element of the gathered operand (2: bf16 activations; 4: the fp32 rows of mvg_linear_fprop_mixed).
+bool bf16_conv_ok(const mvg_conv_desc &d, int a_elem, const char *what) {
+  auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
+  const int64_t rows = (int64_t)d.n * d.ho * d.wo, src = (int64_t)d.n * d.h * d.w;
+  const char *why = nullptr;
+  if (d.ho < 1 || d.wo < 1) why = "an empty output map";
+  else if (d.cin % 8 != 0 || d.cout % 8 != 0) why = "cin and cout must be multiples of 8";
+  else if (d.r * d.s > 1 && !(pow2(d.cin) && pow2(d.cout))) why = "a filter larger than 1x1 needs power-of-two channels";
+  else if (rows >= (1LL << 31) || src >= (1LL << 31)) why = "the rows of a group overflow 32 bits";
+  else if (a_elem * src * d.cin >= 0x7FFFFFF0LL || 2LL * d.cout * d.r * d.s * d.cin >= 0x7FFFFFF0LL) why = "a group of the input, or the weights, reach 2 GiB";
+  else if (rows * d.cout >= (1LL << 31)) why = "a group of the output reaches 2^31 elements";
+  else if ((int64_t)d.groups * ((rows + 127) / 128) * ((d.cout + (d.cout >= 128 ? 127 : 63)) / (d.cout >= 128 ? 128 : 64)) >= (1LL << 31))
+    why = "the grid is too large";
+  if (why) set_error("session_create (bf16): %s [%d x %d x %d x %d x %d -> %d, %dx%d / %d]: %s", what, d.groups, d.n, d.h, d.w, d.cin,
+                     d.cout, d.r, d.s, d.stride, why);
+  return why == nullptr;
+}
+
+// The plan of the bf16 inference form: what MultiViewGaze.run_views queues with compute_dtype = torch.bfloat16 under eval() /
+// no_grad() with Backbone.bf16_fold_eval.  A change to the bf16 launches of backbone.py / heads.py is made here too.
+int build_bf16(const mvg_session_cfg &c, SessionPlan &p) {
+  Builder B(p);
+  p.compute = MVG_SESSION_BF16;
+  const int V = c.views, N = c.batch, H = c.height, W = c.width, I = c.num_iter;
+  ConvSpec stem;
+  std::vector<BlockSpec> blocks;
+  int cf = 0;
+  backbone_spec(c.depth, stem, blocks, cf);
+  p.fc_dim = cf;
+  const int D = V * (V - 1), rows = D * N;
+  p.dirs = D;
+  p.head_rows = rows;
+
+  // ---- tensors, in state_dict order; one bf16 KRSC copy per conv (Backbone._prepare_weights, mode 0: every conv of
+  // spec.all_convs(), the stem's 3 channels padded to 8) and one fold per BatchNorm
+  struct ConvT {
+    ConvSpec s;
+    int t = 0, fold = -1, wprep = -1;
+  };
+  std::vector<ConvT> convs;
+  int64_t aff_bytes = 0, wk_bytes = 0;
+  auto prep = [&](std::vector<SWPrep> &to, int tensor, int cout, int rs, int cin, int cin_pad) {
+    SWPrep w;
+    w.tensor = tensor;
+    w.cout = cout;
+    w.rs = rs;
+    w.cin = cin;
+    w.cin_pad = cin_pad;
+    w.wk_off = wk_bytes;
+    wk_bytes += align_up((int64_t)cout * rs * cin_pad * 2);
+    to.push_back(w);
+    return (int)to.size() - 1;
+  };
+  auto add_conv = [&](const ConvSpec &s, bool is_stem) {
+    ConvT ct;
+    ct.s = s;
+    ct.t = B.add_tensor(s.name + ".weight", (int64_t)s.cout * s.cin * s.k * s.k);
+    B.add_tensor(s.bn + ".weight", s.cout);
+    B.add_tensor(s.bn + ".bias", s.cout);
+    B.add_tensor(s.bn + ".running_mean", s.cout);
+    B.add_tensor(s.bn + ".running_var", s.cout);
+    p.max_c = std::max(p.max_c, s.cout);
+    ct.fold = (int)p.folds.size();
+    // the stem's pass reads [V][cout] rows (Backbone._unit_fwd folds it with G = V): V records of the same BatchNorm, the
+    // scale rows first, then the shift rows; every other unit one row, shift behind scale
+    const int nrec = is_stem ? V : 1;
+    for (int v = 0; v < nrec; ++v) {
+      SBnFold f;
+      f.gamma = ct.t + 1;
+      f.c = s.cout;
+      f.aff_off = aff_bytes + 4LL * s.cout * v;
+      f.shift_off = aff_bytes + 4LL * s.cout * (nrec + v);
+      p.folds.push_back(f);
+    }
+    aff_bytes += align_up(2LL * nrec * s.cout * 4);
+    ct.wprep = prep(p.wprep_backbone, ct.t, s.cout, s.k * s.k, s.cin, s.cin == 3 ? 8 : s.cin);
+    convs.push_back(ct);
+    return (int)convs.size() - 1;
+  };
+  const int ci_stem = add_conv(stem, true);
+  std::vector<std::vector<int>> blk_convs(blocks.size());
+  std::vector<int> blk_ds(blocks.size(), -1);
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    for (const ConvSpec &s : blocks[b].convs) blk_convs[b].push_back(add_conv(s, false));
+    if (blocks[b].has_ds) blk_ds[b] = add_conv(blocks[b].ds, false);
+  }
+  struct Lin {
+    int w = 0, b = 0, fin = 0, fout = 0, wprep = -1;
+  };
+  auto add_lin = [&](const std::string &name, int fin, int fout) {
+    Lin l;
+    l.fin = fin;
+    l.fout = fout;
+    l.w = B.add_tensor(name + ".weight", (int64_t)fout * fin);
+    l.b = B.add_tensor(name + ".bias", fout);
+    return l;
+  };
+  const int kin = cf + ROT_DIM;
+  Lin lift0 = add_lin("_lifter._lifter.blocks.0.0", cf, ROT_DIM), lift1 = add_lin("_lifter._lifter.blocks.1.0", ROT_DIM, ROT_DIM);
+  const int nmod = c.share_weights ? 1 : I;
+  std::vector<Lin> fu0(nmod), fu1(nmod), hd0(nmod), hd1(nmod);
+  for (int i = 0; i < nmod; ++i) {
+    const std::string pre = "_img_fusers." + std::to_string(i) + "._fuser.blocks.";
+    fu0[i] = add_lin(pre + "0.0", kin, kin);
+    fu1[i] = add_lin(pre + "1.0", kin, ROT_DIM);
+  }
+  for (int i = 0; i < nmod; ++i) {
+    const std::string pre = "_gaze_estimators." + std::to_string(i) + ".blocks.";
+    hd0[i] = add_lin(pre + "0.0", kin, HEAD_HID);
+    hd1[i] = add_lin(pre + "1.0", HEAD_HID, 2);
+  }
+  // Mlp._use_mixed: a layer runs on mvg_linear_fprop_mixed unless it is padded (a width that is no multiple of 4: none in
+  // the variants a session serves) or it is a module's last layer with fout <= 4 (the heads' 512 -> 2: mvg_linear_skinny_fwd)
+  auto use_mixed = [](const Lin &l, bool last) { return l.fin % 4 == 0 && l.fout % 4 == 0 && !(last && l.fout <= 4); };
+  // FusionHead._prepare_split_weights(mixed=True): the lifter, then heads and fusers from the last iteration down
+  auto prep_lin = [&](Lin &l, bool last) {
+    if (use_mixed(l, last)) l.wprep = prep(p.wprep_head, l.w, l.fout, 1, l.fin, l.fin);
+  };
+  prep_lin(lift0, false);
+  prep_lin(lift1, true);
+  for (int i = nmod - 1; i >= 0; --i) {
+    prep_lin(hd0[i], false);
+    prep_lin(hd1[i], true);
+    prep_lin(fu0[i], false);
+    prep_lin(fu1[i], true);
+  }
+  if (!use_mixed(lift0, false) || !use_mixed(lift1, true) || use_mixed(hd1[0], true)) {
+    set_error("session_create (bf16): a Linear of this model is not on the path the session restates");
+    return 2;
+  }
+
+  // ---- persistent buffers (bind writes them)
+  p.tab_folds = 0;
+  p.tab_wprep_backbone = align_up((int64_t)p.folds.size() * 56);
+  p.tab_wprep_head = p.tab_wprep_backbone + align_up((int64_t)p.wprep_backbone.size() * 48);
+  p.tab_bytes = p.tab_wprep_head + align_up((int64_t)p.wprep_head.size() * 48);
+  p.buf_tables = B.new_buf(p.tab_bytes, "record tables", true);
+  const int64_t rt = align_up((int64_t)rows * 4), dt = align_up((int64_t)D * 4);
+  p.rows_vi = 0;
+  p.rows_vj = dt;
+  p.rows_img = 2 * dt;
+  p.rows_view = 2 * dt + rt;
+  p.rows_partner = 2 * dt + 2 * rt;
+  p.rows_ident = 2 * dt + 3 * rt;
+  p.buf_rows = B.new_buf(2 * dt + 4 * rt, "pair / row tables", true);
+  p.dirs_partner = 0;
+  p.dirs_ident = dt;
+  p.buf_dirs = B.new_buf(2 * dt, "direction tables (partner, ident)", true);
+  p.buf_affine = B.new_buf(aff_bytes, "folded BatchNorm (scale, shift)", true);
+  p.buf_wk = B.new_buf(wk_bytes, "bf16 weight copies (KRSC)", true);
+  p.buf_scratch = B.new_buf((int64_t)SESSION_SCRATCH_BYTES, "scratch", true);
+
+  auto scale_of = [&](int ci) { return B.ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].aff_off); };
+  auto shift_of = [&](int ci) { return B.ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].shift_off); };
+  auto wk_of = [&](const SWPrep &w) { return B.ref(SR_BUF, p.buf_wk, w.wk_off); };
+  auto act_bytes = [&](int h, int w, int ch) { return (int64_t)V * N * h * w * ch * 2; };
+
+  // ---- input layout (Backbone._input_layout, bf16; no row-window stem outside training): V launches into x0 [V][B][H][W][8]
+  const int x0 = B.new_buf(act_bytes(H, W, 8), "input NHWC8 (bf16)");
+  for (int v = 0; v < V; ++v) {
+    SStep s;
+    s.op = c.raw_u8 ? SOP_PREPROCESS_U8_BF16 : SOP_NCHW_TO_NHWC8_BF16;
+    s.r[0] = B.ref(SR_VIEW, v);
+    s.r[1] = B.buf(x0, (int64_t)v * N * H * W * 8 * 2);
+    if (c.raw_u8) {
+      s.i[0] = N; s.i[1] = c.in_h; s.i[2] = c.in_w; s.i[3] = H; s.i[4] = W; s.i[5] = c.input_bgr ? 1 : 0;
+    } else {
+      s.i[0] = N; s.i[1] = 3; s.i[2] = H; s.i[3] = W;
+    }
+    B.push(s);
+  }
+
+  // ---- stem (Backbone._unit_fwd, pool=True, not training): the raw conv output, then BatchNorm + ReLU + max pool in one pass
+  const mvg_conv_desc dstem = make_desc(V, N, H, W, 8, stem.cout, stem.k, stem.stride, stem.pad);
+  if (!bf16_conv_ok(dstem, 2, "the stem")) return 2;
+  const int hp = (dstem.ho + 2 - 3) / 2 + 1, wp = (dstem.wo + 2 - 3) / 2 + 1;
+  if ((int64_t)V * N * hp >= 65536) {          // mvg_bn_relu_maxpool_fwd_bf16: images x pooled rows is a grid dimension
+    set_error("session_create (bf16): views x batch x pooled rows = %lld (the stem's pooling pass serves fewer than 65536)",
+              (long long)V * N * hp);
+    return 2;
+  }
+  struct Map {               // a bf16 activation of the backbone: a buffer holding [V][B][h][w][c]
+    int buf = -1, h = 0, w = 0, c = 0;
+  };
+  Map x;
+  {
+    const int ystem = B.new_buf(act_bytes(dstem.ho, dstem.wo, stem.cout), "stem conv output (bf16)");
+    SStep s;
+    s.op = SOP_CONV_BF16;
+    s.d = dstem;
+    s.r[0] = B.buf(x0);
+    s.r[1] = wk_of(p.wprep_backbone[convs[ci_stem].wprep]);
+    s.r[2] = B.buf(ystem);
+    B.push(s);
+    const int pooled = B.new_buf(act_bytes(hp, wp, stem.cout), "pooled map (bf16)");
+    const int argmax = B.new_buf((int64_t)V * N * hp * wp * stem.cout, "pool argmax");
+    SStep t;
+    t.op = SOP_BN_RELU_MAXPOOL_BF16;
+    t.r[0] = B.buf(ystem);
+    t.r[1] = scale_of(ci_stem);
+    t.r[2] = shift_of(ci_stem);
+    t.r[3] = B.buf(pooled);
+    t.r[4] = B.buf(argmax);
+    t.i[0] = V; t.i[1] = N; t.i[2] = dstem.ho; t.i[3] = dstem.wo; t.i[4] = stem.cout;
+    t.cnt[0] = hp; t.cnt[1] = wp;
+    B.push(t);
+    x.buf = pooled;
+    x.h = hp;
+    x.w = wp;
+    x.c = stem.cout;
+  }
+
+  // ---- residual blocks.  unit() = Backbone._unit_infer's bf16 branch (one mvg_conv_fprop_bf16_affine); the loop =
+  // Backbone._forward_infer
+  bool bad = false;
+  auto unit = [&](int ci, const Map &in, bool relu, const Map *residual) {
+    const ConvSpec &cs = convs[ci].s;
+    const mvg_conv_desc d = make_desc(V, N, in.h, in.w, cs.cin, cs.cout, cs.k, cs.stride, cs.pad);
+    if (!bad && !bf16_conv_ok(d, 2, cs.name.c_str())) bad = true;
+    Map out;
+    out.h = std::max(d.ho, 1);
+    out.w = std::max(d.wo, 1);
+    out.c = cs.cout;
+    out.buf = B.new_buf(act_bytes(out.h, out.w, out.c), "unit output (bf16)");
+    SStep s;
+    s.op = SOP_CONV_BF16_AFFINE;
+    s.d = d;
+    s.r[0] = B.buf(in.buf);
+    s.r[1] = wk_of(p.wprep_backbone[convs[ci].wprep]);
+    s.r[2] = B.buf(out.buf);
+    s.r[3] = scale_of(ci);
+    s.r[4] = shift_of(ci);
+    if (residual) s.r[5] = B.buf(residual->buf);
+    s.i[0] = relu ? 1 : 0;
+    B.push(s);
+    return out;
+  };
+  for (size_t b = 0; b < blocks.size(); ++b) {
+    Map identity = x, out = x;
+    const std::vector<int> &cv = blk_convs[b];
+    for (size_t k = 0; k + 1 < cv.size(); ++k) out = unit(cv[k], out, true, nullptr);
+    if (blk_ds[b] >= 0) identity = unit(blk_ds[b], x, false, nullptr);
+    x = unit(cv.back(), out, true, &identity);
+  }
+  if (bad) return 2;
+  {
+    SStep s;
+    s.op = SOP_AVGPOOL_BF16;
+    s.r[0] = B.buf(x.buf);
+    s.r[1] = B.ref(SR_IMG_FEAT);
+    s.i[0] = V * N; s.i[1] = x.h * x.w; s.i[2] = cf;
+    B.push(s);
+  }
+
+  // ---- FusionHead.forward, mixed: lifter, relative rotations, then per iteration the materialised fuser input
+  // (_fuser_input: mvg_rotcat_fwd), the fuser, the materialised head input (_head_input), the head
+  auto linear = [&](const SRef &xin, const Lin &l, bool last, const SRef &y, int r) {
+    const mvg_conv_desc d = make_desc(1, r, 1, 1, l.fin, l.fout, 1, 1, 0);
+    if (!bad && !bf16_conv_ok(d, 4, "a Linear")) bad = true;
+    SStep s;
+    s.op = SOP_LINEAR_MIXED;
+    s.r[0] = xin;
+    s.r[1] = wk_of(p.wprep_head[l.wprep]);
+    s.r[2] = B.tensor(l.b);
+    s.r[3] = y;
+    s.i[0] = last ? 0 : 1; s.i[1] = r; s.i[2] = l.fin; s.i[3] = l.fout;       // (ReLU on every layer but a module's last)
+    B.push(s);
+  };
+  const int hl = B.new_buf((int64_t)V * N * ROT_DIM * 4, "lifter hidden");
+  linear(B.ref(SR_IMG_FEAT), lift0, false, B.buf(hl), V * N);
+  linear(B.buf(hl), lift1, true, B.ref(SR_LIFTED), V * N);
+  const int rel = B.new_buf((int64_t)rows * 9 * 4, "relative rotations");
+  const SRef t_vi = B.ref(SR_BUF, p.buf_rows, p.rows_vi), t_vj = B.ref(SR_BUF, p.buf_rows, p.rows_vj),
+             t_partner = B.ref(SR_BUF, p.buf_dirs, p.dirs_partner), t_ident = B.ref(SR_BUF, p.buf_dirs, p.dirs_ident);
+  {
+    SStep s;
+    s.op = SOP_RELROT;
+    s.r[0] = B.ref(SR_ROT);
+    s.r[1] = t_vi;
+    s.r[2] = t_vj;
+    s.r[3] = B.buf(rel);
+    s.i[0] = N; s.i[1] = V; s.i[2] = D;
+    B.push(s);
+  }
+  auto rotcat = [&](const SRef &feat, bool rotate, const SRef &src_of, int xbuf) {
+    SStep s;
+    s.op = SOP_ROTCAT;
+    s.r[0] = B.ref(SR_IMG_FEAT);
+    s.r[1] = feat;
+    if (rotate) s.r[2] = B.buf(rel);
+    s.r[3] = t_vi;
+    s.r[4] = src_of;
+    s.r[5] = B.buf(xbuf);
+    s.i[0] = N; s.i[1] = D; s.i[2] = cf; s.i[3] = NVEC;
+    B.push(s);
+  };
+  const int64_t feat_it = (int64_t)rows * ROT_DIM * 4, pred_it = (int64_t)rows * 2 * 4, xbytes = (int64_t)rows * kin * 4;
+  for (int it = 0; it < I; ++it) {
+    const int m = c.share_weights ? 0 : it;
+    const SRef src = it == 0 ? B.ref(SR_LIFTED) : B.ref(SR_FEATS, 0, (it - 1) * feat_it), fn = B.ref(SR_FEATS, 0, it * feat_it);
+    const int xf = B.new_buf(xbytes, "fuser input"), hf = B.new_buf(xbytes, "fuser hidden");
+    rotcat(src, !c.ignore_rotmat, it == 0 ? t_vj : t_partner, xf);
+    linear(B.buf(xf), fu0[m], false, B.buf(hf), rows);
+    linear(B.buf(hf), fu1[m], true, fn, rows);
+    const int xh = B.new_buf(xbytes, "head input"), hh = B.new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
+    rotcat(fn, false, t_ident, xh);
+    linear(B.buf(xh), hd0[m], false, B.buf(hh), rows);
+    SStep s;
+    s.op = SOP_SKINNY;
+    s.r[0] = B.buf(hh);
+    s.r[1] = B.tensor(hd1[m].w);
+    s.r[2] = B.tensor(hd1[m].b);
+    s.r[3] = B.ref(SR_PREDS, 0, it * pred_it);
+    s.i[0] = rows; s.i[1] = HEAD_HID; s.i[2] = 2;
+    B.push(s);
+  }
+  if (bad) return 2;
+
+  allocate(p);
+  char why[256];
+  if (!self_check(p, why, sizeof(why))) {
+    set_error("session_create: the buffer plan failed its self-check: %s", why);
+    return 3;
+  }
+  return 0;
+}
+
 }  // namespace
+
+namespace mvg {
+const char *sop_name(int op) {
+  static const char *const names[SOP_COUNT] = {
+      "nchw_to_nhwc4", "preprocess_u8hwc_resize", "conv_fprop_affine", "conv_fprop_split_affine", "maxpool3x3s2_fwd", "split_f32",
+      "avgpool_fwd", "avgpool_fwd_split_scaled", "linear_fprop", "fuser_fprop", "linear_skinny_fwd", "relative_rotation", "memset",
+      "absmax_multi", "fuse_build_split", "linear_fprop_split",
+      "nchw_to_nhwc8_bf16", "preprocess_u8hwc_resize_bf16", "conv_fprop_bf16", "bn_relu_maxpool_fwd_bf16", "conv_fprop_bf16_affine",
+      "avgpool_fwd_bf16", "linear_fprop_mixed", "rotcat_fwd"};
+  return op >= 0 && op < SOP_COUNT ? names[op] : nullptr;
+}
+}  // namespace mvg
 
 extern "C" {
 
-int mvg_session_create(const mvg_session_cfg *cfg, mvg_session **out) {
+int mvg_session_create(const mvg_session_cfg *cfg, mvg_session **out) { return mvg_session_create_ex(cfg, MVG_SESSION_FP32, out); }
+
+int mvg_session_create_ex(const mvg_session_cfg *cfg, int32_t compute, mvg_session **out) {
   if (out) *out = nullptr;
   if (!cfg || !out) {
     mvg::set_error("session_create: cfg and out are required");
+    return 2;
+  }
+  if (compute != MVG_SESSION_FP32 && compute != MVG_SESSION_BF16) {
+    mvg::set_error("session_create: compute %d (MVG_SESSION_FP32 = 0 or MVG_SESSION_BF16 = 1)", (int)compute);
     return 2;
   }
   const mvg_session_cfg &c = *cfg;
@@ -716,7 +1067,7 @@ int mvg_session_create(const mvg_session_cfg *cfg, mvg_session **out) {
     return 1;
   }
   s->cfg = c;
-  const int rc = build(c, s->plan);
+  const int rc = compute == MVG_SESSION_BF16 ? build_bf16(c, s->plan) : build(c, s->plan);
   if (rc != 0) {
     delete s;
     return rc;
@@ -742,6 +1093,15 @@ int64_t mvg_session_tensor_numel(const mvg_session *s, int i) {
 size_t mvg_session_workspace_bytes(const mvg_session *s) { return s ? (size_t)s->plan.workspace_bytes : 0; }
 
 int mvg_session_launches(const mvg_session *s) { return s ? (int)s->plan.steps.size() : -1; }
+
+int mvg_session_compute(const mvg_session *s) { return s ? s->plan.compute : -1; }
+
+int mvg_session_num_steps(const mvg_session *s) { return s ? (int)s->plan.steps.size() : -1; }
+
+const char *mvg_session_step_name(const mvg_session *s, int i) {
+  if (!s || i < 0 || i >= (int)s->plan.steps.size()) return nullptr;
+  return mvg::sop_name(s->plan.steps[i].op);
+}
 
 int mvg_session_num_range_units(const mvg_session *s) { return s ? (int)s->plan.range_units.size() : -1; }
 

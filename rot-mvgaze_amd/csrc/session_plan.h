@@ -25,8 +25,12 @@ struct SRef {
 // One library call of the forward.  r / i / n by op - see the executor (session.hip: run_step), which is their only reader.
 enum SOp {
   SOP_NCHW_TO_NHWC4 = 0, SOP_PREPROCESS_U8, SOP_CONV_AFFINE, SOP_CONV_SPLIT_AFFINE, SOP_MAXPOOL, SOP_SPLIT_F32, SOP_AVGPOOL,
-  SOP_AVGPOOL_SPLIT, SOP_LINEAR, SOP_FUSER, SOP_SKINNY, SOP_RELROT, SOP_CLEAR, SOP_ABSMAX, SOP_FUSE_BUILD, SOP_LINEAR_SPLIT
+  SOP_AVGPOOL_SPLIT, SOP_LINEAR, SOP_FUSER, SOP_SKINNY, SOP_RELROT, SOP_CLEAR, SOP_ABSMAX, SOP_FUSE_BUILD, SOP_LINEAR_SPLIT,
+  // the bf16 inference form (MVG_SESSION_BF16)
+  SOP_NCHW_TO_NHWC8_BF16, SOP_PREPROCESS_U8_BF16, SOP_CONV_BF16, SOP_BN_RELU_MAXPOOL_BF16, SOP_CONV_BF16_AFFINE, SOP_AVGPOOL_BF16,
+  SOP_LINEAR_MIXED, SOP_ROTCAT, SOP_COUNT
 };
+const char *sop_name(int op);              // the entry point the op calls, without the "mvg_" prefix (session_plan.cpp)
 struct SStep {
   int32_t op = 0;
   mvg_conv_desc d = {};
@@ -54,10 +58,12 @@ struct STensor {
 struct SBnFold {             // one record of mvg_bn_eval_affine_batch: tensors gamma .. gamma + 3, (scale, shift) at aff_off
   int32_t gamma = 0, c = 0;
   int64_t aff_off = 0;       // bytes into buf_affine: scale[c] then shift[c]
+  int64_t shift_off = -1;    // bytes into buf_affine of shift[c] when it does not follow the scale (the bf16 stem's [V][c] rows)
 };
-struct SWPrep {              // one record of mvg_weights_prep_batch (mode 1, no transposed copy)
+struct SWPrep {              // one record of mvg_weights_prep_batch (no transposed copy): mode 1 (sp), or mode 0 (bf16) in a bf16 session
   int32_t tensor = 0, stat = 0, cout = 0, rs = 0, cin = 0;
   int64_t wk_off = 0;        // bytes into buf_wk
+  int32_t cin_pad = 0;       // mode 0: the copy's channels per tap (the stem: 3 -> 8); 0 = cin
 };
 
 constexpr int SESSION_MAX_VIEWS = 8;            // the pair tables travel to the device as a kernel argument
@@ -72,8 +78,11 @@ struct SessionPlan {
   std::vector<SWPrep> wprep_backbone, wprep_head;
   int32_t stem_weight = -1;                     // tensor: the 3-channel stem filter bind pads to 4 channels (buf_w4)
   int32_t stem_cout = 0;
+  int32_t compute = MVG_SESSION_FP32;           // MVG_SESSION_FP32 | MVG_SESSION_BF16: which of the two forms the steps state
   int32_t buf_tables = -1, buf_rows = -1, buf_affine = -1, buf_wstat = -1, buf_wk = -1, buf_w4 = -1, buf_slots = -1,
           buf_scratch = -1;
+  int32_t buf_dirs = -1;                        // bf16 form: the per-direction tables of mvg_rotcat_fwd (partner, ident)
+  int64_t dirs_partner = 0, dirs_ident = 0;     // byte offsets inside buf_dirs
   int64_t tab_folds = 0, tab_wprep_backbone = 0, tab_wprep_head = 0, tab_bytes = 0;   // byte offsets inside buf_tables
   int64_t rows_vi = 0, rows_vj = 0, rows_img = 0, rows_view = 0, rows_partner = 0, rows_ident = 0;   // inside buf_rows
   int32_t dirs = 0, head_rows = 0, max_c = 0;

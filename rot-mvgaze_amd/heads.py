@@ -377,7 +377,10 @@ class FusionHead:
     # ---------------------------------------------------------------- forward
     def forward(self, img_feat: Tensor, rot: Tensor, keep_tape: bool, training: bool = True):
         """img_feat [V,B,Cf]; rot [B,V,3,3].  Returns (lifted [V,B,3,512], feats [I,D,B,3,512],
-        preds [I,D,B,2], tape)."""
+        preds [I,D,B,2], tape).
+        csrc/session_plan.cpp restates the inference launches of this method as data: the fused-input fp32 path and
+        _forward_split in build, the `mixed` branch (materialised _fuser_input / _head_input, _Mlp._use_mixed per layer) in
+        build_bf16.  A change to the launches here must be made there too."""
         V, B, cf = img_feat.shape
         dev = img_feat.device
         ix = self._indices(V, dev)

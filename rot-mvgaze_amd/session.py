@@ -7,6 +7,10 @@ BatchNorm folded, pools, lifter, fusion iterations, gaze heads - so its four out
 What depends on the weights only (sp weight copies, BatchNorm folds, index tables) is queued once by ``bind`` /
 ``refresh``; ``run`` queues the per-input launches, allocates nothing when given its outputs and never synchronises.
 
+Two compute forms: the fp32 model (default), and with ``compute=torch.bfloat16`` the bf16 inference form - what ``run_views``
+queues with ``compute_dtype = torch.bfloat16`` (BatchNorm folded into ``mvg_conv_fprop_bf16_affine``, uint8 patches straight
+to the bf16 stem input, the Linears "mixed" on the bf16 matrix cores), again bit for bit.
+
 The model's own ``forward`` / ``forward_multiview`` do not route through a session.
 """
 from __future__ import annotations
@@ -17,17 +21,19 @@ from typing import List, Optional, Sequence, Tuple
 import torch
 
 from . import ops
-from ._lib import SessionCfg, check, lib
+from ._lib import SESSION_BF16, SESSION_FP32, SessionCfg, check, lib
 from .arch import NUM_FEAT_VEC, RANGE_OVER_BITS
 
 Tensor = torch.Tensor
 
 
 class InferenceSession:
-    """``InferenceSession(model, views, batch, height, width, raw_hw=None, input_bgr=False)``.
+    """``InferenceSession(model, views, batch, height, width, raw_hw=None, input_bgr=False, range_record=False, compute=None)``.
 
-    model: a ``MultiViewGaze`` / ``FeatRotationSymm`` on the GPU (default, ``share_weights`` or ``ignore_rotmat`` variant,
-    ``compute_dtype`` float32).  height / width: the network's input size.  raw_hw = (h, w): the views are raw uint8
+    model: a ``MultiViewGaze`` / ``FeatRotationSymm`` on the GPU (default, ``share_weights`` or ``ignore_rotmat`` variant).
+    compute: None - the fp32 form, ``model.compute_dtype`` must be float32; ``torch.bfloat16`` - the bf16 inference form,
+    ``model.compute_dtype`` must be bfloat16 (the kernel-family switch below does not apply, and there are no range units:
+    ``range_record=True`` gives empty reports).  height / width: the network's input size.  raw_hw = (h, w): the views are raw uint8
     ``[B, h, w, 3]`` patches, resized and normalised on the GPU (``input_bgr``: swap B and R first); otherwise fp32
     ``[B, 3, height, width]``.  The kernel family follows ``model._backbone.split`` (MVG_SPLIT); the 2 GiB guard of the split
     path is evaluated from the real sizes.  Several sessions may share one model.
@@ -37,12 +43,17 @@ class InferenceSession:
     session has no fallback: on an overflow build one over a model with ``_backbone.split = False``."""
 
     def __init__(self, model, views: int, batch: int, height: int, width: int, raw_hw: Optional[Tuple[int, int]] = None,
-                 input_bgr: bool = False, range_record: bool = False) -> None:
+                 input_bgr: bool = False, range_record: bool = False, compute: Optional[torch.dtype] = None) -> None:
         v = model._variant
         if v.encode_rotmat or v.share_feature:
             raise ValueError("InferenceSession: the encode_rotmat and share_feature variants are not served by the native session")
-        if model.compute_dtype != torch.float32:
-            raise ValueError("InferenceSession: compute_dtype must be torch.float32 (the bf16 inference form is not served)")
+        if compute not in (None, torch.float32, torch.bfloat16):
+            raise ValueError("InferenceSession: compute must be None, torch.float32 or torch.bfloat16")
+        want = torch.bfloat16 if compute == torch.bfloat16 else torch.float32
+        if model.compute_dtype != want:
+            raise ValueError(f"InferenceSession: this session computes in {want} and model.compute_dtype is {model.compute_dtype}: "
+                             "pass compute=torch.bfloat16 for a model on the bf16 path (compute=None serves the fp32 model)")
+        self.compute = want
         self._h = None
         self.model = model
         model.ensure_layout()
@@ -54,7 +65,8 @@ class InferenceSession:
                          split=int(model._backbone.split), raw_u8=int(self.raw_hw is not None), in_h=int(in_h), in_w=int(in_w),
                          input_bgr=int(bool(input_bgr)))
         h = C.c_void_p()
-        check(lib().mvg_session_create(C.byref(cfg), C.byref(h)), "session_create")
+        check(lib().mvg_session_create_ex(C.byref(cfg), SESSION_BF16 if want == torch.bfloat16 else SESSION_FP32, C.byref(h)),
+              "session_create")
         self._h = h
         self.tensor_names: List[str] = [lib().mvg_session_tensor_name(h, i).decode() for i in range(lib().mvg_session_num_tensors(h))]
         self.workspace_bytes = int(lib().mvg_session_workspace_bytes(h))
