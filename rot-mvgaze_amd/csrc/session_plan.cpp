@@ -1,15 +1,27 @@
 // The inference session's plan builder and its host-only entry points (mvg_session_create / _destroy and the queries).
 // No HIP here, like pair_index.cpp: this file compiles and runs stand-alone (tests/native/session_plan_check.cpp).
 //
-// The plan restates, as data, what the Python module decides per call for model.eval() under torch.no_grad() on the fp32
-// path: arch.py's layer table, Backbone.forward's 2 GiB guard, Backbone._unit_infer's launches per unit and
-// Backbone._forward_infer's unit order (backbone.py: conv1.., downsample, last conv with the residual), FusionHead.forward's
-// choice between the generated-input fp32-MFMA Linears and _forward_split (heads.py: D * B >= 1024 rows).  Every step is one
-// call of an existing entry point; session.hip executes them.
-//
-// build_bf16 below restates the same forward for the bf16 storage path (MVG_SESSION_BF16): the bf16 branches of
-// Backbone._input_layout, _forward_infer, _unit_infer and the non-training pool=True branch of _unit_fwd (backbone.py), and the
-// `mixed` branch of FusionHead.forward with Mlp._use_mixed per layer (heads.py).
+// The plan restates, as data, what the Python module decides per call for model.eval() under torch.no_grad().  Every step is
+// one call of an existing entry point; session.hip executes them.  One Builder holds what the compute forms share, each part
+// written once:
+//   register_model  arch.py's layer table and the Linears of heads.py, as tensors in state_dict order
+//   table_buffers   the record tables and the pair / row tables that bind writes
+//   input_layout    Backbone._input_layout, one launch per view
+//   block_loop      Backbone._forward_infer's unit order (backbone.py: conv1.., downsample, last conv with the residual)
+//   relrot, skinny  FusionHead.forward's relative rotations and the heads' 512 -> 2 layer (heads.py)
+//   finish          offsets for every buffer and the self-check
+// and two form functions state what differs:
+//   build           the fp32 path: Backbone.forward's 2 GiB guard, the stem, Backbone._unit_infer's launch per unit (fp32-MFMA
+//                   or split), FusionHead.forward's choice between the generated-input fp32-MFMA Linears and _forward_split
+//                   (heads.py: D * B >= 1024 rows)
+//   build_bf16      the bf16 storage path (MVG_SESSION_BF16): the bf16 branches of Backbone._input_layout, _forward_infer,
+//                   _unit_infer and the non-training pool=True branch of _unit_fwd (backbone.py), and the `mixed` branch of
+//                   FusionHead.forward with Mlp._use_mixed per layer (heads.py)
+// A change to the forward's order in backbone.py / heads.py is made once here, in the shared part; a change to a form's
+// launches in that form's function.  Buffer ids are creation order and decide the offsets (allocate breaks ties of first use
+// by id), so the order in which each form calls new_buf is part of the plan and is frozen by
+// tests/golden/session_plan_digests.txt - also where it is not the order of first use (fp32: the Linear split-K workspace
+// before the lifter's hidden layer, the pool argmax between the two pooled maps).  Moving a new_buf moves the fixture.
 #include <limits.h>
 #include <stdio.h>
 #include <string.h>
@@ -87,15 +99,48 @@ mvg_conv_desc make_desc(int groups, int n, int h, int w, int cin, int cout, int 
 
 int64_t align_up(int64_t v) { return (v + ALIGN - 1) / ALIGN * ALIGN; }
 
-struct Act {               // an activation of the backbone: a buffer holding [V][B][h][w][c], 4 bytes per element in fp32 and in sp
+struct Act {               // an activation of the backbone: a buffer holding [V][B][h][w][c]; sp: fp32 form only (both 4 bytes)
   int buf = -1;
   bool sp = false;
   int h = 0, w = 0, c = 0;
 };
+struct ConvT {             // a conv of the layer table: its weight tensor, its first fold record and its weight copy
+  ConvSpec s;
+  int t = 0, fold = -1, wprep = -1;
+};
+struct Lin {
+  int w = 0, b = 0, fin = 0, fout = 0, wprep = -1;
+};
+
+void allocate(SessionPlan &p);
+bool self_check(const SessionPlan &p, char *why, size_t n);
 
 struct Builder {
   SessionPlan &p;
-  explicit Builder(SessionPlan &plan) : p(plan) {}
+  const mvg_session_cfg &c;
+  const int V, N, H, W, I, D, rows, nmod;
+  const int elem;                                 // bytes per element of an activation and of a weight copy: 4 (fp32, sp), 2 (bf16)
+  ConvSpec stem;
+  std::vector<BlockSpec> blocks;
+  int cf = 0, kin = 0;                            // arch.head_dims, default / ignore_rotmat variants: ImageFeatFuser
+  std::vector<ConvT> convs;
+  int ci_stem = 0;
+  std::vector<std::vector<int>> blk_convs;
+  std::vector<int> blk_ds;
+  Lin lift0, lift1;
+  std::vector<Lin> fu0, fu1, hd0, hd1;
+  int64_t aff_bytes = 0, wk_bytes = 0;
+  const int64_t feat_it, pred_it;                 // one iteration's bytes of the feats and preds outputs
+
+  Builder(const mvg_session_cfg &cfg, SessionPlan &plan, int elem_bytes)
+      : p(plan), c(cfg), V(cfg.views), N(cfg.batch), H(cfg.height), W(cfg.width), I(cfg.num_iter), D(V * (V - 1)), rows(D * N),
+        nmod(cfg.share_weights ? 1 : I), elem(elem_bytes), feat_it((int64_t)rows * ROT_DIM * 4), pred_it((int64_t)rows * 2 * 4) {
+    backbone_spec(c.depth, stem, blocks, cf);
+    kin = cf + ROT_DIM;
+    p.fc_dim = cf;
+    p.dirs = D;
+    p.head_rows = rows;
+  }
 
   int new_buf(int64_t bytes, const char *what, bool persistent = false) {
     SBuf b;
@@ -114,11 +159,7 @@ struct Builder {
       b.first = std::min(b.first, s);
       b.last = std::max(b.last, s);
     }
-    SRef r;
-    r.space = SR_BUF;
-    r.idx = id;
-    r.off = off;
-    return r;
+    return ref(SR_BUF, id, off);
   }
   static SRef ref(int space, int idx = 0, int64_t off = 0) {
     SRef r;
@@ -136,6 +177,176 @@ struct Builder {
     return (int)p.tensors.size() - 1;
   }
   void push(const SStep &s) { p.steps.push_back(s); }
+
+  // one record of a weight copy of `bytes`-byte elements behind the ones before it in buf_wk; cin_pad 0 = cin
+  int prep(std::vector<SWPrep> &to, int tensor, int cout, int rs, int cin, int bytes, int cin_pad) {
+    SWPrep w;
+    w.tensor = tensor;
+    w.cout = cout;
+    w.rs = rs;
+    w.cin = cin;
+    w.cin_pad = cin_pad;
+    w.wk_off = wk_bytes;
+    wk_bytes += align_up((int64_t)cout * rs * (cin_pad ? cin_pad : cin) * bytes);
+    to.push_back(w);
+    return (int)to.size() - 1;
+  }
+  void prep_lin(Lin &l, int cin_pad) { l.wprep = prep(p.wprep_head, l.w, l.fout, 1, l.fin, elem, cin_pad); }
+
+  // The model's tensors in state_dict order: stem, blocks (each with its downsample), lifter, fusers, heads; one fold per
+  // BatchNorm, the stem's `stem_folds` times (rows of scales, then rows of shifts; shift_apart: every fold names its shift).
+  // conv_copy(spec): the cin_pad of the conv's weight copy (0 = cin), or -1 for a conv without one.
+  template <class ConvCopy>
+  void register_model(int stem_folds, bool shift_apart, ConvCopy conv_copy) {
+    auto add_conv = [&](const ConvSpec &s, int nrec) {
+      ConvT ct;
+      ct.s = s;
+      ct.t = add_tensor(s.name + ".weight", (int64_t)s.cout * s.cin * s.k * s.k);
+      add_tensor(s.bn + ".weight", s.cout);
+      add_tensor(s.bn + ".bias", s.cout);
+      add_tensor(s.bn + ".running_mean", s.cout);
+      add_tensor(s.bn + ".running_var", s.cout);
+      p.max_c = std::max(p.max_c, s.cout);
+      ct.fold = (int)p.folds.size();
+      for (int v = 0; v < nrec; ++v) {
+        SBnFold f;
+        f.gamma = ct.t + 1;
+        f.c = s.cout;
+        f.aff_off = aff_bytes + 4LL * s.cout * v;
+        if (shift_apart) f.shift_off = aff_bytes + 4LL * s.cout * (nrec + v);
+        p.folds.push_back(f);
+      }
+      aff_bytes += align_up(2LL * nrec * s.cout * 4);
+      const int cin_pad = conv_copy(s);
+      if (cin_pad >= 0) ct.wprep = prep(p.wprep_backbone, ct.t, s.cout, s.k * s.k, s.cin, elem, cin_pad);
+      convs.push_back(ct);
+      return (int)convs.size() - 1;
+    };
+    ci_stem = add_conv(stem, stem_folds);
+    blk_convs.resize(blocks.size());
+    blk_ds.assign(blocks.size(), -1);
+    for (size_t b = 0; b < blocks.size(); ++b) {
+      for (const ConvSpec &s : blocks[b].convs) blk_convs[b].push_back(add_conv(s, 1));
+      if (blocks[b].has_ds) blk_ds[b] = add_conv(blocks[b].ds, 1);
+    }
+    auto add_lin = [&](const std::string &name, int fin, int fout) {
+      Lin l;
+      l.fin = fin;
+      l.fout = fout;
+      l.w = add_tensor(name + ".weight", (int64_t)fout * fin);
+      l.b = add_tensor(name + ".bias", fout);
+      return l;
+    };
+    lift0 = add_lin("_lifter._lifter.blocks.0.0", cf, ROT_DIM);
+    lift1 = add_lin("_lifter._lifter.blocks.1.0", ROT_DIM, ROT_DIM);
+    fu0.resize(nmod), fu1.resize(nmod), hd0.resize(nmod), hd1.resize(nmod);
+    for (int i = 0; i < nmod; ++i) {
+      const std::string pre = "_img_fusers." + std::to_string(i) + "._fuser.blocks.";
+      fu0[i] = add_lin(pre + "0.0", kin, kin);
+      fu1[i] = add_lin(pre + "1.0", kin, ROT_DIM);
+    }
+    for (int i = 0; i < nmod; ++i) {
+      const std::string pre = "_gaze_estimators." + std::to_string(i) + ".blocks.";
+      hd0[i] = add_lin(pre + "0.0", kin, HEAD_HID);
+      hd1[i] = add_lin(pre + "1.0", HEAD_HID, 2);
+    }
+  }
+
+  // The first two persistent buffers (bind writes them), once the folds and the weight-copy records are complete; the form
+  // creates the rest of its persistent buffers behind them
+  void table_buffers() {
+    p.tab_folds = 0;
+    p.tab_wprep_backbone = align_up((int64_t)p.folds.size() * 56);
+    p.tab_wprep_head = p.tab_wprep_backbone + align_up((int64_t)p.wprep_backbone.size() * 48);
+    p.tab_bytes = p.tab_wprep_head + align_up((int64_t)p.wprep_head.size() * 48);
+    p.buf_tables = new_buf(p.tab_bytes, "record tables", true);
+    const int64_t rt = align_up((int64_t)rows * 4), dt = align_up((int64_t)D * 4);
+    p.rows_vi = 0;
+    p.rows_vj = dt;
+    p.rows_img = 2 * dt;
+    p.rows_view = 2 * dt + rt;
+    p.rows_partner = 2 * dt + 2 * rt;
+    p.rows_ident = 2 * dt + 3 * rt;
+    p.buf_rows = new_buf(2 * dt + 4 * rt, "pair / row tables", true);
+  }
+
+  SRef scale_of(int ci) const { return ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].aff_off); }
+  SRef shift_of(int ci) const {
+    const SBnFold &f = p.folds[convs[ci].fold];
+    return ref(SR_BUF, p.buf_affine, f.shift_off >= 0 ? f.shift_off : f.aff_off + 4LL * f.c);
+  }
+  SRef wk_of(const SWPrep &w) const { return ref(SR_BUF, p.buf_wk, w.wk_off); }
+  SRef rows_ref(int64_t off) const { return ref(SR_BUF, p.buf_rows, off); }
+  int64_t act_bytes(int h, int w, int ch) const { return (int64_t)V * N * h * w * ch * elem; }
+
+  // Backbone._input_layout: V launches into x0 [V][B][H][W][ch]
+  int input_layout(int op_plain, int op_raw, int ch, const char *what) {
+    const int x0 = new_buf(act_bytes(H, W, ch), what);
+    for (int v = 0; v < V; ++v) {
+      SStep s;
+      s.op = c.raw_u8 ? op_raw : op_plain;
+      s.r[0] = ref(SR_VIEW, v);
+      s.r[1] = buf(x0, (int64_t)v * N * H * W * ch * elem);
+      if (c.raw_u8) {
+        s.i[0] = N; s.i[1] = c.in_h; s.i[2] = c.in_w; s.i[3] = H; s.i[4] = W; s.i[5] = c.input_bgr ? 1 : 0;
+      } else {
+        s.i[0] = N; s.i[1] = 3; s.i[2] = H; s.i[3] = W;
+      }
+      push(s);
+    }
+    return x0;
+  }
+
+  // Backbone._forward_infer's residual blocks over unit(conv, input, relu, residual) = the form's Backbone._unit_infer: conv +
+  // folded BatchNorm (+ residual) (+ ReLU) in one launch.  A change to the order is made in backbone.py too
+  template <class Unit>
+  Act block_loop(Act x, Unit unit) {
+    for (size_t b = 0; b < blocks.size(); ++b) {
+      Act identity = x, out = x;
+      const std::vector<int> &cv = blk_convs[b];
+      for (size_t k = 0; k + 1 < cv.size(); ++k) out = unit(cv[k], out, true, nullptr);
+      if (blk_ds[b] >= 0) identity = unit(blk_ds[b], x, false, nullptr);
+      x = unit(cv.back(), out, true, &identity);
+    }
+    return x;
+  }
+
+  // FusionHead.forward: the relative rotation of every directed pair, and the heads' last layer (both head paths, both forms)
+  int relrot() {
+    const int rel = new_buf((int64_t)rows * 9 * 4, "relative rotations");
+    SStep s;
+    s.op = SOP_RELROT;
+    s.r[0] = ref(SR_ROT);
+    s.r[1] = rows_ref(p.rows_vi);
+    s.r[2] = rows_ref(p.rows_vj);
+    s.r[3] = buf(rel);
+    s.i[0] = N; s.i[1] = V; s.i[2] = D;
+    push(s);
+    return rel;
+  }
+  void skinny(const SRef &xin, const Lin &l, int it) {
+    SStep s;
+    s.op = SOP_SKINNY;
+    s.r[0] = xin;
+    s.r[1] = tensor(l.w);
+    s.r[2] = tensor(l.b);
+    s.r[3] = ref(SR_PREDS, 0, it * pred_it);
+    s.i[0] = rows; s.i[1] = HEAD_HID; s.i[2] = 2;
+    push(s);
+  }
+
+  int finish() {
+    allocate(p);
+    char why[256];
+    if (!self_check(p, why, sizeof(why))) {
+      set_error("session_create: the buffer plan failed its self-check: %s", why);
+      return 3;
+    }
+    return 0;
+  }
+
+  int build();
+  int build_bf16();
 };
 
 // Offsets for every buffer: in order of first use, each at the lowest offset where it overlaps no placed buffer whose live
@@ -211,162 +422,44 @@ bool self_check(const SessionPlan &p, char *why, size_t n) {
   return true;
 }
 
-int build(const mvg_session_cfg &c, SessionPlan &p) {
-  Builder B(p);
-  const int V = c.views, N = c.batch, H = c.height, W = c.width, I = c.num_iter;
-  ConvSpec stem;
-  std::vector<BlockSpec> blocks;
-  int cf = 0;
-  backbone_spec(c.depth, stem, blocks, cf);
-  p.fc_dim = cf;
-
+// The plan of the fp32 path: the backbone on the fp32-MFMA kernels or, with cfg.split below the 2 GiB guard, on the split
+// kernels; the fusers and heads on the generated-input fp32-MFMA Linears or, from 1024 rows with cfg.split, on the split Linears.
+int Builder::build() {
   // Backbone.forward: one view of the largest sp tensor (layer1's output) is addressed with 32-bit offsets
   const int64_t biggest_view = (int64_t)N * ((H + 3) / 4) * ((W + 3) / 4) * blocks[0].convs.back().cout;
   p.split_now = (c.split != 0 && 4 * biggest_view < 0x7FFFFFF0LL) ? 1 : 0;
-  const int D = V * (V - 1), rows = D * N;
-  p.dirs = D;
-  p.head_rows = rows;
   p.head_split = (c.split != 0 && rows >= SPLIT_MIN_ROWS) ? 1 : 0;      // model.run_views: head.split = backbone.split
   if (p.head_split && !(2 + I <= 8 && 11 * I + 2 <= SESSION_SLOTS)) {
     set_error("session_create: num_iter %d is more than the split head path's slot arena serves (at most 5)", I);
     return 2;
   }
 
-  // ---- tensors, in state_dict order
-  struct ConvT {
-    ConvSpec s;
-    int t = 0, fold = -1, wprep = -1;
-  };
-  std::vector<ConvT> convs;
-  int64_t aff_bytes = 0, wk_bytes = 0;
-  auto add_conv = [&](const ConvSpec &s) {
-    ConvT ct;
-    ct.s = s;
-    ct.t = B.add_tensor(s.name + ".weight", (int64_t)s.cout * s.cin * s.k * s.k);
-    B.add_tensor(s.bn + ".weight", s.cout);
-    B.add_tensor(s.bn + ".bias", s.cout);
-    B.add_tensor(s.bn + ".running_mean", s.cout);
-    B.add_tensor(s.bn + ".running_var", s.cout);
-    SBnFold f;
-    f.gamma = ct.t + 1;
-    f.c = s.cout;
-    f.aff_off = aff_bytes;
-    aff_bytes += align_up(2LL * s.cout * 4);
-    p.max_c = std::max(p.max_c, s.cout);
-    ct.fold = (int)p.folds.size();
-    p.folds.push_back(f);
-    if (p.split_now && s.cin != 3) {
-      SWPrep w;
-      w.tensor = ct.t;
-      w.cout = s.cout;
-      w.rs = s.k * s.k;
-      w.cin = s.cin;
-      w.wk_off = wk_bytes;
-      wk_bytes += align_up((int64_t)s.cout * s.k * s.k * s.cin * 4);
-      ct.wprep = (int)p.wprep_backbone.size();
-      p.wprep_backbone.push_back(w);
-    }
-    convs.push_back(ct);
-    return (int)convs.size() - 1;
-  };
-  const int ci_stem = add_conv(stem);
-  std::vector<std::vector<int>> blk_convs(blocks.size());
-  std::vector<int> blk_ds(blocks.size(), -1);
-  for (size_t b = 0; b < blocks.size(); ++b) {
-    for (const ConvSpec &s : blocks[b].convs) blk_convs[b].push_back(add_conv(s));
-    if (blocks[b].has_ds) blk_ds[b] = add_conv(blocks[b].ds);
-  }
+  // ---- tensors; an sp KRSC copy of every conv the split kernels run (all but the stem)
+  register_model(1, false, [&](const ConvSpec &s) { return p.split_now && s.cin != 3 ? 0 : -1; });
   p.stem_weight = convs[ci_stem].t;
   p.stem_cout = stem.cout;
-  struct Lin {
-    int w = 0, b = 0, fin = 0, fout = 0, wprep = -1;
-  };
-  auto add_lin = [&](const std::string &name, int fin, int fout) {
-    Lin l;
-    l.fin = fin;
-    l.fout = fout;
-    l.w = B.add_tensor(name + ".weight", (int64_t)fout * fin);
-    l.b = B.add_tensor(name + ".bias", fout);
-    return l;
-  };
-  const int kin = cf + ROT_DIM;                   // arch.head_dims, default / ignore_rotmat variants: ImageFeatFuser
-  Lin lift0 = add_lin("_lifter._lifter.blocks.0.0", cf, ROT_DIM), lift1 = add_lin("_lifter._lifter.blocks.1.0", ROT_DIM, ROT_DIM);
-  const int nmod = c.share_weights ? 1 : I;
-  std::vector<Lin> fu0(nmod), fu1(nmod), hd0(nmod), hd1(nmod);
-  for (int i = 0; i < nmod; ++i) {
-    const std::string pre = "_img_fusers." + std::to_string(i) + "._fuser.blocks.";
-    fu0[i] = add_lin(pre + "0.0", kin, kin);
-    fu1[i] = add_lin(pre + "1.0", kin, ROT_DIM);
-  }
-  for (int i = 0; i < nmod; ++i) {
-    const std::string pre = "_gaze_estimators." + std::to_string(i) + ".blocks.";
-    hd0[i] = add_lin(pre + "0.0", kin, HEAD_HID);
-    hd1[i] = add_lin(pre + "1.0", HEAD_HID, 2);
-  }
-  if (p.head_split) {
+  if (p.head_split)
     // FusionHead._prepare_split_weights: heads and fusers from the last iteration down, every layer with fin, fout % 32 == 0
-    auto prep = [&](Lin &l) {
-      SWPrep w;
-      w.tensor = l.w;
-      w.cout = l.fout;
-      w.rs = 1;
-      w.cin = l.fin;
-      w.wk_off = wk_bytes;
-      wk_bytes += align_up((int64_t)l.fout * l.fin * 4);
-      l.wprep = (int)p.wprep_head.size();
-      p.wprep_head.push_back(w);
-    };
     for (int i = nmod - 1; i >= 0; --i) {
-      prep(hd0[i]);
-      prep(fu0[i]);
-      prep(fu1[i]);
+      prep_lin(hd0[i], 0);
+      prep_lin(fu0[i], 0);
+      prep_lin(fu1[i], 0);
     }
-  }
   for (size_t k = 0; k < p.wprep_backbone.size(); ++k) p.wprep_backbone[k].stat = (int)k;
   for (size_t k = 0; k < p.wprep_head.size(); ++k) p.wprep_head[k].stat = (int)(p.wprep_backbone.size() + k);
   const int nstat = (int)(p.wprep_backbone.size() + p.wprep_head.size());
 
   // ---- persistent buffers (bind writes them)
-  p.tab_folds = 0;
-  p.tab_wprep_backbone = align_up((int64_t)p.folds.size() * 56);
-  p.tab_wprep_head = p.tab_wprep_backbone + align_up((int64_t)p.wprep_backbone.size() * 48);
-  p.tab_bytes = p.tab_wprep_head + align_up((int64_t)p.wprep_head.size() * 48);
-  p.buf_tables = B.new_buf(p.tab_bytes, "record tables", true);
-  const int64_t rt = align_up((int64_t)rows * 4), dt = align_up((int64_t)D * 4);
-  p.rows_vi = 0;
-  p.rows_vj = dt;
-  p.rows_img = 2 * dt;
-  p.rows_view = 2 * dt + rt;
-  p.rows_partner = 2 * dt + 2 * rt;
-  p.rows_ident = 2 * dt + 3 * rt;
-  p.buf_rows = B.new_buf(2 * dt + 4 * rt, "pair / row tables", true);
-  p.buf_affine = B.new_buf(aff_bytes, "folded BatchNorm (scale, shift)", true);
-  p.buf_wstat = B.new_buf(std::max(nstat, 1) * 8LL, "weight copy scales", true);
-  p.buf_wk = B.new_buf(wk_bytes, "sp weight copies (KRSC)", true);
-  p.buf_w4 = B.new_buf((int64_t)stem.cout * stem.k * stem.k * 4 * 4, "stem filter, 4 channels", true);
-  p.buf_slots = B.new_buf(SESSION_SLOTS * 4, "head scale slots", true);
-  p.buf_scratch = B.new_buf((int64_t)SESSION_SCRATCH_BYTES, "scratch", true);
+  table_buffers();
+  p.buf_affine = new_buf(aff_bytes, "folded BatchNorm (scale, shift)", true);
+  p.buf_wstat = new_buf(std::max(nstat, 1) * 8LL, "weight copy scales", true);
+  p.buf_wk = new_buf(wk_bytes, "sp weight copies (KRSC)", true);
+  p.buf_w4 = new_buf((int64_t)stem.cout * stem.k * stem.k * 4 * 4, "stem filter, 4 channels", true);
+  p.buf_slots = new_buf(SESSION_SLOTS * 4, "head scale slots", true);
+  p.buf_scratch = new_buf((int64_t)SESSION_SCRATCH_BYTES, "scratch", true);
+  auto sinv_of = [&](const SWPrep &w) { return ref(SR_BUF, p.buf_wstat, 8LL * w.stat + 4); };
 
-  auto scale_of = [&](int ci) { return B.ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].aff_off); };
-  auto shift_of = [&](int ci) { return B.ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].aff_off + 4LL * convs[ci].s.cout); };
-  auto wk_of = [&](const SWPrep &w) { return B.ref(SR_BUF, p.buf_wk, w.wk_off); };
-  auto sinv_of = [&](const SWPrep &w) { return B.ref(SR_BUF, p.buf_wstat, 8LL * w.stat + 4); };
-  auto act_bytes = [&](int h, int w, int ch) { return (int64_t)V * N * h * w * ch * 4; };
-
-  // ---- input layout: V launches into x0 [V][B][H][W][4]
-  const int x0 = B.new_buf(act_bytes(H, W, 4), "input NHWC4");
-  for (int v = 0; v < V; ++v) {
-    SStep s;
-    s.op = c.raw_u8 ? SOP_PREPROCESS_U8 : SOP_NCHW_TO_NHWC4;
-    s.r[0] = B.ref(SR_VIEW, v);
-    s.r[1] = B.buf(x0, (int64_t)v * N * H * W * 4 * 4);
-    if (c.raw_u8) {
-      s.i[0] = N; s.i[1] = c.in_h; s.i[2] = c.in_w; s.i[3] = H; s.i[4] = W; s.i[5] = c.input_bgr ? 1 : 0;
-    } else {
-      s.i[0] = N; s.i[1] = 3; s.i[2] = H; s.i[3] = W;
-    }
-    B.push(s);
-  }
+  const int x0 = input_layout(SOP_NCHW_TO_NHWC4, SOP_PREPROCESS_U8, 4, "input NHWC4");
 
   // ---- stem: fp32-MFMA kernel on the 4-channel image (also on the split path), plain max pool, split of the pooled map
   const mvg_conv_desc dstem = make_desc(V, N, H, W, 4, stem.cout, stem.k, stem.stride, stem.pad);
@@ -374,18 +467,18 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
     set_error("session_create: %d x %d is too small for the stem", H, W);
     return 2;
   }
-  const int ystem = B.new_buf(act_bytes(dstem.ho, dstem.wo, stem.cout), "stem output");
+  const int ystem = new_buf(act_bytes(dstem.ho, dstem.wo, stem.cout), "stem output");
   {
     SStep s;
     s.op = SOP_CONV_AFFINE;
     s.d = dstem;
-    s.r[0] = B.buf(x0);
-    s.r[1] = B.ref(SR_BUF, p.buf_w4);
-    s.r[2] = B.buf(ystem);
+    s.r[0] = buf(x0);
+    s.r[1] = ref(SR_BUF, p.buf_w4);
+    s.r[2] = buf(ystem);
     s.r[3] = scale_of(ci_stem);
     s.r[4] = shift_of(ci_stem);
     s.i[0] = 1;
-    B.push(s);
+    push(s);
   }
   const int hp = (dstem.ho + 2 - 3) / 2 + 1, wp = (dstem.wo + 2 - 3) / 2 + 1;
   Act x;
@@ -393,35 +486,35 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
   x.w = wp;
   x.c = stem.cout;
   {
-    const int pooled = B.new_buf(act_bytes(hp, wp, stem.cout), "pooled map");
-    const int argmax = B.new_buf((int64_t)V * N * hp * wp * stem.cout, "pool argmax");
+    const int pooled = new_buf(act_bytes(hp, wp, stem.cout), "pooled map");
+    const int argmax = new_buf((int64_t)V * N * hp * wp * stem.cout, "pool argmax");
     SStep s;
     s.op = SOP_MAXPOOL;
-    s.r[0] = B.buf(ystem);
-    s.r[1] = B.buf(pooled);
-    s.r[2] = B.buf(argmax);
+    s.r[0] = buf(ystem);
+    s.r[1] = buf(pooled);
+    s.r[2] = buf(argmax);
     s.i[0] = V * N; s.i[1] = dstem.ho; s.i[2] = dstem.wo; s.i[3] = stem.cout; s.i[4] = hp; s.i[5] = wp;
-    B.push(s);
+    push(s);
     x.buf = pooled;
     if (p.split_now) {
-      const int pooled_sp = B.new_buf(act_bytes(hp, wp, stem.cout), "pooled map (sp)");
+      const int pooled_sp = new_buf(act_bytes(hp, wp, stem.cout), "pooled map (sp)");
       SStep t;
       t.op = SOP_SPLIT_F32;
-      t.r[0] = B.buf(pooled);
-      t.r[1] = B.buf(pooled_sp);
+      t.r[0] = buf(pooled);
+      t.r[1] = buf(pooled_sp);
       t.n = (int64_t)V * N * hp * wp * stem.cout;
       t.range = (int32_t)p.range_units.size();
       p.range_units.push_back(stem.name);
-      B.push(t);
+      push(t);
       x.buf = pooled_sp;
       x.sp = true;
     }
   }
 
-  // ---- residual blocks.  unit(): conv + folded BatchNorm (+ residual) (+ ReLU) in one launch = Backbone._unit_infer (fp32-MFMA
-  // and split forms); the block loop below = Backbone._forward_infer.  A change to either is made in backbone.py too
+  // ---- residual blocks: Backbone._unit_infer, fp32-MFMA and split forms.  An empty map is clamped to 1 so that the walk
+  // finishes, and reported after it
   bool bad_size = false;
-  auto unit = [&](int ci, const Act &in, bool relu, const Act *residual) {
+  x = block_loop(x, [&](int ci, const Act &in, bool relu, const Act *residual) {
     const ConvSpec &cs = convs[ci].s;
     const mvg_conv_desc d = make_desc(V, N, in.h, in.w, cs.cin, cs.cout, cs.k, cs.stride, cs.pad);
     if (d.ho < 1 || d.wo < 1) bad_size = true;
@@ -429,7 +522,7 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
     out.h = std::max(d.ho, 1);
     out.w = std::max(d.wo, 1);
     out.c = cs.cout;
-    out.buf = B.new_buf(act_bytes(out.h, out.w, out.c), "unit output");
+    out.buf = new_buf(act_bytes(out.h, out.w, out.c), "unit output");
     SStep s;
     s.d = d;
     if (p.split_now) {
@@ -437,13 +530,13 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
       const SWPrep &w = p.wprep_backbone[convs[ci].wprep];
       out.sp = relu;
       s.op = SOP_CONV_SPLIT_AFFINE;
-      s.r[0] = B.buf(in.buf);
+      s.r[0] = buf(in.buf);
       s.r[1] = wk_of(w);
       s.r[2] = sinv_of(w);
-      s.r[3] = B.buf(out.buf);
+      s.r[3] = buf(out.buf);
       s.r[4] = scale_of(ci);
       s.r[5] = shift_of(ci);
-      if (residual) s.r[6] = B.buf(residual->buf);
+      if (residual) s.r[6] = buf(residual->buf);
       s.i[0] = out.sp ? 1 : 0;
       s.i[1] = (residual && residual->sp) ? 1 : 0;
       s.i[2] = relu ? 1 : 0;
@@ -453,24 +546,17 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
       }
     } else {
       s.op = SOP_CONV_AFFINE;
-      s.r[0] = B.buf(in.buf);
-      s.r[1] = B.tensor(convs[ci].t);
-      s.r[2] = B.buf(out.buf);
+      s.r[0] = buf(in.buf);
+      s.r[1] = tensor(convs[ci].t);
+      s.r[2] = buf(out.buf);
       s.r[3] = scale_of(ci);
       s.r[4] = shift_of(ci);
-      if (residual) s.r[5] = B.buf(residual->buf);
+      if (residual) s.r[5] = buf(residual->buf);
       s.i[0] = relu ? 1 : 0;
     }
-    B.push(s);
+    push(s);
     return out;
-  };
-  for (size_t b = 0; b < blocks.size(); ++b) {
-    Act identity = x, out = x;
-    const std::vector<int> &cv = blk_convs[b];
-    for (size_t k = 0; k + 1 < cv.size(); ++k) out = unit(cv[k], out, true, nullptr);
-    if (blk_ds[b] >= 0) identity = unit(blk_ds[b], x, false, nullptr);
-    x = unit(cv.back(), out, true, &identity);
-  }
+  });
   if (bad_size) {
     set_error("session_create: %d x %d is too small for ResNet-%d (a layer's map would be empty)", H, W, c.depth);
     return 2;
@@ -478,10 +564,10 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
   {
     SStep s;
     s.op = x.sp ? SOP_AVGPOOL_SPLIT : SOP_AVGPOOL;
-    s.r[0] = B.buf(x.buf);
-    s.r[1] = B.ref(SR_IMG_FEAT);
+    s.r[0] = buf(x.buf);
+    s.r[1] = ref(SR_IMG_FEAT);
     s.i[0] = V * N; s.i[1] = x.h * x.w; s.i[2] = cf;
-    B.push(s);
+    push(s);
   }
 
   // ---- lifter, relative rotations (both head paths)
@@ -498,78 +584,57 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
     lin_ws(rows, kin, ROT_DIM);
     lin_ws(rows, kin, HEAD_HID);
   }
-  const int ws = B.new_buf(lin_ws_floats * 4, "Linear split-K workspace");
+  const int ws = new_buf(lin_ws_floats * 4, "Linear split-K workspace");
   auto linear = [&](const SRef &xin, const Lin &l, bool relu, const SRef &y, int r) {
     SStep s;
     s.op = SOP_LINEAR;
     s.r[0] = xin;
-    s.r[1] = B.tensor(l.w);
-    s.r[2] = B.tensor(l.b);
+    s.r[1] = tensor(l.w);
+    s.r[2] = tensor(l.b);
     s.r[3] = y;
-    s.r[4] = B.buf(ws);
+    s.r[4] = buf(ws);
     s.i[0] = relu ? 1 : 0; s.i[1] = r; s.i[2] = l.fin; s.i[3] = l.fout;
     s.n = lin_ws(r, l.fin, l.fout);
-    B.push(s);
+    push(s);
   };
-  const int hl = B.new_buf((int64_t)V * N * ROT_DIM * 4, "lifter hidden");
-  linear(B.ref(SR_IMG_FEAT), lift0, true, B.buf(hl), V * N);
-  linear(B.buf(hl), lift1, false, B.ref(SR_LIFTED), V * N);
-  const int rel = B.new_buf((int64_t)rows * 9 * 4, "relative rotations");
-  {
-    SStep s;
-    s.op = SOP_RELROT;
-    s.r[0] = B.ref(SR_ROT);
-    s.r[1] = B.ref(SR_BUF, p.buf_rows, p.rows_vi);
-    s.r[2] = B.ref(SR_BUF, p.buf_rows, p.rows_vj);
-    s.r[3] = B.buf(rel);
-    s.i[0] = N; s.i[1] = V; s.i[2] = D;
-    B.push(s);
-  }
-  const SRef t_img = B.ref(SR_BUF, p.buf_rows, p.rows_img), t_view = B.ref(SR_BUF, p.buf_rows, p.rows_view),
-             t_partner = B.ref(SR_BUF, p.buf_rows, p.rows_partner), t_ident = B.ref(SR_BUF, p.buf_rows, p.rows_ident);
-  const int64_t feat_it = (int64_t)rows * ROT_DIM * 4, pred_it = (int64_t)rows * 2 * 4;
-  auto skinny = [&](const SRef &xin, const Lin &l, int it) {
-    SStep s;
-    s.op = SOP_SKINNY;
-    s.r[0] = xin;
-    s.r[1] = B.tensor(l.w);
-    s.r[2] = B.tensor(l.b);
-    s.r[3] = B.ref(SR_PREDS, 0, it * pred_it);
-    s.i[0] = rows; s.i[1] = HEAD_HID; s.i[2] = 2;
-    B.push(s);
-  };
+  const int hl = new_buf((int64_t)V * N * ROT_DIM * 4, "lifter hidden");
+  linear(ref(SR_IMG_FEAT), lift0, true, buf(hl), V * N);
+  linear(buf(hl), lift1, false, ref(SR_LIFTED), V * N);
+  const int rel = relrot();
+  const SRef t_img = rows_ref(p.rows_img), t_view = rows_ref(p.rows_view), t_partner = rows_ref(p.rows_partner),
+             t_ident = rows_ref(p.rows_ident);
 
   if (!p.head_split) {
     // FusionHead.forward, fused_in: [img_feat | R @ F] is generated inside the first Linear's operand loader
     auto fuser = [&](const SRef &feat, int feat_rows, bool rotate, const SRef &row_src, const Lin &l, const SRef &y) {
       SStep s;
       s.op = SOP_FUSER;
-      s.r[0] = B.ref(SR_IMG_FEAT);
+      s.r[0] = ref(SR_IMG_FEAT);
       s.r[1] = feat;
-      if (rotate) s.r[2] = B.buf(rel);
+      if (rotate) s.r[2] = buf(rel);
       s.r[3] = t_img;
       s.r[4] = row_src;
-      s.r[5] = B.tensor(l.w);
-      s.r[6] = B.tensor(l.b);
+      s.r[5] = tensor(l.w);
+      s.r[6] = tensor(l.b);
       s.r[7] = y;
-      s.r[8] = B.buf(ws);
+      s.r[8] = buf(ws);
       s.i[0] = 1; s.i[1] = rows; s.i[2] = cf; s.i[3] = l.fout; s.i[4] = V * N; s.i[5] = feat_rows;
       s.n = lin_ws(rows, cf + ROT_DIM, l.fout);
-      B.push(s);
+      push(s);
     };
     for (int it = 0; it < I; ++it) {
       const int m = c.share_weights ? 0 : it;
-      const int hf = B.new_buf((int64_t)rows * kin * 4, "fuser hidden"), hh = B.new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
-      const SRef src = it == 0 ? B.ref(SR_LIFTED) : B.ref(SR_FEATS, 0, (it - 1) * feat_it);
-      fuser(src, it == 0 ? V * N : rows, !c.ignore_rotmat, it == 0 ? t_view : t_partner, fu0[m], B.buf(hf));
-      linear(B.buf(hf), fu1[m], false, B.ref(SR_FEATS, 0, it * feat_it), rows);
-      fuser(B.ref(SR_FEATS, 0, it * feat_it), rows, false, t_ident, hd0[m], B.buf(hh));
-      skinny(B.buf(hh), hd1[m], it);
+      const int hf = new_buf((int64_t)rows * kin * 4, "fuser hidden"), hh = new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
+      const SRef src = it == 0 ? ref(SR_LIFTED) : ref(SR_FEATS, 0, (it - 1) * feat_it);
+      fuser(src, it == 0 ? V * N : rows, !c.ignore_rotmat, it == 0 ? t_view : t_partner, fu0[m], buf(hf));
+      linear(buf(hf), fu1[m], false, ref(SR_FEATS, 0, it * feat_it), rows);
+      fuser(ref(SR_FEATS, 0, it * feat_it), rows, false, t_ident, hd0[m], buf(hh));
+      skinny(buf(hh), hd1[m], it);
     }
   } else {
     // FusionHead._forward_split: every operand of a split Linear with its own power-of-two scale, found without extra passes
     int nslot = 0;
-    auto slot = [&]() { return B.ref(SR_BUF, p.buf_slots, 4LL * nslot++); };
+    auto slot = [&]() { return ref(SR_BUF, p.buf_slots, 4LL * nslot++); };
     const SRef am_img = slot(), am_lift = slot();
     std::vector<SRef> bam(I), am_f(I);
     for (int it = 0; it < I; ++it) bam[it] = slot();
@@ -577,90 +642,90 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
     {
       SStep s;                               // abs-max slots start at zero, every forward
       s.op = SOP_CLEAR;
-      s.r[0] = B.ref(SR_BUF, p.buf_slots);
+      s.r[0] = ref(SR_BUF, p.buf_slots);
       s.n = SESSION_SLOTS * 4;
-      B.push(s);
+      push(s);
     }
     {
       SStep s;
       s.op = SOP_ABSMAX;
       s.i[0] = 2 + I;
-      s.r[0] = B.ref(SR_IMG_FEAT);
+      s.r[0] = ref(SR_IMG_FEAT);
       s.cnt[0] = (int64_t)V * N * cf;
       s.r[8] = am_img;
-      s.r[1] = B.ref(SR_LIFTED);
+      s.r[1] = ref(SR_LIFTED);
       s.cnt[1] = (int64_t)V * N * ROT_DIM;
       s.r[9] = am_lift;
       for (int it = 0; it < I; ++it) {
-        s.r[2 + it] = B.tensor(fu0[c.share_weights ? 0 : it].b);
+        s.r[2 + it] = tensor(fu0[c.share_weights ? 0 : it].b);
         s.cnt[2 + it] = kin;
         s.r[10 + it] = bam[it];
       }
-      B.push(s);
+      push(s);
     }
     auto build_inputs = [&](const SRef &feat, const SRef &am_feat, const SRef &row_src_f, int xf, const SRef &xf_sinv, int xh,
                             const SRef &xh_sinv) {
       SStep s;
       s.op = SOP_FUSE_BUILD;
-      s.r[0] = B.ref(SR_IMG_FEAT);
+      s.r[0] = ref(SR_IMG_FEAT);
       s.r[1] = feat;
-      if (!c.ignore_rotmat) s.r[2] = B.buf(rel);
+      if (!c.ignore_rotmat) s.r[2] = buf(rel);
       s.r[3] = t_img;
       s.r[4] = row_src_f;
       if (xh >= 0) s.r[5] = t_ident;
       if (xf >= 0) {
-        s.r[6] = B.buf(xf);
+        s.r[6] = buf(xf);
         s.r[10] = xf_sinv;
       }
       if (xh >= 0) {
-        s.r[7] = B.buf(xh);
+        s.r[7] = buf(xh);
         s.r[11] = xh_sinv;
       }
       s.r[8] = am_img;
       s.r[9] = am_feat;
       s.i[0] = rows; s.i[1] = cf;
-      B.push(s);
+      push(s);
     };
     auto linear_split = [&](int xin, const SRef &x_sinv, const Lin &l, bool relu, const SRef &out, bool out_sp, const SRef &out_sinv,
                             const SRef &bias_absmax, const SRef &out_absmax) {
       const SWPrep &w = p.wprep_head[l.wprep];
       SStep s;
       s.op = SOP_LINEAR_SPLIT;
-      s.r[0] = B.buf(xin);
+      s.r[0] = buf(xin);
       s.r[1] = x_sinv;
       s.r[2] = wk_of(w);
       s.r[3] = sinv_of(w);
-      s.r[4] = B.tensor(l.b);
+      s.r[4] = tensor(l.b);
       s.r[5] = out;
       s.r[6] = out_sinv;
       s.r[7] = bias_absmax;
       s.r[8] = out_absmax;
       s.i[0] = rows; s.i[1] = l.fin; s.i[2] = l.fout; s.i[3] = relu ? 1 : 0; s.i[4] = out_sp ? 1 : 0;
-      B.push(s);
+      push(s);
     };
     const SRef none;
     const int64_t xbytes = (int64_t)rows * kin * 4;
-    int xf = B.new_buf(xbytes, "fuser input (sp)");
+    int xf = new_buf(xbytes, "fuser input (sp)");
     SRef xf_sinv = slot();
-    build_inputs(B.ref(SR_LIFTED), am_lift, t_view, xf, xf_sinv, -1, none);
+    build_inputs(ref(SR_LIFTED), am_lift, t_view, xf, xf_sinv, -1, none);
     for (int it = 0; it < I; ++it) {
       const int m = c.share_weights ? 0 : it;
-      const int h = B.new_buf(xbytes, "fuser hidden (sp)");
+      const int h = new_buf(xbytes, "fuser hidden (sp)");
       const SRef h_sinv = slot();
-      linear_split(xf, xf_sinv, fu0[m], true, B.buf(h), true, h_sinv, bam[it], none);
-      linear_split(h, h_sinv, fu1[m], false, B.ref(SR_FEATS, 0, it * feat_it), false, none, none, am_f[it]);
-      const int xh = B.new_buf(xbytes, "head input (sp)");
+      linear_split(xf, xf_sinv, fu0[m], true, buf(h), true, h_sinv, bam[it], none);
+      linear_split(h, h_sinv, fu1[m], false, ref(SR_FEATS, 0, it * feat_it), false, none, none, am_f[it]);
+      const int xh = new_buf(xbytes, "head input (sp)");
       const SRef xh_sinv = slot();
       int xf_next = -1;
       SRef xf_next_sinv;
       if (it + 1 < I) {
-        xf_next = B.new_buf(xbytes, "fuser input (sp)");
+        xf_next = new_buf(xbytes, "fuser input (sp)");
         xf_next_sinv = slot();
       }
-      build_inputs(B.ref(SR_FEATS, 0, it * feat_it), am_f[it], t_partner, xf_next, xf_next_sinv, xh, xh_sinv);
-      const int hh = B.new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
-      linear_split(xh, xh_sinv, hd0[m], true, B.buf(hh), false, none, none, none);
-      skinny(B.buf(hh), hd1[m], it);
+      build_inputs(ref(SR_FEATS, 0, it * feat_it), am_f[it], t_partner, xf_next, xf_next_sinv, xh, xh_sinv);
+      const int hh = new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
+      linear_split(xh, xh_sinv, hd0[m], true, buf(hh), false, none, none, none);
+      skinny(buf(hh), hd1[m], it);
       xf = xf_next;
       xf_sinv = xf_next_sinv;
     }
@@ -669,14 +734,7 @@ int build(const mvg_session_cfg &c, SessionPlan &p) {
       return 2;
     }
   }
-
-  allocate(p);
-  char why[256];
-  if (!self_check(p, why, sizeof(why))) {
-    set_error("session_create: the buffer plan failed its self-check: %s", why);
-    return 3;
-  }
-  return 0;
+  return finish();
 }
 
 // ---- the bf16 form.  What the bf16 entry points require of a launch, restated so that create rejects what forward would
@@ -701,111 +759,26 @@ bool bf16_conv_ok(const mvg_conv_desc &d, int a_elem, const char *what) {
 
 // The plan of the bf16 inference form: what MultiViewGaze.run_views queues with compute_dtype = torch.bfloat16 under eval() /
 // no_grad() with Backbone.bf16_fold_eval.  A change to the bf16 launches of backbone.py / heads.py is made here too.
-int build_bf16(const mvg_session_cfg &c, SessionPlan &p) {
-  Builder B(p);
+int Builder::build_bf16() {
   p.compute = MVG_SESSION_BF16;
-  const int V = c.views, N = c.batch, H = c.height, W = c.width, I = c.num_iter;
-  ConvSpec stem;
-  std::vector<BlockSpec> blocks;
-  int cf = 0;
-  backbone_spec(c.depth, stem, blocks, cf);
-  p.fc_dim = cf;
-  const int D = V * (V - 1), rows = D * N;
-  p.dirs = D;
-  p.head_rows = rows;
-
-  // ---- tensors, in state_dict order; one bf16 KRSC copy per conv (Backbone._prepare_weights, mode 0: every conv of
-  // spec.all_convs(), the stem's 3 channels padded to 8) and one fold per BatchNorm
-  struct ConvT {
-    ConvSpec s;
-    int t = 0, fold = -1, wprep = -1;
-  };
-  std::vector<ConvT> convs;
-  int64_t aff_bytes = 0, wk_bytes = 0;
-  auto prep = [&](std::vector<SWPrep> &to, int tensor, int cout, int rs, int cin, int cin_pad) {
-    SWPrep w;
-    w.tensor = tensor;
-    w.cout = cout;
-    w.rs = rs;
-    w.cin = cin;
-    w.cin_pad = cin_pad;
-    w.wk_off = wk_bytes;
-    wk_bytes += align_up((int64_t)cout * rs * cin_pad * 2);
-    to.push_back(w);
-    return (int)to.size() - 1;
-  };
-  auto add_conv = [&](const ConvSpec &s, bool is_stem) {
-    ConvT ct;
-    ct.s = s;
-    ct.t = B.add_tensor(s.name + ".weight", (int64_t)s.cout * s.cin * s.k * s.k);
-    B.add_tensor(s.bn + ".weight", s.cout);
-    B.add_tensor(s.bn + ".bias", s.cout);
-    B.add_tensor(s.bn + ".running_mean", s.cout);
-    B.add_tensor(s.bn + ".running_var", s.cout);
-    p.max_c = std::max(p.max_c, s.cout);
-    ct.fold = (int)p.folds.size();
-    // the stem's pass reads [V][cout] rows (Backbone._unit_fwd folds it with G = V): V records of the same BatchNorm, the
-    // scale rows first, then the shift rows; every other unit one row, shift behind scale
-    const int nrec = is_stem ? V : 1;
-    for (int v = 0; v < nrec; ++v) {
-      SBnFold f;
-      f.gamma = ct.t + 1;
-      f.c = s.cout;
-      f.aff_off = aff_bytes + 4LL * s.cout * v;
-      f.shift_off = aff_bytes + 4LL * s.cout * (nrec + v);
-      p.folds.push_back(f);
-    }
-    aff_bytes += align_up(2LL * nrec * s.cout * 4);
-    ct.wprep = prep(p.wprep_backbone, ct.t, s.cout, s.k * s.k, s.cin, s.cin == 3 ? 8 : s.cin);
-    convs.push_back(ct);
-    return (int)convs.size() - 1;
-  };
-  const int ci_stem = add_conv(stem, true);
-  std::vector<std::vector<int>> blk_convs(blocks.size());
-  std::vector<int> blk_ds(blocks.size(), -1);
-  for (size_t b = 0; b < blocks.size(); ++b) {
-    for (const ConvSpec &s : blocks[b].convs) blk_convs[b].push_back(add_conv(s, false));
-    if (blocks[b].has_ds) blk_ds[b] = add_conv(blocks[b].ds, false);
-  }
-  struct Lin {
-    int w = 0, b = 0, fin = 0, fout = 0, wprep = -1;
-  };
-  auto add_lin = [&](const std::string &name, int fin, int fout) {
-    Lin l;
-    l.fin = fin;
-    l.fout = fout;
-    l.w = B.add_tensor(name + ".weight", (int64_t)fout * fin);
-    l.b = B.add_tensor(name + ".bias", fout);
-    return l;
-  };
-  const int kin = cf + ROT_DIM;
-  Lin lift0 = add_lin("_lifter._lifter.blocks.0.0", cf, ROT_DIM), lift1 = add_lin("_lifter._lifter.blocks.1.0", ROT_DIM, ROT_DIM);
-  const int nmod = c.share_weights ? 1 : I;
-  std::vector<Lin> fu0(nmod), fu1(nmod), hd0(nmod), hd1(nmod);
-  for (int i = 0; i < nmod; ++i) {
-    const std::string pre = "_img_fusers." + std::to_string(i) + "._fuser.blocks.";
-    fu0[i] = add_lin(pre + "0.0", kin, kin);
-    fu1[i] = add_lin(pre + "1.0", kin, ROT_DIM);
-  }
-  for (int i = 0; i < nmod; ++i) {
-    const std::string pre = "_gaze_estimators." + std::to_string(i) + ".blocks.";
-    hd0[i] = add_lin(pre + "0.0", kin, HEAD_HID);
-    hd1[i] = add_lin(pre + "1.0", HEAD_HID, 2);
-  }
+  // ---- tensors; one bf16 KRSC copy per conv (Backbone._prepare_weights, mode 0: every conv of spec.all_convs(), the stem's 3
+  // channels padded to 8).  The stem's pass reads [V][cout] rows (Backbone._unit_fwd folds it with G = V): V records of the
+  // same BatchNorm, the scale rows first, then the shift rows; every other unit one row, shift behind scale
+  register_model(V, true, [](const ConvSpec &s) { return s.cin == 3 ? 8 : s.cin; });
   // Mlp._use_mixed: a layer runs on mvg_linear_fprop_mixed unless it is padded (a width that is no multiple of 4: none in
   // the variants a session serves) or it is a module's last layer with fout <= 4 (the heads' 512 -> 2: mvg_linear_skinny_fwd)
   auto use_mixed = [](const Lin &l, bool last) { return l.fin % 4 == 0 && l.fout % 4 == 0 && !(last && l.fout <= 4); };
   // FusionHead._prepare_split_weights(mixed=True): the lifter, then heads and fusers from the last iteration down
-  auto prep_lin = [&](Lin &l, bool last) {
-    if (use_mixed(l, last)) l.wprep = prep(p.wprep_head, l.w, l.fout, 1, l.fin, l.fin);
+  auto prep_mixed = [&](Lin &l, bool last) {
+    if (use_mixed(l, last)) prep_lin(l, l.fin);
   };
-  prep_lin(lift0, false);
-  prep_lin(lift1, true);
+  prep_mixed(lift0, false);
+  prep_mixed(lift1, true);
   for (int i = nmod - 1; i >= 0; --i) {
-    prep_lin(hd0[i], false);
-    prep_lin(hd1[i], true);
-    prep_lin(fu0[i], false);
-    prep_lin(fu1[i], true);
+    prep_mixed(hd0[i], false);
+    prep_mixed(hd1[i], true);
+    prep_mixed(fu0[i], false);
+    prep_mixed(fu1[i], true);
   }
   if (!use_mixed(lift0, false) || !use_mixed(lift1, true) || use_mixed(hd1[0], true)) {
     set_error("session_create (bf16): a Linear of this model is not on the path the session restates");
@@ -813,45 +786,17 @@ int build_bf16(const mvg_session_cfg &c, SessionPlan &p) {
   }
 
   // ---- persistent buffers (bind writes them)
-  p.tab_folds = 0;
-  p.tab_wprep_backbone = align_up((int64_t)p.folds.size() * 56);
-  p.tab_wprep_head = p.tab_wprep_backbone + align_up((int64_t)p.wprep_backbone.size() * 48);
-  p.tab_bytes = p.tab_wprep_head + align_up((int64_t)p.wprep_head.size() * 48);
-  p.buf_tables = B.new_buf(p.tab_bytes, "record tables", true);
-  const int64_t rt = align_up((int64_t)rows * 4), dt = align_up((int64_t)D * 4);
-  p.rows_vi = 0;
-  p.rows_vj = dt;
-  p.rows_img = 2 * dt;
-  p.rows_view = 2 * dt + rt;
-  p.rows_partner = 2 * dt + 2 * rt;
-  p.rows_ident = 2 * dt + 3 * rt;
-  p.buf_rows = B.new_buf(2 * dt + 4 * rt, "pair / row tables", true);
+  table_buffers();
+  const int64_t dt = align_up((int64_t)D * 4);
   p.dirs_partner = 0;
   p.dirs_ident = dt;
-  p.buf_dirs = B.new_buf(2 * dt, "direction tables (partner, ident)", true);
-  p.buf_affine = B.new_buf(aff_bytes, "folded BatchNorm (scale, shift)", true);
-  p.buf_wk = B.new_buf(wk_bytes, "bf16 weight copies (KRSC)", true);
-  p.buf_scratch = B.new_buf((int64_t)SESSION_SCRATCH_BYTES, "scratch", true);
+  p.buf_dirs = new_buf(2 * dt, "direction tables (partner, ident)", true);
+  p.buf_affine = new_buf(aff_bytes, "folded BatchNorm (scale, shift)", true);
+  p.buf_wk = new_buf(wk_bytes, "bf16 weight copies (KRSC)", true);
+  p.buf_scratch = new_buf((int64_t)SESSION_SCRATCH_BYTES, "scratch", true);
 
-  auto scale_of = [&](int ci) { return B.ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].aff_off); };
-  auto shift_of = [&](int ci) { return B.ref(SR_BUF, p.buf_affine, p.folds[convs[ci].fold].shift_off); };
-  auto wk_of = [&](const SWPrep &w) { return B.ref(SR_BUF, p.buf_wk, w.wk_off); };
-  auto act_bytes = [&](int h, int w, int ch) { return (int64_t)V * N * h * w * ch * 2; };
-
-  // ---- input layout (Backbone._input_layout, bf16; no row-window stem outside training): V launches into x0 [V][B][H][W][8]
-  const int x0 = B.new_buf(act_bytes(H, W, 8), "input NHWC8 (bf16)");
-  for (int v = 0; v < V; ++v) {
-    SStep s;
-    s.op = c.raw_u8 ? SOP_PREPROCESS_U8_BF16 : SOP_NCHW_TO_NHWC8_BF16;
-    s.r[0] = B.ref(SR_VIEW, v);
-    s.r[1] = B.buf(x0, (int64_t)v * N * H * W * 8 * 2);
-    if (c.raw_u8) {
-      s.i[0] = N; s.i[1] = c.in_h; s.i[2] = c.in_w; s.i[3] = H; s.i[4] = W; s.i[5] = c.input_bgr ? 1 : 0;
-    } else {
-      s.i[0] = N; s.i[1] = 3; s.i[2] = H; s.i[3] = W;
-    }
-    B.push(s);
-  }
+  // (no row-window stem outside training)
+  const int x0 = input_layout(SOP_NCHW_TO_NHWC8_BF16, SOP_PREPROCESS_U8_BF16, 8, "input NHWC8 (bf16)");
 
   // ---- stem (Backbone._unit_fwd, pool=True, not training): the raw conv output, then BatchNorm + ReLU + max pool in one pass
   const mvg_conv_desc dstem = make_desc(V, N, H, W, 8, stem.cout, stem.k, stem.stride, stem.pad);
@@ -862,77 +807,67 @@ int build_bf16(const mvg_session_cfg &c, SessionPlan &p) {
               (long long)V * N * hp);
     return 2;
   }
-  struct Map {               // a bf16 activation of the backbone: a buffer holding [V][B][h][w][c]
-    int buf = -1, h = 0, w = 0, c = 0;
-  };
-  Map x;
+  Act x;
   {
-    const int ystem = B.new_buf(act_bytes(dstem.ho, dstem.wo, stem.cout), "stem conv output (bf16)");
+    const int ystem = new_buf(act_bytes(dstem.ho, dstem.wo, stem.cout), "stem conv output (bf16)");
     SStep s;
     s.op = SOP_CONV_BF16;
     s.d = dstem;
-    s.r[0] = B.buf(x0);
+    s.r[0] = buf(x0);
     s.r[1] = wk_of(p.wprep_backbone[convs[ci_stem].wprep]);
-    s.r[2] = B.buf(ystem);
-    B.push(s);
-    const int pooled = B.new_buf(act_bytes(hp, wp, stem.cout), "pooled map (bf16)");
-    const int argmax = B.new_buf((int64_t)V * N * hp * wp * stem.cout, "pool argmax");
+    s.r[2] = buf(ystem);
+    push(s);
+    const int pooled = new_buf(act_bytes(hp, wp, stem.cout), "pooled map (bf16)");
+    const int argmax = new_buf((int64_t)V * N * hp * wp * stem.cout, "pool argmax");
     SStep t;
     t.op = SOP_BN_RELU_MAXPOOL_BF16;
-    t.r[0] = B.buf(ystem);
+    t.r[0] = buf(ystem);
     t.r[1] = scale_of(ci_stem);
     t.r[2] = shift_of(ci_stem);
-    t.r[3] = B.buf(pooled);
-    t.r[4] = B.buf(argmax);
+    t.r[3] = buf(pooled);
+    t.r[4] = buf(argmax);
     t.i[0] = V; t.i[1] = N; t.i[2] = dstem.ho; t.i[3] = dstem.wo; t.i[4] = stem.cout;
     t.cnt[0] = hp; t.cnt[1] = wp;
-    B.push(t);
+    push(t);
     x.buf = pooled;
     x.h = hp;
     x.w = wp;
     x.c = stem.cout;
   }
 
-  // ---- residual blocks.  unit() = Backbone._unit_infer's bf16 branch (one mvg_conv_fprop_bf16_affine); the loop =
-  // Backbone._forward_infer
+  // ---- residual blocks: Backbone._unit_infer's bf16 branch (one mvg_conv_fprop_bf16_affine).  Only the first launch the
+  // bf16 entry points would reject is reported
   bool bad = false;
-  auto unit = [&](int ci, const Map &in, bool relu, const Map *residual) {
+  x = block_loop(x, [&](int ci, const Act &in, bool relu, const Act *residual) {
     const ConvSpec &cs = convs[ci].s;
     const mvg_conv_desc d = make_desc(V, N, in.h, in.w, cs.cin, cs.cout, cs.k, cs.stride, cs.pad);
     if (!bad && !bf16_conv_ok(d, 2, cs.name.c_str())) bad = true;
-    Map out;
+    Act out;
     out.h = std::max(d.ho, 1);
     out.w = std::max(d.wo, 1);
     out.c = cs.cout;
-    out.buf = B.new_buf(act_bytes(out.h, out.w, out.c), "unit output (bf16)");
+    out.buf = new_buf(act_bytes(out.h, out.w, out.c), "unit output (bf16)");
     SStep s;
     s.op = SOP_CONV_BF16_AFFINE;
     s.d = d;
-    s.r[0] = B.buf(in.buf);
+    s.r[0] = buf(in.buf);
     s.r[1] = wk_of(p.wprep_backbone[convs[ci].wprep]);
-    s.r[2] = B.buf(out.buf);
+    s.r[2] = buf(out.buf);
     s.r[3] = scale_of(ci);
     s.r[4] = shift_of(ci);
-    if (residual) s.r[5] = B.buf(residual->buf);
+    if (residual) s.r[5] = buf(residual->buf);
     s.i[0] = relu ? 1 : 0;
-    B.push(s);
+    push(s);
     return out;
-  };
-  for (size_t b = 0; b < blocks.size(); ++b) {
-    Map identity = x, out = x;
-    const std::vector<int> &cv = blk_convs[b];
-    for (size_t k = 0; k + 1 < cv.size(); ++k) out = unit(cv[k], out, true, nullptr);
-    if (blk_ds[b] >= 0) identity = unit(blk_ds[b], x, false, nullptr);
-    x = unit(cv.back(), out, true, &identity);
-  }
+  });
   if (bad) return 2;
   {
     SStep s;
     s.op = SOP_AVGPOOL_BF16;
-    s.r[0] = B.buf(x.buf);
-    s.r[1] = B.ref(SR_IMG_FEAT);
+    s.r[0] = buf(x.buf);
+    s.r[1] = ref(SR_IMG_FEAT);
     s.i[0] = V * N; s.i[1] = x.h * x.w; s.i[2] = cf;
-    B.push(s);
+    push(s);
   }
 
   // ---- FusionHead.forward, mixed: lifter, relative rotations, then per iteration the materialised fuser input
@@ -944,68 +879,44 @@ int build_bf16(const mvg_session_cfg &c, SessionPlan &p) {
     s.op = SOP_LINEAR_MIXED;
     s.r[0] = xin;
     s.r[1] = wk_of(p.wprep_head[l.wprep]);
-    s.r[2] = B.tensor(l.b);
+    s.r[2] = tensor(l.b);
     s.r[3] = y;
     s.i[0] = last ? 0 : 1; s.i[1] = r; s.i[2] = l.fin; s.i[3] = l.fout;       // (ReLU on every layer but a module's last)
-    B.push(s);
+    push(s);
   };
-  const int hl = B.new_buf((int64_t)V * N * ROT_DIM * 4, "lifter hidden");
-  linear(B.ref(SR_IMG_FEAT), lift0, false, B.buf(hl), V * N);
-  linear(B.buf(hl), lift1, true, B.ref(SR_LIFTED), V * N);
-  const int rel = B.new_buf((int64_t)rows * 9 * 4, "relative rotations");
-  const SRef t_vi = B.ref(SR_BUF, p.buf_rows, p.rows_vi), t_vj = B.ref(SR_BUF, p.buf_rows, p.rows_vj),
-             t_partner = B.ref(SR_BUF, p.buf_dirs, p.dirs_partner), t_ident = B.ref(SR_BUF, p.buf_dirs, p.dirs_ident);
-  {
-    SStep s;
-    s.op = SOP_RELROT;
-    s.r[0] = B.ref(SR_ROT);
-    s.r[1] = t_vi;
-    s.r[2] = t_vj;
-    s.r[3] = B.buf(rel);
-    s.i[0] = N; s.i[1] = V; s.i[2] = D;
-    B.push(s);
-  }
+  const int hl = new_buf((int64_t)V * N * ROT_DIM * 4, "lifter hidden");
+  linear(ref(SR_IMG_FEAT), lift0, false, buf(hl), V * N);
+  linear(buf(hl), lift1, true, ref(SR_LIFTED), V * N);
+  const int rel = relrot();
+  const SRef t_vi = rows_ref(p.rows_vi), t_vj = rows_ref(p.rows_vj), t_partner = ref(SR_BUF, p.buf_dirs, p.dirs_partner),
+             t_ident = ref(SR_BUF, p.buf_dirs, p.dirs_ident);
   auto rotcat = [&](const SRef &feat, bool rotate, const SRef &src_of, int xbuf) {
     SStep s;
     s.op = SOP_ROTCAT;
-    s.r[0] = B.ref(SR_IMG_FEAT);
+    s.r[0] = ref(SR_IMG_FEAT);
     s.r[1] = feat;
-    if (rotate) s.r[2] = B.buf(rel);
+    if (rotate) s.r[2] = buf(rel);
     s.r[3] = t_vi;
     s.r[4] = src_of;
-    s.r[5] = B.buf(xbuf);
+    s.r[5] = buf(xbuf);
     s.i[0] = N; s.i[1] = D; s.i[2] = cf; s.i[3] = NVEC;
-    B.push(s);
+    push(s);
   };
-  const int64_t feat_it = (int64_t)rows * ROT_DIM * 4, pred_it = (int64_t)rows * 2 * 4, xbytes = (int64_t)rows * kin * 4;
+  const int64_t xbytes = (int64_t)rows * kin * 4;
   for (int it = 0; it < I; ++it) {
     const int m = c.share_weights ? 0 : it;
-    const SRef src = it == 0 ? B.ref(SR_LIFTED) : B.ref(SR_FEATS, 0, (it - 1) * feat_it), fn = B.ref(SR_FEATS, 0, it * feat_it);
-    const int xf = B.new_buf(xbytes, "fuser input"), hf = B.new_buf(xbytes, "fuser hidden");
+    const SRef src = it == 0 ? ref(SR_LIFTED) : ref(SR_FEATS, 0, (it - 1) * feat_it), fn = ref(SR_FEATS, 0, it * feat_it);
+    const int xf = new_buf(xbytes, "fuser input"), hf = new_buf(xbytes, "fuser hidden");
     rotcat(src, !c.ignore_rotmat, it == 0 ? t_vj : t_partner, xf);
-    linear(B.buf(xf), fu0[m], false, B.buf(hf), rows);
-    linear(B.buf(hf), fu1[m], true, fn, rows);
-    const int xh = B.new_buf(xbytes, "head input"), hh = B.new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
+    linear(buf(xf), fu0[m], false, buf(hf), rows);
+    linear(buf(hf), fu1[m], true, fn, rows);
+    const int xh = new_buf(xbytes, "head input"), hh = new_buf((int64_t)rows * HEAD_HID * 4, "head hidden");
     rotcat(fn, false, t_ident, xh);
-    linear(B.buf(xh), hd0[m], false, B.buf(hh), rows);
-    SStep s;
-    s.op = SOP_SKINNY;
-    s.r[0] = B.buf(hh);
-    s.r[1] = B.tensor(hd1[m].w);
-    s.r[2] = B.tensor(hd1[m].b);
-    s.r[3] = B.ref(SR_PREDS, 0, it * pred_it);
-    s.i[0] = rows; s.i[1] = HEAD_HID; s.i[2] = 2;
-    B.push(s);
+    linear(buf(xh), hd0[m], false, buf(hh), rows);
+    skinny(buf(hh), hd1[m], it);
   }
   if (bad) return 2;
-
-  allocate(p);
-  char why[256];
-  if (!self_check(p, why, sizeof(why))) {
-    set_error("session_create: the buffer plan failed its self-check: %s", why);
-    return 3;
-  }
-  return 0;
+  return finish();
 }
 
 }  // namespace
@@ -1067,7 +978,7 @@ int mvg_session_create_ex(const mvg_session_cfg *cfg, int32_t compute, mvg_sessi
     return 1;
   }
   s->cfg = c;
-  const int rc = compute == MVG_SESSION_BF16 ? build_bf16(c, s->plan) : build(c, s->plan);
+  const int rc = compute == MVG_SESSION_BF16 ? Builder(c, s->plan, 2).build_bf16() : Builder(c, s->plan, 4).build();
   if (rc != 0) {
     delete s;
     return rc;

@@ -1,55 +1,12 @@
 // Stand-alone check of the inference session's plan builder (rot-mvgaze_amd/csrc/session_plan.cpp): compiled together with
 // that file alone - no HIP, no Python - under -fsanitize=address,undefined and run as a plain executable by
-// tests/test_session_cpu.py.  Creates, queries and destroys sessions over the grid the CPU tests use, and the rejected
-// configurations; exits 0 when everything holds.
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
+// tests/test_session_cpu.py.  Creates, queries and destroys sessions over the grid the CPU tests use, runs check_plan
+// (session_check.h) on each - the fp32-MFMA and split plans' buffers, checked apart from the builder's self-check - and tries
+// the rejected configurations; exits 0 when everything holds.
 #include <set>
 #include <string>
 
-#include "../../include/rotmvgaze.h"
-
-// what api.hip provides inside the library
-static char g_err[512] = "";
-namespace mvg {
-void set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-}  // namespace mvg
-
-static int g_fail = 0;
-#define EXPECT(cond, ...)          \
-  do {                             \
-    if (!(cond)) {                 \
-      fprintf(stderr, __VA_ARGS__); \
-      fprintf(stderr, "\n");       \
-      ++g_fail;                    \
-    }                              \
-  } while (0)
-
-static mvg_session_cfg make_cfg(int depth, int views, int batch, int hw, int split, int raw, int share) {
-  mvg_session_cfg c;
-  memset(&c, 0, sizeof(c));
-  c.depth = depth;
-  c.num_iter = 3;
-  c.views = views;
-  c.batch = batch;
-  c.height = c.width = hw;
-  c.split = split;
-  c.share_weights = share;
-  c.raw_u8 = raw;
-  if (raw) {
-    c.in_h = 80;
-    c.in_w = 72;
-    c.input_bgr = 1;
-  }
-  return c;
-}
+#include "session_check.h"
 
 static void expect_rejected(const mvg_session_cfg *cfg, const char *what) {
   mvg_session *s = (mvg_session *)0x1;
@@ -88,6 +45,9 @@ int main() {
                 EXPECT(mvg_session_tensor_name(s, nt) == nullptr && mvg_session_tensor_name(s, -1) == nullptr, "out-of-range name");
                 EXPECT(mvg_session_tensor_numel(s, nt) == -1, "out-of-range numel");
                 EXPECT(mvg_session_workspace_bytes(s) > 0 && mvg_session_launches(s) > 0, "empty plan");
+                char tag[96];
+                snprintf(tag, sizeof(tag), "R%d V%d B%d %dpx split%d raw%d share%d", depth, views, batch, hw, split, raw, share);
+                check_plan(s, MVG_SESSION_FP32, tag);
                 mvg_session_destroy(s);
               }
   // out of scope

@@ -2,48 +2,11 @@
 // (rot-mvgaze_amd/csrc/session_plan.cpp): compiled together with that file alone - no HIP, no Python - under
 // -fsanitize=address,undefined and run as a plain executable by tests/test_range_guard_cpu.py.  Reads the plan itself
 // (session_plan.h): every sp-writing conv step and the split of the pooled map carries a distinct word index in [0, n),
-// every other step carries none, and the names are the layer table's in forward order.  Exits 0 when everything holds.
-#include <stdarg.h>
-#include <stdio.h>
-#include <string.h>
-
+// every other step carries none, and the names are the layer table's in forward order; each plan also goes through check_plan
+// (session_check.h).  Exits 0 when everything holds.
 #include <string>
-#include <vector>
 
-#include "../../rot-mvgaze_amd/csrc/session_plan.h"
-
-// what api.hip provides inside the library
-static char g_err[512] = "";
-namespace mvg {
-void set_error(const char *fmt, ...) {
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(g_err, sizeof(g_err), fmt, ap);
-  va_end(ap);
-}
-}  // namespace mvg
-
-static int g_fail = 0;
-#define EXPECT(cond, ...)          \
-  do {                             \
-    if (!(cond)) {                 \
-      fprintf(stderr, __VA_ARGS__); \
-      fprintf(stderr, "\n");       \
-      ++g_fail;                    \
-    }                              \
-  } while (0)
-
-static mvg_session_cfg make_cfg(int depth, int views, int batch, int hw, int split) {
-  mvg_session_cfg c;
-  memset(&c, 0, sizeof(c));
-  c.depth = depth;
-  c.num_iter = 3;
-  c.views = views;
-  c.batch = batch;
-  c.height = c.width = hw;
-  c.split = split;
-  return c;
-}
+#include "session_check.h"
 
 int main() {
   long checked = 0;
@@ -53,12 +16,15 @@ int main() {
       for (int batch : batches)
         for (int hw : sizes)
           for (int split = 0; split < 2; ++split) {
-            const mvg_session_cfg c = make_cfg(depth, views, batch, hw, split);
+            const mvg_session_cfg c = make_cfg(depth, views, batch, hw, split, 0, 0);
             mvg_session *s = nullptr;
             const int rc = mvg_session_create(&c, &s);
             EXPECT(rc == 0 && s != nullptr, "create(%d, V%d, B%d, %d px, split %d): rc %d '%s'", depth, views, batch, hw, split, rc, g_err);
             if (rc != 0 || !s) continue;
             ++checked;
+            char tag[96];
+            snprintf(tag, sizeof(tag), "R%d V%d B%d %dpx split%d", depth, views, batch, hw, split);
+            check_plan(s, MVG_SESSION_FP32, tag);
             const int n = mvg_session_num_range_units(s);
             // the 2 GiB guard: one view of layer1's output (4 bytes per element) stays below 0x7FFFFFF0 bytes - ResNet-50 at 224 px
             // fits up to batch 668 and leaves the split kernels from 669

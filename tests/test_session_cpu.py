@@ -151,16 +151,40 @@ def test_rejected_configurations(L, bad):
     assert L.mvg_last_error()
 
 
-def test_plan_builder_standalone_under_sanitizers(tmp_path):
+def _build_standalone(tmp_path, name):
+    """tests/native/<name>.cpp and session_plan.cpp, and nothing else, as one executable under ASan + UBSan."""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
-    assert cxx, "a host C++ compiler is needed to build tests/native/session_plan_check.cpp"
-    exe = str(tmp_path / "session_plan_check")
+    assert cxx, f"a host C++ compiler is needed to build tests/native/{name}.cpp"
+    exe = str(tmp_path / name)
     # the sanitizer runtimes are linked into the executable: it runs as it is, with nothing preloaded
     static = ["-static-libasan", "-static-libubsan"] if "clang" not in os.path.basename(cxx) else ["-static-libsan"]
     subprocess.run([cxx, "-std=c++17", "-O1", "-fsanitize=address,undefined", "-fno-sanitize-recover=undefined"] + static + ["-o", exe,
-                    os.path.join(ROOT, "tests", "native", "session_plan_check.cpp"),
+                    os.path.join(ROOT, "tests", "native", name + ".cpp"),
                     os.path.join(ROOT, "rot-mvgaze_amd", "csrc", "session_plan.cpp")], check=True)
-    r = subprocess.run([exe], capture_output=True, text=True)
+    return exe
+
+
+def test_plan_builder_standalone_under_sanitizers(tmp_path):
+    r = subprocess.run([_build_standalone(tmp_path, "session_plan_check")], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "session_plan_check: ok" in r.stdout
     assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+
+
+def test_plans_match_the_recorded_digests(tmp_path):
+    """Every field of every plan over the dump's sweep (both depths, 2 / 3 / 8 views, batch up to 700, 64 and 224 px, the
+    fp32-MFMA, split and bf16 forms, raw_u8 / share_weights / ignore_rotmat, num_iter 1 .. 6, 32 px, 96 x 64) is what
+    tests/golden/session_plan_digests.txt records, and the rejected configurations are rejected with the recorded text: the
+    executor reads nothing but the plan, so the forward a session queues has not moved.
+
+    A change that means to move the plan regenerates the fixture from its own build and says so:
+        g++ -std=c++17 -O1 -o /tmp/session_plan_dump tests/native/session_plan_dump.cpp rot-mvgaze_amd/csrc/session_plan.cpp
+        /tmp/session_plan_dump > tests/golden/session_plan_digests.txt
+    (`session_plan_dump --full` prints the rendering behind each digest; diff two of them to see what moved.)"""
+    r = subprocess.run([_build_standalone(tmp_path, "session_plan_dump")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stderr
+    assert "ERROR" not in r.stderr and "runtime error" not in r.stderr, r.stderr
+    want = open(os.path.join(ROOT, "tests", "golden", "session_plan_digests.txt")).read()
+    got, exp = r.stdout.splitlines(), want.splitlines()
+    moved = [f"{g!r} (recorded: {e!r})" for g, e in zip(got, exp) if g != e]
+    assert r.stdout == want, f"{len(got)} lines against {len(exp)} recorded; {len(moved)} differ, the first: {moved[:3]}"
