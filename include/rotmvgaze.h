@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MVG_ABI_VERSION 11
+#define MVG_ABI_VERSION 12
 
 /* ---------------------------------------------------------------- library */
 int mvg_abi_version(void);
@@ -128,6 +128,30 @@ int mvg_conv_wgrad(const mvg_conv_desc *d, const float *x, const float *dy, floa
                    float *workspace, int splits, int accumulate, void *stream);
 /* a split count that fills the device for this shape (host helper, no launch). */
 int mvg_conv_wgrad_splits(const mvg_conv_desc *d);
+/* Host-only plan queries of the fp32-MFMA kernels (tests guard with them which form a shape runs): answered by the
+ * code the launches plan with, for the CUs the planners may use now (mvg_set_reserved_cus); nothing is launched and
+ * no device is needed (then: 256 CUs, one workgroup per CU where the occupancy query fails).  -1 (and a message)
+ * for a descriptor the launch would reject.
+ * mvg_conv_plan_query: `kind` names the launch - MVG_PLAN_FPROP (mvg_conv_fprop without stats, mvg_conv_fprop_affine,
+ * mvg_linear_fprop), MVG_PLAN_FPROP_STATS (mvg_conv_fprop with stats: never split-K), MVG_PLAN_DGRAD (mvg_conv_dgrad,
+ * mvg_linear_dgrad), MVG_PLAN_FUSER_FPROP (mvg_fuser_fprop with the descriptor {1, rows, 1, 1, cf + 3 nvec, fout, 1, 1,
+ * 1, 0, 1, 1}); ws_floats is the split-K workspace the launch would be given (0: none).  out may be NULL. */
+enum { MVG_PLAN_FPROP = 0, MVG_PLAN_FPROP_STATS = 1, MVG_PLAN_DGRAD = 2, MVG_PLAN_FUSER_FPROP = 3 };
+typedef struct {
+  int32_t bm, bn, bk;      /* tile and K-step depth of the kernel instantiation */
+  int32_t fasta;           /* 1: the uniform-tap operand loader */
+  int32_t ncls;            /* classes in the launch (backward-data at stride 2: up to 4; those without taps are dropped) */
+  int32_t cls_tiles[4];    /* per class, in launch order: tiles, */
+  int32_t cls_kt[4];       /* ... and K-steps per tile */
+  int32_t streamk_grid;    /* persistent workgroups of the stream-K form; 0: one tile (times splitk) per workgroup */
+  int32_t splitk;          /* K splits into the caller's workspace (1: none) */
+  int64_t scratch_floats;  /* registered scratch the stream-K form needs (0 when streamk_grid == 0); with less
+                            * registered for the stream the launch takes the plain form */
+} mvg_conv_plan;
+int mvg_conv_plan_query(const mvg_conv_desc *d, int kind, size_t ws_floats, mvg_conv_plan *out);
+/* the tile (bm rows of cout x bn columns of r*s*cin) mvg_conv_wgrad runs `d` on, and whether its loader steps the
+ * pixel coordinates incrementally; every out-pointer may be NULL. */
+int mvg_conv_wgrad_tile(const mvg_conv_desc *d, int32_t *bm, int32_t *bn, int32_t *incremental);
 /* The cross-view fusion GEMM with its input generated inside the kernel (rot_mv.py:44-50 ImageFeatFuser
  * first layer on cat([img_feat_i, (R_ij @ F_j).flatten]), :234-239; and the gaze head's first layer on
  * cat([img_feat_i, F_i.flatten]), :249-254, with rel = NULL):

@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "librotmvgaze_hip.so")
 
 K_FAMILIES = 18
-ABI_VERSION = 11
+ABI_VERSION = 12
 SESSION_FP32, SESSION_BF16 = 0, 1         # MVG_SESSION_FP32 / MVG_SESSION_BF16 (mvg_session_create_ex)
 
 
@@ -29,6 +29,16 @@ class ConvDesc(C.Structure):
     @classmethod
     def linear(cls, rows, fin, fout):
         return cls(1, rows, 1, 1, fin, fout, 1, 1, 1, 0, 1, 1)
+
+
+PLAN_FPROP, PLAN_FPROP_STATS, PLAN_DGRAD, PLAN_FUSER_FPROP = 0, 1, 2, 3       # MVG_PLAN_* (mvg_conv_plan_query)
+
+
+class ConvPlan(C.Structure):
+    """mvg_conv_plan (include/rotmvgaze.h)."""
+    _fields_ = [("bm", C.c_int32), ("bn", C.c_int32), ("bk", C.c_int32), ("fasta", C.c_int32), ("ncls", C.c_int32),
+                ("cls_tiles", C.c_int32 * 4), ("cls_kt", C.c_int32 * 4), ("streamk_grid", C.c_int32), ("splitk", C.c_int32),
+                ("scratch_floats", C.c_int64)]
 
 
 class ProfEntry(C.Structure):
@@ -67,6 +77,8 @@ SIGNATURES = {
     "mvg_conv_dgrad": (_I, [_D, _P, _P, _P, _P, _P, _P]),
     "mvg_conv_wgrad": (_I, [_D, _P, _P, _P, _P, _I, _I, _P]),
     "mvg_conv_wgrad_splits": (_I, [_D]),
+    "mvg_conv_plan_query": (_I, [_D, _I, C.c_size_t, C.POINTER(ConvPlan)]),
+    "mvg_conv_wgrad_tile": (_I, [_D, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mvg_linear_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),
     "mvg_fuser_fprop": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),
     "mvg_fuser_wgrad": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P]),

@@ -1092,13 +1092,25 @@ static TileChoice choose_tile(long long rows_per_group, int groups, int ncols, i
   return choose_tile_multi(&rows_per_group, &ktotal, 1, groups, ncols, dgrad);
 }
 
+// `query` != nullptr (mvg_conv_plan_query): the plan of this instantiation is written there and nothing is launched
 template <int BM, int BN, int BK, int WGM, int WGN, bool DGRAD, bool FASTA = false, int AMODE = 0>
-static int launch_igemm_tile(IgemmParams &p, long long tiles, long long units, hipStream_t st) {
+static int launch_igemm_tile(IgemmParams &p, long long tiles, long long units, hipStream_t st, mvg_conv_plan *query) {
   int P = 0;
   if (p.splits == 1 && units > tiles)
     P = plan_streamk(tiles, (int)(units / tiles), BM, BN, igemm_occupancy<BM, BN, BK, WGM, WGN, DGRAD, FASTA, AMODE>(), BK);
+  const size_t scratch_floats = (size_t)P * 2 * BM * BN;
+  if (query) {
+    query->bm = BM;
+    query->bn = BN;
+    query->bk = BK;
+    query->fasta = FASTA ? 1 : 0;
+    query->streamk_grid = P;
+    query->splitk = p.splits;
+    query->scratch_floats = (int64_t)scratch_floats;
+    return 0;
+  }
   if (P > 0) {
-    float *scratch = stream_scratch(st, (size_t)P * 2 * BM * BN);
+    float *scratch = stream_scratch(st, scratch_floats);
     if (!scratch) P = 0;                                   // no scratch: plain launch
     else p.slab = scratch;
   }
@@ -1116,7 +1128,7 @@ static int launch_igemm_tile(IgemmParams &p, long long tiles, long long units, h
 
 // p.cls[0 .. ncls) hold the classes (out_h .. ow_div filled in); tile and unit offsets are set here
 template <bool DGRAD>
-static int launch_igemm(IgemmParams &p, TileChoice t, hipStream_t st) {
+static int launch_igemm(IgemmParams &p, TileChoice t, hipStream_t st, mvg_conv_plan *query = nullptr) {
   p.ntiles = ceil_div(p.ncols, t.bn);
   if (p.splits < 1) p.splits = 1;
   if (p.splits == 1) p.ktiles_per_split = 1 << 30;
@@ -1132,7 +1144,12 @@ static int launch_igemm(IgemmParams &p, TileChoice t, hipStream_t st) {
     const long long ti = (long long)p.groups * c.mtiles_per_group * p.ntiles;
     tiles += ti;
     units += ti * c.KT;
+    if (query) {
+      query->cls_tiles[i] = (int32_t)ti;
+      query->cls_kt[i] = c.KT;
+    }
   }
+  if (query) query->ncls = p.ncls;
   MVG_REQUIRE(tiles * p.splits < (1LL << 31), "conv: grid too large");
   MVG_REQUIRE(p.splits == 1 || p.ncls == 1, "conv: split-K with several classes");
   if (tiles <= 0) return 0;
@@ -1145,28 +1162,28 @@ static int launch_igemm(IgemmParams &p, TileChoice t, hipStream_t st) {
   if constexpr (!DGRAD) {
     if (p.rc_feat != nullptr) {
       MVG_REQUIRE(fasta && t.bn >= 64, "fuser GEMM: shape not covered by the rotate + concat loader");
-      if (t.bm == 128 && t.bn == 128) return launch_igemm_tile<128, 128, 16, 2, 2, false, true, 1>(p, tiles, units, st);
-      if (t.bm == 128 && t.bn == 64) return launch_igemm_tile<128, 64, 16, 2, 2, false, true, 1>(p, tiles, units, st);
-      return launch_igemm_tile<64, 64, 16, 2, 2, false, true, 1>(p, tiles, units, st);
+      if (t.bm == 128 && t.bn == 128) return launch_igemm_tile<128, 128, 16, 2, 2, false, true, 1>(p, tiles, units, st, query);
+      if (t.bm == 128 && t.bn == 64) return launch_igemm_tile<128, 64, 16, 2, 2, false, true, 1>(p, tiles, units, st, query);
+      return launch_igemm_tile<64, 64, 16, 2, 2, false, true, 1>(p, tiles, units, st, query);
     }
   }
   if (t.bm == 128 && t.bn == 128) {
     if (bk == 32) {
-      if (fasta) return launch_igemm_tile<128, 128, 32, 2, 2, DGRAD, true>(p, tiles, units, st);
-      return launch_igemm_tile<128, 128, 32, 2, 2, DGRAD>(p, tiles, units, st);
+      if (fasta) return launch_igemm_tile<128, 128, 32, 2, 2, DGRAD, true>(p, tiles, units, st, query);
+      return launch_igemm_tile<128, 128, 32, 2, 2, DGRAD>(p, tiles, units, st, query);
     }
-    if (fasta) return launch_igemm_tile<128, 128, 16, 2, 2, DGRAD, true>(p, tiles, units, st);
-    return launch_igemm_tile<128, 128, 16, 2, 2, DGRAD>(p, tiles, units, st);
+    if (fasta) return launch_igemm_tile<128, 128, 16, 2, 2, DGRAD, true>(p, tiles, units, st, query);
+    return launch_igemm_tile<128, 128, 16, 2, 2, DGRAD>(p, tiles, units, st, query);
   }
   if (t.bm == 128 && t.bn == 64) {
-    if (fasta) return launch_igemm_tile<128, 64, 16, 2, 2, DGRAD, true>(p, tiles, units, st);
-    return launch_igemm_tile<128, 64, 16, 2, 2, DGRAD>(p, tiles, units, st);
+    if (fasta) return launch_igemm_tile<128, 64, 16, 2, 2, DGRAD, true>(p, tiles, units, st, query);
+    return launch_igemm_tile<128, 64, 16, 2, 2, DGRAD>(p, tiles, units, st, query);
   }
   if (t.bm == 64 && t.bn == 64) {
-    if (fasta) return launch_igemm_tile<64, 64, 16, 2, 2, DGRAD, true>(p, tiles, units, st);     // the fusion block's Linears
-    return launch_igemm_tile<64, 64, 16, 2, 2, DGRAD>(p, tiles, units, st);
+    if (fasta) return launch_igemm_tile<64, 64, 16, 2, 2, DGRAD, true>(p, tiles, units, st, query);     // the fusion block's Linears
+    return launch_igemm_tile<64, 64, 16, 2, 2, DGRAD>(p, tiles, units, st, query);
   }
-  return launch_igemm_tile<128, 32, 16, 4, 1, DGRAD>(p, tiles, units, st);
+  return launch_igemm_tile<128, 32, 16, 4, 1, DGRAD>(p, tiles, units, st, query);
 }
 
 // split-K plan for a GEMM whose tile grid cannot fill the device: returns splits (>= 1) and sets
@@ -1227,7 +1244,7 @@ struct RotCat {            // generated cross-view input, see IgemmParams::rc_*
 
 static int fprop_impl(const mvg_conv_desc *d, const float *x, const float *wgt, float *y, const float *bias, int relu,
                       float *stats, float *ws, size_t ws_floats, void *stream, const float *scale = nullptr,
-                      const float *residual = nullptr, const RotCat *rc = nullptr) {
+                      const float *residual = nullptr, const RotCat *rc = nullptr, mvg_conv_plan *query = nullptr) {
   if (validate(d)) return 2;
   IgemmParams p;
   memset(&p, 0, sizeof(p));
@@ -1256,8 +1273,10 @@ static int fprop_impl(const mvg_conv_desc *d, const float *x, const float *wgt, 
   const double bytes = 4.0 * (d->groups * (double)d->n * d->h * d->w * alg_cin(d) + (double)d->cout * d->r * d->s * alg_cin(d) +
                               d->groups * (double)p.rows_per_group * d->cout);
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
+  const bool splitk = !stats && plan_splitk(p, t, (ws || query) ? ws_floats : 0, false) > 1;
+  if (query) return launch_igemm<false>(p, t, nullptr, query);        // plan only: nothing is launched
   ProfScope ps(lin ? MVG_K_LINEAR_FPROP : MVG_K_CONV_FPROP, (hipStream_t)stream, flops, bytes);
-  if (!stats && plan_splitk(p, t, ws ? ws_floats : 0, false) > 1) {
+  if (splitk) {
     p.slab = ws;
     if (launch_igemm<false>(p, t, (hipStream_t)stream)) return 1;
     return launch_splitk_reduce(p, (hipStream_t)stream);
@@ -1266,7 +1285,7 @@ static int fprop_impl(const mvg_conv_desc *d, const float *x, const float *wgt, 
 }
 
 static int dgrad_impl(const mvg_conv_desc *d, const float *dy, const float *wgt, float *dx, const float *mask,
-                      const float *addend, float *ws, size_t ws_floats, void *stream) {
+                      const float *addend, float *ws, size_t ws_floats, void *stream, mvg_conv_plan *query = nullptr) {
   if (validate(d)) return 2;
   MVG_REQUIRE(d->cout % 4 == 0, "dgrad: cout %% 4 != 0 (%d)", d->cout);
   IgemmParams p;
@@ -1282,22 +1301,34 @@ static int dgrad_impl(const mvg_conv_desc *d, const float *dy, const float *wgt,
   const double bytes = 4.0 * (d->groups * (double)d->n * d->ho * d->wo * d->cout + (double)d->cout * d->r * d->s * alg_cin(d) +
                               d->groups * (double)d->n * d->h * d->w * alg_cin(d));
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
+  // the class table, the tile over it, the split-K plan and launch_igemm: what a launch runs and what a query reports
+  auto run = [&]() -> int {
+    if (query) {                     // plan only: the class table without the fills of the classes it drops
+      DgradDropped dropped;
+      dgrad_plan_classes(p, d, false, dropped);
+    } else if (int e = dgrad_classes(p, d, false, 4, dx, addend, (hipStream_t)stream)) {
+      return e;
+    }
+    if (p.ncls == 0) return 0;
+    long long cls_rows[4];
+    int cls_k[4];
+    for (int i = 0; i < p.ncls; ++i) {
+      cls_rows[i] = p.cls[i].rows_per_group;
+      cls_k[i] = p.cls[i].ktotal;
+    }
+    const TileChoice t = choose_tile_multi(cls_rows, cls_k, p.ncls, d->groups, d->cin, true);
+    const bool splitk = p.ncls == 1 && d->stride == 1 && plan_splitk(p, t, (ws || query) ? ws_floats : 0, true) > 1;
+    if (query) return launch_igemm<true>(p, t, nullptr, query);
+    if (splitk) {
+      p.slab = ws;
+      if (launch_igemm<true>(p, t, (hipStream_t)stream)) return 1;
+      return launch_splitk_reduce(p, (hipStream_t)stream);
+    }
+    return launch_igemm<true>(p, t, (hipStream_t)stream);
+  };
+  if (query) return run();
   ProfScope ps(lin ? MVG_K_LINEAR_DGRAD : MVG_K_CONV_DGRAD, (hipStream_t)stream, flops, bytes);
-  if (int e = dgrad_classes(p, d, false, 4, dx, addend, (hipStream_t)stream)) return e;
-  if (p.ncls == 0) return 0;
-  long long cls_rows[4];
-  int cls_k[4];
-  for (int i = 0; i < p.ncls; ++i) {
-    cls_rows[i] = p.cls[i].rows_per_group;
-    cls_k[i] = p.cls[i].ktotal;
-  }
-  const TileChoice t = choose_tile_multi(cls_rows, cls_k, p.ncls, d->groups, d->cin, true);
-  if (p.ncls == 1 && d->stride == 1 && plan_splitk(p, t, ws ? ws_floats : 0, true) > 1) {
-    p.slab = ws;
-    if (launch_igemm<true>(p, t, (hipStream_t)stream)) return 1;
-    return launch_splitk_reduce(p, (hipStream_t)stream);
-  }
-  return launch_igemm<true>(p, t, (hipStream_t)stream);
+  return run();
 }
 
 static mvg_conv_desc linear_desc(int rows, int fin, int fout) {
@@ -1325,6 +1356,29 @@ int mvg_conv_fprop_affine(const mvg_conv_desc *d, const float *x, const float *w
   return fprop_impl(d, x, wgt, out, shift, relu, nullptr, nullptr, 0, stream, scale, residual);
 }
 
+int mvg_conv_plan_query(const mvg_conv_desc *d, int kind, size_t ws_floats, mvg_conv_plan *out) {
+  mvg_conv_plan plan;
+  memset(&plan, 0, sizeof(plan));
+  plan.splitk = 1;
+  int rc = 2;
+  static float rc_marker;            // the loaders' rc_feat != nullptr is what selects the rotate + concat instantiations
+  if (kind == MVG_PLAN_FPROP) {
+    rc = fprop_impl(d, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, ws_floats, nullptr, nullptr, nullptr, nullptr, &plan);
+  } else if (kind == MVG_PLAN_FPROP_STATS) {
+    rc = fprop_impl(d, nullptr, nullptr, nullptr, nullptr, 0, &rc_marker, nullptr, ws_floats, nullptr, nullptr, nullptr, nullptr, &plan);
+  } else if (kind == MVG_PLAN_DGRAD) {
+    rc = dgrad_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, ws_floats, nullptr, &plan);
+  } else if (kind == MVG_PLAN_FUSER_FPROP) {
+    const RotCat rotcat = {&rc_marker, nullptr, nullptr, nullptr, 128, 128, 1, 1};
+    rc = fprop_impl(d, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, ws_floats, nullptr, nullptr, nullptr, &rotcat, &plan);
+  } else {
+    set_error("conv_plan_query: unknown kind %d", kind);
+  }
+  if (rc) return -1;
+  if (out) *out = plan;
+  return 0;
+}
+
 size_t mvg_linear_workspace_floats(int rows, int fin, int fout) {
   // up to 16 K-slices of the larger of the two GEMM outputs (fprop: rows x fout, dgrad: rows x fin)
   const size_t m = (size_t)rows * (size_t)(fin > fout ? fin : fout);
@@ -1350,6 +1404,12 @@ static TileChoice wgrad_tile(const mvg_conv_desc *d) {
   if (ncols >= 64 && d->cout >= 64) return {64, 64};
   if (d->cout < 64) return {32, 128};   // skinny cout (e.g. 2-wide head is handled elsewhere)
   return {128, 32};
+}
+// incremental pixel stepping of the wgrad loader: needs >= 32 pixels per image (one image wrap per step at most), 24-bit
+// factors in the offset multiplies and 32-bit x offsets
+static bool wgrad_incremental(const mvg_conv_desc *d) {
+  return (long long)d->ho * d->wo >= 32 && d->ho < (1 << 20) && d->wo < (1 << 20) &&
+         (long long)d->stride * d->w * d->cin * 4 < (1 << 24);
 }
 
 }  // extern "C"
@@ -1385,6 +1445,15 @@ int mvg_conv_wgrad_splits(const mvg_conv_desc *d) {
   return wgrad_split_count(tiles, (long long)d->groups * d->n * d->ho * d->wo, wpc > 4 ? 4 : wpc, 256);   // 16 K-steps per split
 }
 
+int mvg_conv_wgrad_tile(const mvg_conv_desc *d, int32_t *bm, int32_t *bn, int32_t *incremental) {
+  if (validate(d)) return -1;
+  const TileChoice t = wgrad_tile(d);
+  if (bm) *bm = t.bm;
+  if (bn) *bn = t.bn;
+  if (incremental) *incremental = wgrad_incremental(d) ? 1 : 0;
+  return 0;
+}
+
 static int wgrad_impl(const mvg_conv_desc *d, const float *x, const float *dy, float *dw, float *db, float *workspace,
                       int splits, int accumulate, void *stream, const RotCat *rc = nullptr) {
   if (validate(d)) return 2;
@@ -1416,10 +1485,7 @@ static int wgrad_impl(const mvg_conv_desc *d, const float *x, const float *dy, f
     ProfScope ps(lin ? MVG_K_LINEAR_WGRAD : MVG_K_CONV_WGRAD, st, flops, bytes);
     MVG_REQUIRE((long long)p.mtiles * p.ntiles * splits < (1LL << 31), "wgrad: grid too large");
     dim3 grid(p.mtiles * p.ntiles * splits), block(256);
-    // incremental pixel stepping: needs >= 32 pixels per image (one image wrap per step at most), 24-bit
-    // factors in the offset multiplies and 32-bit x offsets
-    const bool incr = (long long)d->ho * d->wo >= 32 && d->ho < (1 << 20) && d->wo < (1 << 20) &&
-                      (long long)d->stride * d->w * d->cin * 4 < (1 << 24);
+    const bool incr = wgrad_incremental(d);
 #define MVG_WGRAD_LAUNCH(BM_, BN_, WGM_, WGN_)                                                              \
   do {                                                                                                      \
     if (incr) hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, 16, WGM_, WGN_, true>), grid, block, 0, st, p);    \

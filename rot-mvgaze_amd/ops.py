@@ -139,6 +139,29 @@ def conv_wgrad(d: ConvDesc, x: Tensor, dy: Tensor, dw: Tensor, accumulate: bool 
     check(_fn("mvg_conv_wgrad", x)(C.byref(d), _p(x), _p(dy), _p(dw), _p(ws), splits, int(accumulate), _s()), "conv_wgrad")
 
 
+def conv_plan_query(d: ConvDesc, kind: int = 0, ws_floats: int = 0) -> dict:
+    """What the fp32-MFMA launch of ``d`` would run on this device with the CUs the planners may use now (set_reserved_cus),
+    answered by the code the launch plans with; nothing is launched.  kind: _lib.PLAN_FPROP (conv_fprop without stats,
+    conv_fprop_affine, linear_fprop), PLAN_FPROP_STATS, PLAN_DGRAD, PLAN_FUSER_FPROP (fuser_fprop; d = ConvDesc.linear(rows,
+    cf + 3 nvec, fout)); ws_floats: the split-K workspace of the Linear entry points.  Keys: bm, bn, bk, fasta, cls_tiles and
+    cls_kt (one entry per class of the launch), streamk_grid (0: one tile per workgroup), splitk, scratch_floats."""
+    from ._lib import ConvPlan
+    pl = ConvPlan()
+    if lib().mvg_conv_plan_query(C.byref(d), int(kind), int(ws_floats), C.byref(pl)) != 0:
+        check(1, "conv_plan_query")
+    return {"bm": pl.bm, "bn": pl.bn, "bk": pl.bk, "fasta": bool(pl.fasta), "cls_tiles": list(pl.cls_tiles[:pl.ncls]),
+            "cls_kt": list(pl.cls_kt[:pl.ncls]), "streamk_grid": pl.streamk_grid, "splitk": pl.splitk,
+            "scratch_floats": pl.scratch_floats}
+
+
+def conv_wgrad_tile(d: ConvDesc):
+    """(bm, bn, incremental): the tile conv_wgrad runs ``d`` on and whether the kernel addresses pixels incrementally."""
+    bm, bn, incr = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if lib().mvg_conv_wgrad_tile(C.byref(d), C.byref(bm), C.byref(bn), C.byref(incr)) != 0:
+        check(1, "conv_wgrad_tile")
+    return bm.value, bn.value, bool(incr.value)
+
+
 def linear_wgrad(x: Tensor, dy: Tensor, dw: Tensor, db: Optional[Tensor], rows: int, fin: int, fout: int, accumulate: bool = False):
     """dw (+)= dy^T x and db (+)= column sums of dy in one launch (+ the fixed-order slab reduce)."""
     d = ConvDesc.linear(rows, fin, fout)

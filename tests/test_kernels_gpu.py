@@ -51,26 +51,40 @@ CONV_CASES = [
     (1, 2, 17, 18, 64, 64, 7, 2, 3),      # 7x7 stride 2 dgrad (4/3-tap lattices per axis)
     (2, 8, 56, 56, 256, 512, 1, 2, 0),
     (2, 64, 56, 56, 64, 128, 1, 2, 0),    # many more wgrad splits than pixels/272: empty trailing splits
-    (2, 16, 28, 28, 128, 128, 3, 1, 1),   # 196 tiles of 128x128 on 512 slots -> stream-K (fprop and dgrad)
-    (2, 16, 56, 56, 64, 64, 3, 1, 1),     # 784 tiles of 128x64 -> stream-K with several tiles per workgroup
-    (2, 16, 56, 56, 64, 128, 3, 2, 1),    # stride 2: stream-K fprop, parity-class dgrad
+    (2, 16, 28, 28, 128, 128, 3, 1, 1),   # 196 tiles of 128x128 on 512 / 768 slots -> stream-K (fprop and dgrad), see STREAMK_CLAIMS
+    (2, 16, 56, 56, 64, 64, 3, 1, 1),     # 784 tiles of 128x64 on 1280 slots: one tile per workgroup (stream-K only below 2 per CU)
+    (2, 16, 56, 56, 64, 128, 3, 2, 1),    # stride 2: 784 tiles of 64x64 forward, four parity classes of 196 128x64 tiles backward
     (1, 30, 14, 14, 256, 256, 3, 1, 1),   # ragged last M tile (5880 rows) under stream-K
     (1, 24, 57, 57, 64, 64, 1, 1, 0),     # 1219 BN partials (ragged last one): two-level bn_finalize
     (1, 4, 20, 20, 16, 64, 3, 1, 1),      # 16 channels per tap: uniform-tap loader with tap-major K order
     (2, 6, 30, 30, 16, 128, 3, 2, 1),     # same, stride 2 (dgrad classes over 128 channels)
 ]
+# (forward, backward-data) runs as stream-K on the 256 CUs of an MI355X: asserted through the plan query before the launches.
+# Structures the two plain cases once claimed (several whole tiles per workgroup, stream-K over stride-2 classes) run in
+# test_igemm_forms_gpu.py.
+STREAMK_CLAIMS = {
+    (2, 16, 28, 28, 128, 128, 3, 1, 1): (True, True),
+    (2, 16, 56, 56, 64, 64, 3, 1, 1): (False, False),
+    (2, 16, 56, 56, 64, 128, 3, 2, 1): (False, False),
+    (1, 30, 14, 14, 256, 256, 3, 1, 1): (True, True),
+}
 
 
 @pytest.mark.parametrize("case", CONV_CASES)
 def test_conv_fprop_dgrad_wgrad(case):
     from rot_mvgaze_amd import ops
-    from rot_mvgaze_amd._lib import ConvDesc
+    from rot_mvgaze_amd._lib import ConvDesc, PLAN_DGRAD, PLAN_FPROP_STATS, lib
     G, N, H, W, Cin, Cout, k, st, pad = case
     x = rnd((G, N, Cin, H, W), 1, "x")
     if Cin == 4:
         x[:, :, 3] = 0
     w = rnd((Cout, Cin, k, k), 2, "w", 1.0 / np.sqrt(Cin * k * k))
     d = ConvDesc.make(G, N, H, W, Cin, Cout, k, st, pad)
+    if case in STREAMK_CLAIMS:
+        assert lib().mvg_device_cus() == 256, "STREAMK_CLAIMS is written for 256 CUs"
+        plans = ops.conv_plan_query(d, PLAN_FPROP_STATS), ops.conv_plan_query(d, PLAN_DGRAD)
+        assert tuple(p["streamk_grid"] > 0 for p in plans) == STREAMK_CLAIMS[case], plans
+        assert all(p["scratch_floats"] * 4 <= lib().mvg_scratch_bytes() for p in plans)
     xr = x.reshape(G * N, Cin, H, W).double().requires_grad_(True)
     wr = w.double().requires_grad_(True)
     yr = F.conv2d(xr, wr, None, st, pad)

@@ -1,5 +1,5 @@
 """Host side of the inference range guard (no GPU): the new entry points are declared in include/rotmvgaze.h, exported and
-bound in _lib.SIGNATURES with the header's arity while the ABI version stays 11; arch.range_unit_names is the session's list;
+bound in _lib.SIGNATURES with the header's arity while the ABI version is 12; arch.range_unit_names is the session's list;
 a session off the split kernels has no range units; setting a record moves nothing in the plan; and the plan's word indices,
 checked by a stand-alone program built with the plan builder alone under AddressSanitizer + UBSan (a plain executable:
 nothing is loaded into Python and nothing is preloaded)."""
@@ -58,8 +58,8 @@ class _Session:
 def test_range_entry_points_declared_exported_and_bound(L):
     from rot_mvgaze_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+11\b", hdr)
-    assert L.mvg_abi_version() == _lib.ABI_VERSION == 11
+    assert re.search(r"#define\s+MVG_ABI_VERSION\s+12\b", hdr)
+    assert L.mvg_abi_version() == _lib.ABI_VERSION == 12
     code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in NEW + tuple(UNCHANGED):
         m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", code, flags=re.S)
