@@ -327,6 +327,28 @@ int mvg_preprocess_u8hwc_resize(const uint8_t *src, float *dst, int n, int h, in
  * host (rot_mvgaze_amd/augment.py replays the reference's RNG calls). */
 int mvg_multi_erase_nchw(float *img, const float *masks, const int32_t *grid, int gmax, int n, int c,
                          int h, int w, void *stream);
+/* The random part of the reference's training transform (main.py:41-49) on raw uint8 patches, one launch per batch:
+ * ColorJitter(brightness, contrast, saturation) and RandomAffine(degrees=0, scale, translate), bit for bit what
+ * torchvision computes on the PIL image - Pillow's ImageEnhance.{Brightness, Contrast, Color} (ImagingBlend against
+ * a degenerate image; every op quantises to uint8) in a per-image order, then Image.transform(AFFINE, NEAREST) on its
+ * scale-only path (per-axis source-index tables built by repeated double additions; outside = 0).
+ * One record per image, in a DEVICE array (the draws stay on the host: rot_mvgaze_amd/augment.py TrainAugment). */
+typedef struct mvg_augment_rec {
+  float factor[3];   /* brightness, contrast, saturation factor (1 = identity) */
+  int32_t order[3];  /* the ops in the order applied: a permutation of 0 brightness, 1 contrast, 2 saturation */
+  double a0, cx;     /* inverse affine map, x axis: src_x = a0 * (x + 0.5) + cx (torchvision's matrix[0], matrix[2]) */
+  double a4, cy;     /* ... y axis (matrix[4], matrix[5]); the off-diagonal terms are zero */
+} mvg_augment_rec;
+/* src [n][h][w][3] uint8 (swap_rb: stored BGR, swapped first: grey is computed on RGB).  Destinations, at least one:
+ * dst_u8 [n][h][w][3], the augmented RGB image, and / or dst_nhwc4 [n][h][w][4] fp32, that image through ToTensor and
+ * Normalize exactly as mvg_preprocess_u8hwc computes them (channel 3 zero), then - masks / grid non-null - times the
+ * RandomMultiErasing keep-mask by mvg_multi_erase_nchw's index rule (masks [n][gmax*gmax], grid [n]; the uint8
+ * destination is the image before ToTensor and is not erased).  recs_host (optional): the same n records in host
+ * memory, checked before the launch (the order must be a permutation).  h, w <= 8192 and h*w <= 16843009. */
+int mvg_augment_u8hwc(const uint8_t *src, const mvg_augment_rec *recs, const mvg_augment_rec *recs_host,
+                      uint8_t *dst_u8, float *dst_nhwc4, const float *masks, const int32_t *grid, int gmax, int n,
+                      int h, int w, float mean0, float mean1, float mean2, float std0, float std1, float std2,
+                      int swap_rb, void *stream);
 
 /* ---------------------------------------------------------------- geometry
  * rotation_matrix_2d utils/math.py:188-219; relative rotations rot_mv.py:193-194. */

@@ -1,5 +1,7 @@
-"""RandomMultiErasing on a device batch (the last step of the reference's
-training transform, /root/reference/main.py:48, /root/reference/utils/augment.py:10-47).
+"""The random part of the reference's training transform on device batches (SURVEY.md §8(f) rank 3,
+main.py:41-49): RandomMultiErasing, its last step (main.py:48, utils/augment.py:10-47),
+and TrainAugment - ColorJitter and RandomAffine on the raw uint8 patches, with ToTensor, Normalize and the erase in
+the same launch.
 
 The random draws stay on the host and replay the reference's calls in its order - per image:
 ``random.random()`` (apply?), ``np.random.uniform(*dot_size)``, ``np.random.uniform(*proportion)``,
@@ -9,12 +11,13 @@ same cells.  The multiply runs in one HIP launch over the whole batch (mvg_multi
 from __future__ import annotations
 
 import random
-from typing import List, Sequence, Tuple
+from typing import List, NamedTuple, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
 
 from . import ops
+from .backbone import IMAGE_MEAN, IMAGE_STD
 
 Tensor = torch.Tensor
 
@@ -62,3 +65,139 @@ class RandomMultiErasing:
         x = img.unsqueeze(0) if one else img
         self.apply(x, self.draw(x.shape[0]))
         return img
+
+
+# mvg_augment_rec (include/rotmvgaze.h): one record per image, 56 bytes
+REC_DTYPE = np.dtype([("factor", np.float32, 3), ("order", np.int32, 3), ("a0", np.float64), ("cx", np.float64),
+                      ("a4", np.float64), ("cy", np.float64)], align=True)
+assert REC_DTYPE.itemsize == 56
+BRIGHTNESS, CONTRAST, SATURATION = 0, 1, 2          # op ids of a record's order
+
+
+class AugmentDraws(NamedTuple):
+    recs: np.ndarray                                   # [n] REC_DTYPE
+    erase: Optional[List[Tuple[int, Tensor]]]          # RandomMultiErasing.draw's list, or None
+
+
+def inverse_affine(h: int, w: int, scale: float, tx: float, ty: float) -> Tuple[float, float, float, float]:
+    """torchvision's _get_inverse_affine_matrix for angle 0 and no shear about the centre (w/2, h/2), in Python doubles
+    and in its order of operations: (a0, c_x, a4, c_y); the off-diagonal terms are exactly zero."""
+    cx, cy = w * 0.5, h * 0.5
+    a0 = a4 = 1.0 / scale
+    return a0, a0 * (-cx - tx) + cx, a4, a4 * (-cy - ty) + cy
+
+
+def _jitter_range(name: str, value: float) -> Optional[Tuple[float, float]]:
+    """ColorJitter._check_input for a scalar: [max(0, 1 - v), 1 + v], None (no draw, op left out) when that is [1, 1]."""
+    if value < 0:
+        raise ValueError(f"If {name} is a single number, it must be non negative.")
+    lo, hi = max(0.0, 1.0 - float(value)), 1.0 + float(value)
+    return None if lo == hi == 1.0 else (lo, hi)
+
+
+class TrainAugment:
+    """ColorJitter(brightness, contrast, saturation) -> RandomAffine(degrees=0, scale, translate) -> ToTensor ->
+    Normalize -> RandomMultiErasing of main.py:41-49 on a device batch of raw uint8 [n, h, w, 3] patches, one HIP launch
+    (mvg_augment_u8hwc).  The pixel arithmetic is Pillow's, bit for bit (what torchvision runs on the PIL image; pinned by
+    tests/golden/color_affine.npz).  Patches keep their size: the reference's Resize(224) is the identity on the
+    datasets' 224 x 224 patches, and a resize after the augmentation is not served.
+
+    hue, rotation and shear take other Pillow code paths and raise NotImplementedError here."""
+
+    def __init__(self, brightness: float = 1.0, contrast: float = 0.1, saturation: float = 0.1,
+                 scale: Optional[Sequence[float]] = (0.99, 1.01), translate: Optional[Sequence[float]] = (0.01, 0.01),
+                 erase: Optional[RandomMultiErasing] = None, hue: float = 0.0, degrees: float = 0.0, shear=None):
+        if hue is not None and any(float(v) != 0.0 for v in np.atleast_1d(hue)):
+            raise NotImplementedError("TrainAugment: hue jitter (an HSV round trip in Pillow) is not implemented")
+        if any(float(v) != 0.0 for v in np.atleast_1d(degrees)):
+            raise NotImplementedError("TrainAugment: rotation (Pillow's general affine path) is not implemented: degrees must be 0")
+        if shear is not None and any(float(v) != 0.0 for v in np.atleast_1d(shear)):
+            raise NotImplementedError("TrainAugment: shear (Pillow's general affine path) is not implemented")
+        self.ranges = [_jitter_range("brightness", brightness), _jitter_range("contrast", contrast),
+                       _jitter_range("saturation", saturation)]
+        if scale is not None and not (len(scale) == 2 and 0 < scale[0] <= scale[1]):
+            raise ValueError("scale must be (low, high) with 0 < low <= high")
+        if translate is not None and not (len(translate) == 2 and all(0.0 <= t <= 1.0 for t in translate)):
+            raise ValueError("translation values should be between 0 and 1")
+        self.scale, self.translate, self.erase = scale, translate, erase
+
+    def draw(self, n: int, h: int, w: int) -> AugmentDraws:
+        """The host draws for n images of h x w, image by image, in the order torchvision's transforms make them - restated
+        from torchvision's source as documented (ColorJitter.get_params / forward, RandomAffine.get_params), NOT pinned by a
+        fixture: torchvision is not a dependency of the tests; only the pixel arithmetic is pinned.  Per image:
+        ``torch.randperm(4)`` (index 3 is hue: skipped), ``torch.empty(1).uniform_`` for the brightness, contrast and
+        saturation factors (an op whose range is [1, 1] draws nothing and is the identity), the affine angle (drawn from
+        [0, 0], consumed), ``tx = int(round(uniform(-translate[0]*w, translate[0]*w)))``, ``ty`` likewise with h, the
+        scale, then RandomMultiErasing.draw's calls for that image."""
+        recs = np.zeros(n, dtype=REC_DTYPE)
+        erase: Optional[List[Tuple[int, Tensor]]] = [] if self.erase is not None else None
+        for i in range(n):
+            perm = torch.randperm(4).tolist()
+            recs["order"][i] = [op for op in perm if op != 3]
+            for op, rng in enumerate(self.ranges):
+                recs["factor"][i, op] = 1.0 if rng is None else float(torch.empty(1).uniform_(rng[0], rng[1]))
+            float(torch.empty(1).uniform_(0.0, 0.0).item())                 # the angle
+            tx = ty = 0
+            if self.translate is not None:
+                max_dx, max_dy = float(self.translate[0] * w), float(self.translate[1] * h)
+                tx = int(round(torch.empty(1).uniform_(-max_dx, max_dx).item()))
+                ty = int(round(torch.empty(1).uniform_(-max_dy, max_dy).item()))
+            scale = 1.0
+            if self.scale is not None:
+                scale = float(torch.empty(1).uniform_(self.scale[0], self.scale[1]).item())
+            recs["a0"][i], recs["cx"][i], recs["a4"][i], recs["cy"][i] = inverse_affine(h, w, scale, tx, ty)
+            if erase is not None:
+                erase += self.erase.draw(1)
+        return AugmentDraws(recs, erase)
+
+    def launch(self, u8: Tensor, draws: AugmentDraws, dst_u8: Optional[Tensor], dst_nhwc4: Optional[Tensor], bgr: bool = False) -> None:
+        """One launch into caller-owned destinations (uint8 [n, h, w, 3] and / or fp32 [n, h, w, 4]); one host-to-device copy
+        carries the records (and, with erase draws, one each the masks and grid sizes)."""
+        if not u8.is_cuda:
+            raise RuntimeError("TrainAugment (MI355X build) works on device batches: no CPU fallback")
+        if u8.dim() != 4 or u8.shape[3] != 3 or u8.dtype != torch.uint8:
+            raise ValueError(f"TrainAugment: expected uint8 [n, h, w, 3] patches (got {u8.dtype} {tuple(u8.shape)})")
+        n, h, w, _ = u8.shape
+        recs = np.ascontiguousarray(draws.recs, dtype=REC_DTYPE)
+        if recs.shape != (n,):
+            raise ValueError(f"TrainAugment: {recs.shape[0] if recs.ndim else 0} records for {n} images")
+        masks = grid = None
+        gmax = 0
+        if draws.erase is not None and any(g for g, _ in draws.erase):
+            if dst_nhwc4 is None:
+                raise ValueError("TrainAugment: the erase multiplies the normalised image: out='u8' needs erase=None")
+            assert len(draws.erase) == n
+            gmax = max(g for g, _ in draws.erase)
+            mh, gh = torch.zeros(n, gmax * gmax, dtype=torch.float32), torch.zeros(n, dtype=torch.int32)
+            for i, (g, m) in enumerate(draws.erase):
+                gh[i] = g
+                if g:
+                    mh[i, : g * g] = m.reshape(-1)
+            masks, grid = mh.to(u8.device), gh.to(u8.device)
+        dev_recs = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(u8.device)
+        ops.augment_u8hwc(u8.contiguous(), dev_recs, dst_u8, dst_nhwc4, masks, grid, gmax, n, h, w, IMAGE_MEAN, IMAGE_STD, bgr,
+                          recs_host=recs)
+
+    def apply(self, u8: Tensor, draws: AugmentDraws, out: str = "nhwc4", bgr: bool = False) -> Tensor:
+        """u8 [n, h, w, 3] uint8 on the GPU (bgr: stored BGR) -> ``"nhwc4"``: fp32 [n, h, w, 4], the backbone's input layout
+        (channel 3 zero); ``"nchw"``: fp32 [n, 3, h, w], the reference transform's output format (for callers outside the
+        model, and for bf16 training); ``"u8"``: uint8 [n, h, w, 3] RGB, the image before ToTensor (no erase)."""
+        if out not in ("nhwc4", "u8", "nchw"):
+            raise ValueError(f"out must be 'nhwc4', 'u8' or 'nchw' (got {out!r})")
+        if not u8.is_cuda:
+            raise RuntimeError("TrainAugment (MI355X build) works on device batches: no CPU fallback")
+        n, h, w = u8.shape[:3]
+        if out == "u8":
+            dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=u8.device)
+            self.launch(u8, draws, dst, None, bgr)
+            return dst
+        x = torch.empty(n, h, w, 4, dtype=torch.float32, device=u8.device)
+        self.launch(u8, draws, None, x, bgr)
+        if out == "nhwc4":
+            return x
+        y = torch.empty(n, 3, h, w, dtype=torch.float32, device=u8.device)
+        ops.nhwc4_to_nchw(x, y, n, 3, h, w)
+        return y
+
+    def __call__(self, u8: Tensor, out: str = "nhwc4", bgr: bool = False) -> Tensor:
+        return self.apply(u8, self.draw(u8.shape[0], u8.shape[1], u8.shape[2]), out, bgr)

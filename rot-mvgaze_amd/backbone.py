@@ -567,10 +567,12 @@ class Backbone:
             ops.bn_relu_maxpool_fwd(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
         return out, (argmax, scale, shift, d.ho, d.wo, hp, wp_)
 
-    def _input_layout(self, imgs: List[Tensor], B: int, H: int, W: int, input_bgr: bool) -> Tensor:
+    def _input_layout(self, imgs: List[Tensor], B: int, H: int, W: int, input_bgr: bool, augment=None) -> Tensor:
         """x0, the stem's input operand, one launch per view: row windows straight from the NCHW input when the stem runs in
         row-window form (no NHWC image is built); else the NHWC image padded to 4 (bf16: 8) channels, from raw uint8 patches
-        or NCHW fp32 - and the windows from that image for raw input with a row-window stem.
+        or NCHW fp32 - and the windows from that image for raw input with a row-window stem.  augment (training steps on raw
+        patches: an augment.TrainAugment): its launch - ColorJitter, RandomAffine, ToTensor, Normalize, erase - takes the
+        place of the preprocess launch; the draws are host work, taken in view order, then image order.
         (The bf16 branch without a row-window stem is restated by csrc/session_plan.cpp's build_bf16.)"""
         V, dev, bf = len(imgs), imgs[0].device, self.bf16
         raw = imgs[0].dtype == torch.uint8
@@ -584,6 +586,15 @@ class Backbone:
             x0 = torch.empty(V, B, H, W, 8 if bf else 4, dtype=self.act_dtype, device=dev)
         for v, im in enumerate(imgs):
             assert im.shape == imgs[0].shape and im.is_cuda and im.dtype == imgs[0].dtype
+            if raw and augment is not None:
+                if tuple(im.shape[1:3]) != (H, W):
+                    raise ValueError(f"input_augment: {im.shape[1]} x {im.shape[2]} patches with input_size {H} x {W}: a resize "
+                                     "after the augmentation is not served (set model.input_size = None, or feed patches of that size)")
+                if torch.cuda.is_current_stream_capturing():
+                    raise RuntimeError("input_augment draws on the host for every step and cannot be captured (graph.GraphedStep): "
+                                       "augment outside the captured step (TrainAugment.apply) and feed the result")
+                augment.launch(im, augment.draw(B, H, W), None, x0[v], input_bgr)
+                continue
             if raw:                             # (bf16: inference only - no fp32 image in between)
                 prep = ops.preprocess_u8hwc_resize_bf16 if bf else ops.preprocess_u8hwc_resize
                 prep(im.contiguous(), x0[v], B, im.shape[1], im.shape[2], H, W, IMAGE_MEAN, IMAGE_STD, input_bgr)
@@ -598,11 +609,12 @@ class Backbone:
         return x0
 
     def forward(self, imgs: List[Tensor], training: bool, keep_tape: bool, input_bgr: bool = False,
-                input_size: Optional[int] = None, need_dimg: bool = False):
+                input_size: Optional[int] = None, need_dimg: bool = False, input_augment=None):
         """imgs: V tensors [B,3,H,W] fp32 NCHW (the reference's input format, rot_mv.py:188-189), or
         V raw uint8 [B,H,W,3] face patches, put through test_transform of main.py:50-55 on the GPU
         (ToTensor, Resize((input_size, input_size), antialias=True) when the patch has another size,
-        Normalize).  Returns (img_feat [V,B,fc_dim], tape or None)."""
+        Normalize) - in a training step with input_augment (augment.TrainAugment) through the random
+        part of train_transform (main.py:41-49) as well.  Returns (img_feat [V,B,fc_dim], tape or None)."""
         V = len(imgs)
         raw = imgs[0].dtype == torch.uint8
         if raw:
@@ -637,7 +649,7 @@ class Backbone:
         else:
             self._stem_rw = (self._split_now and self.stem_rowwindow and training and not need_dimg and W % 2 == 0
                              and self.batch_weight_prep and 32 * B * H * (W // 2) * 4 < 0x7FFFFFF0)
-        x0 = self._input_layout(imgs, B, H, W, input_bgr)
+        x0 = self._input_layout(imgs, B, H, W, input_bgr, input_augment if (raw and training) else None)
         self._wprep = None
         if training:
             self.invalidate_weight_cache()       # the weights are about to change: drop the inference copies

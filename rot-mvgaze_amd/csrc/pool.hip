@@ -161,13 +161,18 @@ __global__ __launch_bounds__(256) void nhwc4_to_nchw_kernel(const float4 *__rest
 // pipeline (dataset/gaze.py:106-111 BGR->RGB; main.py:50-55 ToTensor = /255, Normalize(mean, std)).
 // The per-pixel arithmetic is ONE device function for the fp32 (NHWC4) and the bf16 (NHWC8) kernels: the same
 // source, the same contractions, so the bf16 output is the fp32 output rounded once.
+// (ToTensor and Normalize of one RGB pixel held as floats 0..255: also the tail of augment_u8_kernel)
+__device__ __forceinline__ void preprocess_u8_norm(float m0, float m1, float m2, float s0, float s1, float s2, float &c0, float &c1,
+                                                   float &c2) {
+  c0 = (c0 / 255.0f - m0) / s0;
+  c1 = (c1 / 255.0f - m1) / s1;
+  c2 = (c2 / 255.0f - m2) / s2;
+}
 __device__ __forceinline__ void preprocess_u8_px(const unsigned char *__restrict__ src, long long i, float m0, float m1, float m2,
                                                  float s0, float s1, float s2, int swap_rb, float &c0, float &c1, float &c2) {
   const unsigned char *p = src + 3 * i;
   c0 = (float)p[swap_rb ? 2 : 0], c1 = (float)p[1], c2 = (float)p[swap_rb ? 0 : 2];
-  c0 = (c0 / 255.0f - m0) / s0;
-  c1 = (c1 / 255.0f - m1) / s1;
-  c2 = (c2 / 255.0f - m2) / s2;
+  preprocess_u8_norm(m0, m1, m2, s0, s1, s2, c0, c1, c2);
 }
 __global__ __launch_bounds__(256) void preprocess_u8_kernel(const unsigned char *__restrict__ src,
                                                             float4 *__restrict__ dst, long long pixels, float m0,
@@ -302,6 +307,157 @@ __global__ __launch_bounds__(256) void multi_erase_kernel(float *__restrict__ im
     mx = mx < g - 1 ? mx : g - 1;
     const float keep = m[my * g + mx];
     for (int ch = 0; ch < c; ++ch) img[((long long)n * c + ch) * hw + i] *= keep;
+  }
+}
+
+// ColorJitter(brightness, contrast, saturation) and RandomAffine(degrees=0, scale, translate) of the reference's training
+// transform (main.py:41-49) on raw uint8 patches, bit for bit what torchvision computes on the PIL image (Pillow's
+// ImageEnhance.{Brightness, Contrast, Color} = ImagingBlend against a degenerate image, Image.transform(AFFINE, NEAREST)
+// = ImagingScaleAffine), optionally followed by ToTensor + Normalize (preprocess_u8_norm) and the RandomMultiErasing
+// multiply.  Every enhance op quantises to uint8; brightness and saturation are pointwise, contrast blends against ONE
+// value per image, m = int(mean of grey + 0.5) of the image as it stands when contrast runs - so, given m, the three ops
+// commute with the nearest-neighbour gather that follows them, and the only whole-image quantity is the grey sum S.
+// One workgroup per image: phase A sums the grey of every source pixel after the ops that precede contrast (integers:
+// wave shuffle, then LDS) while one lane per axis builds Pillow's source-index table by the same sequential double
+// additions; phase B gathers each output pixel through the tables, applies the three ops and stores.  The second read of
+// the image comes from L2.
+constexpr int kAugThreads = 1024;
+constexpr int kAugBatch = 4;                     // pixels per thread and pass
+constexpr int kAugMaxSide = 8192;                // two int16 tables in LDS
+constexpr long long kAugMaxPixels = 0xFFFFFFFFll / 255;      // S = sum of grey <= 255 h w stays in 32 bits
+
+// Pillow's ImagingBlend: deg + f * (pix - deg), every step rounded to float32; 0 <= f <= 1 interpolates (truncation),
+// any other f extrapolates and clamps.  The product must be a rounded value of its own - device code is compiled with
+// contraction on and __fmul_rn / __fadd_rn are plain operators to it (see aa_window): the empty asm makes it opaque.
+__device__ __forceinline__ int aug_blend(float deg, float pix, float f) {
+  float prod = __fmul_rn(f, __fsub_rn(pix, deg));
+  asm volatile("" : "+v"(prod));
+  const float t = __fadd_rn(deg, prod);
+  if (f >= 0.f && f <= 1.f) return (int)t;
+  return t <= 0.f ? 0 : (t >= 255.f ? 255 : (int)t);
+}
+__device__ __forceinline__ int aug_grey(int r, int g, int b) { return (r * 19595 + g * 38470 + b * 7471 + 0x8000) >> 16; }
+// op: 0 brightness (degenerate 0), 1 contrast (degenerate m), 2 saturation (degenerate = the pixel's grey); others: nothing
+__device__ __forceinline__ void aug_op(int op, float f0, float f1, float f2, int m, int &r, int &g, int &b) {
+  if ((unsigned)op > 2u) return;
+  const float f = op == 0 ? f0 : (op == 1 ? f1 : f2);
+  const float deg = op == 0 ? 0.f : (op == 1 ? (float)m : (float)aug_grey(r, g, b));
+  r = aug_blend(deg, (float)r, f);
+  g = aug_blend(deg, (float)g, f);
+  b = aug_blend(deg, (float)b, f);
+}
+
+__global__ __launch_bounds__(kAugThreads) void augment_u8_kernel(const unsigned char *__restrict__ src,
+                                                                 const mvg_augment_rec *__restrict__ recs,
+                                                                 unsigned char *__restrict__ dst_u8, float4 *__restrict__ dst_f,
+                                                                 const float *__restrict__ masks, const int *__restrict__ grid,
+                                                                 int gmax, int h, int w, float m0, float m1, float m2, float s0,
+                                                                 float s1, float s2, int swap_rb) {
+  __shared__ short xtab[kAugMaxSide], ytab[kAugMaxSide];
+  __shared__ unsigned wave_part[kAugThreads / 64];
+  __shared__ int mean_s;
+  const int img = blockIdx.x, tid = threadIdx.x;
+  const mvg_augment_rec &rec = recs[img];
+  const int o0 = rec.order[0], o1 = rec.order[1], o2 = rec.order[2];
+  const float f0 = rec.factor[0], f1 = rec.factor[1], f2 = rec.factor[2];
+  const int hw = h * w;
+  const unsigned char *in = src + (long long)img * hw * 3;
+  const int ir = swap_rb ? 2 : 0, ib = swap_rb ? 0 : 2;
+
+  // ---- phase A: the index tables (lane 0 of waves 0 and 1) and S
+  if (tid == 0 || tid == 64) {
+    const bool xs = tid == 0;
+    const int size = xs ? w : h;
+    const double a = xs ? rec.a0 : rec.a4;
+    short *tab = xs ? xtab : ytab;
+    double o = (xs ? rec.cx : rec.cy) + a * 0.5;         // (a * 0.5 is exact: fused or not, one rounding)
+    for (int i = 0; i < size; ++i) {
+      int s = o < 0.0 ? -1 : (int)o;                      // NaN and out-of-range doubles convert to a saturated int: fill
+      if (s >= size) s = -1;
+      tab[i] = (short)s;
+      o += a;
+    }
+  }
+  // (both walks take kAugBatch pixels per pass, loads first: a workgroup is alone with its image's latency)
+  unsigned part = 0;
+  for (int p0 = tid; p0 < hw; p0 += kAugThreads * kAugBatch) {
+    int r[kAugBatch], g[kAugBatch], b[kAugBatch];
+#pragma unroll
+    for (int u = 0; u < kAugBatch; ++u) {
+      const int p = p0 + u * kAugThreads;
+      const unsigned char *q = in + 3 * (p < hw ? p : hw - 1);          // past the end: the last pixel, not counted
+      r[u] = q[ir], g[u] = q[1], b[u] = q[ib];
+    }
+#pragma unroll
+    for (int u = 0; u < kAugBatch; ++u) {
+      if (p0 + u * kAugThreads >= hw) break;
+      if (o0 != 1) {                                      // the ops that precede contrast
+        aug_op(o0, f0, f1, f2, 0, r[u], g[u], b[u]);
+        if (o1 != 1) {
+          aug_op(o1, f0, f1, f2, 0, r[u], g[u], b[u]);
+          if (o2 != 1) aug_op(o2, f0, f1, f2, 0, r[u], g[u], b[u]);
+        }
+      }
+      part += (unsigned)aug_grey(r[u], g[u], b[u]);
+    }
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+  if ((tid & 63) == 0) wave_part[tid >> 6] = part;
+  __syncthreads();
+  if (tid == 0) {
+    unsigned s = 0;
+    for (int k = 0; k < kAugThreads / 64; ++k) s += wave_part[k];
+    mean_s = (int)((double)s / (double)hw + 0.5);
+  }
+  __syncthreads();
+  const int m = mean_s;
+
+  // ---- phase B: gather, the three ops, store
+  const int gcells = grid ? (grid[img] < gmax ? grid[img] : gmax) : 0;      // (never past the image's gmax x gmax slot)
+  const float *mk = masks + (long long)img * gmax * gmax;
+  const float sy = (float)gcells / (float)h, sx = (float)gcells / (float)w;
+  for (int p0 = tid; p0 < hw; p0 += kAugThreads * kAugBatch) {
+    int r[kAugBatch], g[kAugBatch], b[kAugBatch], y[kAugBatch], x[kAugBatch];
+    bool inside[kAugBatch];
+#pragma unroll
+    for (int u = 0; u < kAugBatch; ++u) {
+      const int p = p0 + u * kAugThreads, pc = p < hw ? p : hw - 1;
+      y[u] = pc / w, x[u] = pc - y[u] * w;
+      const int ys = ytab[y[u]], xsrc = xtab[x[u]];
+      inside[u] = ys >= 0 && xsrc >= 0;
+      const unsigned char *q = in + (inside[u] ? (ys * w + xsrc) * 3 : 0);      // fill: pixel 0 is read and dropped
+      r[u] = q[ir], g[u] = q[1], b[u] = q[ib];
+    }
+#pragma unroll
+    for (int u = 0; u < kAugBatch; ++u) {
+      const int p = p0 + u * kAugThreads;
+      if (p >= hw) break;
+      if (inside[u]) {
+        aug_op(o0, f0, f1, f2, m, r[u], g[u], b[u]);
+        aug_op(o1, f0, f1, f2, m, r[u], g[u], b[u]);
+        aug_op(o2, f0, f1, f2, m, r[u], g[u], b[u]);
+      } else {
+        r[u] = g[u] = b[u] = 0;                            // fill: zeros, AFTER the jitter
+      }
+      const long long o = (long long)img * hw + p;
+      if (dst_u8) {
+        unsigned char *d = dst_u8 + 3 * o;
+        d[0] = (unsigned char)r[u], d[1] = (unsigned char)g[u], d[2] = (unsigned char)b[u];
+      }
+      if (dst_f) {
+        float c0 = (float)r[u], c1 = (float)g[u], c2 = (float)b[u];
+        preprocess_u8_norm(m0, m1, m2, s0, s1, s2, c0, c1, c2);
+        if (gcells > 0) {                                  // multi_erase_kernel's index rule
+          int my = (int)floorf((float)y[u] * sy), mx = (int)floorf((float)x[u] * sx);
+          my = my < gcells - 1 ? my : gcells - 1;
+          mx = mx < gcells - 1 ? mx : gcells - 1;
+          const float keep = mk[my * gcells + mx];
+          c0 *= keep, c1 *= keep, c2 *= keep;
+        }
+        dst_f[o] = make_float4(c0, c1, c2, 0.f);
+      }
+    }
   }
 }
 
@@ -457,6 +613,32 @@ int mvg_multi_erase_nchw(float *img, const float *masks, const int32_t *grid, in
   if (bx > 64) bx = 64;
   hipLaunchKernelGGL(multi_erase_kernel, dim3((unsigned)bx, n), dim3(256), 0, st, img, masks, grid, gmax, c, h, w);
   return check_launch("multi_erase");
+}
+
+int mvg_augment_u8hwc(const uint8_t *src, const mvg_augment_rec *recs, const mvg_augment_rec *recs_host, uint8_t *dst_u8,
+                      float *dst_nhwc4, const float *masks, const int32_t *grid, int gmax, int n, int h, int w, float mean0,
+                      float mean1, float mean2, float std0, float std1, float std2, int swap_rb, void *stream) {
+  MVG_REQUIRE(src && recs, "augment: src and the device records are required");
+  MVG_REQUIRE(dst_u8 || dst_nhwc4, "augment: no destination (dst_u8 and dst_nhwc4 are both null)");
+  MVG_REQUIRE(n > 0 && h > 0 && w > 0, "augment: bad sizes");
+  MVG_REQUIRE(h <= kAugMaxSide && w <= kAugMaxSide, "augment: a side of %d x %d is longer than the index tables hold (%d)", h, w,
+              kAugMaxSide);
+  MVG_REQUIRE((long long)h * w <= kAugMaxPixels, "augment: %d x %d pixels overflow the 32-bit grey sum (at most %lld)", h, w,
+              kAugMaxPixels);
+  MVG_REQUIRE(std0 > 0.f && std1 > 0.f && std2 > 0.f, "augment: std must be positive");
+  MVG_REQUIRE((masks == nullptr) == (grid == nullptr), "augment: erase masks and grid come together");
+  MVG_REQUIRE(!masks || (dst_nhwc4 && gmax > 0), "augment: the erase multiplies the normalised image (dst_nhwc4) and needs gmax > 0");
+  if (recs_host)
+    for (int i = 0; i < n; ++i) {
+      const int32_t *o = recs_host[i].order;
+      MVG_REQUIRE(o[0] >= 0 && o[0] <= 2 && o[1] >= 0 && o[1] <= 2 && o[2] >= 0 && o[2] <= 2 && o[0] != o[1] && o[0] != o[2] && o[1] != o[2],
+                  "augment: record %d: order (%d, %d, %d) is not a permutation of 0, 1, 2", i, o[0], o[1], o[2]);
+    }
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_LAYOUT, st, 0.0, (double)n * h * w * (6.0 + (dst_u8 ? 3.0 : 0.0) + (dst_nhwc4 ? 16.0 : 0.0)));
+  hipLaunchKernelGGL(augment_u8_kernel, dim3(n), dim3(kAugThreads), 0, st, src, recs, dst_u8, (float4 *)dst_nhwc4, masks, grid, gmax,
+                     h, w, mean0, mean1, mean2, std0, std1, std2, swap_rb);
+  return check_launch("augment_u8hwc");
 }
 
 int mvg_nhwc4_to_nchw(const float *src, float *dst, int n, int c, int h, int w, void *stream) {

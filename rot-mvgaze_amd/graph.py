@@ -37,6 +37,9 @@ class GraphedStep:
         if optimizer is not None and not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedStep needs rot_mvgaze_amd.optim.Adam(capturable=True): the step counter and the "
                              "learning rate must live on the device")
+        if getattr(model, "input_augment", None) is not None:
+            raise RuntimeError("GraphedStep: model.input_augment draws on the host for every step and cannot be captured: augment "
+                               "outside the step (TrainAugment.apply into the static input) and set input_augment = None")
         self.model, self.optimizer = model, optimizer
         self._step_fn = step_fn
         dev = next(model.parameters()).device

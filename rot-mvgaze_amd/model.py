@@ -106,7 +106,8 @@ class _BackboneFn(torch.autograd.Function):
         # tape-less path (BatchNorm folded into the conv epilogues) even though the parameters require grad
         keep = model._grad_mode and any(ctx.needs_input_grad)
         ctx.need_dimg = any(ctx.needs_input_grad[3:3 + n_views])
-        feat, tape = model._backbone.forward(imgs, training, keep, model.input_bgr, model.input_size, need_dimg=ctx.need_dimg)
+        feat, tape = model._backbone.forward(imgs, training, keep, model.input_bgr, model.input_size, need_dimg=ctx.need_dimg,
+                                             input_augment=model.input_augment)
         ctx.model, ctx.tape, ctx.n_views = model, tape, n_views
         if model._debug_keep_tapes:
             model._last_backbone_tape = tape
@@ -212,6 +213,9 @@ class MultiViewGaze(nn.Module):
         self._grad_mode = True                    # the caller's grad mode at the last forward (see _BackboneFn.forward)
         self.input_bgr = False                    # raw uint8 inputs: swap B and R first (dataset color_type 'bgr')
         self.input_size: Optional[int] = 224      # raw uint8 inputs: Resize((S, S), antialias=True), main.py:40,53; None = keep
+        # raw uint8 inputs in train() mode: an augment.TrainAugment puts every view through ColorJitter / RandomAffine (/ erase)
+        # of main.py:41-49 on the GPU, in the launch that normalises it; eval() ignores it
+        self.input_augment = None
         self._sink = _ArenaSink(self)
         self._wgrad_low_priority = True           # data-parallel runs set False (dp.GradAllReducer._configure)
         # storage / matrix-core type of the backbone: torch.float32 (default: the path held to 1e-4 against the

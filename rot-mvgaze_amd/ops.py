@@ -727,6 +727,25 @@ def multi_erase_nchw(img, masks, grid, gmax, n, c, h, w):
     check(lib().mvg_multi_erase_nchw(_p(img), _p(masks), _p(grid), gmax, n, c, h, w, _s()), "multi_erase_nchw")
 
 
+def augment_u8hwc(src, recs, dst_u8, dst_nhwc4, masks, grid, gmax, n, h, w, mean, std, swap_rb, recs_host=None):
+    """ColorJitter + RandomAffine (+ ToTensor, Normalize, erase) of uint8 [n, h, w, 3] in one launch (mvg_augment_u8hwc).
+    recs: the n mvg_augment_rec records as a uint8 device tensor; recs_host: the same records as a C-contiguous numpy array
+    (augment.REC_DTYPE), which the library checks before it launches.  dst_u8 uint8 [n, h, w, 3] and / or dst_nhwc4 fp32
+    [n, h, w, 4]; masks fp32 [n, gmax*gmax] and grid int32 [n] (or both None)."""
+    assert src.dtype == torch.uint8 and src.is_contiguous() and src.numel() == n * h * w * 3
+    assert recs.dtype == torch.uint8 and recs.is_contiguous() and recs.numel() == n * 56
+    assert dst_u8 is None or (dst_u8.dtype == torch.uint8 and dst_u8.is_contiguous() and dst_u8.numel() == n * h * w * 3)
+    assert dst_nhwc4 is None or (dst_nhwc4.dtype == torch.float32 and dst_nhwc4.is_contiguous() and dst_nhwc4.numel() == n * h * w * 4)
+    assert masks is None or (masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() == n * gmax * gmax)
+    assert grid is None or (grid.dtype == torch.int32 and grid.is_contiguous() and grid.numel() == n)
+    host = None
+    if recs_host is not None:
+        assert recs_host.flags["C_CONTIGUOUS"] and recs_host.nbytes == n * 56
+        host = C.c_void_p(recs_host.ctypes.data)
+    check(lib().mvg_augment_u8hwc(_p(src), _p(recs), host, _p(dst_u8), _p(dst_nhwc4), _p(masks), _p(grid), gmax, n, h, w,
+                                  mean[0], mean[1], mean[2], std[0], std[1], std[2], int(swap_rb), _s()), "augment_u8hwc")
+
+
 def preprocess_u8hwc_resize(src, dst, n, h, w, oh, ow, mean, std, swap_rb):
     check(lib().mvg_preprocess_u8hwc_resize(_p(src), _p(dst), n, h, w, oh, ow, mean[0], mean[1], mean[2], std[0], std[1],
                                             std[2], int(swap_rb), _s()), "preprocess_u8hwc_resize")

@@ -1,0 +1,233 @@
+"""mvg_augment_u8hwc - ColorJitter and RandomAffine of the reference's training transform (main.py:41-49) on raw uint8
+patches - against what Pillow computed (tests/golden/color_affine.npz, written by make_golden_augment.py), against the
+NumPy restatement at the training size, and through the model's raw-input path.  Every comparison is exact."""
+import os
+import random
+
+import numpy as np
+import pytest
+import torch
+
+import augment_ref as R
+import rot_mvgaze_amd  # noqa: F401
+from rot_mvgaze_amd import ops, synth
+from rot_mvgaze_amd.augment import REC_DTYPE, AugmentDraws, RandomMultiErasing, TrainAugment
+from rot_mvgaze_amd.backbone import IMAGE_MEAN, IMAGE_STD
+
+pytestmark = pytest.mark.gpu
+
+
+def dev():
+    return torch.device("cuda:0")
+
+
+@pytest.fixture(scope="module")
+def cases(golden_dir):
+    g = np.load(os.path.join(golden_dir, "color_affine.npz"))
+    n = len(g["swap"])
+    return [(g[f"in_{k:02d}"], g["factors"][k], g["order"][k], g["matrix"][k], int(g["swap"][k]), g[f"out_{k:02d}"]) for k in range(n)]
+
+
+def records(factors, orders, matrices):
+    recs = np.zeros(len(factors), dtype=REC_DTYPE)
+    recs["factor"], recs["order"] = np.asarray(factors, np.float32), np.asarray(orders, np.int32)
+    m = np.asarray(matrices, np.float64)
+    recs["a0"], recs["cx"], recs["a4"], recs["cy"] = m[:, 0], m[:, 1], m[:, 2], m[:, 3]
+    return recs
+
+
+def preprocess(u8_rgb):
+    """ops.preprocess_u8hwc of an RGB uint8 device batch: the un-augmented raw path."""
+    n, h, w, _ = u8_rgb.shape
+    dst = torch.empty(n, h, w, 4, dtype=torch.float32, device=u8_rgb.device)
+    ops.preprocess_u8hwc(u8_rgb.contiguous(), dst, n, h, w, IMAGE_MEAN, IMAGE_STD, False)
+    return dst
+
+
+def test_uint8_output_equals_pillow_fixture(cases):
+    aug = TrainAugment()
+    for k, (img, factors, order, matrix, swap, want) in enumerate(cases):
+        draws = AugmentDraws(records([factors], [order], [matrix]), None)
+        got = aug.apply(torch.from_numpy(img[None]).to(dev()), draws, out="u8", bgr=bool(swap))
+        assert got.dtype == torch.uint8 and np.array_equal(got.cpu().numpy()[0], want), f"case {k}"
+    # ... and as batches (one workgroup per image, each with its own record): the cases that share a shape and a channel order
+    groups = {}
+    for c in cases:
+        groups.setdefault((c[0].shape, c[4]), []).append(c)
+    assert max(len(v) for v in groups.values()) >= 3
+    for (shape, swap), cs in groups.items():
+        draws = AugmentDraws(records([c[1] for c in cs], [c[2] for c in cs], [c[3] for c in cs]), None)
+        got = aug.apply(torch.from_numpy(np.stack([c[0] for c in cs])).to(dev()), draws, out="u8", bgr=bool(swap))
+        assert np.array_equal(got.cpu().numpy(), np.stack([c[5] for c in cs])), (shape, swap)
+
+
+def test_nhwc4_output_equals_preprocess_of_fixture_and_erase(cases):
+    aug = TrainAugment()
+    rng = np.random.RandomState(3)
+    erased = 0
+    for k, (img, factors, order, matrix, swap, want) in enumerate(cases):
+        h, w = img.shape[:2]
+        src = torch.from_numpy(img[None]).to(dev())
+        recs = records([factors], [order], [matrix])
+        ref = preprocess(torch.from_numpy(want[None]).to(dev()))
+        got = aug.apply(src, AugmentDraws(recs, None), out="nhwc4", bgr=bool(swap))
+        assert torch.equal(got, ref), f"case {k}"
+        assert (got[..., 3] == 0).all()
+        # both destinations from one launch
+        d8, d4 = torch.empty(1, h, w, 3, dtype=torch.uint8, device=dev()), torch.empty(1, h, w, 4, dtype=torch.float32, device=dev())
+        aug.launch(src, AugmentDraws(recs, None), d8, d4, bool(swap))
+        assert np.array_equal(d8.cpu().numpy()[0], want) and torch.equal(d4, ref), f"case {k}"
+        # erase: the keep-mask built by the existing erase kernel on NCHW ones, permuted
+        g = int(rng.randint(0, 8))                     # 0: this image is left alone
+        mask = (torch.from_numpy(rng.rand(g, g)) > 0.5).to(torch.float32)
+        keep = torch.ones(1, 3, h, w, device=dev())
+        RandomMultiErasing([0.5, 0.6], 0.5, [0.05, 0.3]).apply(keep, [(g, mask)])
+        got_e = aug.apply(src, AugmentDraws(recs, [(g, mask)]), out="nhwc4", bgr=bool(swap))
+        want_e = ref.clone()
+        want_e[..., :3] *= keep.permute(0, 2, 3, 1)
+        assert torch.equal(got_e, want_e), f"case {k} erase g={g}"
+        assert (got_e[..., 3] == 0).all()
+        erased += int(g > 0 and not torch.equal(got_e, ref))
+    assert erased >= 10
+
+
+@pytest.fixture(scope="module")
+def big():
+    """3 images of 224 x 224 (12.25 passes of the workgroup's 4 x 1024 pixels per image: the last one partial) and the restatement's result, computed once."""
+    rng = np.random.RandomState(21)
+    imgs = rng.randint(0, 256, (3, 224, 224, 3)).astype(np.uint8)
+    imgs[1] //= 4                                       # a dark image: brightness 2 does not saturate everything
+    factors = [(1.7, 0.93, 1.08), (2.0, 1.1, 0.9), (0.4, 1.05, 1.0)]
+    orders = [(2, 0, 1), (0, 1, 2), (1, 2, 0)]
+    mats = [R.affine_matrix(224, 224, 0.9931, 2, -1), R.affine_matrix(224, 224, 1.0087, -2, 2), R.affine_matrix(224, 224, 1.0, 0, 0)]
+    want = np.stack([R.augment(imgs[i], factors[i], orders[i], mats[i], True) for i in range(3)])
+    return imgs, records(factors, orders, mats), want
+
+
+def test_batch_at_224_equals_restatement(big):
+    imgs, recs, want = big
+    got = TrainAugment().apply(torch.from_numpy(imgs).to(dev()), AugmentDraws(recs, None), out="u8", bgr=True)
+    assert np.array_equal(got.cpu().numpy(), want)
+    assert not np.array_equal(want[2], imgs[2][..., ::-1])
+
+
+def test_nchw_output_is_the_nhwc4_result_permuted(big):
+    imgs, recs, want = big
+    aug, src = TrainAugment(), torch.from_numpy(imgs).to(dev())
+    a = aug.apply(src, AugmentDraws(recs, None), out="nhwc4", bgr=True)
+    b = aug.apply(src, AugmentDraws(recs, None), out="nchw", bgr=True)
+    assert b.shape == (3, 3, 224, 224) and b.is_contiguous()
+    assert torch.equal(b, a[..., :3].permute(0, 3, 1, 2))
+    assert torch.equal(a, preprocess(torch.from_numpy(want).to(dev())))
+    # __call__ = draw + apply: seeded alike, the same image
+    torch.manual_seed(5)
+    c = aug(src[:, :40, :56].contiguous(), out="u8")
+    torch.manual_seed(5)
+    d = aug.apply(src[:, :40, :56].contiguous(), aug.draw(3, 40, 56), out="u8")
+    assert torch.equal(c, d)
+
+
+def test_bad_arguments_raise():
+    n, h, w = 2, 8, 8
+    src = torch.zeros(n, h, w, 3, dtype=torch.uint8, device=dev())
+    recs = records([(1, 1, 1)] * n, [(0, 1, 2)] * n, [(1, 0, 1, 0)] * n)
+    rdev = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(dev())
+    d8 = torch.empty(n, h, w, 3, dtype=torch.uint8, device=dev())
+    d4 = torch.empty(n, h, w, 4, dtype=torch.float32, device=dev())
+
+    def call(**kw):
+        a = dict(src=src, recs=rdev, dst_u8=d8, dst_nhwc4=d4, masks=None, grid=None, gmax=0, n=n, h=h, w=w, mean=IMAGE_MEAN, std=IMAGE_STD,
+                 swap_rb=False, recs_host=recs)
+        a.update(kw)
+        ops.augment_u8hwc(**a)
+    call()
+    with pytest.raises(RuntimeError, match="no destination"):
+        call(dst_u8=None, dst_nhwc4=None)
+    bad = recs.copy()
+    bad["order"][1] = (0, 0, 2)
+    with pytest.raises(RuntimeError, match="record 1.*not a permutation"):
+        call(recs_host=bad)
+    bad["order"][1] = (0, 1, 3)
+    with pytest.raises(RuntimeError, match="not a permutation"):
+        call(recs_host=bad)
+    with pytest.raises(RuntimeError, match="std must be positive"):
+        call(std=(0.2, 0.0, 0.2))
+    grid = torch.zeros(n, dtype=torch.int32, device=dev())
+    masks = torch.zeros(n, 4, dtype=torch.float32, device=dev())
+    with pytest.raises(RuntimeError, match="come together"):
+        call(grid=grid)
+    with pytest.raises(RuntimeError, match="normalised image"):
+        call(masks=masks, grid=grid, gmax=2, dst_nhwc4=None)
+    # sizes are checked before anything is launched: the library sees the numbers, not the tensors
+    lib, p = rot_mvgaze_amd._lib.lib(), ops._p
+    for hh, ww, msg in ((8193, 8, "longer than the index tables"), (8, 8193, "longer than the index tables"), (8192, 4096, "grey sum"),
+                        (0, 8, "bad sizes")):
+        rc = lib.mvg_augment_u8hwc(p(src), p(rdev), None, p(d8), None, None, None, 0, n, hh, ww, *IMAGE_MEAN, *IMAGE_STD, 0, ops._s())
+        assert rc != 0 and msg in lib.mvg_last_error().decode(), (hh, ww)
+    aug = TrainAugment(erase=RandomMultiErasing([0.5, 0.6], 1.0, [0.2, 0.3]))
+    with pytest.raises(ValueError, match="erase"):
+        aug(src, out="u8")
+    with pytest.raises(ValueError, match="records"):
+        TrainAugment().apply(src, AugmentDraws(recs[:1], None))
+    torch.cuda.synchronize()
+
+
+def test_model_train_forward_with_input_augment():
+    """ResNet-18, V=2, B=2, 64 x 64 BGR patches, train mode: a forward with model.input_augment equals a forward of the same
+    weights on the kernel's uint8 output (same draws: reseeded, view order then image order) - outputs, loss, BatchNorm
+    running statistics, bit for bit; eval mode ignores the attribute."""
+    from rot_mvgaze_amd.geometry import rotation_matrix_2d
+    from rot_mvgaze_amd.losses import IterationLoss, StereoL1Loss
+    from rot_mvgaze_amd.model import FeatRotationSymm
+    B, hw = 2, 64
+    rng = np.random.RandomState(9)
+    u8 = [torch.from_numpy(rng.randint(0, 256, (B, hw, hw, 3)).astype(np.uint8)).to(dev()) for _ in range(2)]
+    inp = synth.make_inputs(B, 2, 1234, hw)
+    hp, gt = (torch.from_numpy(inp[k]).to(dev()) for k in ("head_pose", "gt_gaze"))
+    rest = {"rot_0": rotation_matrix_2d(hp[:, 0].contiguous()), "rot_1": rotation_matrix_2d(hp[:, 1].contiguous()),
+            "gt_gaze": gt[:, 0].contiguous(), "gt_gaze_1": gt[:, 1].contiguous()}
+    sd = {k: torch.from_numpy(np.array(v)) for k, v in synth.make_state_dict(18, 0, 3, perturb_bn=True).items()}
+    metrics = IterationLoss(StereoL1Loss(rel_weight=0.01, reference_decay=1.0), iter_decay=0.5)
+    aug = TrainAugment()
+
+    def model():
+        m = FeatRotationSymm(backbone_depth=18, num_iter=3)
+        m.load_state_dict(sd, strict=True)
+        m.input_size = None
+        return m.to(dev()).train()
+
+    def seed():
+        torch.manual_seed(77), random.seed(77), np.random.seed(77)
+
+    a = model()
+    a.input_augment, a.input_bgr = aug, True
+    seed()
+    da = a(dict(rest, img_0=u8[0], img_1=u8[1]))
+    la = metrics(da)
+    seed()
+    jit = [aug.apply(u, aug.draw(B, hw, hw), out="u8", bgr=True) for u in u8]
+    assert all(not torch.equal(j, u.flip(-1)) for j, u in zip(jit, u8))
+    b = model()
+    db = b(dict(rest, img_0=jit[0], img_1=jit[1]))
+    lb = metrics(db)
+    for k in ("pred_gaze", "img_feat_0", "img_feat_1", "_mvg_preds"):
+        assert torch.equal(da[k], db[k]), k
+    assert torch.equal(la, lb)
+    ba, bb = dict(a.named_buffers()), dict(b.named_buffers())
+    moved = 0
+    for k, v in ba.items():
+        assert torch.equal(v, bb[k]), k
+        moved += int("running_mean" in k and not torch.equal(v.cpu(), sd[k]))
+    assert moved >= 10
+    # a patch of another size than input_size: refused, not resized
+    a.input_size = 32
+    with pytest.raises(ValueError, match="resize"):
+        a(dict(rest, img_0=u8[0], img_1=u8[1]))
+    a.input_size = None
+    # eval mode: the attribute is ignored
+    a.eval(), b.eval()
+    b.input_bgr = True
+    with torch.no_grad():
+        ea = a(dict(rest, img_0=u8[0], img_1=u8[1]))
+        eb = b(dict(rest, img_0=u8[0], img_1=u8[1]))
+    assert torch.equal(ea["pred_gaze"], eb["pred_gaze"]) and torch.equal(ea["img_feat_1"], eb["img_feat_1"])
