@@ -37,7 +37,7 @@
 extern "C" {
 #endif
 
-#define MVG_ABI_VERSION 12
+#define MVG_ABI_VERSION 13
 
 /* ---------------------------------------------------------------- library */
 int mvg_abi_version(void);
@@ -268,6 +268,42 @@ int mvg_bn_eval_bwd(const float *g, const float *act, const uint8_t *relu_bits, 
                     float eps, int groups, int64_t rows_per_group, int c, float *dy, float *dz_out, float *dgamma,
                     float *dbeta, int accumulate, float *workspace, void *stream);
 size_t mvg_bn_eval_bwd_workspace_floats(int groups, int64_t rows_per_group, int c);
+
+/* Host-only plan query of the BatchNorm passes (ABI v13; tests guard with it which form a shape runs): answered by the
+ * functions the launches plan with, for the CUs the planners may use now (mvg_set_reserved_cus; 256 without a device);
+ * nothing is launched.  -1 (and a message) for sizes the launch would reject.  `pass` names the launch, `elem` the
+ * storage family (SP: mvg_bn_apply_split / mvg_bn_bwd_apply_split / the _split reduce entry points, which read fp32 and
+ * keep a third workspace row).  rows_per_group: rows of [rows][c] (ignored by the POOL passes, which take n_per_group, h,
+ * w of the conv output and pool 3x3 / 2 / 1); partials and scratch_floats (the floats registered for the stream with
+ * mvg_set_scratch, 0: none) matter to FINALIZE only.  Fields a pass does not have stay 0.  out may be NULL. */
+enum { MVG_BN_PASS_APPLY = 0, MVG_BN_PASS_BWD_APPLY = 1, MVG_BN_PASS_BWD_REDUCE = 2, MVG_BN_PASS_EVAL_BWD = 3,
+       MVG_BN_PASS_POOL_BWD_REDUCE = 4, MVG_BN_PASS_POOL_EVAL_BWD = 5, MVG_BN_PASS_FINALIZE = 6 };
+enum { MVG_BN_ELEM_FP32 = 0, MVG_BN_ELEM_BF16 = 1, MVG_BN_ELEM_SP = 2 };
+enum { MVG_BN_MERGE_WALK_GROUPS = 0, MVG_BN_MERGE_ALL_GROUPS = 1, MVG_BN_MERGE_PER_GROUP = 2 };
+typedef struct {
+  /* streaming passes (APPLY, BWD_APPLY) */
+  int64_t accesses_per_group; /* 16-byte accesses (sp: 8-channel chunks) per group */
+  int32_t grid_x;             /* workgroups of 256 lanes per group (at most 4096) */
+  int32_t trips;              /* loop trips of the busiest lane */
+  int32_t step;               /* column groups a lane advances by per trip (0: it keeps its channels) */
+  /* reduce-type passes (BWD_REDUCE, EVAL_BWD, POOL_BWD_REDUCE, POOL_EVAL_BWD) */
+  int32_t cwn, cw;            /* column groups per row, and per column block */
+  int32_t column_blocks;      /* grid.y; the last block is partly masked when cw does not divide cwn */
+  int32_t row_lanes;          /* 256 / cw */
+  int32_t chunks;             /* grid.x: row ranges (POOL_BWD_REDUCE: ranges of pooled lines; POOL_EVAL_BWD: workgroups) */
+  int32_t empty_chunks;       /* trailing chunks that receive no rows */
+  int64_t rows_per_chunk;     /* rows (pooled lines) per chunk; 0 for POOL_EVAL_BWD's grid-stride loop */
+  int64_t workspace_floats;   /* what the reported chunks write of the caller's workspace */
+  /* FINALIZE */
+  int32_t form;               /* MVG_BN_MERGE_*: one workgroup walks the groups / 2 - 4 groups share a workgroup's lanes /
+                               * one workgroup per group, then the running-statistics update */
+  int32_t lanes_per_group;    /* partial lanes merging one (channel, group) */
+  int32_t slices;             /* slices per group the partials are first collapsed to (0: unsliced) */
+  int32_t partials_per_slice; /* 0 when unsliced */
+  int64_t scratch_floats;     /* what the stream must have registered for the fastest form of these sizes (0: none) */
+} mvg_bn_plan;
+int mvg_bn_plan_query(int pass, int elem, int groups, int64_t rows_per_group, int c, int n_per_group, int h, int w,
+                      int partials, size_t scratch_floats, mvg_bn_plan *out);
 
 /* ---------------------------------------------------------------- pooling / layout
  * nn.MaxPool2d(3,2,1) resnet.py:189; nn.AdaptiveAvgPool2d((1,1)) resnet.py:200 + rot_mv.py:126;

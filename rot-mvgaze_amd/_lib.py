@@ -12,7 +12,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "librotmvgaze_hip.so")
 
 K_FAMILIES = 18
-ABI_VERSION = 12
+ABI_VERSION = 13
 SESSION_FP32, SESSION_BF16 = 0, 1         # MVG_SESSION_FP32 / MVG_SESSION_BF16 (mvg_session_create_ex)
 
 
@@ -39,6 +39,20 @@ class ConvPlan(C.Structure):
     _fields_ = [("bm", C.c_int32), ("bn", C.c_int32), ("bk", C.c_int32), ("fasta", C.c_int32), ("ncls", C.c_int32),
                 ("cls_tiles", C.c_int32 * 4), ("cls_kt", C.c_int32 * 4), ("streamk_grid", C.c_int32), ("splitk", C.c_int32),
                 ("scratch_floats", C.c_int64)]
+
+
+BN_PASS_APPLY, BN_PASS_BWD_APPLY, BN_PASS_BWD_REDUCE, BN_PASS_EVAL_BWD, BN_PASS_POOL_BWD_REDUCE, BN_PASS_POOL_EVAL_BWD, \
+    BN_PASS_FINALIZE = range(7)                                             # MVG_BN_PASS_* (mvg_bn_plan_query)
+BN_ELEM_FP32, BN_ELEM_BF16, BN_ELEM_SP = 0, 1, 2                            # MVG_BN_ELEM_*
+BN_MERGE_WALK_GROUPS, BN_MERGE_ALL_GROUPS, BN_MERGE_PER_GROUP = 0, 1, 2     # MVG_BN_MERGE_*
+
+
+class BnPlan(C.Structure):
+    """mvg_bn_plan (include/rotmvgaze.h)."""
+    _fields_ = [("accesses_per_group", C.c_int64), ("grid_x", C.c_int32), ("trips", C.c_int32), ("step", C.c_int32),
+                ("cwn", C.c_int32), ("cw", C.c_int32), ("column_blocks", C.c_int32), ("row_lanes", C.c_int32), ("chunks", C.c_int32),
+                ("empty_chunks", C.c_int32), ("rows_per_chunk", C.c_int64), ("workspace_floats", C.c_int64), ("form", C.c_int32),
+                ("lanes_per_group", C.c_int32), ("slices", C.c_int32), ("partials_per_slice", C.c_int32), ("scratch_floats", C.c_int64)]
 
 
 class ProfEntry(C.Structure):
@@ -78,6 +92,7 @@ SIGNATURES = {
     "mvg_conv_wgrad": (_I, [_D, _P, _P, _P, _P, _I, _I, _P]),
     "mvg_conv_wgrad_splits": (_I, [_D]),
     "mvg_conv_plan_query": (_I, [_D, _I, C.c_size_t, C.POINTER(ConvPlan)]),
+    "mvg_bn_plan_query": (_I, [_I, _I, _I, _I64, _I, _I, _I, _I, _I, C.c_size_t, C.POINTER(BnPlan)]),
     "mvg_conv_wgrad_tile": (_I, [_D, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mvg_linear_wgrad": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),
     "mvg_fuser_fprop": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, C.c_size_t, _P]),

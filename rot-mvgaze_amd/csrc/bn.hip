@@ -11,6 +11,14 @@
 namespace mvg {
 
 // ---- finalize: merge the conv epilogue's per-wave partials (sum, centred sumsq) -------------
+// Chan's merge needs the between-partials term  sum_p s_p^2 / cnt_p - S^2 / n.  Taken of the raw sums it subtracts two numbers
+// of size n mean^2: float64 keeps 2^-53 of THAT, and a channel with mean^2 >> var + eps (a constant channel at 1e3: variance
+// noise of 1e-5 eps) gets a wrong invstd.  So every kernel below sums d_p = s_p - cnt_p * pivot instead, pivot = the mean of
+// the group's first partial: the same identity (it holds for any shift), both terms now of the size of the variance itself.
+__device__ __forceinline__ double bn_merge_pivot(const float *__restrict__ st, int ch, long long rows, int rows_per_partial) {
+  return (double)st[ch] / (double)(rows < rows_per_partial ? rows : (long long)rows_per_partial);
+}
+
 // grid = c/8 blocks, 1024 threads = 8 channels x 128 partial-lanes.  Every group (= view) is merged
 // by the same workgroup, one after the other, so that the running statistics are updated in group
 // order (the reference runs the backbone on view 0, then view 1: models/rot_mv.py:204-205).
@@ -34,6 +42,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float *__restri
   for (int g = 0; g < groups; ++g) {
     const float *st = stats + (long long)g * partials * 2 * c;
     double s = 0.0, q = 0.0, ss = 0.0;
+    const double pivot = ch < c ? bn_merge_pivot(st, ch, rows, rows_per_partial) : 0.0;
     if (ch < c && sliced) {
       for (int k = pl; k < slices; k += 128) {
         const double *o = sliced + (((long long)g * slices + k) * 3) * c;
@@ -45,21 +54,24 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float *__restri
       // branch-free body (no early exit) so that the loads of several iterations are in flight at once
       const int valid = (int)((rows + rows_per_partial - 1) / rows_per_partial) < partials
                             ? (int)((rows + rows_per_partial - 1) / rows_per_partial) : partials;
+      const double full_pivot = (double)rows_per_partial * pivot;
 #pragma unroll 4
       for (int p = pl; p < valid; p += 128) {
         const float sp_f = st[((long long)p * 2) * c + ch];
         const float qp_f = st[((long long)p * 2 + 1) * c + ch];
-        const double sp = sp_f, qp = qp_f;
+        const double sp = (double)sp_f - full_pivot, qp = qp_f;
         s += sp;
         q += qp;
         ss += sp * sp;
       }
       ss *= inv_full;
-      // the ragged last partial was scaled by 1/rows_per_partial above: correct it to 1/cnt
+      // the ragged last partial was taken as a full one above (pivot and 1/rows_per_partial): correct it to its count
       const long long last_cnt = rows - (long long)(valid - 1) * rows_per_partial;
       if (valid > 0 && last_cnt < rows_per_partial && ((valid - 1) & 127) == pl) {
-        const double sp = st[((long long)(valid - 1) * 2) * c + ch];
-        ss += sp * sp * (1.0 / (double)last_cnt - inv_full);
+        const double raw = st[((long long)(valid - 1) * 2) * c + ch];
+        const double was = raw - full_pivot, sp = raw - (double)last_cnt * pivot;
+        s += sp - was;
+        ss += sp * sp / (double)last_cnt - was * was * inv_full;
       }
     }
     // reduce over the 128 partial lanes: lanes 8/16/32 apart inside the wave (shuffles), then the 16
@@ -91,8 +103,9 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float *__restri
     }
     if (pl == 0 && ch < c) {
       const double n = (double)rows;
-      const double mean = sh[0][0][cl] / n;
-      double m2 = sh[1][0][cl] + (sh[2][0][cl] - sh[0][0][cl] * mean);   // Chan merge of the partials
+      const double dmean = sh[0][0][cl] / n;                             // the sums are of s_p - cnt_p * pivot
+      const double mean = pivot + dmean;
+      double m2 = sh[1][0][cl] + (sh[2][0][cl] - sh[0][0][cl] * dmean);  // Chan merge of the partials
       if (m2 < 0.0) m2 = 0.0;
       const double var = m2 / n;
       const float invstd = (float)(1.0 / sqrt(var + (double)eps));
@@ -133,6 +146,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_group_kernel(const float *__
   const double inv_full = 1.0 / (double)rows_per_partial;
   const float *st = stats + (long long)g * partials * 2 * c;
   double s = 0.0, q = 0.0, ss = 0.0;
+  const double pivot = ch < c ? bn_merge_pivot(st, ch, rows, rows_per_partial) : 0.0;
   if (ch < c && sliced) {
     for (int k = pl; k < slices; k += 128) {
       const double *o = sliced + (((long long)g * slices + k) * 3) * c;
@@ -143,11 +157,12 @@ __global__ __launch_bounds__(1024) void bn_finalize_group_kernel(const float *__
   } else if (ch < c) {
     const int valid = (int)((rows + rows_per_partial - 1) / rows_per_partial) < partials
                           ? (int)((rows + rows_per_partial - 1) / rows_per_partial) : partials;
+    const double full_pivot = (double)rows_per_partial * pivot;
 #pragma unroll 4
     for (int p = pl; p < valid; p += 128) {
       const float sp_f = st[((long long)p * 2) * c + ch];
       const float qp_f = st[((long long)p * 2 + 1) * c + ch];
-      const double sp = sp_f, qp = qp_f;
+      const double sp = (double)sp_f - full_pivot, qp = qp_f;
       s += sp;
       q += qp;
       ss += sp * sp;
@@ -155,8 +170,10 @@ __global__ __launch_bounds__(1024) void bn_finalize_group_kernel(const float *__
     ss *= inv_full;
     const long long last_cnt = rows - (long long)(valid - 1) * rows_per_partial;
     if (valid > 0 && last_cnt < rows_per_partial && ((valid - 1) & 127) == pl) {
-      const double sp = st[((long long)(valid - 1) * 2) * c + ch];
-      ss += sp * sp * (1.0 / (double)last_cnt - inv_full);
+      const double raw = st[((long long)(valid - 1) * 2) * c + ch];
+      const double was = raw - full_pivot, sp = raw - (double)last_cnt * pivot;
+      s += sp - was;
+      ss += sp * sp / (double)last_cnt - was * was * inv_full;
     }
   }
 #pragma unroll
@@ -181,8 +198,9 @@ __global__ __launch_bounds__(1024) void bn_finalize_group_kernel(const float *__
       ss += sh[2][k][cl];
     }
     const double n = (double)rows;
-    const double mean = s / n;
-    double m2 = q + (ss - s * mean);                   // Chan merge of the partials
+    const double dmean = s / n;                         // the sums are of s_p - cnt_p * pivot
+    const double mean = pivot + dmean;
+    double m2 = q + (ss - s * dmean);                  // Chan merge of the partials
     if (m2 < 0.0) m2 = 0.0;
     const double var = m2 / n;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
@@ -213,7 +231,7 @@ __global__ __launch_bounds__(256) void bn_running_update_kernel(const double *__
 }
 
 // Large partial counts (stem at C2: 25 088 per group) first collapse to <= 64 slices per group with
-// all CUs busy; bn_finalize_kernel then merges the slices.  slice record: (sum, q, sum of s^2/cnt) in
+// all CUs busy; bn_finalize_kernel then merges the slices.  slice record: (sum, q, sum of s^2/cnt) of the pivoted s_p - cnt_p * pivot, in
 // fp64, [group][slice][3][c].
 __global__ __launch_bounds__(256) void bn_partials_slice_kernel(const float *__restrict__ stats, int partials,
                                                                 int rows_per_partial, long long rows, int c,
@@ -230,10 +248,13 @@ __global__ __launch_bounds__(256) void bn_partials_slice_kernel(const float *__r
   double s = 0.0, q = 0.0, ss = 0.0;
   if (ch < c) {
     const double inv_full = 1.0 / (double)rows_per_partial;
+    const double pivot = bn_merge_pivot(st, ch, rows, rows_per_partial);      // the finalize kernels form the same one
 #pragma unroll 4
     for (int p = p0 + pl; p < p1; p += 32) {
-      const double sp = st[((long long)p * 2) * c + ch], qp = st[((long long)p * 2 + 1) * c + ch];
+      const double raw = st[((long long)p * 2) * c + ch], qp = st[((long long)p * 2 + 1) * c + ch];
       long long cnt = rows - (long long)p * rows_per_partial;
+      if (cnt > rows_per_partial) cnt = rows_per_partial;
+      const double sp = raw - (double)cnt * pivot;
       s += sp;
       q += qp;
       ss += sp * sp * (cnt >= rows_per_partial ? inv_full : 1.0 / (double)cnt);
@@ -275,8 +296,9 @@ __global__ __launch_bounds__(1024) void bn_finalize_allgroups_kernel(const float
   const int cl = threadIdx.x & 7, l = threadIdx.x >> 3;
   const int g = l / lpg, pl = l - g * lpg;
   const int ch = blockIdx.x * 8 + cl;
-  double s = 0.0, q = 0.0, ss = 0.0;
+  double s = 0.0, q = 0.0, ss = 0.0, pivot = 0.0;
   if (ch < c && g < groups) {
+    pivot = bn_merge_pivot(stats + (long long)g * partials * 2 * c, ch, rows, rows_per_partial);
     if (sliced) {
       for (int k = pl; k < slices; k += lpg) {
         const double *o = sliced + (((long long)g * slices + k) * 3) * c;
@@ -291,8 +313,10 @@ __global__ __launch_bounds__(1024) void bn_finalize_allgroups_kernel(const float
                             ? (int)((rows + rows_per_partial - 1) / rows_per_partial) : partials;
 #pragma unroll 4
       for (int p = pl; p < valid; p += lpg) {
-        const double sp = st[((long long)p * 2) * c + ch], qp = st[((long long)p * 2 + 1) * c + ch];
-        const long long cnt = rows - (long long)p * rows_per_partial;
+        const double raw = st[((long long)p * 2) * c + ch], qp = st[((long long)p * 2 + 1) * c + ch];
+        long long cnt = rows - (long long)p * rows_per_partial;
+        if (cnt > rows_per_partial) cnt = rows_per_partial;
+        const double sp = raw - (double)cnt * pivot;
         s += sp;
         q += qp;
         ss += sp * sp * (cnt >= rows_per_partial ? inv_full : 1.0 / (double)cnt);
@@ -310,8 +334,9 @@ __global__ __launch_bounds__(1024) void bn_finalize_allgroups_kernel(const float
       ss += sh[2][l + k][cl];
     }
     const double n = (double)rows;
-    const double mean = s / n;
-    double m2 = q + (ss - s * mean);                   // Chan merge of the partials
+    const double dmean = s / n;                         // the sums are of s_p - cnt_p * pivot
+    const double mean = pivot + dmean;
+    double m2 = q + (ss - s * dmean);                  // Chan merge of the partials
     if (m2 < 0.0) m2 = 0.0;
     const double var = m2 / n;
     const float invstd = (float)(1.0 / sqrt(var + (double)eps));
@@ -1270,10 +1295,77 @@ struct ReduceGeom {
 static int reduce_geometry(const char *who, int groups, long long rows, int c, int W, ReduceGeom &g) {
   g.cwn = c / 4 / W;
   g.cw = g.cwn < 256 ? g.cwn : 256;
-  MVG_REQUIRE(256 % g.cw == 0, "%s: c/%d must divide 256 or be a multiple of it (c=%d)", who, 4 * W, c);
+  // (more than 256 column groups: blocks of 256, the last one masked where cwn is no multiple of 256 - c = 1536 in fp32)
+  MVG_REQUIRE(g.cw > 0 && 256 % g.cw == 0, "%s: c/%d must divide 256 or be larger than 256 (c=%d)", who, 4 * W, c);
   g.chunks = bwd_chunks(groups, rows, c);
   g.rows_per_chunk = (rows + g.chunks - 1) / g.chunks;
   return 0;
+}
+
+// The stem tail's reduce pass cuts POOLED lines (image, oy), not rows: never more chunks than lines, and none without one.
+static int pool_reduce_chunks(int chunks, int lines, int &lines_per_chunk) {
+  if (chunks > lines) chunks = lines;
+  lines_per_chunk = (lines + chunks - 1) / chunks;
+  return (lines + lines_per_chunk - 1) / lines_per_chunk;
+}
+
+// workgroups per group of bn_pool_eval_bwd_kernel: one per 256 (quad, channel group) items, at most eval_pool_chunks
+static int eval_pool_grid(int groups, int n_per_group, int h, int w, int c4n) {
+  const long long items = (long long)n_per_group * ((h + 1) / 2) * ((w + 1) / 2) * c4n;
+  long long chunks = (items + 255) / 256;
+  if (chunks > eval_pool_chunks(groups)) chunks = eval_pool_chunks(groups);
+  return (int)chunks;
+}
+
+// The geometry of the streaming passes over `accesses` 16-byte accesses per group, cwn of them per row: grid_for's
+// workgroups of 256 lanes, every lane looping with the grid's stride; `step` is what the kernels advance a lane's column
+// group by per trip (0: it keeps its columns, and the bf16 / sp kernels their per-channel factors).
+struct StreamGeom {
+  int grid, trips, step;
+};
+static StreamGeom stream_geometry(long long accesses, int cwn) {
+  StreamGeom s;
+  s.grid = grid_for(accesses);
+  const long long stride = (long long)s.grid * 256;
+  s.trips = (int)((accesses + stride - 1) / stride);
+  s.step = (int)(stride % cwn);
+  return s;
+}
+
+// Which merge mvg_bn_finalize runs, from the sizes and the scratch the stream has (api.hip: mvg_set_scratch):
+//   form 0  bn_finalize_kernel walks the groups (one group, or no scratch for the per-group records)
+//   form 1  bn_finalize_allgroups_kernel: 2 - 4 groups share a workgroup's 128 lanes
+//   form 2  bn_finalize_group_kernel + bn_running_update_kernel
+// and whether bn_partials_slice_kernel runs first (>= 1024 partials and scratch for the slices behind the records).
+struct FinalizePlan {
+  int form, lanes_per_group, slices, per_slice;
+  size_t mv_floats, need_floats;     // scratch of the per-group records; of records + slices (what the sliced form asks for)
+};
+static FinalizePlan finalize_plan(int groups, int partials, int c, size_t scratch_floats) {
+  FinalizePlan f;
+  f.mv_floats = (size_t)groups * 2 * c * 2;      // [groups][2][c] doubles
+  f.need_floats = f.mv_floats;
+  f.slices = f.per_slice = 0;
+  const bool mv = groups > 1 && scratch_floats >= f.mv_floats;
+  if (partials >= 1024) {
+    const int per_slice = ceil_div(partials, 64);
+    const int slices = ceil_div(partials, per_slice);
+    f.need_floats = f.mv_floats + (size_t)groups * slices * 3 * c * 2;
+    if (scratch_floats >= f.need_floats) {
+      f.slices = slices;
+      f.per_slice = per_slice;
+    }
+  }
+  if (groups > 1 && groups <= 4 && (partials < 1024 || f.slices)) {
+    // (>= 32 lanes per group; with 8 groups - C5's shapes - 16 lanes per group made the call slower than the two launches
+    // of form 2: bn_finalize 1.00 -> 1.39 ms per C5 step)
+    f.form = 1;
+    f.lanes_per_group = 128 / groups;
+  } else {
+    f.form = mv ? 2 : 0;
+    f.lanes_per_group = 128;
+  }
+  return f;
 }
 
 // The ReLU mask of a backward pass comes ONE way: the activation, the bits bn_apply recorded, or y with (scale, shift).
@@ -1281,6 +1373,22 @@ static int require_one_mask(const char *who, const char *ways, const void *act, 
                             const float *relu_shift) {
   MVG_REQUIRE((act ? 1 : 0) + (relu_bits ? 1 : 0) + (relu_scale ? 1 : 0) <= 1, "%s: give the ReLU mask %s", who, ways);
   MVG_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "%s: relu_scale and relu_shift go together", who);
+  return 0;
+}
+
+// The channel counts the passes take (shared with mvg_bn_plan_query): W float4 groups per 16-byte access; 8 channels per lane in sp
+static int require_channels(const char *who, int c, int W) {
+  MVG_REQUIRE(c % 4 == 0, "%s: c %% 4 != 0", who);
+  MVG_REQUIRE(c % (4 * W) == 0, "%s: c must be a multiple of %d", who, 4 * W);
+  return 0;
+}
+static int require_c8(const char *who, int c) {
+  MVG_REQUIRE(c % 8 == 0, "%s: c %% 8 != 0", who);
+  return 0;
+}
+static int require_pool_eval_sizes(int groups, int n_per_group, int h, int w, int c) {
+  MVG_REQUIRE(groups > 0 && groups < 65536 && n_per_group > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && 256 % (c / 4) == 0,
+              "bn_relu_maxpool_eval_bwd: bad sizes (c/4 must divide 256, c=%d)", c);
   return 0;
 }
 
@@ -1324,34 +1432,33 @@ int mvg_bn_finalize(const float *stats, int groups, int partials, int rows_per_p
   MVG_REQUIRE(groups > 0 && partials > 0 && c > 0 && rows_per_group > 0, "bn_finalize: bad sizes");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_BN_FINALIZE, st, 0.0, 4.0 * groups * (double)partials * 2 * c);
-  const double *sliced = nullptr;
-  int slices = 0;
-  // scratch: [groups][2][c] doubles for the group-parallel form, then the slices
-  const size_t mv_floats = (size_t)groups * 2 * c * 2;
-  double *mv = groups > 1 ? (double *)stream_scratch(st, mv_floats) : nullptr;
-  if (partials >= 1024) {
-    slices = 64;
-    const int per_slice = ceil_div(partials, slices);
-    slices = ceil_div(partials, per_slice);
-    float *base = stream_scratch(st, mv_floats + (size_t)groups * slices * 3 * c * 2);
-    double *buf = base ? (double *)(base + mv_floats) : nullptr;
-    if (buf) {
-      hipLaunchKernelGGL(bn_partials_slice_kernel, dim3(ceil_div(c, 8), slices, groups), dim3(256), 0, st, stats, partials,
-                         rows_per_partial, (long long)rows_per_group, c, per_slice, buf, slices);
-      if (check_launch("bn_partials_slice")) return 1;
-      sliced = buf;
-    }
+  // scratch: [groups][2][c] doubles for the group-parallel form, then the slices; the plan is made for what the stream has
+  size_t have = 0;
+  {
+    const FinalizePlan want = finalize_plan(groups, partials, c, (size_t)-1);
+    if (stream_scratch(st, want.need_floats)) have = want.need_floats;
+    else if (stream_scratch(st, want.mv_floats)) have = want.mv_floats;
   }
-  if (groups > 1 && groups <= 4 && (partials < 1024 || sliced)) {
-    // every group's statistics and the running statistics in ONE launch (the workgroup's lanes divided between the groups:
-    // >= 32 lanes per group; with 8 groups - C5's shapes - 16 lanes per group made the call slower than the two launches
-    // below: bn_finalize 1.00 -> 1.39 ms per C5 step)
-    hipLaunchKernelGGL(bn_finalize_allgroups_kernel, dim3(ceil_div(c, 8)), dim3(1024), 0, st, stats, sliced, slices, groups, 128 / groups,
+  const FinalizePlan fp = finalize_plan(groups, partials, c, have);
+  float *base = have ? stream_scratch(st, have) : nullptr;
+  double *mv = fp.form == 2 ? (double *)base : nullptr;
+  const double *sliced = nullptr;
+  const int slices = fp.slices;
+  if (slices) {
+    double *buf = (double *)(base + fp.mv_floats);
+    hipLaunchKernelGGL(bn_partials_slice_kernel, dim3(ceil_div(c, 8), slices, groups), dim3(256), 0, st, stats, partials,
+                       rows_per_partial, (long long)rows_per_group, c, fp.per_slice, buf, slices);
+    if (check_launch("bn_partials_slice")) return 1;
+    sliced = buf;
+  }
+  if (fp.form == 1) {
+    // every group's statistics and the running statistics in ONE launch (the workgroup's lanes divided between the groups)
+    hipLaunchKernelGGL(bn_finalize_allgroups_kernel, dim3(ceil_div(c, 8)), dim3(1024), 0, st, stats, sliced, slices, groups, fp.lanes_per_group,
                        partials, rows_per_partial, (long long)rows_per_group, c, gamma, beta, eps, momentum, mean, invstd, scale, shift,
                        running_mean, running_var);
     return check_launch("bn_finalize(all groups)");
   }
-  if (mv) {
+  if (fp.form == 2) {
     hipLaunchKernelGGL(bn_finalize_group_kernel, dim3(ceil_div(c, 8), groups), dim3(1024), 0, st, stats, sliced, slices, partials,
                        rows_per_partial, (long long)rows_per_group, c, gamma, beta, eps, mean, invstd, scale, shift, mv);
     if (check_launch("bn_finalize(groups)")) return 1;
@@ -1395,16 +1502,15 @@ template <typename T, typename TO = T, typename TR = T>
 static int bn_apply_impl(const T *y, const float *scale, const float *shift, const TR *residual, const float *res_scale,
                          const float *res_shift, int relu, TO *out, int groups, int64_t rows_per_group, int c, void *stream,
                          uint8_t *relu_bits = nullptr) {
-  MVG_REQUIRE(c % 4 == 0, "bn_apply: c %% 4 != 0");
   MVG_REQUIRE((res_scale == nullptr) == (res_shift == nullptr) && (residual || !res_scale),
               "bn_apply: res_scale / res_shift go together and need a residual");
   hipStream_t st = (hipStream_t)stream;
   const long long n4 = rows_per_group * (c / 4);
   constexpr int W = Elem<T>::W;
-  MVG_REQUIRE(c % (4 * W) == 0, "bn_apply: c must be a multiple of %d", 4 * W);
+  if (int e = require_channels("bn_apply", c, W)) return e;
   ProfScope ps(MVG_K_BN_APPLY, st, 0.0,
                4.0 * groups * (double)n4 * (Elem<T>::kBytes + Elem<TO>::kBytes + (residual ? Elem<TR>::kBytes : 0.0)));
-  hipLaunchKernelGGL((bn_apply_kernel<T, TO, TR>), dim3(grid_for(n4 / W), groups), dim3(256), 0, st, y, scale, shift, residual, res_scale,
+  hipLaunchKernelGGL((bn_apply_kernel<T, TO, TR>), dim3(stream_geometry(n4 / W, c / 4 / W).grid, groups), dim3(256), 0, st, y, scale, shift, residual, res_scale,
                      res_shift, relu, out, n4 / W, c / 4 / W, c, relu_bits);
   return check_launch("bn_apply");
 }
@@ -1417,11 +1523,10 @@ static int bn_bwd_reduce_impl(const T *g, const T *act, const T *y, const float 
                               float *dy_sinv = nullptr) {
   if (int e = require_one_mask("bn_bwd_reduce", "ONE way: act, (relu_scale, relu_shift) or relu_bits", act, relu_bits, relu_scale, relu_shift))
     return e;
-  MVG_REQUIRE(c % 4 == 0, "bn_bwd_reduce: c %% 4 != 0");
   MVG_REQUIRE(workspace != nullptr, "bn_bwd_reduce: workspace required");
   hipStream_t st = (hipStream_t)stream;
   constexpr int W = Elem<T>::W;
-  MVG_REQUIRE(c % (4 * W) == 0, "bn_bwd_reduce: c must be a multiple of %d", 4 * W);
+  if (int e = require_channels("bn_bwd_reduce", c, W)) return e;
   ReduceGeom q;
   if (int e = reduce_geometry("bn_bwd_reduce", groups, rows_per_group, c, W, q)) return e;
   ProfScope ps(MVG_K_BN_BWD_REDUCE, st, 0.0, Elem<T>::kBytes * groups * (double)rows_per_group * c * ((act ? 3 : 2) + (dz_out ? 1 : 0)));
@@ -1438,14 +1543,13 @@ static int bn_bwd_apply_impl(const T *g, const T *act, const T *y, const float *
                              const float *s1, const float *s2, const float *relu_scale, const float *relu_shift, int groups,
                              int64_t rows_per_group, int c, TO *dy, T *dz_out, void *stream) {
   if (int e = require_one_mask("bn_bwd_apply", "either as act or as (relu_scale, relu_shift)", act, nullptr, relu_scale, relu_shift)) return e;
-  MVG_REQUIRE(c % 4 == 0, "bn_bwd_apply: c %% 4 != 0");
   hipStream_t st = (hipStream_t)stream;
   const long long n4 = rows_per_group * (c / 4);
   constexpr int W = Elem<T>::W;
-  MVG_REQUIRE(c % (4 * W) == 0, "bn_bwd_apply: c must be a multiple of %d", 4 * W);
+  if (int e = require_channels("bn_bwd_apply", c, W)) return e;
   ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0,
                4.0 * groups * (double)n4 * (Elem<T>::kBytes * ((act ? 3 : 2) + (dz_out ? 1 : 0)) + Elem<TO>::kBytes));
-  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, TO>), dim3(grid_for(n4 / W), groups), dim3(256), 0, st, g, act, y, mean, invstd, gamma, s1, s2,
+  hipLaunchKernelGGL((bn_bwd_apply_kernel<T, TO>), dim3(stream_geometry(n4 / W, c / 4 / W).grid, groups), dim3(256), 0, st, g, act, y, mean, invstd, gamma, s1, s2,
                      relu_scale, relu_shift, n4 / W, 1.0f / (float)rows_per_group, c / 4 / W, c, dy, dz_out);
   return check_launch("bn_bwd_apply");
 }
@@ -1472,7 +1576,7 @@ static int bn_relu_maxpool_bwd_reduce_impl(const T *g_pooled, const uint8_t *arg
                                            int n_per_group, int h, int w, int c, int ho, int wo, float *s1, float *s2,
                                            float *dgamma, float *dbeta, int accumulate, float *workspace, void *stream,
                                            float *mx = nullptr, const float *gamma = nullptr, float *dy_sinv = nullptr) {
-  MVG_REQUIRE(c % 4 == 0, "bn_relu_maxpool_bwd_reduce: c %% 4 != 0");
+  if (int e = require_channels("bn_relu_maxpool_bwd_reduce", c, 1)) return e;
   MVG_REQUIRE(workspace != nullptr, "bn_relu_maxpool_bwd_reduce: workspace required");
   hipStream_t st = (hipStream_t)stream;
   const long long rows = (long long)n_per_group * h * w;
@@ -1481,10 +1585,8 @@ static int bn_relu_maxpool_bwd_reduce_impl(const T *g_pooled, const uint8_t *arg
   const int c4n = q.cwn, cw = q.cw;
   // chunk = whole image lines; never more chunks than mvg_bn_bwd_workspace_floats(groups, rows, c) sizes
   const int lines = n_per_group * ho;                 // pooled lines
-  int chunks = q.chunks;
-  if (chunks > lines) chunks = lines;
-  const int lpc = (lines + chunks - 1) / chunks;
-  chunks = (lines + lpc - 1) / lpc;
+  int lpc = 0;
+  const int chunks = pool_reduce_chunks(q.chunks, lines, lpc);
   ProfScope ps(MVG_K_BN_BWD_REDUCE, st, 0.0,
                Elem<T>::kBytes * groups * ((double)rows * c + (double)n_per_group * ho * wo * c * 1.25));
   hipLaunchKernelGGL(bn_pool_bwd_reduce_kernel<T>, dim3(chunks, ceil_div(c4n, cw), groups), dim3(256), 0, st, g_pooled,
@@ -1596,14 +1698,14 @@ int mvg_bn_bwd_reduce_split(const float *g, const uint8_t *relu_bits, const floa
 static int bn_apply_split_impl(const float *y, const float *scale, const float *shift, const void *residual, int residual_sp,
                                const float *res_scale, const float *res_shift, const float *res_sinv, int relu, void *out_sp,
                                const float *out_sinv, uint8_t *relu_bits, int groups, int64_t rows_per_group, int c, void *stream) {
-  MVG_REQUIRE(c % 8 == 0, "bn_apply_split: c %% 8 != 0");
+  if (int e = require_c8("bn_apply_split", c)) return e;
   MVG_REQUIRE(!(residual_sp && res_scale), "bn_apply_split: an sp residual is already normalised (no res_scale / res_shift)");
   MVG_REQUIRE((res_scale == nullptr) == (res_shift == nullptr) && (residual || !res_scale),
               "bn_apply_split: res_scale / res_shift go together and need a residual");
   hipStream_t st = (hipStream_t)stream;
   const long long n8 = rows_per_group * (c / 8);
   ProfScope ps(MVG_K_BN_APPLY, st, 0.0, 8.0 * groups * (double)n8 * (4.0 + SP_BYTES + (residual ? (residual_sp ? (double)SP_BYTES : 4.0) : 0.0)));
-  const dim3 grid(grid_for(n8), groups), block(256);
+  const dim3 grid(stream_geometry(n8, c / 8).grid, groups), block(256);
   if (residual && residual_sp)
     hipLaunchKernelGGL(bn_apply_sp_kernel<true>, grid, block, 0, st, y, scale, shift, residual, res_scale, res_shift, relu,
                        (sp_t *)out_sp, n8, c / 8, c, (unsigned short *)relu_bits, out_sinv, res_sinv);
@@ -1646,14 +1748,14 @@ int mvg_act_scales(const void *items_dev, int n, float *slots, int n_slots, void
 int mvg_bn_bwd_apply_split(const float *g, const float *y, const float *mean, const float *invstd, const float *gamma,
                            const float *s1, const float *s2, const float *relu_scale, const float *relu_shift, int groups,
                            int64_t rows_per_group, int c, void *dy_sp, const float *mx, float *dy_sinv, int dy_sinv_ready, void *stream) {
-  MVG_REQUIRE(c % 8 == 0, "bn_bwd_apply_split: c %% 8 != 0");
+  if (int e = require_c8("bn_bwd_apply_split", c)) return e;
   MVG_REQUIRE(mx && dy_sinv, "bn_bwd_apply_split: mx (max |masked gradient| per (group, channel) from the reduce pass) and dy_sinv are required");
   MVG_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "bn_bwd_apply_split: relu_scale and relu_shift go together");
   hipStream_t st = (hipStream_t)stream;
   const long long n8 = rows_per_group * (c / 8);
   ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0, 8.0 * groups * (double)n8 * (8.0 + SP_BYTES));
   if (ensure_dy_scale(dy_sinv_ready, gamma, invstd, s1, s2, mx, groups, c, rows_per_group, dy_sinv, st)) return 1;
-  hipLaunchKernelGGL(bn_bwd_apply_sp_kernel, dim3(grid_for(n8), groups), dim3(256), 0, st, g, y, mean, invstd, gamma, s1, s2,
+  hipLaunchKernelGGL(bn_bwd_apply_sp_kernel, dim3(stream_geometry(n8, c / 8).grid, groups), dim3(256), 0, st, g, y, mean, invstd, gamma, s1, s2,
                      relu_scale, relu_shift, n8, 1.0f / (float)rows_per_group, c / 8, c, (sp_t *)dy_sp, dy_sinv);
   return check_launch("bn_bwd_apply_split");
 }
@@ -1739,23 +1841,107 @@ int mvg_bn_relu_maxpool_eval_bwd(const float *g_pooled, const uint8_t *argmax, c
                                  int accumulate, float *workspace, void *stream) {
   MVG_REQUIRE(g_pooled && argmax && y && scale && shift && gamma && running_mean && running_var && dy && workspace,
               "bn_relu_maxpool_eval_bwd: every pointer but dgamma / dbeta is required");
-  MVG_REQUIRE(groups > 0 && groups < 65536 && n_per_group > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && 256 % (c / 4) == 0,
-              "bn_relu_maxpool_eval_bwd: bad sizes (c/4 must divide 256, c=%d)", c);
+  if (int e = require_pool_eval_sizes(groups, n_per_group, h, w, c)) return e;
   MVG_REQUIRE(ho == (h + 2 - 3) / 2 + 1 && wo == (w + 2 - 3) / 2 + 1, "bn_relu_maxpool_eval_bwd: bad output size");
   hipStream_t st = (hipStream_t)stream;
   const int c4n = c / 4;
-  const long long items = (long long)n_per_group * ((h + 1) / 2) * ((w + 1) / 2) * c4n;
-  long long chunks = (items + 255) / 256;
-  if (chunks > eval_pool_chunks(groups)) chunks = eval_pool_chunks(groups);
+  const int chunks = eval_pool_grid(groups, n_per_group, h, w, c4n);
   ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0,
                4.0 * groups * ((double)n_per_group * h * w * c * 2 + (double)n_per_group * ho * wo * c * 1.25));
-  hipLaunchKernelGGL(bn_pool_eval_bwd_kernel, dim3((int)chunks, groups), dim3(256), 0, st, g_pooled, (const uchar4 *)argmax, y, scale,
+  hipLaunchKernelGGL(bn_pool_eval_bwd_kernel, dim3(chunks, groups), dim3(256), 0, st, g_pooled, (const uchar4 *)argmax, y, scale,
                      shift, gamma, running_mean, running_var, eps, n_per_group, h, w, ho, wo, c4n, dy, workspace);
   if (check_launch("bn_relu_maxpool_eval_bwd")) return 1;
   if (!dgamma && !dbeta) return 0;
-  hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(1024), 0, st, workspace, groups * (int)chunks, c, dgamma,
+  hipLaunchKernelGGL(bn_eval_bwd_finalize_kernel, dim3(ceil_div(c, 16)), dim3(1024), 0, st, workspace, groups * chunks, c, dgamma,
                      dbeta, accumulate);
   return check_launch("bn_eval_bwd_finalize");
+}
+
+// ---- host-only plan query: the geometry functions above, asked without launching -----------------------------------
+static int bn_plan_impl(int pass, int elem, int groups, int64_t rows_per_group, int c, int n_per_group, int h, int w, int partials,
+                        size_t scratch_floats, mvg_bn_plan &p) {
+  MVG_REQUIRE(elem == MVG_BN_ELEM_FP32 || elem == MVG_BN_ELEM_BF16 || elem == MVG_BN_ELEM_SP, "bn_plan_query: unknown element kind %d", elem);
+  MVG_REQUIRE(groups > 0 && groups < 65536 && c > 0, "bn_plan_query: bad sizes");
+  const int W = elem == MVG_BN_ELEM_BF16 ? 2 : 1;      // float4 groups per 16-byte access of the reduce-type kernels
+  if (pass == MVG_BN_PASS_APPLY || pass == MVG_BN_PASS_BWD_APPLY) {
+    MVG_REQUIRE(rows_per_group > 0, "bn_plan_query: bad sizes");
+    const char *who = pass == MVG_BN_PASS_APPLY ? "bn_apply" : "bn_bwd_apply";
+    int cwn;
+    if (elem == MVG_BN_ELEM_SP) {        // bn_apply_sp_kernel / bn_bwd_apply_sp_kernel: 8 channels per lane
+      if (int e = require_c8(pass == MVG_BN_PASS_APPLY ? "bn_apply_split" : "bn_bwd_apply_split", c)) return e;
+      cwn = c / 8;
+    } else {
+      if (int e = require_channels(who, c, W)) return e;
+      cwn = c / 4 / W;
+    }
+    p.accesses_per_group = rows_per_group * cwn;
+    const StreamGeom s = stream_geometry(p.accesses_per_group, cwn);
+    p.grid_x = s.grid;
+    p.trips = s.trips;
+    p.step = s.step;
+    return 0;
+  }
+  if (pass == MVG_BN_PASS_BWD_REDUCE || pass == MVG_BN_PASS_EVAL_BWD || pass == MVG_BN_PASS_POOL_BWD_REDUCE) {
+    const bool pool = pass == MVG_BN_PASS_POOL_BWD_REDUCE;
+    const char *who = pass == MVG_BN_PASS_BWD_REDUCE ? "bn_bwd_reduce" : pool ? "bn_relu_maxpool_bwd_reduce" : "bn_eval_bwd";
+    MVG_REQUIRE(pass != MVG_BN_PASS_EVAL_BWD || elem == MVG_BN_ELEM_FP32, "bn_plan_query: the eval-mode backward is fp32 only");
+    if (pool) MVG_REQUIRE(n_per_group > 0 && h > 0 && w > 0, "bn_plan_query: bad sizes");
+    const long long rows = pool ? (long long)n_per_group * h * w : (long long)rows_per_group;
+    MVG_REQUIRE(rows > 0, "bn_plan_query: bad sizes");
+    const int Wg = pool ? 1 : W;         // the pooled reduce reads 4 channels per lane whatever the storage
+    if (int e = require_channels(who, c, Wg)) return e;
+    ReduceGeom q;
+    if (int e = reduce_geometry(who, groups, rows, c, Wg, q)) return e;
+    p.cwn = q.cwn;
+    p.cw = q.cw;
+    p.column_blocks = ceil_div(q.cwn, q.cw);
+    p.row_lanes = 256 / q.cw;
+    if (pool) {
+      int lpc = 0;
+      p.chunks = pool_reduce_chunks(q.chunks, n_per_group * ((h - 1) / 2 + 1), lpc);
+      p.rows_per_chunk = lpc;
+      p.empty_chunks = 0;
+    } else {
+      p.chunks = q.chunks;
+      p.rows_per_chunk = q.rows_per_chunk;
+      p.empty_chunks = q.chunks - (int)((rows + q.rows_per_chunk - 1) / q.rows_per_chunk);
+    }
+    p.workspace_floats = (int64_t)groups * p.chunks * (pass == MVG_BN_PASS_EVAL_BWD ? 2 : elem == MVG_BN_ELEM_SP ? 3 : 2) * c;
+    return 0;
+  }
+  if (pass == MVG_BN_PASS_POOL_EVAL_BWD) {
+    MVG_REQUIRE(elem == MVG_BN_ELEM_FP32, "bn_plan_query: the eval-mode backward is fp32 only");
+    if (int e = require_pool_eval_sizes(groups, n_per_group, h, w, c)) return e;
+    p.cwn = p.cw = c / 4;
+    p.column_blocks = 1;
+    p.row_lanes = 256 / p.cw;
+    p.chunks = eval_pool_grid(groups, n_per_group, h, w, c / 4);
+    p.rows_per_chunk = 0;                // a grid-stride loop over (quad, channel group) items, not a range of rows
+    p.empty_chunks = 0;
+    p.workspace_floats = (int64_t)groups * p.chunks * 2 * c;
+    return 0;
+  }
+  if (pass == MVG_BN_PASS_FINALIZE) {
+    MVG_REQUIRE(groups > 0 && partials > 0 && c > 0 && rows_per_group > 0, "bn_finalize: bad sizes");
+    const FinalizePlan f = finalize_plan(groups, partials, c, scratch_floats);
+    p.form = f.form;
+    p.lanes_per_group = f.lanes_per_group;
+    p.slices = f.slices;
+    p.partials_per_slice = f.per_slice;
+    p.scratch_floats = (int64_t)(groups > 1 || partials >= 1024 ? f.need_floats : 0);
+    return 0;
+  }
+  MVG_REQUIRE(false, "bn_plan_query: unknown pass %d", pass);
+  return 0;
+}
+
+int mvg_bn_plan_query(int pass, int elem, int groups, int64_t rows_per_group, int c, int n_per_group, int h, int w, int partials,
+                      size_t scratch_floats, mvg_bn_plan *out) {
+  mvg_bn_plan plan;
+  memset(&plan, 0, sizeof(plan));
+  if (bn_plan_impl(pass, elem, groups, rows_per_group, c, n_per_group, h, w, partials, scratch_floats, plan)) return -1;
+  if (out) *out = plan;
+  return 0;
 }
 
 }  // extern "C"

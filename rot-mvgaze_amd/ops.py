@@ -154,6 +154,22 @@ def conv_plan_query(d: ConvDesc, kind: int = 0, ws_floats: int = 0) -> dict:
             "scratch_floats": pl.scratch_floats}
 
 
+def bn_plan_query(bn_pass: int, elem: int = 0, groups: int = 1, rows_per_group: int = 0, c: int = 0, n_per_group: int = 0, h: int = 0,
+                  w: int = 0, partials: int = 0, scratch_floats: int = 0) -> dict:
+    """What a BatchNorm pass of these sizes would run with the CUs the planners may use now (set_reserved_cus), answered by the
+    functions the launches plan with; nothing is launched.  bn_pass: _lib.BN_PASS_*; elem: _lib.BN_ELEM_* (the storage family).
+    Streaming passes (APPLY, BWD_APPLY): accesses_per_group, grid_x, trips, step.  Reduce-type passes: cwn, cw, column_blocks,
+    row_lanes, chunks, empty_chunks, rows_per_chunk, workspace_floats (the POOL passes take n_per_group, h, w).  FINALIZE
+    (groups, partials and the scratch_floats registered for the stream): form (_lib.BN_MERGE_*), lanes_per_group, slices,
+    partials_per_slice, scratch_floats.  Raises with the launch's message for sizes the launch would reject."""
+    from ._lib import BnPlan
+    pl = BnPlan()
+    if lib().mvg_bn_plan_query(int(bn_pass), int(elem), int(groups), int(rows_per_group), int(c), int(n_per_group), int(h), int(w),
+                               int(partials), int(scratch_floats), C.byref(pl)) != 0:
+        check(1, "bn_plan_query")
+    return {n: int(getattr(pl, n)) for n, _ in BnPlan._fields_}
+
+
 def conv_wgrad_tile(d: ConvDesc):
     """(bm, bn, incremental): the tile conv_wgrad runs ``d`` on and whether the kernel addresses pixels incrementally."""
     bm, bn, incr = C.c_int32(0), C.c_int32(0), C.c_int32(0)

@@ -14,7 +14,7 @@ bad = 0
 for it in range(cases):
     G, N = int(rng.integers(1, 4)), int(rng.integers(1, 7))
     H, W = int(rng.integers(1, 40)), int(rng.integers(1, 40))
-    C = 4 * int(rng.choice([1, 2, 4, 8, 16, 32, 64, 128, 256, 512]))      # c/4 must divide 256 or be a multiple of it (checked by the library)
+    C = 4 * int(rng.choice([1, 2, 4, 8, 16, 32, 64, 128, 256, 512]))      # c/4 must divide 256 or be larger than 256 (checked by the library)
     relu, res = bool(rng.integers(0, 2)), bool(rng.integers(0, 2))
     if N * H * W < 2:
         continue

@@ -47,7 +47,7 @@ def test_act_scale_entry_points_declared_exported_and_bound(built_lib):
         assert len(_lib.SIGNATURES[name][1]) == nargs, (name, nargs, len(_lib.SIGNATURES[name][1]))
         if name in UNCHANGED:
             assert nargs == UNCHANGED[name], f"{name} changed its signature"
-    assert _lib.ABI_VERSION == 12 and built_lib.mvg_abi_version() == 12
+    assert _lib.ABI_VERSION == 13 and built_lib.mvg_abi_version() == 13
 
 
 def test_act_scale_ops_wrappers_exist():

@@ -166,7 +166,7 @@ def test_header_row_and_abi():
         want = _lib._P if "*" in a else (_lib._F if a.startswith("float") else _lib._I)
         assert t is want, a
     assert set(re.findall(r"\b(mvg_[a-z0-9_]+)\s*\(", body)) == set(_lib.SIGNATURES)
-    assert _lib.ABI_VERSION == 12 and re.search(r"#define\s+MVG_ABI_VERSION\s+12\b", hdr)
+    assert _lib.ABI_VERSION == 13 and re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr)
     # the record the header declares is the record the host packs: 3 floats, 3 int32, 4 doubles at 24..56
     assert re.search(r"float factor\[3\];.*int32_t order\[3\];.*double a0, cx;.*double a4, cy;", hdr, flags=re.S)
     assert REC_DTYPE.itemsize == 56 and [REC_DTYPE.fields[k][1] for k in ("factor", "order", "a0", "cx", "a4", "cy")] == [0, 12, 24, 32, 40, 48]

@@ -49,8 +49,8 @@ def test_affine_signature_mirrors_the_fp32_one():
 def test_abi_version_in_header_binding_and_library_agree(built_lib):
     from rot_mvgaze_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+12\b", hdr)
-    assert _lib.ABI_VERSION == 12 == built_lib.mvg_abi_version()
+    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr)
+    assert _lib.ABI_VERSION == 13 == built_lib.mvg_abi_version()
 
 
 def test_backbone_switch_and_debug_hook_defaults():

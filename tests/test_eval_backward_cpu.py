@@ -34,7 +34,7 @@ def test_eval_backward_entry_points_declared_exported_and_bound(built_lib):
         assert name in _lib.SIGNATURES, f"{name} is not in _lib.SIGNATURES"
         nargs = len([a for a in decl[name].split(",") if a.strip()])
         assert len(_lib.SIGNATURES[name][1]) == nargs, (name, nargs, len(_lib.SIGNATURES[name][1]))
-    assert _lib.ABI_VERSION == 12
+    assert _lib.ABI_VERSION == 13
 
 
 def test_eval_backward_ops_wrappers_exist():

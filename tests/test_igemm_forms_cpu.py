@@ -44,7 +44,7 @@ def test_plan_queries_are_declared_and_have_signatures():
         res, args = _lib.SIGNATURES[name]
         assert res is _lib._I and len(args) == nargs
         assert hasattr(_lib.lib(), name)
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+12\b", hdr) and _lib.ABI_VERSION == 12 == _lib.lib().mvg_abi_version()
+    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr) and _lib.ABI_VERSION == 13 == _lib.lib().mvg_abi_version()
     # the binding's struct is the header's: seven int32 declarations (15 values) and one int64
     m = re.search(r"typedef struct \{([^}]*)\} mvg_conv_plan;", hdr)
     assert m and len(re.findall(r"\bint32_t\b", m.group(1))) == 7 and len(re.findall(r"\bint64_t\b", m.group(1))) == 1

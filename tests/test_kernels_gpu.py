@@ -623,6 +623,12 @@ def test_bn_finalize_with_and_without_registered_scratch_agree_bit_for_bit(G, P,
     import ctypes as C_
     from rot_mvgaze_amd import ops
     from rot_mvgaze_amd._lib import lib
+    from rot_mvgaze_amd._lib import BN_MERGE_ALL_GROUPS, BN_MERGE_PER_GROUP, BN_MERGE_WALK_GROUPS, BN_PASS_FINALIZE
+    # the two forms this test is about, from the launch's own plan: with the registered scratch / on a stream without any
+    plans = [ops.bn_plan_query(BN_PASS_FINALIZE, 0, G, rows, C, partials=P, scratch_floats=n) for n in (lib().mvg_scratch_bytes() // 4, 0)]
+    assert plans[0]["form"] == (BN_MERGE_WALK_GROUPS if G == 1 else BN_MERGE_ALL_GROUPS if G <= 4 else BN_MERGE_PER_GROUP)
+    assert plans[1]["form"] == (BN_MERGE_ALL_GROUPS if 1 < G <= 4 and P < 1024 else BN_MERGE_WALK_GROUPS)
+    assert (plans[0]["slices"] > 0) == (P >= 1024) and plans[1]["slices"] == 0 and plans[0]["scratch_floats"] <= lib().mvg_scratch_bytes() // 4
     torch.manual_seed(G * P + C)
     stats = torch.randn(G, P, 2, C, device=dev())
     stats[:, :, 1].abs_()                                   # centred sums of squares are non-negative

@@ -75,8 +75,8 @@ class _Session:
 def test_symbols(L):
     from rot_mvgaze_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+12\b", hdr)
-    assert L.mvg_abi_version() == _lib.ABI_VERSION == 12
+    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr)
+    assert L.mvg_abi_version() == _lib.ABI_VERSION == 13
     assert re.search(r"#define\s+MVG_SESSION_FP32\s+0\b", hdr) and re.search(r"#define\s+MVG_SESSION_BF16\s+1\b", hdr)
     assert (_lib.SESSION_FP32, _lib.SESSION_BF16) == (FP32, BF16)
     code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)

@@ -62,8 +62,8 @@ class _Session:
 def test_abi_additions(L):
     from rot_mvgaze_amd import _lib
     hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+12\b", hdr)
-    assert L.mvg_abi_version() == _lib.ABI_VERSION == 12
+    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr)
+    assert L.mvg_abi_version() == _lib.ABI_VERSION == 13
     code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
     for name in SESSION_ENTRY_POINTS:
         m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", code, flags=re.S)

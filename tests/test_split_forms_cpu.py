@@ -34,7 +34,7 @@ def test_plan_queries_are_declared_and_have_signatures():
         res, args = _lib.SIGNATURES[name]
         assert res is _lib._I and len(args) == nargs
         assert hasattr(_lib.lib(), name)
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+12\b", hdr) and _lib.ABI_VERSION == 12
+    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr) and _lib.ABI_VERSION == 13
 
 
 def test_plan_queries_reject_bad_descriptors():
