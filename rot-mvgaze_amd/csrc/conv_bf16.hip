@@ -34,7 +34,8 @@ constexpr int BF_BM = 128, BF_BK = 64, BF_LDK = BF_BK + 8;
 
 // ------------------------------------------------------------------------------------------
 // wgrad: dw[o][tap][c] = sum over pixels of dy[pix][o] * x[pix at tap][c]; M = cout, N = (tap, c),
-// K = pixels split into slabs (fixed-order reduce: wgrad_reduce_kernel).  Both operands arrive
+// K = pixels split into slabs (fixed-order reduce: wgrad_reduce_kernel).  Tile decode, column and pixel addressing and
+// the epilogue are conv_shared.h's (wgrad_tile_id, wgrad_column, WgradPixel, wgrad_store_acc).  Both operands arrive
 // pixel-major (NHWC rows), i.e. k-strided for the MFMA: the LDS images stay pixel-major [k][m] and the
 // fragments are read with the hardware transpose read ds_read_b64_tr_b16 (4 k x 16 m per 16-lane group,
 // cdna_hip_programming.md T10); rows of (BM + 32) * 2 bytes put the four k-rows of a read on disjoint
@@ -61,26 +62,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(WgradParams p) {
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
   const int li = lane & 31, lh = lane >> 5;
-  const int tiles = p.mtiles * p.ntiles;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = logical / tiles;
-  const int tile = logical - split * tiles;
-  const int ntile = tile % p.ntiles, mtile = tile / p.ntiles;
-  const long long m_begin = (long long)split * p.pixels_per_split;
-  long long m_end = m_begin + p.pixels_per_split;
-  if (m_end > p.pixels) m_end = p.pixels;
-  const int m_count = m_end > m_begin ? (int)(m_end - m_begin) : 0;
-  const int ohw = p.ho * p.wo;
-  const long long img0 = m_begin / ohw;
-  const unsigned rem0 = (unsigned)(m_begin - img0 * ohw);
+  const WgradTile t = wgrad_tile_id(p);
 
   const char *dy = reinterpret_cast<const char *>(p.dy);
   const char *x = reinterpret_cast<const char *>(p.x);
-  const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(dy + m_begin * p.cout * EB, (long long)EB * m_count * p.cout);
+  const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(dy + t.m_begin * p.cout * EB, (long long)EB * t.m_count * p.cout);
   const long long x_img_elems = (long long)p.h * p.w * p.cin;
-  const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(x + img0 * x_img_elems * EB, p.x_bytes - (long long)EB * img0 * x_img_elems);
+  const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(x + t.img0 * x_img_elems * EB, p.x_bytes - (long long)EB * t.img0 * x_img_elems);
   const int a_mv = tid % MV, a_k0 = tid / MV;
-  const int a_col = mtile * BM + a_mv * 8;
+  const int a_col = t.mtile * BM + a_mv * 8;
   const bool a_cok = a_col < p.cout;
   unsigned a_off[A_PASSES];
 #pragma unroll
@@ -93,35 +83,15 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(WgradParams p) {
   constexpr int B_CPT = NVB / B_TPR;                    // column groups per thread
   static_assert(NVB % B_TPR == 0 && B_CPT >= 1, "wgrad loader mapping");
   const int i_row = tid / B_TPR, i_nv0 = tid % B_TPR;
-  int i_dy[B_CPT], i_dx[B_CPT];
-  unsigned i_tconst[B_CPT];
-  bool i_cok[B_CPT];
+  WgradColumn i_col[B_CPT];
 #pragma unroll
-  for (int j = 0; j < B_CPT; ++j) {
-    const int col = ntile * BN + (i_nv0 + j * B_TPR) * 8;
-    i_cok[j] = col < p.ncols;
-    const int tap = (int)fdiv((unsigned)(i_cok[j] ? col : 0), p.cin_div);
-    const int cc = (i_cok[j] ? col : 0) - tap * p.cin;
-    const int fr = (int)fdiv((unsigned)tap, p.s_div), fs = tap - fr * p.s;
-    i_dy[j] = fr - p.pad;
-    i_dx[j] = fs - p.pad_w;
-    i_tconst[j] = (unsigned)((i_dy[j] * p.w + i_dx[j]) * p.cin + cc) * EB;
-  }
+  for (int j = 0; j < B_CPT; ++j) i_col[j] = wgrad_column(p, t.ntile * BN + (i_nv0 + j * B_TPR) * 8, EB, p.pad_w);
   const unsigned row_bytes = (unsigned)(p.stride * p.w * p.cin) * EB, col_bytes = (unsigned)(p.stride_w * p.cin) * EB;
   const unsigned img_bytes = (unsigned)x_img_elems * EB;
-  int s_oy = 0, s_ox = 0;
-  unsigned s_imgoff = 0;
-  if (INCR) {
-    const unsigned pix = rem0 + (unsigned)i_row;
-    const unsigned img = fdiv(pix, p.ohw_div);
-    const unsigned rem = pix - img * (unsigned)ohw;
-    const unsigned oy = fdiv(rem, p.wo_div);
-    s_oy = (int)oy;
-    s_ox = (int)(rem - oy * (unsigned)p.wo);
-    s_imgoff = img * img_bytes;
-  }
+  WgradPixel s_px = {0, 0, 0u};
+  if (INCR) s_px.decode(p, t.rem0 + (unsigned)i_row, img_bytes);
   u32x4 a_reg[A_PASSES][AL], b_reg[B_CPT][AL];
-  const bool do_bias = F32IN && (p.db != nullptr) && (ntile == 0);
+  const bool do_bias = F32IN && (p.db != nullptr) && (t.ntile == 0);
   float bsum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
   auto load_tiles = [&](int kt) {
 #pragma unroll
@@ -130,41 +100,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(WgradParams p) {
       if constexpr (F32IN) a_reg[i][1] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, a_off[i] + 16u, 0, 0);
       a_off[i] += (unsigned)(BK * p.cout) * EB;
     }
-    const bool mok = kt * BK + i_row < m_count;
-    int oy, ox;
-    unsigned imgoff;
-    if constexpr (INCR) {
-      oy = s_oy;
-      ox = s_ox;
-      imgoff = s_imgoff;
-    } else {
-      const unsigned pix = rem0 + (unsigned)(kt * BK + i_row);
-      const unsigned img = fdiv(pix, p.ohw_div);
-      const unsigned rem = pix - img * (unsigned)ohw;
-      const unsigned uy = fdiv(rem, p.wo_div);
-      oy = (int)uy;
-      ox = (int)(rem - uy * (unsigned)p.wo);
-      imgoff = img * img_bytes;
-    }
-    const int iy0 = oy * p.stride, ix0 = ox * p.stride_w;
-    const unsigned pixoff = imgoff + (unsigned)oy * row_bytes + (unsigned)ox * col_bytes;
+    const bool mok = kt * BK + i_row < t.m_count;
+    WgradPixel px = s_px;
+    if constexpr (!INCR) px.decode(p, t.rem0 + (unsigned)(kt * BK + i_row), img_bytes);
+    const int iy0 = px.oy * p.stride, ix0 = px.ox * p.stride_w;
+    const unsigned pixoff = px.imgoff + (unsigned)px.oy * row_bytes + (unsigned)px.ox * col_bytes;
 #pragma unroll
     for (int j = 0; j < B_CPT; ++j) {
-      const bool ok = mok & i_cok[j] & ((unsigned)(iy0 + i_dy[j]) < (unsigned)p.h) & ((unsigned)(ix0 + i_dx[j]) < (unsigned)p.w);
-      b_reg[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, pred_off(pixoff + i_tconst[j], ok), 0, 0);
-      if constexpr (F32IN) b_reg[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, pred_off(pixoff + i_tconst[j] + 16u, ok), 0, 0);
+      const WgradColumn &c = i_col[j];
+      const bool ok = mok & c.cok & ((unsigned)(iy0 + c.dy) < (unsigned)p.h) & ((unsigned)(ix0 + c.dx) < (unsigned)p.w);
+      b_reg[j][0] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, pred_off(pixoff + c.tconst, ok), 0, 0);
+      if constexpr (F32IN) b_reg[j][1] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, pred_off(pixoff + c.tconst + 16u, ok), 0, 0);
     }
-    if constexpr (INCR) {
-      // advance BK pixels: columns wrap into rows, rows into the next image (at most once: ho*wo >= 2*BK)
-      unsigned nx = (unsigned)s_ox + BK;
-      const unsigned q = fdiv(nx, p.wo_div);
-      nx -= q * (unsigned)p.wo;
-      s_ox = (int)nx;
-      const int noy = s_oy + (int)q;
-      const bool wrap = noy >= p.ho;
-      s_oy = wrap ? noy - p.ho : noy;
-      s_imgoff += wrap ? img_bytes : 0u;
-    }
+    if constexpr (INCR) s_px.template advance<BK>(p, img_bytes);
   };
   auto to_bf16 = [&](const u32x4 (&r)[AL]) -> u32x4 {
     if constexpr (!F32IN) return r[0];
@@ -203,7 +151,7 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(WgradParams p) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-  const int KT = (m_count + BK - 1) / BK;
+  const int KT = (t.m_count + BK - 1) / BK;
   load_tiles(0);
   store_tiles(0);
   load_tiles(1);
@@ -236,35 +184,19 @@ __global__ __launch_bounds__(256, 2) void wgrad_bf16_kernel(WgradParams p) {
       for (int k = 0; k < 8; ++k) sh[tid * 8 + k] = bsum[k];
       __syncthreads();
       if (a_k0 == 0 && a_cok) {
-        float t[8];
+        float s[8];
 #pragma unroll
-        for (int k = 0; k < 8; ++k) t[k] = sh[a_mv * 8 + k];
+        for (int k = 0; k < 8; ++k) s[k] = sh[a_mv * 8 + k];
         for (int r = 1; r < A_KRPP; ++r)
 #pragma unroll
-          for (int k = 0; k < 8; ++k) t[k] += sh[(r * MV + a_mv) * 8 + k];
-        float *dst = p.db + (long long)split * p.cout + a_col;
+          for (int k = 0; k < 8; ++k) s[k] += sh[(r * MV + a_mv) * 8 + k];
+        float *dst = p.db + (long long)t.split * p.cout + a_col;
 #pragma unroll
-        for (int k = 0; k < 8; ++k) dst[k] = (p.accumulate ? dst[k] : 0.f) + t[k];
+        for (int k = 0; k < 8; ++k) dst[k] = (p.accumulate ? dst[k] : 0.f) + s[k];
       }
     }
   }
-  float *out = p.out + (long long)split * p.cout * p.ncols;
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = ntile * BN + wn * WTN + j * 32 + li;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = mtile * BM + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-        if (row < p.cout && col < p.ncols) {
-          const long long off = (long long)row * p.ncols + col;
-          float v = acc[i][j][e];
-          if (p.accumulate) v += out[off];
-          out[off] = v;
-        }
-      }
-    }
+  wgrad_store_acc(p, acc, p.out + (long long)t.split * p.cout * p.ncols, t.mtile * BM + wm * WTM, t.ntile * BN + wn * WTN, li, lh, 1.f);
 }
 
 // The stem's folded row-window operand (mvg_stem_fprop_bf16): window m of an image row holds image columns 4 m - 4 ..
@@ -583,13 +515,17 @@ static void wgrad_bf16_tile(const mvg_conv_desc *d, int &bm, int &bn) {
   bn = ncols >= 128 ? 128 : 64;
 }
 
-int mvg_conv_wgrad_splits_bf16(const mvg_conv_desc *d) {
-  if (validate_bf16(d)) return -1;
+// The pixel splits of a checked descriptor (the stem's folded one included) at its tile.
+static int wgrad_bf16_splits(const mvg_conv_desc *d) {
   int bm, bn;
   wgrad_bf16_tile(d, bm, bn);
-  const long long tiles = (long long)ceil_div(d->cout, bm) * ceil_div(d->r * d->s * d->cin, bn);
   // one resident round at two workgroups per CU, at least 512 pixels (8 K-steps) per split
-  return wgrad_split_count(tiles, (long long)d->groups * d->n * d->ho * d->wo, 2, 512);
+  return wgrad_split_count(wgrad_tiles(d, bm, bn), (long long)d->groups * d->n * d->ho * d->wo, 2, 512);
+}
+
+int mvg_conv_wgrad_splits_bf16(const mvg_conv_desc *d) {
+  if (validate_bf16(d)) return -1;
+  return wgrad_bf16_splits(d);
 }
 
 static int wgrad_bf16_impl(const mvg_conv_desc *d, const void *x, const void *dy, float *dw, float *db, float *workspace,
@@ -600,36 +536,29 @@ static int wgrad_bf16_impl(const mvg_conv_desc *d, const void *x, const void *dy
   memset(&p, 0, sizeof(p));
   p.x = (const float *)x;
   p.dy = (const float *)dy;
-  if (wgrad_geometry(p, d, f32in ? 4 : 2, 64, dw, db, workspace, splits, accumulate, "wgrad_bf16", stride_w, pad_w)) return 2;
   int bm, bn;
   wgrad_bf16_tile(d, bm, bn);
-  p.mtiles = ceil_div(d->cout, bm);
-  p.ntiles = ceil_div(p.ncols, bn);
-  hipStream_t st = (hipStream_t)stream;
-  const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
-  {
-    const double acin = d->cin == 8 && d->r == 7 ? 3.0 : (double)d->cin;
-    const double flops = 2.0 * (double)p.pixels * d->cout * d->r * d->s * acin * (stride_w >= 0 ? 147.0 / 448.0 : 1.0);
-    const double bytes = 2.0 * ((double)d->groups * d->n * d->h * d->w * acin + (double)p.pixels * d->cout) +
-                         4.0 * (double)d->cout * d->r * d->s * acin;
-    ProfScope ps(lin ? MVG_K_LINEAR_WGRAD : MVG_K_CONV_WGRAD, st, flops, bytes);
-    MVG_REQUIRE((long long)p.mtiles * p.ntiles * splits < (1LL << 31), "wgrad_bf16: grid too large");
-    dim3 grid(p.mtiles * p.ntiles * splits), block(256);
-    const bool incr = (long long)d->ho * d->wo >= 128;       // at most one image wrap per 64-pixel step
+  const double pixels = (double)d->groups * d->n * d->ho * d->wo;
+  const double acin = d->cin == 8 && d->r == 7 ? 3.0 : (double)d->cin;
+  const double flops = 2.0 * pixels * d->cout * d->r * d->s * acin * (stride_w >= 0 ? 147.0 / 448.0 : 1.0);
+  const double bytes = 2.0 * ((double)d->groups * d->n * d->h * d->w * acin + pixels * d->cout) + 4.0 * (double)d->cout * d->r * d->s * acin;
+  const bool incr = (long long)d->ho * d->wo >= 128;       // at most one image wrap per 64-pixel step
+  const auto dispatch = [&](dim3 grid, dim3 block, hipStream_t st, const WgradParams &wp) {
 #define MVG_WGRAD_BF16(BM_, BN_)                                                                          \
   do {                                                                                                    \
-    if (f32in) hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, false, true>), grid, block, 0, st, p);     \
-    else if (incr) hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, true>), grid, block, 0, st, p);        \
-    else hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, false>), grid, block, 0, st, p);                 \
+    if (f32in) hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, false, true>), grid, block, 0, st, wp);     \
+    else if (incr) hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, true>), grid, block, 0, st, wp);        \
+    else hipLaunchKernelGGL((wgrad_bf16_kernel<BM_, BN_, false>), grid, block, 0, st, wp);                 \
   } while (0)
     if (bm == 128 && bn == 128) MVG_WGRAD_BF16(128, 128);
     else if (bm == 64 && bn == 128) MVG_WGRAD_BF16(64, 128);
     else if (bm == 128 && bn == 64) MVG_WGRAD_BF16(128, 64);
     else MVG_WGRAD_BF16(64, 64);
 #undef MVG_WGRAD_BF16
-    if (check_launch("conv_wgrad_bf16")) return 1;
-  }
-  return splits > 1 && !slabs_only ? wgrad_reduce_slabs(p, workspace, dw, db, splits, accumulate, st, "wgrad_bf16") : 0;
+    return 0;
+  };
+  return wgrad_launch(p, d, f32in ? 4 : 2, 64, bm, bn, dw, db, workspace, splits, accumulate, slabs_only, (hipStream_t)stream, flops, bytes,
+                      "wgrad_bf16", "conv_wgrad_bf16", stride_w, pad_w, dispatch);
 }
 
 int mvg_conv_wgrad_bf16(const mvg_conv_desc *d, const void *x, const void *dy, float *dw, float *workspace, int splits,
@@ -645,8 +574,9 @@ int mvg_conv_wgrad_bf16_slabs(const mvg_conv_desc *d, const void *x, const void 
 int mvg_stem_wgrad_splits_bf16(const mvg_conv_desc *d) {
   mvg_conv_desc rw;
   if (stem_fold_desc(d, &rw)) return -1;
-  const long long tiles = (long long)ceil_div(rw.cout, 128) * ceil_div(7 * 64, 128);
-  return wgrad_split_count(tiles, (long long)rw.groups * rw.n * rw.ho * rw.wo, 2, 512);
+  // the folded descriptor's own tile, as wgrad_bf16_impl launches it: 7 x 64 columns -> bn = 128; cout a multiple of 32 ->
+  // rw.cout a multiple of 64, and the 64-row tile (rw.cout == 64 only) makes one row tile just as a 128-row tile would
+  return wgrad_bf16_splits(&rw);
 }
 
 int mvg_stem_wgrad_bf16(const mvg_conv_desc *d, const void *xw, const void *dy, float *dw_fold, float *workspace, int splits,

@@ -683,6 +683,8 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const float4 *__rest
 // wgrad
 // ------------------------------------------------------------------------------------------
 
+// Tile decode, column and pixel addressing and the predicated epilogue are conv_shared.h's (wgrad_tile_id, wgrad_column,
+// WgradPixel, wgrad_store_acc), shared with the split and bf16 kernels.
 // INCR (host: ho*wo >= 32, every product below fits 24 x 24 bits): the pixel coordinates of a loader
 // row advance by exactly BK pixels per K-step, so (image offset, oy, ox) are carried in registers and
 // stepped with one multiply-shift division instead of being decoded from the pixel index every time
@@ -706,40 +708,22 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
   const int li = lane & 31, lh = lane >> 5;
-  // 1-D grid, XCD-aware: workgroups round-robin over the 8 XCDs, so the bijective remap hands every
-  // XCD a contiguous run of (split, tile) ids.  All tiles of a split (the same pixel range of dy and
-  // x) then run on ONE XCD at about the same time and share its L2 - spread over the XCDs, every
-  // tile re-read its operands from memory (16x the algorithmic bytes on the 256-channel layers).
-  const int tiles = p.mtiles * p.ntiles;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = logical / tiles;
-  const int tile = logical - split * tiles;
-  const int ntile = tile % p.ntiles, mtile = tile / p.ntiles;
-  const long long m_begin = (long long)split * p.pixels_per_split;
-  long long m_end = m_begin + p.pixels_per_split;
-  if (m_end > p.pixels) m_end = p.pixels;
-  const int m_count = m_end > m_begin ? (int)(m_end - m_begin) : 0;       // pixels of this split
-  const int ohw = p.ho * p.wo;
-  const long long img0 = m_begin / ohw;                                    // scalar, once
-  const unsigned rem0 = (unsigned)(m_begin - img0 * ohw);
+  const WgradTile t = wgrad_tile_id(p);
 
   // A: dy rows of this split, contiguous along cout.  B: x gathered per (pixel, tap); this thread's
   // column (tap, c) is fixed for the whole K loop.
-  const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(p.dy + m_begin * p.cout, 4ll * m_count * p.cout);
+  const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(p.dy + t.m_begin * p.cout, 4ll * t.m_count * p.cout);
   const long long x_img_elems = (long long)p.h * p.w * p.cin;
-  const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(p.x + img0 * x_img_elems, p.x_bytes - 4ll * img0 * x_img_elems);
+  const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(p.x + t.img0 * x_img_elems, p.x_bytes - 4ll * t.img0 * x_img_elems);
   const __amdgpu_buffer_rsrc_t rs_xi = XMODE == 1 ? make_rsrc(p.x, p.rc_img_bytes) : rs_b;
   const __amdgpu_buffer_rsrc_t rs_xf = XMODE == 1 ? make_rsrc(p.rc_feat, p.rc_feat_bytes) : rs_b;
   const int a_mv = tid % MV, a_k0 = tid / MV;
-  const int a_col = mtile * BM + a_mv * 4;
+  const int a_col = t.mtile * BM + a_mv * 4;
   const bool a_cok = a_col < p.cout;
   const int b_nv = tid % NVB, b_k0 = tid / NVB;
-  const int b_col = ntile * BN + b_nv * 4;
-  const bool b_cok = b_col < p.ncols;
-  const int b_tap = (int)fdiv((unsigned)(b_cok ? b_col : 0), p.cin_div);
-  const int b_c = (b_cok ? b_col : 0) - b_tap * p.cin;
-  const int b_fr = (int)fdiv((unsigned)b_tap, p.s_div), b_fs = b_tap - b_fr * p.s;
-  const int b_dy = b_fr - p.pad, b_dx = b_fs - p.pad;
+  const int b_col = t.ntile * BN + b_nv * 4;
+  int b_c;
+  const WgradColumn b_cd = wgrad_column(p, b_col, 4u, p.pad, &b_c);
 
   // INCR: a thread's B loads all come from ONE pixel row of the K-step (row = tid / (NVB / B_PASSES)) and
   // differ in the column group, so the pixel state (oy, ox, image offset) is carried and stepped once per
@@ -747,32 +731,15 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
   constexpr int B_TPR = NVB / B_PASSES;                 // threads per k-row
   static_assert(!INCR || NVB % B_PASSES == 0, "wgrad loader mapping");
   const int i_row = tid / B_TPR, i_nv0 = tid % B_TPR;
-  int s_oy = 0, s_ox = 0;
-  unsigned s_imgoff = 0, a_off[A_PASSES];
-  int i_dy[B_PASSES], i_dx[B_PASSES];
-  unsigned i_tconst[B_PASSES];
-  bool i_cok[B_PASSES];
+  WgradPixel s_px = {0, 0, 0u};
+  unsigned a_off[A_PASSES];
+  WgradColumn i_col[B_PASSES];
   const unsigned row_bytes = (unsigned)(p.stride * p.w * p.cin * 4), col_bytes = (unsigned)(p.stride * p.cin * 4);
   const unsigned img_bytes = (unsigned)(x_img_elems * 4);
   if (INCR) {
-    const unsigned pix = rem0 + (unsigned)i_row;
-    const unsigned img = fdiv(pix, p.ohw_div);
-    const unsigned rem = pix - img * (unsigned)ohw;
-    const unsigned oy = fdiv(rem, p.wo_div);
-    s_oy = (int)oy;
-    s_ox = (int)(rem - oy * (unsigned)p.wo);
-    s_imgoff = img * img_bytes;
+    s_px.decode(p, t.rem0 + (unsigned)i_row, img_bytes);
 #pragma unroll
-    for (int j = 0; j < B_PASSES; ++j) {
-      const int col = ntile * BN + (i_nv0 + j * B_TPR) * 4;
-      i_cok[j] = col < p.ncols;
-      const int tap = (int)fdiv((unsigned)(i_cok[j] ? col : 0), p.cin_div);
-      const int cc = (i_cok[j] ? col : 0) - tap * p.cin;
-      const int fr = (int)fdiv((unsigned)tap, p.s_div), fs = tap - fr * p.s;
-      i_dy[j] = fr - p.pad;
-      i_dx[j] = fs - p.pad;
-      i_tconst[j] = (unsigned)(((i_dy[j] * p.w + i_dx[j]) * p.cin + cc) * 4);
-    }
+    for (int j = 0; j < B_PASSES; ++j) i_col[j] = wgrad_column(p, t.ntile * BN + (i_nv0 + j * B_TPR) * 4, 4u, p.pad);
 #pragma unroll
     for (int i = 0; i < A_PASSES; ++i)
       a_off[i] = a_cok ? (unsigned)((a_k0 + i * A_KRPP) * p.cout + a_col) * 4u : 0x80000000u;
@@ -786,16 +753,17 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
         a_reg[i] = buf_ld16(rs_a, a_off[i]);                 // rows >= m_count are beyond the descriptor: zeros
         a_off[i] += (unsigned)(BK * p.cout * 4);
       }
-      const bool mok = (kt * BK + i_row < m_count) & (i_row < BK);
-      const int iy0 = s_oy * p.stride, ix0 = s_ox * p.stride;
-      const unsigned pixoff = s_imgoff + __umul24((unsigned)s_oy, row_bytes) + __umul24((unsigned)s_ox, col_bytes);
+      const bool mok = (kt * BK + i_row < t.m_count) & (i_row < BK);
+      const int iy0 = s_px.oy * p.stride, ix0 = s_px.ox * p.stride;
+      const unsigned pixoff = s_px.imgoff + __umul24((unsigned)s_px.oy, row_bytes) + __umul24((unsigned)s_px.ox, col_bytes);
 #pragma unroll
       for (int j = 0; j < B_PASSES; ++j) {
-        const bool ok = mok & i_cok[j] & ((unsigned)(iy0 + i_dy[j]) < (unsigned)p.h) & ((unsigned)(ix0 + i_dx[j]) < (unsigned)p.w);
-        b_reg[j] = buf_ld16(rs_b, pred_off(pixoff + i_tconst[j], ok));
+        const WgradColumn &c = i_col[j];
+        const bool ok = mok & c.cok & ((unsigned)(iy0 + c.dy) < (unsigned)p.h) & ((unsigned)(ix0 + c.dx) < (unsigned)p.w);
+        b_reg[j] = buf_ld16(rs_b, pred_off(pixoff + c.tconst, ok));
       }
-      // advance BK pixels: columns wrap into rows, rows into the next image (at most once: ho*wo >= 2*BK)
-      unsigned nx = (unsigned)s_ox + BK;
+      // WgradPixel::advance<BK> with a fast path of this kernel's own
+      unsigned nx = (unsigned)s_px.ox + BK;
       unsigned q;
       if (p.wo >= BK) {                                      // uniform: at most one row wrap
         q = nx >= (unsigned)p.wo ? 1u : 0u;
@@ -804,17 +772,17 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
         q = fdiv(nx, p.wo_div);
         nx -= q * (unsigned)p.wo;
       }
-      s_ox = (int)nx;
-      const int noy = s_oy + (int)q;
+      s_px.ox = (int)nx;
+      const int noy = s_px.oy + (int)q;
       const bool wrap = noy >= p.ho;
-      s_oy = wrap ? noy - p.ho : noy;
-      s_imgoff += wrap ? img_bytes : 0u;
+      s_px.oy = wrap ? noy - p.ho : noy;
+      s_px.imgoff += wrap ? img_bytes : 0u;
       return;
     }
 #pragma unroll
     for (int i = 0; i < A_PASSES; ++i) {
       const int m = kt * BK + a_k0 + i * A_KRPP;
-      a_reg[i] = buf_ld16(rs_a, pred_off((unsigned)(m * p.cout + a_col) * 4u, (m < m_count) & a_cok));
+      a_reg[i] = buf_ld16(rs_a, pred_off((unsigned)(m * p.cout + a_col) * 4u, (m < t.m_count) & a_cok));
     }
     if constexpr (XMODE == 1) {
       const bool is_img = b_col < p.rc_cf;                       // uniform over the workgroup: cf is a multiple of BN
@@ -824,8 +792,8 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
 #pragma unroll
       for (int i = 0; i < B_PASSES; ++i) {
         const int m = kt * BK + b_k0 + i * B_KRPP;
-        const bool ok = (m < m_count) & b_cok;
-        const long long row = ok ? m_begin + m : 0;
+        const bool ok = (m < t.m_count) & b_cd.cok;
+        const long long row = ok ? t.m_begin + m : 0;
         if (is_img) {
           b_reg[i] = buf_ld16(rs_xi, pred_off(((unsigned)p.rc_row_img[row] * (unsigned)p.rc_cf + (unsigned)b_col) * 4u, ok));
         } else {
@@ -849,19 +817,16 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
 #pragma unroll
     for (int i = 0; i < B_PASSES; ++i) {
       const int m = kt * BK + b_k0 + i * B_KRPP;
-      const unsigned pix = rem0 + (unsigned)m;
-      const unsigned img = fdiv(pix, p.ohw_div);
-      const unsigned rem = pix - img * (unsigned)ohw;
-      const unsigned oy = fdiv(rem, p.wo_div);
-      const unsigned ox = rem - oy * (unsigned)p.wo;
-      const int iy = (int)oy * p.stride + b_dy, ix = (int)ox * p.stride + b_dx;
-      const bool ok = (m < m_count) & b_cok & ((unsigned)iy < (unsigned)p.h) & ((unsigned)ix < (unsigned)p.w);
-      b_reg[i] = buf_ld16(rs_b, pred_off((unsigned)(((img * p.h + iy) * p.w + ix) * p.cin + b_c) * 4u, ok));
+      WgradPixel px;
+      px.decode(p, t.rem0 + (unsigned)m, 1u);                      // one "byte" per image: imgoff counts images
+      const int iy = px.oy * p.stride + b_cd.dy, ix = px.ox * p.stride + b_cd.dx;
+      const bool ok = (m < t.m_count) & b_cd.cok & ((unsigned)iy < (unsigned)p.h) & ((unsigned)ix < (unsigned)p.w);
+      b_reg[i] = buf_ld16(rs_b, pred_off((unsigned)(((px.imgoff * p.h + iy) * p.w + ix) * p.cin + b_c) * 4u, ok));
     }
   };
   // Linear layers: the bias gradient is the column sum of dy, and this kernel streams dy anyway: the
   // workgroups of the first column tile add up what they load (each K-step's rows exactly once, in order)
-  const bool do_bias = (p.db != nullptr) & (ntile == 0);
+  const bool do_bias = (p.db != nullptr) & (t.ntile == 0);
   float4 bsum = make_float4(0.f, 0.f, 0.f, 0.f);
   auto store_tiles = [&](int buf) {
     float *As = smem + buf * (A_ELEMS + B_ELEMS);
@@ -897,7 +862,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-  const int KT = (m_count + BK - 1) / BK;
+  const int KT = (t.m_count + BK - 1) / BK;
   load_tiles(0);
   store_tiles(0);
   load_tiles(1);
@@ -938,35 +903,35 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
     sh[tid] = bsum;
     __syncthreads();
     if (a_k0 == 0 && a_cok) {
-      float4 t = sh[a_mv];
+      float4 s = sh[a_mv];
       for (int k = 1; k < A_KRPP; ++k) {
         const float4 v = sh[k * MV + a_mv];
-        t.x += v.x;
-        t.y += v.y;
-        t.z += v.z;
-        t.w += v.w;
+        s.x += v.x;
+        s.y += v.y;
+        s.z += v.z;
+        s.w += v.w;
       }
-      float4 *dst = reinterpret_cast<float4 *>(p.db + (long long)split * p.cout + a_col);
+      float4 *dst = reinterpret_cast<float4 *>(p.db + (long long)t.split * p.cout + a_col);
       if (p.accumulate) {
         const float4 o = *dst;
-        t.x += o.x;
-        t.y += o.y;
-        t.z += o.z;
-        t.w += o.w;
+        s.x += o.x;
+        s.y += o.y;
+        s.z += o.z;
+        s.w += o.w;
       }
-      *dst = t;
+      *dst = s;
     }
   }
-  float *out = p.out + (long long)split * p.cout * p.ncols;
+  float *out = p.out + (long long)t.split * p.cout * p.ncols;
   // fast path (wave-uniform): the wave's block lies inside dw - no predicates, 32-bit offsets
-  if (mtile * BM + wm * WTM + WTM <= p.cout && ntile * BN + wn * WTN + WTN <= p.ncols &&
+  if (t.mtile * BM + wm * WTM + WTM <= p.cout && t.ntile * BN + wn * WTN + WTN <= p.ncols &&
       (long long)p.cout * p.ncols < (1ll << 30)) {
-    float *out_t = out + (long long)(mtile * BM + wm * WTM) * p.ncols;
+    float *out_t = out + (long long)(t.mtile * BM + wm * WTM) * p.ncols;
 #pragma unroll
     for (int i = 0; i < TM; ++i)
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
-        const unsigned lane_off = (unsigned)(i * 32 + 4 * lh) * (unsigned)p.ncols + (unsigned)(ntile * BN + wn * WTN + j * 32 + li);
+        const unsigned lane_off = (unsigned)(i * 32 + 4 * lh) * (unsigned)p.ncols + (unsigned)(t.ntile * BN + wn * WTN + j * 32 + li);
 #pragma unroll
         for (int e = 0; e < 16; ++e) {
           const unsigned off = (unsigned)((e & 3) + 8 * (e >> 2)) * (unsigned)p.ncols + lane_off;
@@ -977,22 +942,7 @@ __global__ __launch_bounds__(256) void wgrad_kernel(WgradParams p) {
       }
     return;
   }
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = ntile * BN + wn * WTN + j * 32 + li;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = mtile * BM + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-        if (row < p.cout && col < p.ncols) {
-          const long long off = (long long)row * p.ncols + col;
-          float v = acc[i][j][e];
-          if (p.accumulate) v += out[off];
-          out[off] = v;
-        }
-      }
-    }
+  wgrad_store_acc(p, acc, out, t.mtile * BM + wm * WTM, t.ntile * BN + wn * WTN, li, lh, 1.f);
 }
 
 // ------------------------------------------------------------------------------------------
@@ -1440,9 +1390,8 @@ extern "C" {
 int mvg_conv_wgrad_splits(const mvg_conv_desc *d) {
   if (validate(d)) return -1;
   const TileChoice t = wgrad_tile(d);
-  const long long tiles = (long long)ceil_div(d->cout, t.bm) * ceil_div(d->r * d->s * d->cin, t.bn);
   const int wpc = wgrad_occupancy(t);
-  return wgrad_split_count(tiles, (long long)d->groups * d->n * d->ho * d->wo, wpc > 4 ? 4 : wpc, 256);   // 16 K-steps per split
+  return wgrad_split_count(wgrad_tiles(d, t.bm, t.bn), (long long)d->groups * d->n * d->ho * d->wo, wpc > 4 ? 4 : wpc, 256);   // 16 K-steps per split
 }
 
 int mvg_conv_wgrad_tile(const mvg_conv_desc *d, int32_t *bm, int32_t *bn, int32_t *incremental) {
@@ -1462,10 +1411,7 @@ static int wgrad_impl(const mvg_conv_desc *d, const float *x, const float *dy, f
   memset(&p, 0, sizeof(p));
   p.x = x;
   p.dy = dy;
-  if (wgrad_geometry(p, d, 4, 16, dw, db, workspace, splits, accumulate, "wgrad")) return 2;
   const TileChoice t = wgrad_tile(d);
-  p.mtiles = ceil_div(d->cout, t.bm);
-  p.ntiles = ceil_div(p.ncols, t.bn);
   if (rc) {
     p.rc_feat = rc->feat;
     p.rc_rel = rc->rel;
@@ -1476,34 +1422,30 @@ static int wgrad_impl(const mvg_conv_desc *d, const float *x, const float *dy, f
     p.rc_img_bytes = 4ll * rc->img_rows * rc->cf;
     p.rc_feat_bytes = 4ll * rc->feat_rows * 3 * rc->nvec;
   }
-  hipStream_t st = (hipStream_t)stream;
-  const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
-  {
-    const double flops = 2.0 * (double)p.pixels * d->cout * d->r * d->s * alg_cin(d);
-    const double bytes = 4.0 * ((double)d->groups * d->n * d->h * d->w * alg_cin(d) + (double)p.pixels * d->cout +
-                                (double)d->cout * d->r * d->s * alg_cin(d));
-    ProfScope ps(lin ? MVG_K_LINEAR_WGRAD : MVG_K_CONV_WGRAD, st, flops, bytes);
-    MVG_REQUIRE((long long)p.mtiles * p.ntiles * splits < (1LL << 31), "wgrad: grid too large");
-    dim3 grid(p.mtiles * p.ntiles * splits), block(256);
-    const bool incr = wgrad_incremental(d);
+  const double pixels = (double)d->groups * d->n * d->ho * d->wo;
+  const double flops = 2.0 * pixels * d->cout * d->r * d->s * alg_cin(d);
+  const double bytes = 4.0 * ((double)d->groups * d->n * d->h * d->w * alg_cin(d) + pixels * d->cout + (double)d->cout * d->r * d->s * alg_cin(d));
+  const bool incr = wgrad_incremental(d);
+  const auto dispatch = [&](dim3 grid, dim3 block, hipStream_t st, const WgradParams &wp) {
 #define MVG_WGRAD_LAUNCH(BM_, BN_, WGM_, WGN_)                                                              \
   do {                                                                                                      \
-    if (incr) hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, 16, WGM_, WGN_, true>), grid, block, 0, st, p);    \
-    else hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, 16, WGM_, WGN_, false>), grid, block, 0, st, p);        \
+    if (incr) hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, 16, WGM_, WGN_, true>), grid, block, 0, st, wp);    \
+    else hipLaunchKernelGGL((wgrad_kernel<BM_, BN_, 16, WGM_, WGN_, false>), grid, block, 0, st, wp);        \
   } while (0)
     if (rc) {
       MVG_REQUIRE(t.bn == 128 && (t.bm == 128 || t.bm == 64), "fuser wgrad: shape not covered by the generated-input loader");
-      if (t.bm == 128) hipLaunchKernelGGL((wgrad_kernel<128, 128, 16, 2, 2, false, 1>), grid, block, 0, st, p);
-      else hipLaunchKernelGGL((wgrad_kernel<64, 128, 16, 2, 2, false, 1>), grid, block, 0, st, p);
+      if (t.bm == 128) hipLaunchKernelGGL((wgrad_kernel<128, 128, 16, 2, 2, false, 1>), grid, block, 0, st, wp);
+      else hipLaunchKernelGGL((wgrad_kernel<64, 128, 16, 2, 2, false, 1>), grid, block, 0, st, wp);
     } else if (t.bm == 128 && t.bn == 128) MVG_WGRAD_LAUNCH(128, 128, 2, 2);
     else if (t.bm == 64 && t.bn == 128) MVG_WGRAD_LAUNCH(64, 128, 2, 2);
     else if (t.bm == 64 && t.bn == 64) MVG_WGRAD_LAUNCH(64, 64, 2, 2);
     else if (t.bm == 32 && t.bn == 128) MVG_WGRAD_LAUNCH(32, 128, 1, 4);
     else MVG_WGRAD_LAUNCH(128, 32, 4, 1);
 #undef MVG_WGRAD_LAUNCH
-    if (check_launch("conv_wgrad")) return 1;
-  }
-  return splits > 1 ? wgrad_reduce_slabs(p, workspace, dw, db, splits, accumulate, st, "wgrad") : 0;
+    return 0;
+  };
+  return wgrad_launch(p, d, 4, 16, t.bm, t.bn, dw, db, workspace, splits, accumulate, false, (hipStream_t)stream, flops, bytes, "wgrad", "conv_wgrad", -1,
+                      -1, dispatch);
 }
 
 int mvg_conv_wgrad(const mvg_conv_desc *d, const float *x, const float *dy, float *dw, float *workspace, int splits,

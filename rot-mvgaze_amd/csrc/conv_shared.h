@@ -216,20 +216,134 @@ struct WgradParams {
   int stride_w, pad_w;            // split kernels: horizontal stride / padding (see IgemmParams)
 };
 
+// ---- what the three weight-gradient kernels (wgrad_kernel, wgrad_split_kernel, wgrad_bf16_kernel) do alike ----------------
+// The kernels keep what differs on purpose: loader thread mappings, LDS images, fragments, the MFMA step and the K loop.
+
+// A workgroup's (pixel split, row tile, column tile) and its split's pixels: m_count of them from m_begin on, the first one
+// pixel rem0 of image img0.
+// 1-D grid, XCD-aware: workgroups round-robin over the 8 XCDs, so the bijective remap hands every
+// XCD a contiguous run of (split, tile) ids.  All tiles of a split (the same pixel range of dy and
+// x) then run on ONE XCD at about the same time and share its L2 - spread over the XCDs, every
+// tile re-read its operands from memory (16x the algorithmic bytes on the 256-channel layers).
+struct WgradTile {
+  int split, mtile, ntile;
+  long long m_begin, img0;
+  int m_count;
+  unsigned rem0;
+};
+__device__ __forceinline__ WgradTile wgrad_tile_id(const WgradParams &p) {
+  WgradTile t;
+  const int tiles = p.mtiles * p.ntiles;
+  const int logical = xcd_remap(blockIdx.x, gridDim.x);
+  t.split = logical / tiles;
+  const int tile = logical - t.split * tiles;
+  t.ntile = tile % p.ntiles;
+  t.mtile = tile / p.ntiles;
+  t.m_begin = (long long)t.split * p.pixels_per_split;
+  long long m_end = t.m_begin + p.pixels_per_split;
+  if (m_end > p.pixels) m_end = p.pixels;
+  t.m_count = m_end > t.m_begin ? (int)(m_end - t.m_begin) : 0;
+  const int ohw = p.ho * p.wo;
+  t.img0 = t.m_begin / ohw;                                                // scalar, once
+  t.rem0 = (unsigned)(t.m_begin - t.img0 * ohw);
+  return t;
+}
+
+// Column col = (tap, channel) of the x operand: whether it exists, the tap's displacement (dy, dx) from a pixel's window
+// origin and its byte offset from that origin's first channel; elem bytes per element, pad_w the horizontal padding.
+// channel (optional): receives the column's channel inside its tap.
+struct WgradColumn {
+  bool cok;
+  int dy, dx;
+  unsigned tconst;
+};
+__device__ __forceinline__ WgradColumn wgrad_column(const WgradParams &p, int col, unsigned elem, int pad_w, int *channel = nullptr) {
+  WgradColumn c;
+  c.cok = col < p.ncols;
+  const int tap = (int)fdiv((unsigned)(c.cok ? col : 0), p.cin_div);
+  const int cc = (c.cok ? col : 0) - tap * p.cin;
+  if (channel) *channel = cc;
+  const int fr = (int)fdiv((unsigned)tap, p.s_div), fs = tap - fr * p.s;
+  c.dy = fr - p.pad;
+  c.dx = fs - pad_w;
+  c.tconst = (unsigned)((c.dy * p.w + c.dx) * p.cin + cc) * elem;
+  return c;
+}
+
+// An output pixel of the split as the x loaders address it: (oy, ox) and the byte offset of its image from the split's
+// first (img_bytes per image).  decode() from the pixel's index counted from that first image's pixel 0; advance<BK>()
+// steps BK pixels on: columns wrap into rows, rows into the next image (at most once: the hosts ask for ho*wo >= 2*BK).
+struct WgradPixel {
+  int oy, ox;
+  unsigned imgoff;
+  __device__ __forceinline__ void decode(const WgradParams &p, unsigned pix, unsigned img_bytes) {
+    const unsigned img = fdiv(pix, p.ohw_div);
+    const unsigned rem = pix - img * (unsigned)(p.ho * p.wo);
+    const unsigned uy = fdiv(rem, p.wo_div);
+    oy = (int)uy;
+    ox = (int)(rem - uy * (unsigned)p.wo);
+    imgoff = img * img_bytes;
+  }
+  template <int BK>
+  __device__ __forceinline__ void advance(const WgradParams &p, unsigned img_bytes) {
+    unsigned nx = (unsigned)ox + BK;
+    const unsigned q = fdiv(nx, p.wo_div);
+    nx -= q * (unsigned)p.wo;
+    ox = (int)nx;
+    const int noy = oy + (int)q;
+    const bool wrap = noy >= p.ho;
+    oy = wrap ? noy - p.ho : noy;
+    imgoff += wrap ? img_bytes : 0u;
+  }
+};
+
+// The epilogue: a wave's TM x TN accumulator tiles of 32 x 32, times scale, to (or, accumulating, onto) `out`
+// [cout][ncols], predicated per element.  (row0, col0): the wave's block in `out`; the MFMA result map gives lane l, with
+// li = l & 31 and lh = l >> 5, column li and rows 4 * lh + (e & 3) + 8 * (e >> 2) of a tile.
+// Code-generation note (profiles/r15_isa_wgrad_shared_vs_parent.txt): p by value and li / lh from the caller is the form
+// under which the split and bf16 kernels compile as they did with the loop written out in them.
+template <int TM, int TN>
+__device__ __forceinline__ void wgrad_store_acc(const WgradParams p, const f32x16 (&acc)[TM][TN], float *out, int row0, int col0,
+                                                int li, int lh, float scale) {
+#pragma unroll
+  for (int i = 0; i < TM; ++i)
+#pragma unroll
+    for (int j = 0; j < TN; ++j) {
+      const int col = col0 + j * 32 + li;
+#pragma unroll
+      for (int e = 0; e < 16; ++e) {
+        const int row = row0 + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
+        if (row < p.cout && col < p.ncols) {
+          const long long off = (long long)row * p.ncols + col;
+          float v = acc[i][j][e] * scale;
+          if (p.accumulate) v += out[off];
+          out[off] = v;
+        }
+      }
+    }
+}
+
 // Sum of the per-split slabs.  A workgroup covers 256/lanes float4 columns; `lanes` threads per column
 // each add every lanes-th slab, then the lanes are summed through LDS in a fixed order
 // (deterministic).  With one thread per column (the obvious form) a 64-channel layer has 144
 // workgroups each issuing 150 dependent loads: latency-bound at ~1.2 TB/s.
-static __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ slabs, float *__restrict__ dw,
-                                                           long long n4, int splits, int accumulate, int lanes) {
-  __shared__ float4 sh[256];
-  const int cols = 256 / lanes;
+// One such sum: n4 float4 columns of `splits` slabs into (accumulate: onto) dw, by the workgroups from block0 on
+// (conv_split.hip's wgrad_reduce_batch_kernel runs several in one launch).  sh: 256 float4 of LDS.
+struct ReduceItem {
+  const float *slabs;
+  float *dw;
+  long long n4;
+  int splits, accumulate, lanes, block0;
+};
+template <class Item>
+__device__ __forceinline__ void wgrad_slab_sum(float4 *sh, const Item &r) {
+  const int cols = 256 / r.lanes;
   const int c = threadIdx.x % cols, l = threadIdx.x / cols;
-  const long long i = (long long)blockIdx.x * cols + c;
+  const long long i = (long long)(blockIdx.x - r.block0) * cols + c;
   float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (i < n4)
-    for (int k = l; k < splits; k += lanes) {
-      const float4 v = reinterpret_cast<const float4 *>(slabs)[(long long)k * n4 + i];
+  if (i < r.n4)
+    for (int k = l; k < r.splits; k += r.lanes) {
+      const float4 v = reinterpret_cast<const float4 *>(r.slabs)[(long long)k * r.n4 + i];
       s.x += v.x;
       s.y += v.y;
       s.z += v.z;
@@ -237,17 +351,29 @@ static __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *_
     }
   sh[threadIdx.x] = s;
   __syncthreads();
-  if (l == 0 && i < n4) {
-    float4 t = accumulate ? reinterpret_cast<const float4 *>(dw)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int k = 0; k < lanes; ++k) {
+  if (l == 0 && i < r.n4) {
+    float4 t = r.accumulate ? reinterpret_cast<const float4 *>(r.dw)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
+    for (int k = 0; k < r.lanes; ++k) {
       const float4 v = sh[k * cols + c];
       t.x += v.x;
       t.y += v.y;
       t.z += v.z;
       t.w += v.w;
     }
-    reinterpret_cast<float4 *>(dw)[i] = t;
+    reinterpret_cast<float4 *>(r.dw)[i] = t;
   }
+}
+static __global__ __launch_bounds__(256) void wgrad_reduce_kernel(const float *__restrict__ slabs, float *__restrict__ dw,
+                                                           long long n4, int splits, int accumulate, int lanes) {
+  __shared__ float4 sh[256];
+  struct {          // the arguments as an item, by reference: each is still read where the sum uses it
+    const float *__restrict__ const &slabs;
+    float *__restrict__ const &dw;
+    const long long &n4;
+    const int &splits, &accumulate, &lanes;
+    int block0;
+  } r = {slabs, dw, n4, splits, accumulate, lanes, 0};
+  wgrad_slab_sum(sh, r);
 }
 
 // Algorithmic input channels of a conv for the profiler's FLOP / byte accounting: the 7x7 stem is the
@@ -504,13 +630,16 @@ static int wgrad_geometry(WgradParams &p, const mvg_conv_desc *d, int elem, int 
   return 0;
 }
 
+// threads per float4 column of the slab sum (wgrad_slab_sum)
+static int wgrad_reduce_lanes(int splits) { return splits >= 32 ? 16 : (splits >= 8 ? 4 : 1); }
+
 // The sums of a pixel-split weight gradient's slabs into dw (and of the bias slabs after them into db, when given).
 static int wgrad_reduce_slabs(const WgradParams &p, float *workspace, float *dw, float *db, int splits, int accumulate, hipStream_t st,
                               const char *what) {
   const long long n = (long long)p.cout * p.ncols;
   MVG_REQUIRE(n % 4 == 0, "%s: weight elements %% 4 != 0", what);
   ProfScope ps(MVG_K_WGRAD_REDUCE, st, 0.0, 4.0 * n * (splits + 1));
-  const int lanes = splits >= 32 ? 16 : (splits >= 8 ? 4 : 1);
+  const int lanes = wgrad_reduce_lanes(splits);
   const long long blocks = (n / 4 + 256 / lanes - 1) / (256 / lanes);
   hipLaunchKernelGGL(wgrad_reduce_kernel, dim3((unsigned)blocks), dim3(256), 0, st, workspace, dw, n / 4, splits, accumulate, lanes);
   if (check_launch("wgrad_reduce")) return 1;
@@ -533,6 +662,33 @@ static int wgrad_split_count(long long tiles, long long pixels, int workgroups_p
   if (want < 1) want = 1;
   if (want > 1024) want = 1024;
   return (int)want;
+}
+
+// output tiles of a weight gradient at the family's bm x bn tile
+static long long wgrad_tiles(const mvg_conv_desc *d, int bm, int bn) {
+  return (long long)ceil_div(d->cout, bm) * ceil_div(d->r * d->s * d->cin, bn);
+}
+
+// A weight-gradient launch of any family, the caller's fields of p set: geometry (elem, px_align, stride_w / pad_w as in
+// wgrad_geometry), the bm x bn tiles, the profiler's family (flops, bytes: the caller's accounting), the kernel through
+// dispatch(grid, block, st, p) - the family's tile -> instantiation switch; nonzero = its error
+// (the fuser's shape check) - and, unless the slabs
+// are the result (slabs_only), their sum.  `what` prefixes the error messages, launch_name names the launch check's.
+template <class Dispatch>
+static int wgrad_launch(WgradParams &p, const mvg_conv_desc *d, int elem, int px_align, int bm, int bn, float *dw, float *db,
+                        float *workspace, int splits, int accumulate, bool slabs_only, hipStream_t st, double flops, double bytes,
+                        const char *what, const char *launch_name, int stride_w, int pad_w, Dispatch dispatch) {
+  if (wgrad_geometry(p, d, elem, px_align, dw, db, workspace, splits, accumulate, what, stride_w, pad_w)) return 2;
+  p.mtiles = ceil_div(d->cout, bm);
+  p.ntiles = ceil_div(p.ncols, bn);
+  {
+    const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
+    ProfScope ps(lin ? MVG_K_LINEAR_WGRAD : MVG_K_CONV_WGRAD, st, flops, bytes);
+    MVG_REQUIRE(wgrad_tiles(d, bm, bn) * splits < (1LL << 31), "%s: grid too large", what);
+    if (int e = dispatch(dim3(p.mtiles * p.ntiles * splits), dim3(256), st, p)) return e;
+    if (check_launch(launch_name)) return 1;
+  }
+  return splits > 1 && !slabs_only ? wgrad_reduce_slabs(p, workspace, dw, db, splits, accumulate, st, what) : 0;
 }
 
 }  // namespace mvg

@@ -453,8 +453,9 @@ struct OutFormer {
 #undef MVG_SPLIT_RNG
 
 // ------------------------------------------------------------------------------------------
-// wgrad: dw[o][tap][c] = sum over pixels of dy[pix][o] * x[pix at tap][c] with both operands in sp.  Like the bf16
-// kernel (conv_bf16.hip): M = cout, N = (tap, c), K = pixels split into slabs; the LDS images stay pixel-major
+// wgrad: dw[o][tap][c] = sum over pixels of dy[pix][o] * x[pix at tap][c] with both operands in sp.  M = cout,
+// N = (tap, c), K = pixels split into slabs; tile decode, column and pixel addressing and the epilogue are conv_shared.h's
+// (wgrad_tile_id, wgrad_column, WgradPixel, wgrad_store_acc).  The LDS images stay pixel-major
 // [piece][k][m] (rows padded by 32 elements) and the fragments come from ds_read_b64_tr_b16 (v_mfma_f32_32x32x16_f16,
 // three products per 16 pixels).  A K-step is 16 pixels: 20 KB per stage, two stages; a thread's two piece vectors of
 // one 8-channel chunk are 32 contiguous bytes in memory.  The result is multiplied by dy's 2^-k (p.dy_sinv).
@@ -482,24 +483,13 @@ __global__ __launch_bounds__(256, BN >= 256 ? 2 : 3) void wgrad_split_kernel(Wgr
   const int lane = tid & 63, wave = tid >> 6;
   const int wm = wave / WGN, wn = wave % WGN;
   const int li = lane & 31, lh = lane >> 5;
-  const int tiles = p.mtiles * p.ntiles;
-  const int logical = xcd_remap(blockIdx.x, gridDim.x);
-  const int split = logical / tiles;
-  const int tile = logical - split * tiles;
-  const int ntile = tile % p.ntiles, mtile = tile / p.ntiles;
-  const long long m_begin = (long long)split * p.pixels_per_split;
-  long long m_end = m_begin + p.pixels_per_split;
-  if (m_end > p.pixels) m_end = p.pixels;
-  const int m_count = m_end > m_begin ? (int)(m_end - m_begin) : 0;
-  const int ohw = p.ho * p.wo;
-  const long long img0 = m_begin / ohw;
-  const unsigned rem0 = (unsigned)(m_begin - img0 * ohw);
+  const WgradTile t = wgrad_tile_id(p);
 
   const char *dy = reinterpret_cast<const char *>(p.dy);
   const char *x = reinterpret_cast<const char *>(p.x);
-  const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(dy + m_begin * p.cout * SP_BYTES, (long long)SP_BYTES * m_count * p.cout);
+  const __amdgpu_buffer_rsrc_t rs_a = make_rsrc(dy + t.m_begin * p.cout * SP_BYTES, (long long)SP_BYTES * t.m_count * p.cout);
   const long long x_img_elems = (long long)p.h * p.w * p.cin;
-  const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(x + img0 * x_img_elems * SP_BYTES, p.x_bytes - (long long)SP_BYTES * img0 * x_img_elems);
+  const __amdgpu_buffer_rsrc_t rs_b = make_rsrc(x + t.img0 * x_img_elems * SP_BYTES, p.x_bytes - (long long)SP_BYTES * t.img0 * x_img_elems);
   // both loaders: pixel row i_row = tid / 16, chunk lane i_v0 = tid % 16 (+ 16 per extra chunk)
   const int i_row = tid / A_TPR, i_v0 = tid % A_TPR;
   unsigned a_off[A_CPT];
@@ -507,39 +497,23 @@ __global__ __launch_bounds__(256, BN >= 256 ? 2 : 3) void wgrad_split_kernel(Wgr
 #pragma unroll
   for (int j = 0; j < A_CPT; ++j) {
     const int cv = i_v0 + j * A_TPR;
-    const int col = mtile * BM + cv * 8;
+    const int col = t.mtile * BM + cv * 8;
     a_on[j] = cv < MV;
     a_off[j] = (a_on[j] && col < p.cout) ? (unsigned)(i_row * p.cout + col) * (unsigned)SP_BYTES : 0x80000000u;
   }
-  int i_dy[B_CPT], i_dx[B_CPT];
-  unsigned i_tconst[B_CPT];
-  bool i_cok[B_CPT], b_on[B_CPT];
+  WgradColumn i_col[B_CPT];
+  bool b_on[B_CPT];
 #pragma unroll
   for (int j = 0; j < B_CPT; ++j) {
     const int cv = i_v0 + j * A_TPR;
-    const int col = ntile * BN + cv * 8;
     b_on[j] = cv < NVB;
-    i_cok[j] = b_on[j] && col < p.ncols;
-    const int tap = (int)fdiv((unsigned)(i_cok[j] ? col : 0), p.cin_div);
-    const int cc = (i_cok[j] ? col : 0) - tap * p.cin;
-    const int fr = (int)fdiv((unsigned)tap, p.s_div), fs = tap - fr * p.s;
-    i_dy[j] = fr - p.pad;
-    i_dx[j] = fs - p.pad_w;
-    i_tconst[j] = (unsigned)((i_dy[j] * p.w + i_dx[j]) * p.cin + cc) * (unsigned)SP_BYTES;
+    i_col[j] = wgrad_column(p, t.ntile * BN + cv * 8, (unsigned)SP_BYTES, p.pad_w);
+    i_col[j].cok &= b_on[j];
   }
   const unsigned row_bytes = (unsigned)(p.stride * p.w * p.cin) * (unsigned)SP_BYTES, col_bytes = (unsigned)(p.stride_w * p.cin) * (unsigned)SP_BYTES;
   const unsigned img_bytes = (unsigned)x_img_elems * (unsigned)SP_BYTES;
-  int s_oy = 0, s_ox = 0;
-  unsigned s_imgoff = 0;
-  if (INCR) {
-    const unsigned pix = rem0 + (unsigned)i_row;
-    const unsigned img = fdiv(pix, p.ohw_div);
-    const unsigned rem = pix - img * (unsigned)ohw;
-    const unsigned oy = fdiv(rem, p.wo_div);
-    s_oy = (int)oy;
-    s_ox = (int)(rem - oy * (unsigned)p.wo);
-    s_imgoff = img * img_bytes;
-  }
+  WgradPixel s_px = {0, 0, 0u};
+  if (INCR) s_px.decode(p, t.rem0 + (unsigned)i_row, img_bytes);
   u32x4 a_reg[A_CPT][SP_NP], b_reg[B_CPT][SP_NP];
   auto load_tiles = [&](int kt) {
 #pragma unroll
@@ -549,42 +523,20 @@ __global__ __launch_bounds__(256, BN >= 256 ? 2 : 3) void wgrad_split_kernel(Wgr
         a_reg[j][pc] = __builtin_amdgcn_raw_buffer_load_b128(rs_a, a_off[j] + 16u * pc, 0, 0);
       a_off[j] += (unsigned)(BK * p.cout) * (unsigned)SP_BYTES;
     }
-    const bool mok = kt * BK + i_row < m_count;
-    int oy, ox;
-    unsigned imgoff;
-    if constexpr (INCR) {
-      oy = s_oy;
-      ox = s_ox;
-      imgoff = s_imgoff;
-    } else {
-      const unsigned pix = rem0 + (unsigned)(kt * BK + i_row);
-      const unsigned img = fdiv(pix, p.ohw_div);
-      const unsigned rem = pix - img * (unsigned)ohw;
-      const unsigned uy = fdiv(rem, p.wo_div);
-      oy = (int)uy;
-      ox = (int)(rem - uy * (unsigned)p.wo);
-      imgoff = img * img_bytes;
-    }
-    const int iy0 = oy * p.stride, ix0 = ox * p.stride_w;
-    const unsigned pixoff = imgoff + (unsigned)oy * row_bytes + (unsigned)ox * col_bytes;
+    const bool mok = kt * BK + i_row < t.m_count;
+    WgradPixel px = s_px;
+    if constexpr (!INCR) px.decode(p, t.rem0 + (unsigned)(kt * BK + i_row), img_bytes);
+    const int iy0 = px.oy * p.stride, ix0 = px.ox * p.stride_w;
+    const unsigned pixoff = px.imgoff + (unsigned)px.oy * row_bytes + (unsigned)px.ox * col_bytes;
 #pragma unroll
     for (int j = 0; j < B_CPT; ++j) {
-      const bool ok = mok & i_cok[j] & ((unsigned)(iy0 + i_dy[j]) < (unsigned)p.h) & ((unsigned)(ix0 + i_dx[j]) < (unsigned)p.w);
+      const WgradColumn &c = i_col[j];
+      const bool ok = mok & c.cok & ((unsigned)(iy0 + c.dy) < (unsigned)p.h) & ((unsigned)(ix0 + c.dx) < (unsigned)p.w);
 #pragma unroll
       for (int pc = 0; pc < SP_NP; ++pc)
-        b_reg[j][pc] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, pred_off(pixoff + i_tconst[j] + 16u * pc, ok), 0, 0);
+        b_reg[j][pc] = __builtin_amdgcn_raw_buffer_load_b128(rs_b, pred_off(pixoff + c.tconst + 16u * pc, ok), 0, 0);
     }
-    if constexpr (INCR) {
-      // advance BK pixels: columns wrap into rows, rows into the next image (at most once: ho*wo >= 2*BK)
-      unsigned nx = (unsigned)s_ox + BK;
-      const unsigned q = fdiv(nx, p.wo_div);
-      nx -= q * (unsigned)p.wo;
-      s_ox = (int)nx;
-      const int noy = s_oy + (int)q;
-      const bool wrap = noy >= p.ho;
-      s_oy = wrap ? noy - p.ho : noy;
-      s_imgoff += wrap ? img_bytes : 0u;
-    }
+    if constexpr (INCR) s_px.template advance<BK>(p, img_bytes);
   };
   auto store_tiles = [&](int buf) {
     unsigned short *As = smem + buf * STAGE;
@@ -613,7 +565,7 @@ __global__ __launch_bounds__(256, BN >= 256 ? 2 : 3) void wgrad_split_kernel(Wgr
 #pragma unroll
       for (int e = 0; e < 16; ++e) acc[i][j][e] = 0.f;
 
-  const int KT = (m_count + BK - 1) / BK;
+  const int KT = (t.m_count + BK - 1) / BK;
   load_tiles(0);
   store_tiles(0);
   load_tiles(1);
@@ -636,34 +588,12 @@ __global__ __launch_bounds__(256, BN >= 256 ? 2 : 3) void wgrad_split_kernel(Wgr
     __syncthreads();
   }
 
-  float *out = p.out + (long long)split * p.cout * p.ncols;
   const float osc = (p.dy_sinv ? *p.dy_sinv : 1.f) * (p.x_sinv ? *p.x_sinv : 1.f);
-#pragma unroll
-  for (int i = 0; i < TM; ++i)
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const int col = ntile * BN + wn * WTN + j * 32 + li;
-#pragma unroll
-      for (int e = 0; e < 16; ++e) {
-        const int row = mtile * BM + wm * WTM + i * 32 + (e & 3) + 8 * (e >> 2) + 4 * lh;
-        if (row < p.cout && col < p.ncols) {
-          const long long off = (long long)row * p.ncols + col;
-          float v = acc[i][j][e] * osc;
-          if (p.accumulate) v += out[off];
-          out[off] = v;
-        }
-      }
-    }
+  wgrad_store_acc(p, acc, p.out + (long long)t.split * p.cout * p.ncols, t.mtile * BM + wm * WTM, t.ntile * BN + wn * WTN, li, lh, osc);
 }
 
 // The slab sums of SEVERAL weight gradients in one launch (a residual block's 3-4 convs: round 3 ran one 10 us reduce
-// launch behind every wgrad launch, 63 per ResNet-50 step).  Same arithmetic and order as wgrad_reduce_kernel per item.
-struct ReduceItem {
-  const float *slabs;
-  float *dw;
-  long long n4;
-  int splits, accumulate, lanes, block0;          // block0: first workgroup of this item
-};
+// launch behind every wgrad launch, 63 per ResNet-50 step): wgrad_reduce_kernel's sum (wgrad_slab_sum) per item.
 struct ReduceBatch {
   ReduceItem it[8];
   int n;
@@ -672,32 +602,7 @@ __global__ __launch_bounds__(256) void wgrad_reduce_batch_kernel(ReduceBatch b) 
   __shared__ float4 sh[256];
   int k = 0;
   for (int i = 1; i < b.n; ++i) k += (int)blockIdx.x >= b.it[i].block0;
-  const ReduceItem &r = b.it[k];
-  const int cols = 256 / r.lanes;
-  const int c = threadIdx.x % cols, l = threadIdx.x / cols;
-  const long long i = (long long)(blockIdx.x - r.block0) * cols + c;
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-  if (i < r.n4)
-    for (int q = l; q < r.splits; q += r.lanes) {
-      const float4 v = reinterpret_cast<const float4 *>(r.slabs)[(long long)q * r.n4 + i];
-      s.x += v.x;
-      s.y += v.y;
-      s.z += v.z;
-      s.w += v.w;
-    }
-  sh[threadIdx.x] = s;
-  __syncthreads();
-  if (l == 0 && i < r.n4) {
-    float4 t = r.accumulate ? reinterpret_cast<const float4 *>(r.dw)[i] : make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int q = 0; q < r.lanes; ++q) {
-      const float4 v = sh[q * cols + c];
-      t.x += v.x;
-      t.y += v.y;
-      t.z += v.z;
-      t.w += v.w;
-    }
-    reinterpret_cast<float4 *>(r.dw)[i] = t;
-  }
+  wgrad_slab_sum(sh, b.it[k]);
 }
 
 // The stem's row-window operand (see mvg_stem_fprop_split): one thread per 8-value chunk = image columns (2 ox - 4 + 2 q,
@@ -1235,15 +1140,19 @@ static void wgrad_split_tile(const mvg_conv_desc *d, int &bm, int &bn, bool &inc
   else if (ncols % 192 == 0) bn = 192;
 }
 
-int mvg_conv_wgrad_splits_split(const mvg_conv_desc *d) {
-  if (validate_split(d)) return -1;
+// The pixel splits of a checked descriptor (the stem's rewritten one included) at its tile.
+static int wgrad_split_splits(const mvg_conv_desc *d) {
   int bm, bn;
   bool incr;
   wgrad_split_tile(d, bm, bn, incr);
-  const long long tiles = (long long)ceil_div(d->cout, bm) * ceil_div(d->r * d->s * d->cin, bn);
   // one resident round: three workgroups per CU (128-column tiles; measured at C3: 2 / 3 / 4 / 6 per CU -> 17.8 / 16.8 / 16.7 /
   // 17.7 ms of wgrad per step), two with the 256-column tiles (2 / 3 / 4 / 6 -> 15.6 / 16.8 / 16.4 / 17.3 ms); 16 K-steps per split
-  return wgrad_split_count(tiles, (long long)d->groups * d->n * d->ho * d->wo, bn == 256 ? 2 : 3, 256);
+  return wgrad_split_count(wgrad_tiles(d, bm, bn), (long long)d->groups * d->n * d->ho * d->wo, bn == 256 ? 2 : 3, 256);
+}
+
+int mvg_conv_wgrad_splits_split(const mvg_conv_desc *d) {
+  if (validate_split(d)) return -1;
+  return wgrad_split_splits(d);
 }
 
 int mvg_conv_wgrad_split_tile(const mvg_conv_desc *d, int32_t *bm, int32_t *bn, int32_t *incremental) {
@@ -1267,25 +1176,18 @@ static int wgrad_split_impl(const mvg_conv_desc *d, const void *x_sp, const void
   p.dy = (const float *)dy_sp;
   p.dy_sinv = dy_sinv;
   p.x_sinv = x_sinv;
-  if (wgrad_geometry(p, d, SP_BYTES, 16, dw, nullptr, workspace, splits, accumulate, "wgrad_split", stride_w, pad_w)) return 2;
   int bm, bn;
   bool incr;
   wgrad_split_tile(d, bm, bn, incr);
-  p.mtiles = ceil_div(d->cout, bm);
-  p.ntiles = ceil_div(p.ncols, bn);
-  hipStream_t st = (hipStream_t)stream;
-  const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
-  {
-    const double flops = 2.0 * (double)p.pixels * d->cout * d->r * d->s * d->cin * (stride_w >= 0 ? 147.0 / 224.0 : 1.0);
-    const double bytes = (double)SP_BYTES * ((double)d->groups * d->n * d->h * d->w * d->cin + (double)p.pixels * d->cout) +
-                         4.0 * (double)d->cout * d->r * d->s * d->cin;
-    ProfScope ps(lin ? MVG_K_LINEAR_WGRAD : MVG_K_CONV_WGRAD, st, flops, bytes);
-    MVG_REQUIRE((long long)p.mtiles * p.ntiles * splits < (1LL << 31), "wgrad_split: grid too large");
-    dim3 grid(p.mtiles * p.ntiles * splits), block(256);
+  const double pixels = (double)d->groups * d->n * d->ho * d->wo;
+  const double flops = 2.0 * pixels * d->cout * d->r * d->s * d->cin * (stride_w >= 0 ? 147.0 / 224.0 : 1.0);
+  const double bytes = (double)SP_BYTES * ((double)d->groups * d->n * d->h * d->w * d->cin + pixels * d->cout) +
+                       4.0 * (double)d->cout * d->r * d->s * d->cin;
+  const auto dispatch = [&](dim3 grid, dim3 block, hipStream_t st, const WgradParams &wp) {
 #define MVG_WGRAD_SPLIT(BM_, BN_)                                                                  \
   do {                                                                                             \
-    if (incr) hipLaunchKernelGGL((wgrad_split_kernel<BM_, BN_, true>), grid, block, 0, st, p);     \
-    else hipLaunchKernelGGL((wgrad_split_kernel<BM_, BN_, false>), grid, block, 0, st, p);         \
+    if (incr) hipLaunchKernelGGL((wgrad_split_kernel<BM_, BN_, true>), grid, block, 0, st, wp);     \
+    else hipLaunchKernelGGL((wgrad_split_kernel<BM_, BN_, false>), grid, block, 0, st, wp);         \
   } while (0)
     if (bm == 128 && bn == 256) MVG_WGRAD_SPLIT(128, 256);
     else if (bm == 128 && bn == 192) MVG_WGRAD_SPLIT(128, 192);
@@ -1295,9 +1197,10 @@ static int wgrad_split_impl(const mvg_conv_desc *d, const void *x_sp, const void
     else if (bm == 128 && bn == 64) MVG_WGRAD_SPLIT(128, 64);
     else MVG_WGRAD_SPLIT(64, 64);
 #undef MVG_WGRAD_SPLIT
-    if (check_launch("conv_wgrad_split")) return 1;
-  }
-  return splits > 1 && !slabs_only ? wgrad_reduce_slabs(p, workspace, dw, nullptr, splits, accumulate, st, "wgrad_split") : 0;
+    return 0;
+  };
+  return wgrad_launch(p, d, SP_BYTES, 16, bm, bn, dw, nullptr, workspace, splits, accumulate, slabs_only, (hipStream_t)stream, flops, bytes,
+                      "wgrad_split", "conv_wgrad_split", stride_w, pad_w, dispatch);
 }
 
 // x_sinv (may be NULL = unscaled): the 2^-k of an activation operand stored times 2^k (bn.hip: act_scales_kernel)
@@ -1341,7 +1244,7 @@ int mvg_wgrad_reduce_batch(const float *const *host_slabs, float *const *host_dw
     r.n4 = host_n[i] / 4;
     r.splits = host_splits[i];
     r.accumulate = host_accumulate[i];
-    r.lanes = r.splits >= 32 ? 16 : (r.splits >= 8 ? 4 : 1);
+    r.lanes = wgrad_reduce_lanes(r.splits);
     r.block0 = (int)blocks;
     blocks += (r.n4 + 256 / r.lanes - 1) / (256 / r.lanes);
     bytes += 4.0 * host_n[i] * (r.splits + 1);
@@ -1445,8 +1348,9 @@ int mvg_stem_fprop_split(const mvg_conv_desc *d, const void *xw_sp, const void *
 int mvg_stem_wgrad_splits_split(const mvg_conv_desc *d) {
   mvg_conv_desc rw;
   if (stem_desc(d, &rw)) return -1;
-  const long long tiles = (long long)ceil_div(rw.cout, rw.cout >= 128 ? 128 : 64) * ceil_div(7 * 32, 128);
-  return wgrad_split_count(tiles, (long long)rw.groups * rw.n * rw.ho * rw.wo, 3, 256);
+  // the rewritten descriptor's own tile, as wgrad_split_impl launches it: its 7 x 32 = 224 columns are >= 128 and a multiple of
+  // neither 256 nor 192, so wgrad_split_tile answers bn = 128 (three workgroups per CU) and bm = 128 or 64 by cout, for every cout
+  return wgrad_split_splits(&rw);
 }
 
 int mvg_stem_wgrad_split(const mvg_conv_desc *d, const void *xw_sp, const void *dy_sp, const float *dy_sinv, float *dw_rw, float *workspace,

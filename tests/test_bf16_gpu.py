@@ -97,6 +97,8 @@ BF16_CONV_CASES = [
     (1, 30, 14, 14, 256, 256, 3, 1, 1),   # ragged last M tile
     (1, 3, 9, 9, 32, 32, 3, 1, 1),        # 32 channels per tap (not a multiple of the 64-deep K-step)
     (2, 16, 56, 56, 64, 64, 3, 1, 1),     # large: many tiles, several wgrad splits
+    (1, 4, 14, 14, 64, 64, 1, 1, 0),      # wgrad's 64x64 tile, incremental pixel stepping
+    (1, 4, 7, 7, 64, 64, 1, 1, 0),        # ... and with the per-step pixel decode
 ]
 
 
@@ -269,7 +271,9 @@ def test_bf16_stem_as_folded_row_windows(G, N, H, W):
 
 
 @pytest.mark.parametrize("rows,fin,fout,relu", [(3584, 3584, 3584, True), (384, 2048, 1536, False), (70, 3584, 512, True),
-                                                (1000, 512, 1536, True)])
+                                                (1000, 512, 1536, True),
+                                                # wgrad's other fp32-operand tiles: 64x128, 128x64, 64x64
+                                                (70, 128, 64, False), (70, 64, 128, True), (70, 64, 64, True)])
 def test_mixed_linear_fp32_tensors_bf16_products(rows, fin, fout, relu):
     """mvg_linear_*_mixed: fp32 tensors in memory, operands rounded to bf16 in the loaders, fp32 accumulation and
     fp32 results == float64 arithmetic on the rounded operands to fp32 accumulation noise (no output rounding)."""
