@@ -667,8 +667,9 @@ int mvg_conv_dgrad_split(const mvg_conv_desc *d, const void *dy_sp, const float 
  * mx [groups][c] = max |masked gradient| per (group, channel), left by mvg_bn_bwd_reduce_split or
  * mvg_conv_dgrad_split_bnreduce; *dy_sinv receives 2^-k for mvg_conv_dgrad_split / _wgrad_split.  The reduce entries
  * (mvg_bn_bwd_reduce_split, mvg_conv_dgrad_split_bnreduce, mvg_bn_relu_maxpool_bwd_reduce_split) take the unit's gamma and
- * dy_sinv (both NULL, or both given): their finalize launch then leaves *dy_sinv itself - partials, dgamma / dbeta and the
- * bound in ONE launch, folded into the last-arriving workgroups - and the apply entry is told so (dy_sinv_ready != 0). */
+ * dy_sinv (both NULL, or both given): their finalize then leaves *dy_sinv itself - bn_bwd_finalize_kernel (partials -> s1 / s2 /
+ * mx), then the single-workgroup bn_bwd_dgamma_dyscale_kernel (dgamma / dbeta and the bound's 2^-k) in place of the plain
+ * dgamma / dbeta launch - and the apply entry is told so (dy_sinv_ready != 0). */
 int mvg_bn_apply_split(const float *y, const float *scale, const float *shift, const void *residual, int residual_sp,
                        const float *res_scale, const float *res_shift, int relu, void *out_sp, uint8_t *relu_bits,
                        int groups, int64_t rows_per_group, int c, void *stream);

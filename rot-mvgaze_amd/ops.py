@@ -31,8 +31,10 @@ _raw_stream = getattr(torch._C, "_cuda_getCurrentRawStream", None)      # the cu
 
 
 def _s(scratch: bool = False):
-    """The current HIP stream as the library's `void *stream`.  scratch=True (the entry points that can use scratch:
-    fp32 conv / Linear fprop and dgrad - stream-K pieces - and bn_finalize): the first such launch on a
+    """The current HIP stream as the library's `void *stream`.  scratch=True (the entry points that can use scratch, all
+    through the fp32-MFMA GEMM launcher's stream-K pieces or bn_finalize's two-level merge: mvg_conv_fprop,
+    mvg_conv_fprop_affine, mvg_conv_dgrad, mvg_fuser_fprop, mvg_linear_fprop, mvg_linear_dgrad and mvg_bn_finalize; no split,
+    bf16 or other BatchNorm entry point asks for any): the first such launch on a
     (device, stream) allocates that stream's workspace from PyTorch's caching allocator and registers it
     (mvg_set_scratch) - the library itself never allocates device memory ("caller owns every buffer
     incl. workspace").  At most _MAX_WORKSPACES stay registered; the least recently used one is dropped (uses are
@@ -397,7 +399,7 @@ def bn_relu_maxpool_bwd_reduce_split(g_pooled, argmax, y, mean, invstd, scale, s
     ws = torch.empty(n, dtype=torch.float32, device=y.device)
     check(lib().mvg_bn_relu_maxpool_bwd_reduce_split(_p(g_pooled), _p(argmax), _p(y), _p(mean), _p(invstd), _p(scale), _p(shift), groups,
                                                      n_per_group, h, w, c, ho, wo, _p(s1), _p(s2), _p(dgamma), _p(dbeta), int(accumulate),
-                                                     _p(ws), _p(mx), _p(gamma), _p(dy_sinv), _s(True)), "bn_relu_maxpool_bwd_reduce_split")
+                                                     _p(ws), _p(mx), _p(gamma), _p(dy_sinv), _s()), "bn_relu_maxpool_bwd_reduce_split")
 
 
 def bn_relu_maxpool_bwd_apply_split(g_pooled, argmax, y, mean, invstd, gamma, scale, shift, s1, s2, groups, n_per_group, h, w, c, ho, wo,
@@ -445,7 +447,7 @@ def conv_dgrad_split_bnreduce(d: ConvDesc, dy_sp, wt_sp, dx, addend, bn_y, bn_bi
     rs, rh = relu_affine if relu_affine is not None else (None, None)
     check(lib().mvg_conv_dgrad_split_bnreduce(C.byref(d), _p(dy_sp), _sinv(dy_sp), _p(wt_sp), _sinv(wt_sp), _p(dx), _p(addend), _p(bn_y),
                                               _p(bn_bits), _p(bn_mean), _p(bn_invstd), _p(rs), _p(rh), _p(part), _p(s1), _p(s2),
-                                              _p(dgamma), _p(dbeta), int(accumulate), _p(mx), _p(bn_gamma), _p(dx_dy_sinv), _s(True)),
+                                              _p(dgamma), _p(dbeta), int(accumulate), _p(mx), _p(bn_gamma), _p(dx_dy_sinv), _s()),
           "conv_dgrad_split_bnreduce")
 
 
@@ -464,7 +466,7 @@ def conv_dgrad_split_bnapply_bnreduce(d: ConvDesc, dy_sp, dy_sinv, dz, y, mean, 
                                                       _p(un_s1), _p(un_s2), rows_per_group, _p(wt_sp), _sinv(wt_sp), _p(dx), _p(addend),
                                                       _p(bn_y), _p(bn_bits), _p(bn_mean), _p(bn_invstd), _p(rs), _p(rh), _p(part), _p(s1),
                                                       _p(s2), _p(dgamma), _p(dbeta), int(accumulate), _p(mx), _p(bn_gamma),
-                                                      _p(dx_dy_sinv), _s(True)), "conv_dgrad_split_bnapply_bnreduce")
+                                                      _p(dx_dy_sinv), _s()), "conv_dgrad_split_bnapply_bnreduce")
 
 
 def conv_dgrad_bf16_bnreduce(d: ConvDesc, dy, wt, dx, addend, bn_y, bn_bits, bn_mean, bn_invstd, relu_affine, s1, s2, dgamma, dbeta,
@@ -539,7 +541,7 @@ def bn_bwd_reduce_split(g, relu_bits, y, mean, invstd, groups, rows_per_group, c
     ws = torch.empty(n, dtype=torch.float32, device=g.device)
     check(lib().mvg_bn_bwd_reduce_split(_p(g), _p(relu_bits), _p(y), _p(mean), _p(invstd), _p(rs), _p(rh), groups, rows_per_group, c,
                                         _p(s1), _p(s2), _p(dgamma), _p(dbeta), int(accumulate), _p(ws), _p(dz_out), _p(mx), _p(gamma),
-                                        _p(dy_sinv), _s(True)), "bn_bwd_reduce_split")
+                                        _p(dy_sinv), _s()), "bn_bwd_reduce_split")
 
 
 def bn_bwd_apply_split(g, y, mean, invstd, gamma, s1, s2, groups, rows_per_group, c, dy_sp, relu_affine=None, mx=None, dy_sinv=None):

@@ -1,20 +1,18 @@
 """CPU-side checks of the backbone activations' per-tensor scales (training steps on the split kernels): the new entry
-points are declared in include/rotmvgaze.h, exported, bound in _lib.SIGNATURES with the header's arity and wrapped in
-ops; and the bound chain itself - evaluated on the host by tests/act_range_ref.py - leaves every tensor of the networks
+points are declared in include/rotmvgaze.h beside the unchanged ones they extend (exported and bound: tests/test_cabi_cpu.py,
+for every function) and wrapped in ops; and the bound chain itself - evaluated on the host by tests/act_range_ref.py - leaves every tensor of the networks
 the tests and the benchmark build UNSCALED (the dead band 1 <= bound < 2^15: those networks keep their bits) and gives
 the modified networks of tests/test_act_range_gpu.py the power of two the formula says."""
 import math
-import os
-import re
 
 import numpy as np
 import pytest
 
+import cabi_header as hdr
 import rot_mvgaze_amd  # noqa: F401
 from rot_mvgaze_amd.arch import backbone_spec
 from act_range_ref import P, RANGE_CASES, RANGE_IDS, expected_bounds, expected_sinv, modified_state_dict, sinv_for
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NAMES = ("mvg_act_scales", "mvg_bn_apply_split_scaled", "mvg_bn_relu_maxpool_fwd_split_scaled", "mvg_avgpool_fwd_split_scaled",
          "mvg_conv_wgrad_split_xs", "mvg_conv_wgrad_split_slabs_xs")
 # the entry points these extend keep their signatures (the ABI version does not move)
@@ -22,32 +20,11 @@ UNCHANGED = {"mvg_bn_apply_split": 14, "mvg_bn_relu_maxpool_fwd_split": 13, "mvg
              "mvg_conv_wgrad_split_slabs": 7, "mvg_conv_fprop_split": 8}
 
 
-@pytest.fixture(scope="module")
-def built_lib():
-    import __graft_entry__ as ge
-    ge.build()
-    from rot_mvgaze_amd import _lib
-    return _lib.lib()
-
-
-def _declarations():
-    hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    hdr = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
-    return {m.group(1): m.group(2) for m in re.finditer(r"\b(mvg_[a-z0-9_]+)\s*\(([^)]*)\)\s*;", hdr)}
-
-
-def test_act_scale_entry_points_declared_exported_and_bound(built_lib):
-    from rot_mvgaze_amd import _lib
-    decl = _declarations()
+def test_act_scale_entry_points_declared_exported_and_bound():
     for name in NAMES + tuple(UNCHANGED):
-        assert name in decl, f"{name} is not declared in include/rotmvgaze.h"
-        assert hasattr(built_lib, name), f"{name} is not exported"
-        assert name in _lib.SIGNATURES, f"{name} is not in _lib.SIGNATURES"
-        nargs = len([a for a in decl[name].split(",") if a.strip()])
-        assert len(_lib.SIGNATURES[name][1]) == nargs, (name, nargs, len(_lib.SIGNATURES[name][1]))
-        if name in UNCHANGED:
-            assert nargs == UNCHANGED[name], f"{name} changed its signature"
-    assert _lib.ABI_VERSION == 13 and built_lib.mvg_abi_version() == 13
+        assert name in hdr.functions, f"{name} is not declared in include/rotmvgaze.h"
+    for name, nargs in UNCHANGED.items():
+        assert hdr.arity(name) == nargs, f"{name} changed its signature"
 
 
 def test_act_scale_ops_wrappers_exist():

@@ -159,10 +159,10 @@ def test_bad_arguments_raise():
     with pytest.raises(RuntimeError, match="normalised image"):
         call(masks=masks, grid=grid, gmax=2, dst_nhwc4=None)
     # sizes are checked before anything is launched: the library sees the numbers, not the tensors
-    lib, p = rot_mvgaze_amd._lib.lib(), ops._p
+    lib, p, (m0, m1, m2), (s0, s1, s2) = rot_mvgaze_amd._lib.lib(), ops._p, IMAGE_MEAN, IMAGE_STD
     for hh, ww, msg in ((8193, 8, "longer than the index tables"), (8, 8193, "longer than the index tables"), (8192, 4096, "grey sum"),
                         (0, 8, "bad sizes")):
-        rc = lib.mvg_augment_u8hwc(p(src), p(rdev), None, p(d8), None, None, None, 0, n, hh, ww, *IMAGE_MEAN, *IMAGE_STD, 0, ops._s())
+        rc = lib.mvg_augment_u8hwc(p(src), p(rdev), None, p(d8), None, None, None, 0, n, hh, ww, m0, m1, m2, s0, s1, s2, 0, ops._s())
         assert rc != 0 and msg in lib.mvg_last_error().decode(), (hh, ww)
     aug = TrainAugment(erase=RandomMultiErasing([0.5, 0.6], 1.0, [0.2, 0.3]))
     with pytest.raises(ValueError, match="erase"):

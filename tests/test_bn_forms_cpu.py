@@ -1,16 +1,15 @@
 """No GPU: (1) the float64 restatements of tests/bn_forms_ref.py against PyTorch's own BatchNorm on CPU - partial writer ->
 merge must reproduce F.batch_norm's batch statistics and running-statistics updates, the backward formulas autograd; (2) the
-host-only plan query of the BatchNorm passes (mvg_bn_plan_query, ABI 13): declared, bound, and - without a device the planners
+host-only plan query of the BatchNorm passes (mvg_bn_plan_query): declared, its plan's fields the keys ops.bn_plan_query returns, and - without a device the planners
 assume 256 CUs - the tabulated form for every case of tests/test_bn_forms_gpu.py, the launches' rejection messages, and a
 workspace (mvg_bn_bwd_workspace_floats / mvg_bn_eval_bwd_workspace_floats) that holds what the reported chunks write."""
 import ctypes as C
-import os
-import re
 
 import pytest
 import torch
 import torch.nn.functional as F
 
+import cabi_header as hdr
 import rot_mvgaze_amd  # noqa: F401
 from rot_mvgaze_amd import _lib, ops
 from rot_mvgaze_amd._lib import (BN_PASS_APPLY, BN_PASS_BWD_APPLY, BN_PASS_BWD_REDUCE, BN_PASS_EVAL_BWD, BN_PASS_FINALIZE,
@@ -19,7 +18,6 @@ from rot_mvgaze_amd._lib import (BN_PASS_APPLY, BN_PASS_BWD_APPLY, BN_PASS_BWD_R
 import bn_forms_ref as ref
 from bn_forms_ref import BF16, EPS, FP32, MOMENTUM, SP
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 @pytest.fixture()
@@ -118,21 +116,14 @@ def test_mask_bytes_and_dy_scale():
 
 # ---------------------------------------------------------------- the query
 def test_bn_plan_query_is_declared_and_bound():
-    hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    m = re.search(r"\bint\s+mvg_bn_plan_query\s*\(([^;]*)\);", hdr)
-    assert m and len(m.group(1).split(",")) == 11
-    res, args = _lib.SIGNATURES["mvg_bn_plan_query"]
-    assert res is _lib._I and len(args) == 11 and hasattr(_lib.lib(), "mvg_bn_plan_query")
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr) and _lib.ABI_VERSION == 13 == _lib.lib().mvg_abi_version()
-    m = re.search(r"typedef struct \{([^}]*)\} mvg_bn_plan;", hdr, re.S)
-    fields = re.findall(r"\bint(?:32|64)_t\s+([^;]*);", m.group(1))
-    names = [n.strip() for f in fields for n in f.split(",")]
-    assert names == [n for n, _ in BnPlan._fields_]
+    assert hdr.functions["mvg_bn_plan_query"][0] == "int" and hdr.arity("mvg_bn_plan_query") == 11
+    (_, elem, G, rows, Cc), _ = next(iter(ref.STREAM_CASES.items()))
+    assert hdr.field_names("mvg_bn_plan") == list(ops.bn_plan_query(BN_PASS_APPLY, elem, G, rows, Cc))
     assert C.sizeof(BnPlan) == 8 + 9 * 4 + 4 + 2 * 8 + 4 * 4 + 8
     for group, prefix in ((("APPLY", "BWD_APPLY", "BWD_REDUCE", "EVAL_BWD", "POOL_BWD_REDUCE", "POOL_EVAL_BWD", "FINALIZE"), "BN_PASS_"),
                           (("FP32", "BF16", "SP"), "BN_ELEM_"), (("WALK_GROUPS", "ALL_GROUPS", "PER_GROUP"), "BN_MERGE_")):
         for k, name in enumerate(group):
-            assert re.search(r"\bMVG_%s%s = %d\b" % (prefix, name, k), hdr) and getattr(_lib, prefix + name) == k
+            assert hdr.constants["MVG_" + prefix + name] == getattr(_lib, prefix + name) == k
     assert (ref.FP32, ref.BF16, ref.SP) == (_lib.BN_ELEM_FP32, _lib.BN_ELEM_BF16, _lib.BN_ELEM_SP)
     assert (ref.WALK_GROUPS, ref.ALL_GROUPS, ref.PER_GROUP) == (_lib.BN_MERGE_WALK_GROUPS, _lib.BN_MERGE_ALL_GROUPS, _lib.BN_MERGE_PER_GROUP)
 

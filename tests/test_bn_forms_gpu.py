@@ -241,9 +241,11 @@ def _finalize_launch(stats, G, P, rows, Cc, gamma, beta, rm, rv, outs, scratch):
         side = torch.cuda.Stream()                           # a stream nobody registered a workspace for
         side.wait_stream(torch.cuda.current_stream())
         ptr = lambda t: C.c_void_p(t.data_ptr() if t is not None else None)
+        mean, invstd, scale, shift = outs
         with torch.cuda.stream(side):
             rc = lib().mvg_bn_finalize(ptr(stats), G, P, ROWS_PER_PARTIAL, rows, Cc, ptr(gamma), ptr(beta), ptr(rm), ptr(rv),
-                                       C.c_float(MOMENTUM), C.c_float(EPS), *[ptr(t) for t in outs], C.c_void_p(side.cuda_stream))
+                                       C.c_float(MOMENTUM), C.c_float(EPS), ptr(mean), ptr(invstd), ptr(scale), ptr(shift),
+                                       C.c_void_p(side.cuda_stream))
         assert rc == 0
         side.synchronize()
     torch.cuda.synchronize()

@@ -1,14 +1,10 @@
 """Which block outputs are formed inside the next block's conv1 forward launch (backbone.bn_apply_fprop_eligible /
 bn_apply_fprop_pairs): decided from the architecture plan and the mode alone, no GPU.  And the new C entries' declarations."""
-import os
-import re
-
+import cabi_header as hdr
 import rot_mvgaze_amd  # noqa: F401
-from rot_mvgaze_amd import _lib
 from rot_mvgaze_amd.arch import ConvSpec, backbone_spec
 from rot_mvgaze_amd.backbone import Backbone, bn_apply_fprop_eligible, bn_apply_fprop_pairs
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 P = "_feat_extractor.0."
 R50_PAIRS = [(P + "layer1.0.conv3", P + "layer1.1.conv1"), (P + "layer1.1.conv3", P + "layer1.2.conv1"),
              (P + "layer1.2.conv3", P + "layer2.0.conv1"), (P + "layer2.0.conv3", P + "layer2.1.conv1"),
@@ -63,11 +59,6 @@ def test_switch_defaults_on():
 
 
 def test_new_entries_are_declared_and_have_signatures():
-    hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
     for name, nargs in (("mvg_conv_fprop_split_bnapply", 17), ("mvg_conv_fprop_split_stages", 1)):
-        m = re.search(r"\bint\s+%s\s*\(([^;]*)\);" % name, hdr)
-        assert m, name + " is not declared in include/rotmvgaze.h"
-        assert len(m.group(1).split(",")) == nargs
-        res, args = _lib.SIGNATURES[name]
-        assert res is _lib._I and len(args) == nargs
-    assert hasattr(_lib.lib(), "mvg_conv_fprop_split_bnapply")
+        assert name in hdr.functions, name + " is not declared in include/rotmvgaze.h"
+        assert hdr.functions[name][0] == "int" and hdr.arity(name) == nargs

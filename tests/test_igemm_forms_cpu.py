@@ -4,11 +4,10 @@ consistent, for every case of tests/test_igemm_forms_gpu.py, with the class tabl
 enumerator of the stream-K unit space those tests name their structures with (igemm_forms_ref.streamk_structures), on unit
 spaces written out by hand."""
 import ctypes as C
-import os
-import re
 
 import pytest
 
+import cabi_header as hdr
 import rot_mvgaze_amd  # noqa: F401
 from rot_mvgaze_amd import _lib, ops
 from rot_mvgaze_amd._lib import ConvDesc, ConvPlan
@@ -16,7 +15,6 @@ from rot_mvgaze_amd._lib import ConvDesc, ConvPlan
 import igemm_forms_ref as ref
 from igemm_forms_ref import BWD, FWD, streamk_structures
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
 def desc(case):
@@ -36,22 +34,14 @@ def reserve():
 
 
 def test_plan_queries_are_declared_and_have_signatures():
-    hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
     for name, nargs in (("mvg_conv_plan_query", 4), ("mvg_conv_wgrad_tile", 4)):
-        m = re.search(r"\bint\s+%s\s*\(([^;]*)\);" % name, hdr)
-        assert m, name + " is not declared in include/rotmvgaze.h"
-        assert len(m.group(1).split(",")) == nargs
-        res, args = _lib.SIGNATURES[name]
-        assert res is _lib._I and len(args) == nargs
-        assert hasattr(_lib.lib(), name)
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr) and _lib.ABI_VERSION == 13 == _lib.lib().mvg_abi_version()
-    # the binding's struct is the header's: seven int32 declarations (15 values) and one int64
-    m = re.search(r"typedef struct \{([^}]*)\} mvg_conv_plan;", hdr)
-    assert m and len(re.findall(r"\bint32_t\b", m.group(1))) == 7 and len(re.findall(r"\bint64_t\b", m.group(1))) == 1
-    assert C.sizeof(ConvPlan) == 15 * 4 + 4 + 8 and [n for n, _ in ConvPlan._fields_] == \
+        assert name in hdr.functions, name + " is not declared in include/rotmvgaze.h"
+        assert hdr.functions[name][0] == "int" and hdr.arity(name) == nargs
+    # the plan struct: 15 int32 values (two arrays of 4 among them) and one int64, under these names
+    assert C.sizeof(ConvPlan) == 15 * 4 + 4 + 8 and hdr.field_names("mvg_conv_plan") == \
         ["bm", "bn", "bk", "fasta", "ncls", "cls_tiles", "cls_kt", "streamk_grid", "splitk", "scratch_floats"]
     for k, name in enumerate(("MVG_PLAN_FPROP", "MVG_PLAN_FPROP_STATS", "MVG_PLAN_DGRAD", "MVG_PLAN_FUSER_FPROP")):
-        assert re.search(r"\b%s = %d\b" % (name, k), hdr)
+        assert hdr.constants[name] == k
     assert (_lib.PLAN_FPROP, _lib.PLAN_FPROP_STATS, _lib.PLAN_DGRAD, _lib.PLAN_FUSER_FPROP) == (0, 1, 2, 3)
 
 

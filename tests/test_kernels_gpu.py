@@ -645,8 +645,8 @@ def test_bn_finalize_with_and_without_registered_scratch_agree_bit_for_bit(G, P,
             with torch.cuda.stream(side):
                 rc = lib().mvg_bn_finalize(C_.c_void_p(stats.data_ptr()), G, P, 64, rows, C, C_.c_void_p(gamma.data_ptr()),
                                            C_.c_void_p(beta.data_ptr()), C_.c_void_p(rm.data_ptr()), C_.c_void_p(rv.data_ptr()),
-                                           C_.c_float(0.1), C_.c_float(1e-5), *[C_.c_void_p(t.data_ptr()) for t in o],
-                                           C_.c_void_p(side.cuda_stream))
+                                           C_.c_float(0.1), C_.c_float(1e-5), C_.c_void_p(o[0].data_ptr()), C_.c_void_p(o[1].data_ptr()),
+                                           C_.c_void_p(o[2].data_ptr()), C_.c_void_p(o[3].data_ptr()), C_.c_void_p(side.cuda_stream))
             assert rc == 0
             side.synchronize()
         torch.cuda.synchronize()

