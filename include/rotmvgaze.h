@@ -385,6 +385,19 @@ int mvg_augment_u8hwc(const uint8_t *src, const mvg_augment_rec *recs, const mvg
                       uint8_t *dst_u8, float *dst_nhwc4, const float *masks, const int32_t *grid, int gmax, int n,
                       int h, int w, float mean0, float mean1, float mean2, float std0, float std1, float std2,
                       int swap_rb, void *stream);
+/* The same launch straight into the bf16 stem's operand (training steps of the bf16 storage path on raw patches: no
+ * fp32 image in between).  Every value is mvg_augment_u8hwc's dst_nhwc4 value - normalised, times the keep-mask -
+ * rounded once to bf16 (nearest even).  Destinations, at least one, both from one launch allowed:
+ * dst_nhwc8 [n][h][w][8], channels 3..7 zero (mvg_preprocess_u8hwc_resize_bf16's layout), and / or dst_rw
+ * [n][h][w/4][64], mvg_stem_rowwindow_bf16's folded row windows: window m of an image row holds image columns
+ * 4m-4 .. 4m+11 x (r, g, b, 0); columns outside [0, w) are bf16 zero (padding - the pixels the affine map fills are
+ * inside the image and carry normalised black).  dst_rw needs w % 4 == 0.  The launch writes every byte of its
+ * destinations, which may arrive uninitialised.  The other arguments and checks are mvg_augment_u8hwc's.
+ * (Added under ABI v13: additive.) */
+int mvg_augment_u8hwc_bf16(const uint8_t *src, const mvg_augment_rec *recs, const mvg_augment_rec *recs_host,
+                           uint16_t *dst_nhwc8, uint16_t *dst_rw, const float *masks, const int32_t *grid, int gmax,
+                           int n, int h, int w, float mean0, float mean1, float mean2, float std0, float std1,
+                           float std2, int swap_rb, void *stream);
 
 /* ---------------------------------------------------------------- geometry
  * rotation_matrix_2d utils/math.py:188-219; relative rotations rot_mv.py:193-194. */

@@ -170,6 +170,7 @@ SIGNATURES = {
     "mvg_preprocess_u8hwc_resize": (_I, [_P, _P, _I, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mvg_multi_erase_nchw": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mvg_augment_u8hwc": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
+    "mvg_augment_u8hwc_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mvg_rotation_matrix_2d": (_I, [_P, _P, _I, _I, _P]),
     "mvg_relative_rotation": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "mvg_rotcat_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

@@ -98,7 +98,7 @@ def _jitter_range(name: str, value: float) -> Optional[Tuple[float, float]]:
 class TrainAugment:
     """ColorJitter(brightness, contrast, saturation) -> RandomAffine(degrees=0, scale, translate) -> ToTensor ->
     Normalize -> RandomMultiErasing of main.py:41-49 on a device batch of raw uint8 [n, h, w, 3] patches, one HIP launch
-    (mvg_augment_u8hwc).  The pixel arithmetic is Pillow's, bit for bit (what torchvision runs on the PIL image; pinned by
+    (mvg_augment_u8hwc; mvg_augment_u8hwc_bf16 stores the bf16 stem's operand instead).  The pixel arithmetic is Pillow's, bit for bit (what torchvision runs on the PIL image; pinned by
     tests/golden/color_affine.npz).  Patches keep their size: the reference's Resize(224) is the identity on the
     datasets' 224 x 224 patches, and a resize after the augmentation is not served.
 
@@ -150,21 +150,29 @@ class TrainAugment:
                 erase += self.erase.draw(1)
         return AugmentDraws(recs, erase)
 
-    def launch(self, u8: Tensor, draws: AugmentDraws, dst_u8: Optional[Tensor], dst_nhwc4: Optional[Tensor], bgr: bool = False) -> None:
+    def launch(self, u8: Tensor, draws: AugmentDraws, dst_u8: Optional[Tensor], dst_nhwc4: Optional[Tensor], bgr: bool = False, *,
+               dst_nhwc8: Optional[Tensor] = None, dst_rw: Optional[Tensor] = None) -> None:
         """One launch into caller-owned destinations (uint8 [n, h, w, 3] and / or fp32 [n, h, w, 4]); one host-to-device copy
-        carries the records (and, with erase draws, one each the masks and grid sizes)."""
+        carries the records (and, with erase draws, one each the masks and grid sizes).  dst_nhwc8 (bf16 [n, h, w, 8]) and /
+        or dst_rw (bf16 [n, h, w/4, 64], the bf16 stem's row windows: w % 4 == 0): the same launch straight into the bf16
+        stem's operand (mvg_augment_u8hwc_bf16), the fp32 value rounded once; not together with dst_u8 / dst_nhwc4."""
+        bf16 = dst_nhwc8 is not None or dst_rw is not None
+        if bf16 and (dst_u8 is not None or dst_nhwc4 is not None):
+            raise ValueError("TrainAugment: bf16 destinations (dst_nhwc8, dst_rw) and dst_u8 / dst_nhwc4 take a launch each")
         if not u8.is_cuda:
             raise RuntimeError("TrainAugment (MI355X build) works on device batches: no CPU fallback")
         if u8.dim() != 4 or u8.shape[3] != 3 or u8.dtype != torch.uint8:
             raise ValueError(f"TrainAugment: expected uint8 [n, h, w, 3] patches (got {u8.dtype} {tuple(u8.shape)})")
         n, h, w, _ = u8.shape
+        if dst_rw is not None and w % 4:
+            raise ValueError(f"TrainAugment: the bf16 row windows need a width that is a multiple of 4 (got {w})")
         recs = np.ascontiguousarray(draws.recs, dtype=REC_DTYPE)
         if recs.shape != (n,):
             raise ValueError(f"TrainAugment: {recs.shape[0] if recs.ndim else 0} records for {n} images")
         masks = grid = None
         gmax = 0
         if draws.erase is not None and any(g for g, _ in draws.erase):
-            if dst_nhwc4 is None:
+            if dst_nhwc4 is None and not bf16:
                 raise ValueError("TrainAugment: the erase multiplies the normalised image: out='u8' needs erase=None")
             assert len(draws.erase) == n
             gmax = max(g for g, _ in draws.erase)
@@ -175,18 +183,34 @@ class TrainAugment:
                     mh[i, : g * g] = m.reshape(-1)
             masks, grid = mh.to(u8.device), gh.to(u8.device)
         dev_recs = torch.from_numpy(recs.view(np.uint8).reshape(-1)).to(u8.device)
-        ops.augment_u8hwc(u8.contiguous(), dev_recs, dst_u8, dst_nhwc4, masks, grid, gmax, n, h, w, IMAGE_MEAN, IMAGE_STD, bgr,
-                          recs_host=recs)
+        if bf16:
+            ops.augment_u8hwc_bf16(u8.contiguous(), dev_recs, dst_nhwc8, dst_rw, masks, grid, gmax, n, h, w, IMAGE_MEAN, IMAGE_STD, bgr,
+                                   recs_host=recs)
+        else:
+            ops.augment_u8hwc(u8.contiguous(), dev_recs, dst_u8, dst_nhwc4, masks, grid, gmax, n, h, w, IMAGE_MEAN, IMAGE_STD, bgr,
+                              recs_host=recs)
 
     def apply(self, u8: Tensor, draws: AugmentDraws, out: str = "nhwc4", bgr: bool = False) -> Tensor:
         """u8 [n, h, w, 3] uint8 on the GPU (bgr: stored BGR) -> ``"nhwc4"``: fp32 [n, h, w, 4], the backbone's input layout
         (channel 3 zero); ``"nchw"``: fp32 [n, 3, h, w], the reference transform's output format (for callers outside the
-        model, and for bf16 training); ``"u8"``: uint8 [n, h, w, 3] RGB, the image before ToTensor (no erase)."""
-        if out not in ("nhwc4", "u8", "nchw"):
-            raise ValueError(f"out must be 'nhwc4', 'u8' or 'nchw' (got {out!r})")
+        model); ``"u8"``: uint8 [n, h, w, 3] RGB, the image before ToTensor (no erase); ``"nhwc8_bf16"``: bf16 [n, h, w, 8],
+        the nhwc4 values rounded once, channels 3..7 zero; ``"rw_bf16"``: bf16 [n, h, w/4, 64], the bf16 stem's row windows of
+        that image (ops.stem_rowwindow_bf16's layout; w % 4 == 0) - the two operands of the bf16 stem, one launch each."""
+        if out not in ("nhwc4", "u8", "nchw", "nhwc8_bf16", "rw_bf16"):
+            raise ValueError(f"out must be 'nhwc4', 'u8', 'nchw', 'nhwc8_bf16' or 'rw_bf16' (got {out!r})")
         if not u8.is_cuda:
             raise RuntimeError("TrainAugment (MI355X build) works on device batches: no CPU fallback")
         n, h, w = u8.shape[:3]
+        if out == "rw_bf16":
+            if w % 4:
+                raise ValueError(f"out='rw_bf16': the bf16 row windows need a width that is a multiple of 4 (got {w})")
+            dst = torch.empty(n, h, w // 4, 64, dtype=torch.bfloat16, device=u8.device)
+            self.launch(u8, draws, None, None, bgr, dst_rw=dst)
+            return dst
+        if out == "nhwc8_bf16":
+            dst = torch.empty(n, h, w, 8, dtype=torch.bfloat16, device=u8.device)
+            self.launch(u8, draws, None, None, bgr, dst_nhwc8=dst)
+            return dst
         if out == "u8":
             dst = torch.empty(n, h, w, 3, dtype=torch.uint8, device=u8.device)
             self.launch(u8, draws, dst, None, bgr)

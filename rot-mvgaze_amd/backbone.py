@@ -572,11 +572,13 @@ class Backbone:
         row-window form (no NHWC image is built); else the NHWC image padded to 4 (bf16: 8) channels, from raw uint8 patches
         or NCHW fp32 - and the windows from that image for raw input with a row-window stem.  augment (training steps on raw
         patches: an augment.TrainAugment): its launch - ColorJitter, RandomAffine, ToTensor, Normalize, erase - takes the
-        place of the preprocess launch; the draws are host work, taken in view order, then image order.
+        place of the preprocess launch; the draws are host work, taken in view order, then image order.  On the bf16 path
+        that launch stores the stem's operand itself - the row windows when the stem runs in row-window form, else the NHWC8
+        image - rounded once from the fp32 value: one launch per view, no fp32 image in between.
         (The bf16 branch without a row-window stem is restated by csrc/session_plan.cpp's build_bf16.)"""
         V, dev, bf = len(imgs), imgs[0].device, self.bf16
         raw = imgs[0].dtype == torch.uint8
-        direct = self._stem_rw and not raw
+        direct = self._stem_rw and (not raw or (bf and augment is not None))    # each view's launch writes the windows itself
         if direct and bf:
             x0 = torch.empty(V, B, H, W // 4, 64, dtype=self.act_dtype, device=dev)
         elif direct:
@@ -593,9 +595,14 @@ class Backbone:
                 if torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("input_augment draws on the host for every step and cannot be captured (graph.GraphedStep): "
                                        "augment outside the captured step (TrainAugment.apply) and feed the result")
-                augment.launch(im, augment.draw(B, H, W), None, x0[v], input_bgr)
+                if bf and direct:
+                    augment.launch(im, augment.draw(B, H, W), None, None, input_bgr, dst_rw=x0[v])
+                elif bf:
+                    augment.launch(im, augment.draw(B, H, W), None, None, input_bgr, dst_nhwc8=x0[v])
+                else:
+                    augment.launch(im, augment.draw(B, H, W), None, x0[v], input_bgr)
                 continue
-            if raw:                             # (bf16: inference only - no fp32 image in between)
+            if raw:                             # (bf16: no fp32 image in between)
                 prep = ops.preprocess_u8hwc_resize_bf16 if bf else ops.preprocess_u8hwc_resize
                 prep(im.contiguous(), x0[v], B, im.shape[1], im.shape[2], H, W, IMAGE_MEAN, IMAGE_STD, input_bgr)
                 continue
@@ -614,7 +621,9 @@ class Backbone:
         V raw uint8 [B,H,W,3] face patches, put through test_transform of main.py:50-55 on the GPU
         (ToTensor, Resize((input_size, input_size), antialias=True) when the patch has another size,
         Normalize) - in a training step with input_augment (augment.TrainAugment) through the random
-        part of train_transform (main.py:41-49) as well.  Returns (img_feat [V,B,fc_dim], tape or None)."""
+        part of train_transform (main.py:41-49) as well.  The bf16 path takes raw patches for inference and, with
+        input_augment, for training steps (the augment launch stores the bf16 stem operand); a training step or a taped
+        forward on raw patches without it raises NotImplementedError.  Returns (img_feat [V,B,fc_dim], tape or None)."""
         V = len(imgs)
         raw = imgs[0].dtype == torch.uint8
         if raw:
@@ -624,9 +633,10 @@ class Backbone:
             B, C, H, W = imgs[0].shape
         assert C == 3
         dev = imgs[0].device
-        if self.bf16 and raw and (training or keep_tape):
+        if self.bf16 and raw and (training or keep_tape) and not (training and input_augment is not None):
             raise NotImplementedError("raw uint8 input with the bf16 path is served for inference only (model.eval() under "
-                                      "torch.no_grad()): for training steps normalise to fp32 NCHW first")
+                                      "torch.no_grad()) and for training steps with model.input_augment (augment.TrainAugment; the "
+                                      "identity augment for un-augmented steps): else normalise to fp32 NCHW first")
         # The split kernels address one view of an sp tensor (4 bytes per element) with 32-bit offsets: the largest one
         # (layer1's output: (H/4) x (W/4) x 64 or 256 channels per image) must stay below 2 GiB, or this call runs on the
         # fp32-MFMA kernels (64-bit row offsets there; B < 668 per view at 224 x 224 with ResNet-50)

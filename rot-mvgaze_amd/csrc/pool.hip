@@ -347,12 +347,30 @@ __device__ __forceinline__ void aug_op(int op, float f0, float f1, float f2, int
   b = aug_blend(deg, (float)b, f);
 }
 
-__global__ __launch_bounds__(kAugThreads) void augment_u8_kernel(const unsigned char *__restrict__ src,
-                                                                 const mvg_augment_rec *__restrict__ recs,
-                                                                 unsigned char *__restrict__ dst_u8, float4 *__restrict__ dst_f,
-                                                                 const float *__restrict__ masks, const int *__restrict__ grid,
-                                                                 int gmax, int h, int w, float m0, float m1, float m2, float s0,
-                                                                 float s1, float s2, int swap_rb) {
+// The destinations, chosen at compile time (the fp32 / uint8 kernel is the one of before the bf16 destinations came):
+//   kAugF32: dst_u8 [n][h][w][3] and / or dst_f [n][h][w] float4;
+//   kAugNhwc8: dst_h [n][h][w] uint4 = 8 bf16, the fp32 value rounded once by bf16_pack2, channels 3..7 zero
+//     (preprocess_u8_bf16_kernel's layout);
+//   kAugRw: dst_rw, stem_rowwindow_bf16_kernel's folded row windows [n][h][w/4][8] uint4 - chunk q of window m holds
+//     image columns 4 m - 4 + 2 q and the next one x (r, g, b, 0), zero outside [0, w) - and, optionally, dst_h.
+// kAugRw walks phase B in column pairs (w % 4 == 0: a pair stays in its row, h*w is even): a thread's four pixels of a
+// pass are two pairs, and the pair at column 4 k + 2 e is chunk e + 2 t of window k + 1 - t for t = 0..3 where that window
+// exists: four 16-byte stores.  The chunks no pixel lands in are the row's padding: 2 in front of window 0, 4 behind the
+// last window and 2 behind the one before it; a loop of its own zeroes them, so that every byte of dst_rw is written.
+enum { kAugF32 = 0, kAugNhwc8 = 1, kAugRw = 2 };
+
+// pixel u of a thread's batch in the pass that starts at pixel p0 (kAugF32 / kAugNhwc8: p0 already holds tid)
+template <int kDst>
+__device__ __forceinline__ int aug_pixel(int p0, int tid, int u) {
+  return kDst == kAugRw ? p0 + 2 * (tid + (u >> 1) * kAugThreads) + (u & 1) : p0 + u * kAugThreads;
+}
+
+template <int kDst>
+__device__ __forceinline__ void augment_u8_body(const unsigned char *__restrict__ src, const mvg_augment_rec *__restrict__ recs,
+                                                unsigned char *__restrict__ dst_u8, float4 *__restrict__ dst_f,
+                                                uint4 *__restrict__ dst_h, uint4 *__restrict__ dst_rw,
+                                                const float *__restrict__ masks, const int *__restrict__ grid, int gmax, int h,
+                                                int w, float m0, float m1, float m2, float s0, float s1, float s2, int swap_rb) {
   __shared__ short xtab[kAugMaxSide], ytab[kAugMaxSide];
   __shared__ unsigned wave_part[kAugThreads / 64];
   __shared__ int mean_s;
@@ -417,21 +435,23 @@ __global__ __launch_bounds__(kAugThreads) void augment_u8_kernel(const unsigned 
   const int gcells = grid ? (grid[img] < gmax ? grid[img] : gmax) : 0;      // (never past the image's gmax x gmax slot)
   const float *mk = masks + (long long)img * gmax * gmax;
   const float sy = (float)gcells / (float)h, sx = (float)gcells / (float)w;
-  for (int p0 = tid; p0 < hw; p0 += kAugThreads * kAugBatch) {
+  const int wm = w >> 2;                                 // (kAugRw) windows per image row
+  for (int p0 = kDst == kAugRw ? 0 : tid; p0 < hw; p0 += kAugThreads * kAugBatch) {
     int r[kAugBatch], g[kAugBatch], b[kAugBatch], y[kAugBatch], x[kAugBatch];
     bool inside[kAugBatch];
 #pragma unroll
     for (int u = 0; u < kAugBatch; ++u) {
-      const int p = p0 + u * kAugThreads, pc = p < hw ? p : hw - 1;
+      const int p = aug_pixel<kDst>(p0, tid, u), pc = p < hw ? p : hw - 1;
       y[u] = pc / w, x[u] = pc - y[u] * w;
       const int ys = ytab[y[u]], xsrc = xtab[x[u]];
       inside[u] = ys >= 0 && xsrc >= 0;
       const unsigned char *q = in + (inside[u] ? (ys * w + xsrc) * 3 : 0);      // fill: pixel 0 is read and dropped
       r[u] = q[ir], g[u] = q[1], b[u] = q[ib];
     }
+    uint2 even = make_uint2(0u, 0u);                      // (kAugRw) the pair's first pixel, packed
 #pragma unroll
     for (int u = 0; u < kAugBatch; ++u) {
-      const int p = p0 + u * kAugThreads;
+      const int p = aug_pixel<kDst>(p0, tid, u);
       if (p >= hw) break;
       if (inside[u]) {
         aug_op(o0, f0, f1, f2, m, r[u], g[u], b[u]);
@@ -441,11 +461,11 @@ __global__ __launch_bounds__(kAugThreads) void augment_u8_kernel(const unsigned 
         r[u] = g[u] = b[u] = 0;                            // fill: zeros, AFTER the jitter
       }
       const long long o = (long long)img * hw + p;
-      if (dst_u8) {
+      if (kDst == kAugF32 && dst_u8) {
         unsigned char *d = dst_u8 + 3 * o;
         d[0] = (unsigned char)r[u], d[1] = (unsigned char)g[u], d[2] = (unsigned char)b[u];
       }
-      if (dst_f) {
+      if (kDst != kAugF32 || dst_f) {
         float c0 = (float)r[u], c1 = (float)g[u], c2 = (float)b[u];
         preprocess_u8_norm(m0, m1, m2, s0, s1, s2, c0, c1, c2);
         if (gcells > 0) {                                  // multi_erase_kernel's index rule
@@ -455,10 +475,56 @@ __global__ __launch_bounds__(kAugThreads) void augment_u8_kernel(const unsigned 
           const float keep = mk[my * gcells + mx];
           c0 *= keep, c1 *= keep, c2 *= keep;
         }
-        dst_f[o] = make_float4(c0, c1, c2, 0.f);
+        if constexpr (kDst == kAugF32) {
+          dst_f[o] = make_float4(c0, c1, c2, 0.f);
+        } else {
+          const uint2 px = make_uint2(bf16_pack2(c0, c1), bf16_pack2(c2, 0.f));
+          if (kDst == kAugNhwc8 || dst_h) dst_h[o] = make_uint4(px.x, px.y, 0u, 0u);
+          if constexpr (kDst == kAugRw) {
+            if (u & 1) {                                   // x[u] is the pair's odd column: 4 k + 2 e + 1
+              const int k = x[u] >> 2, e = (x[u] >> 1) & 1;
+              uint4 *row = dst_rw + ((long long)img * h + y[u]) * wm * 8;
+              const uint4 chunk = make_uint4(even.x, even.y, px.x, px.y);
+#pragma unroll
+              for (int t = 0; t < 4; ++t) {
+                const int mw = k + 1 - t;
+                if (mw >= 0 && mw < wm) row[mw * 8 + e + 2 * t] = chunk;
+              }
+            } else {
+              even = px;
+            }
+          }
+        }
       }
     }
   }
+  if constexpr (kDst == kAugRw) {                          // the padding chunks: 8 per row (6 when the row is one window)
+    for (int i = tid; i < h * 8; i += kAugThreads) {
+      const int yy = i >> 3, s = i & 7;
+      const int mw = s < 2 ? 0 : (s < 6 ? wm - 1 : wm - 2), q = (s < 2 || s >= 6) ? s : s + 2;
+      if (mw >= 0) dst_rw[(((long long)img * h + yy) * wm + mw) * 8 + q] = make_uint4(0u, 0u, 0u, 0u);
+    }
+  }
+}
+
+__global__ __launch_bounds__(kAugThreads) void augment_u8_kernel(const unsigned char *__restrict__ src,
+                                                                 const mvg_augment_rec *__restrict__ recs,
+                                                                 unsigned char *__restrict__ dst_u8, float4 *__restrict__ dst_f,
+                                                                 const float *__restrict__ masks, const int *__restrict__ grid,
+                                                                 int gmax, int h, int w, float m0, float m1, float m2, float s0,
+                                                                 float s1, float s2, int swap_rb) {
+  augment_u8_body<kAugF32>(src, recs, dst_u8, dst_f, nullptr, nullptr, masks, grid, gmax, h, w, m0, m1, m2, s0, s1, s2, swap_rb);
+}
+// ... straight to the bf16 stem's operand: NHWC8 (kRw false: any width) or the row windows, with or without NHWC8
+template <bool kRw>
+__global__ __launch_bounds__(kAugThreads) void augment_u8_bf16_kernel(const unsigned char *__restrict__ src,
+                                                                      const mvg_augment_rec *__restrict__ recs,
+                                                                      uint4 *__restrict__ dst_h, uint4 *__restrict__ dst_rw,
+                                                                      const float *__restrict__ masks, const int *__restrict__ grid,
+                                                                      int gmax, int h, int w, float m0, float m1, float m2, float s0,
+                                                                      float s1, float s2, int swap_rb) {
+  augment_u8_body<kRw ? kAugRw : kAugNhwc8>(src, recs, nullptr, nullptr, dst_h, dst_rw, masks, grid, gmax, h, w, m0, m1, m2, s0, s1,
+                                            s2, swap_rb);
 }
 
 }  // namespace mvg
@@ -615,11 +681,13 @@ int mvg_multi_erase_nchw(float *img, const float *masks, const int32_t *grid, in
   return check_launch("multi_erase");
 }
 
-int mvg_augment_u8hwc(const uint8_t *src, const mvg_augment_rec *recs, const mvg_augment_rec *recs_host, uint8_t *dst_u8,
-                      float *dst_nhwc4, const float *masks, const int32_t *grid, int gmax, int n, int h, int w, float mean0,
-                      float mean1, float mean2, float std0, float std1, float std2, int swap_rb, void *stream) {
+// the checks of the two augment entry points, in one order (0, or MVG_REQUIRE's status with the message set); no_dst /
+// bad_erase: the entry point's own message when it has no destination / cannot serve the erase, else null
+static int augment_check(const uint8_t *src, const mvg_augment_rec *recs, const mvg_augment_rec *recs_host, const char *no_dst,
+                         const float *masks, const int32_t *grid, const char *bad_erase, int n, int h, int w, float std0, float std1,
+                         float std2) {
   MVG_REQUIRE(src && recs, "augment: src and the device records are required");
-  MVG_REQUIRE(dst_u8 || dst_nhwc4, "augment: no destination (dst_u8 and dst_nhwc4 are both null)");
+  MVG_REQUIRE(!no_dst, "%s", no_dst);
   MVG_REQUIRE(n > 0 && h > 0 && w > 0, "augment: bad sizes");
   MVG_REQUIRE(h <= kAugMaxSide && w <= kAugMaxSide, "augment: a side of %d x %d is longer than the index tables hold (%d)", h, w,
               kAugMaxSide);
@@ -627,18 +695,46 @@ int mvg_augment_u8hwc(const uint8_t *src, const mvg_augment_rec *recs, const mvg
               kAugMaxPixels);
   MVG_REQUIRE(std0 > 0.f && std1 > 0.f && std2 > 0.f, "augment: std must be positive");
   MVG_REQUIRE((masks == nullptr) == (grid == nullptr), "augment: erase masks and grid come together");
-  MVG_REQUIRE(!masks || (dst_nhwc4 && gmax > 0), "augment: the erase multiplies the normalised image (dst_nhwc4) and needs gmax > 0");
+  MVG_REQUIRE(!bad_erase, "%s", bad_erase);
   if (recs_host)
     for (int i = 0; i < n; ++i) {
       const int32_t *o = recs_host[i].order;
       MVG_REQUIRE(o[0] >= 0 && o[0] <= 2 && o[1] >= 0 && o[1] <= 2 && o[2] >= 0 && o[2] <= 2 && o[0] != o[1] && o[0] != o[2] && o[1] != o[2],
                   "augment: record %d: order (%d, %d, %d) is not a permutation of 0, 1, 2", i, o[0], o[1], o[2]);
     }
+  return 0;
+}
+
+int mvg_augment_u8hwc(const uint8_t *src, const mvg_augment_rec *recs, const mvg_augment_rec *recs_host, uint8_t *dst_u8,
+                      float *dst_nhwc4, const float *masks, const int32_t *grid, int gmax, int n, int h, int w, float mean0,
+                      float mean1, float mean2, float std0, float std1, float std2, int swap_rb, void *stream) {
+  const char *no_dst = dst_u8 || dst_nhwc4 ? nullptr : "augment: no destination (dst_u8 and dst_nhwc4 are both null)";
+  const char *bad_erase =
+      !masks || (dst_nhwc4 && gmax > 0) ? nullptr : "augment: the erase multiplies the normalised image (dst_nhwc4) and needs gmax > 0";
+  if (const int rc = augment_check(src, recs, recs_host, no_dst, masks, grid, bad_erase, n, h, w, std0, std1, std2)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_LAYOUT, st, 0.0, (double)n * h * w * (6.0 + (dst_u8 ? 3.0 : 0.0) + (dst_nhwc4 ? 16.0 : 0.0)));
   hipLaunchKernelGGL(augment_u8_kernel, dim3(n), dim3(kAugThreads), 0, st, src, recs, dst_u8, (float4 *)dst_nhwc4, masks, grid, gmax,
                      h, w, mean0, mean1, mean2, std0, std1, std2, swap_rb);
   return check_launch("augment_u8hwc");
+}
+
+int mvg_augment_u8hwc_bf16(const uint8_t *src, const mvg_augment_rec *recs, const mvg_augment_rec *recs_host, uint16_t *dst_nhwc8,
+                           uint16_t *dst_rw, const float *masks, const int32_t *grid, int gmax, int n, int h, int w, float mean0,
+                           float mean1, float mean2, float std0, float std1, float std2, int swap_rb, void *stream) {
+  const char *no_dst = dst_nhwc8 || dst_rw ? nullptr : "augment_bf16: no destination (dst_nhwc8 and dst_rw are both null)";
+  const char *bad_erase = !masks || gmax > 0 ? nullptr : "augment_bf16: the erase needs gmax > 0";
+  if (const int rc = augment_check(src, recs, recs_host, no_dst, masks, grid, bad_erase, n, h, w, std0, std1, std2)) return rc;
+  MVG_REQUIRE(!dst_rw || w % 4 == 0, "augment_bf16: the row windows (dst_rw) need w %% 4 == 0 (w = %d)", w);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_LAYOUT, st, 0.0, (double)n * h * w * (6.0 + (dst_nhwc8 ? 16.0 : 0.0) + (dst_rw ? 32.0 : 0.0)));
+  if (dst_rw)
+    hipLaunchKernelGGL(augment_u8_bf16_kernel<true>, dim3(n), dim3(kAugThreads), 0, st, src, recs, (uint4 *)dst_nhwc8, (uint4 *)dst_rw,
+                       masks, grid, gmax, h, w, mean0, mean1, mean2, std0, std1, std2, swap_rb);
+  else
+    hipLaunchKernelGGL(augment_u8_bf16_kernel<false>, dim3(n), dim3(kAugThreads), 0, st, src, recs, (uint4 *)dst_nhwc8, (uint4 *)nullptr,
+                       masks, grid, gmax, h, w, mean0, mean1, mean2, std0, std1, std2, swap_rb);
+  return check_launch("augment_u8hwc_bf16");
 }
 
 int mvg_nhwc4_to_nchw(const float *src, float *dst, int n, int c, int h, int w, void *stream) {

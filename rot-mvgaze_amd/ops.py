@@ -764,6 +764,23 @@ def augment_u8hwc(src, recs, dst_u8, dst_nhwc4, masks, grid, gmax, n, h, w, mean
                                   mean[0], mean[1], mean[2], std[0], std[1], std[2], int(swap_rb), _s()), "augment_u8hwc")
 
 
+def augment_u8hwc_bf16(src, recs, dst_nhwc8, dst_rw, masks, grid, gmax, n, h, w, mean, std, swap_rb, recs_host=None):
+    """augment_u8hwc straight into the bf16 stem's operand (mvg_augment_u8hwc_bf16): dst_nhwc8 bf16 [n, h, w, 8] and / or
+    dst_rw bf16 [n, h, w/4, 64], stem_rowwindow_bf16's row windows (w % 4 == 0); every byte of both is written."""
+    assert src.dtype == torch.uint8 and src.is_contiguous() and src.numel() == n * h * w * 3
+    assert recs.dtype == torch.uint8 and recs.is_contiguous() and recs.numel() == n * 56
+    assert dst_nhwc8 is None or (dst_nhwc8.dtype == torch.bfloat16 and dst_nhwc8.is_contiguous() and dst_nhwc8.numel() == n * h * w * 8)
+    assert dst_rw is None or (dst_rw.dtype == torch.bfloat16 and dst_rw.is_contiguous() and dst_rw.numel() == n * h * (w // 4) * 64)
+    assert masks is None or (masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() == n * gmax * gmax)
+    assert grid is None or (grid.dtype == torch.int32 and grid.is_contiguous() and grid.numel() == n)
+    host = None
+    if recs_host is not None:
+        assert recs_host.flags["C_CONTIGUOUS"] and recs_host.nbytes == n * 56
+        host = C.c_void_p(recs_host.ctypes.data)
+    check(lib().mvg_augment_u8hwc_bf16(_p(src), _p(recs), host, _p(dst_nhwc8), _p(dst_rw), _p(masks), _p(grid), gmax, n, h, w,
+                                       mean[0], mean[1], mean[2], std[0], std[1], std[2], int(swap_rb), _s()), "augment_u8hwc_bf16")
+
+
 def preprocess_u8hwc_resize(src, dst, n, h, w, oh, ow, mean, std, swap_rb):
     check(lib().mvg_preprocess_u8hwc_resize(_p(src), _p(dst), n, h, w, oh, ow, mean[0], mean[1], mean[2], std[0], std[1],
                                             std[2], int(swap_rb), _s()), "preprocess_u8hwc_resize")
