@@ -475,6 +475,18 @@ int mvg_adam_step(float *param, const float *grad, float *exp_avg, float *exp_av
  * sqrt(1 - beta2^step)} - zero-initialised, advanced by a one-thread launch in front of the update. */
 int mvg_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev,
                       float *state3, float beta1, float beta2, float eps, float weight_decay, void *stream);
+/* The step of mvg_adam_step over SEGMENTS of the arenas only - parameter groups with their own hyper-parameters, parameters
+ * without a gradient left out (fine-tuning: optim.Adam).  Segment i is the element range [host_bounds[2 i], host_bounds[2 i + 1])
+ * (both multiples of 4, begin < end, inside [0, n)), updated with host_hyper[5 i ..] = {lr, beta1, beta2, eps, weight_decay} and
+ * the bias corrections of its OWN step count host_steps[i] >= 1 (computed on the host in double, as mvg_adam_step does).  The
+ * three arrays are HOST memory, sorted by begin and disjoint; anything else is rejected before the first launch.  Each launch
+ * takes up to MVG_ADAM_MAX_SEGMENTS segments by value in its kernel arguments (no device table, no copy); more segments are more
+ * launches.  Elements outside every segment are neither read nor written: a launch moves 28 B per element of its segments.
+ * A segment's result equals, bit for bit, mvg_adam_step over that slice with the same hyper-parameters and step. */
+enum { MVG_ADAM_MAX_SEGMENTS = 16 };
+int mvg_adam_step_segments(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                           const int64_t *host_bounds, const float *host_hyper, const int32_t *host_steps, int n_segments,
+                           void *stream);
 
 /* ---------------------------------------------------------------- loss
  * gaze_angular_loss losses/gaze_loss.py:42-52 over pitchyaw_to_vector utils/math.py:52-60:

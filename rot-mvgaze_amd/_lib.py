@@ -14,6 +14,7 @@ LIB_PATH = os.path.join(_HERE, "csrc", "librotmvgaze_hip.so")
 K_FAMILIES = 18
 ABI_VERSION = 13
 SESSION_FP32, SESSION_BF16 = 0, 1         # MVG_SESSION_FP32 / MVG_SESSION_BF16 (mvg_session_create_ex)
+ADAM_MAX_SEGMENTS = 16                    # MVG_ADAM_MAX_SEGMENTS: segments per launch of mvg_adam_step_segments
 
 
 class ConvDesc(C.Structure):
@@ -189,6 +190,7 @@ SIGNATURES = {
     "mvg_gaze_angular_loss": (_I, [_P, _P, _I, _F, _P, _I, _P, _P, _P]),
     "mvg_gaze_angular_loss_multi": (_I, [_P, _P, _I, _I, _I, C.POINTER(C.c_float), _P, _P, _P]),
     "mvg_adam_step_dev": (_I, [_P, _P, _P, _P, _I64, _P, _P, _F, _F, _F, _F, _P]),
+    "mvg_adam_step_segments": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), _I, _P]),
     # the fusion block on the split kernels
     "mvg_absmax_multi": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), _I, _P]),
     "mvg_fuse_build_split": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -91,10 +91,15 @@ def bn_apply_fprop_pairs(spec: BackboneSpec, *, split: bool = True, bf16: bool =
 class GradSink:
     """Where parameter gradients go.  ``view(p)`` returns the tensor the kernels write into and
     ``accumulate(p)`` says whether they must add to it; ``publish(ps)`` is called once a group of
-    parameters has its final gradient (in grad-ready order: DP buckets hang off this)."""
+    parameters has its final gradient (in grad-ready order: DP buckets hang off this).  ``wants(p)`` is False for a
+    parameter this backward owes no gradient (``requires_grad = False``): a launch that would write its gradient alone is
+    not made, and ``publish`` leaves it out."""
 
     def view(self, p: torch.nn.Parameter) -> Tensor:
         raise NotImplementedError
+
+    def wants(self, p: torch.nn.Parameter) -> bool:
+        return True
 
     def accumulate(self, p: torch.nn.Parameter) -> bool:
         raise NotImplementedError
@@ -668,7 +673,7 @@ class Backbone:
         # ... and one launch gives every sp activation of the step its scale (x, out and identity carry it as .sinv; the
         # tape's x_in / out keep it for the backward's weight gradients)
         self._act_sinv = self._prepare_act_scales(dev, B, H, W) if (self._split_now and training and not self.bf16) else None
-        tape: Optional[dict] = {"units": [], "blocks": [], "V": V, "B": B} if keep_tape else None
+        tape: Optional[dict] = {"units": [], "blocks": [], "V": V, "B": B, "boundary": self._boundary(need_dimg)} if keep_tape else None
         if keep_tape and self._wprep is not None:
             tape["wprep_versions"] = self._wprep_versions
         if training:
@@ -723,7 +728,10 @@ class Backbone:
         inference.  Fills tape["units"] / tape["blocks"]."""
         s = self.spec
         ulist = tape["units"] if tape is not None else None
+        boundary = tape["boundary"] if tape is not None else -1
         x = self._unit_fwd(s.stem, x0, V, B, H, W, training, True, None, ulist, pool=True).out
+        if boundary > -1:
+            self._release(ulist[0])
         pending = None        # the previous block's apply pass, when this block's first conv forms its own input
         for bi, blk in enumerate(s.blocks):
             first = len(ulist) if ulist is not None else 0
@@ -743,15 +751,42 @@ class Backbone:
                                            residual_affine=ident_affine, next_conv=nxt)
             if ulist is not None:
                 tape["blocks"].append((list(range(first, first + len(blk.convs) - 1)) + [len(ulist) - 1], ds_idx))
+                if bi < boundary:
+                    for u in ulist[first:]:
+                        self._release(u)
         return x
+
+    def _boundary(self, need_dimg: bool) -> int:
+        """Where back-propagation stops: the first unit in forward order - -1 for the stem, else the index of a residual block,
+        its downsample unit counting with it - that owns a parameter with ``requires_grad``; len(blocks) when none does.
+        Below it nothing is back-propagated (no BatchNorm backward, backward-data or weight-gradient launch, and the tape
+        keeps none of those units' activations); the boundary block's own input gradient is not computed either.  A caller
+        that wants d(loss)/d(img) back-propagates everything: -1."""
+        s = self.spec
+
+        def trainable(c: ConvSpec) -> bool:
+            return any(getattr(self.p[n], "requires_grad", False) for n in (c.name + ".weight", c.bn + ".weight", c.bn + ".bias"))
+        if need_dimg or trainable(s.stem):
+            return -1
+        for bi, blk in enumerate(s.blocks):
+            if any(trainable(c) for c in list(blk.convs) + ([blk.downsample] if blk.downsample is not None else [])):
+                return bi
+        return len(s.blocks)
+
+    @staticmethod
+    def _release(u: _Unit) -> None:
+        """A unit below the boundary: the tape keeps its place (the block records index into the list) and nothing else.  The
+        forward launches were the same; what later units still read stays alive through their own x_in."""
+        u.x_in = u.y = u.out = u.mean = u.invstd = u.w = u.pool = u.relu_affine = u.fused_s12 = u.relu_bits = None
 
     # ---------------------------------------------------------------- backward
     def _bn_params(self, c: ConvSpec, sink: GradSink):
         """(gamma, beta, accumulate): the BatchNorm parameters of unit ``c`` and whether their gradients are added to."""
         gp, bp = self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]
-        acc = sink.accumulate(gp)
-        assert acc == sink.accumulate(bp)
-        return gp, bp, acc
+        # (one flag serves both sums: a frozen one of the two follows the other - its slice of the arena is nobody's .grad)
+        accs = {sink.accumulate(q) for q in (gp, bp) if sink.wants(q)}
+        assert len(accs) <= 1
+        return gp, bp, bool(accs) and accs.pop()
 
     def _unit_params(self, c: ConvSpec) -> List[torch.nn.Parameter]:
         """The parameters whose gradients are final once unit ``c``'s backward is queued (GradSink.publish)."""
@@ -859,7 +894,9 @@ class Backbone:
             dx = torch.empty(ops.sp_shape(u.x_in), dtype=torch.float32, device=dy.device)
             self._dgrad(u, dy, dx, addend, fuse_for, sink)
             need_dx = False
-        if self.overlap_wgrad and dy.is_cuda:
+        if not sink.wants(self.p[u.spec.name + ".weight"]):
+            pass          # a frozen conv weight: no weight-gradient launch, no slabs for the block's deferred reduce
+        elif self.overlap_wgrad and dy.is_cuda:
             side = self._side(dy.device)
             side.wait_stream(torch.cuda.current_stream())         # dy (and everything before it) is ready
             with torch.cuda.stream(side):
@@ -1013,8 +1050,12 @@ class Backbone:
         ops.avgpool_bwd(dfeat.contiguous(), g, V * B, Hc * Wc, self.fc_dim)
         self._wg_defer = []
         blocks = tape["blocks"]
-        for bi in range(len(blocks) - 1, -1, -1):
+        # fine-tuning (see _boundary): back-propagation ends with the boundary block, whose input gradient nobody reads
+        boundary = tape.get("boundary", -1)
+        assert not (need_dimg and boundary > -1), "the forward was not told that d(loss)/d(img) is wanted"
+        for bi in range(len(blocks) - 1, max(boundary, 0) - 1, -1):
             idx, ds_idx = blocks[bi]
+            need_in = bi > boundary               # False: the boundary block - no gradient leaves it
             last = units[idx[-1]]
             # the unit that receives this block's input gradient: the previous block's last unit (the stem's
             # fused pool backward takes it for the first block)
@@ -1032,7 +1073,9 @@ class Backbone:
             for k in range(len(idx) - 2, -1, -1):
                 u = units[idx[k]]
                 dy, _ = self._bn_bwd(u, d, False, sink)
-                if k == 0:
+                if k == 0 and not need_in:
+                    d = self._conv_bwd(u, dy, False, None, sink)              # the weight gradient only
+                elif k == 0:
                     # with a downsample branch the block-input gradient is final only after that branch's launch
                     d = self._conv_bwd(u, dy, True, dz if ds_idx is None else None, sink,
                                        fuse_for=prev_last if ds_idx is None else None)
@@ -1044,21 +1087,24 @@ class Backbone:
                 ud = units[ds_idx]
                 dyd, _ = self._bn_bwd(ud, dz, False, sink)
                 self._conv_bwd(ud, dyd, False, None, sink)                # wgrad only
-                self._dgrad(ud, dyd, d, d, prev_last, sink)               # d += dgrad (aliasing addend): now final
+                if need_in:
+                    self._dgrad(ud, dyd, d, d, prev_last, sink)           # d += dgrad (aliasing addend): now final
                 done += self._unit_params(ud.spec)
                 ud.y = ud.out = None
             self._flush_wgrad_reduces(g.device)               # this block's weight gradients are final once their slabs are summed
             sink.publish(done)
             g = d
-            if "debug" in tape:
+            if "debug" in tape and g is not None:
                 tape["debug"].append(g.clone())
-        stem = units[0]
-        dy = self._stem_bn_bwd(stem, g, V, B, sink)
-        dx0 = self._conv_bwd(stem, dy, need_dimg, None, sink)
-        self._flush_wgrad_reduces(g.device)
+        dx0 = None
+        if boundary < 0:
+            stem = units[0]
+            dy = self._stem_bn_bwd(stem, g, V, B, sink)
+            dx0 = self._conv_bwd(stem, dy, need_dimg, None, sink)
+            self._flush_wgrad_reduces(dfeat.device)
+            sink.publish(self._unit_params(stem.spec))
         self._wg_defer = None
-        sink.publish(self._unit_params(stem.spec))
-        if self._wg_stream is not None and dy.is_cuda and (self.overlap_wgrad or not torch.cuda.is_current_stream_capturing()):
+        if self._wg_stream is not None and dfeat.is_cuda and (self.overlap_wgrad or not torch.cuda.is_current_stream_capturing()):
             torch.cuda.current_stream().wait_stream(self._wg_stream)      # gradients complete for the optimizer
         if not need_dimg:
             return None

@@ -441,26 +441,59 @@ __global__ __launch_bounds__(256) void axpby_kernel(const float *__restrict__ x,
 
 // ---- Adam (torch.optim.Adam semantics: coupled L2 weight decay, bias correction) over flat arenas --
 // trainer.py:54 optim.Adam(params, lr, weight_decay=1e-6); one launch updates every parameter.
+// The update of one element, stated once for adam_kernel, adam_dev_kernel and adam_segments_kernel.
+__device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, float b1, float b2, float eps, float wd,
+                                      float step_size, float bc2_sqrt) {
+  const float gr = g + wd * p;
+  m = b1 * m + (1.f - b1) * gr;
+  v = b2 * v + (1.f - b2) * gr * gr;
+  const float denom = sqrtf(v) / bc2_sqrt + eps;
+  p = p - step_size * (m / denom);
+}
+// ... and of the four elements of one 16-byte slot: three loads + a gradient load, three stores
+__device__ __forceinline__ void adam4(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
+                                      float4 *__restrict__ v, long long i, float b1, float b2, float eps, float wd,
+                                      float step_size, float bc2_sqrt) {
+  float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
+  adam1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, wd, step_size, bc2_sqrt);
+  adam1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, wd, step_size, bc2_sqrt);
+  adam1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, wd, step_size, bc2_sqrt);
+  adam1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, wd, step_size, bc2_sqrt);
+  p[i] = pp;
+  m[i] = mm;
+  v[i] = vv;
+}
+
 __global__ __launch_bounds__(256) void adam_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
                                                    float4 *__restrict__ m, float4 *__restrict__ v, long long n4, float lr,
                                                    float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
   const long long stride = (long long)gridDim.x * 256;
   const float step_size = lr / bc1;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-    float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
-#define MVG_ADAM1(c)                                             \
-    {                                                            \
-      const float gr = gg.c + wd * pp.c;                         \
-      mm.c = b1 * mm.c + (1.f - b1) * gr;                        \
-      vv.c = b2 * vv.c + (1.f - b2) * gr * gr;                   \
-      const float denom = sqrtf(vv.c) / bc2_sqrt + eps;          \
-      pp.c = pp.c - step_size * (mm.c / denom);                  \
-    }
-    MVG_ADAM1(x) MVG_ADAM1(y) MVG_ADAM1(z) MVG_ADAM1(w)
-#undef MVG_ADAM1
-    p[i] = pp;
-    m[i] = mm;
-    v[i] = vv;
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
+    adam4(p, g, m, v, i, b1, b2, eps, wd, step_size, bc2_sqrt);
+}
+
+// Adam over SEGMENTS of the arenas (parameter groups, parameters without a gradient: optim.Adam): up to
+// MVG_ADAM_MAX_SEGMENTS element ranges, each with its own hyper-parameters and bias corrections, travel BY VALUE in the
+// kernel arguments - no device table, nothing a later step could overwrite under a launch still in flight.  The grid-stride
+// index runs over the segments laid end to end (16-byte slots): a lane finds its segment by counting the prefix ends at or
+// below its index and adds that segment's offset to reach the arena slot.  Nothing outside the segments is read or written.
+struct AdamSegments {
+  long long end4[MVG_ADAM_MAX_SEGMENTS];      // prefix ends in the concatenated index space; unused entries = the total
+  long long shift4[MVG_ADAM_MAX_SEGMENTS];    // arena slot = concatenated index + shift4[segment]
+  float lr[MVG_ADAM_MAX_SEGMENTS], bc1[MVG_ADAM_MAX_SEGMENTS], b1[MVG_ADAM_MAX_SEGMENTS], b2[MVG_ADAM_MAX_SEGMENTS],
+      eps[MVG_ADAM_MAX_SEGMENTS], wd[MVG_ADAM_MAX_SEGMENTS], bc2_sqrt[MVG_ADAM_MAX_SEGMENTS];
+};
+__global__ __launch_bounds__(256) void adam_segments_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
+                                                            float4 *__restrict__ m, float4 *__restrict__ v, AdamSegments t) {
+  const long long stride = (long long)gridDim.x * 256;
+  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
+    // (lr / bc1 on the device, in float, as adam_kernel forms it: the same bits for the same hyper-parameters)
+    adam4(p, g, m, v, i + t.shift4[k], t.b1[k], t.b2[k], t.eps[k], t.wd[k], t.lr[k] / t.bc1[k], t.bc2_sqrt[k]);
   }
 }
 
@@ -672,22 +705,8 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float4 *__restrict__ p, c
                                                        const float *__restrict__ state, float b1, float b2, float eps, float wd) {
   const long long stride = (long long)gridDim.x * 256;
   const float step_size = lr_dev[0] / state[1], bc2_sqrt = state[2];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-    float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
-#define MVG_ADAM1(c)                                             \
-    {                                                            \
-      const float gr = gg.c + wd * pp.c;                         \
-      mm.c = b1 * mm.c + (1.f - b1) * gr;                        \
-      vv.c = b2 * vv.c + (1.f - b2) * gr * gr;                   \
-      const float denom = sqrtf(vv.c) / bc2_sqrt + eps;          \
-      pp.c = pp.c - step_size * (mm.c / denom);                  \
-    }
-    MVG_ADAM1(x) MVG_ADAM1(y) MVG_ADAM1(z) MVG_ADAM1(w)
-#undef MVG_ADAM1
-    p[i] = pp;
-    m[i] = mm;
-    v[i] = vv;
-  }
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
+    adam4(p, g, m, v, i, b1, b2, eps, wd, step_size, bc2_sqrt);
 }
 
 }  // namespace mvg
@@ -822,6 +841,59 @@ int mvg_adam_step(float *param, const float *grad, float *exp_avg, float *exp_av
                      (float4 *)exp_avg, (float4 *)exp_avg_sq, (long long)(n / 4), lr, beta1, beta2, eps, weight_decay,
                      (float)bc1, (float)sqrt(bc2));
   return check_launch("adam_step");
+}
+
+int mvg_adam_step_segments(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
+                           const float *host_hyper, const int32_t *host_steps, int n_segments, void *stream) {
+  MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && host_bounds && host_hyper && host_steps && n % 4 == 0 && n_segments >= 1,
+              "adam_step_segments: null argument, n %% 4 != 0 or no segment");
+  // every segment is checked before the first launch: a rejected call has updated nothing
+  double active = 0.0;
+  for (int i = 0; i < n_segments; ++i) {
+    const int64_t b = host_bounds[2 * i], e = host_bounds[2 * i + 1];
+    MVG_REQUIRE(b % 4 == 0 && e % 4 == 0, "adam_step_segments: segment %d [%lld, %lld) is not aligned to 4 elements", i, (long long)b, (long long)e);
+    MVG_REQUIRE(b >= 0 && e <= n, "adam_step_segments: segment %d [%lld, %lld) is outside the arena of %lld elements", i, (long long)b,
+                (long long)e, (long long)n);
+    MVG_REQUIRE(b < e, "adam_step_segments: segment %d [%lld, %lld) is empty or reversed", i, (long long)b, (long long)e);
+    if (i > 0) {
+      MVG_REQUIRE(b >= host_bounds[2 * i - 2], "adam_step_segments: segment %d begins before segment %d (unsorted)", i, i - 1);
+      MVG_REQUIRE(b >= host_bounds[2 * i - 1], "adam_step_segments: segment %d overlaps segment %d", i, i - 1);
+    }
+    MVG_REQUIRE(host_steps[i] >= 1, "adam_step_segments: segment %d has step %d < 1", i, (int)host_steps[i]);
+    active += (double)(e - b);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * active);
+  for (int s0 = 0; s0 < n_segments; s0 += MVG_ADAM_MAX_SEGMENTS) {
+    const int cnt = n_segments - s0 < MVG_ADAM_MAX_SEGMENTS ? n_segments - s0 : MVG_ADAM_MAX_SEGMENTS;
+    AdamSegments t;
+    memset(&t, 0, sizeof(t));
+    long long total = 0;
+    for (int k = 0; k < MVG_ADAM_MAX_SEGMENTS; ++k) {
+      const int i = s0 + (k < cnt ? k : cnt - 1);          // (unused entries repeat the last segment: never selected)
+      const float *h = host_hyper + 5 * i;
+      if (k < cnt) {
+        t.shift4[k] = host_bounds[2 * i] / 4 - total;
+        total += (host_bounds[2 * i + 1] - host_bounds[2 * i]) / 4;
+      } else {
+        t.shift4[k] = t.shift4[cnt - 1];
+      }
+      t.end4[k] = total;
+      t.lr[k] = h[0];
+      t.b1[k] = h[1];
+      t.b2[k] = h[2];
+      t.eps[k] = h[3];
+      t.wd[k] = h[4];
+      t.bc1[k] = (float)(1.0 - pow((double)h[1], (double)host_steps[i]));
+      t.bc2_sqrt[k] = (float)sqrt(1.0 - pow((double)h[2], (double)host_steps[i]));
+    }
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(adam_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
+                       (float4 *)exp_avg, (float4 *)exp_avg_sq, t);
+    if (check_launch("adam_step_segments")) return 1;
+  }
+  return 0;
 }
 
 int mvg_absmax_multi(const float *const *host_ptrs, const int64_t *host_counts, float *const *host_out_slots, int n, void *stream) {

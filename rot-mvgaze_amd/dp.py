@@ -49,6 +49,11 @@ class GradAllReducer:
         if first is not None and hasattr(model, "ensure_layout") and first.is_cuda:
             model.ensure_layout()
             self._build()
+            try:
+                self._refuse_frozen()
+            except NotImplementedError:
+                model._on_grads_ready = model._on_backward_done = None
+                raise
         if broadcast and hasattr(model, "param_arena"):
             self.sync()
 
@@ -151,8 +156,23 @@ class GradAllReducer:
             if self.average:
                 buf.mul_(1.0 / self.world)
 
+    def _refuse_frozen(self):
+        """A bucket ships when EVERY parameter inside it was published, and a frozen parameter (requires_grad = False) never
+        is: its bucket would wait for the end of backward and then be zero-filled and averaged for nothing.  Data-parallel
+        fine-tuning with frozen parameters is not served - checked at construction and again at every backward, since
+        freezing needs no rebuild."""
+        if not self.active:
+            return
+        frozen = sum(1 for (p, _, _) in self._entries if not p.requires_grad)
+        if frozen:
+            raise NotImplementedError(f"dp.GradAllReducer: {frozen} of the model's {len(self._entries)} arena parameters have "
+                                      "requires_grad = False; data-parallel runs with frozen parameters are not implemented "
+                                      "(bucket completion counts on every parameter being published)")
+
     def _on_ready(self, params):
         self._build()
+        if self._next == 0 and not self._published:
+            self._refuse_frozen()
         for p in params:
             self._published.add(id(p))
         # buckets ship in arena order (= grad-ready order), each as soon as all of its parameters are final

@@ -59,18 +59,25 @@ class _ArenaSink(GradSink):
         self.m = model
         self._acc: Dict[int, bool] = {}
         self._foreign: Dict[int, bool] = {}
+        self._frozen: Dict[int, bool] = {}
         self.active = False
 
     def begin(self):
-        """Decide, per parameter, whether this backward accumulates into an existing .grad."""
+        """Decide, per parameter, whether this backward accumulates into an existing .grad - and which parameters it serves
+        at all: one with ``requires_grad = False`` is never given a .grad (whatever a fused launch still writes into its
+        arena slice stays behind the view nobody holds) and is left out of what the publish hook sees."""
         if self.active:
             return
         self.active = True
         self._acc.clear()
         self._foreign.clear()
+        self._frozen.clear()
         for p in self.m._grad_order:
             v = self.m._grad_views[id(p)]
-            if p.grad is None:
+            if not p.requires_grad:
+                self._frozen[id(p)] = True
+                self._acc[id(p)] = False
+            elif p.grad is None:
                 self._acc[id(p)] = False
             elif p.grad.data_ptr() == v.data_ptr():
                 self._acc[id(p)] = True                      # kernels accumulate in place
@@ -84,7 +91,14 @@ class _ArenaSink(GradSink):
     def accumulate(self, p):
         return self._acc[id(p)]
 
+    def wants(self, p):
+        return id(p) not in self._frozen
+
     def publish(self, ps):
+        if self._frozen:
+            ps = [p for p in ps if id(p) not in self._frozen]
+            if not ps:
+                return
         for p in ps:
             v = self.m._grad_views[id(p)]
             if self._foreign.get(id(p)):

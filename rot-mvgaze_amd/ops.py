@@ -937,6 +937,18 @@ def gaze_angular_loss_multi(pred, gt, iters, dirs, batch, weights, loss, dpred=N
     check(lib().mvg_gaze_angular_loss_multi(_p(pred), _p(gt), iters, dirs, batch, w, _p(loss), _p(dpred), _s()), "gaze_angular_loss_multi")
 
 
+def adam_step_segments(param, grad, exp_avg, exp_avg_sq, segments):
+    """The Adam step over ``segments`` of the arenas only: (begin, end, lr, beta1, beta2, eps, weight_decay, step) records -
+    element ranges sorted by begin, disjoint, aligned to 4 - each with its own hyper-parameters and step count
+    (mvg_adam_step_segments: MVG_ADAM_MAX_SEGMENTS per launch, by value).  Nothing outside the segments is touched."""
+    n = len(segments)
+    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
+    hyper = (C.c_float * (5 * n))(*[float(v) for s in segments for v in s[2:7]])
+    steps = (C.c_int32 * n)(*[int(s[7]) for s in segments])
+    check(lib().mvg_adam_step_segments(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, steps, n, _s()),
+          "adam_step_segments")
+
+
 def adam_step_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, state3, beta1, beta2, eps, weight_decay):
     check(lib().mvg_adam_step_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(lr_dev), _p(state3), beta1, beta2, eps,
                                   weight_decay, _s()), "adam_step_dev")

@@ -5,15 +5,70 @@ Mirrors ``optim.Adam(self.model.parameters(), lr=0, weight_decay=1e-6)`` of
 ``torch.optim.Optimizer`` subclass, so ``CyclicLR(optimizer, ..., cycle_momentum=False)`` works on it
 unchanged.  The update itself is ``mvg_adam_step`` over the model's parameter / gradient arenas
 (identical offsets), i.e. one kernel for all ~90 M parameters instead of ~190 foreach launches.
-Parameters without a gradient (the unused ``resnet.fc``) are skipped, as torch does.
+
+Fine-tuning goes beyond the reference's one group: any number of parameter groups, each with its own ``lr`` / ``betas`` /
+``eps`` / ``weight_decay``, and parameters without a gradient (frozen ones, ``requires_grad = False``) skipped as torch skips
+them - value, moments and step count untouched.  Step counts are per parameter (``torch.optim.Adam``'s ``state[p]['step']``):
+a parameter unfrozen at step 5 starts its bias correction at 1.  Such a step is ``mvg_adam_step_segments``: ``plan_segments``
+merges arena-adjacent parameters with a gradient, the same hyper-parameters and the same step count into element ranges, and
+one launch (16 ranges at a time) updates those ranges only.  One group with every gradient present and one step count is the
+reference-shaped case and stays the ``mvg_adam_step`` launch.
 """
 from __future__ import annotations
 
-from typing import Dict
+from typing import Dict, Hashable, List, NamedTuple, Sequence, Tuple
 
 import torch
 
 from . import ops
+
+
+class Segment(NamedTuple):
+    """One element range [begin, end) of the arenas (both multiples of 4) updated with one set of hyper-parameters."""
+    begin: int
+    end: int
+    group: Hashable       # what plan_segments was given as the parameters' group key
+    step: int
+
+
+def plan_segments(entries: Sequence[Tuple[int, int]], group_of: Sequence[Hashable], has_grad: Sequence[bool],
+                  steps: Sequence[int]) -> List[Segment]:
+    """The segments of one optimizer step, from the arena layout alone (no device, no library).
+
+    entries: (offset, numel) of every arena parameter, in arena order (offsets are multiples of 4: every entry starts on a
+    16-byte slot); group_of[i]: a hashable key - two parameters may share a segment only when their keys are equal (optim.Adam
+    passes the group's hyper-parameters); has_grad[i]: whether parameter i takes part in this step; steps[i]: the step count
+    this update uses for it (>= 1, i.e. already advanced).
+
+    Maximal runs of arena-adjacent parameters that take part and agree in key and step count become one segment.  Bounds are
+    rounded to the 4-element slots: a run ends on its last entry's slot boundary, so the zero padding between and behind
+    entries (2-element head biases) sits inside the run - Adam maps zero parameter, gradient and moments to zero.  Sorted by
+    begin, disjoint."""
+    if not (len(entries) == len(group_of) == len(has_grad) == len(steps)):
+        raise ValueError("plan_segments: entries, group_of, has_grad and steps must have one item per parameter")
+    out: List[Segment] = []
+    cur = None                                    # [begin, end, key, step] of the open run
+    last_end = 0
+    for (off, numel), key, has, step in zip(entries, group_of, has_grad, steps):
+        if off % 4 or numel <= 0 or off < last_end:
+            raise ValueError(f"plan_segments: entry at {off} (+{numel}) is unaligned, empty or out of arena order")
+        end = last_end = (off + numel + 3) // 4 * 4
+        if not has:
+            if cur is not None:
+                out.append(Segment(*cur))
+                cur = None
+            continue
+        if step < 1:
+            raise ValueError("plan_segments: a parameter that takes part needs a step count >= 1")
+        if cur is not None and cur[1] == off and cur[2] == key and cur[3] == step:
+            cur[1] = end
+            continue
+        if cur is not None:
+            out.append(Segment(*cur))
+        cur = [off, end, key, int(step)]
+    if cur is not None:
+        out.append(Segment(*cur))
+    return out
 
 
 class Adam(torch.optim.Optimizer):
@@ -21,8 +76,9 @@ class Adam(torch.optim.Optimizer):
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid Adam hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
-        if len(self.param_groups) != 1:
-            raise NotImplementedError("one parameter group (the reference uses one)")
+        for g in self.param_groups:
+            if g["lr"] < 0 or g["eps"] < 0 or g["weight_decay"] < 0 or not (0 <= g["betas"][0] < 1 and 0 <= g["betas"][1] < 1):
+                raise ValueError("invalid Adam hyper-parameter in a parameter group")
         self._flat: Dict[int, dict] = {}
         self._pending = None          # moments restored by load_state_dict, adopted by the next step()
         # capturable (like torch.optim.Adam's flag): the step counter, the bias corrections and the learning rate live on
@@ -30,6 +86,10 @@ class Adam(torch.optim.Optimizer):
         # with nothing from the host; the learning rate is pushed to the device by sync_lr() - outside a capture - whenever
         # the scheduler changed it (the reference steps CyclicLR once per epoch, trainer.py:147).
         self.capturable = bool(capturable)
+        if self.capturable and len(self.param_groups) != 1:
+            raise NotImplementedError("Adam(capturable=True) takes one parameter group (refused at construction): the captured "
+                                      "step keeps ONE learning rate and ONE step counter on the device; grouped steps run with "
+                                      "capturable=False")
 
     def sync_lr(self):
         """capturable: copy param_groups[0]['lr'] to the device scalar the captured update reads (no-op when unchanged)."""
@@ -44,14 +104,42 @@ class Adam(torch.optim.Optimizer):
 
     def _owners(self):
         owners = {}
-        for p in self.param_groups[0]["params"]:
-            ref = getattr(p, "_mvg_owner", None)
-            model = ref() if ref is not None else None
-            if model is None:
-                raise RuntimeError("rot_mvgaze_amd.optim.Adam only updates parameters of the MI355X "
-                                   "FeatRotationSymm / MultiViewGaze modules")
-            owners[id(model)] = model
+        for g in self.param_groups:
+            for p in g["params"]:
+                ref = getattr(p, "_mvg_owner", None)
+                model = ref() if ref is not None else None
+                if model is None:
+                    raise RuntimeError("rot_mvgaze_amd.optim.Adam only updates parameters of the MI355X "
+                                       "FeatRotationSymm / MultiViewGaze modules")
+                owners[id(model)] = model
         return list(owners.values())
+
+    @staticmethod
+    def _hyper(g) -> tuple:
+        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+
+    def _state_for(self, model, arena_p, n_entries: int) -> dict:
+        """The flat state of ``model``: the two moment buffers at arena offsets and one step count per arena parameter."""
+        st = self._flat.get(id(model))
+        if st is None and self._pending:
+            saved = self._pending.pop(0)
+            if saved["exp_avg"].numel() != arena_p.numel():
+                raise RuntimeError("optimizer state does not match this model's parameter arena "
+                                   f"({saved['exp_avg'].numel()} vs {arena_p.numel()} elements)")
+            # (an entry written before per-parameter counts existed holds one "step": every parameter gets it)
+            steps = [int(s) for s in saved["steps"]] if "steps" in saved else [int(saved["step"])] * n_entries
+            if len(steps) != n_entries:
+                raise RuntimeError(f"optimizer state holds {len(steps)} step counts for {n_entries} arena parameters")
+            st = {"step": max(steps), "steps": steps, "n": arena_p.numel(),
+                  "exp_avg": saved["exp_avg"].to(arena_p.device, torch.float32).contiguous(),
+                  "exp_avg_sq": saved["exp_avg_sq"].to(arena_p.device, torch.float32).contiguous()}
+            self._flat[id(model)] = st
+        if st is None or st["exp_avg"].data_ptr() == 0 or st["n"] != arena_p.numel() or \
+                st["exp_avg"].device != arena_p.device or len(st["steps"]) != n_entries:
+            st = {"step": 0, "steps": [0] * n_entries, "n": arena_p.numel(), "exp_avg": torch.zeros_like(arena_p),
+                  "exp_avg_sq": torch.zeros_like(arena_p)}
+            self._flat[id(model)] = st
+        return st
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -59,35 +147,32 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        g = self.param_groups[0]
+        group_of = {id(p): g for g in self.param_groups for p in g["params"]}
         for model in self._owners():
             model.ensure_layout()
             arena_g, entries = model.grad_arena()
-            have = [p.grad is not None for (p, _, _) in entries]
+            # a parameter takes part when it is in a group and holds a gradient; torch skips every other one, and so do we
+            groups = [group_of.get(id(p)) for (p, _, _) in entries]
+            have = [g is not None and p.grad is not None for (p, _, _), g in zip(entries, groups)]
             if not any(have):
                 continue                              # nothing was back-propagated: torch skips too
-            for (p, off, n) in entries:
-                if p.grad is None or p.grad.data_ptr() != arena_g.data_ptr() + 4 * off:
+            for (p, off, n), h in zip(entries, have):
+                if h and p.grad.data_ptr() != arena_g.data_ptr() + 4 * off:
                     raise RuntimeError("every trainable parameter must hold the gradient written by the "
                                        "module's backward (a view of its gradient arena)")
-            st = self._flat.get(id(model))
             arena_p = model.param_arena()
-            if st is None and self._pending:
-                saved = self._pending.pop(0)
-                if saved["exp_avg"].numel() != arena_p.numel():
-                    raise RuntimeError("optimizer state does not match this model's parameter arena "
-                                       f"({saved['exp_avg'].numel()} vs {arena_p.numel()} elements)")
-                st = {"step": int(saved["step"]), "n": arena_p.numel(),
-                      "exp_avg": saved["exp_avg"].to(arena_p.device, torch.float32).contiguous(),
-                      "exp_avg_sq": saved["exp_avg_sq"].to(arena_p.device, torch.float32).contiguous()}
-                self._flat[id(model)] = st
-            if st is None or st["exp_avg"].data_ptr() == 0 or st["n"] != arena_p.numel() or \
-                    st["exp_avg"].device != arena_p.device:
-                st = {"step": 0, "n": arena_p.numel(), "exp_avg": torch.zeros_like(arena_p),
-                      "exp_avg_sq": torch.zeros_like(arena_p)}
-                self._flat[id(model)] = st
-            st["step"] += 1
+            st = self._state_for(model, arena_p, len(entries))
+            steps = [s + 1 if h else s for s, h in zip(st["steps"], have)]
+            # the reference-shaped step: one group, every arena parameter in it with a gradient, one step count
+            whole = len(self.param_groups) == 1 and all(have) and len(set(steps)) == 1
+            if self.capturable and not whole:
+                raise NotImplementedError("Adam(capturable=True) cannot skip parameters (refused at step()): a parameter without a "
+                                          "gradient, or with a step count of its own, needs the segmented step, which takes its "
+                                          "segments from the host; use capturable=False for frozen or later-unfrozen parameters")
+            st["steps"] = steps
+            st["step"] = max(steps)
             if self.capturable:
+                g = self.param_groups[0]
                 if "lr_dev" not in st:
                     if torch.cuda.is_current_stream_capturing():
                         raise RuntimeError("Adam(capturable=True): run one eager step before capturing (its device state is created then)")
@@ -98,18 +183,27 @@ class Adam(torch.optim.Optimizer):
                 self.sync_lr()
                 ops.adam_step_dev(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["lr_dev"], st["state3"], float(g["betas"][0]),
                                   float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
-            else:
+            elif whole:
+                g = self.param_groups[0]
                 ops.adam_step(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], float(g["lr"]), float(g["betas"][0]),
                               float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), st["step"])
+            else:
+                segs = plan_segments([(off, n) for (_, off, n) in entries], [self._hyper(g) if g is not None else None for g in groups],
+                                     have, steps)
+                ops.adam_step_segments(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"],
+                                       [(s.begin, s.end) + s.group + (s.step,) for s in segs])
             # the parameters alias the arena through `.data` (their own version counters): mark them modified, as an
             # in-place torch op would (the inference path's cache of split weights keys on the version)
-            for (p, _, _) in entries:
-                torch.autograd.graph.increment_version(p)
+            for (p, _, _), h in zip(entries, have):
+                if h:
+                    torch.autograd.graph.increment_version(p)
         return loss
 
     # The moments live in flat buffers that mirror the model's parameter arena (one launch updates all of
     # them), not in ``self.state``; checkpoints carry them under one extra key so that a resumed run keeps
     # its bias correction and moments (the reference itself checkpoints the model only, trainer.py:91-96).
+    # "steps" holds one count per arena parameter, in arena order; "step" (their maximum) is what entries held before
+    # per-parameter counts, and an entry with "step" alone still loads: every parameter gets that count.
     def state_dict(self):
         sd = super().state_dict()
         flat = []
@@ -118,7 +212,8 @@ class Adam(torch.optim.Optimizer):
             if st is not None:
                 if "state3" in st:                  # capturable: the device counter is the truth (graph replays advance it)
                     st["step"] = int(round(float(st["state3"][0].item())))
-                flat.append({"step": st["step"], "exp_avg": st["exp_avg"].detach().clone(),
+                    st["steps"] = [st["step"]] * len(st["steps"])
+                flat.append({"step": st["step"], "steps": list(st["steps"]), "exp_avg": st["exp_avg"].detach().clone(),
                              "exp_avg_sq": st["exp_avg_sq"].detach().clone()})
         sd["mvg_arena_state"] = flat
         return sd
