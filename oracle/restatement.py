@@ -179,6 +179,11 @@ def _one(mask):
     return None if mask is None else iter([mask])
 
 
+def _each(masks):
+    """The hidden-layer masks of a three-layer Mlp, in layer order (None: ReLU from the sign)."""
+    return None if masks is None else iter(masks)
+
+
 def lift(sd: SD, img_feat: Tensor, mask=None) -> Tensor:
     """Feat3dLifter: Mlp(C_f,[1536,1536]) -> [B,3,512].  /root/reference/models/rot_mv.py:91-98."""
     return mlp(sd, "_lifter._lifter.", img_feat, 2, _one(mask)).reshape(-1, 3, NUM_FEAT_VEC)
@@ -191,11 +196,12 @@ def fuse(sd: SD, it: int, img_feat: Tensor, rotated: Tensor, mask=None) -> Tenso
     return mlp(sd, f"_img_fusers.{it}._fuser.", x, 2, _one(mask)).reshape(-1, 3, NUM_FEAT_VEC)
 
 
-def fuse_rotmat(sd: SD, it: int, img_feat: Tensor, feat: Tensor, rot: Tensor) -> Tensor:
+def fuse_rotmat(sd: SD, it: int, img_feat: Tensor, feat: Tensor, rot: Tensor, masks=None) -> Tensor:
     """ImageRotmatFeatFuser (encode_rotmat): the partner's feature is NOT rotated; the relative
-    rotation is appended as 9 more inputs of a 3-layer Mlp.  /root/reference/models/rot_mv.py:53-69,219-225."""
+    rotation is appended as 9 more inputs of a 3-layer Mlp.  /root/reference/models/rot_mv.py:53-69,219-225.
+    ``masks`` (test aid, see _relu): the two hidden layers' imposed ReLU patterns, in layer order."""
     x = torch.cat([img_feat, feat.flatten(-2, -1), rot.flatten(-2, -1)], dim=-1)
-    return mlp(sd, f"_img_fusers.{it}._fuser.", x, 3).reshape(-1, 3, NUM_FEAT_VEC)
+    return mlp(sd, f"_img_fusers.{it}._fuser.", x, 3, _each(masks)).reshape(-1, 3, NUM_FEAT_VEC)
 
 
 def intensity_batchnorm(sd: SD, prefix: str, x: Tensor, training: bool, momentum: float = 0.05,
@@ -211,15 +217,15 @@ def intensity_batchnorm(sd: SD, prefix: str, x: Tensor, training: bool, momentum
     return x / (sd[key] + eps)
 
 
-def fuse_rotfeat(sd: SD, it: int, feat_0: Tensor, feat_1: Tensor, training: bool) -> Tensor:
+def fuse_rotfeat(sd: SD, it: int, feat_0: Tensor, feat_1: Tensor, training: bool, masks=None) -> Tensor:
     """RotFeatFuser (share_feature): both [B,3,F] inputs pass the fuser's ONE IntensityBatchNorm
     (feat_0 first), are concatenated along F, flattened axis-major and go through a 3-layer Mlp.
-    /root/reference/models/rot_mv.py:72-86."""
+    /root/reference/models/rot_mv.py:72-86.  ``masks``: as in fuse_rotmat."""
     pre = f"_img_fusers.{it}._batchnorm."
     n0 = intensity_batchnorm(sd, pre, feat_0, training)
     n1 = intensity_batchnorm(sd, pre, feat_1, training)
     x = torch.cat([n0, n1], dim=-1).flatten(-2, -1)
-    return mlp(sd, f"_img_fusers.{it}._fuser.", x, 3).reshape(-1, 3, NUM_FEAT_VEC)
+    return mlp(sd, f"_img_fusers.{it}._fuser.", x, 3, _each(masks)).reshape(-1, 3, NUM_FEAT_VEC)
 
 
 def gaze_head(sd: SD, it: int, img_feat: Tensor, feat: Tensor, mask=None) -> Tensor:
@@ -236,15 +242,15 @@ def fuse_pair(sd: SD, num_iter: int, img_feat_0: Tensor, img_feat_1: Tensor, f0:
               rot_0: Tensor, rot_1: Tensor, masks: Optional[Dict[Any, Any]] = None, variant=None,
               training: bool = False) -> Dict[str, Any]:
     """The two-view recurrence of /root/reference/models/rot_mv.py:193-194,205-265 given the
-    per-view pooled and lifted features.  ``masks`` (test aid, see _relu, default variant only):
-    {("fuse", it): [m0, m1], ("head", it): [m0, m1]} imposed hidden-layer ReLU patterns.
+    per-view pooled and lifted features.  ``masks`` (test aid, see _relu):
+    {("fuse", it): [m0, m1], ("head", it): [m0, m1]} imposed hidden-layer ReLU patterns; for the three-layer fusers of
+    encode_rotmat / share_feature each of m0, m1 is the PAIR (first hidden layer's mask, second hidden layer's mask).
     ``variant``: arch.Variant (ablations, :136-171,219-247); share_weights needs nothing here -
     the state_dict holds the same tensors under every iteration's names."""
     mk = (lambda kind, it, v: masks[(kind, it)][v]) if masks is not None else (lambda kind, it, v: None)
     enc = variant is not None and variant.encode_rotmat
     ign = variant is not None and variant.ignore_rotmat
     shf = variant is not None and variant.share_feature
-    assert masks is None or not (enc or shf)
     rot_10 = rot_0 @ rot_1.transpose(-1, -2)
     rot_01 = rot_1 @ rot_0.transpose(-1, -2)
     if shf:                                            # :199-201
@@ -257,14 +263,14 @@ def fuse_pair(sd: SD, num_iter: int, img_feat_0: Tensor, img_feat_1: Tensor, f0:
     for it in range(num_iter):
         f0_prev = f0                                   # rot_mv.py:217 - view 1 reads view 0's OLD feature
         if enc:
-            f0 = fuse_rotmat(sd, it, img_feat_0, f1, rot_10)
-            f1 = fuse_rotmat(sd, it, img_feat_1, f0_prev, rot_01)
+            f0 = fuse_rotmat(sd, it, img_feat_0, f1, rot_10, mk("fuse", it, 0))
+            f1 = fuse_rotmat(sd, it, img_feat_1, f0_prev, rot_01, mk("fuse", it, 1))
         elif ign:
             f0 = fuse(sd, it, img_feat_0, f1, mk("fuse", it, 0))
             f1 = fuse(sd, it, img_feat_1, f0_prev, mk("fuse", it, 1))
         elif shf:
-            f0 = fuse_rotfeat(sd, it, img_feat_0, rot_10 @ f1, training)
-            f1 = fuse_rotfeat(sd, it, img_feat_1, rot_01 @ f0_prev, training)
+            f0 = fuse_rotfeat(sd, it, img_feat_0, rot_10 @ f1, training, mk("fuse", it, 0))
+            f1 = fuse_rotfeat(sd, it, img_feat_1, rot_01 @ f0_prev, training, mk("fuse", it, 1))
         else:
             f0 = fuse(sd, it, img_feat_0, rot_10 @ f1, mk("fuse", it, 0))
             f1 = fuse(sd, it, img_feat_1, rot_01 @ f0_prev, mk("fuse", it, 1))

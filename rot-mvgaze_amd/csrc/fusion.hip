@@ -724,6 +724,7 @@ int mvg_rotation_matrix_2d(const float *pitch_yaw, float *rot, int n, int invers
 
 int mvg_relative_rotation(const float *rot, const int32_t *vi, const int32_t *vj, float *rel, int batch, int views,
                           int dirs, void *stream) {
+  MVG_REQUIRE(batch > 0 && views > 0 && dirs > 0, "relative_rotation: batch, views and dirs must be positive");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_GEOMETRY, st, 0.0, 108.0 * dirs * batch);
   hipLaunchKernelGGL(relative_rotation_kernel, dim3(ceil_div((long long)dirs * batch, 256)), dim3(256), 0, st, rot, vi, vj,
@@ -734,6 +735,8 @@ int mvg_relative_rotation(const float *rot, const int32_t *vi, const int32_t *vj
 int mvg_rotcat_fwd(const float *img_feat, const float *feat, const float *rel, const int32_t *view_of,
                    const int32_t *src_of, float *x, int batch, int dirs, int cf, int nvec, void *stream) {
   MVG_REQUIRE(cf % 4 == 0, "rotcat: cf %% 4 != 0");
+  MVG_REQUIRE(nvec > 0 && nvec % 4 == 0, "rotcat: nvec %% 4 != 0 (nvec=%d: rows of cf + 3 nvec floats move as 16-byte vectors)", nvec);
+  MVG_REQUIRE(batch > 0 && dirs > 0, "rotcat: batch and dirs must be positive");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ROTCAT, st, 18.0 * dirs * batch * nvec, 8.0 * dirs * (double)batch * (cf + 3 * nvec));
   hipLaunchKernelGGL(rotcat_fwd_kernel, dim3(dirs * batch), dim3(256), 0, st, img_feat, feat, rel, view_of, src_of, x,
@@ -743,6 +746,9 @@ int mvg_rotcat_fwd(const float *img_feat, const float *feat, const float *rel, c
 
 int mvg_rotcat_bwd(const float *dx, const float *rel, const int32_t *src_of, float *dfeat, int batch, int dirs, int cf,
                    int nvec, void *stream) {
+  MVG_REQUIRE(cf % 4 == 0, "rotcat_bwd: cf %% 4 != 0");
+  MVG_REQUIRE(nvec > 0 && nvec % 4 == 0, "rotcat_bwd: nvec %% 4 != 0 (nvec=%d)", nvec);
+  MVG_REQUIRE(batch > 0 && dirs > 0, "rotcat_bwd: batch and dirs must be positive");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ROTCAT, st, 18.0 * dirs * batch * nvec, 24.0 * dirs * (double)batch * nvec);
   hipLaunchKernelGGL(rotcat_bwd_feat_kernel, dim3(dirs * batch), dim3(256), 0, st, dx, rel, src_of, dfeat, batch, cf, nvec);
@@ -753,7 +759,9 @@ int mvg_rotcat_ext_fwd(const float *img_feat, const float *feat, const float *re
                        const int32_t *view_of, const int32_t *src_of, float *x, int ld, int batch, int dirs, int cf, int nvec,
                        void *stream) {
   MVG_REQUIRE(cf % 4 == 0 && ld % 4 == 0, "rotcat_ext: cf / ld %% 4 != 0");
+  MVG_REQUIRE(nvec > 0 && nvec % 4 == 0, "rotcat_ext: nvec %% 4 != 0 (nvec=%d)", nvec);
   MVG_REQUIRE(ld >= cf + 3 * nvec + (rel_append ? 9 : 0), "rotcat_ext: ld too small");
+  MVG_REQUIRE(batch > 0 && dirs > 0, "rotcat_ext: batch and dirs must be positive");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ROTCAT, st, 18.0 * dirs * batch * nvec, 8.0 * dirs * (double)batch * ld);
   hipLaunchKernelGGL(rotcat_ext_fwd_kernel, dim3(dirs * batch), dim3(256), 0, st, img_feat, feat, rel_apply, rel_append, view_of,
@@ -763,6 +771,10 @@ int mvg_rotcat_ext_fwd(const float *img_feat, const float *feat, const float *re
 
 int mvg_rotcat_ext_bwd(const float *dx, int ld, const float *rel, const int32_t *src_of, float *dfeat, int batch, int dirs,
                        int cf, int nvec, void *stream) {
+  MVG_REQUIRE(cf % 4 == 0 && ld % 4 == 0, "rotcat_ext_bwd: cf / ld %% 4 != 0");
+  MVG_REQUIRE(nvec > 0 && nvec % 4 == 0, "rotcat_ext_bwd: nvec %% 4 != 0 (nvec=%d)", nvec);
+  MVG_REQUIRE(ld >= cf + 3 * nvec, "rotcat_ext_bwd: ld too small");
+  MVG_REQUIRE(batch > 0 && dirs > 0, "rotcat_ext_bwd: batch and dirs must be positive");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ROTCAT, st, 18.0 * dirs * batch * nvec, 24.0 * dirs * (double)batch * nvec);
   hipLaunchKernelGGL(rotcat_ext_bwd_kernel, dim3(dirs * batch), dim3(256), 0, st, dx, ld, rel, src_of, dfeat, batch, cf, nvec);
@@ -781,6 +793,8 @@ int mvg_ibn_scales(const float *a, const float *feat, const int32_t *view_of, co
 
 int mvg_paircat_fwd(const float *a, const float *feat, const float *rel, const float *scales, const int32_t *view_of,
                     const int32_t *src_of, float *x, int batch, int dirs, int nvec, void *stream) {
+  MVG_REQUIRE(nvec > 0 && nvec % 4 == 0, "paircat: nvec %% 4 != 0 (nvec=%d)", nvec);
+  MVG_REQUIRE(batch > 0 && dirs > 0, "paircat: batch and dirs must be positive");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ROTCAT, st, 18.0 * dirs * batch * nvec, 48.0 * dirs * (double)batch * nvec);
   hipLaunchKernelGGL(paircat_fwd_kernel, dim3(dirs * batch), dim3(256), 0, st, a, feat, rel, scales, view_of, src_of, x, batch,
@@ -790,6 +804,8 @@ int mvg_paircat_fwd(const float *a, const float *feat, const float *rel, const f
 
 int mvg_paircat_bwd(const float *dx, const float *rel, const float *scales, const int32_t *src_of, float *da_dir, float *dfeat,
                     int batch, int dirs, int nvec, void *stream) {
+  MVG_REQUIRE(nvec > 0 && nvec % 4 == 0, "paircat_bwd: nvec %% 4 != 0 (nvec=%d)", nvec);
+  MVG_REQUIRE(batch > 0 && dirs > 0, "paircat_bwd: batch and dirs must be positive");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ROTCAT, st, 18.0 * dirs * batch * nvec, 48.0 * dirs * (double)batch * nvec);
   hipLaunchKernelGGL(paircat_bwd_kernel, dim3(dirs * batch), dim3(256), 0, st, dx, rel, scales, src_of, da_dir, dfeat, batch,
@@ -800,6 +816,7 @@ int mvg_paircat_bwd(const float *dx, const float *rel, const float *scales, cons
 int mvg_segment_sum(const float *x, int64_t row_stride, int width, const int32_t *seg_of, float *out, int batch, int dirs,
                     int segments, int accumulate, void *stream) {
   MVG_REQUIRE(width % 4 == 0 && row_stride % 4 == 0, "segment_sum: width/row_stride %% 4 != 0");
+  MVG_REQUIRE(batch > 0 && dirs > 0 && segments > 0 && width > 0, "segment_sum: batch, dirs, segments and width must be positive");
   hipStream_t st = (hipStream_t)stream;
   const long long total = (long long)segments * batch * (width / 4);
   ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 4.0 * (double)batch * width * (dirs + segments));
@@ -936,6 +953,7 @@ int mvg_fuse_unbuild(const float *dxh, const float *dxn, const float *rel, const
                      int da_accumulate, int segments, int views, int dirs, int batch, int cf, int nvec, float *absmax, void *stream) {
   MVG_REQUIRE((dxh || dxn) && seg && vi && dfeat && da, "fuse_unbuild: null argument");
   MVG_REQUIRE(cf % 4 == 0 && segments > 0 && views > 0 && dirs > 0 && batch > 0, "fuse_unbuild: bad sizes");
+  MVG_REQUIRE(nvec > 0 && nvec % 4 == 0, "fuse_unbuild: nvec %% 4 != 0 (nvec=%d: rows of cf + 3 nvec floats move as 16-byte vectors)", nvec);
   MVG_REQUIRE(!dxh || segments == dirs, "fuse_unbuild: the head-input gradient has one row per direction (segments == dirs)");
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ROTCAT, st, 18.0 * dirs * batch * nvec, 4.0 * (double)batch * ((dxh ? 1 : 0) + (dxn ? 1 : 0)) * dirs * (cf + 3 * nvec));
