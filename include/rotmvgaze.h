@@ -581,6 +581,24 @@ int mvg_conv_wgrad_bf16(const mvg_conv_desc *d, const void *x, const void *dy, f
 int mvg_conv_wgrad_splits_bf16(const mvg_conv_desc *d);
 /* the launch without its slab reduce (splits > 1), for mvg_wgrad_reduce_batch - see mvg_conv_wgrad_split_slabs */
 int mvg_conv_wgrad_bf16_slabs(const mvg_conv_desc *d, const void *x, const void *dy, float *workspace, int splits, void *stream);
+/* Host-only plan queries of the bf16 kernels (like mvg_conv_plan_query / mvg_conv_wgrad_tile: tests guard with them which
+ * form a shape runs): answered by the code the launches plan with; nothing is launched and no device is needed.  -1 (and
+ * a message) for a descriptor or kind the launch would reject.
+ * mvg_conv_plan_query_bf16: `kind` names the launch - MVG_PLAN_BF16_FPROP (mvg_conv_fprop_bf16), MVG_PLAN_BF16_DGRAD
+ * (mvg_conv_dgrad_bf16), MVG_PLAN_BF16_DGRAD_BNREDUCE (mvg_conv_dgrad_bf16_bnreduce: classes without taps stay in the
+ * launch, with 0 K-steps), MVG_PLAN_BF16_AFFINE (mvg_conv_fprop_bf16_affine), MVG_PLAN_BF16_LINEAR_FPROP_MIXED /
+ * MVG_PLAN_BF16_LINEAR_DGRAD_MIXED (mvg_linear_fprop_mixed / mvg_linear_dgrad_mixed with the descriptor {1, rows, 1, 1, fin,
+ * fout, 1, 1, 1, 0, 1, 1}); the stem's folded forms are not covered.  The plan: bm = 128, bk = 64, bn = 128 or 64, fasta
+ * (the uniform-tap loader), ncls / cls_tiles / cls_kt as in mvg_conv_plan_query, streamk_grid = 0, splitk = 1,
+ * scratch_floats = 0.  The kernel follows: the LDS-DMA kernel iff fasta and the kind is not a mixed one (those run the
+ * register-staged kernel with fp32 operands, fasta choosing its loader); otherwise the register-staged kernel.  out may be NULL.
+ * mvg_conv_wgrad_tile_bf16: the tile (bm rows of cout x bn columns of r*s*cin) mvg_conv_wgrad_bf16 (f32in = 0) or
+ * mvg_linear_wgrad_mixed (f32in != 0) runs `d` on, and whether its loader steps the pixel coordinates incrementally (never
+ * with fp32 operands); every out-pointer may be NULL. */
+enum { MVG_PLAN_BF16_FPROP = 0, MVG_PLAN_BF16_DGRAD = 1, MVG_PLAN_BF16_DGRAD_BNREDUCE = 2, MVG_PLAN_BF16_AFFINE = 3,
+       MVG_PLAN_BF16_LINEAR_FPROP_MIXED = 4, MVG_PLAN_BF16_LINEAR_DGRAD_MIXED = 5 };
+int mvg_conv_plan_query_bf16(const mvg_conv_desc *d, int kind, mvg_conv_plan *out);
+int mvg_conv_wgrad_tile_bf16(const mvg_conv_desc *d, int f32in, int32_t *bm, int32_t *bn, int32_t *incremental);
 /* nn.Linear of the fusion block in the bf16 path ("mixed"): activations, gradients, biases and outputs stay
  * fp32 in memory, the operand loaders round to bf16 on the way into LDS and the product runs on the bf16
  * matrix cores against the bf16 weight copies (w_bf16 [fout][fin]; wt_bf16 [fin][fout] for backward-data).

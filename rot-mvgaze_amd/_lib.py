@@ -33,6 +33,8 @@ class ConvDesc(C.Structure):
 
 
 PLAN_FPROP, PLAN_FPROP_STATS, PLAN_DGRAD, PLAN_FUSER_FPROP = 0, 1, 2, 3       # MVG_PLAN_* (mvg_conv_plan_query)
+PLAN_BF16_FPROP, PLAN_BF16_DGRAD, PLAN_BF16_DGRAD_BNREDUCE, PLAN_BF16_AFFINE, PLAN_BF16_LINEAR_FPROP_MIXED, \
+    PLAN_BF16_LINEAR_DGRAD_MIXED = range(6)                                   # MVG_PLAN_BF16_* (mvg_conv_plan_query_bf16)
 
 
 class ConvPlan(C.Structure):
@@ -214,6 +216,8 @@ SIGNATURES = {
     "mvg_stem_wgrad_bf16": (_I, [_D, _P, _P, _P, _P, _I, _I, _P]),
     "mvg_conv_wgrad_splits_bf16": (_I, [_D]),
     "mvg_conv_wgrad_bf16_slabs": (_I, [_D, _P, _P, _P, _I, _P]),
+    "mvg_conv_plan_query_bf16": (_I, [_D, _I, C.POINTER(ConvPlan)]),
+    "mvg_conv_wgrad_tile_bf16": (_I, [_D, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mvg_linear_fprop_mixed": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "mvg_linear_dgrad_mixed": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "mvg_linear_wgrad_mixed": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),

@@ -251,13 +251,18 @@ static int validate_bf16(const mvg_conv_desc *d) {
   return 0;
 }
 
+// The plan of a forward / backward-data launch, host arithmetic only: the column tile, each class's tiles and K-steps, the
+// K order, and whether every class can take the uniform-tap loader (fasta).  p: the geometry and the classes; the launch
+// fields (ntiles, the classes' tile offsets, bn_parts) are set here.  What launch_igemm_bf16 launches by and what
+// mvg_conv_plan_query_bf16 reports.  The kernel follows from the plan: the LDS-DMA kernel iff fasta with bf16 operands
+// (the fp32-operand Linears stay on the register-staged kernel, fasta choosing its loader).
 template <bool DGRAD>
-static int launch_igemm_bf16(IgemmParams &p, hipStream_t st, bool f32io = false, bool affine = false) {
+static int plan_igemm_bf16(IgemmParams &p, bool f32io, mvg_conv_plan &pl, long long &tiles) {
   const int bn = p.ncols >= 128 ? 128 : 64;
   p.ntiles = ceil_div(p.ncols, bn);
   p.splits = 1;
   p.sk_tiles = 0;
-  long long tiles = 0;
+  tiles = 0;
   bool fasta = true;
   const bool bnf = DGRAD && p.bn_part != nullptr;
   p.bn_parts = 0;
@@ -271,11 +276,38 @@ static int launch_igemm_bf16(IgemmParams &p, hipStream_t st, bool f32io = false,
     c.unit0 = 0;
     c.part0 = p.bn_parts;
     p.bn_parts += c.mtiles_per_group;
-    tiles += (long long)p.groups * c.mtiles_per_group * p.ntiles;
+    const long long ti = (long long)p.groups * c.mtiles_per_group * p.ntiles;
+    tiles += ti;
     fasta = fasta && (c.ntaps >= 1 || bnf) && c.ntaps <= 32 && c.ktotal % BF_BK == 0 && p.src_c % BF_BK == 0;
+    pl.cls_tiles[i] = (int32_t)ti;
+    pl.cls_kt[i] = c.KT;
   }
   MVG_REQUIRE(tiles < (1LL << 31), "bf16 conv: grid too large");
   MVG_REQUIRE(!bnf || (fasta && !f32io), "bf16 dgrad with a fused BatchNorm reduce: bf16 operands, channel counts in multiples of 64");
+  pl.bm = BF_BM;
+  pl.bn = bn;
+  pl.bk = BF_BK;
+  pl.fasta = fasta ? 1 : 0;
+  pl.ncls = p.ncls;
+  pl.streamk_grid = 0;
+  pl.splitk = 1;
+  pl.scratch_floats = 0;
+  return 0;
+}
+
+// `query` != nullptr (mvg_conv_plan_query_bf16): the plan is written there and nothing is launched
+template <bool DGRAD>
+static int launch_igemm_bf16(IgemmParams &p, hipStream_t st, bool f32io = false, bool affine = false, mvg_conv_plan *query = nullptr) {
+  mvg_conv_plan pl;
+  memset(&pl, 0, sizeof(pl));
+  long long tiles = 0;
+  if (int e = plan_igemm_bf16<DGRAD>(p, f32io, pl, tiles)) return e;
+  if (query) {
+    *query = pl;
+    return 0;
+  }
+  const int bn = pl.bn;
+  const bool fasta = pl.fasta != 0;
   if (tiles <= 0) return 0;
   dim3 grid((unsigned)tiles), block(256);
   if constexpr (!DGRAD) {
@@ -346,7 +378,8 @@ struct Bf16Affine {        // inference: y = bf16([relu](acc * scale + shift (+ 
 };
 
 static int fprop_bf16_impl(const mvg_conv_desc *d, const void *x, const void *wgt, void *y, const float *bias, int relu,
-                           float *stats, void *stream, bool f32io, int stride_w = -1, int pad_w = -1, const Bf16Affine *aff = nullptr) {
+                           float *stats, void *stream, bool f32io, int stride_w = -1, int pad_w = -1, const Bf16Affine *aff = nullptr,
+                           mvg_conv_plan *query = nullptr) {
   if (stride_w < 0 && validate_bf16(d)) return 2;
   IgemmParams p;
   memset(&p, 0, sizeof(p));
@@ -369,6 +402,7 @@ static int fprop_bf16_impl(const mvg_conv_desc *d, const void *x, const void *wg
   const double bytes = 2.0 * (d->groups * (double)d->n * d->h * d->w * acin + (double)d->cout * d->r * d->s * acin +
                               (aff && aff->residual ? 2.0 : 1.0) * d->groups * (double)p.rows_per_group * d->cout) + (aff ? 8.0 * d->cout : 0.0);
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
+  if (query) return launch_igemm_bf16<false>(p, nullptr, f32io, aff != nullptr, query);        // plan only: nothing is launched
   ProfScope ps(lin ? MVG_K_LINEAR_FPROP : MVG_K_CONV_FPROP, (hipStream_t)stream, flops, bytes);
   return launch_igemm_bf16<false>(p, (hipStream_t)stream, f32io, aff != nullptr);
 }
@@ -395,7 +429,7 @@ struct Bf16BnFuse {        // fused BatchNorm-backward reduce of the unit whose 
 };
 
 static int dgrad_bf16_impl(const mvg_conv_desc *d, const void *dy, const void *wgt_crsk, void *dx, const void *mask,
-                           const void *addend, void *stream, bool f32io, const Bf16BnFuse *bnf = nullptr) {
+                           const void *addend, void *stream, bool f32io, const Bf16BnFuse *bnf = nullptr, mvg_conv_plan *query = nullptr) {
   if (validate_bf16(d)) return 2;
   MVG_REQUIRE(!f32io || d->stride == 1, "bf16 dgrad with fp32 operands: stride 1 only");
   IgemmParams p;
@@ -421,6 +455,11 @@ static int dgrad_bf16_impl(const mvg_conv_desc *d, const void *dy, const void *w
   const double bytes = 2.0 * (d->groups * (double)d->n * d->ho * d->wo * d->cout + (double)d->cout * d->r * d->s * d->cin) +
                        (bnf ? 4.125 : 2.0) * d->groups * (double)d->n * d->h * d->w * d->cin;      // (fused reduce: + y and the mask bits)
   const bool lin = d->r == 1 && d->s == 1 && d->h == 1 && d->w == 1;
+  if (query) {                       // plan only: the class table without the fills of the classes it drops
+    DgradDropped dropped;
+    dgrad_plan_classes(p, d, bnf != nullptr, dropped);
+    return launch_igemm_bf16<true>(p, nullptr, f32io, false, query);
+  }
   ProfScope ps(lin ? MVG_K_LINEAR_DGRAD : MVG_K_CONV_DGRAD, (hipStream_t)stream, flops, bytes);
   if (int e = dgrad_classes(p, d, bnf != nullptr, f32io ? 4 : 2, dx, addend, (hipStream_t)stream)) return e;
   if (p.ncls == 0) return 0;
@@ -515,6 +554,10 @@ static void wgrad_bf16_tile(const mvg_conv_desc *d, int &bm, int &bn) {
   bn = ncols >= 128 ? 128 : 64;
 }
 
+// incremental pixel stepping of the bf16-operand loader: at most one image wrap per 64-pixel step (the fp32-operand form
+// decodes every step)
+static bool wgrad_bf16_incremental(const mvg_conv_desc *d) { return (long long)d->ho * d->wo >= 128; }
+
 // The pixel splits of a checked descriptor (the stem's folded one included) at its tile.
 static int wgrad_bf16_splits(const mvg_conv_desc *d) {
   int bm, bn;
@@ -542,7 +585,7 @@ static int wgrad_bf16_impl(const mvg_conv_desc *d, const void *x, const void *dy
   const double acin = d->cin == 8 && d->r == 7 ? 3.0 : (double)d->cin;
   const double flops = 2.0 * pixels * d->cout * d->r * d->s * acin * (stride_w >= 0 ? 147.0 / 448.0 : 1.0);
   const double bytes = 2.0 * ((double)d->groups * d->n * d->h * d->w * acin + pixels * d->cout) + 4.0 * (double)d->cout * d->r * d->s * acin;
-  const bool incr = (long long)d->ho * d->wo >= 128;       // at most one image wrap per 64-pixel step
+  const bool incr = wgrad_bf16_incremental(d);
   const auto dispatch = [&](dim3 grid, dim3 block, hipStream_t st, const WgradParams &wp) {
 #define MVG_WGRAD_BF16(BM_, BN_)                                                                          \
   do {                                                                                                    \
@@ -590,6 +633,44 @@ int mvg_linear_wgrad_mixed(const float *x, const float *dy, float *dw, float *db
                            int splits, int accumulate, void *stream) {
   const mvg_conv_desc d = linear_desc_bf16(rows, fin, fout);
   return wgrad_bf16_impl(&d, x, dy, dw, db, workspace, splits, accumulate, stream, true);
+}
+
+int mvg_conv_plan_query_bf16(const mvg_conv_desc *d, int kind, mvg_conv_plan *out) {
+  mvg_conv_plan plan;
+  memset(&plan, 0, sizeof(plan));
+  plan.splitk = 1;
+  int rc = 2;
+  static float marker;               // a non-null bn_part / scale is what selects the fused-reduce plan / the affine kernels
+  if (kind == MVG_PLAN_BF16_FPROP) {
+    rc = fprop_bf16_impl(d, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, false, -1, -1, nullptr, &plan);
+  } else if (kind == MVG_PLAN_BF16_AFFINE) {
+    const Bf16Affine a = {&marker, &marker, nullptr};
+    rc = fprop_bf16_impl(d, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, false, -1, -1, &a, &plan);
+  } else if (kind == MVG_PLAN_BF16_DGRAD) {
+    rc = dgrad_bf16_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, nullptr, &plan);
+  } else if (kind == MVG_PLAN_BF16_DGRAD_BNREDUCE) {
+    const Bf16BnFuse f = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, &marker};
+    rc = dgrad_bf16_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, false, &f, &plan);
+  } else if (kind == MVG_PLAN_BF16_LINEAR_FPROP_MIXED) {
+    rc = fprop_bf16_impl(d, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, true, -1, -1, nullptr, &plan);
+  } else if (kind == MVG_PLAN_BF16_LINEAR_DGRAD_MIXED) {
+    rc = dgrad_bf16_impl(d, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, true, nullptr, &plan);
+  } else {
+    set_error("conv_plan_query_bf16: unknown kind %d", kind);
+  }
+  if (rc) return -1;
+  if (out) *out = plan;
+  return 0;
+}
+
+int mvg_conv_wgrad_tile_bf16(const mvg_conv_desc *d, int f32in, int32_t *bm, int32_t *bn, int32_t *incremental) {
+  if (validate_bf16(d)) return -1;
+  int tm, tn;
+  wgrad_bf16_tile(d, tm, tn);
+  if (bm) *bm = tm;
+  if (bn) *bn = tn;
+  if (incremental) *incremental = (!f32in && wgrad_bf16_incremental(d)) ? 1 : 0;
+  return 0;
 }
 
 }  // extern "C"

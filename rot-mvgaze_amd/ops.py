@@ -180,6 +180,31 @@ def conv_wgrad_tile(d: ConvDesc):
     return bm.value, bn.value, bool(incr.value)
 
 
+def conv_plan_query_bf16(d: ConvDesc, kind: int = 0) -> dict:
+    """What the bf16 launch of ``d`` would run, answered by the code the launch plans with; nothing is launched.  kind:
+    _lib.PLAN_BF16_FPROP (conv_fprop_bf16), PLAN_BF16_DGRAD, PLAN_BF16_DGRAD_BNREDUCE, PLAN_BF16_AFFINE, and
+    PLAN_BF16_LINEAR_FPROP_MIXED / PLAN_BF16_LINEAR_DGRAD_MIXED (d = ConvDesc.linear(rows, fin, fout)).  Keys as conv_plan_query,
+    and "kernel": "dma" (the LDS-DMA kernel: fasta, not a mixed kind), "mixed" (the register-staged kernel on fp32 operands) or
+    "reg" (the register-staged kernel).  Raises with the launch's message for what the launch would reject."""
+    from ._lib import ConvPlan, PLAN_BF16_LINEAR_FPROP_MIXED, PLAN_BF16_LINEAR_DGRAD_MIXED
+    pl = ConvPlan()
+    if lib().mvg_conv_plan_query_bf16(C.byref(d), int(kind), C.byref(pl)) != 0:
+        check(1, "conv_plan_query_bf16")
+    mixed = int(kind) in (PLAN_BF16_LINEAR_FPROP_MIXED, PLAN_BF16_LINEAR_DGRAD_MIXED)
+    return {"bm": pl.bm, "bn": pl.bn, "bk": pl.bk, "fasta": bool(pl.fasta), "cls_tiles": list(pl.cls_tiles[:pl.ncls]),
+            "cls_kt": list(pl.cls_kt[:pl.ncls]), "streamk_grid": pl.streamk_grid, "splitk": pl.splitk,
+            "scratch_floats": pl.scratch_floats, "kernel": "mixed" if mixed else ("dma" if pl.fasta else "reg")}
+
+
+def conv_wgrad_tile_bf16(d: ConvDesc, f32in: bool = False):
+    """(bm, bn, incremental): the tile conv_wgrad on bf16 operands (f32in: linear_wgrad_mixed) runs ``d`` on and whether the
+    kernel addresses pixels incrementally."""
+    bm, bn, incr = C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if lib().mvg_conv_wgrad_tile_bf16(C.byref(d), int(bool(f32in)), C.byref(bm), C.byref(bn), C.byref(incr)) != 0:
+        check(1, "conv_wgrad_tile_bf16")
+    return bm.value, bn.value, bool(incr.value)
+
+
 def linear_wgrad(x: Tensor, dy: Tensor, dw: Tensor, db: Optional[Tensor], rows: int, fin: int, fout: int, accumulate: bool = False):
     """dw (+)= dy^T x and db (+)= column sums of dy in one launch (+ the fixed-order slab reduce)."""
     d = ConvDesc.linear(rows, fin, fout)
