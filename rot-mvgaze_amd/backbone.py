@@ -6,12 +6,31 @@ BasicBlock :80-96 / Bottleneck :128-148).  The reference runs one backbone pass 
 all V views go through each kernel launch as V *groups* - BatchNorm statistics stay per group and
 running statistics are updated once per group in view order, so results equal V separate passes.
 
-Data layout in HBM: activations NHWC fp32 ``[V][B][H][W][C]``; per conv+BN unit the tape keeps
-the raw conv output ``y`` (BN backward needs x-hat) and the post-activation ``out`` (next conv's
-input, ReLU mask); weights are the PyTorch parameters themselves in channels_last (= KRSC).
+Data layout in HBM: activations NHWC ``[V][B][H][W][C]``; per conv+BN unit the tape keeps the raw conv output ``y`` (BN
+backward needs x-hat) and the post-activation ``out`` (next conv's input, ReLU mask).
+
+Three kernel families run a unit's conv (``Family``), each with a stem form of its own:
+* FP32   the fp32-MFMA kernels: fp32 NHWC activations, the weights are the PyTorch parameters themselves in channels_last
+         (= KRSC); the 3-channel stem reads an image padded to 4 channels;
+* SPLIT  the split-operand kernels: an fp32 value held as two fp16 pieces ("sp") with a per-tensor 2^-k (``.sinv``), the
+         weights as per-step sp copies; the stem in row-window form (``stem_rw``);
+* BF16   the bf16 kernels: bf16 activations, per-step bf16 weight copies; the stem on 8-channel taps or in its folded
+         row-window form (``stem_rw``).
+
+Where each decision is made:
+* ``plan_call`` decides, once per ``forward`` call and on the host alone, what the call runs on - the 2 GiB guard of the
+  split kernels, the range guard of inference, the stem's form - and returns the frozen ``Call`` record that every helper
+  takes as an argument and that the tape keeps;
+* ``unit_family(call, c)`` is the one rule that gives conv ``c`` its family.  Whether a unit's OUTPUT is stored in sp is a
+  property of the call (``Call.sp``), not of its conv: the fp32-MFMA stem of a split call writes an sp pooled map;
+* every stage - conv launch, statistics partials, weights operand, apply form, stem tail, weight gradient, backward-data,
+  the BatchNorm-backward passes, the stem's pool backward - is one ``if family`` chain;
+* the backward reads the family from the tape (``_Unit.family`` / ``_Unit.stem_rw``), never from what the Backbone object
+  is set to by then; the hand-offs between launches are named tuples (``_Apply``, ``_PendingDy``, ``_FusedSums``, ``_Pool``).
 """
 from __future__ import annotations
 
+import enum
 import math
 import os
 from dataclasses import dataclass
@@ -108,6 +127,123 @@ class GradSink:
         raise NotImplementedError
 
 
+class Family(enum.Enum):
+    """The kernel family that runs a unit's conv (see the module docstring)."""
+    FP32 = 0      # fp32-MFMA kernels (conv_igemm.hip)
+    SPLIT = 1     # split-operand kernels (conv_split.hip): operands (x_in, out, dy, w) in sp
+    BF16 = 2      # bf16 kernels (conv_bf16.hip)
+
+
+class Call(NamedTuple):
+    """One Backbone.forward call: what plan_call decided, plus the per-step operands forward() makes (wprep, act_sinv).
+    Passed down explicitly and kept on the tape; nothing of it lives on the Backbone object."""
+    V: int
+    B: int
+    H: int
+    W: int
+    training: bool
+    keep_tape: bool
+    bf16: bool
+    split: bool                 # the split kernels may serve this call (off: MVG_SPLIT=0, the 2 GiB guard, a tripped range guard)
+    sp: bool                    # the activations of this call are stored in sp: training steps and folded inference of a split call
+    stem_rw: bool               # the stem runs in row-window form (Backbone.stem_rowwindow)
+    taped: bool                 # through _forward_taped (training, a tape, unfolded bf16 inference); else the folded _forward_infer
+    guard: Optional[str]        # split_eval_guard where it applies (folded fp32 inference), else None
+    range_live: bool            # the ranged launches are in use
+    need_dimg: bool
+    boundary: int               # Backbone._boundary (-1 without a tape)
+    wprep: Optional[Dict[str, tuple]] = None        # conv name -> this step's (w, w_t) copies, when ONE launch made them
+    act_sinv: Optional[Dict[str, Tensor]] = None    # conv name -> its output's 1-element 2^-k slot (sp training steps)
+
+
+def plan_call(spec: BackboneSpec, *, V: int, B: int, H: int, W: int, training: bool, keep_tape: bool, raw: bool = False,
+              augment: bool = False, need_dimg: bool = False, boundary: int = -1, bf16: bool = False, split: bool = True,
+              split_eval: bool = True, split_eval_guard: Optional[str] = None, stem_rowwindow: bool = True,
+              batch_weight_prep: bool = True, bf16_fold_eval: bool = True, guard_scale: int = 1, tripped: bool = False,
+              capturing: bool = False) -> Call:
+    """The size and mode decisions of one forward call, from shapes and flags alone (no tensor, no device).  raw: uint8
+    patches; augment: an input augment is set; tripped: an earlier "fallback" call overflowed (Backbone._range_tripped);
+    capturing: the stream is being captured; the other flags are the Backbone attributes of the same names."""
+    if bf16 and raw and (training or keep_tape) and not (training and augment):
+        raise NotImplementedError("raw uint8 input with the bf16 path is served for inference only (model.eval() under "
+                                  "torch.no_grad()) and for training steps with model.input_augment (augment.TrainAugment; the "
+                                  "identity augment for un-augmented steps): else normalise to fp32 NCHW first")
+    # The split kernels address one view of an sp tensor (4 bytes per element) with 32-bit offsets: the largest one
+    # (layer1's output: (H/4) x (W/4) x 64 or 256 channels per image) must stay below 2 GiB, or this call runs on the
+    # fp32-MFMA kernels (64-bit row offsets there; B <= 668 per view at 224 x 224 with ResNet-50)
+    biggest_view_elems = B * ((H + 3) // 4) * ((W + 3) // 4) * spec.blocks[0].convs[-1].cout
+    split = split and 4 * biggest_view_elems * guard_scale < 0x7FFFFFF0
+    infer = not (training or keep_tape or bf16)         # the folded fp32 inference forward: what split_eval_guard covers
+    if split_eval_guard not in (None, "record", "fallback"):
+        raise ValueError(f"split_eval_guard must be None, 'record' or 'fallback' (got {split_eval_guard!r})")
+    guard = split_eval_guard if infer else None
+    if guard == "fallback" and capturing:
+        raise RuntimeError("split_eval_guard = 'fallback' reads the range record on the host and cannot run while the stream "
+                           "is capturing: capture with 'record' and check overflowed() after the replay")
+    if guard == "fallback" and tripped:
+        split = False                        # an earlier call overflowed: fp32-MFMA kernels until the weights change
+    # the stem's form for this call (see stem_rowwindow)
+    if bf16:        # folded windows: width % 4, whole 64-row partials (n * ho * wo / 2), the stem's weights through the batch
+        ho, wo = (H - 1) // 2 + 1, W // 2
+        stem_rw = (stem_rowwindow and training and W % 4 == 0 and (B * ho * (wo // 2)) % 64 == 0 and batch_weight_prep
+                   and spec.stem.k == 7)
+    else:
+        stem_rw = (split and stem_rowwindow and training and not need_dimg and W % 2 == 0
+                   and batch_weight_prep and 32 * B * H * (W // 2) * 4 < 0x7FFFFFF0)
+    taped = training or keep_tape or (bf16 and not bf16_fold_eval)
+    # sp storage: training steps of the fp32 model; folded inference with split_eval (an eval-mode tape: fp32-MFMA kernels)
+    sp = split and not bf16 and (training or (infer and split_eval))
+    return Call(V, B, H, W, training, keep_tape, bf16, split, sp, stem_rw, taped, guard,
+                range_live=guard is not None and sp, need_dimg=need_dimg, boundary=boundary)
+
+
+def unit_family(call: Call, c: ConvSpec) -> Family:
+    """The family that runs conv ``c`` in ``call``: everything on a bf16 call is bf16; every conv of an sp call is split but
+    the 3-channel stem, which is fp32-MFMA (on 4-channel taps) unless the row-window form is on; else fp32-MFMA."""
+    if call.bf16:
+        return Family.BF16
+    if call.sp and (c.cin != 3 or call.stem_rw):
+        return Family.SPLIT
+    return Family.FP32
+
+
+class _Apply(NamedTuple):
+    """A residual unit's forward apply pass, handed to the next block's first conv (bn_apply_fprop_eligible)."""
+    y: Tensor
+    scale: Tensor
+    shift: Tensor
+    residual: Optional[Tensor]
+    residual_affine: Optional[tuple]
+    bits: Optional[Tensor]
+
+
+class _PendingDy(NamedTuple):
+    """What the backward-data launch of a unit needs, besides the unit's own tape record, to form the unit's dy in its loader
+    (bn_apply_dgrad_eligible): the masked gradient and its sums.  dy's 2^-k is its .sinv."""
+    dz: Tensor
+    s1: Tensor
+    s2: Tensor
+
+
+class _FusedSums(NamedTuple):
+    """BatchNorm-backward sums delivered by the backward-data launch that produced a unit's (masked) gradient."""
+    s1: Tensor
+    s2: Tensor
+    mx: Optional[Tensor] = None       # split: max |dz| per channel
+    sinv: Optional[Tensor] = None     # split: the 2^-k of the dy the unit's apply pass will write
+
+
+class _Pool(NamedTuple):
+    """The stem's fused max pool, for its backward."""
+    argmax: Tensor
+    scale: Tensor
+    shift: Tensor
+    ho: int
+    wo: int
+    hp: int
+    wp: int
+
+
 @dataclass(slots=True)
 class _Unit:
     """Saved state of one conv + BN (+ReLU) (+residual) for the backward pass."""
@@ -122,19 +258,19 @@ class _Unit:
     rows: int = 0
     w: Optional[Tensor] = None        # the backward-data operand: the transposed copy on the bf16 / split kernels
     trained: bool = True              # normalised with batch statistics (False: eval mode, running statistics)
-    pool: Optional[tuple] = None      # the stem: (argmax, scale, shift, ho, wo, hp, wp) of the fused max pool
+    pool: Optional[_Pool] = None      # the stem: its fused max pool
     relu_affine: Optional[tuple] = None   # ReLU without residual: (scale, shift) - the backward rebuilds the mask from y
-    fused_s12: Optional[object] = None    # BatchNorm-backward sums delivered by the backward-data launch that produced this unit's gradient
+    fused_s12: Optional[_FusedSums] = None    # delivered by the backward-data launch that produced this unit's gradient
     relu_bits: Optional[Tensor] = None    # residual units: the ReLU mask as one byte per 16-byte access (ops.bn_apply_bits)
-    split: bool = False       # conv operands (x_in, out, dy, w) in sp (two fp16 pieces), split-operand kernels (conv_split.hip)
-    stem_rw: bool = False     # the stem in row-window form: x_in is the window operand, dy goes out in sp
+    family: Family = Family.FP32      # what ran the conv in the forward (unit_family): the backward follows it
+    stem_rw: bool = False     # the stem in row-window form: x_in is the window operand (split: dy goes out in sp)
 
 
 class _Fwd(NamedTuple):
     """What Backbone._unit_fwd returns, whatever its mode (members a mode does not produce are None)."""
     out: Tensor                       # the unit's output; the pooled map (pool); the raw conv output y (defer_apply)
     affine: Optional[tuple] = None    # defer_apply: the (scale, shift) the consumer normalises ``out`` with
-    pending: Optional[tuple] = None   # the apply pass handed to next_conv's forward launch (bn_apply_fprop_eligible)
+    pending: Optional[_Apply] = None  # the apply pass handed to next_conv's forward launch (bn_apply_fprop_eligible)
 
 
 class Backbone:
@@ -204,8 +340,7 @@ class Backbone:
         self.split_eval_guard: Optional[str] = None
         self._range_record: Optional[Tensor] = None       # int32 [len(range_unit_names)]: a plain attribute, not a buffer
         self._range_slot: Dict[str, int] = {n: i for i, n in enumerate(range_unit_names(depth, prefix))}
-        self._range_live = False              # per forward call: the ranged launches are in use
-        self._range_tripped = False           # "fallback" saw an overflow: inference stays on the fp32-MFMA kernels
+        self._range_tripped = False         # "fallback" saw an overflow: inference stays on the fp32-MFMA kernels
         # bf16 path, inference (no tape): BatchNorm on the running statistics, the residual and the ReLU folded into the conv
         # epilogue (mvg_conv_fprop_bf16_affine) - every activation written once and rounded once - the downsample branch
         # stored normalised, and the bf16 weight copies kept between calls.  (attribute False: the training-shaped launches -
@@ -215,31 +350,39 @@ class Backbone:
         self._wk_cache: Dict[str, tuple] = {}     # inference: conv name -> (data_ptr, version, sp weights)
         # training: one launch per step makes every conv's bf16 / sp weight copies
         self.batch_weight_prep = True
-        self._wprep: Optional[Dict[str, tuple]] = None
         self._wprep_state = None
         self._wprep_versions = None
         # split path, training: per-tensor scales of the sp activations (one launch per step: _prepare_act_scales)
         self._ascale_state = None             # (key, device table, records, conv name -> slot, slots)
-        self._act_sinv: Optional[Dict[str, Tensor]] = None    # per forward call: conv name -> its output's 1-element slot
         self._wg_defer: Optional[list] = None # backward: (slabs, dw, splits, accumulate) of the split wgrads whose reduce is pending
-        self._split_now = self.split          # per forward call: off when a view's largest sp tensor would exceed 2 GiB
-        self._stem_rw = False                 # per forward call: the stem runs in row-window form on the split kernels
+        self._last_call: Optional[Call] = None    # the record of the last forward call (tests and tools read it through the properties below)
         self._stem_w8 = None
 
     @property
     def bf16(self) -> bool:
         return self.act_dtype == torch.bfloat16
 
+    @property
+    def _split_now(self) -> bool:             # the last call: off when a view's largest sp tensor would exceed 2 GiB
+        return self._last_call.split if self._last_call is not None else self.split
+
+    @property
+    def _stem_rw(self) -> bool:               # the last call: the stem ran in row-window form
+        return self._last_call is not None and self._last_call.stem_rw
+
+    @property
+    def _act_sinv(self) -> Optional[Dict[str, Tensor]]:       # the last call: conv name -> its output's 1-element slot
+        return self._last_call.act_sinv if self._last_call is not None else None
+
     # ---------------------------------------------------------------- helpers
-    def _prepare_weights(self, dev, reuse: bool = False) -> Dict[str, tuple]:
+    def _prepare_weights(self, dev, family: Family, stem_rw: bool, reuse: bool = False) -> Dict[str, tuple]:
         """The per-step copies of every conv's weights the bf16 / split kernels read (KRSC for fprop, CRSK for
         backward-data), made by ONE launch: destination buffers and the launch's device-resident table of
         (source, destinations, shape) records are built once per parameter placement and reused every step.
         reuse (bf16 inference): no launch when the buffers already hold these parameters - same placement, same version
         counters as _wprep_versions, and nothing invalidated them since (invalidate_weight_cache, train(), any other
         forward).  The buffers then hold exactly what _wprep_versions says, as the tapes that point into them expect."""
-        mode = 0 if self.bf16 else 1
-        stem_rw = self._stem_rw
+        mode = 0 if family is Family.BF16 else 1          # (the launch's own numbering)
         convs = [c for c in self.spec.all_convs() if not (mode == 1 and c.cin == 3 and not stem_rw)]
         key = (mode, stem_rw, str(dev), tuple(self.p[c.name + ".weight"].data_ptr() for c in convs))
         if self._wprep_state is None or self._wprep_state[0] != key:
@@ -381,46 +524,44 @@ class Backbone:
         return [self.p[c.bn + ".num_batches_tracked"] for c in self.spec.all_convs()]
 
     # ---------------------------------------------------------------- forward
-    def _conv_weights(self, c: ConvSpec, d: ConvDesc, sp: bool, need_transposed: bool):
-        """(w, w_t): the KRSC weight operand of conv ``c`` and its transposed copy for backward-data (or None).  sp: the launch
-        reads sp operands (split kernels; the stem in row-window form).  sp / bf16: this step's copies when ONE launch at the
-        start of forward() made them (_wprep), else a split / cast per call; otherwise the fp32 parameter itself."""
-        if (sp or self.bf16) and self._wprep is not None:
-            return self._wprep[c.name]
+    def _conv_weights(self, call: Call, c: ConvSpec, d: ConvDesc, family: Family, need_transposed: bool):
+        """(w, w_t): the KRSC weight operand of conv ``c`` and its transposed copy for backward-data (or None).  SPLIT / BF16:
+        this step's copies when ONE launch at the start of forward() made them (call.wprep), else a split / cast per call;
+        FP32: the fp32 parameter itself."""
+        if family is not Family.FP32 and call.wprep is not None:
+            return call.wprep[c.name]
         wsrc = self.p[c.name + ".weight"].detach()
-        if c.cin == 3 and not (sp or self.bf16):                          # the 3-channel stem padded to 4 channels
+        if family is Family.FP32 and c.cin == 3:                          # the 3-channel stem padded to 4 channels
             w4 = torch.zeros(c.cout, c.k, c.k, 4, dtype=torch.float32, device=wsrc.device)
             w4[..., :3].copy_(wsrc.permute(0, 2, 3, 1))                   # 9408 floats: layout plumbing
             return w4, None
         assert wsrc.is_contiguous(memory_format=torch.channels_last) or (c.k == 1 and wsrc.is_contiguous()), \
             f"{c.name}.weight must be channels_last (KRSC)"
-        if not (sp or self.bf16):
+        if family is Family.FP32:
             return wsrc, None
-        if sp:
+        if family is Family.SPLIT:
             return ops.split_weights(d, wsrc, need_transposed=need_transposed)
         # one cast of the fp32 master weights per step: KRSC for fprop, CRSK (transposed) for backward-data
         return ops.cast_weights_bf16(d, wsrc, c.cin, need_transposed=need_transposed and c.cin != 3)
 
-    def _unit_infer(self, c: ConvSpec, x: Tensor, G: int, N: int, H: int, W: int, relu: bool, residual: Optional[Tensor],
+    def _unit_infer(self, call: Call, c: ConvSpec, x: Tensor, H: int, W: int, relu: bool, residual: Optional[Tensor],
                     pool: bool = False) -> Tensor:
         """Folded inference unit (no tape, not training, not the unfolded bf16 form): conv with BatchNorm on the running
         statistics (+ residual) (+ ReLU) in its epilogue - ONE launch, the output written once.  Returns the unit's output;
         pool (the fp32 stem): the max-pooled map, in sp when the split kernels serve the call.
         csrc/session_plan.cpp restates this method (its unit()) and _forward_infer (its block loop) as data, for the fp32
         model (build) and for the bf16 branch (build_bf16): a change to the launches here must be made there too."""
-        bf = self.bf16
-        assert not (bf and pool)                 # the bf16 stem goes through _unit_fwd
+        family, G, N = unit_family(call, c), call.V, call.B
+        assert not (family is Family.BF16 and pool)      # the bf16 stem goes through _unit_fwd
         d = ConvDesc.make(G, N, H, W, 4 if c.cin == 3 else c.cin, c.cout, c.k, c.stride, c.pad)
         dev = x.device
-        sp_eval = self._split_now and self.split_eval and not bf
-        sp = sp_eval and c.cin != 3              # this conv on the split kernels (the 3-channel stem: fp32-MFMA)
-        if not sp:
-            w, _ = self._conv_weights(c, d, False, False)
+        if family is not Family.SPLIT:           # (SPLIT: the cached sp copy below)
+            w, _ = self._conv_weights(call, c, d, family, False)
         aff = torch.empty(2, 1, c.cout, dtype=torch.float32, device=dev)
         ops.bn_eval_affine(1, c.cout, self.p[c.bn + ".weight"].detach(), self.p[c.bn + ".bias"].detach(),
                            self.p[c.bn + ".running_mean"], self.p[c.bn + ".running_var"], BN_EPS, aff[0], aff[1])
         scale, shift = aff[0, 0], aff[1, 0]
-        if sp:
+        if family is Family.SPLIT:
             # the epilogue writes the next conv's sp operand directly (the downsample branch, read only as a residual, stays
             # fp32).  The sp copy of the weights is kept between calls while the parameter is unchanged (its version counter:
             # load_state_dict, optimizer steps - the fused Adam bumps it explicitly - and broadcasts all move it)
@@ -429,17 +570,17 @@ class Backbone:
             if hit is not None and hit[0] == wsrc.data_ptr() and hit[1] == wsrc._version:
                 wk = hit[2]
             else:
-                wk, _ = self._conv_weights(c, d, True, False)
+                wk, _ = self._conv_weights(call, c, d, family, False)
                 self._wk_cache[c.name] = (wsrc.data_ptr(), wsrc._version, wk)
             out = (ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev) if relu
                    else torch.empty(G, N, d.ho, d.wo, c.cout, dtype=torch.float32, device=dev))
-            if self._range_live and relu:        # (an sp output: every unit but the downsample branches)
+            if call.range_live and relu:         # (an sp output: every unit but the downsample branches)
                 ops.conv_fprop_split_affine_ranged(d, x, wk, out, scale, shift, residual, relu, self._range_word(c))
             else:
                 ops.conv_fprop_split_affine(d, x, wk, out, scale, shift, residual, relu)
             return out
         y = torch.empty(G, N, d.ho, d.wo, c.cout, dtype=self.act_dtype, device=dev)
-        if bf:                                   # y is the unit's output, written once, rounded once
+        if family is Family.BF16:                # y is the unit's output, written once, rounded once
             ops.conv_fprop_bf16_affine(d, x, w, y, scale, shift, residual, relu)
             if self._debug_units is not None:
                 self._debug_units.append((c.name, x, residual, y))
@@ -448,9 +589,9 @@ class Backbone:
         if not pool:
             return y
         pooled = self._pool_plain(y, G, N, d.ho, d.wo, c.cout)
-        if sp_eval and self._range_live:
+        if call.range_live:                      # (the pooled map of an sp call)
             return ops.split_f32_ranged(pooled, self._range_word(c))
-        return ops.split_f32(pooled) if sp_eval else pooled
+        return ops.split_f32(pooled) if call.sp else pooled
 
     def _range_word(self, c: ConvSpec) -> Tensor:
         i = self._range_slot[c.name]
@@ -464,18 +605,23 @@ class Backbone:
         ops.maxpool_fwd(a0, x, argmax, G * N, h, w, c, hp, wp_)
         return x
 
-    def _stats_partials(self, c: ConvSpec, d: ConvDesc, sp_in: bool, stem_rw: bool):
+    @staticmethod
+    def _stats_partials(c: ConvSpec, d: ConvDesc, family: Family, stem_rw: bool):
         """(partials per group, rows per partial) of the batch statistics that the unit's forward launch leaves."""
-        if stem_rw and self.bf16:   # two output columns per GEMM row: twice the partials of a forward over n x ho x wo/2 rows
-            P, rpp = ops.conv_stats_partials(ConvDesc.make(d.groups, d.n, d.ho, d.wo // 2, 64, 2 * c.cout, 1, 1, 0), True)
-            return 2 * P, rpp
-        if stem_rw:                 # the same row tiles as any split forward with these n, ho, wo
-            return ops.conv_stats_partials_split(ConvDesc.make(d.groups, d.n, d.ho, d.wo, 32, c.cout, 1, 1, 0))
-        return ops.conv_stats_partials_split(d) if sp_in else ops.conv_stats_partials(d, self.bf16)
+        if family is Family.BF16:
+            if stem_rw:             # two output columns per GEMM row: twice the partials of a forward over n x ho x wo/2 rows
+                P, rpp = ops.conv_stats_partials(ConvDesc.make(d.groups, d.n, d.ho, d.wo // 2, 64, 2 * c.cout, 1, 1, 0), True)
+                return 2 * P, rpp
+            return ops.conv_stats_partials(d, True)
+        if family is Family.SPLIT:
+            if stem_rw:             # the same row tiles as any split forward with these n, ho, wo
+                return ops.conv_stats_partials_split(ConvDesc.make(d.groups, d.n, d.ho, d.wo, 32, c.cout, 1, 1, 0))
+            return ops.conv_stats_partials_split(d)
+        return ops.conv_stats_partials(d, False)
 
-    def _unit_fwd(self, c: ConvSpec, x: Tensor, G: int, N: int, H: int, W: int, training: bool, relu: bool,
-                  residual: Optional[Tensor], tape: Optional[list], pool: bool = False, residual_affine=None,
-                  defer_apply: bool = False, next_conv: Optional[ConvSpec] = None, pending_apply: Optional[tuple] = None) -> _Fwd:
+    def _unit_fwd(self, call: Call, c: ConvSpec, x: Tensor, H: int, W: int, *, relu: bool, residual: Optional[Tensor] = None,
+                  tape: Optional[list] = None, pool: bool = False, residual_affine=None, defer_apply: bool = False,
+                  next_conv: Optional[ConvSpec] = None, pending_apply: Optional[_Apply] = None) -> _Fwd:
         """conv -> BatchNorm (-> + residual) (-> ReLU), the BatchNorm as passes of its own: batch statistics (training) or
         the running ones (eval mode with a tape; bf16 inference that is not folded; the bf16 inference stem).  Returns _Fwd.
         pool=True (the stem): the 3x3/2 max pool is fused behind the ReLU - out is the pooled map; the normalised map is not stored.
@@ -487,92 +633,117 @@ class Backbone:
         next_conv (a block's last unit: the next block's first conv): when bn_apply_fprop_eligible accepts the pair, this unit's
         apply pass is NOT launched - out is allocated and recorded on the tape as usual, and the next block's first unit
         takes ``pending`` as pending_apply: its forward launch forms, uses and writes ``x`` (= that out)."""
-        bf = self.bf16
-        d = ConvDesc.make(G, N, H, W, (8 if bf else 4) if c.cin == 3 else c.cin, c.cout, c.k, c.stride, c.pad)
-        dev = x.device
-        # split path: training steps of the fp32 model; sp_in = this conv reads sp operands (all but the stem),
-        # sp_out = its consumers do (every unit: the stem's pooled map feeds layer1)
-        sp_out = self._split_now and training and not bf
-        sp_in = sp_out and c.cin != 3
-        stem_rw = c.cin == 3 and self._stem_rw and (sp_out or bf)  # x is then the row-window operand (ops.stem_rowwindow_split / _bf16)
-        assert pending_apply is None or (sp_in and not stem_rw)
-        assert not stem_rw or self._wprep is not None               # the row-window filter comes from the batched weight prep only
-        keep = tape is not None
-        w, w_t = self._conv_weights(c, d, sp_in or stem_rw, keep)
-        y = torch.empty(G, N, d.ho, d.wo, c.cout, dtype=self.act_dtype, device=dev)
+        family = unit_family(call, c)
+        stem_rw = c.cin == 3 and call.stem_rw     # x is then the row-window operand (ops.stem_rowwindow_split / _bf16)
+        G, N, training, keep = call.V, call.B, call.training, tape is not None
+        d = ConvDesc.make(G, N, H, W, (8 if family is Family.BF16 else 4) if c.cin == 3 else c.cin, c.cout, c.k, c.stride, c.pad)
+        assert pending_apply is None or (family is Family.SPLIT and not stem_rw)
+        assert not stem_rw or call.wprep is not None                # the row-window filter comes from the batched weight prep only
+        w, w_t = self._conv_weights(call, c, d, family, keep)
         rows = N * d.ho * d.wo
-        gamma, beta = self.p[c.bn + ".weight"].detach(), self.p[c.bn + ".bias"].detach()
-        rm, rv = self.p[c.bn + ".running_mean"], self.p[c.bn + ".running_var"]
-        mean, invstd, scale, shift = torch.empty(4, G, c.cout, dtype=torch.float32, device=dev)
-        stats = None                             # training: the launch leaves partial batch statistics per row tile
-        if training:
-            P, rpp = self._stats_partials(c, d, sp_in, stem_rw)
-            stats = torch.empty(G, P, 2, c.cout, dtype=torch.float32, device=dev)
-        if stem_rw and bf:
-            ops.stem_fprop_bf16(d, x, w, y, stats)
-        elif stem_rw:
-            ops.stem_fprop_split(d, x, w, y, stats)
-        elif pending_apply is not None:
-            # x does not exist yet: this launch forms it from the previous block's last unit, then every later reader finds it
-            py, pscale, pshift, pres, pres_affine, pbits = pending_apply
-            ops.conv_fprop_split_bnapply(d, x, py, pscale, pshift, pres, w, y, stats, pres_affine, pbits)
-        elif sp_in:
-            ops.conv_fprop_split(d, x, w, y, stats)
-        else:
-            ops.conv_fprop(d, x, w, y, None, False, stats)
-        if training:
-            ops.bn_finalize(stats, G, P, rpp, rows, c.cout, gamma, beta, rm, rv, BN_MOMENTUM, BN_EPS, mean, invstd,
-                            scale, shift)
-        else:
-            ops.bn_eval_affine(G, c.cout, gamma, beta, rm, rv, BN_EPS, scale, shift)
+        # training: (partials per group, rows per partial) of the batch statistics that the conv launch leaves
+        partials = self._stats_partials(c, d, family, stem_rw) if training else None
+        y, stats = self._conv_fwd(c, d, family, stem_rw, x, w, pending_apply, partials)
+        mean, invstd, scale, shift = self._bn_fwd_stats(c, G, rows, stats, partials)
         out = bits = pool_rec = handed = None
         if defer_apply:
             assert not relu and residual is None and not pool
         elif pool:
             assert relu and residual is None
-            out, pool_rec = self._stem_tail(c, d, y, scale, shift, sp_out)
+            out, pool_rec = self._stem_tail(call, c, d, y, scale, shift)
             if self._debug_units is not None and not keep and not training:
                 self._debug_units.append((c.name, x, y, out))
-        elif sp_out:
-            out = ops.sp_empty(G, N, d.ho, d.wo, c.cout, device=dev)
-            out.sinv = self._act_sinv[c.name]       # this step's 2^-k of the unit's output (an sp identity brings its own)
-            want_bits = keep and relu and residual is not None
-            if (next_conv is not None and self.fuse_bn_apply_fprop
-                    and bn_apply_fprop_eligible(c, next_conv, split=sp_in, trained=training, residual=residual is not None, relu=relu)
-                    and ops.conv_fprop_split_stages(ConvDesc.make(G, N, d.ho, d.wo, next_conv.cin, next_conv.cout, 1, 1, 0)) == 1):
-                bits = torch.empty(G * rows * c.cout // 4, dtype=torch.uint8, device=dev) if want_bits else None
-                handed = (y, scale, shift, residual, residual_affine, bits)
-            else:
-                bits = ops.bn_apply_split(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine, want_bits=want_bits)
         else:
-            out = torch.empty_like(y) if keep else y            # inference: normalise in place
-            if keep and relu and residual is not None and self.relu_bits:
-                bits = ops.bn_apply_bits(y, scale, shift, residual, out, G, rows, c.cout, residual_affine)
-            else:
-                ops.bn_apply(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine)
+            out, bits, handed = self._apply_fwd(call, c, d, family, y, scale, shift, relu, residual, residual_affine, keep, next_conv)
         if keep:
             # (ReLU without residual: the backward rebuilds the mask from y - saves reading `out` twice)
             tape.append(_Unit(spec=c, desc=d, x_in=x, y=y, out=None if pool else out, mean=mean, invstd=invstd, relu=relu,
-                              rows=rows, w=w_t if (bf or sp_in) else w, trained=training, split=sp_in, stem_rw=stem_rw,
+                              rows=rows, w=w if family is Family.FP32 else w_t, trained=training, family=family, stem_rw=stem_rw,
                               relu_affine=(scale, shift) if (relu and residual is None and not pool) else None,
                               pool=pool_rec, relu_bits=bits))
         return _Fwd(y, affine=(scale, shift)) if defer_apply else _Fwd(out, pending=handed)
 
-    def _stem_tail(self, c: ConvSpec, d: ConvDesc, y: Tensor, scale: Tensor, shift: Tensor, sp_out: bool):
-        """BatchNorm apply + ReLU + 3x3/2 max pool of the stem in one pass.  Returns (pooled map, the _Unit.pool record)."""
+    def _conv_fwd(self, c: ConvSpec, d: ConvDesc, family: Family, stem_rw: bool, x: Tensor, w: Tensor,
+                  pending_apply: Optional[_Apply], partials: Optional[tuple]):
+        """Stage 1 of _unit_fwd, the conv launch.  Returns (y, stats): the raw conv output and, in training, the partial batch
+        statistics per row tile that the launch leaves (else None)."""
+        dev = x.device
+        y = torch.empty(d.groups, d.n, d.ho, d.wo, c.cout, dtype=self.act_dtype, device=dev)
+        stats = None
+        if partials is not None:
+            stats = torch.empty(d.groups, partials[0], 2, c.cout, dtype=torch.float32, device=dev)
+        if family is Family.BF16:
+            if stem_rw:
+                ops.stem_fprop_bf16(d, x, w, y, stats)
+            else:
+                ops.conv_fprop(d, x, w, y, None, False, stats)
+        elif family is Family.SPLIT:
+            if stem_rw:
+                ops.stem_fprop_split(d, x, w, y, stats)
+            elif pending_apply is not None:
+                # x does not exist yet: this launch forms it from the previous block's last unit, then every later reader finds it
+                p = pending_apply
+                ops.conv_fprop_split_bnapply(d, x, p.y, p.scale, p.shift, p.residual, w, y, stats, p.residual_affine, p.bits)
+            else:
+                ops.conv_fprop_split(d, x, w, y, stats)
+        else:
+            ops.conv_fprop(d, x, w, y, None, False, stats)
+        return y, stats
+
+    def _bn_fwd_stats(self, c: ConvSpec, G: int, rows: int, stats: Optional[Tensor], partials: Optional[tuple]):
+        """Stage 2 of _unit_fwd: (mean, invstd, scale, shift) from the launch's partials (training: batch statistics, and the
+        running ones updated), else from the running statistics (mean / invstd are then left unfilled)."""
+        gamma, beta = self.p[c.bn + ".weight"].detach(), self.p[c.bn + ".bias"].detach()
+        rm, rv = self.p[c.bn + ".running_mean"], self.p[c.bn + ".running_var"]
+        mean, invstd, scale, shift = torch.empty(4, G, c.cout, dtype=torch.float32, device=gamma.device)
+        if partials is not None:
+            P, rpp = partials
+            ops.bn_finalize(stats, G, P, rpp, rows, c.cout, gamma, beta, rm, rv, BN_MOMENTUM, BN_EPS, mean, invstd,
+                            scale, shift)
+        else:
+            ops.bn_eval_affine(G, c.cout, gamma, beta, rm, rv, BN_EPS, scale, shift)
+        return mean, invstd, scale, shift
+
+    def _apply_fwd(self, call: Call, c: ConvSpec, d: ConvDesc, family: Family, y: Tensor, scale: Tensor, shift: Tensor, relu: bool,
+                   residual: Optional[Tensor], residual_affine, keep: bool, next_conv: Optional[ConvSpec]):
+        """Stage 3 of _unit_fwd: the apply pass (+ residual) (+ ReLU), or its hand-off to next_conv's launch.  The output's
+        storage follows the call (sp or the activation type).  Returns (out, the ReLU mask bits or None, the _Apply handed on
+        or None)."""
+        G, rows = d.groups, d.n * d.ho * d.wo
+        if call.sp:
+            out = ops.sp_empty(G, d.n, d.ho, d.wo, c.cout, device=y.device)
+            out.sinv = call.act_sinv[c.name]        # this step's 2^-k of the unit's output (an sp identity brings its own)
+            want_bits = keep and relu and residual is not None
+            if (next_conv is not None and self.fuse_bn_apply_fprop
+                    and bn_apply_fprop_eligible(c, next_conv, split=family is Family.SPLIT, trained=call.training,
+                                                residual=residual is not None, relu=relu)
+                    and ops.conv_fprop_split_stages(ConvDesc.make(G, d.n, d.ho, d.wo, next_conv.cin, next_conv.cout, 1, 1, 0)) == 1):
+                bits = torch.empty(G * rows * c.cout // 4, dtype=torch.uint8, device=y.device) if want_bits else None
+                return out, bits, _Apply(y, scale, shift, residual, residual_affine, bits)
+            bits = ops.bn_apply_split(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine, want_bits=want_bits)
+            return out, bits, None
+        out = torch.empty_like(y) if keep else y            # inference: normalise in place
+        if keep and relu and residual is not None and self.relu_bits:
+            return out, ops.bn_apply_bits(y, scale, shift, residual, out, G, rows, c.cout, residual_affine), None
+        ops.bn_apply(y, scale, shift, residual, relu, out, G, rows, c.cout, residual_affine)
+        return out, None, None
+
+    def _stem_tail(self, call: Call, c: ConvSpec, d: ConvDesc, y: Tensor, scale: Tensor, shift: Tensor):
+        """BatchNorm apply + ReLU + 3x3/2 max pool of the stem in one pass, the pooled map stored as the call stores its
+        activations.  Returns (pooled map, the _Unit.pool record)."""
         G, N = y.shape[0], y.shape[1]
         hp, wp_ = (d.ho + 2 - 3) // 2 + 1, (d.wo + 2 - 3) // 2 + 1
         argmax = torch.empty(G, N, hp, wp_, c.cout, dtype=torch.uint8, device=y.device)
-        if sp_out:
+        if call.sp:
             out = ops.sp_empty(G, N, hp, wp_, c.cout, device=y.device)
-            out.sinv = self._act_sinv[c.name]
+            out.sinv = call.act_sinv[c.name]
             ops.bn_relu_maxpool_fwd_split(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
         else:
             out = torch.empty(G, N, hp, wp_, c.cout, dtype=self.act_dtype, device=y.device)
             ops.bn_relu_maxpool_fwd(y, scale, shift, out, argmax, G, N, d.ho, d.wo, c.cout, hp, wp_)
-        return out, (argmax, scale, shift, d.ho, d.wo, hp, wp_)
+        return out, _Pool(argmax, scale, shift, d.ho, d.wo, hp, wp_)
 
-    def _input_layout(self, imgs: List[Tensor], B: int, H: int, W: int, input_bgr: bool, augment=None) -> Tensor:
+    def _input_layout(self, call: Call, imgs: List[Tensor], input_bgr: bool, augment=None) -> Tensor:
         """x0, the stem's input operand, one launch per view: row windows straight from the NCHW input when the stem runs in
         row-window form (no NHWC image is built); else the NHWC image padded to 4 (bf16: 8) channels, from raw uint8 patches
         or NCHW fp32 - and the windows from that image for raw input with a row-window stem.  augment (training steps on raw
@@ -581,9 +752,9 @@ class Backbone:
         that launch stores the stem's operand itself - the row windows when the stem runs in row-window form, else the NHWC8
         image - rounded once from the fp32 value: one launch per view, no fp32 image in between.
         (The bf16 branch without a row-window stem is restated by csrc/session_plan.cpp's build_bf16.)"""
-        V, dev, bf = len(imgs), imgs[0].device, self.bf16
+        V, B, H, W, dev, bf = call.V, call.B, call.H, call.W, imgs[0].device, call.bf16
         raw = imgs[0].dtype == torch.uint8
-        direct = self._stem_rw and (not raw or (bf and augment is not None))    # each view's launch writes the windows itself
+        direct = call.stem_rw and (not raw or (bf and augment is not None))     # each view's launch writes the windows itself
         if direct and bf:
             x0 = torch.empty(V, B, H, W // 4, 64, dtype=self.act_dtype, device=dev)
         elif direct:
@@ -616,7 +787,7 @@ class Backbone:
                 (ops.stem_rowwindow_bf16 if bf else ops.stem_rowwindow_split_nchw)(im.detach().contiguous(), x0[v])
             else:
                 (ops.nchw_to_nhwc8_bf16 if bf else ops.nchw_to_nhwc4)(im.detach().contiguous(), x0[v], B, 3, H, W)
-        if self._stem_rw and not direct:                # raw uint8 input: windows from the normalised NHWC4 image
+        if call.stem_rw and not direct:                 # raw uint8 input: windows from the normalised NHWC4 image
             x0 = ops.stem_rowwindow_split(x0)
         return x0
 
@@ -638,62 +809,43 @@ class Backbone:
             B, C, H, W = imgs[0].shape
         assert C == 3
         dev = imgs[0].device
-        if self.bf16 and raw and (training or keep_tape) and not (training and input_augment is not None):
-            raise NotImplementedError("raw uint8 input with the bf16 path is served for inference only (model.eval() under "
-                                      "torch.no_grad()) and for training steps with model.input_augment (augment.TrainAugment; the "
-                                      "identity augment for un-augmented steps): else normalise to fp32 NCHW first")
-        # The split kernels address one view of an sp tensor (4 bytes per element) with 32-bit offsets: the largest one
-        # (layer1's output: (H/4) x (W/4) x 64 or 256 channels per image) must stay below 2 GiB, or this call runs on the
-        # fp32-MFMA kernels (64-bit row offsets there; B < 668 per view at 224 x 224 with ResNet-50)
-        biggest_view_elems = B * ((H + 3) // 4) * ((W + 3) // 4) * self.spec.blocks[0].convs[-1].cout
-        self._split_now = self.split and 4 * biggest_view_elems * self._guard_scale < 0x7FFFFFF0
-        infer = not (training or keep_tape or self.bf16)         # the folded fp32 inference forward: what split_eval_guard covers
-        if self.split_eval_guard not in (None, "record", "fallback"):
-            raise ValueError(f"split_eval_guard must be None, 'record' or 'fallback' (got {self.split_eval_guard!r})")
-        guard = self.split_eval_guard if infer else None
-        if guard == "fallback" and torch.cuda.is_current_stream_capturing():
-            raise RuntimeError("split_eval_guard = 'fallback' reads the range record on the host and cannot run while the stream "
-                               "is capturing: capture with 'record' and check overflowed() after the replay")
-        if guard == "fallback" and self._range_tripped:
-            self._split_now = False              # an earlier call overflowed: fp32-MFMA kernels until the weights change
-        # the stem's form for this call (see stem_rowwindow)
-        if self.bf16:        # folded windows: width % 4, whole 64-row partials (n * ho * wo / 2), the stem's weights through the batch
-            ho, wo = (H - 1) // 2 + 1, W // 2
-            self._stem_rw = (self.stem_rowwindow and training and W % 4 == 0 and (B * ho * (wo // 2)) % 64 == 0 and self.batch_weight_prep
-                             and self.spec.stem.k == 7)
-        else:
-            self._stem_rw = (self._split_now and self.stem_rowwindow and training and not need_dimg and W % 2 == 0
-                             and self.batch_weight_prep and 32 * B * H * (W // 2) * 4 < 0x7FFFFFF0)
-        x0 = self._input_layout(imgs, B, H, W, input_bgr, input_augment if (raw and training) else None)
-        self._wprep = None
+        call = plan_call(self.spec, V=V, B=B, H=H, W=W, training=training, keep_tape=keep_tape, raw=raw,
+                         augment=input_augment is not None, need_dimg=need_dimg, boundary=self._boundary(need_dimg) if keep_tape else -1,
+                         bf16=self.bf16, split=self.split, split_eval=self.split_eval, split_eval_guard=self.split_eval_guard,
+                         stem_rowwindow=self.stem_rowwindow, batch_weight_prep=self.batch_weight_prep,
+                         bf16_fold_eval=self.bf16_fold_eval, guard_scale=self._guard_scale, tripped=self._range_tripped,
+                         capturing=self.split_eval_guard == "fallback" and torch.cuda.is_current_stream_capturing())
+        x0 = self._input_layout(call, imgs, input_bgr, input_augment if (raw and training) else None)
         if training:
             self.invalidate_weight_cache()       # the weights are about to change: drop the inference copies
-        if self.batch_weight_prep and (self.bf16 or (self._split_now and training)):
-            self._wprep = self._prepare_weights(dev, reuse=self.bf16 and self.bf16_fold_eval and not training and not keep_tape)
+        wprep = None
+        if self.batch_weight_prep and (call.bf16 or (call.sp and training)):
+            wprep = self._prepare_weights(dev, Family.BF16 if call.bf16 else Family.SPLIT, call.stem_rw,
+                                          reuse=call.bf16 and self.bf16_fold_eval and not training and not keep_tape)
         # ... and one launch gives every sp activation of the step its scale (x, out and identity carry it as .sinv; the
         # tape's x_in / out keep it for the backward's weight gradients)
-        self._act_sinv = self._prepare_act_scales(dev, B, H, W) if (self._split_now and training and not self.bf16) else None
-        tape: Optional[dict] = {"units": [], "blocks": [], "V": V, "B": B, "boundary": self._boundary(need_dimg)} if keep_tape else None
-        if keep_tape and self._wprep is not None:
+        call = call._replace(wprep=wprep, act_sinv=self._prepare_act_scales(dev, B, H, W) if (call.sp and training) else None)
+        # (V, B and boundary stay as keys of their own: tests and tools read them)
+        tape: Optional[dict] = {"units": [], "blocks": [], "call": call, "V": V, "B": B, "boundary": call.boundary} if keep_tape else None
+        if keep_tape and wprep is not None:
             tape["wprep_versions"] = self._wprep_versions
         if training:
             torch._foreach_add_(self.bn_count_buffers(), V)       # num_batches_tracked += 1 per view call
-        if training or keep_tape or (self.bf16 and not self.bf16_fold_eval):
-            x = self._forward_taped(x0, V, B, H, W, training, tape)
+        if call.taped:
+            x = self._forward_taped(x0, call, tape)
         else:
-            self._range_live = guard is not None and self._split_now and self.split_eval
-            if guard is not None:
+            if call.guard is not None:
                 if self._range_record is None or self._range_record.device != dev:
                     self._range_record = torch.zeros(len(self._range_slot), dtype=torch.int32, device=dev)
                 else:
                     self._range_record.zero_()
-            x = self._forward_infer(x0, V, B, H, W)
-            if guard == "fallback" and self._range_live:
+            x = self._forward_infer(x0, call)
+            if call.guard == "fallback" and call.range_live:
                 if max(self._range_record.tolist()) >= RANGE_OVER_BITS:      # one small copy + a synchronisation (|v|: sign bit clear)
                     self._range_tripped = True
-                    self._split_now = self._range_live = False
-                    x = self._forward_infer(x0, V, B, H, W)
-            self._range_live = False
+                    call = call._replace(split=False, sp=False, range_live=False)
+                    x = self._forward_infer(x0, call)
+        self._last_call = call
         Hc, Wc = x.shape[2], x.shape[3]
         feat = torch.empty(V, B, self.fc_dim, dtype=torch.float32, device=dev)
         if x.dtype == torch.float16:                                # sp activation of the split path
@@ -704,32 +856,32 @@ class Backbone:
             tape["final_hw"] = (Hc, Wc)
         return feat, tape
 
-    def _forward_infer(self, x0: Tensor, V: int, B: int, H: int, W: int) -> Tensor:
+    def _forward_infer(self, x0: Tensor, call: Call) -> Tensor:
         """Stem and residual blocks of the folded inference forward (see _unit_infer), in the order csrc/session_plan.cpp
         states (build for the fp32 model, build_bf16 for the bf16 path): conv1 up to the last conv, the downsample branch as a
         normalised residual, the last conv with residual + ReLU."""
         s = self.spec
-        if self.bf16:         # the bf16 stem keeps the training-shaped launches: conv, then BatchNorm + ReLU + max pool in one pass
-            x = self._unit_fwd(s.stem, x0, V, B, H, W, False, True, None, None, pool=True).out
+        if call.bf16:         # the bf16 stem keeps the training-shaped launches: conv, then BatchNorm + ReLU + max pool in one pass
+            x = self._unit_fwd(call, s.stem, x0, call.H, call.W, relu=True, pool=True).out
         else:
-            x = self._unit_infer(s.stem, x0, V, B, H, W, True, None, pool=True)
+            x = self._unit_infer(call, s.stem, x0, call.H, call.W, True, None, pool=True)
         for blk in s.blocks:
             out = x
             for c in blk.convs[:-1]:
-                out = self._unit_infer(c, out, V, B, out.shape[2], out.shape[3], True, None)
+                out = self._unit_infer(call, c, out, out.shape[2], out.shape[3], True, None)
             identity = x
             if blk.downsample is not None:
-                identity = self._unit_infer(blk.downsample, x, V, B, x.shape[2], x.shape[3], False, None)
-            x = self._unit_infer(blk.convs[-1], out, V, B, out.shape[2], out.shape[3], True, identity)
+                identity = self._unit_infer(call, blk.downsample, x, x.shape[2], x.shape[3], False, None)
+            x = self._unit_infer(call, blk.convs[-1], out, out.shape[2], out.shape[3], True, identity)
         return x
 
-    def _forward_taped(self, x0: Tensor, V: int, B: int, H: int, W: int, training: bool, tape: Optional[dict]) -> Tensor:
+    def _forward_taped(self, x0: Tensor, call: Call, tape: Optional[dict]) -> Tensor:
         """Stem and residual blocks through _unit_fwd: training, eval mode with a tape, and (tape None) unfolded bf16
         inference.  Fills tape["units"] / tape["blocks"]."""
         s = self.spec
         ulist = tape["units"] if tape is not None else None
-        boundary = tape["boundary"] if tape is not None else -1
-        x = self._unit_fwd(s.stem, x0, V, B, H, W, training, True, None, ulist, pool=True).out
+        boundary = call.boundary
+        x = self._unit_fwd(call, s.stem, x0, call.H, call.W, relu=True, tape=ulist, pool=True).out
         if boundary > -1:
             self._release(ulist[0])
         pending = None        # the previous block's apply pass, when this block's first conv forms its own input
@@ -739,16 +891,16 @@ class Backbone:
             out = x
             for c in blk.convs[:-1]:
                 # (conv1 runs before the downsample branch and before anything else that reads the block input)
-                out = self._unit_fwd(c, out, V, B, out.shape[2], out.shape[3], training, True, None, ulist, pending_apply=pending).out
+                out = self._unit_fwd(call, c, out, out.shape[2], out.shape[3], relu=True, tape=ulist, pending_apply=pending).out
                 pending = None
             if blk.downsample is not None:
                 # raw downsample conv output + its (scale, shift): normalised inside the last unit's bn_apply
-                identity, ident_affine, _ = self._unit_fwd(blk.downsample, x, V, B, x.shape[2], x.shape[3], training, False,
-                                                           None, ulist, defer_apply=True)
+                identity, ident_affine, _ = self._unit_fwd(call, blk.downsample, x, x.shape[2], x.shape[3], relu=False, tape=ulist,
+                                                           defer_apply=True)
                 ds_idx = len(ulist) - 1 if ulist is not None else None
-            nxt = s.blocks[bi + 1].convs[0] if (bi + 1 < len(s.blocks) and training and not self.bf16) else None
-            x, _, pending = self._unit_fwd(blk.convs[-1], out, V, B, out.shape[2], out.shape[3], training, True, identity, ulist,
-                                           residual_affine=ident_affine, next_conv=nxt)
+            nxt = s.blocks[bi + 1].convs[0] if (bi + 1 < len(s.blocks) and call.training and not call.bf16) else None
+            x, _, pending = self._unit_fwd(call, blk.convs[-1], out, out.shape[2], out.shape[3], relu=True, residual=identity,
+                                           tape=ulist, residual_affine=ident_affine, next_conv=nxt)
             if ulist is not None:
                 tape["blocks"].append((list(range(first, first + len(blk.convs) - 1)) + [len(ulist) - 1], ds_idx))
                 if bi < boundary:
@@ -793,47 +945,46 @@ class Backbone:
         return [self.p[c.name + ".weight"], self.p[c.bn + ".weight"], self.p[c.bn + ".bias"]]
 
     def _bn_bwd(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink, defer_apply: bool = False):
-        """g = grad wrt the unit's output.  Returns (dy, dz): dy = grad wrt the conv output;
+        """g = grad wrt the unit's output.  Returns (dy, dz, pending): dy = grad wrt the conv output;
         dz = g masked by the unit's ReLU (written in place into g) when the residual branch needs it.
         defer_apply (a unit that bn_apply_dgrad_eligible accepted): dy is only allocated - the unit's backward-data launch
-        forms and writes it (dy.bn_apply holds what that launch needs)."""
+        forms and writes it from ``pending`` (a _PendingDy; else None)."""
         if not u.trained:
-            return self._bn_bwd_eval(u, g, need_dz, sink)
+            return self._bn_bwd_eval(u, g, need_dz, sink) + (None,)
         c = u.spec
         G = u.y.shape[0]
         gp, bp, acc = self._bn_params(c, sink)
-        if u.fused_s12 is not None and u.split:
-            # split path, fused: g arrived masked and the sums came with it; dy goes out in sp
-            (s12, sinv), u.fused_s12 = u.fused_s12, None
+        fs, u.fused_s12 = u.fused_s12, None
+        if u.family is Family.SPLIT:
+            # g and y are fp32, dy goes to the conv kernels in sp
             dy = ops.sp_empty(*u.y.shape, device=g.device)
-            if defer_apply:
-                dy.sinv = sinv
-                dy.bn_apply = (g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], u.rows)
-            else:
-                ops.bn_bwd_apply_split(g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, None, s12[2], sinv)
-            return dy, (g if need_dz else None)
-        if u.fused_s12 is not None:
-            # g arrived masked by this unit's ReLU and its sums (incl. dgamma / dbeta) came with it
-            s12, u.fused_s12 = u.fused_s12, None
-            dy = torch.empty_like(g) if need_dz else g
-            ops.bn_bwd_apply(g, None, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, None, None)
-            return dy, (g if need_dz else None)
-        s12 = torch.empty(3 if u.split else 2, G, c.cout, dtype=torch.float32, device=g.device)     # s1, s2 (, max |dz| per channel)
-        ra = u.relu_affine
-        act = u.out if (u.relu and ra is None) else None
-        if u.split:
-            # split path: g and y are fp32, dy goes to the conv kernels in sp; residual units carry their mask as bits.
-            # No pass here reads the (scaled) sp activation: the mask comes from the bits or from fma(y, scale, shift) > 0,
-            # both decided on the unscaled value
-            assert not (u.relu and ra is None) or u.relu_bits is not None
+            if fs is not None:
+                # fused: g arrived masked and the sums came with it
+                if defer_apply:
+                    dy.sinv = fs.sinv
+                    return dy, (g if need_dz else None), _PendingDy(g, fs.s1, fs.s2)
+                ops.bn_bwd_apply_split(g, u.y, u.mean, u.invstd, gp.detach(), fs.s1, fs.s2, G, u.rows, c.cout, dy, None, fs.mx, fs.sinv)
+                return dy, (g if need_dz else None), None
+            # residual units carry their mask as bits.  No pass here reads the (scaled) sp activation: the mask comes from
+            # the bits or from fma(y, scale, shift) > 0, both decided on the unscaled value
+            bits, ra = u.relu_bits, u.relu_affine
+            assert not (u.relu and ra is None) or bits is not None
+            s12 = torch.empty(3, G, c.cout, dtype=torch.float32, device=g.device)     # s1, s2, max |dz| per channel
             sinv = torch.empty(1, dtype=torch.float32, device=g.device)       # dy's 2^-k: left by the reduce pass's finalize launch
-            bits = u.relu_bits
             ra = None if bits is not None else ra                 # one mask source; with bits the reduce pass leaves dz in g
             ops.bn_bwd_reduce_split(g, bits, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp), sink.view(bp),
                                     acc, s12[2], ra, dz_out=g if bits is not None else None, gamma=gp.detach(), dy_sinv=sinv)
-            dy = ops.sp_empty(*u.y.shape, device=g.device)
             ops.bn_bwd_apply_split(g, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, ra, s12[2], sinv)
-            return dy, (g if need_dz else None)
+            return dy, (g if need_dz else None), None
+        # FP32 / BF16: the passes follow the storage type of g
+        if fs is not None:
+            # g arrived masked by this unit's ReLU and its sums (incl. dgamma / dbeta) came with it
+            dy = torch.empty_like(g) if need_dz else g
+            ops.bn_bwd_apply(g, None, u.y, u.mean, u.invstd, gp.detach(), fs.s1, fs.s2, G, u.rows, c.cout, dy, None, None)
+            return dy, (g if need_dz else None), None
+        s12 = torch.empty(2, G, c.cout, dtype=torch.float32, device=g.device)         # s1, s2
+        ra = u.relu_affine
+        act = u.out if (u.relu and ra is None) else None
         # need_dz: the reduce pass writes the masked gradient dz over g: the apply pass then reads (dz, y) only - no
         # second look at the ReLU mask, no second dz store - and the residual branch takes dz from g
         if need_dz and u.relu_bits is not None:
@@ -845,9 +996,9 @@ class Backbone:
         if need_dz:
             dy = torch.empty_like(g)
             ops.bn_bwd_apply(g, None, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, dy, None, None)
-            return dy, g
+            return dy, g, None
         ops.bn_bwd_apply(g, act, u.y, u.mean, u.invstd, gp.detach(), s12[0], s12[1], G, u.rows, c.cout, g, None, ra)
-        return g, None
+        return g, None, None
 
     def _bn_bwd_eval(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink):
         """_bn_bwd for a unit whose forward normalised with the running statistics (eval mode, fp32-MFMA kernels): one
@@ -887,12 +1038,13 @@ class Backbone:
         return self._wg_stream
 
     def _conv_bwd(self, u: _Unit, dy: Tensor, need_dx: bool, addend: Optional[Tensor], sink: GradSink,
-                  fuse_for: Optional[_Unit] = None):
+                  fuse_for: Optional[_Unit] = None, pending: Optional[_PendingDy] = None):
+        """The weight gradient of unit u (on the side stream) and, with need_dx, its backward-data launch.  pending: dy does
+        not exist yet - the backward-data launch forms it and writes it first, then the weight gradient reads it."""
         dx = None
-        if getattr(dy, "bn_apply", None) is not None:
-            # dy does not exist yet: the backward-data launch forms it and writes it, then the weight gradient reads it
+        if pending is not None:
             dx = torch.empty(ops.sp_shape(u.x_in), dtype=torch.float32, device=dy.device)
-            self._dgrad(u, dy, dx, addend, fuse_for, sink)
+            self._dgrad(u, dy, dx, addend, fuse_for, sink, pending)
             need_dx = False
         if not sink.wants(self.p[u.spec.name + ".weight"]):
             pass          # a frozen conv weight: no weight-gradient launch, no slabs for the block's deferred reduce
@@ -910,31 +1062,34 @@ class Backbone:
         else:
             self._wgrad(u, dy, sink)
         if need_dx:
-            dx = torch.empty(ops.sp_shape(u.x_in), dtype=torch.float32, device=dy.device) if u.split else torch.empty_like(u.x_in)
+            dx = (torch.empty(ops.sp_shape(u.x_in), dtype=torch.float32, device=dy.device) if u.family is Family.SPLIT
+                  else torch.empty_like(u.x_in))
             self._dgrad(u, dy, dx, addend, fuse_for, sink)
         return dx
 
     def _wgrad(self, u: _Unit, dy: Tensor, sink: GradSink):
         c = u.spec
         wp = self.p[c.name + ".weight"]
-        if u.split:
-            # (slabs now, their sums in ONE launch per residual block: _flush_wgrad_reduces); x_in is read by VALUE: its
-            # .sinv goes into the launch's output scale
-            ops.conv_wgrad_split(u.desc, u.x_in, dy, sink.view(wp), sink.accumulate(wp), defer=self._wg_defer)
-        elif u.stem_rw and self.bf16:
+        if u.family is Family.SPLIT:
+            if u.stem_rw:
+                dw8 = torch.empty(c.cout, 7, 8, 4, dtype=torch.float32, device=dy.device)
+                ops.stem_wgrad_split(u.desc, u.x_in, dy, dw8, False)
+                self._stem_grad(wp, sink, dw8[:, :, 1:, :3])
+            else:
+                # (slabs now, their sums in ONE launch per residual block: _flush_wgrad_reduces); x_in is read by VALUE: its
+                # .sinv goes into the launch's output scale
+                ops.conv_wgrad_split(u.desc, u.x_in, dy, sink.view(wp), sink.accumulate(wp), defer=self._wg_defer)
+        elif u.stem_rw:                      # (BF16: the folded windows)
             dw16 = torch.empty(2 * c.cout, 7, 16, 4, dtype=torch.float32, device=dy.device)
             ops.stem_wgrad_bf16(u.desc, u.x_in, dy, dw16, False)
             self._stem_grad(wp, sink, dw16[:c.cout, :, 1:8, :3], dw16[c.cout:, :, 3:10, :3])    # (second: the odd output columns' taps)
-        elif u.stem_rw:
-            dw8 = torch.empty(c.cout, 7, 8, 4, dtype=torch.float32, device=dy.device)
-            ops.stem_wgrad_split(u.desc, u.x_in, dy, dw8, False)
-            self._stem_grad(wp, sink, dw8[:, :, 1:, :3])
-        elif c.cin == 3:
+        elif c.cin == 3:                     # (FP32 / BF16: the stem on taps padded to 4 / 8 channels)
             dw4 = torch.empty(c.cout, c.k, c.k, u.desc.cin, dtype=torch.float32, device=dy.device)
             ops.conv_wgrad(u.desc, u.x_in, dy, dw4, False)
             self._stem_grad(wp, sink, dw4[..., :3])
         else:
-            ops.conv_wgrad(u.desc, u.x_in, dy, sink.view(wp), sink.accumulate(wp), defer=self._wg_defer if self.bf16 else None)
+            ops.conv_wgrad(u.desc, u.x_in, dy, sink.view(wp), sink.accumulate(wp),
+                           defer=self._wg_defer if u.family is Family.BF16 else None)
 
     @staticmethod
     def _stem_grad(wp: torch.nn.Parameter, sink: GradSink, dw: Tensor, dw_odd: Optional[Tensor] = None):
@@ -959,42 +1114,43 @@ class Backbone:
             ops.wgrad_reduce_batch(self._wg_defer)
 
     def _dgrad(self, u: _Unit, dy: Tensor, dx: Tensor, addend: Optional[Tensor], fuse_for: Optional[_Unit] = None,
-               sink: Optional[GradSink] = None):
+               sink: Optional[GradSink] = None, pending: Optional[_PendingDy] = None):
         """dx = backward-data of unit u (+ addend).  fuse_for = the unit whose OUTPUT gradient dx is, when dx
         is final with this launch: its ReLU mask is applied and its BatchNorm-backward sums (s1, s2, dgamma,
         dbeta) are produced by the same launch (mvg_conv_dgrad_split_bnreduce / mvg_conv_dgrad_bf16_bnreduce; stride-2 launches
-        too: every parity class brings its partials) instead of a pass over (g, act, y)."""
-        U = fuse_for
-        if (self.bf16 and U is not None and self.fuse_bn_split and u.spec.cin != 3 and u.desc.cin % 64 == 0 and u.desc.cout % 64 == 0
-                and (not U.relu or U.relu_bits is not None or U.relu_affine is not None)):     # (relu_bits off: mask from the activation)
-            c = U.spec
-            gp, bp, acc = self._bn_params(c, sink)
-            s12 = torch.empty(2, dx.shape[0], c.cout, dtype=torch.float32, device=dx.device)
-            ops.conv_dgrad_bf16_bnreduce(u.desc, dy, u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd,
-                                         None if U.relu_bits is not None else U.relu_affine, s12[0], s12[1], sink.view(gp),
-                                         sink.view(bp), acc)
-            U.fused_s12 = s12
-            return
-        if u.split:
-            if U is not None and U.split and self.fuse_bn_split:
+        too: every parity class brings its partials) instead of a pass over (g, act, y).  pending: the launch forms dy too."""
+        U = fuse_for if self.fuse_bn_split else None
+        if u.family is Family.BF16:
+            if (U is not None and u.spec.cin != 3 and u.desc.cin % 64 == 0 and u.desc.cout % 64 == 0
+                    and (not U.relu or U.relu_bits is not None or U.relu_affine is not None)):     # (relu_bits off: mask from the activation)
+                c = U.spec
+                gp, bp, acc = self._bn_params(c, sink)
+                s12 = torch.empty(2, dx.shape[0], c.cout, dtype=torch.float32, device=dx.device)
+                ops.conv_dgrad_bf16_bnreduce(u.desc, dy, u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd,
+                                             None if U.relu_bits is not None else U.relu_affine, s12[0], s12[1], sink.view(gp),
+                                             sink.view(bp), acc)
+                U.fused_s12 = _FusedSums(s12[0], s12[1])
+            else:
+                ops.conv_dgrad(u.desc, dy, u.w, dx, None, addend)
+        elif u.family is Family.SPLIT:
+            if U is not None and U.family is Family.SPLIT:
                 c = U.spec
                 gp, bp, acc = self._bn_params(c, sink)
                 # (the fused reduce epilogue masks with U's bits or fma(U.y, scale, shift) > 0: no sp activation is read)
                 s12 = torch.empty(3, dx.shape[0], c.cout, dtype=torch.float32, device=dx.device)     # s1, s2, max |dz| per channel
                 sinv = torch.empty(1, dtype=torch.float32, device=dx.device)      # 2^-k of the dy that U's apply pass will write
                 ra = None if U.relu_bits is not None else U.relu_affine
-                pend = getattr(dy, "bn_apply", None)
-                if pend is not None:
-                    dz, y, mean, invstd, gamma, us1, us2, rows = pend
-                    dy.bn_apply = None
-                    ops.conv_dgrad_split_bnapply_bnreduce(u.desc, dy, dy.sinv, dz, y, mean, invstd, gamma, us1, us2, rows, u.w, dx,
-                                                          addend, U.y, U.relu_bits, U.mean, U.invstd, ra, s12[0], s12[1],
+                if pending is not None:
+                    p, ugamma = pending, self.p[u.spec.bn + ".weight"].detach()
+                    ops.conv_dgrad_split_bnapply_bnreduce(u.desc, dy, dy.sinv, p.dz, u.y, u.mean, u.invstd, ugamma, p.s1, p.s2, u.rows,
+                                                          u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd, ra, s12[0], s12[1],
                                                           sink.view(gp), sink.view(bp), acc, s12[2], gp.detach(), sinv)
                 else:
                     ops.conv_dgrad_split_bnreduce(u.desc, dy, u.w, dx, addend, U.y, U.relu_bits, U.mean, U.invstd, ra, s12[0], s12[1],
                                                   sink.view(gp), sink.view(bp), acc, s12[2], gp.detach(), sinv)
-                U.fused_s12 = (s12, sinv)
+                U.fused_s12 = _FusedSums(s12[0], s12[1], s12[2], sinv)
             else:
+                assert pending is None       # (bn_apply_dgrad_eligible: the launch that forms dy carries a reduce)
                 ops.conv_dgrad_split(u.desc, dy, u.w, dx, addend)
         else:
             ops.conv_dgrad(u.desc, dy, u.w, dx, None, addend)
@@ -1006,7 +1162,7 @@ class Backbone:
         sc = stem.spec
         P = self.p
         gp, bp, acc = self._bn_params(sc, sink)
-        stem_sp = stem.stem_rw and not self.bf16
+        stem_sp = stem.family is Family.SPLIT       # (the row-window stem of a split call)
         s12 = torch.empty(3 if stem_sp else 2, V, sc.cout, dtype=torch.float32, device=g.device)
         if not stem.trained:
             # eval mode: max pool + ReLU + BatchNorm on the running statistics, one pass (no batch sums to wait for)
@@ -1033,7 +1189,8 @@ class Backbone:
     def backward(self, tape: dict, dfeat: Tensor, sink: GradSink, need_dimg: bool = False):
         """dfeat [V,B,fc_dim] -> parameter gradients into ``sink`` (published layer4 ... stem, the
         order they become final); returns d(img) as V NCHW tensors when need_dimg."""
-        V, B = tape["V"], tape["B"]
+        call: Call = tape["call"]              # what the forward that wrote this tape ran on
+        V, B = call.V, call.B
         units: List[_Unit] = tape["units"]
         if self.bf16 and not all(u.trained for u in units):
             raise NotImplementedError("backward through eval-mode BatchNorm (running statistics) is not implemented on the "
@@ -1041,7 +1198,7 @@ class Backbone:
         Hc, Wc = tape["final_hw"]
         if need_dimg and self.bf16:
             raise NotImplementedError("d(loss)/d(img) is not produced by the bf16 path")
-        if tape.get("wprep_versions") is not None and tape["wprep_versions"] != getattr(self, "_wprep_versions", None):
+        if tape.get("wprep_versions") is not None and tape["wprep_versions"] != self._wprep_versions:
             raise RuntimeError("backward of a tape whose bf16 / sp weight copies were overwritten by a later forward with "
                                "DIFFERENT weights (forward, optimizer step, forward, then backward of the first call): "
                                "backward-data would run with the new weights.  Run backward before the weights change "
@@ -1051,7 +1208,7 @@ class Backbone:
         self._wg_defer = []
         blocks = tape["blocks"]
         # fine-tuning (see _boundary): back-propagation ends with the boundary block, whose input gradient nobody reads
-        boundary = tape.get("boundary", -1)
+        boundary = call.boundary
         assert not (need_dimg and boundary > -1), "the forward was not told that d(loss)/d(img) is wanted"
         for bi in range(len(blocks) - 1, max(boundary, 0) - 1, -1):
             idx, ds_idx = blocks[bi]
@@ -1063,16 +1220,16 @@ class Backbone:
             done: List[torch.nn.Parameter] = []
             below = units[idx[-2]]
             merge = self.fuse_bn_apply_dgrad and bn_apply_dgrad_eligible(
-                last.spec, split=last.split and not self.bf16, trained=last.trained, fused_in=last.fused_s12 is not None,
-                carries_reduce=below.split and self.fuse_bn_split, need_dimg=need_dimg)
-            dy, dz = self._bn_bwd(last, g, True, sink, defer_apply=merge)
-            d = self._conv_bwd(last, dy, True, None, sink, fuse_for=below)
+                last.spec, split=last.family is Family.SPLIT, trained=last.trained, fused_in=last.fused_s12 is not None,
+                carries_reduce=below.family is Family.SPLIT and self.fuse_bn_split, need_dimg=need_dimg)
+            dy, dz, pending = self._bn_bwd(last, g, True, sink, defer_apply=merge)
+            d = self._conv_bwd(last, dy, True, None, sink, fuse_for=below, pending=pending)
             done += self._unit_params(last.spec)
             last.y = last.out = None
             del dy
             for k in range(len(idx) - 2, -1, -1):
                 u = units[idx[k]]
-                dy, _ = self._bn_bwd(u, d, False, sink)
+                dy = self._bn_bwd(u, d, False, sink)[0]
                 if k == 0 and not need_in:
                     d = self._conv_bwd(u, dy, False, None, sink)              # the weight gradient only
                 elif k == 0:
@@ -1085,7 +1242,7 @@ class Backbone:
                 u.y = u.out = None
             if ds_idx is not None:
                 ud = units[ds_idx]
-                dyd, _ = self._bn_bwd(ud, dz, False, sink)
+                dyd = self._bn_bwd(ud, dz, False, sink)[0]
                 self._conv_bwd(ud, dyd, False, None, sink)                # wgrad only
                 if need_in:
                     self._dgrad(ud, dyd, d, d, prev_last, sink)           # d += dgrad (aliasing addend): now final
