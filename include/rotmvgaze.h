@@ -637,6 +637,21 @@ int mvg_bn_relu_maxpool_bwd_apply_bf16(const uint16_t *g_pooled, const uint8_t *
                                        const float *scale, const float *shift, const float *s1,
                                        const float *s2, int groups, int n_per_group, int h, int w, int c,
                                        int ho, int wo, uint16_t *dy, void *stream);
+/* mvg_bn_eval_bwd / mvg_bn_relu_maxpool_eval_bwd with bf16 g, act, y, dy, dz_out (g_pooled, y, dy): a training step that
+ * keeps BatchNorm on its running statistics (frozen BatchNorm) on the bf16 path.  Same contracts: one mask source at most,
+ * dy and dz_out may alias g but not each other, NULL dgamma and dbeta skip the finalize launch; the same workspace.  The
+ * arithmetic is the fp32 entry points' on the widened values, every stored value rounded to bf16 once.  relu_bits: one
+ * byte per 8 elements (mvg_bn_apply_bits_bf16's layout).  Sizes: mvg_bn_bwd_reduce_bf16's (c/8 divides 256 or exceeds it);
+ * the stem tail moves 4 channels per lane in both storage types (c/4 divides 256). */
+int mvg_bn_eval_bwd_bf16(const uint16_t *g, const uint16_t *act, const uint8_t *relu_bits, const uint16_t *y,
+                         const float *relu_scale, const float *relu_shift, const float *gamma, const float *running_mean,
+                         const float *running_var, float eps, int groups, int64_t rows_per_group, int c, uint16_t *dy,
+                         uint16_t *dz_out, float *dgamma, float *dbeta, int accumulate, float *workspace, void *stream);
+int mvg_bn_relu_maxpool_eval_bwd_bf16(const uint16_t *g_pooled, const uint8_t *argmax, const uint16_t *y, const float *scale,
+                                      const float *shift, const float *gamma, const float *running_mean,
+                                      const float *running_var, float eps, int groups, int n_per_group, int h, int w,
+                                      int c, int ho, int wo, uint16_t *dy, float *dgamma, float *dbeta, int accumulate,
+                                      float *workspace, void *stream);
 /* bf16 feature map -> fp32 pooled features and back (the fusion block stays fp32) */
 int mvg_avgpool_fwd_bf16(const uint16_t *x, float *y, int n, int hw, int c, void *stream);
 int mvg_avgpool_bwd_bf16(const float *dy, uint16_t *dx, int n, int hw, int c, void *stream);

@@ -228,6 +228,10 @@ SIGNATURES = {
     "mvg_bn_relu_maxpool_bwd_reduce_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I,
                                                  _P, _P]),
     "mvg_bn_relu_maxpool_bwd_apply_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
+    # frozen BatchNorm on the bf16 path: the one-pass backward on the running statistics in bf16 storage
+    "mvg_bn_eval_bwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I64, _I, _P, _P, _P, _P, _I, _P, _P]),
+    "mvg_bn_relu_maxpool_eval_bwd_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I,
+                                               _P, _P]),
     "mvg_avgpool_fwd_bf16": (_I, [_P, _P, _I, _I, _I, _P]),
     "mvg_avgpool_bwd_bf16": (_I, [_P, _P, _I, _I, _I, _P]),
     "mvg_nchw_to_nhwc8_bf16": (_I, [_P, _P, _I, _I, _I, _I, _P]),

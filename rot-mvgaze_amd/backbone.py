@@ -154,17 +154,23 @@ class Call(NamedTuple):
     boundary: int               # Backbone._boundary (-1 without a tape)
     wprep: Optional[Dict[str, tuple]] = None        # conv name -> this step's (w, w_t) copies, when ONE launch made them
     act_sinv: Optional[Dict[str, Tensor]] = None    # conv name -> its output's 1-element 2^-k slot (sp training steps)
+    train_step: Optional[bool] = None   # a training step (None: = training); differs from ``training`` - BatchNorm on batch
+                                        # statistics - for a frozen-BatchNorm step: training False, train_step True
 
 
 def plan_call(spec: BackboneSpec, *, V: int, B: int, H: int, W: int, training: bool, keep_tape: bool, raw: bool = False,
               augment: bool = False, need_dimg: bool = False, boundary: int = -1, bf16: bool = False, split: bool = True,
               split_eval: bool = True, split_eval_guard: Optional[str] = None, stem_rowwindow: bool = True,
               batch_weight_prep: bool = True, bf16_fold_eval: bool = True, guard_scale: int = 1, tripped: bool = False,
-              capturing: bool = False) -> Call:
+              capturing: bool = False, train_step: Optional[bool] = None) -> Call:
     """The size and mode decisions of one forward call, from shapes and flags alone (no tensor, no device).  raw: uint8
     patches; augment: an input augment is set; tripped: an earlier "fallback" call overflowed (Backbone._range_tripped);
-    capturing: the stream is being captured; the other flags are the Backbone attributes of the same names."""
-    if bf16 and raw and (training or keep_tape) and not (training and augment):
+    capturing: the stream is being captured; the other flags are the Backbone attributes of the same names.
+    training: BatchNorm on batch statistics; train_step (None: = training): the call is a training step - the augment is
+    applied and raw patches with one are accepted on the bf16 path.  A frozen-BatchNorm step is training False, train_step
+    True: it has no statistics, so no row-window stem and no sp storage, exactly like a taped eval forward."""
+    step = training if train_step is None else bool(train_step)
+    if bf16 and raw and (step or keep_tape) and not (step and augment):
         raise NotImplementedError("raw uint8 input with the bf16 path is served for inference only (model.eval() under "
                                   "torch.no_grad()) and for training steps with model.input_augment (augment.TrainAugment; the "
                                   "identity augment for un-augmented steps): else normalise to fp32 NCHW first")
@@ -194,7 +200,7 @@ def plan_call(spec: BackboneSpec, *, V: int, B: int, H: int, W: int, training: b
     # sp storage: training steps of the fp32 model; folded inference with split_eval (an eval-mode tape: fp32-MFMA kernels)
     sp = split and not bf16 and (training or (infer and split_eval))
     return Call(V, B, H, W, training, keep_tape, bf16, split, sp, stem_rw, taped, guard,
-                range_live=guard is not None and sp, need_dimg=need_dimg, boundary=boundary)
+                range_live=guard is not None and sp, need_dimg=need_dimg, boundary=boundary, train_step=step)
 
 
 def unit_family(call: Call, c: ConvSpec) -> Family:
@@ -792,14 +798,19 @@ class Backbone:
         return x0
 
     def forward(self, imgs: List[Tensor], training: bool, keep_tape: bool, input_bgr: bool = False,
-                input_size: Optional[int] = None, need_dimg: bool = False, input_augment=None):
+                input_size: Optional[int] = None, need_dimg: bool = False, input_augment=None,
+                train_step: Optional[bool] = None):
         """imgs: V tensors [B,3,H,W] fp32 NCHW (the reference's input format, rot_mv.py:188-189), or
         V raw uint8 [B,H,W,3] face patches, put through test_transform of main.py:50-55 on the GPU
         (ToTensor, Resize((input_size, input_size), antialias=True) when the patch has another size,
         Normalize) - in a training step with input_augment (augment.TrainAugment) through the random
         part of train_transform (main.py:41-49) as well.  The bf16 path takes raw patches for inference and, with
         input_augment, for training steps (the augment launch stores the bf16 stem operand); a training step or a taped
-        forward on raw patches without it raises NotImplementedError.  Returns (img_feat [V,B,fc_dim], tape or None)."""
+        forward on raw patches without it raises NotImplementedError.  training: BatchNorm on batch statistics; train_step
+        (None: = training): this is a training step - the augment is applied and the inference weight copies are dropped.
+        A frozen-BatchNorm step (MultiViewGaze.freeze_batchnorm) is training False, train_step True.
+        Returns (img_feat [V,B,fc_dim], tape or None)."""
+        step = training if train_step is None else bool(train_step)
         V = len(imgs)
         raw = imgs[0].dtype == torch.uint8
         if raw:
@@ -814,9 +825,10 @@ class Backbone:
                          bf16=self.bf16, split=self.split, split_eval=self.split_eval, split_eval_guard=self.split_eval_guard,
                          stem_rowwindow=self.stem_rowwindow, batch_weight_prep=self.batch_weight_prep,
                          bf16_fold_eval=self.bf16_fold_eval, guard_scale=self._guard_scale, tripped=self._range_tripped,
-                         capturing=self.split_eval_guard == "fallback" and torch.cuda.is_current_stream_capturing())
-        x0 = self._input_layout(call, imgs, input_bgr, input_augment if (raw and training) else None)
-        if training:
+                         capturing=self.split_eval_guard == "fallback" and torch.cuda.is_current_stream_capturing(),
+                         train_step=step)
+        x0 = self._input_layout(call, imgs, input_bgr, input_augment if (raw and step) else None)
+        if step:
             self.invalidate_weight_cache()       # the weights are about to change: drop the inference copies
         wprep = None
         if self.batch_weight_prep and (call.bf16 or (call.sp and training)):
@@ -1001,9 +1013,10 @@ class Backbone:
         return g, None, None
 
     def _bn_bwd_eval(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink):
-        """_bn_bwd for a unit whose forward normalised with the running statistics (eval mode, fp32-MFMA kernels): one
-        pass (ops.bn_eval_bwd) - dy needs no batch sums.  The tape's mean / invstd were never filled and are not read:
-        the kernel takes the running statistics, and the ReLU mask from where the forward left it."""
+        """_bn_bwd for a unit whose forward normalised with the running statistics (eval mode, or a frozen-BatchNorm training
+        step; fp32-MFMA or bf16 kernels - the pass follows the storage type of g): one pass (ops.bn_eval_bwd) - dy needs no
+        batch sums.  The tape's mean / invstd were never filled and are not read: the kernel takes the running statistics, and
+        the ReLU mask from where the forward left it."""
         c = u.spec
         G = u.y.shape[0]
         gp, bp, acc = self._bn_params(c, sink)
@@ -1121,7 +1134,8 @@ class Backbone:
         too: every parity class brings its partials) instead of a pass over (g, act, y).  pending: the launch forms dy too."""
         U = fuse_for if self.fuse_bn_split else None
         if u.family is Family.BF16:
-            if (U is not None and u.spec.cin != 3 and u.desc.cin % 64 == 0 and u.desc.cout % 64 == 0
+            # (a unit on running statistics has no mean / invstd and its one-pass backward needs no batch sums: plain launch)
+            if (U is not None and U.trained and u.spec.cin != 3 and u.desc.cin % 64 == 0 and u.desc.cout % 64 == 0
                     and (not U.relu or U.relu_bits is not None or U.relu_affine is not None)):     # (relu_bits off: mask from the activation)
                 c = U.spec
                 gp, bp, acc = self._bn_params(c, sink)
@@ -1192,9 +1206,10 @@ class Backbone:
         call: Call = tape["call"]              # what the forward that wrote this tape ran on
         V, B = call.V, call.B
         units: List[_Unit] = tape["units"]
-        if self.bf16 and not all(u.trained for u in units):
+        if self.bf16 and not call.train_step and not all(u.trained for u in units):
             raise NotImplementedError("backward through eval-mode BatchNorm (running statistics) is not implemented on the "
-                                      "bf16 path: call model.train() for gradient steps, or use the fp32 model")
+                                      "bf16 path outside a training step: call model.train() - with model.freeze_batchnorm "
+                                      "to keep the running statistics - for gradient steps, or use the fp32 model")
         Hc, Wc = tape["final_hw"]
         if need_dimg and self.bf16:
             raise NotImplementedError("d(loss)/d(img) is not produced by the bf16 path")

@@ -1120,48 +1120,68 @@ __device__ __forceinline__ void bn_eval_factors(const float *gamma, const float 
   k = map4([](float ga, float sd) { return ga / sd; }, ga, sd);     // = bn_eval_affine_kernel's scale
 }
 
-// grid = (chunks, column blocks, groups); thread = one float4 column group x one row lane (bn_bwd_reduce_kernel's shape)
-__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float *g, const float *__restrict__ act, const float *__restrict__ y,
+// grid = (chunks, column blocks, groups); thread = one 16-byte column group (W float4: 4 channels in fp32, 8 in bf16) x one
+// row lane (bn_bwd_reduce_kernel's shape).  bf16 storage: g, act, y are widened to fp32, the arithmetic is the fp32
+// kernel's, and dz / dy are rounded once on their way out; a relu_bits byte covers the access's 8 elements.
+template <typename T>
+__global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const T *g, const T *__restrict__ act, const T *__restrict__ y,
                                                           const unsigned char *__restrict__ relu_bits,
                                                           const float *__restrict__ mscale, const float *__restrict__ mshift,
                                                           const float *__restrict__ gamma, const float *__restrict__ rmean,
                                                           const float *__restrict__ rvar, float eps, long long rows,
-                                                          long long rows_per_chunk, int c, int cwn, int cw, float *dy, float *dz_out,
+                                                          long long rows_per_chunk, int c, int cwn, int cw, T *dy, T *dz_out,
                                                           float *__restrict__ partial, int chunks) {
-  __shared__ float4 sh[2][256][1];
+  typedef Elem<T> E;
+  constexpr int W = E::W;
+  __shared__ float4 sh[2][256][W];
   const int grp = blockIdx.z;
   const int rl = threadIdx.x / cw, cl = threadIdx.x % cw;
   const int nrl = 256 / cw;
   const int cq = blockIdx.y * cw + cl;
   const bool cok = cq < cwn;
-  float4 s1 = zero4(), s2 = s1;
+  float4 s1[W], s2[W];
+#pragma unroll
+  for (int w = 0; w < W; ++w) s1[w] = s2[w] = zero4();
   if (cok) {
-    float4 mu, is, k, ma = s1, mb = s1;
-    bn_eval_factors(gamma, rmean, rvar, eps, cq, mu, is, k);
-    if (mscale) {
-      ma = reinterpret_cast<const float4 *>(mscale + (long long)grp * c)[cq];
-      mb = reinterpret_cast<const float4 *>(mshift + (long long)grp * c)[cq];
+    float4 mu[W], is[W], k[W], ma[W], mb[W];
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      bn_eval_factors(gamma, rmean, rvar, eps, cq * W + w, mu[w], is[w], k[w]);
+      ma[w] = mb[w] = zero4();
+      if (mscale) {
+        ma[w] = reinterpret_cast<const float4 *>(mscale + (long long)grp * c)[cq * W + w];
+        mb[w] = reinterpret_cast<const float4 *>(mshift + (long long)grp * c)[cq * W + w];
+      }
     }
     const long long r0 = (long long)blockIdx.x * rows_per_chunk;
     long long r1 = r0 + rows_per_chunk;
     if (r1 > rows) r1 = rows;
     const long long gbase = (long long)grp * rows * cwn;
-    auto row = [&](long long r, float4 &a1, float4 &a2) {
+    auto row = [&](long long r, float4 (&a1)[W], float4 (&a2)[W]) {
       const long long off = gbase + r * cwn + cq;
-      float4 d = reinterpret_cast<const float4 *>(g)[off];
-      const float4 v = reinterpret_cast<const float4 *>(y)[off];
-      if (relu_bits) d = mask_bits4(d, relu_bits[off]);
-      else if (act) d = mask_act4(d, reinterpret_cast<const float4 *>(act)[off]);
-      else if (mscale) d = mask_affine4(d, v, ma, mb);
-      acc4(a1, d);
-      acc4_xhat(a2, d, v, mu, is);
-      if (dz_out) reinterpret_cast<float4 *>(dz_out)[off] = d;
-      reinterpret_cast<float4 *>(dy)[off] = mul4(k, d);
-    };
-    constexpr int U = 4;          // rows in flight per thread (bn_bwd_reduce_kernel's count for fp32)
-    float4 t1[U - 1], t2[U - 1];
+      float4 d[W], v[W], a[W], o[W];
+      E::ldw(g, off, d);
+      E::ldw(y, off, v);
+      if (act) E::ldw(act, off, a);
+      const unsigned mb8 = relu_bits ? (unsigned)relu_bits[off] : 0u;
 #pragma unroll
-    for (int u = 0; u < U - 1; ++u) t1[u] = t2[u] = zero4();
+      for (int w = 0; w < W; ++w) {
+        if (relu_bits) d[w] = mask_bits4(d[w], mb8 >> (4 * w));
+        else if (act) d[w] = mask_act4(d[w], a[w]);
+        else if (mscale) d[w] = mask_affine4(d[w], v[w], ma[w], mb[w]);
+        acc4(a1[w], d[w]);
+        acc4_xhat(a2[w], d[w], v[w], mu[w], is[w]);
+        o[w] = mul4(k[w], d[w]);
+      }
+      if (dz_out) E::stw(dz_out, off, d);
+      E::stw(dy, off, o);
+    };
+    constexpr int U = W == 1 ? 4 : 2;          // rows in flight per thread (bn_bwd_reduce_kernel's counts)
+    float4 t1[U - 1][W], t2[U - 1][W];
+#pragma unroll
+    for (int u = 0; u < U - 1; ++u)
+#pragma unroll
+      for (int w = 0; w < W; ++w) t1[u][w] = t2[u][w] = zero4();
     long long r = r0 + rl;
     for (; r + (U - 1) * (long long)nrl < r1; r += U * (long long)nrl) {
       row(r, s1, s2);
@@ -1169,23 +1189,33 @@ __global__ __launch_bounds__(256) void bn_eval_bwd_kernel(const float *g, const 
       for (int u = 1; u < U; ++u) row(r + u * (long long)nrl, t1[u - 1], t2[u - 1]);
     }
     for (; r < r1; r += nrl) row(r, s1, s2);
-    acc4(s1, add4(t1[0], add4(t1[1], t1[2])));
-    acc4(s2, add4(t2[0], add4(t2[1], t2[2])));
+#pragma unroll
+    for (int w = 0; w < W; ++w) {
+      if constexpr (U == 4) {
+        acc4(s1[w], add4(t1[0][w], add4(t1[1][w], t1[2][w])));
+        acc4(s2[w], add4(t2[0][w], add4(t2[1][w], t2[2][w])));
+      } else {
+        acc4(s1[w], t1[0][w]);
+        acc4(s2[w], t2[0][w]);
+      }
+    }
   }
-  bn_reduce_tail(sh, &s1, &s2, nullptr, cok, nrl, cw, rl, cl, cq, partial, grp, chunks, c, c / 4);
+  bn_reduce_tail(sh, s1, s2, nullptr, cok, nrl, cw, rl, cl, cq, partial, grp, chunks, c, c / 4);
 }
 
 // The stem tail in eval mode: max-pool backward through argmax, the ReLU mask from y, then dy = gamma invstd_r dz - the
 // quad gather of bn_pool_bwd_apply_kernel (a lane owns a 2 x 2 pixel quad x 4 channels and deals out the four windows that
 // quad can have won), so the 112 x 112 gradient map is written once, as dy.  grid = (chunks, groups), a grid-stride loop
 // over the group's (image, quad row, quad column, channel group) items; c/4 divides 256, so a lane keeps its channels and
-// the workgroup's partial sums go to partial[group][blockIdx.x] ([groups][chunks][2][c], as above).
-__global__ __launch_bounds__(256) void bn_pool_eval_bwd_kernel(const float *__restrict__ gp, const uchar4 *__restrict__ am,
-                                                               const float *__restrict__ y, const float *__restrict__ mscale,
+// the workgroup's partial sums go to partial[group][blockIdx.x] ([groups][chunks][2][c], as above).  4 channels per lane
+// whatever the storage (bf16: 8-byte accesses, as the train-mode pooled reduce has them).
+template <typename T>
+__global__ __launch_bounds__(256) void bn_pool_eval_bwd_kernel(const T *__restrict__ gp, const uchar4 *__restrict__ am,
+                                                               const T *__restrict__ y, const float *__restrict__ mscale,
                                                                const float *__restrict__ mshift, const float *__restrict__ gamma,
                                                                const float *__restrict__ rmean, const float *__restrict__ rvar,
                                                                float eps, int n_per_group, int h, int w, int ho, int wo, int c4n,
-                                                               float *__restrict__ dy, float *__restrict__ partial) {
+                                                               T *__restrict__ dy, float *__restrict__ partial) {
   __shared__ float4 sh[2][256];
   const int hq = (h + 1) >> 1, wq = (w + 1) >> 1;
   const int grp = blockIdx.y;
@@ -1207,7 +1237,7 @@ __global__ __launch_bounds__(256) void bn_pool_eval_bwd_kernel(const float *__re
       d = mask_affine4(d, v, sa, sb);
       acc4(s1, d);
       acc4_xhat(s2, d, v, mu, is);
-      reinterpret_cast<float4 *>(dy)[px] = mul4(k, d);
+      Elem<T>::st4(dy, px, mul4(k, d));
     }, s1, s2);
   }
   // (not bn_reduce_tail: this kernel has no 256 / c4n, and a strided fold over the lanes j = lane + c4n, + 2 c4n, ...)
@@ -1808,25 +1838,30 @@ size_t mvg_bn_eval_bwd_workspace_floats(int groups, int64_t rows_per_group, int 
   return (size_t)groups * (a > b ? a : b) * 2 * c;
 }
 
-int mvg_bn_eval_bwd(const float *g, const float *act, const uint8_t *relu_bits, const float *y, const float *relu_scale,
-                    const float *relu_shift, const float *gamma, const float *running_mean, const float *running_var, float eps,
-                    int groups, int64_t rows_per_group, int c, float *dy, float *dz_out, float *dgamma, float *dbeta,
-                    int accumulate, float *workspace, void *stream) {
+}  // extern "C"
+
+template <typename T>
+static int bn_eval_bwd_impl(const T *g, const T *act, const uint8_t *relu_bits, const T *y, const float *relu_scale,
+                            const float *relu_shift, const float *gamma, const float *running_mean, const float *running_var, float eps,
+                            int groups, int64_t rows_per_group, int c, T *dy, T *dz_out, float *dgamma, float *dbeta,
+                            int accumulate, float *workspace, void *stream) {
+  constexpr int W = Elem<T>::W;
   if (int e = require_one_mask("bn_eval_bwd", "ONE way: act, relu_bits or (relu_scale, relu_shift)", act, relu_bits, relu_scale, relu_shift))
     return e;
   MVG_REQUIRE(g && y && dy && gamma && running_mean && running_var && workspace,
               "bn_eval_bwd: g, y, dy, gamma, running_mean, running_var and workspace are required");
   MVG_REQUIRE(dz_out == nullptr || dz_out != dy, "bn_eval_bwd: dz_out and dy must be different buffers");
   MVG_REQUIRE(groups > 0 && groups < 65536 && rows_per_group > 0 && c > 0 && c % 4 == 0, "bn_eval_bwd: bad sizes");
+  if (int e = require_channels("bn_eval_bwd", c, W)) return e;
   ReduceGeom q;
-  if (int e = reduce_geometry("bn_eval_bwd", groups, rows_per_group, c, 1, q)) return e;
-  const int c4n = q.cwn, cw = q.cw, chunks = q.chunks;
+  if (int e = reduce_geometry("bn_eval_bwd", groups, rows_per_group, c, W, q)) return e;
+  const int cwn = q.cwn, cw = q.cw, chunks = q.chunks;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0,
-               4.0 * groups * (double)rows_per_group * c * (3 + (act ? 1 : 0) + (dz_out ? 1 : 0)) +
-                   (relu_bits ? groups * (double)rows_per_group * c4n : 0.0));
-  hipLaunchKernelGGL(bn_eval_bwd_kernel, dim3(chunks, ceil_div(c4n, cw), groups), dim3(256), 0, st, g, act, y, relu_bits, relu_scale,
-                     relu_shift, gamma, running_mean, running_var, eps, (long long)rows_per_group, q.rows_per_chunk, c, c4n, cw, dy, dz_out, workspace,
+               Elem<T>::kBytes * groups * (double)rows_per_group * c * (3 + (act ? 1 : 0) + (dz_out ? 1 : 0)) +
+                   (relu_bits ? groups * (double)rows_per_group * cwn : 0.0));
+  hipLaunchKernelGGL(bn_eval_bwd_kernel<T>, dim3(chunks, ceil_div(cwn, cw), groups), dim3(256), 0, st, g, act, y, relu_bits, relu_scale,
+                     relu_shift, gamma, running_mean, running_var, eps, (long long)rows_per_group, q.rows_per_chunk, c, cwn, cw, dy, dz_out, workspace,
                      chunks);
   if (check_launch("bn_eval_bwd")) return 1;
   if (!dgamma && !dbeta) return 0;
@@ -1835,10 +1870,11 @@ int mvg_bn_eval_bwd(const float *g, const float *act, const uint8_t *relu_bits, 
   return check_launch("bn_eval_bwd_finalize");
 }
 
-int mvg_bn_relu_maxpool_eval_bwd(const float *g_pooled, const uint8_t *argmax, const float *y, const float *scale, const float *shift,
-                                 const float *gamma, const float *running_mean, const float *running_var, float eps, int groups,
-                                 int n_per_group, int h, int w, int c, int ho, int wo, float *dy, float *dgamma, float *dbeta,
-                                 int accumulate, float *workspace, void *stream) {
+template <typename T>
+static int bn_relu_maxpool_eval_bwd_impl(const T *g_pooled, const uint8_t *argmax, const T *y, const float *scale, const float *shift,
+                                         const float *gamma, const float *running_mean, const float *running_var, float eps, int groups,
+                                         int n_per_group, int h, int w, int c, int ho, int wo, T *dy, float *dgamma, float *dbeta,
+                                         int accumulate, float *workspace, void *stream) {
   MVG_REQUIRE(g_pooled && argmax && y && scale && shift && gamma && running_mean && running_var && dy && workspace,
               "bn_relu_maxpool_eval_bwd: every pointer but dgamma / dbeta is required");
   if (int e = require_pool_eval_sizes(groups, n_per_group, h, w, c)) return e;
@@ -1847,8 +1883,8 @@ int mvg_bn_relu_maxpool_eval_bwd(const float *g_pooled, const uint8_t *argmax, c
   const int c4n = c / 4;
   const int chunks = eval_pool_grid(groups, n_per_group, h, w, c4n);
   ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0,
-               4.0 * groups * ((double)n_per_group * h * w * c * 2 + (double)n_per_group * ho * wo * c * 1.25));
-  hipLaunchKernelGGL(bn_pool_eval_bwd_kernel, dim3(chunks, groups), dim3(256), 0, st, g_pooled, (const uchar4 *)argmax, y, scale,
+               groups * (Elem<T>::kBytes * (double)n_per_group * h * w * c * 2 + (double)n_per_group * ho * wo * c * (Elem<T>::kBytes + 1.0)));
+  hipLaunchKernelGGL(bn_pool_eval_bwd_kernel<T>, dim3(chunks, groups), dim3(256), 0, st, g_pooled, (const uchar4 *)argmax, y, scale,
                      shift, gamma, running_mean, running_var, eps, n_per_group, h, w, ho, wo, c4n, dy, workspace);
   if (check_launch("bn_relu_maxpool_eval_bwd")) return 1;
   if (!dgamma && !dbeta) return 0;
@@ -1856,6 +1892,31 @@ int mvg_bn_relu_maxpool_eval_bwd(const float *g_pooled, const uint8_t *argmax, c
                      dbeta, accumulate);
   return check_launch("bn_eval_bwd_finalize");
 }
+
+extern "C" {
+
+// (fp32, and bf16 storage of g / act / y / dy / dz_out: the geometry of the bf16 train-mode reduce - c/8 divides 256 or
+// exceeds it - and a relu_bits byte per 8 elements; the stem tail keeps 4 channels per lane in both)
+#define MVG_BN_EVAL_FACES(SUFFIX, T)                                                                                             \
+  int mvg_bn_eval_bwd##SUFFIX(const T *g, const T *act, const uint8_t *relu_bits, const T *y, const float *relu_scale,          \
+                              const float *relu_shift, const float *gamma, const float *running_mean,                           \
+                              const float *running_var, float eps, int groups, int64_t rows_per_group, int c, T *dy, T *dz_out, \
+                              float *dgamma, float *dbeta, int accumulate, float *workspace, void *stream) {                    \
+    return bn_eval_bwd_impl<T>(g, act, relu_bits, y, relu_scale, relu_shift, gamma, running_mean, running_var, eps, groups,     \
+                               rows_per_group, c, dy, dz_out, dgamma, dbeta, accumulate, workspace, stream);                    \
+  }                                                                                                                              \
+  int mvg_bn_relu_maxpool_eval_bwd##SUFFIX(const T *g_pooled, const uint8_t *argmax, const T *y, const float *scale,            \
+                                           const float *shift, const float *gamma, const float *running_mean,                   \
+                                           const float *running_var, float eps, int groups, int n_per_group, int h, int w,      \
+                                           int c, int ho, int wo, T *dy, float *dgamma, float *dbeta, int accumulate,           \
+                                           float *workspace, void *stream) {                                                    \
+    return bn_relu_maxpool_eval_bwd_impl<T>(g_pooled, argmax, y, scale, shift, gamma, running_mean, running_var, eps, groups,   \
+                                            n_per_group, h, w, c, ho, wo, dy, dgamma, dbeta, accumulate, workspace, stream);    \
+  }
+
+MVG_BN_EVAL_FACES(, float)
+MVG_BN_EVAL_FACES(_bf16, uint16_t)
+#undef MVG_BN_EVAL_FACES
 
 // ---- host-only plan query: the geometry functions above, asked without launching -----------------------------------
 static int bn_plan_impl(int pass, int elem, int groups, int64_t rows_per_group, int c, int n_per_group, int h, int w, int partials,

@@ -120,8 +120,9 @@ class _BackboneFn(torch.autograd.Function):
         # tape-less path (BatchNorm folded into the conv epilogues) even though the parameters require grad
         keep = model._grad_mode and any(ctx.needs_input_grad)
         ctx.need_dimg = any(ctx.needs_input_grad[3:3 + n_views])
+        # training: the BatchNorm flag (batch statistics); model.training: whether this is a training step (freeze_batchnorm)
         feat, tape = model._backbone.forward(imgs, training, keep, model.input_bgr, model.input_size, need_dimg=ctx.need_dimg,
-                                             input_augment=model.input_augment)
+                                             input_augment=model.input_augment, train_step=model.training)
         ctx.model, ctx.tape, ctx.n_views = model, tape, n_views
         if model._debug_keep_tapes:
             model._last_backbone_tape = tape
@@ -180,7 +181,17 @@ class _HeadFn(torch.autograd.Function):
 
 
 class MultiViewGaze(nn.Module):
-    """V-view engine (V >= 2).  ``FeatRotationSymm`` below is its two-view, reference-shaped face."""
+    """V-view engine (V >= 2).  ``FeatRotationSymm`` below is its two-view, reference-shaped face.
+
+    ``freeze_batchnorm`` (default False): with ``model.training`` and this flag the backbone's BatchNorm layers behave as in
+    eval mode - they normalise with ``running_mean`` / ``running_var``, update neither them nor ``num_batches_tracked``, and the
+    backward differentiates through the running statistics - which is what ``bn.eval()`` on every ``nn.BatchNorm2d`` does to a
+    PyTorch model inside ``train()`` (this backbone has no such modules: its parameters live in an arena).  Everything else
+    stays a training step: ``input_augment`` is applied to raw uint8 patches, the inference weight caches are invalidated and
+    the head receives ``model.training`` unchanged.  ``IntensityBatchNorm`` of the ``share_feature`` variant is not an
+    ``nn.BatchNorm2d``: it keeps following ``model.training`` (its ``running_mean`` keeps updating), as the idiom would leave
+    it.  In ``eval()`` the flag has no effect; with the flag off nothing changes anywhere.  Served by the fp32 model (on the
+    fp32-MFMA kernels, like an ``eval()`` step with gradients) and by ``compute_dtype = torch.bfloat16``."""
 
     def __init__(self, backbone_depth: int = 50, num_iter: int = 3, variant: Variant = DEFAULT_VARIANT) -> None:
         super().__init__()
@@ -230,6 +241,14 @@ class MultiViewGaze(nn.Module):
         # raw uint8 inputs in train() mode: an augment.TrainAugment puts every view through ColorJitter / RandomAffine (/ erase)
         # of main.py:41-49 on the GPU, in the launch that normalises it; eval() ignores it
         self.input_augment = None
+        # fine-tuning with frozen BatchNorm statistics (PyTorch's idiom: bn.eval() on every nn.BatchNorm2d of a model in
+        # train() mode).  With model.training and this flag the backbone's BatchNorm layers normalise with running_mean /
+        # running_var, update neither them nor num_batches_tracked, and the backward differentiates through the running
+        # statistics; everything else stays a training step: input_augment is applied to raw uint8 patches, the inference
+        # weight caches are dropped, and the head receives model.training unchanged - IntensityBatchNorm of the
+        # share_feature variant is not an nn.BatchNorm2d and keeps following model.training, as the idiom would leave it.
+        # No effect in eval(); off: nothing changes anywhere.  (The trainer calls model.train() every epoch: set it once.)
+        self.freeze_batchnorm: bool = False
         self._sink = _ArenaSink(self)
         self._wgrad_low_priority = True           # data-parallel runs set False (dp.GradAllReducer._configure)
         # storage / matrix-core type of the backbone: torch.float32 (default: the path held to 1e-4 against the
@@ -367,7 +386,7 @@ class MultiViewGaze(nn.Module):
         self._head.split = self._backbone.split          # one switch (MVG_SPLIT) selects the kernel family everywhere
         self._sink.active = False
         self._grad_mode = torch.is_grad_enabled()
-        img_feat = _BackboneFn.apply(self, self.training, len(imgs), *imgs, *self._backbone_params)
+        img_feat = _BackboneFn.apply(self, self.training and not self.freeze_batchnorm, len(imgs), *imgs, *self._backbone_params)
         lifted, feats, preds = _HeadFn.apply(self, img_feat, rot, *self._head_params)
         return img_feat, lifted, feats, preds
 

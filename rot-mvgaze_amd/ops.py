@@ -74,6 +74,18 @@ def _f32c(t: Tensor) -> Tensor:
     return t
 
 
+def _actc(like: Tensor):
+    """A checker for the activation-typed operands of a pass that runs in fp32 or bf16 storage: contiguous device tensors of
+    ``like``'s type."""
+    dt = like.dtype
+    assert dt in (torch.float32, torch.bfloat16), dt
+
+    def chk(t: Tensor) -> Tensor:
+        assert t.dtype == dt and t.is_cuda and t.is_contiguous(), f"expected contiguous {dt} device tensor"
+        return t
+    return chk
+
+
 def _fn(name: str, t: Tensor):
     """The entry point for t's storage type: activations are fp32 (parity path) or bf16 (config C5's path)."""
     return getattr(lib(), name + "_bf16" if t.dtype == torch.bfloat16 else name)
@@ -683,23 +695,28 @@ def bn_eval_bwd(g, y, gamma, running_mean, running_var, eps, groups, rows_per_gr
                 act=None, relu_bits=None, relu_affine=None, dz_out=None):
     """Eval-mode BatchNorm backward (running statistics) in one pass: dy = gamma * invstd_r * dz, dgamma / dbeta (+)= the
     sums over every group.  The ReLU mask from ONE of act, relu_bits, relu_affine = (scale, shift) of bn_eval_affine, or
-    none.  dy may be g itself; dz_out (may be g, not dy) receives the masked gradient."""
+    none.  dy may be g itself; dz_out (may be g, not dy) receives the masked gradient.  g, act, y, dy and dz_out are fp32 or
+    bf16 (one type; bf16 relu_bits: one byte per 8 elements, as bn_apply_bits writes them); everything else is fp32."""
     n = lib().mvg_bn_eval_bwd_workspace_floats(groups, rows_per_group, c)
     ws = torch.empty(n, dtype=torch.float32, device=g.device)
     rs, rh = relu_affine if relu_affine is not None else (None, None)
-    check(lib().mvg_bn_eval_bwd(_p(_f32c(g)), _p(act), _p(relu_bits), _p(_f32c(y)), _p(rs), _p(rh), _p(gamma), _p(running_mean),
-                                _p(running_var), eps, groups, rows_per_group, c, _p(_f32c(dy)), _p(dz_out), _p(dgamma), _p(dbeta),
-                                int(accumulate), _p(ws), _s()), "bn_eval_bwd")
+    a = _actc(g)              # fp32 or bf16: every activation-typed operand has g's storage type
+    assert dz_out is None or dz_out.dtype == g.dtype
+    check(_fn("mvg_bn_eval_bwd", g)(_p(a(g)), _p(a(act) if act is not None else None), _p(relu_bits), _p(a(y)), _p(rs), _p(rh),
+                                    _p(gamma), _p(running_mean), _p(running_var), eps, groups, rows_per_group, c, _p(a(dy)),
+                                    _p(dz_out), _p(dgamma), _p(dbeta), int(accumulate), _p(ws), _s()), "bn_eval_bwd")
 
 
 def bn_relu_maxpool_eval_bwd(g_pooled, argmax, y, scale, shift, gamma, running_mean, running_var, eps, groups, n_per_group, h, w,
                              c, ho, wo, dy, dgamma, dbeta, accumulate):
-    """The stem tail in eval mode: max-pool backward + ReLU + BatchNorm on the running statistics, dy written once."""
+    """The stem tail in eval mode: max-pool backward + ReLU + BatchNorm on the running statistics, dy written once.  g_pooled,
+    y and dy are fp32 or bf16 (one type)."""
     n = lib().mvg_bn_eval_bwd_workspace_floats(groups, n_per_group * h * w, c)
     ws = torch.empty(n, dtype=torch.float32, device=y.device)
-    check(lib().mvg_bn_relu_maxpool_eval_bwd(_p(_f32c(g_pooled)), _p(argmax), _p(_f32c(y)), _p(scale), _p(shift), _p(gamma),
-                                             _p(running_mean), _p(running_var), eps, groups, n_per_group, h, w, c, ho, wo,
-                                             _p(_f32c(dy)), _p(dgamma), _p(dbeta), int(accumulate), _p(ws), _s()),
+    a = _actc(y)
+    check(_fn("mvg_bn_relu_maxpool_eval_bwd", y)(_p(a(g_pooled)), _p(argmax), _p(a(y)), _p(scale), _p(shift), _p(gamma),
+                                                 _p(running_mean), _p(running_var), eps, groups, n_per_group, h, w, c, ho, wo,
+                                                 _p(a(dy)), _p(dgamma), _p(dbeta), int(accumulate), _p(ws), _s()),
           "bn_relu_maxpool_eval_bwd")
 
 
