@@ -487,6 +487,20 @@ enum { MVG_ADAM_MAX_SEGMENTS = 16 };
 int mvg_adam_step_segments(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                            const int64_t *host_bounds, const float *host_hyper, const int32_t *host_steps, int n_segments,
                            void *stream);
+/* mvg_adam_step_segments with nothing from the host but the launch itself (a fine-tuning step captured in a hipGraph replays
+ * it).  The segments travel by value as above - host_bounds as there, host_hyper[4 i ..] = {beta1, beta2, eps, weight_decay},
+ * host_lr_index[i] in [0, n_lr): constants of a captured plan - and two things live on the DEVICE: lr_dev[n_lr], one float per
+ * parameter group (the host rewrites an entry between replays when a scheduler moved that group's learning rate; segment i
+ * reads lr_dev[host_lr_index[i]]), and state3_dev[n_segments][3], one row {step, 1 - beta1^step, sqrt(1 - beta2^step)} per
+ * segment (a row starts as {count so far, 0, 0}).  Per MVG_ADAM_MAX_SEGMENTS segments there are two launches: a small one that
+ * advances those segments' rows, each exactly once and with its segment's betas (the arithmetic of mvg_adam_step_dev's tick),
+ * then the update, which reads lr_dev[..] / row[1] and row[2].  Null pointers, an lr index outside [0, n_lr) and segments that
+ * are unsorted, overlapping, not aligned to 4, outside [0, n) or empty are rejected before the first launch, the tick included:
+ * a rejected call has advanced no row and updated nothing.  Elements outside every segment are neither read nor written.  A
+ * segment's result equals, bit for bit, mvg_adam_step_dev over that slice with a one-element lr_dev and the same row. */
+int mvg_adam_step_segments_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                               const int64_t *host_bounds, const float *host_hyper, const int32_t *host_lr_index, int n_segments,
+                               const float *lr_dev, int n_lr, float *state3_dev, void *stream);
 
 /* ---------------------------------------------------------------- loss
  * gaze_angular_loss losses/gaze_loss.py:42-52 over pitchyaw_to_vector utils/math.py:52-60:

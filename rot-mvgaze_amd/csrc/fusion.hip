@@ -693,12 +693,16 @@ __global__ __launch_bounds__(256) void gaze_loss_multi_kernel(const float *__res
 // Adam with its step counter and learning rate on the DEVICE (a captured step replays with nothing from the host):
 // adam_tick_kernel advances state = {step, bias correction 1, sqrt(bias correction 2)} (one thread), adam_dev_kernel is
 // adam_kernel reading lr from hyper[0] and the corrections from state.
-__global__ void adam_tick_kernel(float *__restrict__ state, float b1, float b2) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+// (the advance of one state row, stated once for adam_tick_kernel and adam_tick_segments_kernel)
+__device__ __forceinline__ void adam_tick1(float *__restrict__ state, float b1, float b2) {
   const float step = state[0] + 1.f;
   state[0] = step;
   state[1] = (float)(1.0 - pow((double)b1, (double)step));
   state[2] = (float)sqrt(1.0 - pow((double)b2, (double)step));
+}
+__global__ void adam_tick_kernel(float *__restrict__ state, float b1, float b2) {
+  if (threadIdx.x != 0 || blockIdx.x != 0) return;
+  adam_tick1(state, b1, b2);
 }
 __global__ __launch_bounds__(256) void adam_dev_kernel(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
                                                        float4 *__restrict__ v, long long n4, const float *__restrict__ lr_dev,
@@ -707,6 +711,41 @@ __global__ __launch_bounds__(256) void adam_dev_kernel(float4 *__restrict__ p, c
   const float step_size = lr_dev[0] / state[1], bc2_sqrt = state[2];
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
     adam4(p, g, m, v, i, b1, b2, eps, wd, step_size, bc2_sqrt);
+}
+
+// The segmented step with its learning rates and step counters on the DEVICE (a captured fine-tuning step): the segments'
+// bounds and constants travel by value as in adam_segments_kernel, but a segment's learning rate is lr_dev[lr_index] (one float
+// per parameter group, written by the host between replays) and its bias corrections are its row of state =
+// {step, 1 - beta1^step, sqrt(1 - beta2^step)}, advanced by adam_tick_segments_kernel in front of the update: lane k < count
+// advances row k with segment k's betas, every row exactly once.
+struct AdamTicks {
+  float b1[MVG_ADAM_MAX_SEGMENTS], b2[MVG_ADAM_MAX_SEGMENTS];
+  int count;
+};
+__global__ void adam_tick_segments_kernel(float *__restrict__ state, AdamTicks t) {
+  const int k = threadIdx.x;
+  if (blockIdx.x != 0 || k >= t.count || k >= MVG_ADAM_MAX_SEGMENTS) return;
+  adam_tick1(state + 3 * k, t.b1[k], t.b2[k]);
+}
+struct AdamSegmentsDev {
+  long long end4[MVG_ADAM_MAX_SEGMENTS];      // as AdamSegments
+  long long shift4[MVG_ADAM_MAX_SEGMENTS];
+  int lr_index[MVG_ADAM_MAX_SEGMENTS];        // into lr_dev
+  float b1[MVG_ADAM_MAX_SEGMENTS], b2[MVG_ADAM_MAX_SEGMENTS], eps[MVG_ADAM_MAX_SEGMENTS], wd[MVG_ADAM_MAX_SEGMENTS];
+};
+__global__ __launch_bounds__(256) void adam_segments_dev_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
+                                                                float4 *__restrict__ m, float4 *__restrict__ v,
+                                                                const float *__restrict__ lr_dev, const float *__restrict__ state,
+                                                                AdamSegmentsDev t) {
+  const long long stride = (long long)gridDim.x * 256;
+  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
+    // (lr / bc1 in float, as adam_dev_kernel forms it: the same bits for the same device scalars)
+    adam4(p, g, m, v, i + t.shift4[k], t.b1[k], t.b2[k], t.eps[k], t.wd[k], lr_dev[t.lr_index[k]] / state[3 * k + 1], state[3 * k + 2]);
+  }
 }
 
 }  // namespace mvg
@@ -988,6 +1027,67 @@ int mvg_adam_step_dev(float *param, const float *grad, float *exp_avg, float *ex
   hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad, (float4 *)exp_avg,
                      (float4 *)exp_avg_sq, (long long)(n / 4), lr_dev, state3, beta1, beta2, eps, weight_decay);
   return check_launch("adam_step_dev");
+}
+
+int mvg_adam_step_segments_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
+                               const float *host_hyper, const int32_t *host_lr_index, int n_segments, const float *lr_dev, int n_lr,
+                               float *state3_dev, void *stream) {
+  MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && host_bounds && host_hyper && host_lr_index && lr_dev && state3_dev,
+              "adam_step_segments_dev: null argument");
+  MVG_REQUIRE(n % 4 == 0 && n_segments >= 1 && n_lr >= 1, "adam_step_segments_dev: n %% 4 != 0, no segment or no learning rate");
+  // every segment is checked before the first launch (the tick included): a rejected call has advanced and updated nothing
+  double active = 0.0;
+  for (int i = 0; i < n_segments; ++i) {
+    const int64_t b = host_bounds[2 * i], e = host_bounds[2 * i + 1];
+    MVG_REQUIRE(b % 4 == 0 && e % 4 == 0, "adam_step_segments_dev: segment %d [%lld, %lld) is not aligned to 4 elements", i, (long long)b,
+                (long long)e);
+    MVG_REQUIRE(b >= 0 && e <= n, "adam_step_segments_dev: segment %d [%lld, %lld) is outside the arena of %lld elements", i, (long long)b,
+                (long long)e, (long long)n);
+    MVG_REQUIRE(b < e, "adam_step_segments_dev: segment %d [%lld, %lld) is empty or reversed", i, (long long)b, (long long)e);
+    if (i > 0) {
+      MVG_REQUIRE(b >= host_bounds[2 * i - 2], "adam_step_segments_dev: segment %d begins before segment %d (unsorted)", i, i - 1);
+      MVG_REQUIRE(b >= host_bounds[2 * i - 1], "adam_step_segments_dev: segment %d overlaps segment %d", i, i - 1);
+    }
+    MVG_REQUIRE(host_lr_index[i] >= 0 && host_lr_index[i] < n_lr, "adam_step_segments_dev: segment %d has lr index %d outside [0, %d)", i,
+                (int)host_lr_index[i], n_lr);
+    active += (double)(e - b);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * active);
+  for (int s0 = 0; s0 < n_segments; s0 += MVG_ADAM_MAX_SEGMENTS) {
+    const int cnt = n_segments - s0 < MVG_ADAM_MAX_SEGMENTS ? n_segments - s0 : MVG_ADAM_MAX_SEGMENTS;
+    AdamTicks ticks;
+    AdamSegmentsDev t;
+    memset(&ticks, 0, sizeof(ticks));
+    memset(&t, 0, sizeof(t));
+    ticks.count = cnt;
+    long long total = 0;
+    for (int k = 0; k < MVG_ADAM_MAX_SEGMENTS; ++k) {
+      const int i = s0 + (k < cnt ? k : cnt - 1);          // (unused entries repeat the last segment: never selected)
+      const float *h = host_hyper + 4 * i;
+      if (k < cnt) {
+        t.shift4[k] = host_bounds[2 * i] / 4 - total;
+        total += (host_bounds[2 * i + 1] - host_bounds[2 * i]) / 4;
+      } else {
+        t.shift4[k] = t.shift4[cnt - 1];
+      }
+      t.end4[k] = total;
+      t.lr_index[k] = host_lr_index[i];
+      ticks.b1[k] = t.b1[k] = h[0];
+      ticks.b2[k] = t.b2[k] = h[1];
+      t.eps[k] = h[2];
+      t.wd[k] = h[3];
+    }
+    float *rows = state3_dev + 3 * (size_t)s0;             // this launch's rows of the table
+    hipLaunchKernelGGL(adam_tick_segments_kernel, dim3(1), dim3(64), 0, st, rows, ticks);
+    if (check_launch("adam_tick_segments")) return 1;
+    long long blocks = (total + 255) / 256;
+    if (blocks > 8192) blocks = 8192;
+    hipLaunchKernelGGL(adam_segments_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
+                       (float4 *)exp_avg, (float4 *)exp_avg_sq, lr_dev, (const float *)rows, t);
+    if (check_launch("adam_step_segments_dev")) return 1;
+  }
+  return 0;
 }
 
 int mvg_linear_skinny_fwd(const float *x, const float *w, const float *bias, float *y, int rows, int k, int nout,

@@ -16,6 +16,12 @@ weight-gradient side stream (fork / join events -> a branching graph) replays 1.
 26.2 ms, 15.3 vs 9.0): the capture is therefore taken single-stream (overlap_wgrad off), which gives up the ~6 % the
 overlap is worth on one GPU.  Use it where the host is the bottleneck (many ranks per host, small per-GPU batches).
 
+Fine-tuning steps (frozen parameters, parameter groups, model.freeze_batchnorm) capture the same way over
+optim.Adam(capturable="segments"): one learning rate per group and one step counter per segment on the device.  The captured
+launches hold that optimizer's plan by value, so run() checks on the host that the plan is still the captured one and raises
+otherwise (scripts/graph_finetune_bench.py, profiles/r20_graph_finetune_bench.json: ResNet-50 V=4 B=32 with the stem, layer1 and
+layer2 frozen replays at 16.8 ms of GPU time and 0.16 ms of host time against 15.95 / 13.2 ms eager with the side stream).
+
 PyTorch here is plumbing only: ``torch.cuda.CUDAGraph`` is hipStreamBeginCapture / hipGraphInstantiate / hipGraphLaunch
 plus a private pool of the caching allocator, which is what keeps every buffer the captured launches point at alive
 and un-recycled between replays.
@@ -60,8 +66,37 @@ class GraphedStep:
         with torch.cuda.graph(self.graph):
             self.loss = step_fn()
         self.replays = 0
+        # capturable="segments": the captured launches hold the optimizer's plan (which ranges are updated, from which group, with
+        # which constants) and point at its device table; what they were captured for is checked before every replay
+        self._plan = self._plan_now() if getattr(optimizer, "capturable", None) == "segments" else None
+        self._arena_params = [p for (p, _, _) in model.grad_arena()[1]] if self._plan is not None else None
+
+    def _plan_now(self):
+        return (self.optimizer.plan_signature(), [p.requires_grad for (p, _, _) in self.model.grad_arena()[1]], self.optimizer.plan_epoch(),
+                self.optimizer.plan_inputs())
+
+    def _check_plan(self) -> None:
+        """Host-only: a replay would go on updating a now-frozen parameter from its stale gradient (and never touch an unfrozen one)."""
+        # the signature is a function of the flags, the groups' constants and sizes and the table's epoch: nothing to plan while
+        # those are what they were (the common replay)
+        if self._plan[1] == [p.requires_grad for p in self._arena_params] and self._plan[3] == self.optimizer.plan_inputs():
+            return
+        sig, flags, epoch, _ = self._plan_now()
+        if flags != self._plan[1]:
+            names = {id(p): k for k, p in self.model.named_parameters()}
+            moved = [names.get(id(p), "?") for (p, _, _), a, b in zip(self.model.grad_arena()[1], self._plan[1], flags) if a != b]
+            what = f"requires_grad of {len(moved)} parameter(s) changed since the capture (first: {moved[0]})"
+        elif sig != self._plan[0]:
+            what = "the optimizer's plan changed since the capture (parameter groups, betas, eps or weight_decay)"
+        elif epoch != self._plan[2]:
+            what = "the optimizer rebuilt its device state since the capture (an eager step with another plan ran in between)"
+        else:
+            return
+        raise RuntimeError(f"GraphedStep: {what}; the captured step no longer matches - run one eager step and build a new GraphedStep")
 
     def run(self) -> Tensor:
+        if self._plan is not None:
+            self._check_plan()
         if self.optimizer is not None:
             self.optimizer.sync_lr()                 # a scheduler may have moved the learning rate: one 4-byte fill
         self.graph.replay()

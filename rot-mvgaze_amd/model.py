@@ -56,7 +56,9 @@ def _init_tensor(shape, kind: str) -> Tensor:
 
 class _ArenaSink(GradSink):
     def __init__(self, model: "MultiViewGaze"):
-        self.m = model
+        # (weak: the model owns its sink; a strong reference back made every model a reference cycle, whose arenas, moments and
+        # tapes - hundreds of MB - then stayed allocated until a garbage-collection pass happened to run)
+        self.m = weakref.proxy(model)
         self._acc: Dict[int, bool] = {}
         self._foreign: Dict[int, bool] = {}
         self._frozen: Dict[int, bool] = {}

@@ -991,6 +991,22 @@ def adam_step_segments(param, grad, exp_avg, exp_avg_sq, segments):
           "adam_step_segments")
 
 
+def adam_step_segments_dev(param, grad, exp_avg, exp_avg_sq, segments, lr_dev, state3):
+    """``adam_step_segments`` with the learning rates and step counters on the device: (begin, end, lr_index, beta1, beta2, eps,
+    weight_decay) records, ``lr_dev`` one float per parameter group, ``state3`` one row {step, 1 - beta1^step,
+    sqrt(1 - beta2^step)} per segment, advanced on the device in front of the update (mvg_adam_step_segments_dev)."""
+    n = len(segments)
+    if state3 is not None and (state3.dim() != 2 or tuple(state3.shape) != (n, 3) or not state3.is_contiguous()):
+        raise ValueError(f"adam_step_segments_dev: state3 must be a contiguous [{n}, 3] table, one row per segment")
+    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
+    index = (C.c_int32 * n)(*[int(s[2]) for s in segments])
+    hyper = (C.c_float * (4 * n))(*[float(v) for s in segments for v in s[3:7]])
+    check(lib().mvg_adam_step_segments_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, index, n,
+                                           _p(lr_dev), 0 if lr_dev is None else lr_dev.numel(), _p(state3), _s()), "adam_step_segments_dev")
+    for t in (param, exp_avg, exp_avg_sq):
+        torch.autograd.graph.increment_version(t)
+
+
 def adam_step_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, state3, beta1, beta2, eps, weight_decay):
     check(lib().mvg_adam_step_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(lr_dev), _p(state3), beta1, beta2, eps,
                                   weight_decay, _s()), "adam_step_dev")

@@ -13,6 +13,12 @@ a parameter unfrozen at step 5 starts its bias correction at 1.  Such a step is 
 merges arena-adjacent parameters with a gradient, the same hyper-parameters and the same step count into element ranges, and
 one launch (16 ranges at a time) updates those ranges only.  One group with every gradient present and one step count is the
 reference-shaped case and stays the ``mvg_adam_step`` launch.
+
+``capturable="segments"`` is that fine-tuning step for a hipGraph (graph.GraphedStep): ``mvg_adam_step_segments_dev`` takes the
+segments' bounds and constants by value, as above, but reads each group's learning rate from a device vector and each segment's
+step count and bias corrections from a device table that the step itself advances - a replay needs nothing from the host.  The
+segments, their group indices and constants are the PLAN; its signature tells when the table has to be rebuilt (a parameter was
+frozen or unfrozen, a group added, betas changed), which happens in an eager step only, from the counts read back from the device.
 """
 from __future__ import annotations
 
@@ -85,14 +91,33 @@ class Adam(torch.optim.Optimizer):
         # the DEVICE (mvg_adam_step_dev), so that a step captured in a hipGraph (rot_mvgaze_amd.graph.GraphedStep) replays
         # with nothing from the host; the learning rate is pushed to the device by sync_lr() - outside a capture - whenever
         # the scheduler changed it (the reference steps CyclicLR once per epoch, trainer.py:147).
-        self.capturable = bool(capturable)
-        if self.capturable and len(self.param_groups) != 1:
+        # capturable="segments": the same for the fine-tuning step - any number of groups, parameters without a gradient skipped,
+        # per-parameter step counts (mvg_adam_step_segments_dev: one learning rate per group and one counter per segment on the
+        # device).  Opt-in: True keeps meaning exactly the one-group, nothing-skipped step.
+        if isinstance(capturable, str) and capturable != "segments":
+            raise ValueError(f"Adam: capturable must be False, True or 'segments', not {capturable!r}")
+        self.capturable = "segments" if isinstance(capturable, str) else bool(capturable)
+        if self.capturable is True and len(self.param_groups) != 1:
             raise NotImplementedError("Adam(capturable=True) takes one parameter group (refused at construction): the captured "
                                       "step keeps ONE learning rate and ONE step counter on the device; grouped steps run with "
                                       "capturable=False")
 
     def sync_lr(self):
-        """capturable: copy param_groups[0]['lr'] to the device scalar the captured update reads (no-op when unchanged)."""
+        """capturable: copy param_groups[0]['lr'] to the device scalar the captured update reads (no-op when unchanged);
+        capturable="segments": every group's learning rate that changed, to its slot of the device vector."""
+        if self.capturable == "segments":
+            lrs = [float(g["lr"]) for g in self.param_groups]
+            for st in self._flat.values():
+                if "lr_dev" not in st:
+                    continue
+                for i in range(min(len(lrs), len(st["lr_host"]))):
+                    if st["lr_host"][i] != lrs[i]:
+                        if torch.cuda.is_current_stream_capturing():
+                            raise RuntimeError("Adam(capturable='segments'): a learning rate changed inside a graph capture; call "
+                                               "optimizer.sync_lr() before capturing / replaying")
+                        st["lr_dev"][i:i + 1].fill_(lrs[i])
+                        st["lr_host"][i] = lrs[i]
+            return
         lr = float(self.param_groups[0]["lr"])
         for st in self._flat.values():
             if "lr_dev" in st and st["lr_host"] != lr:
@@ -141,6 +166,78 @@ class Adam(torch.optim.Optimizer):
             self._flat[id(model)] = st
         return st
 
+    # ---- capturable="segments": the plan, its signature and the device table
+    @staticmethod
+    def _segment_key(index: int, g) -> tuple:
+        """What two parameters must share to share a segment of the device-resident step: the group (its INDEX - two groups with
+        equal learning rates today may differ tomorrow) and the constants that travel by value.  The learning rate is not in it."""
+        return (index, float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+
+    def _plan(self, entries, have, steps) -> List[Segment]:
+        """plan_segments over ``entries`` = [(param, offset, numel)] for the parameters ``have`` marks, from counts ``steps`` so far."""
+        key_of = {id(p): self._segment_key(i, g) for i, g in enumerate(self.param_groups) for p in g["params"]}
+        return plan_segments([(off, n) for (_, off, n) in entries], [key_of.get(id(p)) for (p, _, _) in entries], have,
+                             [s + 1 if h else s for s, h in zip(steps, have)])
+
+    @staticmethod
+    def _signature(segs: Sequence[Segment]) -> tuple:
+        """Bounds, group index and by-value constants per segment.  No step count and no learning rate: every row advances once per
+        step, so counts that agreed (or differed) when the table was built still do, and learning rates live in lr_dev."""
+        return tuple((s.begin, s.end) + s.group for s in segs)
+
+    def plan_signature(self, entries=None) -> tuple:
+        """The signature of the plan the next step would run if every parameter that requires a gradient received one.  Host-only
+        (no device read, no launch): graph.GraphedStep compares it before every replay.  ``entries`` = [(param, offset, numel)] in
+        arena order; by default the arena of every model the parameters belong to."""
+        group_params = {id(p) for g in self.param_groups for p in g["params"]}
+        lists = [(None, entries)] if entries is not None else [(m, m.grad_arena()[1]) for m in self._owners()]
+        out = []
+        for model, ents in lists:
+            st = self._flat.get(id(model)) if model is not None else None
+            steps = st["steps"] if st is not None and len(st["steps"]) == len(ents) else [0] * len(ents)
+            have = [id(p) in group_params and p.requires_grad for (p, _, _) in ents]
+            out.append(self._signature(self._plan(ents, have, steps)))
+        return tuple(out)
+
+    def plan_inputs(self) -> tuple:
+        """What plan_signature() is a function of besides the parameters' requires_grad flags: each group's size and by-value
+        constants, and the epoch of the device tables (whose counts decide which neighbours may share a segment)."""
+        return (tuple((len(g["params"]),) + self._segment_key(i, g) for i, g in enumerate(self.param_groups)), self.plan_epoch())
+
+    def plan_epoch(self) -> tuple:
+        """How often each model's device table was (re)built: a graph captured before a rebuild points at the old table."""
+        return tuple(st.get("epoch", 0) for st in self._flat.values())
+
+    @staticmethod
+    def _pull_steps(st) -> None:
+        """Per-parameter counts from the device table - the truth, since replays advance it without Python (one small copy)."""
+        if "state3" in st:
+            rows = [int(round(x)) for x in st["state3"][:, 0].cpu().tolist()]
+            st["steps"] = [rows[k] if k >= 0 else s for s, k in zip(st["steps"], st["seg_of"])]
+            st["step"] = max(st["steps"])
+
+    def _step_segments_dev(self, st, entries, have, arena_p, arena_g) -> None:
+        segs = self._plan(entries, have, st["steps"])
+        if self._signature(segs) != st.get("sig") or len(st["lr_host"]) != len(self.param_groups):
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Adam(capturable='segments'): the plan of this step (which parameters hold a gradient, their groups, "
+                                   "betas / eps / weight_decay) is not the one its device state was built for; run one eager step "
+                                   "before capturing (the device table is created and rebuilt there, never inside a capture)")
+            self._pull_steps(st)                       # counts as the device advanced them, then the plan from those
+            segs = self._plan(entries, have, st["steps"])
+            dev = arena_p.device
+            st["sig"] = self._signature(segs)
+            st["segs"] = [(s.begin, s.end) + s.group for s in segs]
+            st["seg_of"] = [next((k for k, s in enumerate(segs) if s.begin <= off < s.end), -1) if h else -1
+                            for (_, off, _), h in zip(entries, have)]
+            # a row holds the count so far; the step's own launch advances it (a parameter unfrozen later starts at step 1)
+            st["state3"] = torch.tensor([[float(s.step - 1), 0.0, 0.0] for s in segs], dtype=torch.float32).reshape(-1, 3).to(dev)
+            st["lr_host"] = [float(g["lr"]) for g in self.param_groups]
+            st["lr_dev"] = torch.tensor(st["lr_host"], dtype=torch.float32).to(dev)
+            st["epoch"] = st.get("epoch", 0) + 1
+        self.sync_lr()
+        ops.adam_step_segments_dev(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs"], st["lr_dev"], st["state3"])
+
     @torch.no_grad()
     def step(self, closure=None):
         loss = None
@@ -161,10 +258,22 @@ class Adam(torch.optim.Optimizer):
                     raise RuntimeError("every trainable parameter must hold the gradient written by the "
                                        "module's backward (a view of its gradient arena)")
             arena_p = model.param_arena()
+            if self.capturable == "segments" and id(model) not in self._flat and torch.cuda.is_current_stream_capturing():
+                # (before the moments exist: their zero fill would be captured, not run)
+                raise RuntimeError("Adam(capturable='segments'): run one eager step before capturing (the moments and the device "
+                                   "state are created there, never inside a capture)")
             st = self._state_for(model, arena_p, len(entries))
             steps = [s + 1 if h else s for s, h in zip(st["steps"], have)]
             # the reference-shaped step: one group, every arena parameter in it with a gradient, one step count
             whole = len(self.param_groups) == 1 and all(have) and len(set(steps)) == 1
+            if self.capturable == "segments":
+                # (the counts stay the ones the device table was built from: the table itself is advanced by the launch)
+                st.setdefault("lr_host", [])
+                self._step_segments_dev(st, entries, have, arena_p, arena_g)
+                for (p, _, _), h in zip(entries, have):
+                    if h:
+                        torch.autograd.graph.increment_version(p)
+                continue
             if self.capturable and not whole:
                 raise NotImplementedError("Adam(capturable=True) cannot skip parameters (refused at step()): a parameter without a "
                                           "gradient, or with a step count of its own, needs the segmented step, which takes its "
@@ -210,7 +319,9 @@ class Adam(torch.optim.Optimizer):
         for model in self._owners():
             st = self._flat.get(id(model))
             if st is not None:
-                if "state3" in st:                  # capturable: the device counter is the truth (graph replays advance it)
+                if "seg_of" in st:                  # capturable="segments": one device counter per segment
+                    self._pull_steps(st)
+                elif "state3" in st:                # capturable: the device counter is the truth (graph replays advance it)
                     st["step"] = int(round(float(st["state3"][0].item())))
                     st["steps"] = [st["step"]] * len(st["steps"])
                 flat.append({"step": st["step"], "steps": list(st["steps"]), "exp_avg": st["exp_avg"].detach().clone(),

@@ -4,7 +4,9 @@
   seg_full       one segment over the whole arena
   seg_head       the head-only step: heads, fusers and lifter in one segment
   seg_l34_head   layer3 + layer4 at one learning rate and the head at another: two segments
-Device events around CALLS back-to-back launches, ROUNDS rounds that alternate the four, the median over rounds and the
+  dev_full, dev_head, dev_l34_head   the same three plans through mvg_adam_step_segments_dev: learning rates and step counters
+                 on the device, a one-block launch that advances the counters in front of every update (the captured step's form)
+Device events around CALLS back-to-back launches, ROUNDS rounds that alternate the seven, the median over rounds and the
 round-to-round spread (min .. max) per variant; GB/s on 28 B per active element.  Synthetic values.
 Usage: adam_segments_bench.py [--calls 20] [--rounds 5] [--out FILE.json]"""
 import argparse
@@ -60,6 +62,12 @@ def main():
     for k, segs in variants.items():
         runs[k] = (lambda s: lambda: ops.adam_step_segments(p, gr, mo, ve, s))(segs)
     active = {"full": n, **{k: sum(e - b for b, e, *_ in segs) for k, segs in variants.items()}}
+    lr_dev = torch.tensor([HEAD[0], BODY[0]], dtype=torch.float32).to(dev)
+    for k, segs in variants.items():                      # (begin, end, lr index, betas, eps, weight_decay) and one zeroed row per segment
+        recs = [(b, e, 0 if lr == HEAD[0] else 1, b1, b2, eps, wd) for (b, e, lr, b1, b2, eps, wd, _) in segs]
+        rows = torch.zeros(len(recs), 3, device=dev)
+        runs["dev" + k[3:]] = (lambda s, r: lambda: ops.adam_step_segments_dev(p, gr, mo, ve, s, lr_dev, r))(recs, rows)
+        active["dev" + k[3:]] = active[k]
     for fn in runs.values():                              # every variant once: code objects loaded, caches in their steady state
         fn()
     torch.cuda.synchronize()
@@ -76,14 +84,16 @@ def main():
     out = {"device": torch.cuda.get_device_name(0), "arena_elements": n, "calls_per_round": a.calls, "rounds": a.rounds, "variants": {}}
     for k, ts in per_call.items():
         med = float(np.median(ts))
-        out["variants"][k] = {"segments": len(variants[k]) if k in variants else 0, "active_elements": active[k],
+        out["variants"][k] = {"segments": len(variants.get("seg" + k[3:], [])), "active_elements": active[k],
                               "ms_per_call_median": round(med, 4), "ms_per_call_min": round(min(ts), 4),
                               "ms_per_call_max": round(max(ts), 4), "GBps_on_28B_per_active_element": round(28.0 * active[k] / med / 1e6, 1)}
         print(k, json.dumps(out["variants"][k]), flush=True)
     full = out["variants"]["full"]["ms_per_call_median"]
     out["over_full"] = {k: round(v["ms_per_call_median"] / full, 4) for k, v in out["variants"].items()}
     out["active_share"] = {k: round(active[k] / n, 4) for k in runs}
-    print(json.dumps({"over_full": out["over_full"], "active_share": out["active_share"]}), flush=True)
+    out["dev_over_seg"] = {k[4:]: round(out["variants"][k]["ms_per_call_median"] / out["variants"]["seg" + k[3:]]["ms_per_call_median"], 4)
+                           for k in runs if k.startswith("dev_")}
+    print(json.dumps({"over_full": out["over_full"], "active_share": out["active_share"], "dev_over_seg": out["dev_over_seg"]}), flush=True)
     if a.out:
         os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
         with open(a.out, "w") as f:
