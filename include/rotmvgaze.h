@@ -501,6 +501,31 @@ int mvg_adam_step_segments(float *param, const float *grad, float *exp_avg, floa
 int mvg_adam_step_segments_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                                const int64_t *host_bounds, const float *host_hyper, const int32_t *host_lr_index, int n_segments,
                                const float *lr_dev, int n_lr, float *state3_dev, void *stream);
+/* Global-norm gradient clipping and the non-finite guard of the segmented steps.  mvg_grad_norm_segments reads the gradients of
+ * the segments (host_bounds as above, checked by the same rules before the first launch; nothing outside a segment is read)
+ * once and leaves the record clip4_dev = four device floats {norm, coef, skipped, skipped_total}: norm = sqrt(sum of squares),
+ * coef = min(1, max_norm / (norm + 1e-6)) formed in double (torch.nn.utils.clip_grad_norm_'s coefficient; max_norm <= 0: no
+ * clipping, coef = 1), skipped = 1 when skip_nonfinite is set and the sum is not finite (coef is then 0; with skip_nonfinite
+ * clear a non-finite sum gives the NaN / 0 coefficient torch's formula gives), skipped_total += skipped - the one field that is
+ * read before it is written, so the caller zeroes the record once.  The sum is accumulated in double: a finite fp32 gradient
+ * cannot overflow it, and it is non-finite exactly when an element is.  One partial-sum launch per MVG_ADAM_MAX_SEGMENTS
+ * segments, each workgroup storing one double to the caller's workspace ws (at least mvg_grad_norm_workspace_bytes(n_segments)
+ * bytes, 8-byte aligned; a smaller one is rejected), then one one-workgroup launch that adds the partials in a fixed order: no
+ * atomics, and the grids depend on the segment sizes and the CU count alone, so equal inputs give equal bits.  Nothing is
+ * allocated and nothing synchronises.
+ * mvg_adam_step_segments_clip / mvg_adam_step_segments_dev_clip are the two segmented steps reading that record: the gradient is
+ * multiplied by coef as it is loaded (rounded to fp32 on its own: the result equals, bit for bit, the unclipped entry point on a
+ * gradient scaled by coef in fp32; the gradient arena is not rewritten), and with skipped != 0 the update - and the device
+ * form's tick - leave parameters, moments and state rows as they are. */
+int64_t mvg_grad_norm_workspace_bytes(int n_segments);
+int mvg_grad_norm_segments(const float *grad, int64_t n, const int64_t *host_bounds, int n_segments, float max_norm,
+                           int skip_nonfinite, void *ws, int64_t ws_bytes, float *clip4_dev, void *stream);
+int mvg_adam_step_segments_clip(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                const int64_t *host_bounds, const float *host_hyper, const int32_t *host_steps, int n_segments,
+                                const float *clip4_dev, void *stream);
+int mvg_adam_step_segments_dev_clip(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                    const int64_t *host_bounds, const float *host_hyper, const int32_t *host_lr_index, int n_segments,
+                                    const float *lr_dev, int n_lr, float *state3_dev, const float *clip4_dev, void *stream);
 
 /* ---------------------------------------------------------------- loss
  * gaze_angular_loss losses/gaze_loss.py:42-52 over pitchyaw_to_vector utils/math.py:52-60:

@@ -195,6 +195,12 @@ SIGNATURES = {
     "mvg_adam_step_segments": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), _I, _P]),
     "mvg_adam_step_segments_dev": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), _I, _P, _I, _P,
                                         _P]),
+    "mvg_grad_norm_workspace_bytes": (_I64, [_I]),
+    "mvg_grad_norm_segments": (_I, [_P, _I64, C.POINTER(C.c_int64), _I, _F, _I, _P, _I64, _P, _P]),
+    "mvg_adam_step_segments_clip": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), _I, _P,
+                                         _P]),
+    "mvg_adam_step_segments_dev_clip": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), _I, _P,
+                                             _I, _P, _P, _P]),
     # the fusion block on the split kernels
     "mvg_absmax_multi": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), _I, _P]),
     "mvg_fuse_build_split": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -81,7 +81,7 @@ class GraphedStep:
         # those are what they were (the common replay)
         if self._plan[1] == [p.requires_grad for p in self._arena_params] and self._plan[3] == self.optimizer.plan_inputs():
             return
-        sig, flags, epoch, _ = self._plan_now()
+        sig, flags, epoch, inputs = self._plan_now()
         if flags != self._plan[1]:
             names = {id(p): k for k, p in self.model.named_parameters()}
             moved = [names.get(id(p), "?") for (p, _, _), a, b in zip(self.model.grad_arena()[1], self._plan[1], flags) if a != b]
@@ -90,6 +90,8 @@ class GraphedStep:
             what = "the optimizer's plan changed since the capture (parameter groups, betas, eps or weight_decay)"
         elif epoch != self._plan[2]:
             what = "the optimizer rebuilt its device state since the capture (an eager step with another plan ran in between)"
+        elif inputs[2:] != self._plan[3][2:]:
+            what = "the optimizer's max_grad_norm or skip_nonfinite changed since the capture (both travel by value in the captured launches)"
         else:
             return
         raise RuntimeError(f"GraphedStep: {what}; the captured step no longer matches - run one eager step and build a new GraphedStep")

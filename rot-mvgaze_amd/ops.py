@@ -1007,6 +1007,76 @@ def adam_step_segments_dev(param, grad, exp_avg, exp_avg_sq, segments, lr_dev, s
         torch.autograd.graph.increment_version(t)
 
 
+_grad_norm_ws = {}    # device index -> the uint8 workspace of grad_norm_segments (partial sums; uses are ordered by the stream)
+
+
+def grad_norm_workspace_bytes(n_segments: int) -> int:
+    """Bytes of workspace mvg_grad_norm_segments needs for ``n_segments`` segments on the current device."""
+    need = int(lib().mvg_grad_norm_workspace_bytes(int(n_segments)))
+    if need < 0:
+        check(1, "grad_norm_workspace_bytes")
+    return need
+
+
+def grad_norm_workspace(n_segments: int, device) -> Tensor:
+    """The per-device workspace grad_norm_segments uses when it is given none, from PyTorch's allocator; kept and grown on demand
+    (never inside a graph capture).  Its users are ordered by the stream: callers that queue norms on several streams of one
+    device at once own their workspaces (optim.Adam keeps one per model)."""
+    need = grad_norm_workspace_bytes(n_segments)
+    index = torch.device(device).index
+    index = torch.cuda.current_device() if index is None else index
+    ws = _grad_norm_ws.get(index)
+    if ws is None or ws.numel() < need:
+        if torch.cuda.is_current_stream_capturing():
+            raise RuntimeError("grad_norm_segments: the workspace must exist before a graph capture (run one eager step first)")
+        ws = _grad_norm_ws[index] = torch.empty(need, dtype=torch.uint8, device=torch.device("cuda", index))
+    return ws
+
+
+def grad_norm_segments(grad, bounds, max_norm, skip_nonfinite, clip4, ws=None):
+    """clip4 = {norm, coef, skipped, skipped_total} (four device floats, zeroed once by the caller) from the gradients inside
+    ``bounds`` = [(begin, end), ...] (sorted, disjoint, aligned to 4): the global L2 norm, clip_grad_norm_'s coefficient for
+    ``max_norm`` (None or <= 0: 1, no clipping) and, with ``skip_nonfinite``, whether a non-finite gradient asks for the step to
+    be skipped (mvg_grad_norm_segments: one read of the segments, double accumulation, bit-reproducible).  ws: a uint8 workspace
+    of at least mvg_grad_norm_workspace_bytes; by default the cached one of grad's device."""
+    n = len(bounds)
+    if ws is None and n >= 1 and grad is not None:
+        ws = grad_norm_workspace(n, grad.device)
+    b = (C.c_int64 * (2 * n))(*[int(v) for s in bounds for v in s[0:2]])
+    check(lib().mvg_grad_norm_segments(_p(grad), 0 if grad is None else grad.numel(), b, n, 0.0 if max_norm is None else float(max_norm),
+                                       int(bool(skip_nonfinite)), _p(ws), 0 if ws is None else ws.numel() * ws.element_size(), _p(clip4),
+                                       _s()), "grad_norm_segments")
+
+
+def adam_step_segments_clip(param, grad, exp_avg, exp_avg_sq, segments, clip4):
+    """``adam_step_segments`` with the gradient multiplied by clip4's coefficient as it is loaded, and nothing touched when
+    clip4's skipped flag is set (mvg_adam_step_segments_clip; clip4 as grad_norm_segments left it)."""
+    n = len(segments)
+    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
+    hyper = (C.c_float * (5 * n))(*[float(v) for s in segments for v in s[2:7]])
+    steps = (C.c_int32 * n)(*[int(s[7]) for s in segments])
+    check(lib().mvg_adam_step_segments_clip(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, steps, n,
+                                            _p(clip4), _s()), "adam_step_segments_clip")
+    for t in (param, exp_avg, exp_avg_sq):
+        torch.autograd.graph.increment_version(t)
+
+
+def adam_step_segments_dev_clip(param, grad, exp_avg, exp_avg_sq, segments, lr_dev, state3, clip4):
+    """``adam_step_segments_dev`` reading clip4: the clipped update, and neither tick nor update when its skipped flag is set
+    (mvg_adam_step_segments_dev_clip)."""
+    n = len(segments)
+    if state3 is not None and (state3.dim() != 2 or tuple(state3.shape) != (n, 3) or not state3.is_contiguous()):
+        raise ValueError(f"adam_step_segments_dev_clip: state3 must be a contiguous [{n}, 3] table, one row per segment")
+    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
+    index = (C.c_int32 * n)(*[int(s[2]) for s in segments])
+    hyper = (C.c_float * (4 * n))(*[float(v) for s in segments for v in s[3:7]])
+    check(lib().mvg_adam_step_segments_dev_clip(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, index, n,
+                                                _p(lr_dev), 0 if lr_dev is None else lr_dev.numel(), _p(state3), _p(clip4), _s()),
+          "adam_step_segments_dev_clip")
+    for t in (param, exp_avg, exp_avg_sq):
+        torch.autograd.graph.increment_version(t)
+
+
 def adam_step_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, state3, beta1, beta2, eps, weight_decay):
     check(lib().mvg_adam_step_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(lr_dev), _p(state3), beta1, beta2, eps,
                                   weight_decay, _s()), "adam_step_dev")

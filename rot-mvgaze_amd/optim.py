@@ -19,6 +19,17 @@ segments' bounds and constants by value, as above, but reads each group's learni
 step count and bias corrections from a device table that the step itself advances - a replay needs nothing from the host.  The
 segments, their group indices and constants are the PLAN; its signature tells when the table has to be rebuilt (a parameter was
 frozen or unfrozen, a group added, betas changed), which happens in an eager step only, from the counts read back from the device.
+
+``max_grad_norm`` / ``skip_nonfinite`` add global-norm gradient clipping and a guard against non-finite gradients to the step
+itself.  One read of the gradients of the parameters that take part (``mvg_grad_norm_segments`` over the plan's segments) leaves
+``{norm, coef, skipped, skipped_total}`` on the device; the segmented update multiplies each gradient by ``coef`` as it loads it
+and, like the tick of the device-resident counters, returns at once when ``skipped`` is set.  Two differences from
+``torch.nn.utils.clip_grad_norm_``: ``.grad`` KEEPS THE UNSCALED GRADIENT (nothing rewrites the gradient arena; the scaled value
+exists only inside the update), and the norm counts exactly the parameters that take part in the step - a frozen or group-less
+parameter's stale ``.grad`` is not in it.  Clipping alone adds no synchronisation.  ``skip_nonfinite`` with ``capturable=False``
+reads the 16-byte record back after the norm launches - the ONE synchronisation this mode adds (``GradScaler.step`` does the
+same) - and on a skip launches no update and leaves the host step counts alone; with ``capturable="segments"`` nothing comes
+back to the host: the tick and the update read ``skipped`` on the device, so a captured replay clips and skips by itself.
 """
 from __future__ import annotations
 
@@ -78,7 +89,8 @@ def plan_segments(entries: Sequence[Tuple[int, int]], group_of: Sequence[Hashabl
 
 
 class Adam(torch.optim.Optimizer):
-    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False):
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False, max_grad_norm=None,
+                 skip_nonfinite=False):
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid Adam hyper-parameter")
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
@@ -101,6 +113,22 @@ class Adam(torch.optim.Optimizer):
             raise NotImplementedError("Adam(capturable=True) takes one parameter group (refused at construction): the captured "
                                       "step keeps ONE learning rate and ONE step counter on the device; grouped steps run with "
                                       "capturable=False")
+        # max_grad_norm (None: no clipping) / skip_nonfinite: attributes of the optimizer, not of its groups - the norm is global,
+        # and state_dict() keeps the keys it had (see the module docstring for what they do and what they cost)
+        self._check_max_grad_norm(max_grad_norm)
+        self.max_grad_norm = None if max_grad_norm is None else float(max_grad_norm)
+        self.skip_nonfinite = bool(skip_nonfinite)
+        if self.capturable is True and self._clipping():
+            raise ValueError("Adam(capturable=True) takes neither max_grad_norm nor skip_nonfinite: clipping and the guard run on the "
+                             "segmented step; use capturable='segments' (it serves one parameter group as well)")
+
+    @staticmethod
+    def _check_max_grad_norm(value) -> None:
+        if value is not None and not float(value) > 0:
+            raise ValueError(f"Adam: max_grad_norm must be None or > 0, not {value!r}")
+
+    def _clipping(self) -> bool:
+        return self.max_grad_norm is not None or bool(self.skip_nonfinite)
 
     def sync_lr(self):
         """capturable: copy param_groups[0]['lr'] to the device scalar the captured update reads (no-op when unchanged);
@@ -201,8 +229,10 @@ class Adam(torch.optim.Optimizer):
 
     def plan_inputs(self) -> tuple:
         """What plan_signature() is a function of besides the parameters' requires_grad flags: each group's size and by-value
-        constants, and the epoch of the device tables (whose counts decide which neighbours may share a segment)."""
-        return (tuple((len(g["params"]),) + self._segment_key(i, g) for i, g in enumerate(self.param_groups)), self.plan_epoch())
+        constants, and the epoch of the device tables (whose counts decide which neighbours may share a segment); and what else a
+        captured step holds by value: max_grad_norm and skip_nonfinite."""
+        return (tuple((len(g["params"]),) + self._segment_key(i, g) for i, g in enumerate(self.param_groups)), self.plan_epoch(),
+                (None if self.max_grad_norm is None else float(self.max_grad_norm), bool(self.skip_nonfinite)))
 
     def plan_epoch(self) -> tuple:
         """How often each model's device table was (re)built: a graph captured before a rebuild points at the old table."""
@@ -236,7 +266,44 @@ class Adam(torch.optim.Optimizer):
             st["lr_dev"] = torch.tensor(st["lr_host"], dtype=torch.float32).to(dev)
             st["epoch"] = st.get("epoch", 0) + 1
         self.sync_lr()
-        ops.adam_step_segments_dev(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs"], st["lr_dev"], st["state3"])
+        if not self._clipping():
+            ops.adam_step_segments_dev(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs"], st["lr_dev"], st["state3"])
+            return
+        self._check_max_grad_norm(self.max_grad_norm)
+        clip4, ws = self._clip_buffers(st, arena_p.device, len(st["segs"]))
+        ops.grad_norm_segments(arena_g, st["segs"], self.max_grad_norm, self.skip_nonfinite, clip4, ws)
+        ops.adam_step_segments_dev_clip(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs"], st["lr_dev"], st["state3"], clip4)
+
+    # ---- max_grad_norm / skip_nonfinite: the device record and the norm's workspace
+    def _clip_buffers(self, st, device, n_segments: int):
+        """(clip4, workspace) of one model's state: created in an eager step, never inside a capture (a captured step holds their
+        addresses).  clip4 is zeroed once - its skipped_total counts from then on."""
+        if "clip4" not in st or st.get("clip_segments", 0) < n_segments:
+            if torch.cuda.is_current_stream_capturing():
+                raise RuntimeError("Adam: max_grad_norm / skip_nonfinite need one eager step before capturing (the clip record and the "
+                                   "norm's workspace are created there, never inside a capture)")
+            st.setdefault("clip4", torch.zeros(4, dtype=torch.float32, device=device))
+            with torch.cuda.device(device):
+                st["clip_ws"] = torch.empty(ops.grad_norm_workspace_bytes(n_segments), dtype=torch.uint8, device=device)
+            st["clip_segments"] = n_segments
+        return st["clip4"], st["clip_ws"]
+
+    def clip_record(self, model) -> torch.Tensor:
+        """The device record {norm, coef, skipped, skipped_total} of ``model``'s last step (four floats; no synchronisation)."""
+        st = self._flat.get(id(model))
+        if st is None or "clip4" not in st:
+            raise RuntimeError("Adam.clip_record: no step with max_grad_norm or skip_nonfinite has run for this model yet")
+        return st["clip4"]
+
+    def grad_clip_report(self) -> List[dict]:
+        """One {"norm", "coef", "skipped", "skipped_total"} per model, read back from the device (this synchronises)."""
+        out = []
+        for model in self._owners():
+            st = self._flat.get(id(model))
+            if st is not None and "clip4" in st:
+                norm, coef, skipped, total = st["clip4"].cpu().tolist()
+                out.append({"norm": norm, "coef": coef, "skipped": bool(skipped), "skipped_total": int(total)})
+        return out
 
     @torch.no_grad()
     def step(self, closure=None):
@@ -278,6 +345,27 @@ class Adam(torch.optim.Optimizer):
                 raise NotImplementedError("Adam(capturable=True) cannot skip parameters (refused at step()): a parameter without a "
                                           "gradient, or with a step count of its own, needs the segmented step, which takes its "
                                           "segments from the host; use capturable=False for frozen or later-unfrozen parameters")
+            if self._clipping():
+                # the segmented forms over the plan's segments, whatever the plan (a segment equals mvg_adam_step over its slice
+                # bit for bit): the norm over exactly those segments, then the update that reads its record
+                if self.capturable:
+                    raise ValueError("Adam(capturable=True) takes neither max_grad_norm nor skip_nonfinite (set after construction): "
+                                     "use capturable='segments'")
+                self._check_max_grad_norm(self.max_grad_norm)
+                segs = plan_segments([(off, n) for (_, off, n) in entries], [self._hyper(g) if g is not None else None for g in groups],
+                                     have, steps)
+                clip4, ws = self._clip_buffers(st, arena_p.device, len(segs))
+                ops.grad_norm_segments(arena_g, [(s.begin, s.end) for s in segs], self.max_grad_norm, self.skip_nonfinite, clip4, ws)
+                if self.skip_nonfinite and float(clip4[2].item()) != 0.0:      # (the one synchronisation of this mode)
+                    continue                                                    # skipped: no update, the step counts stay
+                st["steps"] = steps
+                st["step"] = max(steps)
+                ops.adam_step_segments_clip(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"],
+                                            [(s.begin, s.end) + s.group + (s.step,) for s in segs], clip4)
+                for (p, _, _), h in zip(entries, have):
+                    if h:
+                        torch.autograd.graph.increment_version(p)
+                continue
             st["steps"] = steps
             st["step"] = max(steps)
             if self.capturable:
