@@ -546,6 +546,27 @@ int mvg_gaze_lp_loss(const float *pred, const float *label, int n, int p, float 
 int mvg_gaze_angular_loss_multi(const float *pred, const float *gt, int iters, int dirs, int batch, const float *host_weights,
                                 float *loss, float *dpred, void *stream);
 
+/* Gaze error meter: the evaluation metric the trainer prints (trainer.py:128,187-192: np.mean(angular_error(pred, gt)), degrees)
+ * accumulated on the DEVICE in double, with no copy to the host per batch.  preds fp32 [iters][dirs][batch][2] (the heads'
+ * stacked (pitch, yaw) buffer, mvg_session_forward's preds), gt fp32 [dirs][batch][2] (row d = the labels of the view direction
+ * d predicts for, the layout of mvg_gaze_angular_loss_multi's gt).  record = double [iters * dirs][MVG_GAZE_ERR_FIELDS], one
+ * cell per (iteration, direction): COUNT, SUM, SUMSQ, MAX of the rows' errors and NONFINITE, the rows left out (counts are
+ * doubles holding integers).  All zero is the empty record; reset is a stream-ordered memset of it (there is no entry point).
+ * Per row, in double: utils/math.py:105-120 (angular_error_numpy) - both pairs to vectors with sin / cos, norms clipped at 1e-7,
+ * similarity = dot / (na nb), acos, * 180 / pi - with ONE deviation: the similarity is clamped to [-1, 1] before acos (the
+ * reference returns NaN where pred == gt rounds to 1 + 2e-16; here such a row is 0).  A row with a NaN or Inf in pred or gt
+ * increments NONFINITE only.  err_out (may be NULL) fp32 [iters * dirs][capacity], the device form of pred_gaze_all /
+ * gt_gaze_all (trainer.py:169-189): row b of this call goes to slot seen_before + b of its cell's row, seen_before = COUNT +
+ * NONFINITE at kernel entry; a non-finite row stores NaN; slots >= capacity are not written while the counters still advance
+ * (the reader sees COUNT + NONFINITE > capacity).  One launch, one workgroup of 256 threads per cell, fixed-order reduction, no
+ * atomics: updates of one record are ordered by the stream, and equal updates leave equal bits.  Nothing is allocated and
+ * nothing synchronises (capturable).  NULL preds / gt / record, iters / dirs / batch < 1, capacity < 0 and err_out with
+ * capacity == 0 are rejected before any HIP call. */
+enum { MVG_GAZE_ERR_COUNT = 0, MVG_GAZE_ERR_SUM = 1, MVG_GAZE_ERR_SUMSQ = 2, MVG_GAZE_ERR_MAX = 3, MVG_GAZE_ERR_NONFINITE = 4,
+       MVG_GAZE_ERR_FIELDS = 5 };
+int mvg_gaze_error_update(const float *preds, const float *gt, int iters, int dirs, int batch, double *record, float *err_out,
+                          int64_t capacity, void *stream);
+
 /* ---------------------------------------------------------------- stereo pair index (HOST)
  * GazeDataset.__init__'s idx_to_kv build, dataset/gaze.py:39-73, driven by CPython's
  * random.seed(int)/random.choice stream (MT19937 + getrandbits rejection).  Pure host integer
@@ -999,7 +1020,8 @@ const char *mvg_session_tensor_name(const mvg_session *s, int i);
 int64_t mvg_session_tensor_numel(const mvg_session *s, int i);
 /* Bytes of the workspace mvg_session_bind wants (host only). */
 size_t mvg_session_workspace_bytes(const mvg_session *s);
-/* Library calls one mvg_session_forward queues (host only; a stream-K / split-K GEMM adds its fix-up kernel on the device). */
+/* Library calls one mvg_session_forward queues (host only; a stream-K / split-K GEMM adds its fix-up kernel on the device):
+ * the plan's steps, and one more while mvg_session_set_error_record holds a record. */
 int mvg_session_launches(const mvg_session *s);
 /* The plan's steps in the order mvg_session_forward queues them (host only, both forms): how many, and the entry point step
  * i calls, without the "mvg_" prefix, e.g. "conv_fprop_bf16_affine" (a step that records ranges still names the plain entry
@@ -1031,6 +1053,14 @@ int mvg_session_forward(mvg_session *s, const void *const *host_view_ptrs, const
 int mvg_session_num_range_units(const mvg_session *s);
 const char *mvg_session_range_unit_name(const mvg_session *s, int i);
 int mvg_session_set_range_record(mvg_session *s, uint32_t *record_dev);
+/* The gaze error record of a session (host only: the pointers are only stored; both compute forms).  gt_dev: the caller's static
+ * fp32 [D][batch][2] label buffer (row d = the labels of the view direction d predicts for), refilled before each forward;
+ * record_dev, err_out, capacity: as mvg_gaze_error_update takes them, cells = num_iter * D.  record_dev = NULL (the default)
+ * restores the plain forward exactly.  With a record mvg_session_forward queues one mvg_gaze_error_update over its own preds
+ * after the plan's last step: the four outputs are unchanged, still no synchronisation and no allocation; the plan - its steps,
+ * their names, mvg_session_num_steps - is untouched, and mvg_session_launches reports one more.  A record without gt_dev,
+ * capacity < 0 and err_out with capacity == 0 are rejected. */
+int mvg_session_set_error_record(mvg_session *s, const float *gt_dev, double *record_dev, float *err_out, int64_t capacity);
 
 #ifdef __cplusplus
 }

@@ -22,9 +22,10 @@ def __getattr__(name):
         "build_pair_index": "pair_index",
         "GradAllReducer": "dp",
         "Adam": "optim",
+        "AngularErrorMeter": "metrics",
     }
     if name in lazy:
         return getattr(importlib.import_module("." + lazy[name], __name__), name)
-    if name in ("model", "losses", "geometry", "pair_index", "dp", "ops", "backbone", "heads", "_lib", "optim"):
+    if name in ("model", "losses", "geometry", "pair_index", "dp", "ops", "backbone", "heads", "_lib", "optim", "metrics"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -15,6 +15,8 @@ K_FAMILIES = 18
 ABI_VERSION = 13
 SESSION_FP32, SESSION_BF16 = 0, 1         # MVG_SESSION_FP32 / MVG_SESSION_BF16 (mvg_session_create_ex)
 ADAM_MAX_SEGMENTS = 16                    # MVG_ADAM_MAX_SEGMENTS: segments per launch of mvg_adam_step_segments
+# MVG_GAZE_ERR_*: the fields of one cell of mvg_gaze_error_update's record (doubles)
+GAZE_ERR_COUNT, GAZE_ERR_SUM, GAZE_ERR_SUMSQ, GAZE_ERR_MAX, GAZE_ERR_NONFINITE, GAZE_ERR_FIELDS = range(6)
 
 
 class ConvDesc(C.Structure):
@@ -267,6 +269,9 @@ SIGNATURES = {
     "mvg_session_compute": (_I, [_P]),
     "mvg_session_num_steps": (_I, [_P]),
     "mvg_session_step_name": (C.c_char_p, [_P, _I]),
+    # gaze error meter (metrics.AngularErrorMeter): float64 angular error accumulated on the device, and its session hook
+    "mvg_gaze_error_update": (_I, [_P, _P, _I, _I, _I, _P, _P, _I64, _P]),
+    "mvg_session_set_error_record": (_I, [_P, _P, _P, _P, _I64]),
 }
 
 _lib = None

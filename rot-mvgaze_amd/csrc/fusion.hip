@@ -690,6 +690,79 @@ __global__ __launch_bounds__(256) void gaze_loss_multi_kernel(const float *__res
   if (threadIdx.x == 0) loss[0] = (float)(sh[0] + sh[1] + sh[2] + sh[3]);
 }
 
+// ---- gaze error meter --------------------------------------------------------------------------
+// The evaluation metric (utils/math.py:105-120, angular_error_numpy) in double, accumulated on the device: one workgroup per
+// (iteration, direction) cell of the record, threads stride over the batch, fixed-order reduction (wave_sum_d, four wave
+// partials, thread 0 adds into the cell) - no atomics; updates of a record are ordered by the stream.  The one deviation
+// from the reference: the similarity is clamped to [-1, 1] before acos (pred == gt rounds to 1 + 2e-16 there and gives NaN).
+// A row with a NaN / Inf input counts in NONFINITE only.  err_out (optional) [cells][capacity] fp32: row b goes to slot
+// seen_before + b of its cell's row, seen_before = COUNT + NONFINITE as every thread reads it before the barrier in front of
+// thread 0's write; slots >= capacity are not written.
+__device__ __forceinline__ double wave_max_d(double v) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o, 64));
+  return v;
+}
+__device__ __forceinline__ double dot3_d(double x0, double x1, double x2, double y0, double y1, double y2) {
+  return fma(x2, y2, fma(x1, y1, x0 * y0));
+}
+__global__ __launch_bounds__(256) void gaze_error_update_kernel(const float *__restrict__ pred, const float *__restrict__ gt, int dirs,
+                                                                int batch, double *record, float *__restrict__ err_out,
+                                                                long long capacity) {
+  __shared__ double sh[5][4];
+  const int cell = blockIdx.x, d = cell % dirs;
+  double *rec = record + (long long)cell * MVG_GAZE_ERR_FIELDS;
+  const long long seen_before = (long long)(rec[MVG_GAZE_ERR_COUNT] + rec[MVG_GAZE_ERR_NONFINITE]);
+  const float *p = pred + (long long)cell * batch * 2, *g = gt + (long long)d * batch * 2;
+  float *eo = err_out ? err_out + (long long)cell * capacity : nullptr;
+  double cnt = 0.0, sum = 0.0, sumsq = 0.0, mx = 0.0, bad = 0.0;
+  for (int b = threadIdx.x; b < batch; b += 256) {
+    const float ppf = p[2 * b], pyf = p[2 * b + 1], gpf = g[2 * b], gyf = g[2 * b + 1];
+    const long long slot = seen_before + b;
+    if (!(isfinite(ppf) && isfinite(pyf) && isfinite(gpf) && isfinite(gyf))) {
+      bad += 1.0;
+      if (eo && slot >= 0 && slot < capacity) eo[slot] = __builtin_nanf("");
+      continue;
+    }
+    const double pp = (double)ppf, py = (double)pyf, gp = (double)gpf, gy = (double)gyf;
+    const double cpp = cos(pp), spp = sin(pp), cgp = cos(gp), sgp = sin(gp);
+    const double a0 = cpp * sin(py), a1 = spp, a2 = cpp * cos(py);
+    const double b0 = cgp * sin(gy), b1 = sgp, b2 = cgp * cos(gy);
+    // (one dot3 for all three products: with pred == gt they are the same bits s, sqrt rounds so that fl(sqrt(s))^2 <= s near 1,
+    // the similarity is >= 1 and the clamp makes the row exactly 0)
+    const double ab = dot3_d(a0, a1, a2, b0, b1, b2);
+    const double na = fmax(sqrt(dot3_d(a0, a1, a2, a0, a1, a2)), 1e-7), nb = fmax(sqrt(dot3_d(b0, b1, b2, b0, b1, b2)), 1e-7);
+    const double sim = fmin(fmax(ab / (na * nb), -1.0), 1.0);
+    const double e = acos(sim) * 180.0 / 3.14159265358979323846;
+    cnt += 1.0;
+    sum += e;
+    sumsq += e * e;
+    mx = fmax(mx, e);
+    if (eo && slot >= 0 && slot < capacity) eo[slot] = (float)e;
+  }
+  cnt = wave_sum_d(cnt);
+  sum = wave_sum_d(sum);
+  sumsq = wave_sum_d(sumsq);
+  mx = wave_max_d(mx);
+  bad = wave_sum_d(bad);
+  if ((threadIdx.x & 63) == 0) {
+    const int w = threadIdx.x >> 6;
+    sh[0][w] = cnt;
+    sh[1][w] = sum;
+    sh[2][w] = sumsq;
+    sh[3][w] = mx;
+    sh[4][w] = bad;
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    rec[MVG_GAZE_ERR_COUNT] += sh[0][0] + sh[0][1] + sh[0][2] + sh[0][3];
+    rec[MVG_GAZE_ERR_SUM] += sh[1][0] + sh[1][1] + sh[1][2] + sh[1][3];
+    rec[MVG_GAZE_ERR_SUMSQ] += sh[2][0] + sh[2][1] + sh[2][2] + sh[2][3];
+    rec[MVG_GAZE_ERR_MAX] = fmax(rec[MVG_GAZE_ERR_MAX], fmax(fmax(sh[3][0], sh[3][1]), fmax(sh[3][2], sh[3][3])));
+    rec[MVG_GAZE_ERR_NONFINITE] += sh[4][0] + sh[4][1] + sh[4][2] + sh[4][3];
+  }
+}
+
 // Adam with its step counter and learning rate on the DEVICE (a captured step replays with nothing from the host):
 // adam_tick_kernel advances state = {step, bias correction 1, sqrt(bias correction 2)} (one thread), adam_dev_kernel is
 // adam_kernel reading lr from hyper[0] and the corrections from state.
@@ -1223,6 +1296,23 @@ int mvg_gaze_angular_loss_multi(const float *pred, const float *gt, int iters, i
   ProfScope ps(MVG_K_LOSS, st, 0.0, 24.0 * iters * dirs * batch);
   hipLaunchKernelGGL(gaze_loss_multi_kernel, dim3(1), dim3(256), 0, st, pred, gt, iters, dirs, batch, lw, loss, dpred);
   return check_launch("gaze_angular_loss_multi");
+}
+
+int mvg_gaze_error_update(const float *preds, const float *gt, int iters, int dirs, int batch, double *record, float *err_out,
+                          int64_t capacity, void *stream) {
+  // (every check comes before the first HIP call: they run on a machine without a GPU)
+  MVG_REQUIRE(preds && gt && record, "gaze_error_update: null preds, gt or record");
+  MVG_REQUIRE(iters >= 1 && dirs >= 1 && batch >= 1, "gaze_error_update: iters, dirs and batch must be >= 1 (got %d, %d, %d)", iters, dirs,
+              batch);
+  MVG_REQUIRE((int64_t)iters * dirs <= INT32_MAX, "gaze_error_update: iters * dirs = %lld cells exceed one grid",
+              (long long)iters * dirs);
+  MVG_REQUIRE(capacity >= 0, "gaze_error_update: capacity must be >= 0 (got %lld)", (long long)capacity);
+  MVG_REQUIRE(!err_out || capacity > 0, "gaze_error_update: err_out needs capacity > 0");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_LOSS, st, 0.0, (double)iters * dirs * (batch * (err_out ? 20.0 : 16.0) + 80.0));
+  hipLaunchKernelGGL(gaze_error_update_kernel, dim3((unsigned)(iters * dirs)), dim3(256), 0, st, preds, gt, dirs, batch, record, err_out,
+                     (long long)capacity);
+  return check_launch("gaze_error_update");
 }
 
 int mvg_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev, float *state3,

@@ -1003,7 +1003,7 @@ int64_t mvg_session_tensor_numel(const mvg_session *s, int i) {
 
 size_t mvg_session_workspace_bytes(const mvg_session *s) { return s ? (size_t)s->plan.workspace_bytes : 0; }
 
-int mvg_session_launches(const mvg_session *s) { return s ? (int)s->plan.steps.size() : -1; }
+int mvg_session_launches(const mvg_session *s) { return s ? (int)s->plan.steps.size() + (s->err_record ? 1 : 0) : -1; }
 
 int mvg_session_compute(const mvg_session *s) { return s ? s->plan.compute : -1; }
 
@@ -1031,6 +1031,26 @@ int mvg_session_set_range_record(mvg_session *s, uint32_t *record_dev) {
     return 2;
   }
   s->range_record = record_dev;
+  return 0;
+}
+
+int mvg_session_set_error_record(mvg_session *s, const float *gt_dev, double *record_dev, float *err_out, int64_t capacity) {
+  if (!s) {
+    mvg::set_error("session_set_error_record: null session");
+    return 2;
+  }
+  if (record_dev && !gt_dev) {
+    mvg::set_error("session_set_error_record: a record needs the label buffer gt_dev");
+    return 2;
+  }
+  if (capacity < 0 || (err_out && capacity == 0)) {
+    mvg::set_error("session_set_error_record: capacity must be >= 0, and > 0 with err_out (got %lld)", (long long)capacity);
+    return 2;
+  }
+  s->err_gt = record_dev ? gt_dev : nullptr;
+  s->err_record = record_dev;
+  s->err_out = record_dev ? err_out : nullptr;
+  s->err_capacity = record_dev ? capacity : 0;
   return 0;
 }
 

@@ -105,4 +105,9 @@ struct mvg_session {
   void *bound_stream = nullptr;
   bool bound = false;
   uint32_t *range_record = nullptr;             // mvg_session_set_range_record: device words, or null (no record)
+  // mvg_session_set_error_record: what mvg_gaze_error_update takes after the last step; err_record null = no update
+  const float *err_gt = nullptr;
+  double *err_record = nullptr;
+  float *err_out = nullptr;
+  int64_t err_capacity = 0;
 };

@@ -10,7 +10,7 @@ from typing import Optional
 
 import torch
 
-from ._lib import ConvDesc, K_FAMILIES, ProfEntry, check, lib
+from ._lib import ConvDesc, GAZE_ERR_FIELDS, K_FAMILIES, ProfEntry, check, lib
 
 Tensor = torch.Tensor
 
@@ -977,6 +977,17 @@ def split_colsum(g, rows, cols, absmax, out_sp, db=None, accumulate=False):
 def gaze_angular_loss_multi(pred, gt, iters, dirs, batch, weights, loss, dpred=None):
     w = (C.c_float * (iters * dirs))(*[float(x) for x in weights])
     check(lib().mvg_gaze_angular_loss_multi(_p(pred), _p(gt), iters, dirs, batch, w, _p(loss), _p(dpred), _s()), "gaze_angular_loss_multi")
+
+
+def gaze_error_update(preds, gt, iters, dirs, batch, record, err_out=None, capacity=0):
+    """record [iters*dirs][GAZE_ERR_FIELDS] (float64) += the float64 angular errors of preds [iters][dirs][batch][2] against
+    gt [dirs][batch][2]; err_out (optional, fp32 [iters*dirs][capacity]) receives the per-row errors.  One launch, no sync."""
+    assert preds.dtype == torch.float32 and gt.dtype == torch.float32 and preds.is_contiguous() and gt.is_contiguous()
+    assert preds.numel() == iters * dirs * batch * 2 and gt.numel() == dirs * batch * 2
+    assert record.is_cuda and record.dtype == torch.float64 and record.is_contiguous() and record.numel() == iters * dirs * GAZE_ERR_FIELDS
+    assert err_out is None or (err_out.dtype == torch.float32 and err_out.is_contiguous() and err_out.numel() == iters * dirs * capacity)
+    check(lib().mvg_gaze_error_update(_p(preds), _p(gt), iters, dirs, batch, record.data_ptr(), _p(err_out), int(capacity), _s()),
+          "gaze_error_update")
 
 
 def adam_step_segments(param, grad, exp_avg, exp_avg_sq, segments):

@@ -23,12 +23,14 @@ import torch
 from . import ops
 from ._lib import SESSION_BF16, SESSION_FP32, SessionCfg, check, lib
 from .arch import NUM_FEAT_VEC, RANGE_OVER_BITS
+from .heads import directed_pairs
 
 Tensor = torch.Tensor
 
 
 class InferenceSession:
-    """``InferenceSession(model, views, batch, height, width, raw_hw=None, input_bgr=False, range_record=False, compute=None)``.
+    """``InferenceSession(model, views, batch, height, width, raw_hw=None, input_bgr=False, range_record=False, compute=None,
+    meter=None)``.
 
     model: a ``MultiViewGaze`` / ``FeatRotationSymm`` on the GPU (default, ``share_weights`` or ``ignore_rotmat`` variant).
     compute: None - the fp32 form, ``model.compute_dtype`` must be float32; ``torch.bfloat16`` - the bf16 inference form,
@@ -40,10 +42,14 @@ class InferenceSession:
 
     range_record=True: every forward also leaves the activation range record of the backbone's sp tensors (one word per name in
     ``range_unit_names``; same launches, same outputs, still no synchronisation) for ``range_report()`` / ``overflowed()``.  A
-    session has no fallback: on an overflow build one over a model with ``_backbone.split = False``."""
+    session has no fallback: on an overflow build one over a model with ``_backbone.split = False``.
+
+    meter: a ``metrics.AngularErrorMeter(num_iter, views * (views - 1), ...)``: every ``run(..., gt=labels)`` also adds the forward's
+    gaze errors to the meter's device record (``mvg_session_set_error_record``: one more launch after the plan's last step, same
+    four outputs, still no synchronisation).  The session owns the static label buffer the hook reads."""
 
     def __init__(self, model, views: int, batch: int, height: int, width: int, raw_hw: Optional[Tuple[int, int]] = None,
-                 input_bgr: bool = False, range_record: bool = False, compute: Optional[torch.dtype] = None) -> None:
+                 input_bgr: bool = False, range_record: bool = False, compute: Optional[torch.dtype] = None, meter=None) -> None:
         v = model._variant
         if v.encode_rotmat or v.share_feature:
             raise ValueError("InferenceSession: the encode_rotmat and share_feature variants are not served by the native session")
@@ -83,7 +89,33 @@ class InferenceSession:
             with torch.cuda.device(self.device):
                 self._range_record = torch.zeros(len(self.range_unit_names), dtype=torch.int32, device=self.device)
             check(lib().mvg_session_set_range_record(h, C.c_void_p(self._range_record.data_ptr())), "session_set_range_record")
+        self.meter = None
+        self._gt: Optional[Tensor] = None
+        if meter is not None:
+            self.bind_meter(meter)
         self.refresh()
+
+    # ---------------------------------------------------------------- gaze error meter
+    def bind_meter(self, meter) -> None:
+        """Attach ``meter`` (None: detach - the plain forward again).  Host only: the library stores four pointers."""
+        if self._h is None:
+            raise RuntimeError("InferenceSession is closed")
+        if meter is None:
+            check(lib().mvg_session_set_error_record(self._h, None, None, None, 0), "session_set_error_record")
+            self.meter = None
+        else:
+            if (meter.num_iter, meter.dirs) != (self.num_iter, self.dirs):
+                raise ValueError(f"InferenceSession: the meter holds {meter.num_iter} x {meter.dirs} cells, the session's forward has "
+                                 f"{self.num_iter} iterations x {self.dirs} directions")
+            meter._ensure(self.device)
+            if self._gt is None:
+                with torch.cuda.device(self.device):
+                    self._gt = torch.zeros(self.dirs, self.batch, 2, dtype=torch.float32, device=self.device)
+            check(lib().mvg_session_set_error_record(self._h, C.c_void_p(self._gt.data_ptr()), C.c_void_p(meter.record.data_ptr()),
+                                                     C.c_void_p(meter.err_out.data_ptr()) if meter.err_out is not None else None,
+                                                     meter.capacity), "session_set_error_record")
+            self.meter = meter
+        self.launches = int(lib().mvg_session_launches(self._h))
 
     # ---------------------------------------------------------------- weights
     def refresh(self) -> None:
@@ -116,10 +148,11 @@ class InferenceSession:
         mk = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
         return mk(V, B, self.fc_dim), mk(V, B, 3, NUM_FEAT_VEC), mk(I, D, B, 3, NUM_FEAT_VEC), mk(I, D, B, 2)
 
-    def run(self, imgs: Sequence[Tensor], rot: Tensor, out=None):
+    def run(self, imgs: Sequence[Tensor], rot: Tensor, out=None, gt: Optional[Tensor] = None):
         """imgs: V tensors (fp32 ``[B,3,H,W]``, or uint8 ``[B,h,w,3]`` with ``raw_hw``); rot fp32 ``[B,V,3,3]``.  Returns
         ``(img_feat [V,B,Cf], lifted [V,B,3,512], feats [I,D,B,3,512], preds [I,D,B,2])`` as ``run_views`` does; ``out``
-        (from ``empty_outputs``) receives them without any allocation.  Queued on the current stream."""
+        (from ``empty_outputs``) receives them without any allocation.  Queued on the current stream.  gt ``[B,V,2]``: with a meter,
+        the labels of this batch, copied (stream-ordered, one small copy per direction) into the session's static label buffer."""
         if self._h is None:
             raise RuntimeError("InferenceSession is closed")
         V, B = self.views, self.batch
@@ -141,6 +174,13 @@ class InferenceSession:
                 if tuple(o.shape) != ref or o.dtype != torch.float32 or o.device != self.device or not o.is_contiguous():
                     raise ValueError(f"InferenceSession.run: an output must be a contiguous fp32 tensor of shape {ref}")
         img_feat, lifted, feats, preds = out
+        if (gt is None) != (self.meter is None):
+            raise ValueError("InferenceSession.run: gt goes with a meter (a session with a meter needs every batch's labels)")
+        if gt is not None:
+            if tuple(gt.shape) != (B, V, 2) or gt.device != self.device:
+                raise ValueError(f"InferenceSession.run: gt must have shape {(B, V, 2)} on {self.device}")
+            for d, v in enumerate(directed_pairs(V)[0]):       # slices (metrics.build_gt_dir): a list index would synchronise
+                self._gt[d].copy_(gt[:, v])
         with torch.cuda.device(self.device):
             check(lib().mvg_session_forward(self._h, self._views_arr, C.c_void_p(rot.data_ptr()), C.c_void_p(img_feat.data_ptr()),
                                             C.c_void_p(lifted.data_ptr()), C.c_void_p(feats.data_ptr()), C.c_void_p(preds.data_ptr()),
@@ -174,6 +214,7 @@ class InferenceSession:
             self._h = None
             self._workspace = None
             self._range_record = None
+            self.meter = self._gt = None
 
     def __del__(self):
         try:
