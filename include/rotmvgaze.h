@@ -368,7 +368,8 @@ int mvg_multi_erase_nchw(float *img, const float *masks, const int32_t *grid, in
  * torchvision computes on the PIL image - Pillow's ImageEnhance.{Brightness, Contrast, Color} (ImagingBlend against
  * a degenerate image; every op quantises to uint8) in a per-image order, then Image.transform(AFFINE, NEAREST) on its
  * scale-only path (per-axis source-index tables built by repeated double additions; outside = 0).
- * One record per image, in a DEVICE array (the draws stay on the host: rot_mvgaze_amd/augment.py TrainAugment). */
+ * One record per image, in a DEVICE array: packed on the host from the reference's RNG calls in its order (the default,
+ * rot_mvgaze_amd/augment.py TrainAugment.draw) or written on the device by mvg_augment_draw below. */
 typedef struct mvg_augment_rec {
   float factor[3];   /* brightness, contrast, saturation factor (1 = identity) */
   int32_t order[3];  /* the ops in the order applied: a permutation of 0 brightness, 1 contrast, 2 saturation */
@@ -398,6 +399,27 @@ int mvg_augment_u8hwc_bf16(const uint8_t *src, const mvg_augment_rec *recs, cons
                            uint16_t *dst_nhwc8, uint16_t *dst_rw, const float *masks, const int32_t *grid, int gmax,
                            int n, int h, int w, float mean0, float mean1, float mean2, float std0, float std1,
                            float std2, int swap_rb, void *stream);
+/* The per-image draws of that transform made on the device: one launch writes the n records, and with an erase the
+ * keep-masks [n][gmax*gmax] and grid sizes [n], that the two entry points above read - no host draw, no copy, no
+ * synchronisation, so an augmented step can be captured.  The distributions are the reference's; the RNG stream is not
+ * (TrainAugment(draws="host") replays that).  cfg: a host mvg_augment_draw_cfg (rotmvgaze_augment_draw.h), read during
+ * the call.  masks and grid may both be NULL (no erase: gmax is then 0); with them, gmax == (int)(1.0 / cfg->dot_lo) <= 64.
+ * Generator: Philox4x32-10, key (seed low word, seed high word), counter (image i, block j, launch counter low word,
+ * high word).  The launch counter is a uint64 in DEVICE memory at counter_dev: every draw of a launch uses the value it
+ * had when the launch began, and the launch adds one to it in stream order - a replayed graph draws afresh on every
+ * replay, and (seed, counter) reproduces a launch.  The word assignment does not depend on which ops are enabled:
+ *   block 0: order, brightness, contrast, saturation     block 1: tx, ty, scale, erase-apply
+ *   block 2: dot size, proportion, two unused            block 3 + c/4, word c%4: mask cell c = row * g + column
+ * Arithmetic, every operation rounded on its own (no fused multiply-add), so that it can be restated exactly:
+ *   u = (float)(x >> 8) * 2^-24;  order = the k-th permutation of (0, 1, 2) in lexicographic order, k = (x * 6) >> 32;
+ *   a factor = u * (hi - lo) + lo in fp32 (torch's uniform_);  tx = (int)rintf(u * (2 max_dx) - max_dx), ty likewise;
+ *   the scale s in fp32 like a factor, then in doubles a0 = a4 = 1.0 / s, cx = a0 * (-w/2 - tx) + w/2, cy likewise with h;
+ *   the erase applies unless (double)u > p;  dot = dot_lo + (dot_hi - dot_lo) * (double)u,  g = (int)(1.0 / dot) clamped
+ *   to [1, gmax],  prop likewise from the proportion range,  cell keep = (double)u > prop ? 1 : 0.
+ * Every byte of recs, masks and grid is written by every launch (they may arrive uninitialised): mask cells past g*g
+ * are 0, and an image that is not erased gets grid 0 and an all-zero mask slot.  (Added under ABI v13: additive.) */
+int mvg_augment_draw(mvg_augment_rec *recs, float *masks, int32_t *grid, int gmax, int n, int h, int w, const void *cfg,
+                     uint64_t seed, uint64_t *counter_dev, void *stream);
 
 /* ---------------------------------------------------------------- geometry
  * rotation_matrix_2d utils/math.py:188-219; relative rotations rot_mv.py:193-194. */

@@ -176,6 +176,8 @@ SIGNATURES = {
     "mvg_multi_erase_nchw": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "mvg_augment_u8hwc": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
     "mvg_augment_u8hwc_bf16": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _F, _F, _F, _F, _F, _I, _P]),
+    # the device draws of TrainAugment(draws="device"): cfg is a host mvg_augment_draw_cfg (augment.DRAW_CFG_DTYPE)
+    "mvg_augment_draw": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, C.c_uint64, _P, _P]),
     "mvg_rotation_matrix_2d": (_I, [_P, _P, _I, _I, _P]),
     "mvg_relative_rotation": (_I, [_P, _P, _P, _P, _I, _I, _I, _P]),
     "mvg_rotcat_fwd": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P]),

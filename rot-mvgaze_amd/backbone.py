@@ -754,7 +754,8 @@ class Backbone:
         row-window form (no NHWC image is built); else the NHWC image padded to 4 (bf16: 8) channels, from raw uint8 patches
         or NCHW fp32 - and the windows from that image for raw input with a row-window stem.  augment (training steps on raw
         patches: an augment.TrainAugment): its launch - ColorJitter, RandomAffine, ToTensor, Normalize, erase - takes the
-        place of the preprocess launch; the draws are host work, taken in view order, then image order.  On the bf16 path
+        place of the preprocess launch; the draws are host work, taken in view order, then image order - or, with a capturable
+        augment (draws="device"), one more launch per view (mvg_augment_draw) and no host work at all.  On the bf16 path
         that launch stores the stem's operand itself - the row windows when the stem runs in row-window form, else the NHWC8
         image - rounded once from the fp32 value: one launch per view, no fp32 image in between.
         (The bf16 branch without a row-window stem is restated by csrc/session_plan.cpp's build_bf16.)"""
@@ -774,15 +775,19 @@ class Backbone:
                 if tuple(im.shape[1:3]) != (H, W):
                     raise ValueError(f"input_augment: {im.shape[1]} x {im.shape[2]} patches with input_size {H} x {W}: a resize "
                                      "after the augmentation is not served (set model.input_size = None, or feed patches of that size)")
-                if torch.cuda.is_current_stream_capturing():
+                if getattr(augment, "capturable", False):       # draws="device": one more launch, nothing on the host
+                    draws = augment.draw_device(B, H, W, dev)
+                elif torch.cuda.is_current_stream_capturing():
                     raise RuntimeError("input_augment draws on the host for every step and cannot be captured (graph.GraphedStep): "
                                        "augment outside the captured step (TrainAugment.apply) and feed the result")
-                if bf and direct:
-                    augment.launch(im, augment.draw(B, H, W), None, None, input_bgr, dst_rw=x0[v])
-                elif bf:
-                    augment.launch(im, augment.draw(B, H, W), None, None, input_bgr, dst_nhwc8=x0[v])
                 else:
-                    augment.launch(im, augment.draw(B, H, W), None, x0[v], input_bgr)
+                    draws = augment.draw(B, H, W)
+                if bf and direct:
+                    augment.launch(im, draws, None, None, input_bgr, dst_rw=x0[v])
+                elif bf:
+                    augment.launch(im, draws, None, None, input_bgr, dst_nhwc8=x0[v])
+                else:
+                    augment.launch(im, draws, None, x0[v], input_bgr)
                 continue
             if raw:                             # (bf16: no fp32 image in between)
                 prep = ops.preprocess_u8hwc_resize_bf16 if bf else ops.preprocess_u8hwc_resize

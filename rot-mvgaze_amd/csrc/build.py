@@ -18,6 +18,7 @@ def _stale(obj, src):
         return True
     deps = [src, os.path.join(HERE, "common.h"), os.path.join(HERE, "conv_shared.h"),
             os.path.join(HERE, "elem.h"), os.path.join(HERE, "bn_math.h"), os.path.join(HERE, "bf16_tile.h"), os.path.join(HERE, "conv_bf16_gemm.inc"), os.path.join(HERE, "conv_split_igemm.inc"), os.path.join(HERE, "session_plan.h"), os.path.join(HERE, "..", "..", "include", "rotmvgaze.h"),
+            os.path.join(HERE, "..", "..", "include", "rotmvgaze_augment_draw.h"),
             os.path.abspath(__file__)]
     return any(os.path.exists(d) and os.path.getmtime(d) > os.path.getmtime(obj) for d in deps)
 

@@ -3,6 +3,7 @@
 
 #include "common.h"
 #include "elem.h"
+#include "../../include/rotmvgaze_augment_draw.h"
 
 namespace mvg {
 
@@ -527,6 +528,101 @@ __global__ __launch_bounds__(kAugThreads) void augment_u8_bf16_kernel(const unsi
                                             s2, swap_rb);
 }
 
+// The draws of those launches made on the device (mvg_augment_draw; the word assignment and the arithmetic are stated
+// in the header and restated in NumPy by tests/augment_draw_ref.py).  One workgroup: a wave per image in turn - every
+// lane computes the image's record (three Philox blocks, wave-uniform), lane 0 stores it, the lanes share the mask's
+// blocks of four cells.  Every draw uses the launch counter as it stood when the launch began: all threads read it,
+// then a barrier, then thread 0 stores counter + 1.
+constexpr int kDrawThreads = 1024;
+constexpr int kDrawMaxGrid = 64;
+
+__device__ __forceinline__ uint4 philox4x32_10(uint4 c, unsigned k0, unsigned k1) {
+#pragma unroll
+  for (int r = 0; r < 10; ++r) {
+    const unsigned hi0 = __umulhi(0xD2511F53u, c.x), lo0 = 0xD2511F53u * c.x;
+    const unsigned hi1 = __umulhi(0xCD9E8D57u, c.z), lo1 = 0xCD9E8D57u * c.z;
+    c = make_uint4(hi1 ^ c.y ^ k0, lo1, hi0 ^ c.w ^ k1, lo0);
+    k0 += 0x9E3779B9u;
+    k1 += 0xBB67AE85u;
+  }
+  return c;
+}
+// Products that feed an add: rounded values of their own (the empty asm keeps the contraction away: see aug_blend).
+__device__ __forceinline__ float draw_mul(float a, float b) {
+  float p = __fmul_rn(a, b);
+  asm volatile("" : "+v"(p));
+  return p;
+}
+__device__ __forceinline__ double draw_mul(double a, double b) {
+  double p = __dmul_rn(a, b);
+  asm volatile("" : "+v"(p));
+  return p;
+}
+__device__ __forceinline__ float draw_u01(unsigned x) { return (float)(x >> 8) * 0x1p-24f; }      // exact
+__device__ __forceinline__ float draw_uniform(unsigned x, float lo, float hi) {                   // torch's uniform_
+  return __fadd_rn(draw_mul(draw_u01(x), __fsub_rn(hi, lo)), lo);
+}
+__device__ __forceinline__ double draw_uniform(unsigned x, double lo, double hi) {                 // numpy's uniform
+  return __dadd_rn(lo, draw_mul(__dsub_rn(hi, lo), (double)draw_u01(x)));
+}
+
+__global__ __launch_bounds__(kDrawThreads) void augment_draw_kernel(mvg_augment_rec *__restrict__ recs, float *__restrict__ masks,
+                                                                    int *__restrict__ grid, int gmax, int n, int h, int w,
+                                                                    mvg_augment_draw_cfg cfg, unsigned k0, unsigned k1,
+                                                                    unsigned long long *counter) {
+  const unsigned long long launch = *counter;
+  const unsigned c2 = (unsigned)launch, c3 = (unsigned)(launch >> 32);
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  const int cells = gmax * gmax;
+  for (int i = wave; i < n; i += kDrawThreads / 64) {
+    const uint4 b0 = philox4x32_10(make_uint4((unsigned)i, 0u, c2, c3), k0, k1);
+    const uint4 b1 = philox4x32_10(make_uint4((unsigned)i, 1u, c2, c3), k0, k1);
+    int g = 0;
+    double prop = 0.0;
+    if (masks && cfg.erase && !((double)draw_u01(b1.w) > cfg.p)) {
+      const uint4 b2 = philox4x32_10(make_uint4((unsigned)i, 2u, c2, c3), k0, k1);
+      g = (int)__ddiv_rn(1.0, draw_uniform(b2.x, cfg.dot_lo, cfg.dot_hi));
+      g = g < 1 ? 1 : (g > gmax ? gmax : g);
+      prop = draw_uniform(b2.y, cfg.prop_lo, cfg.prop_hi);
+    }
+    if (lane == 0) {
+      const int k = (int)(((unsigned long long)b0.x * 6ull) >> 32);        // the k-th permutation of (0, 1, 2)
+      const int o0 = k >> 1, o1 = (k & 1) ? (o0 == 2 ? 1 : 2) : (o0 == 0 ? 1 : 0);
+      mvg_augment_rec r;
+      r.order[0] = o0;
+      r.order[1] = o1;
+      r.order[2] = 3 - o0 - o1;
+      r.factor[0] = draw_uniform(b0.y, cfg.factor_lo[0], cfg.factor_hi[0]);
+      r.factor[1] = draw_uniform(b0.z, cfg.factor_lo[1], cfg.factor_hi[1]);
+      r.factor[2] = draw_uniform(b0.w, cfg.factor_lo[2], cfg.factor_hi[2]);
+      const int tx = (int)rintf(__fsub_rn(draw_mul(draw_u01(b1.x), __fmul_rn(2.f, cfg.max_dx)), cfg.max_dx));
+      const int ty = (int)rintf(__fsub_rn(draw_mul(draw_u01(b1.y), __fmul_rn(2.f, cfg.max_dy)), cfg.max_dy));
+      const double s = (double)draw_uniform(b1.z, cfg.scale_lo, cfg.scale_hi);
+      const double inv = __ddiv_rn(1.0, s), x0 = (double)w * 0.5, y0 = (double)h * 0.5;
+      r.a0 = r.a4 = inv;                                                   // augment.inverse_affine's order of operations
+      r.cx = __dadd_rn(draw_mul(inv, __dsub_rn(-x0, (double)tx)), x0);
+      r.cy = __dadd_rn(draw_mul(inv, __dsub_rn(-y0, (double)ty)), y0);
+      recs[i] = r;
+      if (grid) grid[i] = g;
+    }
+    if (masks) {
+      float *slot = masks + (long long)i * cells;
+      for (int j = lane; 4 * j < cells; j += 64) {
+        uint4 m = make_uint4(0u, 0u, 0u, 0u);
+        if (4 * j < g * g) m = philox4x32_10(make_uint4((unsigned)i, 3u + (unsigned)j, c2, c3), k0, k1);
+        const unsigned word[4] = {m.x, m.y, m.z, m.w};
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const int c = 4 * j + e;
+          if (c < cells) slot[c] = c < g * g && (double)draw_u01(word[e]) > prop ? 1.f : 0.f;
+        }
+      }
+    }
+  }
+  __syncthreads();
+  if (threadIdx.x == 0) *counter = launch + 1ull;
+}
+
 }  // namespace mvg
 
 using namespace mvg;
@@ -735,6 +831,28 @@ int mvg_augment_u8hwc_bf16(const uint8_t *src, const mvg_augment_rec *recs, cons
     hipLaunchKernelGGL(augment_u8_bf16_kernel<false>, dim3(n), dim3(kAugThreads), 0, st, src, recs, (uint4 *)dst_nhwc8, (uint4 *)nullptr,
                        masks, grid, gmax, h, w, mean0, mean1, mean2, std0, std1, std2, swap_rb);
   return check_launch("augment_u8hwc_bf16");
+}
+
+int mvg_augment_draw(mvg_augment_rec *recs, float *masks, int32_t *grid, int gmax, int n, int h, int w, const void *cfg,
+                     uint64_t seed, uint64_t *counter_dev, void *stream) {
+  MVG_REQUIRE(recs && counter_dev, "augment_draw: the device records and the device launch counter are required");
+  MVG_REQUIRE(cfg, "augment_draw: cfg is required");
+  MVG_REQUIRE(n > 0 && h > 0 && w > 0, "augment_draw: bad sizes");
+  MVG_REQUIRE((masks == nullptr) == (grid == nullptr), "augment_draw: erase masks and grid come together");
+  const mvg_augment_draw_cfg &c = *(const mvg_augment_draw_cfg *)cfg;
+  MVG_REQUIRE(!c.erase || masks, "augment_draw: cfg->erase is set and the masks are missing");
+  if (masks) {
+    MVG_REQUIRE(c.dot_lo > 0.0 && c.dot_lo <= c.dot_hi, "augment_draw: the dot-size range needs 0 < dot_lo <= dot_hi");
+    MVG_REQUIRE(gmax == (int)(1.0 / c.dot_lo), "augment_draw: gmax is %d, (int)(1.0 / dot_lo) is %d", gmax, (int)(1.0 / c.dot_lo));
+    MVG_REQUIRE(gmax >= 1 && gmax <= kDrawMaxGrid, "augment_draw: a mask grid of %d cells a side is not served (1..%d)", gmax, kDrawMaxGrid);
+  } else {
+    MVG_REQUIRE(gmax == 0, "augment_draw: gmax is %d without masks (0: no erase)", gmax);
+  }
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_LAYOUT, st, 0.0, (double)n * (sizeof(mvg_augment_rec) + (masks ? 4.0 * gmax * gmax + 4.0 : 0.0)));
+  hipLaunchKernelGGL(augment_draw_kernel, dim3(1), dim3(kDrawThreads), 0, st, recs, masks, grid, gmax, n, h, w, c, (unsigned)seed,
+                     (unsigned)(seed >> 32), (unsigned long long *)counter_dev);
+  return check_launch("augment_draw");
 }
 
 int mvg_nhwc4_to_nchw(const float *src, float *dst, int n, int c, int h, int w, void *stream) {

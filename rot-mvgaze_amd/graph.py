@@ -43,7 +43,8 @@ class GraphedStep:
         if optimizer is not None and not getattr(optimizer, "capturable", False):
             raise ValueError("GraphedStep needs rot_mvgaze_amd.optim.Adam(capturable=True): the step counter and the "
                              "learning rate must live on the device")
-        if getattr(model, "input_augment", None) is not None:
+        aug = getattr(model, "input_augment", None)
+        if aug is not None and not getattr(aug, "capturable", False):     # TrainAugment(draws="device") draws in a launch of its own
             raise RuntimeError("GraphedStep: model.input_augment draws on the host for every step and cannot be captured: augment "
                                "outside the step (TrainAugment.apply into the static input) and set input_augment = None")
         self.model, self.optimizer = model, optimizer

@@ -823,6 +823,19 @@ def augment_u8hwc_bf16(src, recs, dst_nhwc8, dst_rw, masks, grid, gmax, n, h, w,
                                        mean[0], mean[1], mean[2], std[0], std[1], std[2], int(swap_rb), _s()), "augment_u8hwc_bf16")
 
 
+def augment_draw(recs, masks, grid, gmax, n, h, w, cfg, seed, counter):
+    """The draws of augment_u8hwc / augment_u8hwc_bf16 made on the device in one launch (mvg_augment_draw): recs uint8
+    [n * 56], masks fp32 [n, gmax*gmax] and grid int32 [n] (or both None, gmax 0) are written in full; cfg: a one-element
+    numpy array of augment.DRAW_CFG_DTYPE (host); seed: 64 bits; counter: the int64 device launch counter, advanced by one."""
+    assert recs.dtype == torch.uint8 and recs.is_contiguous() and recs.numel() == n * 56
+    assert masks is None or (masks.dtype == torch.float32 and masks.is_contiguous() and masks.numel() == n * gmax * gmax)
+    assert grid is None or (grid.dtype == torch.int32 and grid.is_contiguous() and grid.numel() == n)
+    assert counter.is_cuda and counter.dtype == torch.int64 and counter.numel() == 1
+    assert cfg.flags["C_CONTIGUOUS"] and cfg.nbytes == 88
+    check(lib().mvg_augment_draw(_p(recs), _p(masks), _p(grid), gmax, n, h, w, C.c_void_p(cfg.ctypes.data), seed, counter.data_ptr(), _s()),
+          "augment_draw")
+
+
 def preprocess_u8hwc_resize(src, dst, n, h, w, oh, ow, mean, std, swap_rb):
     check(lib().mvg_preprocess_u8hwc_resize(_p(src), _p(dst), n, h, w, oh, ow, mean[0], mean[1], mean[2], std[0], std[1],
                                             std[2], int(swap_rb), _s()), "preprocess_u8hwc_resize")
