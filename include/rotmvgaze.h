@@ -681,6 +681,11 @@ enum { MVG_PLAN_BF16_FPROP = 0, MVG_PLAN_BF16_DGRAD = 1, MVG_PLAN_BF16_DGRAD_BNR
        MVG_PLAN_BF16_LINEAR_FPROP_MIXED = 4, MVG_PLAN_BF16_LINEAR_DGRAD_MIXED = 5 };
 int mvg_conv_plan_query_bf16(const mvg_conv_desc *d, int kind, mvg_conv_plan *out);
 int mvg_conv_wgrad_tile_bf16(const mvg_conv_desc *d, int f32in, int32_t *bm, int32_t *bn, int32_t *incremental);
+/* The stem's folded forms (d = the stem's own descriptor, as mvg_stem_fprop_bf16 takes it): *fwd = the forward's plan of the
+ * folded descriptor (2 cout GEMM columns, K-steps of 64 over 7 taps) and the weight gradient's tile over (2 cout) x 448 with its
+ * pixel addressing (incremental when ho * wo / 2 >= 128).  Every out-pointer may be NULL; launches nothing; 0, or -1 (and a message)
+ * for a descriptor the stem launches reject. */
+int mvg_stem_plan_query_bf16(const mvg_conv_desc *d, mvg_conv_plan *fwd, int32_t *wgrad_bm, int32_t *wgrad_bn, int32_t *wgrad_incremental);
 /* nn.Linear of the fusion block in the bf16 path ("mixed"): activations, gradients, biases and outputs stay
  * fp32 in memory, the operand loaders round to bf16 on the way into LDS and the product runs on the bf16
  * matrix cores against the bf16 weight copies (w_bf16 [fout][fin]; wt_bf16 [fin][fout] for backward-data).
@@ -918,6 +923,13 @@ int mvg_stem_fprop_split(const mvg_conv_desc *d, const void *xw_sp, const void *
 int mvg_stem_wgrad_splits_split(const mvg_conv_desc *d);
 int mvg_stem_wgrad_split(const mvg_conv_desc *d, const void *xw_sp, const void *dy_sp, const float *dy_sinv, float *dw_rw,
                          float *workspace, int splits, int accumulate, void *stream);
+/* What the two stem launches run for `d` (the stem's own descriptor) with the CUs the planners may use now: the forward's tile
+ * (*fwd_bm x *fwd_bn: 128 x 64, 128 x 128, or 256 x 64 from 65536 output rows per group with 64 columns) and K loop (*fwd_stages:
+ * 1, or 2 = the two-stage pipeline, 128 x 128 tiles only), the weight gradient's tile over cout x 224 and its pixel addressing
+ * (as mvg_conv_wgrad_split_tile).  Every out-pointer may be NULL; launches nothing; 0, or -1 (and a message) for a descriptor the
+ * stem launches reject. */
+int mvg_stem_plan_query_split(const mvg_conv_desc *d, int32_t *fwd_bm, int32_t *fwd_bn, int32_t *fwd_stages, int32_t *wgrad_bm,
+                              int32_t *wgrad_bn, int32_t *wgrad_incremental);
 int mvg_bn_relu_maxpool_bwd_reduce_split(const float *g_pooled, const uint8_t *argmax, const float *y, const float *mean,
                                          const float *invstd, const float *scale, const float *shift, int groups,
                                          int n_per_group, int h, int w, int c, int ho, int wo, float *s1, float *s2,

@@ -135,6 +135,7 @@ SIGNATURES = {
     "mvg_stem_fprop_split": (_I, [_D, _P, _P, _P, _P, _P, _P]),
     "mvg_stem_wgrad_splits_split": (_I, [_D]),
     "mvg_stem_wgrad_split": (_I, [_D, _P, _P, _P, _P, _P, _I, _I, _P]),
+    "mvg_stem_plan_query_split": (_I, [_D] + [C.POINTER(C.c_int32)] * 6),
     "mvg_bn_relu_maxpool_bwd_reduce_split": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _P, _P, _P, _P, _P]),
     "mvg_bn_relu_maxpool_bwd_apply_split": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P, _I, _P]),
     "mvg_conv_dgrad_bn_partials_split": (_I, [_D]),
@@ -230,6 +231,7 @@ SIGNATURES = {
     "mvg_conv_wgrad_bf16_slabs": (_I, [_D, _P, _P, _P, _I, _P]),
     "mvg_conv_plan_query_bf16": (_I, [_D, _I, C.POINTER(ConvPlan)]),
     "mvg_conv_wgrad_tile_bf16": (_I, [_D, _I, C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    "mvg_stem_plan_query_bf16": (_I, [_D, C.POINTER(ConvPlan), C.POINTER(C.c_int32), C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     "mvg_linear_fprop_mixed": (_I, [_P, _P, _P, _I, _P, _I, _I, _I, _P]),
     "mvg_linear_dgrad_mixed": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _P]),
     "mvg_linear_wgrad_mixed": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _I, _I, _P]),

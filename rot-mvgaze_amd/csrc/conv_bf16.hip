@@ -663,6 +663,23 @@ int mvg_conv_plan_query_bf16(const mvg_conv_desc *d, int kind, mvg_conv_plan *ou
   return 0;
 }
 
+int mvg_stem_plan_query_bf16(const mvg_conv_desc *d, mvg_conv_plan *fwd, int32_t *wgrad_bm, int32_t *wgrad_bn, int32_t *wgrad_incremental) {
+  // what mvg_stem_fprop_bf16 / mvg_stem_wgrad_bf16 run for `d`: the folded descriptor through the forward's own query path
+  // (horizontal stride 1 / padding 0) and the weight gradient's tile choice.  Launches nothing.
+  mvg_conv_desc rw;
+  if (stem_fold_desc(d, &rw)) return -1;
+  mvg_conv_plan plan;
+  memset(&plan, 0, sizeof(plan));
+  if (fprop_bf16_impl(&rw, nullptr, nullptr, nullptr, nullptr, 0, nullptr, nullptr, false, 1, 0, nullptr, &plan)) return -1;
+  if (fwd) *fwd = plan;
+  int tm, tn;
+  wgrad_bf16_tile(&rw, tm, tn);
+  if (wgrad_bm) *wgrad_bm = tm;
+  if (wgrad_bn) *wgrad_bn = tn;
+  if (wgrad_incremental) *wgrad_incremental = wgrad_bf16_incremental(&rw) ? 1 : 0;
+  return 0;
+}
+
 int mvg_conv_wgrad_tile_bf16(const mvg_conv_desc *d, int f32in, int32_t *bm, int32_t *bn, int32_t *incremental) {
   if (validate_bf16(d)) return -1;
   int tm, tn;

@@ -1360,4 +1360,26 @@ int mvg_stem_wgrad_split(const mvg_conv_desc *d, const void *xw_sp, const void *
   return wgrad_split_impl(&rw, xw_sp, dy_sp, dy_sinv, dw_rw, workspace, splits, accumulate, stream, 1, 0);
 }
 
+int mvg_stem_plan_query_split(const mvg_conv_desc *d, int32_t *fwd_bm, int32_t *fwd_bn, int32_t *fwd_stages, int32_t *wgrad_bm,
+                              int32_t *wgrad_bn, int32_t *wgrad_incremental) {
+  // what mvg_stem_fprop_split / mvg_stem_wgrad_split run for `d`: the rewritten descriptor through the geometry, the plan and the
+  // tile choice the launches use (fprop_split_impl -> launch_igemm_split; wgrad_split_impl).  Launches nothing.
+  mvg_conv_desc rw;
+  if (stem_desc(d, &rw)) return -1;
+  IgemmParams p;
+  memset(&p, 0, sizeof(p));
+  if (fprop_geometry(p, &rw, SP_BYTES, SP_BYTES, "split conv", 1, 0)) return -1;
+  const SplitPlan pl = split_plan(p.ncols, rw.r * rw.s, p.rows_per_group, p.groups, false, p.cls, p.ncls);
+  if (fwd_bm) *fwd_bm = pl.bm;
+  if (fwd_bn) *fwd_bn = pl.bn;
+  if (fwd_stages) *fwd_stages = split_conv_stages(pl);
+  int tm, tn;
+  bool incr;
+  wgrad_split_tile(&rw, tm, tn, incr);
+  if (wgrad_bm) *wgrad_bm = tm;
+  if (wgrad_bn) *wgrad_bn = tn;
+  if (wgrad_incremental) *wgrad_incremental = incr ? 1 : 0;
+  return 0;
+}
+
 }  // extern "C"

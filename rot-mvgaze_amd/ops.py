@@ -429,6 +429,16 @@ def stem_wgrad_split(d: ConvDesc, xw: Tensor, dy_sp: Tensor, dw_rw: Tensor, accu
           "stem_wgrad_split")
 
 
+def stem_plan_query_split(d: ConvDesc) -> dict:
+    """What stem_fprop_split / stem_wgrad_split run for the stem descriptor ``d`` with the CUs the planners may use now
+    (set_reserved_cus): {"fwd": (bm, bn, stages), "wgrad": (bm, bn, incremental)}.  Host arithmetic by the launches' own plan;
+    raises with the launch's message for a descriptor the stem launches reject."""
+    v = [C.c_int32(0) for _ in range(6)]
+    if lib().mvg_stem_plan_query_split(C.byref(d), C.byref(v[0]), C.byref(v[1]), C.byref(v[2]), C.byref(v[3]), C.byref(v[4]), C.byref(v[5])) != 0:
+        check(1, "stem_plan_query_split")
+    return {"fwd": (v[0].value, v[1].value, v[2].value), "wgrad": (v[3].value, v[4].value, bool(v[5].value))}
+
+
 def bn_relu_maxpool_bwd_reduce_split(g_pooled, argmax, y, mean, invstd, scale, shift, groups, n_per_group, h, w, c, ho, wo, s1, s2,
                                      dgamma, dbeta, accumulate, mx, gamma=None, dy_sinv=None):
     """gamma + dy_sinv (a 1-element device tensor): the finalize launch also leaves the 2^-k of the dy the apply pass will write."""
@@ -465,6 +475,19 @@ def stem_wgrad_bf16(d: ConvDesc, xw: Tensor, dy: Tensor, dw_fold: Tensor, accumu
     """dw_fold [2 cout, 7, 16, 4] fp32 (+)= the stem's weight gradient in the folded-window tap layout."""
     splits, ws = _wgrad_slabs(lib().mvg_stem_wgrad_splits_bf16, "stem_wgrad_splits_bf16", d, 2 * d.cout * 448, xw.device)
     check(lib().mvg_stem_wgrad_bf16(C.byref(d), _p(xw), _p(dy), _p(dw_fold), _p(ws), splits, int(accumulate), _s()), "stem_wgrad_bf16")
+
+
+def stem_plan_query_bf16(d: ConvDesc) -> dict:
+    """What stem_fprop_bf16 / stem_wgrad_bf16 run for the stem descriptor ``d``: {"fwd": the folded forward's plan (keys as
+    conv_plan_query_bf16), "wgrad": (bm, bn, incremental)}.  Nothing is launched; raises with the launch's message for a
+    descriptor the stem launches reject."""
+    from ._lib import ConvPlan
+    pl, bm, bn, incr = ConvPlan(), C.c_int32(0), C.c_int32(0), C.c_int32(0)
+    if lib().mvg_stem_plan_query_bf16(C.byref(d), C.byref(pl), C.byref(bm), C.byref(bn), C.byref(incr)) != 0:
+        check(1, "stem_plan_query_bf16")
+    fwd = {"bm": pl.bm, "bn": pl.bn, "bk": pl.bk, "fasta": bool(pl.fasta), "cls_tiles": list(pl.cls_tiles[:pl.ncls]),
+           "cls_kt": list(pl.cls_kt[:pl.ncls]), "kernel": "dma" if pl.fasta else "reg"}
+    return {"fwd": fwd, "wgrad": (bm.value, bn.value, bool(incr.value))}
 
 
 def conv_dgrad_bn_partials_split(d: ConvDesc) -> int:
