@@ -994,6 +994,12 @@ int mvg_linear_wgrad_split(int rows, int fin, int fout, const void *x_sp, const 
                            float *dw, float *workspace, int splits, int accumulate, void *stream);
 int mvg_split_colsum(const float *g, int rows, int cols, const float *absmax, void *out_sp, float *out_sinv, float *db, int accumulate,
                      void *stream);
+/* What mvg_linear_fprop_split (dgrad == 0) / mvg_linear_dgrad_split (dgrad != 0) run for a Linear with the CUs the planners may use now,
+ * answered by the code those launches plan with: the tile (*bm x *bn: 128 x 128, or 128 x 64 for fewer than 128 columns or where
+ * 128-column tiles would leave half the CUs idle) and the K loop (*stages: 1, or 2 = the two-stage pipeline, which the Linear
+ * kernels have at both widths).  Every out-pointer may be NULL; launches nothing; 0, or -1 (and a message) for sizes the launches
+ * refuse. */
+int mvg_linear_plan_query_split(int rows, int fin, int fout, int dgrad, int32_t *bm, int32_t *bn, int32_t *stages);
 
 /* ---------------------------------------------------------------- inference session (no Python needed)
  * An opaque handle, made for ONE (architecture, views, batch, height, width) shape, that queues the complete eval-mode

@@ -214,6 +214,7 @@ SIGNATURES = {
     "mvg_linear_dgrad_split": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "mvg_linear_wgrad_split": (_I, [_I, _I, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "mvg_split_colsum": (_I, [_P, _I, _I, _P, _P, _P, _P, _I, _P]),
+    "mvg_linear_plan_query_split": (_I, [_I, _I, _I, _I] + [C.POINTER(C.c_int32)] * 3),
     # bf16 storage path (same argument lists as the fp32 entry points)
     "mvg_cast_weights_bf16": (_I, [_D, _P, _I, _P, _P, _P]),
     "mvg_conv_fprop_bf16": (_I, [_D, _P, _P, _P, _P, _I, _P, _P]),

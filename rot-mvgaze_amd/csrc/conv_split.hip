@@ -1297,6 +1297,35 @@ int mvg_linear_wgrad_split(int rows, int fin, int fout, const void *x_sp, const 
   return wgrad_split_impl(&d, x_sp, dy_sp, dy_sinv, dw, workspace, splits, accumulate, stream, -1, -1, x_sinv);
 }
 
+int mvg_linear_plan_query_split(int rows, int fin, int fout, int dgrad, int32_t *bm, int32_t *bn, int32_t *stages) {
+  // what mvg_linear_fprop_split (dgrad == 0) / mvg_linear_dgrad_split (dgrad != 0) run for this Linear: its descriptor through the
+  // checks, the geometry and the plan those launches use (fprop_split_impl / dgrad_split_impl -> launch_igemm_split with lin).
+  // stages: the LIN kernels have the two-stage K loop at both tile widths, so it is the plan's `pipelined` alone - not
+  // split_conv_stages, the convs' rule.  Launches nothing.
+  const mvg_conv_desc d = linear_desc(rows, fin, fout);
+  if (validate_split(&d)) return -1;
+  IgemmParams p;
+  memset(&p, 0, sizeof(p));
+  SplitPlan pl;
+  if (dgrad) {
+    if (dgrad_geometry(p, &d, SP_BYTES, SP_BYTES, "split conv")) return -1;
+    if ((long long)d.n * d.h * d.w * d.cin >= (1ll << 31)) return set_error("split conv: a group of dx exceeds 2^31 elements"), -1;
+    DgradDropped dropped;
+    dgrad_plan_classes(p, &d, false, dropped);
+    if (p.ncls == 0) return -1;
+    pl = split_plan(p.ncols, d.r * d.s, (long long)d.n * d.h * d.w, p.groups, true, p.cls, p.ncls);
+  } else {
+    if (fprop_geometry(p, &d, SP_BYTES, SP_BYTES, "split conv", -1, -1)) return -1;
+    if (p.rows_per_group * (long long)d.cout >= (1ll << 31)) return set_error("split conv: a group of the output exceeds 2^31 elements"), -1;
+    pl = split_plan(p.ncols, d.r * d.s, p.rows_per_group, p.groups, true, p.cls, p.ncls);
+  }
+  if (pl.tiles <= 0 || pl.tiles >= (1LL << 31)) return set_error("split conv: grid too large"), -1;
+  if (bm) *bm = pl.bm;
+  if (bn) *bn = pl.bn;
+  if (stages) *stages = pl.pipelined ? 2 : 1;
+  return 0;
+}
+
 // ---- the 7x7 stride-2 stem on the split kernels ("row-window" form) ------------------------------------------------
 // A 3-channel (stored 4) image has too few channels for a K-step of the implicit GEMM: the fp32-MFMA kernel runs it at
 // ~75 % of ITS peak (117 TFLOP/s with the padding channel).  Rewritten: xw[n][y][ox][j][c], j = 0..7, c = 0..3 holds

@@ -1004,6 +1004,16 @@ def linear_wgrad_split(x_sp, dy_sp, dw, rows, fin, fout, accumulate=False):
                                        int(accumulate), _s()), "linear_wgrad_split")
 
 
+def linear_plan_query_split(rows, fin, fout, dgrad=False):
+    """(bm, bn, stages): the tile and the K loop (1, or 2 = the two-stage pipeline) linear_fprop_split (dgrad: linear_dgrad_split)
+    runs for these sizes with the CUs the planners may use now (set_reserved_cus).  Host arithmetic by the launches' own plan;
+    raises with the launch's message for sizes they refuse."""
+    v = [C.c_int32(0) for _ in range(3)]
+    if lib().mvg_linear_plan_query_split(rows, fin, fout, int(dgrad), C.byref(v[0]), C.byref(v[1]), C.byref(v[2])) != 0:
+        check(1, "linear_plan_query_split")
+    return v[0].value, v[1].value, v[2].value
+
+
 def split_colsum(g, rows, cols, absmax, out_sp, db=None, accumulate=False):
     """out_sp <- g in sp, scaled from the abs-max slot its producer filled (out_sp.sinv slot written); db (+)= column sums of g."""
     assert g.dtype == torch.float32 and g.is_contiguous() and g.numel() == rows * cols and cols % 32 == 0
