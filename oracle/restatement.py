@@ -316,15 +316,23 @@ def stereo_loss(pred0: Tensor, pred1: Tensor, gt0: Tensor, gt1: Tensor,
 
 
 def iteration_loss(data: Dict[str, Any], iter_decay: float = 0.5, rel_weight: float = 0.01,
-                   reference_decay: float = 1.0) -> Tensor:
-    """Horner accumulation over iterations; /root/reference/losses/stereo_loss.py:65-84
-    (``additional_decay`` is None on the path, main.py:240)."""
-    total: Any = 0
-    for i in range(data["num_iter"]):
+                   reference_decay: float = 1.0, additional_decay: Optional[float] = None) -> Tensor:
+    """Horner accumulation over iterations; /root/reference/losses/stereo_loss.py:65-84.
+    ``additional_decay`` (None on the path, main.py:240): when it is a number - 0.0 included, the reference
+    tests ``is not None`` (:71,79) - the Horner accumulation covers the first n - 1 iterations only and the
+    last iteration's loss is added once, multiplied by it.  With n = 1 the Horner part is empty."""
+    n = data["num_iter"]
+    horner = n if additional_decay is None else n - 1
+
+    def one(i):
         it = data[f"iter_{i}"]
-        total = total * iter_decay + stereo_loss(it["pred_gaze_0"], it["pred_gaze_1"],
-                                                 data["gt_gaze"], data["gt_gaze_1"],
-                                                 rel_weight, reference_decay)
+        return stereo_loss(it["pred_gaze_0"], it["pred_gaze_1"], data["gt_gaze"], data["gt_gaze_1"],
+                           rel_weight, reference_decay)
+    total: Any = 0
+    for i in range(horner):
+        total = total * iter_decay + one(i)
+    if additional_decay is not None:
+        total = total + one(horner) * additional_decay
     return total
 
 
@@ -371,14 +379,14 @@ def _multiview_forward(sd, img, rot, depth, num_iter, training, masks, storage, 
 
 
 def multiview_loss(out: Dict[str, Any], gt: Tensor, iter_decay: float = 0.5, rel_weight: float = 0.01,
-                   reference_decay: float = 1.0) -> Tensor:
-    """mean over pairs of the two-view iteration loss (gt [B,V,2])."""
+                   reference_decay: float = 1.0, additional_decay: Optional[float] = None) -> Tensor:
+    """mean over pairs of the two-view iteration loss (gt [B,V,2]); ``additional_decay`` as in iteration_loss, per pair."""
     total: Any = 0
     pairs = out["pairs"]
     for (i, j), pd in pairs.items():
         d = dict(pd)
         d["gt_gaze"], d["gt_gaze_1"] = gt[:, i], gt[:, j]
-        total = total + iteration_loss(d, iter_decay, rel_weight, reference_decay)
+        total = total + iteration_loss(d, iter_decay, rel_weight, reference_decay, additional_decay)
     return total / len(pairs)
 
 

@@ -387,7 +387,9 @@ class FusionHead:
         D, I, NV = ix["D"], self.I, NUM_FEAT_VEC
         # fp32 model, default variant, many rows: the fuser / head Linears on the split-operand kernels (their inputs
         # are then materialised: the span loader of those kernels reads plain rows)
-        split_on = self.split and not self.mixed and not (self.v.share_feature or self.v.encode_rotmat) and D * B >= SPLIT_MIN_ROWS
+        # (an iteration count the split path's slot arena does not serve steps aside to the fp32 Linears below)
+        split_on = (self.split and not self.mixed and not (self.v.share_feature or self.v.encode_rotmat) and D * B >= SPLIT_MIN_ROWS
+                    and self.split_serves(I))
         for m in [self.lifter] + self.fusers + self.heads:
             m.mixed = self.mixed
             m.split = split_on
@@ -444,6 +446,12 @@ class FusionHead:
     # ---------------------------------------------------------------- the split-operand path (fp32 model, >= SPLIT_MIN_ROWS rows)
     _SLOTS = 64
 
+    @classmethod
+    def split_serves(cls, num_iter: int) -> bool:
+        """_forward_split names 11 scale slots per iteration plus 2 in its _SLOTS-float arena and hands 2 + I tensors to one
+        mvg_absmax_multi launch (at most 8): num_iter <= 5.  (csrc/session_plan.cpp: Builder::build holds the same limit.)"""
+        return 2 + num_iter <= 8 and 11 * num_iter + 2 <= cls._SLOTS
+
     def _forward_split(self, img_feat: Tensor, rot: Tensor, keep_tape: bool, ix: dict):
         """The fuser / head Linears on the split kernels (conv_split.hip), every operand with its own power-of-two scale.
 
@@ -456,7 +464,8 @@ class FusionHead:
         dev = img_feat.device
         D, I, NV = ix["D"], self.I, NUM_FEAT_VEC
         rows, kin = D * B, self.kin
-        assert 2 + I <= 8 and 11 * I + 2 <= self._SLOTS
+        if not self.split_serves(I):                 # (forward decides this before it comes here)
+            raise RuntimeError(f"FusionHead: num_iter {I} is more than the split path's slot arena serves (at most 5)")
         self._prepare_split_weights(rows, dev)
         st = torch.zeros(self._SLOTS, dtype=torch.float32, device=dev)          # abs-max slots must start at zero
         names: Dict[str, int] = {}

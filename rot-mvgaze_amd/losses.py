@@ -140,6 +140,15 @@ class _FusedIterLossFn(torch.autograd.Function):
         return out, None, None, None
 
 
+def iteration_weights(num_iter: int, iter_decay: float, additional_decay: Optional[float]):
+    """The weight of each iteration's loss in stereo_loss.py:65-84: Horner over all n iterations, w_i = iter_decay^(n-1-i);
+    with ``additional_decay`` a number (0.0 included: the reference tests ``is not None``) Horner over the first n - 1,
+    w_i = iter_decay^(n-2-i), and the last iteration weighted by it."""
+    if additional_decay is None:
+        return [iter_decay ** (num_iter - 1 - i) for i in range(num_iter)]
+    return [iter_decay ** (num_iter - 2 - i) for i in range(num_iter - 1)] + [additional_decay]
+
+
 class IterationLoss(AbstractLoss):
     def __init__(self, loss: AbstractLoss, iter_decay: float = 1.0, additional_decay: Optional[float] = None) -> None:
         super().__init__()
@@ -176,21 +185,21 @@ class IterationLoss(AbstractLoss):
         if preds.shape[0] != num_iter or preds.shape[1] != 2:
             return None
         l = self._loss
-        if self._addtional_decay is None:
-            iw = [self._iter_decay ** (num_iter - 1 - i) for i in range(num_iter)]
-        else:
-            iw = [self._iter_decay ** (num_iter - 2 - i) for i in range(num_iter - 1)] + [self._addtional_decay]
+        iw = iteration_weights(num_iter, self._iter_decay, self._addtional_decay)
         gt = torch.stack([data["gt_gaze"], data["gt_gaze_1"]], 0).to(torch.float32).contiguous()
         return _FusedIterLossFn.apply(preds, gt, iw, [l._rel_weight, l._rel_weight * l._reference_decay])
 
 
 class MultiViewIterationLoss(AbstractLoss):
-    """V-view loss of SURVEY.md §8(a) A9: mean over unordered pairs of the two-view IterationLoss.
+    """V-view loss of SURVEY.md §8(a) A9: mean over unordered pairs of the two-view IterationLoss
+    (``additional_decay`` with IterationLoss's meaning, on every pair).
     Takes the dict of ``MultiViewGaze.forward_multiview`` plus gt [B,V,2]."""
 
-    def __init__(self, rel_weight: float = 0.01, reference_decay: float = 1.0, iter_decay: float = 0.5):
+    def __init__(self, rel_weight: float = 0.01, reference_decay: float = 1.0, iter_decay: float = 0.5,
+                 additional_decay: Optional[float] = None):
         super().__init__()
         self._rel_weight, self._reference_decay, self._iter_decay = rel_weight, reference_decay, iter_decay
+        self._addtional_decay = additional_decay
 
     def forward(self, out: Dict[str, Any], gt: Tensor) -> Tensor:
         preds = out["_mvg_preds"]
@@ -203,7 +212,7 @@ class MultiViewIterationLoss(AbstractLoss):
         # that stops the host from queueing the next step's launches under this step's backward
         g32 = gt.to(torch.float32)
         gt_dir = torch.stack([g32[:, v] for v in vi], 0)
-        iw = [self._iter_decay ** (I - 1 - i) for i in range(I)]
+        iw = iteration_weights(I, self._iter_decay, self._addtional_decay)
         dw = [(self._rel_weight if d % 2 == 0 else self._rel_weight * self._reference_decay) / npairs
               for d in range(D)]
         return _FusedIterLossFn.apply(preds, gt_dir, iw, dw)

@@ -195,13 +195,13 @@ STAT_SAMPLES = ["_feat_extractor.0.bn1", "_feat_extractor.0.layer1.0.bn2", "_fea
                 "_feat_extractor.0.layer4.1.bn1"]
 
 
-def build_ref(depth, seed, perturb_bn=True, variant=None):
+def build_ref(depth, seed, perturb_bn=True, variant=None, num_iter=3):
     from rot_mvgaze_amd.arch import DEFAULT_VARIANT
     v = variant or DEFAULT_VARIANT
-    model = ref_rot_mv.FeatRotationSymm(backbone_depth=depth, num_iter=3, share_weights=v.share_weights,
+    model = ref_rot_mv.FeatRotationSymm(backbone_depth=depth, num_iter=num_iter, share_weights=v.share_weights,
                                         encode_rotmat=v.encode_rotmat, share_feature=v.share_feature,
                                         ignore_rotmat=v.ignore_rotmat)
-    sd_np = synth.make_state_dict(depth, seed, 3, perturb_bn=perturb_bn, variant=v)
+    sd_np = synth.make_state_dict(depth, seed, num_iter, perturb_bn=perturb_bn, variant=v)
     ref_keys = {k: tuple(v.shape) for k, v in model.state_dict().items()}
     my_keys = {k: tuple(v.shape) for k, v in sd_np.items()}
     assert ref_keys == my_keys, "state_dict contract mismatch"
@@ -220,10 +220,10 @@ def ref_inputs(batch, seed, hw):
     return data
 
 
-def collect_outputs(data, out):
+def collect_outputs(data, out, num_iter=3):
     for k in ("img_feat_0", "img_feat_1", "initial_rot_feat_0", "initial_rot_feat_1", "pred_gaze"):
         out[k] = t2n(data[k])
-    for i in range(3):
+    for i in range(num_iter):
         for k in ("feat_0", "feat_1", "pred_gaze_0", "pred_gaze_1"):
             out[f"iter_{i}.{k}"] = t2n(data[f"iter_{i}"][k])
 
@@ -271,23 +271,47 @@ def gen_variant(name, variant, depth=18, batch=3, hw=64, seed_w=0, seed_in=1234)
     print(tag, "loss", float(loss), "pred_gaze[0]", out["train.pred_gaze"][0])
 
 
-def gen_model(depth, batch, hw, seed_w=0, seed_in=1234):
-    tag = f"model_r{depth}_b{batch}_hw{hw}"
-    metrics = ref_stereo_loss.IterationLoss(
-        loss=ref_stereo_loss.StereoL1Loss(rel_weight=0.01, reference_decay=1.0,
-                                          distance_metric="angular_error", pred_gaze_key="pred_gaze"),
-        iter_decay=0.5)
+def grad_samples(num_iter):
+    """GRAD_SAMPLES for a model of ``num_iter`` iterations: the keys of iteration 2 (the last of three) name the last iteration."""
+    last = num_iter - 1
+    return [(k.replace("_img_fusers.2.", f"_img_fusers.{last}.").replace("_gaze_estimators.2.", f"_gaze_estimators.{last}.")
+             .replace("_img_fusers.1.", f"_img_fusers.{min(1, last)}."), n) for k, n in GRAD_SAMPLES]
+
+
+DECAY_LOSS = dict(iter_decay=0.5, additional_decay=0.25)      # the second loss of the num_iter != 3 fixtures
+DECAY_GRAD_ELEMS = 512                                        # elements kept per sampled gradient under it (+ every norm)
+
+
+def decay_sample(g):
+    """DECAY_GRAD_ELEMS elements at an even stride over the whole tensor (the leading elements of a Linear's weight gradient are
+    one output unit's row: all zeros when that unit's ReLU is off for the fixture's few rows)."""
+    flat = g.reshape(-1)
+    return flat[::max(1, flat.numel() // DECAY_GRAD_ELEMS)][:DECAY_GRAD_ELEMS]
+
+
+def _stereo_l1():
+    return ref_stereo_loss.StereoL1Loss(rel_weight=0.01, reference_decay=1.0,
+                                        distance_metric="angular_error", pred_gaze_key="pred_gaze")
+
+
+def gen_model(depth, batch, hw, seed_w=0, seed_in=1234, num_iter=3):
+    """num_iter = 3: the fixtures of the path (main.py:240).  Any other count: the same contents under the tag ..._it{n},
+    plus a second train step whose loss is IterationLoss(iter_decay=0.5, additional_decay=0.25) (keys decay.*)."""
+    tag = f"model_r{depth}_b{batch}_hw{hw}" + ("" if num_iter == 3 else f"_it{num_iter}")
+    metrics = ref_stereo_loss.IterationLoss(loss=_stereo_l1(), iter_decay=0.5)
+    samples = grad_samples(num_iter)
     out = {}
     # ---- eval forward ----
-    model = build_ref(depth, seed_w)
+    model = build_ref(depth, seed_w, num_iter=num_iter)
     model.eval()
     with torch.no_grad():
         data = model(ref_inputs(batch, seed_in, hw))
+    assert data["num_iter"] == num_iter
     ev = {}
-    collect_outputs(data, ev)
+    collect_outputs(data, ev, num_iter)
     out.update({"eval." + k: v for k, v in ev.items()})
     # ---- train step: forward + loss + backward (+ BN running stats) ----
-    model = build_ref(depth, seed_w)
+    model = build_ref(depth, seed_w, num_iter=num_iter)
     model.train()
     data = ref_inputs(batch, seed_in, hw)
     data["img_0"].requires_grad_(True)
@@ -296,11 +320,11 @@ def gen_model(depth, batch, hw, seed_w=0, seed_in=1234):
     loss = metrics(data)
     loss.backward()
     tr = {}
-    collect_outputs(data, tr)
+    collect_outputs(data, tr, num_iter)
     out.update({"train." + k: v for k, v in tr.items()})
     out["train.loss"] = t2n(loss)
     params = dict(model.named_parameters())
-    for key, n in GRAD_SAMPLES:
+    for key, n in samples:
         g = params[key].grad
         out["grad." + key] = t2n(g).reshape(-1)[:n].copy()
         out["gradnorm." + key] = np.array(float(g.double().norm()))
@@ -313,8 +337,61 @@ def gen_model(depth, batch, hw, seed_w=0, seed_in=1234):
         out["stat." + p + ".running_mean"] = t2n(sd[p + ".running_mean"])
         out["stat." + p + ".running_var"] = t2n(sd[p + ".running_var"])
         out["stat." + p + ".num_batches_tracked"] = t2n(sd[p + ".num_batches_tracked"])
+    if num_iter != 3:
+        # ---- the same train step under the separately weighted last iteration (stereo_loss.py:71-82) ----
+        model = build_ref(depth, seed_w, num_iter=num_iter)
+        model.train()
+        data = ref_inputs(batch, seed_in, hw)
+        data["img_0"].requires_grad_(True)
+        data = model(data)
+        loss2 = ref_stereo_loss.IterationLoss(loss=_stereo_l1(), **DECAY_LOSS)(data)
+        loss2.backward()
+        out["decay.loss"] = t2n(loss2)
+        params = dict(model.named_parameters())
+        for key, n in samples:
+            g = params[key].grad
+            out["decay.grad." + key] = t2n(decay_sample(g)).copy()
+            assert out["decay.grad." + key].any(), key
+            out["decay.gradnorm." + key] = np.array(float(g.double().norm()))
+        out["decay.grad.img_0"] = t2n(data["img_0"].grad)[:, :, ::16, ::16].copy()
+        out["decay.gradnorm.img_0"] = np.array(float(data["img_0"].grad.double().norm()))
     np.savez_compressed(os.path.join(HERE, tag + ".npz"), **out)
     print(tag, "loss", float(loss), "pred_gaze[0]", out["train.pred_gaze"][0])
+
+
+ITER_LOSS_CASES = [(n, d, a) for n in (1, 2, 3, 4) for d in (0.5, 1.0) for a in (None, 0.25, 0.0)]
+ITER_LOSS_B = 5
+
+
+def gen_iteration_loss():
+    """IterationLoss(StereoL1Loss) of the reference (stereo_loss.py:57-84) on synthetic prediction dicts: every count in
+    1..4, iter_decay 0.5 / 1.0, additional_decay None / 0.25 / 0.0 (`is not None` and truthiness differ on 0.0; with one
+    iteration and a decay set the Horner part is empty).  Inputs, the loss and d loss / d pred for every iteration.
+    Every row's angle between prediction and label lies in [1, 179] degrees (the angular loss is singular at coincident
+    and opposite rows) - asserted here with the reference's own float64 metric."""
+    B, nmax = ITER_LOSS_B, 4
+    gt = torch.tensor(synth.uniform01(2 * B * 2, 31, "iterloss_gt").reshape(2, B, 2) - 0.5, dtype=torch.float32) * 2.0
+    # predictions = label + an offset of 0.05 .. 0.6 rad per component with either sign: never coincident, far from opposite
+    mag = torch.tensor(synth.uniform01(nmax * 2 * B * 2, 32, "iterloss_mag").reshape(nmax, 2, B, 2), dtype=torch.float32) * 0.55 + 0.05
+    sgn = torch.tensor(synth.uniform01(nmax * 2 * B * 2, 33, "iterloss_sgn").reshape(nmax, 2, B, 2), dtype=torch.float32)
+    pred = (gt[None] + mag * torch.where(sgn < 0.5, -1.0, 1.0)).contiguous()
+    for it in range(nmax):
+        for side in range(2):
+            ang = ref_math.angular_error_numpy(t2n(pred[it, side]).astype(np.float64), t2n(gt[side]).astype(np.float64))
+            assert ang.min() >= 1.0 and ang.max() <= 179.0, (it, side, ang)
+    out = {"pred": t2n(pred), "gt": t2n(gt),
+           "cases": np.array([(n, d, -1.0 if a is None else a) for n, d, a in ITER_LOSS_CASES], dtype=np.float64)}
+    for idx, (n, d, a) in enumerate(ITER_LOSS_CASES):
+        p = pred[:n].clone().requires_grad_(True)
+        data = {"num_iter": n, "gt_gaze": gt[0], "gt_gaze_1": gt[1]}
+        for it in range(n):
+            data[f"iter_{it}"] = {"pred_gaze_0": p[it, 0], "pred_gaze_1": p[it, 1]}
+        loss = ref_stereo_loss.IterationLoss(loss=_stereo_l1(), iter_decay=d, additional_decay=a)(data)
+        loss.backward()
+        out[f"loss_{idx}"] = t2n(loss)
+        out[f"dpred_{idx}"] = t2n(p.grad)
+    np.savez_compressed(os.path.join(HERE, "iteration_loss_decay.npz"), **out)
+    print("iteration_loss_decay:", len(ITER_LOSS_CASES), "cases; loss_0", float(out["loss_0"]))
 
 
 def gen_multi_erase():
@@ -382,6 +459,10 @@ if __name__ == "__main__":
     if "--resize" in sys.argv:
         gen_resize()
         sys.exit(0)
+    if "--iter" in sys.argv:
+        gen_iteration_loss()
+        gen_model(18, 3, 64, num_iter=2)
+        sys.exit(0)
     gen_geometry()
     gen_pair_index()
     gen_model(18, 2, 224)
@@ -393,3 +474,5 @@ if __name__ == "__main__":
     gen_resize()
     gen_vec2py()
     gen_lp_loss()
+    gen_iteration_loss()
+    gen_model(18, 3, 64, num_iter=2)

@@ -536,8 +536,9 @@ BF16_MODEL_CASES = [
 ]
 
 
-@pytest.mark.parametrize("depth,V,B,hw,recipe", BF16_MODEL_CASES, ids=[f"r{d}_V{v}_B{b}_hw{h}_{r}" for d, v, b, h, r in BF16_MODEL_CASES])
-def test_bf16_training_step_against_bf16_storage_oracle(depth, V, B, hw, recipe):
+@pytest.mark.parametrize("depth,V,B,hw,recipe,num_iter", [c + (3,) for c in BF16_MODEL_CASES] + [(18, 2, 8, 96, "random", 2)],
+                         ids=[f"r{d}_V{v}_B{b}_hw{h}_{r}" for d, v, b, h, r in BF16_MODEL_CASES] + ["r18_V2_B8_hw96_random_it2"])
+def test_bf16_training_step_against_bf16_storage_oracle(depth, V, B, hw, recipe, num_iter):
     """One training step with compute_dtype = bfloat16 against the CPU oracle with the same storage rounding, at the
     tolerances declared above.  Covers C5's network (ResNet-50, V = 8) at C5's image size (224 px: 56 x 56 ... 7 x 7
     maps through the whole model, 112 fusion-block rows per sample pair set) at reduced batch, and ResNet-50 at V = 4 / 224 px.
@@ -548,15 +549,17 @@ def test_bf16_training_step_against_bf16_storage_oracle(depth, V, B, hw, recipe)
     * ResNet-50 with the benchmark's random-init weights: every conv + BatchNorm unit forward and every residual
       block backward teacher-forced (part (b) of the module docstring); end to end the distance is reported and
       sanity-bounded - the network itself turns one flipped rounding into 10-20 % there.
-    The distance to the fp32 oracle is logged (MVG_TEST_L2_LOG) and sanity-bounded in every case."""
+    The distance to the fp32 oracle is logged (MVG_TEST_L2_LOG) and sanity-bounded in every case.
+    The last case runs the first one's recipe with two iterations instead of three, at the same bars."""
     from oracle import restatement as R
     from rot_mvgaze_amd.geometry import rotation_matrix_2d
     from rot_mvgaze_amd.losses import MultiViewIterationLoss
     from rot_mvgaze_amd.model import MultiViewGaze
-    m = MultiViewGaze(depth, 3)
+    I = num_iter
+    m = MultiViewGaze(depth, I)
     conditioned = recipe == "conditioned"
     teacher_forced = not conditioned          # the unit-by-unit checks do not depend on the recipe: run them once per shape
-    sdn = synth.make_state_dict(depth, 0, 3, perturb_bn=True, conditioned=conditioned)
+    sdn = synth.make_state_dict(depth, 0, I, perturb_bn=True, conditioned=conditioned)
     m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sdn.items()})
     m.to(dev()).train()
     m.compute_dtype = torch.bfloat16
@@ -579,7 +582,7 @@ def test_bf16_training_step_against_bf16_storage_oracle(depth, V, B, hw, recipe)
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     rot = R.rotation_matrix_2d(hp.reshape(-1, 2)).reshape(B, V, 3, 3)
     log = os.environ.get("MVG_TEST_L2_LOG")
-    tag = f"bf16[r{depth}_V{V}_B{B}_hw{hw}_{recipe}]"
+    tag = f"bf16[r{depth}_V{V}_B{B}_hw{hw}_{recipe}]" if I == 3 else f"bf16[r{depth}_V{V}_B{B}_hw{hw}_{recipe}_it{I}]"
 
     def note(line):
         if log:
@@ -589,16 +592,17 @@ def test_bf16_training_step_against_bf16_storage_oracle(depth, V, B, hw, recipe)
     # ---- (c) fp32 oracle: report + sanity
     sd32 = {k: torch.from_numpy(np.array(v)) for k, v in sdn.items()}
     with torch.no_grad():
-        o32 = R.multiview_forward(sd32, img, rot, depth, 3, True)
+        o32 = R.multiview_forward(sd32, img, rot, depth, I, True)
     # ---- (b) the same storage rounding on the CPU
     sd = {k: torch.from_numpy(np.array(v)) for k, v in sdn.items()}
     leaves = {k: v.requires_grad_(True) for k, v in sd.items() if v.dtype == torch.float32 and "running" not in k}
-    oo = R.multiview_forward(sd, img, rot, depth, 3, True, None, R.bf16_round)
+    oo = R.multiview_forward(sd, img, rot, depth, I, True, None, R.bf16_round)
     ol = R.multiview_loss(oo, gt, iter_decay=0.5, rel_weight=0.01, reference_decay=1.0)
     ol.backward()
     worst_b, worst_c = 0.0, 0.0
+    assert out["num_iter"] == I and out["_mvg_preds"].shape[0] == I
     for pr in R.view_pairs(V):
-        for it in range(3):
+        for it in range(I):
             for k in ("pred_gaze_0", "pred_gaze_1"):
                 got = out["pairs"][pr][f"iter_{it}"][k].detach().cpu().double()
                 for ref, which in ((oo["pairs"][pr][f"iter_{it}"][k].detach().double(), "b"), (o32["pairs"][pr][f"iter_{it}"][k].double(), "c")):
@@ -611,6 +615,8 @@ def test_bf16_training_step_against_bf16_storage_oracle(depth, V, B, hw, recipe)
              for v in range(V))
     fe32 = max(float((out["img_feat"][v].detach().cpu() - o32["img_feat"][v]).abs().max() / o32["img_feat"][v].abs().max())
                for v in range(V))
+    print(f"ITER-COUNT {tag} pred vs bf16-storage oracle: max-norm {worst_b:.3e} (bar {BF16_PRED_TOL:.1e}); loss "
+          f"{abs(loss.item() - ol.item()) / abs(ol.item()):.3e} (bar {BF16_LOSS_TOL:.1e})")
     note(f"{worst_b:.3e} {BF16_PRED_TOL:.1e} {tag} pred vs bf16-storage oracle (features {fe:.3e})")
     note(f"{worst_c:.3e} {BF16_VS_FP32_SANITY:.1e} {tag} pred vs fp32 oracle [reported] (features {fe32:.3e})")
     note(f"{abs(loss.item() - ol.item()) / abs(ol.item()):.3e} {BF16_LOSS_TOL:.1e} {tag} loss vs bf16-storage oracle")

@@ -68,6 +68,48 @@ def test_update_rejects_bad_arguments(L, bad, word):
     assert _err(L).startswith("gaze_error_update:") and word in _err(L), _err(L)
 
 
+# ---------------------------------------------------------------- the fused loss launch's 512-cell limit
+def _loss_multi(L, iters, dirs):
+    """mvg_gaze_angular_loss_multi at batch 1.  The weights travel by value in a float[512] kernel argument, so iters * dirs is
+    checked before any HIP call.  On a machine with a GPU the tensors are device memory (an accepted call does launch);
+    without one the launch cannot happen and the host buffers are never read."""
+    n = iters * dirs
+    w = (C.c_float * n)()
+    if torch.cuda.is_available():
+        keep = [torch.zeros(n, 1, 2, device="cuda") + 0.1, torch.zeros(dirs, 1, 2, device="cuda"), torch.zeros(1, device="cuda")]
+        ptr = [C.c_void_p(t.data_ptr()) for t in keep]
+    else:
+        keep = [(C.c_float * (2 * n))(), (C.c_float * (2 * dirs))(), (C.c_float * 1)()]
+        ptr = [C.cast(b, C.c_void_p) for b in keep]
+    rc = L.mvg_gaze_angular_loss_multi(ptr[0], ptr[1], iters, dirs, 1, w, ptr[2], None, None)
+    if torch.cuda.is_available():
+        torch.cuda.synchronize()
+    return rc, _err(L)
+
+
+@pytest.mark.parametrize("iters, dirs", [(9, 57), (1, 513), (513, 1), (27, 19)])
+def test_loss_launch_rejects_513_cells(L, iters, dirs):
+    assert iters * dirs == 513
+    assert L.mvg_session_set_error_record(None, None, None, None, 0) != 0       # (another call's message is in place first)
+    rc, msg = _loss_multi(L, iters, dirs)
+    assert rc != 0
+    assert msg.startswith("gaze_angular_loss_multi: bad arguments") and "iters * dirs <= 512" in msg, msg
+
+
+@pytest.mark.parametrize("iters, dirs", [(8, 64), (512, 1), (1, 512)])
+def test_loss_launch_takes_512_cells(L, iters, dirs):
+    """Exactly 512 cells pass the argument check: with a GPU the call succeeds, without one the only complaint is the missing
+    device (the runtime's, from the launch that follows the checks)."""
+    assert iters * dirs == 512
+    assert L.mvg_session_set_error_record(None, None, None, None, 0) != 0
+    rc, msg = _loss_multi(L, iters, dirs)
+    if torch.cuda.is_available():
+        assert rc == 0, msg
+    else:
+        assert "bad arguments" not in msg and "512" not in msg, msg
+        assert rc != 0 and msg.startswith("gaze_angular_loss_multi:") and "device" in msg, msg
+
+
 # ---------------------------------------------------------------- the session hook on a host-built session
 def _cfg(**kw):
     from rot_mvgaze_amd._lib import SessionCfg

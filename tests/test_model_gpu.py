@@ -59,10 +59,10 @@ def dev():
     return torch.device("cuda:0")
 
 
-def build(depth, seed=0, train=True, conditioned=False):
+def build(depth, seed=0, train=True, conditioned=False, num_iter=3):
     from rot_mvgaze_amd.model import FeatRotationSymm
-    m = FeatRotationSymm(backbone_depth=depth, num_iter=3)
-    sd = synth.make_state_dict(depth, seed, 3, perturb_bn=True, conditioned=conditioned)
+    m = FeatRotationSymm(backbone_depth=depth, num_iter=num_iter)
+    sd = synth.make_state_dict(depth, seed, num_iter, perturb_bn=True, conditioned=conditioned)
     m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sd.items()}, strict=True)
     m.to(dev())
     return m.train() if train else m.eval()
@@ -77,10 +77,10 @@ def inputs(batch, hw, seed=1234, views=2):
             "gt_gaze": gt[:, 0].contiguous(), "gt_gaze_1": gt[:, 1].contiguous()}
 
 
-def metrics():
+def metrics(additional_decay=None):
     from rot_mvgaze_amd.losses import IterationLoss, StereoL1Loss
     return IterationLoss(StereoL1Loss(rel_weight=0.01, reference_decay=1.0, distance_metric="angular_error",
-                                      pred_gaze_key="pred_gaze"), iter_decay=0.5)
+                                      pred_gaze_key="pred_gaze"), iter_decay=0.5, additional_decay=additional_decay)
 
 
 def rel_close(got, ref, tol, what):
@@ -101,10 +101,11 @@ def l2_close(got, ref, tol, what):
     assert err <= tol, f"{what}: relative L2 error {err:.3e} > {tol}"
 
 
-def check_outputs(data, g, prefix, tol):
+def check_outputs(data, g, prefix, tol, num_iter=3):
     for k in ("img_feat_0", "img_feat_1", "initial_rot_feat_0", "initial_rot_feat_1", "pred_gaze"):
         rel_close(data[k], g[f"{prefix}.{k}"], tol if k == "pred_gaze" else FTOL, f"{prefix}.{k}")
-    for i in range(3):
+    assert f"iter_{num_iter}" not in data
+    for i in range(num_iter):
         for k in ("feat_0", "feat_1", "pred_gaze_0", "pred_gaze_1"):
             rel_close(data[f"iter_{i}"][k], g[f"{prefix}.iter_{i}.{k}"], tol if "pred" in k else FTOL,
                       f"{prefix}.iter_{i}.{k}")
@@ -122,26 +123,58 @@ def select_kernels(monkeypatch, kernels):
 
 
 @pytest.mark.parametrize("kernels", KERNELS)
-@pytest.mark.parametrize("depth,batch,hw", [(18, 3, 64), (50, 3, 64), (18, 2, 224), (50, 2, 224)])
-def test_against_reference_golden(golden_dir, monkeypatch, depth, batch, hw, kernels):
+@pytest.mark.parametrize("depth,batch,hw,num_iter", [(18, 3, 64, 3), (50, 3, 64, 3), (18, 2, 224, 3), (50, 2, 224, 3), (18, 3, 64, 2)],
+                         ids=["18-3-64", "50-3-64", "18-2-224", "50-2-224", "18-3-64-it2"])
+def test_against_reference_golden(golden_dir, monkeypatch, depth, batch, hw, num_iter, kernels):
+    """num_iter = 2: the reference FeatRotationSymm(num_iter=2) (make_golden.py --iter), with a second train step under
+    IterationLoss(iter_decay=0.5, additional_decay=0.25) - its loss and gradients (keys decay.*) at the same bars."""
     select_kernels(monkeypatch, kernels)
-    g = np.load(os.path.join(golden_dir, f"model_r{depth}_b{batch}_hw{hw}.npz"))
+    I = num_iter
+    g = np.load(os.path.join(golden_dir, f"model_r{depth}_b{batch}_hw{hw}" + ("" if I == 3 else f"_it{I}") + ".npz"))
+    gbar = GTOL_L2_FLIPS_DEEP if depth == 50 else GTOL_L2_FIXTURE
     # ---- eval
-    m = build(depth, train=False)
+    m = build(depth, train=False, num_iter=I)
     with torch.no_grad():
         data = m(inputs(batch, hw))
-    check_outputs(data, g, "eval", TOL)
+    check_outputs(data, g, "eval", TOL, I)
+    if I != 3:
+        # ---- the train step under the separately weighted last iteration
+        m = build(depth, train=True, num_iter=I)
+        data = inputs(batch, hw)
+        data["img_0"].requires_grad_(True)
+        data = m(data)
+        assert data["num_iter"] == I and data["_mvg_preds"].shape[0] == I
+        loss = metrics(0.25)(data)
+        loss.backward()
+        params = dict(m.named_parameters())
+        keys = [k[11:] for k in g.files if k.startswith("decay.grad._")]
+        assert len(keys) == 18
+        # (make_golden.py:decay_sample - 512 elements at an even stride over the tensor in its logical OIHW order)
+        sample = lambda t: t.contiguous().reshape(-1)[::max(1, t.numel() // 512)][:512]
+        figs = sorted((float(np.linalg.norm(sample(params[k].grad).cpu().double().numpy() - g["decay.grad." + k]) / np.linalg.norm(g["decay.grad." + k])), k)
+                      for k in keys)
+        print(f"ITER-COUNT reference fixture I={I} {kernels}, additional_decay=0.25: loss {abs(loss.item() - float(g['decay.loss'])) / float(g['decay.loss']):.3e} "
+              f"(bar {TOL:.1e}); sampled gradients rel-L2 {figs[0][0]:.3e} .. {figs[-1][0]:.3e} over {len(figs)} tensors (largest at {figs[-1][1]}; bar {gbar:.1e})")
+        rel_close(loss, g["decay.loss"], TOL, "decay loss")
+        for key in keys:
+            ref = g["decay.grad." + key]
+            gr = params[key].grad
+            assert ref.any() and sample(gr).shape == ref.shape, key
+            l2_close(sample(gr), ref, gbar, "decay grad " + key)
+            rel_close(gr.double().norm().item(), g["decay.gradnorm." + key], gbar, "decay gradnorm " + key)
+        l2_close(data["img_0"].grad[:, :, ::16, ::16], g["decay.grad.img_0"], gbar, "decay grad img_0")
     # ---- train step
-    m = build(depth, train=True)
+    m = build(depth, train=True, num_iter=I)
     data = inputs(batch, hw)
     data["img_0"].requires_grad_(True)
     extra = {"idx_0": torch.arange(batch), "something": "else"}
     data.update(extra)
     ret = m(data)
-    assert ret is data and data["something"] == "else" and data["num_iter"] == 3      # in-place dict protocol
+    assert ret is data and data["something"] == "else" and data["num_iter"] == I      # in-place dict protocol
+    assert data["pred_gaze"] is data[f"iter_{I - 1}"]["pred_gaze_0"]
     loss = metrics()(data)
     loss.backward()
-    check_outputs(data, g, "train", TOL)
+    check_outputs(data, g, "train", TOL, I)
     rel_close(loss, g["train.loss"], TOL, "loss")
     params = dict(m.named_parameters())
     for key in [k[5:] for k in g.files if k.startswith("grad._")]:
@@ -291,15 +324,20 @@ def _captured_masks(m, V=2):
 
 # ResNet-50 at 160 px: the stem gradients have gone through 50 fp32 layers; their max-norm error moves
 # between 1.5e-4 and 2.1e-4 with the summation order (stream-K cuts, wgrad split count), hence 4e-4.
-@pytest.mark.parametrize("depth,batch,hw,gtol", [(18, 4, 96, GTOL), (50, 2, 160, 2 * GTOL), (18, 2, 224, GTOL),
-                                                 (50, 3, 64, 1e-3),    # 12-sample BatchNorm in layer4
-                                                 (18, 64, 224, GTOL / 2)])   # the benchmark configuration C2 at full size
+STRICT_CASES = [(18, 4, 96, GTOL, 3, None), (50, 2, 160, 2 * GTOL, 3, None), (18, 2, 224, GTOL, 3, None),
+                (50, 3, 64, 1e-3, 3, None),    # 12-sample BatchNorm in layer4
+                (18, 64, 224, GTOL / 2, 3, None),   # the benchmark configuration C2 at full size
+                (18, 4, 96, GTOL, 2, 0.25)]    # two iterations, the last one weighted by additional_decay
+
+
+@pytest.mark.parametrize("depth,batch,hw,gtol,num_iter,additional_decay", STRICT_CASES,
+                         ids=[f"{d}-{b}-{h}-{t}" + ("" if i == 3 else f"-it{i}-decay{a}") for d, b, h, t, i, a in STRICT_CASES])
 @pytest.mark.parametrize("kernels", KERNELS)
-def test_backward_strict_with_imposed_relu_pattern(monkeypatch, depth, batch, hw, gtol, kernels):
+def test_backward_strict_with_imposed_relu_pattern(monkeypatch, depth, batch, hw, gtol, num_iter, additional_decay, kernels):
     """Every parameter gradient (and d/d img) against the fp64 oracle evaluated with the SAME
     ReLU activation pattern as the HIP forward (oracle._relu): isolates the backward kernels from
     the handful of boundary ReLU decisions that fp32 reduction order flips."""
-    _strict_backward_check(monkeypatch, depth, batch, hw, gtol, kernels, True)
+    _strict_backward_check(monkeypatch, depth, batch, hw, gtol, kernels, True, num_iter, additional_decay)
 
 
 @pytest.mark.parametrize("depth,batch,hw,gtol", [(18, 4, 96, GTOL), (50, 2, 160, 2 * GTOL), (18, 64, 224, GTOL / 2)])
@@ -309,10 +347,10 @@ def test_backward_strict_without_image_gradients_stem_on_the_split_kernels(monke
     _strict_backward_check(monkeypatch, depth, batch, hw, gtol, "split", False)
 
 
-def _strict_backward_check(monkeypatch, depth, batch, hw, gtol, kernels, img_grad):
+def _strict_backward_check(monkeypatch, depth, batch, hw, gtol, kernels, img_grad, num_iter=3, additional_decay=None):
     from oracle import restatement as R
     select_kernels(monkeypatch, kernels)
-    m = build(depth)
+    m = build(depth, num_iter=num_iter)
     m._debug_keep_tapes = True
     data = inputs(batch, hw, seed=99)
     if img_grad:
@@ -321,9 +359,10 @@ def _strict_backward_check(monkeypatch, depth, batch, hw, gtol, kernels, img_gra
     data = m(data)
     assert m._backbone._stem_rw == (kernels == "split" and not img_grad)
     masks = _captured_masks(m)            # before backward: it releases the saved activations
-    loss = metrics()(data)
+    assert sum(isinstance(k, tuple) and k[0] == "fuse" for k in masks) == num_iter
+    loss = metrics(additional_decay)(data)
     loss.backward()
-    sd = {k: torch.from_numpy(np.array(v)) for k, v in synth.make_state_dict(depth, 0, 3, perturb_bn=True).items()}
+    sd = {k: torch.from_numpy(np.array(v)) for k, v in synth.make_state_dict(depth, 0, num_iter, perturb_bn=True).items()}
     sd = {k: (v.double() if v.dtype == torch.float32 else v) for k, v in sd.items()}
     leaves = {k: v.requires_grad_(True) for k, v in sd.items() if v.is_floating_point() and "running" not in k}
     inp = synth.make_inputs(batch, 2, 99, hw)
@@ -331,8 +370,8 @@ def _strict_backward_check(monkeypatch, depth, batch, hw, gtol, kernels, img_gra
     od = {"img_0": img[:, 0].double().requires_grad_(True), "img_1": img[:, 1].double().requires_grad_(True),
           "rot_0": R.rotation_matrix_2d(hp[:, 0]).double(), "rot_1": R.rotation_matrix_2d(hp[:, 1]).double(),
           "gt_gaze": gt[:, 0], "gt_gaze_1": gt[:, 1]}
-    od = R.model_forward(sd, od, depth, 3, True, masks)
-    ol = R.iteration_loss(od)
+    od = R.model_forward(sd, od, depth, num_iter, True, masks)
+    ol = R.iteration_loss(od, additional_decay=additional_decay)
     ol.backward()
     rel_close(loss, ol.item(), TOL, "loss")
     n, errs = 0, []
@@ -356,6 +395,7 @@ def _strict_backward_check(monkeypatch, depth, batch, hw, gtol, kernels, img_gra
         assert stem_err <= 5e-3, f"{stem}: {stem_err:.2e}"
         errs = [(e, k) for e, k in errs if k != stem]
     errs.sort(reverse=True)                  # worst first (round 1 forgot the sort and checked one tensor only)
+    print(f"ITER-COUNT strict backward r{depth} B{batch} hw{hw} I={num_iter} decay={additional_decay} {kernels}: worst gradient {errs[0][0]:.3e} ({errs[0][1]}), bar {gtol:.1e}")
     assert errs[0][0] <= gtol, "worst gradients (max-norm relative error): " + ", ".join(f"{k} {e:.2e}" for e, k in errs[:8])
     assert n == len(leaves) - 2          # everything but the unused fc.weight / fc.bias
     if not img_grad:
@@ -695,7 +735,7 @@ MV_CASES = [
 ]
 
 
-def _multiview_case(depth, V, B, hw, seed=5, perturb_bn=True, grad_keys=None, gtol=None):
+def _multiview_case(depth, V, B, hw, seed=5, perturb_bn=True, grad_keys=None, gtol=None, num_iter=3, additional_decay=None):
     """One training step of MultiViewGaze against the CPU oracle on the same inputs: loss, every pair's
     features and predictions (rot_mv.py:187-269 per pair) at 1e-4, sampled weight gradients in relative L2."""
     from oracle import restatement as R
@@ -704,43 +744,48 @@ def _multiview_case(depth, V, B, hw, seed=5, perturb_bn=True, grad_keys=None, gt
     from rot_mvgaze_amd.model import MultiViewGaze
     gtol = l2_bound(depth, B, hw) if gtol is None else gtol
     tol = TOL if B * max(hw // 32, 1) ** 2 >= 32 else 2 * TOL     # < 32 values per layer4 channel: see test_small_and_odd_*
-    m = MultiViewGaze(depth, 3)
-    sdn = synth.make_state_dict(depth, 0, 3, perturb_bn=perturb_bn)
+    I = num_iter
+    m = MultiViewGaze(depth, I)
+    sdn = synth.make_state_dict(depth, 0, I, perturb_bn=perturb_bn)
     m.load_state_dict({k: torch.from_numpy(np.array(v)) for k, v in sdn.items()})
     m.to(dev()).train()
     inp = synth.make_inputs(B, V, seed, hw)
     img, hp, gt = (torch.from_numpy(inp[k]) for k in ("img", "head_pose", "gt_gaze"))
     rot_d = rotation_matrix_2d(hp.reshape(-1, 2).to(dev())).reshape(B, V, 3, 3)
     out = m.forward_multiview([img[:, v].contiguous().to(dev()) for v in range(V)], rot_d)
-    loss = MultiViewIterationLoss(rel_weight=0.01, reference_decay=1.0, iter_decay=0.5)(out, gt.to(dev()))
+    assert out["num_iter"] == I and out["_mvg_preds"].shape[0] == I and out["pred_gaze"] is not None
+    loss = MultiViewIterationLoss(rel_weight=0.01, reference_decay=1.0, iter_decay=0.5, additional_decay=additional_decay)(out, gt.to(dev()))
     loss.backward()
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     sd = {k: torch.from_numpy(np.array(v)) for k, v in sdn.items()}
     leaves = {k: v.requires_grad_(True) for k, v in sd.items() if v.dtype == torch.float32 and "running" not in k}
     rot = R.rotation_matrix_2d(hp.reshape(-1, 2)).reshape(B, V, 3, 3)
-    oo = R.multiview_forward(sd, img, rot, depth, 3, True)
-    ol = R.multiview_loss(oo, gt, iter_decay=0.5, rel_weight=0.01, reference_decay=1.0)
+    oo = R.multiview_forward(sd, img, rot, depth, I, True)
+    ol = R.multiview_loss(oo, gt, iter_decay=0.5, rel_weight=0.01, reference_decay=1.0, additional_decay=additional_decay)
     ol.backward()
     rel_close(loss, ol.item(), TOL, "mv loss")
     for pr in R.view_pairs(V):
-        for it in range(3):
+        assert f"iter_{I}" not in out["pairs"][pr]
+        for it in range(I):
             for k in ("feat_0", "feat_1", "pred_gaze_0", "pred_gaze_1"):
                 rel_close(out["pairs"][pr][f"iter_{it}"][k], oo["pairs"][pr][f"iter_{it}"][k].detach().numpy(), tol,
                           f"pair {pr} iter {it} {k}")
     params = dict(m.named_parameters())
     for k in grad_keys or ("_lifter._lifter.blocks.0.0.weight", "_img_fusers.0._fuser.blocks.0.0.weight",
-                           "_gaze_estimators.1.blocks.1.0.weight", "_feat_extractor.0.layer3.0.conv1.weight",
+                           f"_gaze_estimators.{min(1, I - 1)}.blocks.1.0.weight", "_feat_extractor.0.layer3.0.conv1.weight",
                            "_feat_extractor.0.bn1.bias"):
         l2_close(params[k].grad, leaves[k].grad.numpy(), gtol, "mv grad " + k)
     assert int(m.state_dict()["_feat_extractor.0.bn1.num_batches_tracked"]) == V
     return m
 
 
-@pytest.mark.parametrize("depth,V,B,hw", MV_CASES, ids=[f"r{d}_V{v}_B{b}_hw{h}" for d, v, b, h in MV_CASES])
-def test_multiview_against_oracle(depth, V, B, hw):
+@pytest.mark.parametrize("depth,V,B,hw,num_iter,additional_decay", [c + (3, None) for c in MV_CASES] + [(18, 3, 2, 64, 2, 0.25)],
+                         ids=[f"r{d}_V{v}_B{b}_hw{h}" for d, v, b, h in MV_CASES] + ["r18_V3_B2_hw64_it2_decay0.25"])
+def test_multiview_against_oracle(depth, V, B, hw, num_iter, additional_decay):
     """A9: V > 2 views (configs C3/C4: V = 4, C5: V = 8) for BOTH backbones, at reduced batch, fp32 - shared
-    backbone features, every pair equals the two-view oracle recurrence."""
-    _multiview_case(depth, V, B, hw)
+    backbone features, every pair equals the two-view oracle recurrence.  The last case: two iterations, and the loss
+    weighs the last one by additional_decay on every pair."""
+    _multiview_case(depth, V, B, hw, num_iter=num_iter, additional_decay=additional_decay)
 
 
 @pytest.mark.parametrize("depth,V,B,hw", [(50, 4, 2, 128), (18, 4, 96, 64)], ids=["r50_V4_B2_hw128", "r18_V4_B96_hw64_split_linears"])

@@ -77,8 +77,8 @@ def test_mt19937_matches_cpython():
         assert [random.getrandbits(32) for _ in range(1500)] == [rng.u32() for _ in range(1500)]
 
 
-def _torch_sd(depth, seed=0):
-    return {k: torch.from_numpy(np.array(v)) for k, v in synth.make_state_dict(depth, seed, 3, perturb_bn=True).items()}
+def _torch_sd(depth, seed=0, num_iter=3):
+    return {k: torch.from_numpy(np.array(v)) for k, v in synth.make_state_dict(depth, seed, num_iter, perturb_bn=True).items()}
 
 
 def _data(batch, hw, seed=1234):
@@ -89,11 +89,11 @@ def _data(batch, hw, seed=1234):
             "gt_gaze": gt[:, 0].contiguous(), "gt_gaze_1": gt[:, 1].contiguous()}
 
 
-def _check_outputs(data, g, prefix, rtol):
+def _check_outputs(data, g, prefix, rtol, num_iter=3):
     for k in ("img_feat_0", "img_feat_1", "initial_rot_feat_0", "initial_rot_feat_1", "pred_gaze"):
         ref = g[f"{prefix}.{k}"]
         np.testing.assert_allclose(data[k].detach().numpy(), ref, rtol=rtol, atol=rtol * np.abs(ref).max())
-    for i in range(3):
+    for i in range(num_iter):
         for k in ("feat_0", "feat_1", "pred_gaze_0", "pred_gaze_1"):
             ref = g[f"{prefix}.iter_{i}.{k}"]
             np.testing.assert_allclose(data[f"iter_{i}"][k].detach().numpy(), ref, rtol=rtol,
@@ -130,6 +130,114 @@ def test_model_forward_backward_vs_reference(golden_dir, depth, batch, hw):
     for k in [k for k in g.files if k.startswith("stat.")]:
         np.testing.assert_allclose(sd[k[5:]].detach().numpy(), g[k], rtol=1e-6, atol=1e-7)
     assert int(sd["_feat_extractor.0.bn1.num_batches_tracked"]) == 2
+
+
+def decay_sample(g):
+    """make_golden.py:decay_sample - 512 elements at an even stride over the whole tensor."""
+    flat = g.reshape(-1)
+    return flat[::max(1, flat.numel() // 512)][:512]
+
+
+def test_two_iteration_model_and_decayed_last_iteration_vs_reference(golden_dir):
+    """The reference FeatRotationSymm(backbone_depth=18, num_iter=2) (make_golden.py --iter): the oracle at I = 2, same
+    bars as the I = 3 fixtures above, and a second train step under IterationLoss(iter_decay=0.5, additional_decay=0.25)
+    (keys decay.*: the loss, every sampled gradient's leading elements and norm)."""
+    depth, batch, hw, I = 18, 3, 64, 2
+    g = _load(golden_dir, "model_r18_b3_hw64_it2.npz")
+    assert not [k for k in g.files if "iter_2" in k or "_img_fusers.2" in k or "_gaze_estimators.2" in k]
+    assert os.path.getsize(os.path.join(golden_dir, "model_r18_b3_hw64_it2.npz")) <= os.path.getsize(
+        os.path.join(golden_dir, "model_r18_b3_hw64.npz"))
+    sd = _torch_sd(depth, num_iter=I)
+    with torch.no_grad():
+        data = R.model_forward(sd, _data(batch, hw), depth, I, training=False)
+    assert data["num_iter"] == I and data["pred_gaze"] is data["iter_1"]["pred_gaze_0"] and "iter_2" not in data
+    _check_outputs(data, g, "eval", 1e-6, I)
+    for prefix, kw in (("", {}), ("decay.", dict(iter_decay=0.5, additional_decay=0.25))):
+        sd = _torch_sd(depth, num_iter=I)
+        leaves = {k: v.requires_grad_(True) for k, v in sd.items() if v.dtype == torch.float32 and "running" not in k}
+        data = _data(batch, hw)
+        data["img_0"].requires_grad_(True)
+        data = R.model_forward(sd, data, depth, I, training=True)
+        loss = R.iteration_loss(data, **kw)
+        loss.backward()
+        if not prefix:
+            _check_outputs(data, g, "train", 1e-6, I)
+        np.testing.assert_allclose(loss.item(), g["train.loss" if not prefix else "decay.loss"], rtol=1e-6)
+        keys = [k[len(prefix) + 5:] for k in g.files if k.startswith(prefix + "grad._")]
+        assert len(keys) == 18
+        for key in keys:
+            ref = g[prefix + "grad." + key]
+            got = (decay_sample(leaves[key].grad) if prefix else leaves[key].grad.reshape(-1)[: ref.size]).numpy()
+            assert got.shape == ref.shape and (ref.any() or not prefix), key
+            np.testing.assert_allclose(got, ref, rtol=1e-5, atol=1e-5 * np.abs(ref).max() + 1e-12)
+            np.testing.assert_allclose(float(leaves[key].grad.double().norm()), g[prefix + "gradnorm." + key], rtol=1e-5)
+        ref = g[prefix + "grad.img_0"]
+        np.testing.assert_allclose(data["img_0"].grad[:, :, ::16, ::16].numpy(), ref, rtol=1e-5, atol=1e-5 * np.abs(ref).max())
+        if not prefix:
+            for k in [k for k in g.files if k.startswith("stat.")]:
+                np.testing.assert_allclose(sd[k[5:]].detach().numpy(), g[k], rtol=1e-6, atol=1e-7)
+    # the two losses (0.5 L0 + L1 against L0 + 0.25 L1) differ by far more than the 1e-6 above: the second set is no copy of the first
+    assert abs(float(g["decay.loss"]) - float(g["train.loss"])) > 1e-2 * float(g["train.loss"])
+
+
+def iteration_loss_cases(g):
+    """(index, num_iter, iter_decay, additional_decay or None) of tests/golden/iteration_loss_decay.npz."""
+    return [(i, int(n), float(d), None if a < 0 else float(a)) for i, (n, d, a) in enumerate(g["cases"])]
+
+
+def test_iteration_loss_with_additional_decay_vs_reference(golden_dir):
+    """oracle.restatement.iteration_loss against the reference's IterationLoss(StereoL1Loss) on every row of
+    iteration_loss_decay.npz: counts 1..4, iter_decay 0.5 / 1.0, additional_decay None / 0.25 / 0.0 - loss and
+    d loss / d pred of every iteration, at the bars of test_loss_known_answers."""
+    g = _load(golden_dir, "iteration_loss_decay.npz")
+    cases = iteration_loss_cases(g)
+    assert len(cases) == 24 and {(n, d, a) for _, n, d, a in cases} == {(n, d, a) for n in (1, 2, 3, 4) for d in (0.5, 1.0) for a in (None, 0.25, 0.0)}
+    gt = torch.from_numpy(g["gt"])
+    assert gt.shape == (2, 5, 2)
+    # the generator's condition, re-checked on what it stored: no row within 1 degree of the loss's singularities
+    for it in range(4):
+        for side in range(2):
+            ang = R.angular_error_numpy(g["pred"][it, side].astype(np.float64), g["gt"][side].astype(np.float64))
+            assert ang.min() >= 1.0 and ang.max() <= 179.0
+    for idx, n, d, a in cases:
+        p = torch.from_numpy(g["pred"][:n].copy()).requires_grad_(True)
+        data = {"num_iter": n, "gt_gaze": gt[0], "gt_gaze_1": gt[1]}
+        for it in range(n):
+            data[f"iter_{it}"] = {"pred_gaze_0": p[it, 0], "pred_gaze_1": p[it, 1]}
+        loss = R.iteration_loss(data, iter_decay=d, rel_weight=0.01, reference_decay=1.0, additional_decay=a)
+        loss.backward()
+        np.testing.assert_allclose(loss.item(), g[f"loss_{idx}"], rtol=1e-6, err_msg=str((n, d, a)))
+        np.testing.assert_allclose(p.grad.numpy(), g[f"dpred_{idx}"], rtol=1e-5, atol=1e-6, err_msg=str((n, d, a)))
+        if a == 0.0:
+            assert not p.grad[n - 1].any() and (n == 1 or p.grad[:n - 1].abs().min() > 0)
+    # None, 0.25 and 0.0 are three different losses at every count (None weighs the last iteration with 1)
+    by = {(n, d, a): float(g[f"loss_{i}"]) for i, n, d, a in cases}
+    for n in (1, 2, 3, 4):
+        assert by[(n, 0.5, None)] != by[(n, 0.5, 0.0)] and by[(n, 0.5, 0.25)] != by[(n, 0.5, 0.0)]
+    assert by[(1, 0.5, 0.0)] == 0.0
+
+
+def test_multiview_loss_with_additional_decay_is_the_per_pair_mean():
+    """oracle.restatement.multiview_loss(additional_decay=a): the mean over pairs of iteration_loss(..., a) on each pair."""
+    g = torch.Generator().manual_seed(3)
+    V, B, I = 3, 4, 3
+    gt = torch.rand(B, V, 2, generator=g) - 0.5
+    pairs = {}
+    for (i, j) in R.view_pairs(V):
+        pd = {"num_iter": I}
+        for it in range(I):
+            pd[f"iter_{it}"] = {"pred_gaze_0": gt[:, i] + 0.1 + 0.2 * torch.rand(B, 2, generator=g),
+                                "pred_gaze_1": gt[:, j] - 0.1 - 0.2 * torch.rand(B, 2, generator=g)}
+        pairs[(i, j)] = pd
+    for a in (None, 0.25, 0.0):
+        want = 0
+        for (i, j), pd in pairs.items():
+            d = dict(pd)
+            d["gt_gaze"], d["gt_gaze_1"] = gt[:, i], gt[:, j]
+            want = want + R.iteration_loss(d, 0.5, 0.01, 1.0, a)
+        got = R.multiview_loss({"pairs": pairs}, gt, 0.5, 0.01, 1.0, a)
+        assert got.item() == (want / 3).item()
+    assert R.multiview_loss({"pairs": pairs}, gt, additional_decay=0.0) != R.multiview_loss({"pairs": pairs}, gt)
 
 
 VARIANTS = {

@@ -139,6 +139,24 @@ def test_rejected_configurations(L, bad):
     assert L.mvg_last_error()
 
 
+def test_split_head_serves_at_most_five_iterations(L):
+    """The split head path's slot arena (11 slots per iteration plus 2 of 64) serves num_iter <= 5: from 1024 rows with split = 1
+    a session of 6 is refused in words, 5 builds, and 6 builds wherever the head does not run on the split Linears (fewer rows,
+    split = 0).  (The training head steps aside to its fp32 Linears instead: tests/test_iter_count_gpu.py.)"""
+    from rot_mvgaze_amd.heads import FusionHead, SPLIT_MIN_ROWS
+    assert [FusionHead.split_serves(i) for i in (1, 5, 6, 7)] == [True, True, False, False]
+    big = dict(depth=18, views=4, batch=96)                   # 4 * 3 * 96 = 1152 rows
+    assert 12 * 96 >= SPLIT_MIN_ROWS > 12 * 85
+    h = C.c_void_p(1)
+    assert L.mvg_session_create(C.byref(_cfg(num_iter=6, split=1, **big)), C.byref(h)) != 0 and h.value is None
+    msg = L.mvg_last_error().decode()
+    assert msg == "session_create: num_iter 6 is more than the split head path's slot arena serves (at most 5)", msg
+    with _Session(L, num_iter=5, split=1, **big) as s:
+        assert s.launches() > 0
+    with _Session(L, num_iter=6, split=0, **big) as a, _Session(L, num_iter=6, split=1, depth=18, views=4, batch=85) as b:
+        assert a.launches() > 0 and b.launches() > 0
+
+
 def _build_standalone(tmp_path, name):
     """tests/native/<name>.cpp and session_plan.cpp, and nothing else, as one executable under ASan + UBSan."""
     cxx = os.environ.get("CXX") or shutil.which("g++") or shutil.which("c++") or shutil.which("clang++")
