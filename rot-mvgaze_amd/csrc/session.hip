@@ -242,7 +242,7 @@ int mvg_session_bind(mvg_session *s, const void *const *host_tensor_ptrs, void *
   }
   if (bf16) {
     // mvg_rotcat_fwd's per-direction source tables (FusionHead._indices: partner = d ^ 1, ident = d); then the bf16 weight
-    // copies as Backbone._prepare_weights / FusionHead._prepare_split_weights(mixed=True) make them (mode 0; KRSC only:
+    // copies as Backbone._prepare_weights / FusionHead._prepare_weights (Family.BF16) make them (mode 0; KRSC only:
     // weights_prep_batch_kernel skips a null transposed pointer in both of its mode-0 branches)
     int32_t partner[SESSION_MAX_VIEWS * (SESSION_MAX_VIEWS - 1)], ident[SESSION_MAX_VIEWS * (SESSION_MAX_VIEWS - 1)];
     for (int k = 0; k < pl.dirs; ++k) {

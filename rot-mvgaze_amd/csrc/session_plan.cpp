@@ -12,11 +12,11 @@
 //   finish          offsets for every buffer and the self-check
 // and two form functions state what differs:
 //   build           the fp32 path: Backbone.forward's 2 GiB guard, the stem, Backbone._unit_infer's launch per unit (fp32-MFMA
-//                   or split), FusionHead.forward's choice between the generated-input fp32-MFMA Linears and _forward_split
-//                   (heads.py: D * B >= 1024 rows)
+//                   or split), heads.plan_head's choice between the generated-input fp32-MFMA Linears (_forward_fp32) and
+//                   _forward_split (heads.py: D * B >= 1024 rows)
 //   build_bf16      the bf16 storage path (MVG_SESSION_BF16): the bf16 branches of Backbone._input_layout, _forward_infer,
-//                   _unit_infer and the non-training pool=True branch of _unit_fwd (backbone.py), and the `mixed` branch of
-//                   FusionHead.forward with Mlp._use_mixed per layer (heads.py)
+//                   _unit_infer and the non-training pool=True branch of _unit_fwd (backbone.py), and a Family.BF16 call of
+//                   FusionHead.forward (_forward_fp32) with heads.layer_launch per layer (heads.py)
 // A change to the forward's order in backbone.py / heads.py is made once here, in the shared part; a change to a form's
 // launches in that form's function.  Buffer ids are creation order and decide the offsets (allocate breaks ties of first use
 // by id), so the order in which each form calls new_buf is part of the plan and is frozen by
@@ -439,7 +439,7 @@ int Builder::build() {
   p.stem_weight = convs[ci_stem].t;
   p.stem_cout = stem.cout;
   if (p.head_split)
-    // FusionHead._prepare_split_weights: heads and fusers from the last iteration down, every layer with fin, fout % 32 == 0
+    // FusionHead._prepare_weights (Family.SPLIT): heads and fusers from the last iteration down, every Launch.SPLIT layer
     for (int i = nmod - 1; i >= 0; --i) {
       prep_lin(hd0[i], 0);
       prep_lin(fu0[i], 0);
@@ -765,10 +765,11 @@ int Builder::build_bf16() {
   // channels padded to 8).  The stem's pass reads [V][cout] rows (Backbone._unit_fwd folds it with G = V): V records of the
   // same BatchNorm, the scale rows first, then the shift rows; every other unit one row, shift behind scale
   register_model(V, true, [](const ConvSpec &s) { return s.cin == 3 ? 8 : s.cin; });
-  // Mlp._use_mixed: a layer runs on mvg_linear_fprop_mixed unless it is padded (a width that is no multiple of 4: none in
-  // the variants a session serves) or it is a module's last layer with fout <= 4 (the heads' 512 -> 2: mvg_linear_skinny_fwd)
+  // heads.layer_launch: a layer is Launch.BF16 (mvg_linear_fprop_mixed) unless it is padded (a width that is no multiple of
+  // 4: none in the variants a session serves) or it is a module's last layer with fout <= 4 (the heads' 512 -> 2:
+  // mvg_linear_skinny_fwd)
   auto use_mixed = [](const Lin &l, bool last) { return l.fin % 4 == 0 && l.fout % 4 == 0 && !(last && l.fout <= 4); };
-  // FusionHead._prepare_split_weights(mixed=True): the lifter, then heads and fusers from the last iteration down
+  // FusionHead._prepare_weights (Family.BF16): the lifter, then heads and fusers from the last iteration down
   auto prep_mixed = [&](Lin &l, bool last) {
     if (use_mixed(l, last)) prep_lin(l, l.fin);
   };

@@ -5,7 +5,8 @@ replaced by a proxy; the two methods are wrapped to switch the recording) - the 
 argument, every integer and float argument, whether each pointer argument is null (by the argument types of _lib.SIGNATURES),
 and the stream the call is queued on as an ordinal by first appearance.  Pointer VALUES are not recorded: addresses depend on
 allocation order, which may change.  mvg_set_scratch / mvg_scratch_bytes are left out: whether a stream's workspace is
-already registered depends on what ran earlier in the process.
+already registered depends on what ran earlier in the process.  (The recorder is tests/launch_trace.py, shared with
+tests/test_head_trace_gpu.py.)
 
 tests/golden/backbone_launch_traces.txt holds, per case, a sha256 of the trace, the number of calls and the count per entry
 point; on a mismatch the test says which counts moved.  The file is rewritten by
@@ -15,12 +16,9 @@ keeps the file as the commit before it wrote it: the sequence of launches, their
 
 The module goes through the model's public surface only (attributes of the model and of model._backbone), so it runs on any
 commit that has them.  CASES and run_case are shared with scripts/step_digest.py (the same cases, hashed by value)."""
-import ctypes as C
-import hashlib
 import os
 import random
 import sys
-from collections import Counter
 
 import numpy as np
 import pytest
@@ -30,12 +28,13 @@ if __name__ == "__main__":
     sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 
 import rot_mvgaze_amd  # noqa: F401,E402
-from rot_mvgaze_amd import _lib, ops, synth  # noqa: E402
+from rot_mvgaze_amd import ops, synth  # noqa: E402
+
+import launch_trace as LT  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 GOLDEN_FILE = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "backbone_launch_traces.txt")
 BB = "_feat_extractor.0."
-UNRECORDED = ("mvg_set_scratch", "mvg_scratch_bytes")
 ALL_FUSIONS_OFF = dict(fuse_bn_split=False, fuse_bn_apply_dgrad=False, fuse_bn_apply_fprop=False, relu_bits=False, overlap_wgrad=False)
 
 # name -> how the case is run (run_case): V = 2, B = 2 throughout; 64 x 64 unless hw says otherwise.
@@ -128,126 +127,26 @@ def run_case(name):
     return m, out, loss
 
 
-class _Recorder:
-    """The proxy that stands in for the loaded library: every mvg_* call made while ``depth`` > 0 becomes one trace line."""
-
-    def __init__(self, real):
-        self.real, self.depth, self.lines, self.streams, self.fns = real, 0, [], {}, {}
-
-    def __getattr__(self, name):
-        fn = self.fns.get(name)
-        if fn is None:
-            real_fn = getattr(self.real, name)
-            if not name.startswith("mvg_") or name in UNRECORDED:
-                fn = real_fn
-            else:
-                argtypes = _lib.SIGNATURES[name][1]
-
-                def fn(*args, _real=real_fn, _name=name, _types=argtypes):
-                    if self.depth > 0:
-                        self.lines.append(self.describe(_name, _types, args))
-                    return _real(*args)
-            self.fns[name] = fn
-        return fn
-
-    def describe(self, name, argtypes, args):
-        assert len(args) == len(argtypes), name
-        parts = [name]
-        for t, a in zip(argtypes, args):
-            if t is _lib._D:
-                d = a._obj                                           # C.byref(desc)
-                parts.append("desc(" + ",".join(str(getattr(d, f)) for f, _ in _lib.ConvDesc._fields_) + ")")
-            elif t is _lib._P:
-                v = a.value if isinstance(a, C.c_void_p) else a
-                parts.append("null" if not v else "ptr")
-            elif t in (_lib._I, _lib._I64, C.c_int32, C.c_size_t, C.c_uint64):
-                parts.append(str(int(a)))
-            elif t is _lib._F:
-                parts.append(repr(float(a)))
-            else:                                                    # a host array or an out-parameter
-                parts.append("null" if a is None else "ref")
-        handle = torch.cuda.current_stream().cuda_stream
-        parts.append("stream%d" % self.streams.setdefault(handle, len(self.streams)))
-        return " ".join(parts)
-
-
 def trace_case(name):
-    """The trace lines of one case, and whatever the case's hook returns from (model, data, loss)."""
+    """The trace lines of one case, and whether its stem ran in row-window form."""
     from rot_mvgaze_amd.backbone import Backbone
-    rec = _Recorder(_lib.lib())
-    saved_lib, saved = ops.lib, {n: getattr(Backbone, n) for n in ("forward", "backward")}
-
-    def switched(orig):
-        def method(self, *a, **kw):
-            rec.depth += 1
-            try:
-                return orig(self, *a, **kw)
-            finally:
-                rec.depth -= 1
-        return method
-    ops.lib = lambda: rec
-    for n, orig in saved.items():
-        setattr(Backbone, n, switched(orig))
-    try:
-        m, out, loss = run_case(name)
-        stem_rw = bool(m._backbone._stem_rw)
-    finally:
-        ops.lib = saved_lib
-        for n, orig in saved.items():
-            setattr(Backbone, n, orig)
-    return rec.lines, stem_rw
-
-
-def summarise(lines):
-    counts = Counter(l.split(" ", 1)[0] for l in lines)
-    return hashlib.sha256("\n".join(lines).encode()).hexdigest(), len(lines), dict(sorted(counts.items()))
-
-
-def read_golden():
-    golden = {}
-    with open(GOLDEN_FILE) as f:
-        for line in f:
-            if line.strip() and not line.startswith("#"):
-                name, digest, n, counts = line.split()
-                golden[name] = (digest, int(n), {k: int(v) for k, v in (kv.split("=") for kv in counts.split(","))})
-    return golden
+    lines, (m, out, loss) = LT.record(Backbone, ("forward", "backward"), lambda: run_case(name))
+    return lines, bool(m._backbone._stem_rw)
 
 
 @pytest.mark.parametrize("name", sorted(CASES))
 def test_launch_trace_is_the_recorded_one(name):
     lines, stem_rw = trace_case(name)
-    digest, n, counts = summarise(lines)
+    digest, n, counts = LT.summarise(lines)
     if name == "01_r50_fp32_train":          # the loader-formed launches are reached at this size
         assert counts.get("mvg_conv_fprop_split_bnapply", 0) >= 1 and counts.get("mvg_conv_dgrad_split_bnapply_bnreduce", 0) >= 1, counts
     if name == "07_r50_bf16_train_72":       # 2 * 36 * 18 partial rows: no multiple of 64, the NHWC8 stem
         assert stem_rw is False
-    want_digest, want_n, want_counts = read_golden()[name]
-    moved = {k: (want_counts.get(k, 0), counts.get(k, 0)) for k in sorted(set(counts) | set(want_counts))
-             if counts.get(k, 0) != want_counts.get(k, 0)}
-    assert not moved, f"{name}: launches per entry point moved (recorded, now): {moved}"
-    assert n == want_n
-    assert digest == want_digest, (f"{name}: the same {n} calls per entry point, but their order, arguments or streams differ: "
-                                   "diff the output of --dump DIR on the two commits")
+    LT.assert_matches_golden(name, lines, LT.read_golden(GOLDEN_FILE), "test_backbone_trace_gpu.py")
 
 
 def main(argv):
-    if len(argv) == 2 and argv[0] == "--dump":
-        os.makedirs(argv[1], exist_ok=True)
-    elif argv != ["--write"]:
-        raise SystemExit("usage: test_backbone_trace_gpu.py --write | --dump DIR")
-    rows = []
-    for name in sorted(CASES):
-        lines, _ = trace_case(name)
-        digest, n, counts = summarise(lines)
-        rows.append(f"{name} {digest} {n} " + ",".join(f"{k}={v}" for k, v in counts.items()))
-        print(rows[-1].split(" ")[0], digest, n, flush=True)
-        if argv[0] == "--dump":
-            with open(os.path.join(argv[1], name + ".txt"), "w") as f:
-                f.write("\n".join(lines) + "\n")
-    if argv[0] == "--write":
-        with open(GOLDEN_FILE, "w") as f:
-            f.write("# case sha256(trace) calls entry=count,...   (python tests/test_backbone_trace_gpu.py --write)\n")
-            f.write("\n".join(rows) + "\n")
+    LT.write_or_dump(argv, sorted(CASES), lambda name: trace_case(name)[0], GOLDEN_FILE, "test_backbone_trace_gpu.py")
 
 
 if __name__ == "__main__":

@@ -113,7 +113,7 @@ def test_fp32_plan_unchanged(L, depth):
 
 # ---------------------------------------------------------------- 3. the bf16 plan's order
 def _mixed_mlp(fins_fouts):
-    """heads._Mlp.forward with mixed = True over layers (fin, fout): _use_mixed(l) unless the layer is padded (a width that is
+    """heads._Mlp.forward on a Family.BF16 call over layers (fin, fout): Launch.BF16 unless the layer is padded (a width that is
     no multiple of 4 -> linear_fprop on zero-padded copies) or it is the last layer with fout <= 4 (linear_skinny_fwd)."""
     out = []
     for l, (fin, fout) in enumerate(fins_fouts):
