@@ -861,6 +861,38 @@ int mvg_bn_relu_maxpool_fwd_split_scaled(const float *y, const float *scale, con
                                          const float *pooled_sinv, uint8_t *argmax, int groups, int n_per_group, int h, int w,
                                          int c, int ho, int wo, void *stream);
 int mvg_avgpool_fwd_split_scaled(const void *x_sp, const float *x_sinv, float *y, int n, int hw, int c, void *stream);
+/* Frozen-BatchNorm training steps on the split kernels (Backbone.split_frozen; added under ABI v13: additive).  A unit on the
+ * running statistics has no z-score bound, so its activation scale comes from the conv launch's own statistics partials
+ * (mvg_conv_fprop_split / mvg_stem_fprop_split: `stats`, the layout mvg_bn_finalize reads) - no pass over an activation.  With
+ * mean_b, var_b (biased) of the n = rows_per_group conv outputs of a (group, channel), every element obeys
+ * |y - mean_b| <= sqrt((n - 1) var_b), hence
+ *   |gamma invstd_r (y - rm) + beta| <= |gamma| invstd_r (|mean_b - rm| + sqrt((n - 1) var_b)) + |beta|,
+ *   bound(unit) = max over (group, channel) of that,  bound(block output) = bound(last unit) + bound(identity).
+ * mvg_bn_frozen_finalize, ONE launch per unit in place of mvg_bn_eval_affine:
+ *   scale, shift [groups][c]   the bits mvg_bn_eval_affine writes;
+ *   mean, invstd [groups][c]   running_mean and 1 / sqrt(running_var + eps), broadcast over the groups: what the reduce entry
+ *                              points of the backward (mvg_conv_dgrad_split_bnreduce, mvg_bn_bwd_reduce_split, the stem's) read;
+ *   state                      4 device floats of the unit, state[0] and state[1] ZERO on entry (an integer maximum and an
+ *                              arrival count: the last workgroup to arrive finishes the unit); state[2] receives the chained
+ *                              bound = bound(unit) (+ *ident_bound, the state[2] of an EARLIER unit, or NULL);
+ *   slot (may be NULL)         receives 2^-k by mvg_act_scales' rule: 1 while 1 <= bound < 2^15, else the power of two that
+ *                              maps the bound just below 2^15; a zero, infinite or NaN bound gives 1.
+ * Rounding may only enlarge the bound: the partials are merged in float64 (mvg_bn_finalize's pivoted Chan merge), the
+ * expression is evaluated in float64, and a final factor 1 + 2^-7 (ops.FROZEN_BOUND_MARGIN) covers the fp32 rounding of the
+ * partials themselves and of the chained sum.  The 2^15 target leaves another factor of two below 65 520.  The running
+ * statistics are read, never written.
+ * mvg_bn_frozen_bwd_apply_split: the backward apply pass of such a unit, dy = sp(gamma_c invstd_c dz 2^k) in one pass - no batch
+ * sums.  g already masked, or the mask from fma(y, relu_scale, relu_shift) > 0 (y is read in this form only), or no ReLU
+ * (both NULL).  invstd [groups][c] as mvg_bn_frozen_finalize left it; *dy_sinv = 2^-k as the reduce entry points leave it from
+ * |gamma invstd| (mx + |s1|/n + sqrt(n) |s2|/n), which only adds non-negative terms to |gamma invstd| mx >= |dy|: the
+ * train-mode bound holds for the frozen dy and is kept.  c % 8 == 0. */
+int mvg_bn_frozen_finalize(const float *stats, int groups, int partials, int rows_per_partial, int64_t rows_per_group, int c,
+                           const float *gamma, const float *beta, const float *running_mean, const float *running_var, float eps,
+                           const float *ident_bound, float *mean, float *invstd, float *scale, float *shift, float *state,
+                           float *slot, void *stream);
+int mvg_bn_frozen_bwd_apply_split(const float *g, const float *y, const float *invstd, const float *gamma, const float *relu_scale,
+                                  const float *relu_shift, int groups, int64_t rows_per_group, int c, void *dy_sp,
+                                  const float *dy_sinv, void *stream);
 /* mvg_conv_dgrad_split fused with the BatchNorm-backward reduce pass of the unit whose output gradient dx is (stride 1
  * or 2: a stride-2 launch's parity classes - those a 1x1 filter never touches included - each bring their partials): dx is stored masked by that unit's ReLU (bn_bits from mvg_bn_apply_split, or fma(bn_y, relu_scale,
  * relu_shift) > 0, or no mask) and s1 / s2 / dgamma / dbeta come out of the same launch + a finalize; mx [groups][cin] (may be

@@ -128,7 +128,10 @@ SIGNATURES = {
     "mvg_bn_apply_split_scaled": (_I, [_P, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I64, _I, _P]),
     "mvg_bn_relu_maxpool_fwd_split_scaled": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "mvg_avgpool_fwd_split_scaled": (_I, [_P, _P, _P, _I, _I, _I, _P]),
-    "mvg_conv_wgrad_split_xs": (_I, [_D, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
+    # frozen-BatchNorm training steps on the split kernels (Backbone.split_frozen)
+    "mvg_bn_frozen_finalize": (_I, [_P, _I, _I, _I, _I64, _I, _P, _P, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "mvg_bn_frozen_bwd_apply_split": (_I, [_P, _P, _P, _P, _P, _P, _I, _I64, _I, _P, _P, _P]),
+    "mvg_conv_wgrad_split_xs":(_I, [_D, _P, _P, _P, _P, _P, _P, _I, _I, _P]),
     "mvg_conv_wgrad_split_slabs_xs": (_I, [_D, _P, _P, _P, _P, _P, _I, _P]),
     "mvg_stem_rowwindow_split": (_I, [_P, _P, _I64, _I, _I, _P]),
     "mvg_stem_rowwindow_split_nchw": (_I, [_P, _P, _I64, _I, _I, _P]),

@@ -162,13 +162,17 @@ def plan_call(spec: BackboneSpec, *, V: int, B: int, H: int, W: int, training: b
               augment: bool = False, need_dimg: bool = False, boundary: int = -1, bf16: bool = False, split: bool = True,
               split_eval: bool = True, split_eval_guard: Optional[str] = None, stem_rowwindow: bool = True,
               batch_weight_prep: bool = True, bf16_fold_eval: bool = True, guard_scale: int = 1, tripped: bool = False,
-              capturing: bool = False, train_step: Optional[bool] = None) -> Call:
+              capturing: bool = False, train_step: Optional[bool] = None, split_frozen: bool = False) -> Call:
     """The size and mode decisions of one forward call, from shapes and flags alone (no tensor, no device).  raw: uint8
     patches; augment: an input augment is set; tripped: an earlier "fallback" call overflowed (Backbone._range_tripped);
     capturing: the stream is being captured; the other flags are the Backbone attributes of the same names.
     training: BatchNorm on batch statistics; train_step (None: = training): the call is a training step - the augment is
     applied and raw patches with one are accepted on the bf16 path.  A frozen-BatchNorm step is training False, train_step
-    True: it has no statistics, so no row-window stem and no sp storage, exactly like a taped eval forward."""
+    True: it has no statistics, so no row-window stem and no sp storage, exactly like a taped eval forward - unless
+    split_frozen (Backbone.split_frozen) is set: a frozen step of the fp32 model that keeps a tape, wants no d(img) and passes
+    the 2 GiB guard then stores its activations in sp (the scales come from the conv launches' statistics partials:
+    ops.bn_frozen_finalize) and takes the row-window stem under the conditions a train-mode step does.  Everywhere else -
+    eval-mode tapes, need_dimg, the bf16 path, MVG_SPLIT=0, the guard - the flag is inert."""
     step = training if train_step is None else bool(train_step)
     if bf16 and raw and (step or keep_tape) and not (step and augment):
         raise NotImplementedError("raw uint8 input with the bf16 path is served for inference only (model.eval() under "
@@ -189,18 +193,27 @@ def plan_call(spec: BackboneSpec, *, V: int, B: int, H: int, W: int, training: b
     if guard == "fallback" and tripped:
         split = False                        # an earlier call overflowed: fp32-MFMA kernels until the weights change
     # the stem's form for this call (see stem_rowwindow)
+    frozen = False
     if bf16:        # folded windows: width % 4, whole 64-row partials (n * ho * wo / 2), the stem's weights through the batch
         ho, wo = (H - 1) // 2 + 1, W // 2
         stem_rw = (stem_rowwindow and training and W % 4 == 0 and (B * ho * (wo // 2)) % 64 == 0 and batch_weight_prep
                    and spec.stem.k == 7)
     else:
-        stem_rw = (split and stem_rowwindow and training and not need_dimg and W % 2 == 0
+        # a frozen-BatchNorm step on the split kernels (see frozen_split)
+        frozen = bool(split_frozen and split and step and not training and keep_tape and not need_dimg)
+        stem_rw = (split and stem_rowwindow and (training or frozen) and not need_dimg and W % 2 == 0
                    and batch_weight_prep and 32 * B * H * (W // 2) * 4 < 0x7FFFFFF0)
     taped = training or keep_tape or (bf16 and not bf16_fold_eval)
     # sp storage: training steps of the fp32 model; folded inference with split_eval (an eval-mode tape: fp32-MFMA kernels)
-    sp = split and not bf16 and (training or (infer and split_eval))
+    sp = split and not bf16 and (training or (infer and split_eval) or frozen)
     return Call(V, B, H, W, training, keep_tape, bf16, split, sp, stem_rw, taped, guard,
                 range_live=guard is not None and sp, need_dimg=need_dimg, boundary=boundary, train_step=step)
+
+
+def frozen_split(call: Call) -> bool:
+    """Whether ``call`` is a frozen-BatchNorm training step on the split kernels (plan_call's split_frozen): sp storage on the
+    running statistics with a tape - the one sp call that is neither a train-mode step nor folded inference."""
+    return bool(call.sp and not call.training and call.keep_tape)
 
 
 def unit_family(call: Call, c: ConvSpec) -> Family:
@@ -211,6 +224,12 @@ def unit_family(call: Call, c: ConvSpec) -> Family:
     if call.sp and (c.cin != 3 or call.stem_rw):
         return Family.SPLIT
     return Family.FP32
+
+
+class _FrozenScales(dict):
+    """Call.act_sinv of a frozen step on the split kernels: conv name -> slot as ever, plus ``state``: conv name -> (the unit's
+    4-float bound record, the identity's chained bound or None) - downsample units have a record and no slot."""
+    state: Dict[str, tuple]
 
 
 class _Apply(NamedTuple):
@@ -332,6 +351,12 @@ class Backbone:
         # d(loss)/d(img) (the backward-data launch runs on the fp32 kernel) or the width is odd.
         self.stem_rowwindow = True
         self.split_eval = True      # inference forward on the split kernels too
+        # frozen-BatchNorm training steps (training False, train_step True) of the fp32 model on the split kernels as well
+        # (plan_call; off: such a step runs on the fp32-MFMA kernels like an eval-mode tape).  Every unit's launch then leaves
+        # its statistics partials as in train mode, and ONE launch per unit (ops.bn_frozen_finalize, in place of
+        # bn_eval_affine) turns them into the 2^-k of the unit's sp output: running statistics bound nothing, the conv's own
+        # batch statistics do.  The backward's reduce forms run on the running (mean, invstd), its apply pass needs no sums.
+        self.split_frozen = False
         # Inference on the split kernels stores every activation as two UNSCALED fp16 pieces, and running statistics bound
         # nothing: a checkpoint whose activation reaches 65 520 stores inf, merges to NaN, and a later ReLU can turn that into 0.
         # The guard (folded fp32 inference only; the taped paths and the bf16 path ignore it) makes every sp-producing launch
@@ -360,6 +385,7 @@ class Backbone:
         self._wprep_versions = None
         # split path, training: per-tensor scales of the sp activations (one launch per step: _prepare_act_scales)
         self._ascale_state = None             # (key, device table, records, conv name -> slot, slots)
+        self._frozen_plan = None              # frozen steps on the split kernels: [(conv name, identity's conv name or None, has slot)]
         self._wg_defer: Optional[list] = None # backward: (slabs, dw, splits, accumulate) of the split wgrads whose reduce is pending
         self._last_call: Optional[Call] = None    # the record of the last forward call (tests and tools read it through the properties below)
         self._stem_w8 = None
@@ -499,6 +525,38 @@ class Backbone:
         ops.act_scales(table, n, slots)
         views = slots.split(1)
         return {name: views[i] for name, i in slot_of.items()}
+
+    def _prepare_frozen_scales(self, dev):
+        """The slots and bound records of a frozen-BatchNorm step on the split kernels.  Nothing is computed here: every unit's
+        ops.bn_frozen_finalize launch fills its own slot from its conv's statistics partials and chains its bound to its
+        identity's - the previous block's last unit (first block: the stem), or the block's downsample unit, which has a bound
+        and no slot.  Both tensors are fresh per step (the records arrive zeroed: one fill), the slots kept alive by the sp
+        tensors that carry their 1-element views as ``.sinv``.  Returns a _FrozenScales."""
+        s = self.spec
+        if self._frozen_plan is None:
+            plan = [(s.stem.name, None, True)]
+            prev = s.stem.name
+            for blk in s.blocks:
+                plan += [(c.name, None, True) for c in blk.convs[:-1]]
+                ident = prev
+                if blk.downsample is not None:
+                    plan.append((blk.downsample.name, None, False))
+                    ident = blk.downsample.name
+                plan.append((blk.convs[-1].name, ident, True))
+                prev = blk.convs[-1].name
+            self._frozen_plan = plan
+        plan = self._frozen_plan
+        records = torch.zeros(len(plan), 4, dtype=torch.float32, device=dev)
+        slots = torch.empty(sum(1 for _, _, has in plan if has), dtype=torch.float32, device=dev).split(1)
+        row = {name: i for i, (name, _, _) in enumerate(plan)}
+        sinv, state, k = _FrozenScales(), {}, 0
+        for name, ident, has in plan:
+            if has:
+                sinv[name] = slots[k]
+                k += 1
+            state[name] = (records[row[name]], records[row[ident]][2:3] if ident is not None else None)
+        sinv.state = state
+        return sinv
 
     def invalidate_weight_cache(self):
         """Forget the inference path's cached sp (bf16 path: bf16) copies of the conv weights.  The cache is keyed on each parameter's
@@ -648,9 +706,10 @@ class Backbone:
         w, w_t = self._conv_weights(call, c, d, family, keep)
         rows = N * d.ho * d.wo
         # training: (partials per group, rows per partial) of the batch statistics that the conv launch leaves
-        partials = self._stats_partials(c, d, family, stem_rw) if training else None
+        # (a frozen step on the split kernels asks for them too: its activation scales come from them)
+        partials = self._stats_partials(c, d, family, stem_rw) if (training or frozen_split(call)) else None
         y, stats = self._conv_fwd(c, d, family, stem_rw, x, w, pending_apply, partials)
-        mean, invstd, scale, shift = self._bn_fwd_stats(c, G, rows, stats, partials)
+        mean, invstd, scale, shift = self._bn_fwd_stats(call, c, G, rows, stats, partials)
         out = bits = pool_rec = handed = None
         if defer_apply:
             assert not relu and residual is None and not pool
@@ -696,13 +755,20 @@ class Backbone:
             ops.conv_fprop(d, x, w, y, None, False, stats)
         return y, stats
 
-    def _bn_fwd_stats(self, c: ConvSpec, G: int, rows: int, stats: Optional[Tensor], partials: Optional[tuple]):
+    def _bn_fwd_stats(self, call: Call, c: ConvSpec, G: int, rows: int, stats: Optional[Tensor], partials: Optional[tuple]):
         """Stage 2 of _unit_fwd: (mean, invstd, scale, shift) from the launch's partials (training: batch statistics, and the
-        running ones updated), else from the running statistics (mean / invstd are then left unfilled)."""
+        running ones updated), else from the running statistics (mean / invstd are then left unfilled) - but for a frozen step
+        on the split kernels: one launch writes the eval-mode (scale, shift), mean / invstd := the running values for the
+        backward's reduce forms, and from the partials the unit's bound and the 2^-k of its sp output."""
         gamma, beta = self.p[c.bn + ".weight"].detach(), self.p[c.bn + ".bias"].detach()
         rm, rv = self.p[c.bn + ".running_mean"], self.p[c.bn + ".running_var"]
         mean, invstd, scale, shift = torch.empty(4, G, c.cout, dtype=torch.float32, device=gamma.device)
-        if partials is not None:
+        if frozen_split(call):
+            P, rpp = partials
+            state, ident = call.act_sinv.state[c.name]
+            ops.bn_frozen_finalize(stats, G, P, rpp, rows, c.cout, gamma, beta, rm, rv, BN_EPS, mean, invstd, scale, shift, state,
+                                   call.act_sinv.get(c.name), ident)
+        elif partials is not None:
             P, rpp = partials
             ops.bn_finalize(stats, G, P, rpp, rows, c.cout, gamma, beta, rm, rv, BN_MOMENTUM, BN_EPS, mean, invstd,
                             scale, shift)
@@ -831,17 +897,21 @@ class Backbone:
                          stem_rowwindow=self.stem_rowwindow, batch_weight_prep=self.batch_weight_prep,
                          bf16_fold_eval=self.bf16_fold_eval, guard_scale=self._guard_scale, tripped=self._range_tripped,
                          capturing=self.split_eval_guard == "fallback" and torch.cuda.is_current_stream_capturing(),
-                         train_step=step)
+                         train_step=step, split_frozen=self.split_frozen)
         x0 = self._input_layout(call, imgs, input_bgr, input_augment if (raw and step) else None)
         if step:
             self.invalidate_weight_cache()       # the weights are about to change: drop the inference copies
         wprep = None
-        if self.batch_weight_prep and (call.bf16 or (call.sp and training)):
+        frozen = frozen_split(call)
+        if self.batch_weight_prep and (call.bf16 or (call.sp and (training or frozen))):
             wprep = self._prepare_weights(dev, Family.BF16 if call.bf16 else Family.SPLIT, call.stem_rw,
                                           reuse=call.bf16 and self.bf16_fold_eval and not training and not keep_tape)
         # ... and one launch gives every sp activation of the step its scale (x, out and identity carry it as .sinv; the
         # tape's x_in / out keep it for the backward's weight gradients)
-        call = call._replace(wprep=wprep, act_sinv=self._prepare_act_scales(dev, B, H, W) if (call.sp and training) else None)
+        if frozen:        # ... or, on the running statistics, every unit's own finalize launch does (the slots arrive unfilled)
+            call = call._replace(wprep=wprep, act_sinv=self._prepare_frozen_scales(dev))
+        else:
+            call = call._replace(wprep=wprep, act_sinv=self._prepare_act_scales(dev, B, H, W) if (call.sp and training) else None)
         # (V, B and boundary stay as keys of their own: tests and tools read them)
         tape: Optional[dict] = {"units": [], "blocks": [], "call": call, "V": V, "B": B, "boundary": call.boundary} if keep_tape else None
         if keep_tape and wprep is not None:
@@ -966,6 +1036,8 @@ class Backbone:
         dz = g masked by the unit's ReLU (written in place into g) when the residual branch needs it.
         defer_apply (a unit that bn_apply_dgrad_eligible accepted): dy is only allocated - the unit's backward-data launch
         forms and writes it from ``pending`` (a _PendingDy; else None)."""
+        if not u.trained and u.family is Family.SPLIT:
+            return self._bn_bwd_frozen_split(u, g, need_dz, sink) + (None,)
         if not u.trained:
             return self._bn_bwd_eval(u, g, need_dz, sink) + (None,)
         c = u.spec
@@ -1038,6 +1110,29 @@ class Backbone:
         dy = torch.empty_like(g) if need_dz else g
         ops.bn_eval_bwd(g, u.y, gp.detach(), rm, rv, BN_EPS, G, u.rows, c.cout, dy, sink.view(gp), sink.view(bp), acc,
                         dz_out=g if need_dz else None, **mask)
+        return dy, (g if need_dz else None)
+
+    def _bn_bwd_frozen_split(self, u: _Unit, g: Tensor, need_dz: bool, sink: GradSink):
+        """_bn_bwd for a unit of a frozen-BatchNorm step on the split kernels: the reduce forms of a trained unit - fused into
+        the backward-data launch that produced g, or the pass of its own - run on the tape's (mean, invstd), which hold the
+        running values, so their s1 / s2 ARE dbeta / dgamma and their dy scale bounds the frozen dy; the apply pass is
+        ops.bn_frozen_bwd_apply_split: dy = gamma invstd dz in sp, one pass, no sums."""
+        c = u.spec
+        G = u.y.shape[0]
+        gp, bp, acc = self._bn_params(c, sink)
+        fs, u.fused_s12 = u.fused_s12, None
+        dy = ops.sp_empty(*u.y.shape, device=g.device)
+        if fs is not None:                    # g arrived masked; dgamma, dbeta and the scale came with it
+            ops.bn_frozen_bwd_apply_split(g, u.y, u.invstd, gp.detach(), G, u.rows, c.cout, dy, fs.sinv)
+            return dy, (g if need_dz else None)
+        bits, ra = u.relu_bits, u.relu_affine
+        assert not (u.relu and ra is None) or bits is not None
+        s12 = torch.empty(3, G, c.cout, dtype=torch.float32, device=g.device)     # s1, s2, max |dz| per channel
+        sinv = torch.empty(1, dtype=torch.float32, device=g.device)
+        ra = None if bits is not None else ra                 # one mask source; with bits the reduce pass leaves dz in g
+        ops.bn_bwd_reduce_split(g, bits, u.y, u.mean, u.invstd, G, u.rows, c.cout, s12[0], s12[1], sink.view(gp), sink.view(bp),
+                                acc, s12[2], ra, dz_out=g if bits is not None else None, gamma=gp.detach(), dy_sinv=sinv)
+        ops.bn_frozen_bwd_apply_split(g, u.y, u.invstd, gp.detach(), G, u.rows, c.cout, dy, sinv, ra)
         return dy, (g if need_dz else None)
 
     def _side(self, dev) -> "torch.cuda.Stream":
@@ -1183,7 +1278,18 @@ class Backbone:
         gp, bp, acc = self._bn_params(sc, sink)
         stem_sp = stem.family is Family.SPLIT       # (the row-window stem of a split call)
         s12 = torch.empty(3 if stem_sp else 2, V, sc.cout, dtype=torch.float32, device=g.device)
-        if not stem.trained:
+        if not stem.trained and stem_sp:
+            # a frozen step with the row-window stem (once per step: no form of its own): the train-mode pair on the running
+            # (mean, invstd) the tape holds - the reduce pass leaves dbeta, dgamma and a dy scale whose bound only gains
+            # non-negative terms from the sums - and the apply pass with ZERO sums: dy = gamma invstd dz exactly
+            sinv = torch.empty(1, dtype=torch.float32, device=g.device)
+            ops.bn_relu_maxpool_bwd_reduce_split(g, argmax, stem.y, stem.mean, stem.invstd, scale, shift, V, B, H1, W1, sc.cout, Hp, Wp,
+                                                 s12[0], s12[1], sink.view(gp), sink.view(bp), acc, s12[2], gp.detach(), sinv)
+            zero = torch.zeros(2, V, sc.cout, dtype=torch.float32, device=g.device)
+            dy = ops.sp_empty(*stem.y.shape, device=g.device)
+            ops.bn_relu_maxpool_bwd_apply_split(g, argmax, stem.y, stem.mean, stem.invstd, gp.detach(), scale, shift, zero[0], zero[1],
+                                                V, B, H1, W1, sc.cout, Hp, Wp, dy, s12[2], sinv)
+        elif not stem.trained:
             # eval mode: max pool + ReLU + BatchNorm on the running statistics, one pass (no batch sums to wait for)
             dy = torch.empty_like(stem.y)
             ops.bn_relu_maxpool_eval_bwd(g, argmax, stem.y, scale, shift, gp.detach(), P[sc.bn + ".running_mean"],

@@ -19,6 +19,36 @@ __device__ __forceinline__ double bn_merge_pivot(const float *__restrict__ st, i
   return (double)st[ch] / (double)(rows < rows_per_partial ? rows : (long long)rows_per_partial);
 }
 
+// One lane's share of a group's partials - lane pl takes every 128th - as the pivoted sums every merge kernel reduces:
+// s = sum (s_p - cnt_p pivot), q = sum q_p, ss = sum (s_p - cnt_p pivot)^2 / cnt_p.  (bn_finalize_kernel, bn_finalize_group_kernel and
+// bn_frozen_finalize_kernel call this: one statement of the merge.)
+__device__ __forceinline__ void bn_merge_lane(const float *__restrict__ st, int ch, int c, int pl, int partials, int rows_per_partial,
+                                              long long rows, double pivot, double &s, double &q, double &ss) {
+  const double inv_full = 1.0 / (double)rows_per_partial;
+  // branch-free body (no early exit) so that the loads of several iterations are in flight at once
+  const int valid = (int)((rows + rows_per_partial - 1) / rows_per_partial) < partials
+                        ? (int)((rows + rows_per_partial - 1) / rows_per_partial) : partials;
+  const double full_pivot = (double)rows_per_partial * pivot;
+#pragma unroll 4
+  for (int p = pl; p < valid; p += 128) {
+    const float sp_f = st[((long long)p * 2) * c + ch];
+    const float qp_f = st[((long long)p * 2 + 1) * c + ch];
+    const double sp = (double)sp_f - full_pivot, qp = qp_f;
+    s += sp;
+    q += qp;
+    ss += sp * sp;
+  }
+  ss *= inv_full;
+  // the ragged last partial was taken as a full one above (pivot and 1/rows_per_partial): correct it to its count
+  const long long last_cnt = rows - (long long)(valid - 1) * rows_per_partial;
+  if (valid > 0 && last_cnt < rows_per_partial && ((valid - 1) & 127) == pl) {
+    const double raw = st[((long long)(valid - 1) * 2) * c + ch];
+    const double was = raw - full_pivot, sp = raw - (double)last_cnt * pivot;
+    s += sp - was;
+    ss += sp * sp / (double)last_cnt - was * was * inv_full;
+  }
+}
+
 // grid = c/8 blocks, 1024 threads = 8 channels x 128 partial-lanes.  Every group (= view) is merged
 // by the same workgroup, one after the other, so that the running statistics are updated in group
 // order (the reference runs the backbone on view 0, then view 1: models/rot_mv.py:204-205).
@@ -33,7 +63,6 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float *__restri
   __shared__ double sh[3][128][8];
   const int cl = threadIdx.x & 7, pl = threadIdx.x >> 3;
   const int ch = blockIdx.x * 8 + cl;
-  const double inv_full = 1.0 / (double)rows_per_partial;
   float rm = 0.f, rv = 0.f;
   if (pl == 0 && ch < c) {
     if (running_mean) rm = running_mean[ch];
@@ -51,28 +80,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_kernel(const float *__restri
         ss += o[2 * c + ch];
       }
     } else if (ch < c) {
-      // branch-free body (no early exit) so that the loads of several iterations are in flight at once
-      const int valid = (int)((rows + rows_per_partial - 1) / rows_per_partial) < partials
-                            ? (int)((rows + rows_per_partial - 1) / rows_per_partial) : partials;
-      const double full_pivot = (double)rows_per_partial * pivot;
-#pragma unroll 4
-      for (int p = pl; p < valid; p += 128) {
-        const float sp_f = st[((long long)p * 2) * c + ch];
-        const float qp_f = st[((long long)p * 2 + 1) * c + ch];
-        const double sp = (double)sp_f - full_pivot, qp = qp_f;
-        s += sp;
-        q += qp;
-        ss += sp * sp;
-      }
-      ss *= inv_full;
-      // the ragged last partial was taken as a full one above (pivot and 1/rows_per_partial): correct it to its count
-      const long long last_cnt = rows - (long long)(valid - 1) * rows_per_partial;
-      if (valid > 0 && last_cnt < rows_per_partial && ((valid - 1) & 127) == pl) {
-        const double raw = st[((long long)(valid - 1) * 2) * c + ch];
-        const double was = raw - full_pivot, sp = raw - (double)last_cnt * pivot;
-        s += sp - was;
-        ss += sp * sp / (double)last_cnt - was * was * inv_full;
-      }
+      bn_merge_lane(st, ch, c, pl, partials, rows_per_partial, rows, pivot, s, q, ss);
     }
     // reduce over the 128 partial lanes: lanes 8/16/32 apart inside the wave (shuffles), then the 16
     // waves through LDS - two barriers per group instead of an 8-level LDS tree
@@ -143,7 +151,6 @@ __global__ __launch_bounds__(1024) void bn_finalize_group_kernel(const float *__
   const int cl = threadIdx.x & 7, pl = threadIdx.x >> 3;
   const int ch = blockIdx.x * 8 + cl;
   const int g = blockIdx.y, groups = gridDim.y;
-  const double inv_full = 1.0 / (double)rows_per_partial;
   const float *st = stats + (long long)g * partials * 2 * c;
   double s = 0.0, q = 0.0, ss = 0.0;
   const double pivot = ch < c ? bn_merge_pivot(st, ch, rows, rows_per_partial) : 0.0;
@@ -155,26 +162,7 @@ __global__ __launch_bounds__(1024) void bn_finalize_group_kernel(const float *__
       ss += o[2 * c + ch];
     }
   } else if (ch < c) {
-    const int valid = (int)((rows + rows_per_partial - 1) / rows_per_partial) < partials
-                          ? (int)((rows + rows_per_partial - 1) / rows_per_partial) : partials;
-    const double full_pivot = (double)rows_per_partial * pivot;
-#pragma unroll 4
-    for (int p = pl; p < valid; p += 128) {
-      const float sp_f = st[((long long)p * 2) * c + ch];
-      const float qp_f = st[((long long)p * 2 + 1) * c + ch];
-      const double sp = (double)sp_f - full_pivot, qp = qp_f;
-      s += sp;
-      q += qp;
-      ss += sp * sp;
-    }
-    ss *= inv_full;
-    const long long last_cnt = rows - (long long)(valid - 1) * rows_per_partial;
-    if (valid > 0 && last_cnt < rows_per_partial && ((valid - 1) & 127) == pl) {
-      const double raw = st[((long long)(valid - 1) * 2) * c + ch];
-      const double was = raw - full_pivot, sp = raw - (double)last_cnt * pivot;
-      s += sp - was;
-      ss += sp * sp / (double)last_cnt - was * was * inv_full;
-    }
+    bn_merge_lane(st, ch, c, pl, partials, rows_per_partial, rows, pivot, s, q, ss);
   }
 #pragma unroll
   for (int o = 8; o < 64; o <<= 1) {
@@ -228,6 +216,96 @@ __global__ __launch_bounds__(256) void bn_running_update_kernel(const double *__
   }
   if (running_mean) running_mean[ch] = rm;
   if (running_var) running_var[ch] = rv;
+}
+
+// ---- frozen BatchNorm on the split path: the unit's constants and its activation scale in ONE launch --------------------
+// A unit on the running statistics (a frozen-BatchNorm training step with Backbone.split_frozen) stores its output in sp
+// like a trained one, but a z-score bound does not hold for it.  The conv launch's statistics partials give one without a
+// pass over the activation: with mean_b, var_b (biased) of a (group, channel)'s n conv outputs, |y - mean_b| <= sqrt((n - 1) var_b), so
+//   |gamma invstd_r (y - rm) + beta| <= |gamma| invstd_r (|mean_b - rm| + sqrt((n - 1) var_b)) + |beta|.
+// grid = (c/8, groups), bn_finalize_group_kernel's shape and merge (bn_merge_lane: float64, pivoted).  Per (group, channel)
+// the lane that holds the merged sums writes scale / shift (bn_eval_affine_ch: mvg_bn_eval_affine's bits), mean := rm and
+// invstd := 1 / sqrtf(rv + eps) (the backward's reduce forms read them), and evaluates the bound in float64 times
+// FROZEN_BOUND_MARGIN.  ROUNDING MAY ONLY ENLARGE THE BOUND: the merge and the expression are float64; the margin (1 + 2^-7)
+// covers what float64 cannot - the fp32 rounding of the partials themselves (sums of <= a row tile's values: relative 2^-17
+// or so) - and the two fp32 roundings on the way out (the conversion, the chained sum).  The maximum over (group, channel) is
+// an integer atomic max of the float's bits (non-negative: the order of the bits is the order of the values; NaN goes in as
+// inf) into state[0]; every workgroup then takes a ticket from state[1], and the last one adds the identity's chained bound,
+// writes state[2] and the slot's 2^-k (sp_scale_for_banded: mvg_act_scales' rule).  state[0..1] arrive zeroed.  The running
+// statistics are only read.
+constexpr double FROZEN_BOUND_MARGIN = 1.0078125;
+__global__ __launch_bounds__(1024) void bn_frozen_finalize_kernel(const float *__restrict__ stats, int partials, int rows_per_partial,
+                                                                  long long rows, int c, const float *__restrict__ gamma,
+                                                                  const float *__restrict__ beta, const float *__restrict__ rmean,
+                                                                  const float *__restrict__ rvar, float eps,
+                                                                  const float *__restrict__ ident_bound, float *__restrict__ mean_out,
+                                                                  float *__restrict__ invstd_out, float *__restrict__ scale,
+                                                                  float *__restrict__ shift, unsigned *state, float *slot) {
+  __shared__ double sh[3][16][8];
+  const int cl = threadIdx.x & 7, pl = threadIdx.x >> 3;
+  const int ch = blockIdx.x * 8 + cl;
+  const int g = blockIdx.y;
+  const float *st = stats + (long long)g * partials * 2 * c;
+  double s = 0.0, q = 0.0, ss = 0.0;
+  const double pivot = ch < c ? bn_merge_pivot(st, ch, rows, rows_per_partial) : 0.0;
+  if (ch < c) bn_merge_lane(st, ch, c, pl, partials, rows_per_partial, rows, pivot, s, q, ss);
+#pragma unroll
+  for (int o = 8; o < 64; o <<= 1) {
+    s += __shfl_xor(s, o, 64);
+    q += __shfl_xor(q, o, 64);
+    ss += __shfl_xor(ss, o, 64);
+  }
+  const int wv = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) < 8) {
+    sh[0][wv][cl] = s;
+    sh[1][wv][cl] = q;
+    sh[2][wv][cl] = ss;
+  }
+  __syncthreads();
+  if (threadIdx.x < 64) {        // wave 0: lanes 0..7 hold the workgroup's 8 channels (pl == 0), the others carry a zero bound
+    float bd = 0.f;
+    if (pl == 0 && ch < c) {
+      s = q = ss = 0.0;
+#pragma unroll
+      for (int k = 0; k < 16; ++k) {
+        s += sh[0][k][cl];
+        q += sh[1][k][cl];
+        ss += sh[2][k][cl];
+      }
+      const double n = (double)rows;
+      const double dmean = s / n;                         // the sums are of s_p - cnt_p * pivot
+      const double mean = pivot + dmean;
+      double m2 = q + (ss - s * dmean);                  // Chan merge of the partials
+      if (m2 < 0.0) m2 = 0.0;
+      const float ga = gamma[ch], be = beta[ch], rm = rmean[ch], rv = rvar[ch];
+      const long long o = (long long)g * c + ch;
+      bn_eval_affine_ch(ga, be, rm, rv, eps, scale[o], shift[o]);
+      const float is = 1.f / sqrtf(rv + eps);
+      mean_out[o] = rm;
+      invstd_out[o] = is;
+      // sqrt((n - 1) var_b) = sqrt(m2 (n - 1) / n)
+      const double spread = sqrt(m2 * ((n - 1.0) / n));
+      const double b = (fabs((double)ga) * (double)is * (fabs(mean - (double)rm) + spread) + fabs((double)be)) * FROZEN_BOUND_MARGIN;
+      bd = (float)b;
+      if (!(bd <= 3.0e38f)) bd = INFINITY;               // NaN too: it must not rank below a finite bound
+    }
+    bd = fmaxf(bd, __shfl_xor(bd, 1, 64));
+    bd = fmaxf(bd, __shfl_xor(bd, 2, 64));
+    bd = fmaxf(bd, __shfl_xor(bd, 4, 64));
+    if (threadIdx.x == 0) {
+      atomicMax(&state[0], __float_as_uint(bd));
+      __threadfence();
+      const unsigned ticket = atomicAdd(&state[1], 1u);
+      if (ticket == gridDim.x * gridDim.y - 1) {         // every other workgroup's maximum is in: finish the unit
+        __threadfence();
+        float b = __uint_as_float(atomicMax(&state[0], 0u));
+        if (ident_bound) b = __fadd_rn(b, *ident_bound);
+        if (!(b <= 3.0e38f)) b = INFINITY;
+        reinterpret_cast<float *>(state)[2] = b;
+        if (slot) *slot = 1.f / sp_scale_for_banded(b);
+      }
+    }
+  }
 }
 
 // Large partial counts (stem at C2: 25 088 per group) first collapse to <= 64 slices per group with
@@ -896,6 +974,47 @@ __global__ __launch_bounds__(256) void bn_bwd_apply_sp_kernel(const float *__res
     F8 o;
     // (bn_math.h; conv_split.hip's dy former calls the same function: one launch or two, the same bits)
     bn_dy_chunk(d.v, v.v, mu.v, is.v, ga.v, sa.v, sb.v, inv_rows, dsc, o.v, mscale != nullptr, ma.v, mb.v);
+    st8_sp(dy, base + i, o);
+    cq += step;
+    if (cq >= c8n) cq -= c8n;
+  }
+}
+
+// The same pass for a unit on the running statistics (frozen BatchNorm, Backbone.split_frozen): dy = sp(gamma invstd dz 2^k), no
+// batch sums - invstd [groups][c] is what bn_frozen_finalize_kernel left.  MASKED: the ReLU mask rebuilt from y (mscale / mshift);
+// else g is already masked (or the unit has no ReLU) and y is not read at all: 4 bytes in, 4 bytes out per element (the
+// train-mode pass moves 12).  The same grid-stride loop: 16-byte accesses, per-channel factors in registers, no LDS.
+template <bool MASKED>
+__global__ __launch_bounds__(256) void bn_frozen_bwd_apply_sp_kernel(const float *__restrict__ g, const float *__restrict__ y,
+                                                                     const float *__restrict__ invstd, const float *__restrict__ gamma,
+                                                                     const float *__restrict__ mscale, const float *__restrict__ mshift,
+                                                                     long long n8_per_group, int c8n, int c, sp_t *__restrict__ dy,
+                                                                     const float *__restrict__ dy_sinv) {
+  const float dsc = 1.f / *dy_sinv;            // 2^k from the reduce pass's finalize (exact: a power of two)
+  const int grp = blockIdx.y;
+  const long long base = (long long)grp * n8_per_group;
+  const long long stride = (long long)gridDim.x * 256;
+  long long i = (long long)blockIdx.x * 256 + threadIdx.x;
+  int cq = (int)(i % c8n);
+  const int step = (int)(stride % c8n);
+  const long long gc = (long long)grp * c;
+  F8 f, ma, mb;
+  auto factors = [&]() {
+    const F8 is = ld8(invstd + gc, cq), ga = ld8(gamma, cq);
+#pragma unroll
+    for (int k = 0; k < 8; ++k) f.v[k] = ga.v[k] * is.v[k];
+    if (MASKED) {
+      ma = ld8(mscale + gc, cq);
+      mb = ld8(mshift + gc, cq);
+    }
+  };
+  factors();
+  for (; i < n8_per_group; i += stride) {
+    if (step != 0) factors();                  // (not taken for the ResNet shapes: the stride is a multiple of c8n)
+    const F8 d = ld8(g, base + i);
+    F8 v, o;
+    if (MASKED) v = ld8(y, base + i);
+    bn_frozen_dy_chunk(d.v, v.v, f.v, dsc, o.v, MASKED, ma.v, mb.v);
     st8_sp(dy, base + i, o);
     cq += step;
     if (cq >= c8n) cq -= c8n;
@@ -1788,6 +1907,46 @@ int mvg_bn_bwd_apply_split(const float *g, const float *y, const float *mean, co
   hipLaunchKernelGGL(bn_bwd_apply_sp_kernel, dim3(stream_geometry(n8, c / 8).grid, groups), dim3(256), 0, st, g, y, mean, invstd, gamma, s1, s2,
                      relu_scale, relu_shift, n8, 1.0f / (float)rows_per_group, c / 8, c, (sp_t *)dy_sp, dy_sinv);
   return check_launch("bn_bwd_apply_split");
+}
+
+// ---- frozen BatchNorm on the split path (Backbone.split_frozen) --------------------------------------------------------
+int mvg_bn_frozen_finalize(const float *stats, int groups, int partials, int rows_per_partial, int64_t rows_per_group, int c,
+                           const float *gamma, const float *beta, const float *running_mean, const float *running_var, float eps,
+                           const float *ident_bound, float *mean, float *invstd, float *scale, float *shift, float *state,
+                           float *slot, void *stream) {
+  MVG_REQUIRE(stats && gamma && beta && running_mean && running_var && mean && invstd && scale && shift && state,
+              "bn_frozen_finalize: stats, gamma, beta, the running statistics, mean, invstd, scale, shift and state are required");
+  MVG_REQUIRE(groups > 0 && groups < 65536 && partials > 0 && rows_per_partial > 0 && c > 0 && rows_per_group > 0,
+              "bn_frozen_finalize: bad sizes");
+  MVG_REQUIRE((rows_per_group + rows_per_partial - 1) / rows_per_partial <= partials,
+              "bn_frozen_finalize: %d partials of %d rows do not cover %lld rows", partials, rows_per_partial, (long long)rows_per_group);
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_BN_FINALIZE, st, 0.0, 4.0 * groups * (double)partials * 2 * c);
+  hipLaunchKernelGGL(bn_frozen_finalize_kernel, dim3(ceil_div(c, 8), groups), dim3(1024), 0, st, stats, partials, rows_per_partial,
+                     (long long)rows_per_group, c, gamma, beta, running_mean, running_var, eps, ident_bound, mean, invstd, scale, shift,
+                     (unsigned *)state, slot);
+  return check_launch("bn_frozen_finalize");
+}
+
+int mvg_bn_frozen_bwd_apply_split(const float *g, const float *y, const float *invstd, const float *gamma, const float *relu_scale,
+                                  const float *relu_shift, int groups, int64_t rows_per_group, int c, void *dy_sp,
+                                  const float *dy_sinv, void *stream) {
+  if (int e = require_c8("bn_frozen_bwd_apply_split", c)) return e;
+  MVG_REQUIRE(g && invstd && gamma && dy_sp && dy_sinv, "bn_frozen_bwd_apply_split: g, invstd, gamma, dy_sp and dy_sinv are required");
+  MVG_REQUIRE(groups > 0 && groups < 65536 && rows_per_group > 0, "bn_frozen_bwd_apply_split: bad sizes");
+  MVG_REQUIRE((relu_scale == nullptr) == (relu_shift == nullptr), "bn_frozen_bwd_apply_split: relu_scale and relu_shift go together");
+  MVG_REQUIRE(!relu_scale || y, "bn_frozen_bwd_apply_split: the mask from relu_scale / relu_shift needs y");
+  hipStream_t st = (hipStream_t)stream;
+  const long long n8 = rows_per_group * (c / 8);
+  ProfScope ps(MVG_K_BN_BWD_APPLY, st, 0.0, 8.0 * groups * (double)n8 * ((relu_scale ? 8.0 : 4.0) + SP_BYTES));
+  const dim3 grid(stream_geometry(n8, c / 8).grid, groups), block(256);
+  if (relu_scale)
+    hipLaunchKernelGGL(bn_frozen_bwd_apply_sp_kernel<true>, grid, block, 0, st, g, y, invstd, gamma, relu_scale, relu_shift, n8, c / 8, c,
+                       (sp_t *)dy_sp, dy_sinv);
+  else
+    hipLaunchKernelGGL(bn_frozen_bwd_apply_sp_kernel<false>, grid, block, 0, st, g, y, invstd, gamma, relu_scale, relu_shift, n8, c / 8, c,
+                       (sp_t *)dy_sp, dy_sinv);
+  return check_launch("bn_frozen_bwd_apply_split");
 }
 
 int mvg_bn_relu_maxpool_fwd_split_scaled(const float *y, const float *scale, const float *shift, void *pooled_sp,

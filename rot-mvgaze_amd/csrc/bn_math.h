@@ -108,5 +108,16 @@ __device__ __forceinline__ void bn_dy_chunk(const float (&dz)[8], const float (&
     o[k] = bn_dy(d, y[k], mean[k], invstd[k], gamma[k], s1[k], s2[k], inv_rows) * dsc;
   }
 }
+// The backward apply pass of a unit on the running statistics (frozen BatchNorm): o = (gamma invstd) dz * dsc - no batch sums.
+// f = gamma * invstd per channel, rounded once; masked as above.
+__device__ __forceinline__ void bn_frozen_dy_chunk(const float (&dz)[8], const float (&y)[8], const float (&f)[8], float dsc, float (&o)[8],
+                                                   bool masked, const float (&ms)[8], const float (&mh)[8]) {
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    float d = dz[k];
+    if (masked) d = relu_mask(relu_on(y[k], ms[k], mh[k]), d);
+    o[k] = f[k] * d * dsc;
+  }
+}
 
 }  // namespace mvg

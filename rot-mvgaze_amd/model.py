@@ -193,7 +193,8 @@ class MultiViewGaze(nn.Module):
     the head receives ``model.training`` unchanged.  ``IntensityBatchNorm`` of the ``share_feature`` variant is not an
     ``nn.BatchNorm2d``: it keeps following ``model.training`` (its ``running_mean`` keeps updating), as the idiom would leave
     it.  In ``eval()`` the flag has no effect; with the flag off nothing changes anywhere.  Served by the fp32 model (on the
-    fp32-MFMA kernels, like an ``eval()`` step with gradients) and by ``compute_dtype = torch.bfloat16``."""
+    fp32-MFMA kernels, like an ``eval()`` step with gradients - or, with ``split_frozen = True``, on the split-operand kernels,
+    like a train-mode step) and by ``compute_dtype = torch.bfloat16``."""
 
     def __init__(self, backbone_depth: int = 50, num_iter: int = 3, variant: Variant = DEFAULT_VARIANT) -> None:
         super().__init__()
@@ -251,6 +252,10 @@ class MultiViewGaze(nn.Module):
         # share_feature variant is not an nn.BatchNorm2d and keeps following model.training, as the idiom would leave it.
         # No effect in eval(); off: nothing changes anywhere.  (The trainer calls model.train() every epoch: set it once.)
         self.freeze_batchnorm: bool = False
+        # freeze_batchnorm steps of the fp32 model on the split-operand kernels (Backbone.split_frozen): the activations of such a
+        # step are stored in sp with scales taken from the conv launches' own statistics partials.  Off (default): the step
+        # runs on the fp32-MFMA kernels, exactly as before.  No effect on the bf16 path, in eval() or with MVG_SPLIT=0.
+        self.split_frozen: bool = False
         self._sink = _ArenaSink(self)
         self._wgrad_low_priority = True           # data-parallel runs set False (dp.GradAllReducer._configure)
         # storage / matrix-core type of the backbone: torch.float32 (default: the path held to 1e-4 against the
@@ -384,6 +389,7 @@ class MultiViewGaze(nn.Module):
             raise ValueError("compute_dtype must be torch.float32 or torch.bfloat16")
         self._backbone.act_dtype = self.compute_dtype
         self._backbone.split_eval_guard = self.split_eval_guard
+        self._backbone.split_frozen = self.split_frozen
         self._head.mixed = self.compute_dtype == torch.bfloat16
         self._head.split = self._backbone.split          # one switch (MVG_SPLIT) selects the kernel family everywhere
         self._sink.active = False

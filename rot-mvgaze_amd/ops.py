@@ -615,6 +615,35 @@ def bn_bwd_apply_split(g, y, mean, invstd, gamma, s1, s2, groups, rows_per_group
                                        rows_per_group, c, _p(dy_sp), _p(mx), _p(dy_sp.sinv), int(ready), _s()), "bn_bwd_apply_split")
 
 
+FROZEN_BOUND_MARGIN = 1.0 + 2.0 ** -7       # the final factor of bn_frozen_finalize's bound (bn.hip: FROZEN_BOUND_MARGIN)
+
+
+def bn_frozen_finalize(stats, groups, partials, rows_per_partial, rows_per_group, c, gamma, beta, running_mean, running_var, eps,
+                       mean, invstd, scale, shift, state, slot=None, ident_bound=None):
+    """A frozen-BatchNorm unit of a split call, in place of bn_eval_affine: scale / shift (the same bits), mean / invstd := the
+    running values broadcast to [groups, c], and - from the conv launch's statistics partials ``stats`` - the unit's bound.
+    state: 4 floats, the first two ZERO on entry; state[2] receives the chained bound (+ ident_bound[0], an earlier unit's
+    state[2:3]); slot (1 element, or None) receives the 2^-k of the unit's sp output.  The running statistics are only read."""
+    assert stats.dtype == torch.float32 and stats.is_contiguous() and stats.numel() == groups * partials * 2 * c
+    assert state.dtype == torch.float32 and state.numel() >= 3 and state.is_contiguous()
+    for t in (mean, invstd, scale, shift):
+        assert t.dtype == torch.float32 and t.numel() == groups * c and t.is_contiguous()
+    check(lib().mvg_bn_frozen_finalize(_p(stats), groups, partials, rows_per_partial, rows_per_group, c, _p(gamma), _p(beta),
+                                       _p(running_mean), _p(running_var), eps, _p(ident_bound), _p(mean), _p(invstd), _p(scale),
+                                       _p(shift), _p(state), _p(slot), _s()), "bn_frozen_finalize")
+
+
+def bn_frozen_bwd_apply_split(g, y, invstd, gamma, groups, rows_per_group, c, dy_sp, dy_sinv, relu_affine=None):
+    """dy (sp) = gamma invstd g 2^k of a unit on the running statistics, one pass; g already masked (or no ReLU), or the mask
+    from y through relu_affine = (scale, shift).  dy_sinv: the 2^-k the reduce pass / fused backward-data launch left; it
+    becomes dy_sp.sinv."""
+    rs, rh = relu_affine if relu_affine is not None else (None, None)
+    assert dy_sinv is not None and g.dtype == torch.float32 and g.numel() == groups * rows_per_group * c
+    dy_sp.sinv = dy_sinv
+    check(lib().mvg_bn_frozen_bwd_apply_split(_p(g), _p(y if rs is not None else None), _p(invstd), _p(gamma), _p(rs), _p(rh), groups,
+                                              rows_per_group, c, _p(dy_sp), _p(dy_sinv), _s()), "bn_frozen_bwd_apply_split")
+
+
 def bn_relu_maxpool_fwd_split(y, scale, shift, pooled_sp, argmax, groups, n_per_group, h, w, c, ho, wo):
     """pooled_sp.sinv (an act_scales slot, or None = unscaled): the pooled map is stored times its 2^k."""
     check(lib().mvg_bn_relu_maxpool_fwd_split_scaled(_p(y), _p(scale), _p(shift), _p(pooled_sp), _sinv(pooled_sp), _p(argmax), groups,
