@@ -548,6 +548,34 @@ int mvg_adam_step_segments_clip(float *param, const float *grad, float *exp_avg,
 int mvg_adam_step_segments_dev_clip(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                                     const int64_t *host_bounds, const float *host_hyper, const int32_t *host_lr_index, int n_segments,
                                     const float *lr_dev, int n_lr, float *state3_dev, const float *clip4_dev, void *stream);
+/* DECOUPLED weight decay (torch.optim.AdamW; optim.AdamW and optim.Adam(decoupled_weight_decay=True)) on every step form.  One
+ * element:  f = 1 - lr * weight_decay (float, formed on the device by every form as one fused multiply-add; lr is the plain
+ * learning rate, not lr / bc1),  q = p * f,  m' = b1 m + (1 - b1) g,  v' = b2 v + (1 - b2) g^2,
+ * p' = q - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps) - the gradient alone enters the moments (already multiplied by coef in
+ * a clipped step).  With weight_decay = 0 the result equals the coupled entry point's, bit for bit.
+ * mvg_adamw_step / mvg_adamw_step_dev are mvg_adam_step / mvg_adam_step_dev in that mode: the same arguments, checks, grid and -
+ * for the device form - the same tick on the same state3 (lr_dev[0] is also the lr of f). */
+int mvg_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr,
+                   float beta1, float beta2, float eps, float weight_decay, int step, void *stream);
+int mvg_adamw_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev,
+                       float *state3, float beta1, float beta2, float eps, float weight_decay, void *stream);
+/* The two segmented steps with a MODE per segment: host_decoupled[i] (host memory, like the other per-segment arrays) is 0 for
+ * the coupled update of mvg_adam_step_segments and 1 for the decoupled one; anything else is rejected.  The mode travels by
+ * value in the kernel arguments, so one launch may hold coupled and decoupled segments side by side.  host_hyper is that of
+ * mvg_adam_step_segments (stride 5) resp. mvg_adam_step_segments_dev (stride 4).  clip4_dev may be NULL: no clipping and no
+ * guard (the bits of coef = 1); otherwise the record is read as mvg_adam_step_segments_clip / _dev_clip read it, and with
+ * skipped != 0 nothing is updated and no row advances.  Every rule of those entry points holds here, checked before the first
+ * launch (the tick included): a rejected call has advanced no row and updated nothing.  Elements outside every segment are
+ * neither read nor written.  A coupled segment's result equals, bit for bit, that of mvg_adam_step_segments (_dev, _clip,
+ * _dev_clip) on the same data; a decoupled segment's equals mvg_adamw_step (mvg_adamw_step_dev with a one-element lr_dev and
+ * the same row) over that slice. */
+int mvg_adam_step_segments_ex(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                              const int64_t *host_bounds, const float *host_hyper, const int32_t *host_steps,
+                              const int32_t *host_decoupled, int n_segments, const float *clip4_dev, void *stream);
+int mvg_adam_step_segments_dev_ex(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
+                                  const int64_t *host_bounds, const float *host_hyper, const int32_t *host_lr_index,
+                                  const int32_t *host_decoupled, int n_segments, const float *lr_dev, int n_lr, float *state3_dev,
+                                  const float *clip4_dev, void *stream);
 
 /* ---------------------------------------------------------------- loss
  * gaze_angular_loss losses/gaze_loss.py:42-52 over pitchyaw_to_vector utils/math.py:52-60:

@@ -21,7 +21,7 @@ def __getattr__(name):
         "angular_error": "geometry",
         "build_pair_index": "pair_index",
         "GradAllReducer": "dp",
-        "Adam": "optim",
+        "Adam": "optim", "AdamW": "optim",
         "AngularErrorMeter": "metrics",
     }
     if name in lazy:

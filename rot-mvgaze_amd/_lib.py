@@ -209,6 +209,13 @@ SIGNATURES = {
                                          _P]),
     "mvg_adam_step_segments_dev_clip": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32), _I, _P,
                                              _I, _P, _P, _P]),
+    # decoupled weight decay (AdamW): the two plain forms, and the segmented forms with a mode per segment
+    "mvg_adamw_step": (_I, [_P, _P, _P, _P, _I64, _F, _F, _F, _F, _F, _I, _P]),
+    "mvg_adamw_step_dev": (_I, [_P, _P, _P, _P, _I64, _P, _P, _F, _F, _F, _F, _P]),
+    "mvg_adam_step_segments_ex": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                       C.POINTER(C.c_int32), _I, _P, _P]),
+    "mvg_adam_step_segments_dev_ex": (_I, [_P, _P, _P, _P, _I64, C.POINTER(C.c_int64), C.POINTER(C.c_float), C.POINTER(C.c_int32),
+                                           C.POINTER(C.c_int32), _I, _P, _I, _P, _P, _P]),
     # the fusion block on the split kernels
     "mvg_absmax_multi": (_I, [C.POINTER(C.c_void_p), C.POINTER(C.c_int64), C.POINTER(C.c_void_p), _I, _P]),
     "mvg_fuse_build_split": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _P]),

@@ -497,6 +497,46 @@ __global__ __launch_bounds__(256) void adam_segments_kernel(float4 *__restrict__
   }
 }
 
+// DECOUPLED weight decay (torch.optim.AdamW): the parameter is shrunk by f = 1 - lr * wd and the moments see the gradient alone.
+// The update of one element, stated once for adamw_kernel, adamw_dev_kernel and the decoupled segments of the _ex kernels.
+// lr in f is the plain learning rate (not lr / bc1); f is formed here, on the device, in float, by every form - host-lr forms
+// included - so all forms give the same bits for the same hyper-parameters, as they do for lr / bc1.
+// Which products are fused is WRITTEN here, not left to the compiler: q - step_size * x has two products, and contracted the
+// other way round (p * f fused, the step rounded on its own) the element would differ from adam1's at wd = 0.  The fused
+// multiply-adds are the ones the compiler forms in adam1 (m: (1 - b1) * g fused, b1 * m rounded; v: g * ((1 - b2) * g) fused,
+// b2 * v rounded; p: the step fused), q = p * f is rounded on its own, f is one fused multiply-add: with wd = 0, f = 1, q = p and
+// the element is adam1's in every bit - and every form runs these operations whatever kernel they are inlined into.
+__device__ __forceinline__ float adamw_factor(float lr, float wd) { return __fmaf_rn(-lr, wd, 1.f); }
+__device__ __forceinline__ void adamw1(float &p, float g, float &m, float &v, float b1, float b2, float eps, float f,
+                                       float step_size, float bc2_sqrt) {
+  const float q = p * f;
+  m = __fmaf_rn(1.f - b1, g, b1 * m);
+  v = __fmaf_rn(g, (1.f - b2) * g, b2 * v);
+  const float denom = sqrtf(v) / bc2_sqrt + eps;
+  p = __fmaf_rn(-step_size, m / denom, q);
+}
+__device__ __forceinline__ void adamw4(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
+                                       float4 *__restrict__ v, long long i, float b1, float b2, float eps, float f,
+                                       float step_size, float bc2_sqrt) {
+  float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
+  adamw1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, f, step_size, bc2_sqrt);
+  adamw1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, f, step_size, bc2_sqrt);
+  adamw1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, f, step_size, bc2_sqrt);
+  adamw1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, f, step_size, bc2_sqrt);
+  p[i] = pp;
+  m[i] = mm;
+  v[i] = vv;
+}
+// adam_kernel in decoupled mode
+__global__ __launch_bounds__(256) void adamw_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
+                                                    float4 *__restrict__ m, float4 *__restrict__ v, long long n4, float lr,
+                                                    float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
+  const long long stride = (long long)gridDim.x * 256;
+  const float step_size = lr / bc1, f = adamw_factor(lr, wd);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
+    adamw4(p, g, m, v, i, b1, b2, eps, f, step_size, bc2_sqrt);
+}
+
 // ---- skinny linear (out_features <= 4): the Linear(512 -> 2) of the gaze head ------------------
 // fwd: one wave per row.
 __global__ __launch_bounds__(256) void skinny_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
@@ -940,6 +980,82 @@ __global__ __launch_bounds__(256) void adam_segments_dev_clip_kernel(float4 *__r
   }
 }
 
+// ---- the decoupled mode of the device-lr and segmented forms (optim.AdamW, optim.Adam(decoupled_weight_decay=True))
+// adam_dev_kernel in decoupled mode: the same state row (adam_tick_kernel advances it), f from the device learning rate.
+__global__ __launch_bounds__(256) void adamw_dev_kernel(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
+                                                        float4 *__restrict__ v, long long n4, const float *__restrict__ lr_dev,
+                                                        const float *__restrict__ state, float b1, float b2, float eps, float wd) {
+  const long long stride = (long long)gridDim.x * 256;
+  const float lr = lr_dev[0];
+  const float step_size = lr / state[1], bc2_sqrt = state[2], f = adamw_factor(lr, wd);
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
+    adamw4(p, g, m, v, i, b1, b2, eps, f, step_size, bc2_sqrt);
+}
+// adamw4 with the gradient multiplied by coef as it is loaded (adam4_clip's rule: the product rounded on its own)
+__device__ __forceinline__ void adamw4_clip(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
+                                            float4 *__restrict__ v, long long i, float coef, float b1, float b2, float eps, float f,
+                                            float step_size, float bc2_sqrt) {
+  float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
+  adamw1(pp.x, clip_mul(gg.x, coef), mm.x, vv.x, b1, b2, eps, f, step_size, bc2_sqrt);
+  adamw1(pp.y, clip_mul(gg.y, coef), mm.y, vv.y, b1, b2, eps, f, step_size, bc2_sqrt);
+  adamw1(pp.z, clip_mul(gg.z, coef), mm.z, vv.z, b1, b2, eps, f, step_size, bc2_sqrt);
+  adamw1(pp.w, clip_mul(gg.w, coef), mm.w, vv.w, b1, b2, eps, f, step_size, bc2_sqrt);
+  p[i] = pp;
+  m[i] = mm;
+  v[i] = vv;
+}
+// The segmented kernels with a MODE per segment, by value like wd: decoupled[k] != 0 runs adamw1 on segment k, 0 runs adam1 - one
+// launch may hold both side by side (a segment is a run of whole 16-byte slots, so a wave changes mode at a segment's border
+// only).  clip4 may be null: coef = 1 (g * 1 is g in every bit) and no guard; otherwise the record is read as the clipped
+// kernels read it.  The coupled segments run adam4_clip as adam_segments_clip_kernel does.
+struct AdamModes {
+  int decoupled[MVG_ADAM_MAX_SEGMENTS];
+};
+__global__ __launch_bounds__(256) void adam_segments_ex_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
+                                                               float4 *__restrict__ m, float4 *__restrict__ v,
+                                                               const float *__restrict__ clip4, AdamSegments t, AdamModes md) {
+  float coef = 1.f;
+  if (clip4) {
+    coef = clip4[1];
+    if (clip4[2] != 0.f) return;
+  }
+  const long long stride = (long long)gridDim.x * 256;
+  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
+    if (md.decoupled[k])
+      adamw4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], adamw_factor(t.lr[k], t.wd[k]), t.lr[k] / t.bc1[k],
+                  t.bc2_sqrt[k]);
+    else
+      adam4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], t.wd[k], t.lr[k] / t.bc1[k], t.bc2_sqrt[k]);
+  }
+}
+__global__ __launch_bounds__(256) void adam_segments_dev_ex_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
+                                                                   float4 *__restrict__ m, float4 *__restrict__ v,
+                                                                   const float *__restrict__ lr_dev, const float *__restrict__ state,
+                                                                   const float *__restrict__ clip4, AdamSegmentsDev t, AdamModes md) {
+  float coef = 1.f;
+  if (clip4) {
+    coef = clip4[1];
+    if (clip4[2] != 0.f) return;
+  }
+  const long long stride = (long long)gridDim.x * 256;
+  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
+  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
+    int k = 0;
+#pragma unroll
+    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
+    const float lr = lr_dev[t.lr_index[k]];
+    if (md.decoupled[k])
+      adamw4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], adamw_factor(lr, t.wd[k]), lr / state[3 * k + 1],
+                  state[3 * k + 2]);
+    else
+      adam4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], t.wd[k], lr / state[3 * k + 1], state[3 * k + 2]);
+  }
+}
+
 }  // namespace mvg
 
 using namespace mvg;
@@ -1091,6 +1207,31 @@ int mvg_adam_step(float *param, const float *grad, float *exp_avg, float *exp_av
   return check_launch("adam_step");
 }
 
+// mvg_adam_step in decoupled mode: the same checks, corrections and grid, adamw_kernel
+int mvg_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float beta1,
+                   float beta2, float eps, float weight_decay, int step, void *stream) {
+  MVG_REQUIRE(n % 4 == 0 && step >= 1, "adamw: n %% 4 != 0 or step < 1");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * (double)n);
+  const double bc1 = 1.0 - pow((double)beta1, (double)step);
+  const double bc2 = 1.0 - pow((double)beta2, (double)step);
+  long long blocks = (n / 4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
+                     (float4 *)exp_avg, (float4 *)exp_avg_sq, (long long)(n / 4), lr, beta1, beta2, eps, weight_decay,
+                     (float)bc1, (float)sqrt(bc2));
+  return check_launch("adamw_step");
+}
+
+// The mode rule of the _ex entry points, checked with the segment rules before the first launch.
+static int check_modes(const char *what, const int32_t *host_decoupled, int n_segments) {
+  MVG_REQUIRE(host_decoupled, "%s: null host_decoupled", what);
+  for (int i = 0; i < n_segments; ++i)
+    MVG_REQUIRE(host_decoupled[i] == 0 || host_decoupled[i] == 1, "%s: segment %d has mode %d (0: coupled, 1: decoupled)", what, i,
+                (int)host_decoupled[i]);
+  return 0;
+}
+
 // The segment rules of every segmented entry point, checked before its first launch: aligned to 4, inside [0, n), non-empty,
 // sorted by begin, disjoint.  *active receives the elements the segments hold.
 static int check_segments(const char *what, int64_t n, const int64_t *host_bounds, int n_segments, double *active) {
@@ -1110,10 +1251,11 @@ static int check_segments(const char *what, int64_t n, const int64_t *host_bound
   return 0;
 }
 
-// mvg_adam_step_segments (clip4 == nullptr: its launches as they always were) and mvg_adam_step_segments_clip
+// mvg_adam_step_segments (clip4 == nullptr: its launches as they always were), mvg_adam_step_segments_clip and, with ex set,
+// mvg_adam_step_segments_ex (a mode per segment in host_decoupled, clip4 nullable: adam_segments_ex_kernel)
 static int adam_step_segments_launch(const char *what, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                                      const int64_t *host_bounds, const float *host_hyper, const int32_t *host_steps, int n_segments,
-                                     const float *clip4, void *stream) {
+                                     const float *clip4, void *stream, bool ex = false, const int32_t *host_decoupled = nullptr) {
   MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && host_bounds && host_hyper && host_steps && n % 4 == 0 && n_segments >= 1,
               "%s: null argument, n %% 4 != 0 or no segment", what);
   // every segment is checked before the first launch: a rejected call has updated nothing
@@ -1121,12 +1263,16 @@ static int adam_step_segments_launch(const char *what, float *param, const float
   if (int rc = check_segments(what, n, host_bounds, n_segments, &active)) return rc;
   for (int i = 0; i < n_segments; ++i)
     MVG_REQUIRE(host_steps[i] >= 1, "%s: segment %d has step %d < 1", what, i, (int)host_steps[i]);
+  if (ex)
+    if (int rc = check_modes(what, host_decoupled, n_segments)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * active);
   for (int s0 = 0; s0 < n_segments; s0 += MVG_ADAM_MAX_SEGMENTS) {
     const int cnt = n_segments - s0 < MVG_ADAM_MAX_SEGMENTS ? n_segments - s0 : MVG_ADAM_MAX_SEGMENTS;
     AdamSegments t;
+    AdamModes md;
     memset(&t, 0, sizeof(t));
+    memset(&md, 0, sizeof(md));
     long long total = 0;
     for (int k = 0; k < MVG_ADAM_MAX_SEGMENTS; ++k) {
       const int i = s0 + (k < cnt ? k : cnt - 1);          // (unused entries repeat the last segment: never selected)
@@ -1145,10 +1291,14 @@ static int adam_step_segments_launch(const char *what, float *param, const float
       t.wd[k] = h[4];
       t.bc1[k] = (float)(1.0 - pow((double)h[1], (double)host_steps[i]));
       t.bc2_sqrt[k] = (float)sqrt(1.0 - pow((double)h[2], (double)host_steps[i]));
+      if (ex) md.decoupled[k] = host_decoupled[i];
     }
     long long blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (clip4)
+    if (ex)
+      hipLaunchKernelGGL(adam_segments_ex_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
+                         (float4 *)exp_avg, (float4 *)exp_avg_sq, clip4, t, md);
+    else if (clip4)
       hipLaunchKernelGGL(adam_segments_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
                          (float4 *)exp_avg, (float4 *)exp_avg_sq, clip4, t);
     else
@@ -1170,6 +1320,13 @@ int mvg_adam_step_segments_clip(float *param, const float *grad, float *exp_avg,
   MVG_REQUIRE(clip4_dev, "adam_step_segments_clip: null clip4 record");
   return adam_step_segments_launch("adam_step_segments_clip", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper, host_steps,
                                    n_segments, clip4_dev, stream);
+}
+
+int mvg_adam_step_segments_ex(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
+                              const float *host_hyper, const int32_t *host_steps, const int32_t *host_decoupled, int n_segments,
+                              const float *clip4_dev, void *stream) {
+  return adam_step_segments_launch("adam_step_segments_ex", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper, host_steps,
+                                   n_segments, clip4_dev, stream, true, host_decoupled);
 }
 
 // The grid of one partial-sum launch over `total4` 16-byte slots: eight workgroups per CU the planners may use, at most.
@@ -1329,10 +1486,27 @@ int mvg_adam_step_dev(float *param, const float *grad, float *exp_avg, float *ex
   return check_launch("adam_step_dev");
 }
 
-// mvg_adam_step_segments_dev (clip4 == nullptr: its launches as they always were) and mvg_adam_step_segments_dev_clip
+// mvg_adam_step_dev in decoupled mode: the same tick on the same state3, adamw_dev_kernel
+int mvg_adamw_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev, float *state3,
+                       float beta1, float beta2, float eps, float weight_decay, void *stream) {
+  MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && lr_dev && state3 && n % 4 == 0, "adamw_step_dev: null argument or n %% 4 != 0");
+  hipStream_t st = (hipStream_t)stream;
+  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * (double)n);
+  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st, state3, beta1, beta2);
+  if (check_launch("adam_tick")) return 1;
+  long long blocks = (n / 4 + 255) / 256;
+  if (blocks > 8192) blocks = 8192;
+  hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad, (float4 *)exp_avg,
+                     (float4 *)exp_avg_sq, (long long)(n / 4), lr_dev, state3, beta1, beta2, eps, weight_decay);
+  return check_launch("adamw_step_dev");
+}
+
+// mvg_adam_step_segments_dev (clip4 == nullptr: its launches as they always were), mvg_adam_step_segments_dev_clip and, with ex
+// set, mvg_adam_step_segments_dev_ex (a mode per segment, clip4 nullable: the same ticks, adam_segments_dev_ex_kernel)
 static int adam_step_segments_dev_launch(const char *what, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
                                          const int64_t *host_bounds, const float *host_hyper, const int32_t *host_lr_index, int n_segments,
-                                         const float *lr_dev, int n_lr, float *state3_dev, const float *clip4, void *stream) {
+                                         const float *lr_dev, int n_lr, float *state3_dev, const float *clip4, void *stream,
+                                         bool ex = false, const int32_t *host_decoupled = nullptr) {
   MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && host_bounds && host_hyper && host_lr_index && lr_dev && state3_dev,
               "%s: null argument", what);
   MVG_REQUIRE(n % 4 == 0 && n_segments >= 1 && n_lr >= 1, "%s: n %% 4 != 0, no segment or no learning rate", what);
@@ -1342,14 +1516,18 @@ static int adam_step_segments_dev_launch(const char *what, float *param, const f
   for (int i = 0; i < n_segments; ++i)
     MVG_REQUIRE(host_lr_index[i] >= 0 && host_lr_index[i] < n_lr, "%s: segment %d has lr index %d outside [0, %d)", what, i,
                 (int)host_lr_index[i], n_lr);
+  if (ex)
+    if (int rc = check_modes(what, host_decoupled, n_segments)) return rc;
   hipStream_t st = (hipStream_t)stream;
   ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * active);
   for (int s0 = 0; s0 < n_segments; s0 += MVG_ADAM_MAX_SEGMENTS) {
     const int cnt = n_segments - s0 < MVG_ADAM_MAX_SEGMENTS ? n_segments - s0 : MVG_ADAM_MAX_SEGMENTS;
     AdamTicks ticks;
     AdamSegmentsDev t;
+    AdamModes md;
     memset(&ticks, 0, sizeof(ticks));
     memset(&t, 0, sizeof(t));
+    memset(&md, 0, sizeof(md));
     ticks.count = cnt;
     long long total = 0;
     for (int k = 0; k < MVG_ADAM_MAX_SEGMENTS; ++k) {
@@ -1367,6 +1545,7 @@ static int adam_step_segments_dev_launch(const char *what, float *param, const f
       ticks.b2[k] = t.b2[k] = h[1];
       t.eps[k] = h[2];
       t.wd[k] = h[3];
+      if (ex) md.decoupled[k] = host_decoupled[i];
     }
     float *rows = state3_dev + 3 * (size_t)s0;             // this launch's rows of the table
     if (clip4)
@@ -1376,7 +1555,10 @@ static int adam_step_segments_dev_launch(const char *what, float *param, const f
     if (check_launch("adam_tick_segments")) return 1;
     long long blocks = (total + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    if (clip4)
+    if (ex)
+      hipLaunchKernelGGL(adam_segments_dev_ex_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
+                         (float4 *)exp_avg, (float4 *)exp_avg_sq, lr_dev, (const float *)rows, clip4, t, md);
+    else if (clip4)
       hipLaunchKernelGGL(adam_segments_dev_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
                          (float4 *)exp_avg, (float4 *)exp_avg_sq, lr_dev, (const float *)rows, clip4, t);
     else
@@ -1400,6 +1582,13 @@ int mvg_adam_step_segments_dev_clip(float *param, const float *grad, float *exp_
   MVG_REQUIRE(clip4_dev, "adam_step_segments_dev_clip: null clip4 record");
   return adam_step_segments_dev_launch("adam_step_segments_dev_clip", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper,
                                        host_lr_index, n_segments, lr_dev, n_lr, state3_dev, clip4_dev, stream);
+}
+
+int mvg_adam_step_segments_dev_ex(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
+                                  const float *host_hyper, const int32_t *host_lr_index, const int32_t *host_decoupled, int n_segments,
+                                  const float *lr_dev, int n_lr, float *state3_dev, const float *clip4_dev, void *stream) {
+  return adam_step_segments_dev_launch("adam_step_segments_dev_ex", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper,
+                                       host_lr_index, n_segments, lr_dev, n_lr, state3_dev, clip4_dev, stream, true, host_decoupled);
 }
 
 int mvg_linear_skinny_fwd(const float *x, const float *w, const float *bias, float *y, int rows, int k, int nout,

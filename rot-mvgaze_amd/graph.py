@@ -88,7 +88,7 @@ class GraphedStep:
             moved = [names.get(id(p), "?") for (p, _, _), a, b in zip(self.model.grad_arena()[1], self._plan[1], flags) if a != b]
             what = f"requires_grad of {len(moved)} parameter(s) changed since the capture (first: {moved[0]})"
         elif sig != self._plan[0]:
-            what = "the optimizer's plan changed since the capture (parameter groups, betas, eps or weight_decay)"
+            what = "the optimizer's plan changed since the capture (parameter groups, betas, eps, weight_decay or decoupled_weight_decay)"
         elif epoch != self._plan[2]:
             what = "the optimizer rebuilt its device state since the capture (an eager step with another plan ran in between)"
         elif inputs[2:] != self._plan[3][2:]:

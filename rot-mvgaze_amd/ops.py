@@ -1170,6 +1170,64 @@ def adam_step_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, state3, beta1, beta2
         torch.autograd.graph.increment_version(t)
 
 
+# ---- decoupled weight decay (torch.optim.AdamW): p shrunk by 1 - lr * weight_decay, the moments from the gradient alone
+def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step):
+    """``adam_step`` in decoupled mode (mvg_adamw_step)."""
+    check(lib().mvg_adamw_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, beta1, beta2, eps,
+                               weight_decay, step, _s()), "adamw_step")
+
+
+def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, state3, beta1, beta2, eps, weight_decay):
+    """``adam_step_dev`` in decoupled mode: the same tick on the same state3 (mvg_adamw_step_dev)."""
+    check(lib().mvg_adamw_step_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(lr_dev), _p(state3), beta1, beta2, eps,
+                                   weight_decay, _s()), "adamw_step_dev")
+    for t in (param, exp_avg, exp_avg_sq):
+        torch.autograd.graph.increment_version(t)
+
+
+def _segment_modes(what, segments, at):
+    """The int32 modes of the _ex wrappers from item ``at`` of each record: 0 (False) coupled, 1 (True) decoupled; anything else is
+    refused here, before any launch (the library refuses it as well)."""
+    modes = []
+    for i, s in enumerate(segments):
+        if len(s) != at + 1 or isinstance(s[at], float) or s[at] not in (0, 1):
+            raise ValueError(f"{what}: segment {i} needs {at + 1} items, the last its mode 0 (coupled) or 1 (decoupled): {s!r}")
+        modes.append(int(s[at]))
+    return (C.c_int32 * len(segments))(*modes)
+
+
+def adam_step_segments_ex(param, grad, exp_avg, exp_avg_sq, segments, clip4=None):
+    """``adam_step_segments`` with a mode per segment: (begin, end, lr, beta1, beta2, eps, weight_decay, step, decoupled) records,
+    coupled and decoupled ones side by side in one launch.  clip4 None: no clipping, no guard; otherwise as
+    ``adam_step_segments_clip`` (mvg_adam_step_segments_ex)."""
+    n = len(segments)
+    modes = _segment_modes("adam_step_segments_ex", segments, 8)
+    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
+    hyper = (C.c_float * (5 * n))(*[float(v) for s in segments for v in s[2:7]])
+    steps = (C.c_int32 * n)(*[int(s[7]) for s in segments])
+    check(lib().mvg_adam_step_segments_ex(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, steps, modes, n,
+                                          _p(clip4), _s()), "adam_step_segments_ex")
+    for t in (param, exp_avg, exp_avg_sq):
+        torch.autograd.graph.increment_version(t)
+
+
+def adam_step_segments_dev_ex(param, grad, exp_avg, exp_avg_sq, segments, lr_dev, state3, clip4=None):
+    """``adam_step_segments_dev`` with a mode per segment: (begin, end, lr_index, beta1, beta2, eps, weight_decay, decoupled)
+    records.  clip4 None: no clipping, no guard; otherwise as ``adam_step_segments_dev_clip`` (mvg_adam_step_segments_dev_ex)."""
+    n = len(segments)
+    modes = _segment_modes("adam_step_segments_dev_ex", segments, 7)
+    if state3 is not None and (state3.dim() != 2 or tuple(state3.shape) != (n, 3) or not state3.is_contiguous()):
+        raise ValueError(f"adam_step_segments_dev_ex: state3 must be a contiguous [{n}, 3] table, one row per segment")
+    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
+    index = (C.c_int32 * n)(*[int(s[2]) for s in segments])
+    hyper = (C.c_float * (4 * n))(*[float(v) for s in segments for v in s[3:7]])
+    check(lib().mvg_adam_step_segments_dev_ex(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, index, modes, n,
+                                              _p(lr_dev), 0 if lr_dev is None else lr_dev.numel(), _p(state3), _p(clip4), _s()),
+          "adam_step_segments_dev_ex")
+    for t in (param, exp_avg, exp_avg_sq):
+        torch.autograd.graph.increment_version(t)
+
+
 # ---------------------------------------------------------------- profiling
 def prof_enable(on: bool):
     lib().mvg_prof_enable(int(on))

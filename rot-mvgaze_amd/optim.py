@@ -30,6 +30,14 @@ parameter's stale ``.grad`` is not in it.  Clipping alone adds no synchronisatio
 reads the 16-byte record back after the norm launches - the ONE synchronisation this mode adds (``GradScaler.step`` does the
 same) - and on a skip launches no update and leaves the host step counts alone; with ``capturable="segments"`` nothing comes
 back to the host: the tick and the update read ``skipped`` on the device, so a captured replay clips and skips by itself.
+
+``decoupled_weight_decay`` (a default and a per-group key, ``torch.optim.Adam``'s name; ``AdamW`` is ``Adam`` with it set and
+``weight_decay=1e-2``) selects ``torch.optim.AdamW``'s decay inside the same launches: the parameter is shrunk by
+``1 - lr * weight_decay`` and the moments see the gradient alone.  The mode is one more by-value constant of a segment - it is in
+``_hyper`` and ``_segment_key``, so neighbours that differ in it never share a segment, and flipping it changes the plan.  The
+reference-shaped step is ``mvg_adamw_step`` / ``mvg_adamw_step_dev``; every segmented path calls the ``_ex`` entry points (a mode
+per segment, coupled and decoupled groups in one launch) as soon as one group is decoupled, and exactly today's entry points
+while none is.  A checkpoint written before the key existed loads with ``decoupled_weight_decay = False`` in every group.
 """
 from __future__ import annotations
 
@@ -90,9 +98,13 @@ def plan_segments(entries: Sequence[Tuple[int, int]], group_of: Sequence[Hashabl
 
 class Adam(torch.optim.Optimizer):
     def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, capturable=False, max_grad_norm=None,
-                 skip_nonfinite=False):
+                 skip_nonfinite=False, decoupled_weight_decay=False):
         if lr < 0 or eps < 0 or weight_decay < 0 or not (0 <= betas[0] < 1 and 0 <= betas[1] < 1):
             raise ValueError("invalid Adam hyper-parameter")
+        # decoupled_weight_decay (torch.optim.Adam's name for it; a group may override it): False is Adam's coupled L2 decay,
+        # g + wd * p in both moments; True is AdamW's, p shrunk by 1 - lr * wd and the moments from the gradient alone.  Every
+        # group carries the key (add_param_group fills it in); ``defaults`` keeps the four keys it always had.
+        self._decoupled_default = bool(decoupled_weight_decay)
         super().__init__(params, dict(lr=lr, betas=betas, eps=eps, weight_decay=weight_decay))
         for g in self.param_groups:
             if g["lr"] < 0 or g["eps"] < 0 or g["weight_decay"] < 0 or not (0 <= g["betas"][0] < 1 and 0 <= g["betas"][1] < 1):
@@ -121,6 +133,13 @@ class Adam(torch.optim.Optimizer):
         if self.capturable is True and self._clipping():
             raise ValueError("Adam(capturable=True) takes neither max_grad_norm nor skip_nonfinite: clipping and the guard run on the "
                              "segmented step; use capturable='segments' (it serves one parameter group as well)")
+
+    def add_param_group(self, param_group):
+        """torch's, with the optimizer's decay mode as the default of a group that names none."""
+        if isinstance(param_group, dict):
+            param_group.setdefault("decoupled_weight_decay", self._decoupled_default)
+            param_group["decoupled_weight_decay"] = bool(param_group["decoupled_weight_decay"])
+        super().add_param_group(param_group)
 
     @staticmethod
     def _check_max_grad_norm(value) -> None:
@@ -169,7 +188,24 @@ class Adam(torch.optim.Optimizer):
 
     @staticmethod
     def _hyper(g) -> tuple:
-        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+        return (float(g["lr"]), float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                int(bool(g["decoupled_weight_decay"])))       # the mode: 0 coupled, 1 decoupled, as the C ABI takes it
+
+    def _any_decoupled(self) -> bool:
+        return any(bool(g["decoupled_weight_decay"]) for g in self.param_groups)
+
+    def _step_segments_host(self, arena_p, arena_g, st, segs: Sequence[Segment], clip4) -> None:
+        """The host-lr segmented update over ``segs`` (keys from _hyper): today's entry points while no group is decoupled, the
+        _ex one - a mode per segment - as soon as one is."""
+        if self._any_decoupled():
+            ops.adam_step_segments_ex(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"],
+                                      [(s.begin, s.end) + s.group[:5] + (s.step, s.group[5]) for s in segs], clip4)
+            return
+        records = [(s.begin, s.end) + s.group[:5] + (s.step,) for s in segs]
+        if clip4 is None:
+            ops.adam_step_segments(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], records)
+        else:
+            ops.adam_step_segments_clip(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], records, clip4)
 
     def _state_for(self, model, arena_p, n_entries: int) -> dict:
         """The flat state of ``model``: the two moment buffers at arena offsets and one step count per arena parameter."""
@@ -198,8 +234,10 @@ class Adam(torch.optim.Optimizer):
     @staticmethod
     def _segment_key(index: int, g) -> tuple:
         """What two parameters must share to share a segment of the device-resident step: the group (its INDEX - two groups with
-        equal learning rates today may differ tomorrow) and the constants that travel by value.  The learning rate is not in it."""
-        return (index, float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+        equal learning rates today may differ tomorrow) and the constants that travel by value, the decay mode among them.  The
+        learning rate is not in it."""
+        return (index, float(g["betas"][0]), float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]),
+                int(bool(g["decoupled_weight_decay"])))
 
     def _plan(self, entries, have, steps) -> List[Segment]:
         """plan_segments over ``entries`` = [(param, offset, numel)] for the parameters ``have`` marks, from counts ``steps`` so far."""
@@ -211,7 +249,8 @@ class Adam(torch.optim.Optimizer):
     def _signature(segs: Sequence[Segment]) -> tuple:
         """Bounds, group index and by-value constants per segment.  No step count and no learning rate: every row advances once per
         step, so counts that agreed (or differed) when the table was built still do, and learning rates live in lr_dev."""
-        return tuple((s.begin, s.end) + s.group for s in segs)
+        # (a coupled segment's item is what it was before the mode existed; a decoupled one's ends in "decoupled")
+        return tuple((s.begin, s.end) + s.group[:5] + (("decoupled",) if s.group[5] else ()) for s in segs)
 
     def plan_signature(self, entries=None) -> tuple:
         """The signature of the plan the next step would run if every parameter that requires a gradient received one.  Host-only
@@ -258,6 +297,7 @@ class Adam(torch.optim.Optimizer):
             dev = arena_p.device
             st["sig"] = self._signature(segs)
             st["segs"] = [(s.begin, s.end) + s.group for s in segs]
+            st["segs_coupled"] = [r[:7] for r in st["segs"]]
             st["seg_of"] = [next((k for k, s in enumerate(segs) if s.begin <= off < s.end), -1) if h else -1
                             for (_, off, _), h in zip(entries, have)]
             # a row holds the count so far; the step's own launch advances it (a parameter unfrozen later starts at step 1)
@@ -266,13 +306,20 @@ class Adam(torch.optim.Optimizer):
             st["lr_dev"] = torch.tensor(st["lr_host"], dtype=torch.float32).to(dev)
             st["epoch"] = st.get("epoch", 0) + 1
         self.sync_lr()
-        if not self._clipping():
-            ops.adam_step_segments_dev(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs"], st["lr_dev"], st["state3"])
-            return
-        self._check_max_grad_norm(self.max_grad_norm)
-        clip4, ws = self._clip_buffers(st, arena_p.device, len(st["segs"]))
-        ops.grad_norm_segments(arena_g, st["segs"], self.max_grad_norm, self.skip_nonfinite, clip4, ws)
-        ops.adam_step_segments_dev_clip(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs"], st["lr_dev"], st["state3"], clip4)
+        # st["segs"] = (begin, end, group index, beta1, beta2, eps, weight_decay, mode): the _ex record; today's entry points, which
+        # run while no group is decoupled, take it without the mode
+        clip4 = None
+        if self._clipping():
+            self._check_max_grad_norm(self.max_grad_norm)
+            clip4, ws = self._clip_buffers(st, arena_p.device, len(st["segs"]))
+            ops.grad_norm_segments(arena_g, st["segs"], self.max_grad_norm, self.skip_nonfinite, clip4, ws)
+        if self._any_decoupled():
+            ops.adam_step_segments_dev_ex(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs"], st["lr_dev"], st["state3"], clip4)
+        elif clip4 is None:
+            ops.adam_step_segments_dev(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs_coupled"], st["lr_dev"], st["state3"])
+        else:
+            ops.adam_step_segments_dev_clip(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["segs_coupled"], st["lr_dev"],
+                                            st["state3"], clip4)
 
     # ---- max_grad_norm / skip_nonfinite: the device record and the norm's workspace
     def _clip_buffers(self, st, device, n_segments: int):
@@ -360,8 +407,7 @@ class Adam(torch.optim.Optimizer):
                     continue                                                    # skipped: no update, the step counts stay
                 st["steps"] = steps
                 st["step"] = max(steps)
-                ops.adam_step_segments_clip(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"],
-                                            [(s.begin, s.end) + s.group + (s.step,) for s in segs], clip4)
+                self._step_segments_host(arena_p, arena_g, st, segs, clip4)
                 for (p, _, _), h in zip(entries, have):
                     if h:
                         torch.autograd.graph.increment_version(p)
@@ -378,17 +424,18 @@ class Adam(torch.optim.Optimizer):
                     # {step, 1 - beta1^step, sqrt(1 - beta2^step)}: advanced on the device by every (captured or eager) step
                     st["state3"] = torch.tensor([float(st["step"] - 1), 0.0, 0.0], dtype=torch.float32).to(arena_p.device)
                 self.sync_lr()
-                ops.adam_step_dev(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["lr_dev"], st["state3"], float(g["betas"][0]),
-                                  float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
+                step_dev = ops.adamw_step_dev if g["decoupled_weight_decay"] else ops.adam_step_dev
+                step_dev(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], st["lr_dev"], st["state3"], float(g["betas"][0]),
+                         float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]))
             elif whole:
                 g = self.param_groups[0]
-                ops.adam_step(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], float(g["lr"]), float(g["betas"][0]),
-                              float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), st["step"])
+                step_host = ops.adamw_step if g["decoupled_weight_decay"] else ops.adam_step
+                step_host(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"], float(g["lr"]), float(g["betas"][0]),
+                          float(g["betas"][1]), float(g["eps"]), float(g["weight_decay"]), st["step"])
             else:
                 segs = plan_segments([(off, n) for (_, off, n) in entries], [self._hyper(g) if g is not None else None for g in groups],
                                      have, steps)
-                ops.adam_step_segments(arena_p, arena_g, st["exp_avg"], st["exp_avg_sq"],
-                                       [(s.begin, s.end) + s.group + (s.step,) for s in segs])
+                self._step_segments_host(arena_p, arena_g, st, segs, None)
             # the parameters alias the arena through `.data` (their own version counters): mark them modified, as an
             # in-place torch op would (the inference path's cache of split weights keys on the version)
             for (p, _, _), h in zip(entries, have):
@@ -421,5 +468,18 @@ class Adam(torch.optim.Optimizer):
         sd = dict(state_dict)
         flat = sd.pop("mvg_arena_state", None)
         super().load_state_dict(sd)
+        for g in self.param_groups:                 # (a checkpoint written before the flag existed: the coupled decay it ran)
+            g.setdefault("decoupled_weight_decay", False)
         self._flat.clear()
         self._pending = [dict(e) for e in flat] if flat else None
+
+
+class AdamW(Adam):
+    """``Adam`` with torch.optim.AdamW's defaults: ``weight_decay=1e-2`` and ``decoupled_weight_decay=True``.  Everything else -
+    parameter groups (a group may set ``decoupled_weight_decay=False`` or ``weight_decay=0``), frozen parameters, ``capturable``,
+    ``max_grad_norm``, ``skip_nonfinite``, the checkpoint format - is Adam's."""
+
+    def __init__(self, params, lr=1e-3, betas=(0.9, 0.999), eps=1e-8, weight_decay=1e-2, capturable=False, max_grad_norm=None,
+                 skip_nonfinite=False, decoupled_weight_decay=True):
+        super().__init__(params, lr=lr, betas=betas, eps=eps, weight_decay=weight_decay, capturable=capturable,
+                         max_grad_norm=max_grad_norm, skip_nonfinite=skip_nonfinite, decoupled_weight_decay=decoupled_weight_decay)
