@@ -617,6 +617,36 @@ enum { MVG_GAZE_ERR_COUNT = 0, MVG_GAZE_ERR_SUM = 1, MVG_GAZE_ERR_SUMSQ = 2, MVG
 int mvg_gaze_error_update(const float *preds, const float *gt, int iters, int dirs, int batch, double *record, float *err_out,
                           int64_t capacity, void *stream);
 
+/* Multi-view consensus gaze: ONE estimate per sample from all D = views (views - 1) directed pair predictions, by the model's own
+ * premise that views relate through the head-pose rotations (mvg_relative_rotation: rel = rot_i rot_j^T): rot[b][s]^T takes a
+ * prediction made in view s's camera frame to the head frame, where predictions can be averaged.  preds fp32
+ * [iters][D][batch][2] (pitch, yaw), the heads' stacked buffer: for pair p = (i < j) direction 2p predicts for view s = i with
+ * partner q = j, direction 2p + 1 for s = j with q = i.  rot fp32 [batch][views][3][3].  weights fp32 [batch][views] or NULL
+ * (all 1): a per-view confidence, 0 = the view is missing.  Per item (it, b), in double:
+ *   w_d = weights[b][s(d)] * weights[b][q(d)];  contribution d is active iff w_d > 0.  Inactive contributions are SKIPPED, not
+ *   multiplied by zero: a NaN in their preds row, or in the rot of a view that appears in no active contribution, reaches no sum.
+ *   v_d = (cos p sin y, sin p, cos p cos y);   h = sum_active w_d rot[b][s(d)]^T v_d;   W = sum_active w_d;   e = h / |h|.
+ *   head[it][b] = e.   For EVERY view t, whatever its weight: u = rot[b][t] e, views_out[it][t][b] = (asin(clamp(u.y, -1, 1)),
+ *   atan2(u.x, u.z)); a non-finite rot[b][t] gives a NaN row for that t only.
+ *   stats (may be NULL) [it][b] = (|h| / W, the resultant length in [0, 1];  sum_active w_d acos(clamp(e . rot^T v_d, -1, 1))
+ *   180 / pi / W, the weighted mean disagreement in degrees).  head and views_out have the same bits with and without stats.
+ * An item is degenerate - head, every views_out row and stats are NaN - when no contribution is active, a weight of the sample is
+ * negative or non-finite, an active preds row or the rot of an active source view is non-finite, or |h| <= 1e-4 W (a
+ * definition: below it the predictions cancel).  One thread per item, no LDS, no atomics: equal calls leave equal bits.  Nothing is
+ * allocated and nothing synchronises (capturable).  A NULL preds / rot / head / views_out, views outside 2..8, iters or batch
+ * < 1, iters * batch > INT32_MAX and a preds / views_out pointer that is not 8-byte aligned are rejected before any HIP call.
+ * (Added under ABI v13: additive.) */
+int mvg_gaze_consensus_fwd(const float *preds, const float *rot, const float *weights, int iters, int views, int batch, float *head,
+                           float *views_out, float *stats, void *stream);
+/* Its backward: dviews fp32 [iters][views][batch][2] -> dpreds fp32 [iters][D][batch][2]; every row is written (the caller clears
+ * nothing).  With u = rot[b][t] e as above, the gradient on u is g_t = (dyaw u.z / r2, dpitch / sqrt(1 - u.y^2), -dyaw u.x / r2),
+ * r2 = u.x^2 + u.z^2; a target whose forward row is NaN, or with r2 == 0 or u.y^2 >= 1, is left out.  g_e = sum_t rot[b][t]^T g_t,
+ * g_h = (g_e - (g_e . e) e) / |h|, g_v = w_d rot[b][s(d)] g_h, dpitch_d = g_v . (-sin p sin y, cos p, -sin p cos y), dyaw_d = g_v .
+ * (cos p cos y, 0, -cos p sin y).  Inactive rows and all rows of a degenerate item are exactly 0.  No gradient goes to rot or
+ * weights.  Same checks (dviews, preds, rot, dpreds required; the three row buffers 8-byte aligned), same guarantees. */
+int mvg_gaze_consensus_bwd(const float *dviews, const float *preds, const float *rot, const float *weights, int iters, int views,
+                           int batch, float *dpreds, void *stream);
+
 /* ---------------------------------------------------------------- stereo pair index (HOST)
  * GazeDataset.__init__'s idx_to_kv build, dataset/gaze.py:39-73, driven by CPython's
  * random.seed(int)/random.choice stream (MT19937 + getrandbits rejection).  Pure host integer
@@ -1121,7 +1151,8 @@ int64_t mvg_session_tensor_numel(const mvg_session *s, int i);
 /* Bytes of the workspace mvg_session_bind wants (host only). */
 size_t mvg_session_workspace_bytes(const mvg_session *s);
 /* Library calls one mvg_session_forward queues (host only; a stream-K / split-K GEMM adds its fix-up kernel on the device):
- * the plan's steps, and one more while mvg_session_set_error_record holds a record. */
+ * the plan's steps, one more while mvg_session_set_error_record holds a record, and one more while mvg_session_set_consensus
+ * holds its outputs. */
 int mvg_session_launches(const mvg_session *s);
 /* The plan's steps in the order mvg_session_forward queues them (host only, both forms): how many, and the entry point step
  * i calls, without the "mvg_" prefix, e.g. "conv_fprop_bf16_affine" (a step that records ranges still names the plain entry
@@ -1161,6 +1192,14 @@ int mvg_session_set_range_record(mvg_session *s, uint32_t *record_dev);
  * their names, mvg_session_num_steps - is untouched, and mvg_session_launches reports one more.  A record without gt_dev,
  * capacity < 0 and err_out with capacity == 0 are rejected. */
 int mvg_session_set_error_record(mvg_session *s, const float *gt_dev, double *record_dev, float *err_out, int64_t capacity);
+/* The consensus gaze of a session (host only: the pointers are only stored; both compute forms).  head [num_iter][batch][3],
+ * views_out [num_iter][views][batch][2], stats [num_iter][batch][2] or NULL and weights_dev [batch][views] or NULL: the caller's
+ * static device buffers, as mvg_gaze_consensus_fwd takes them.  views_out = NULL (the default) restores the plain forward exactly.
+ * With views_out mvg_session_forward queues one mvg_gaze_consensus_fwd over its own preds and rot after the plan's last step and
+ * before the error update, if one is set: the four outputs are unchanged, still no synchronisation and no allocation; the plan -
+ * its steps, their names, mvg_session_num_steps - is untouched, and mvg_session_launches reports one more.  views_out without
+ * head is rejected.  (Added under ABI v13: additive.) */
+int mvg_session_set_consensus(mvg_session *s, const float *weights_dev, float *head, float *views_out, float *stats);
 
 #ifdef __cplusplus
 }

@@ -23,9 +23,10 @@ def __getattr__(name):
         "GradAllReducer": "dp",
         "Adam": "optim", "AdamW": "optim",
         "AngularErrorMeter": "metrics",
+        "gaze_consensus": "consensus", "MultiViewConsensusLoss": "losses",
     }
     if name in lazy:
         return getattr(importlib.import_module("." + lazy[name], __name__), name)
-    if name in ("model", "losses", "geometry", "pair_index", "dp", "ops", "backbone", "heads", "_lib", "optim", "metrics"):
+    if name in ("model", "losses", "geometry", "pair_index", "dp", "ops", "backbone", "heads", "_lib", "optim", "metrics", "consensus"):
         return importlib.import_module("." + name, __name__)
     raise AttributeError(name)

@@ -287,6 +287,10 @@ SIGNATURES = {
     # gaze error meter (metrics.AngularErrorMeter): float64 angular error accumulated on the device, and its session hook
     "mvg_gaze_error_update": (_I, [_P, _P, _I, _I, _I, _P, _P, _I64, _P]),
     "mvg_session_set_error_record": (_I, [_P, _P, _P, _P, _I64]),
+    # multi-view consensus gaze (consensus.gaze_consensus): one estimate per sample from all directed pairs, and its session hook
+    "mvg_gaze_consensus_fwd": (_I, [_P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
+    "mvg_gaze_consensus_bwd": (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "mvg_session_set_consensus": (_I, [_P, _P, _P, _P, _P]),
 }
 
 _lib = None

@@ -803,6 +803,192 @@ __global__ __launch_bounds__(256) void gaze_error_update_kernel(const float *__r
   }
 }
 
+// ---- multi-view consensus gaze -------------------------------------------------------------------
+// One gaze per sample from all D = V (V - 1) directed pair predictions: each prediction goes to the head frame through its own
+// view's rotation (rot[b][s]^T, the premise of mvg_relative_rotation), the weighted resultant h is normalised and rotated back
+// into every view.  One thread per (iteration, sample) item, lanes along the batch (the pred / dpred rows of one direction are
+// 8-byte accesses next to each other); the (s, q) of direction d comes from the nested i < j loop, kept rolled; all arithmetic
+// in double like the meter above (a call has I * B items, a few thousand at most), results stored as fp32.  No LDS, no
+// atomics, nothing depends on the launch geometry: equal calls leave equal bits.  An inactive contribution (w_d = weights[s] *
+// weights[q] not > 0) is skipped - neither its pred row nor, unless another active contribution uses it, its view's rot is read
+// into the sums.  The definition, in full, is at mvg_gaze_consensus_fwd in the header.
+struct ConsSum {
+  double h0, h1, h2, W;     // the weighted head-frame resultant and the weight total of the active contributions
+  bool bad;                 // the item is degenerate for a reason other than |h| <= 1e-4 W
+};
+__device__ __forceinline__ bool cons_rot(const float *__restrict__ R, double (&m)[9]) {
+  bool ok = true;
+#pragma unroll
+  for (int k = 0; k < 9; ++k) {
+    const float f = R[k];
+    ok = ok && isfinite(f);
+    m[k] = (double)f;
+  }
+  return ok;
+}
+// (pitch, yaw) -> the unit vector, and its image in the head frame m^T v
+__device__ __forceinline__ void cons_head_vec(const double (&m)[9], double p, double y, double &c0, double &c1, double &c2) {
+  const double cp = cos(p), v0 = cp * sin(y), v1 = sin(p), v2 = cp * cos(y);
+  c0 = dot3_d(m[0], m[3], m[6], v0, v1, v2);
+  c1 = dot3_d(m[1], m[4], m[7], v0, v1, v2);
+  c2 = dot3_d(m[2], m[5], m[8], v0, v1, v2);
+}
+__device__ __forceinline__ double cons_weight(const float *__restrict__ wv, int s, int q) {
+  return wv ? (double)wv[s] * (double)wv[q] : 1.0;
+}
+// P: the item's row of direction 0 (direction d is P[d * batch]); R: rot[b]; wv: weights[b] or null
+__device__ __forceinline__ ConsSum cons_sum(const float2 *__restrict__ P, const float *__restrict__ R, const float *__restrict__ wv,
+                                            int views, int batch) {
+  ConsSum c = {0.0, 0.0, 0.0, 0.0, false};
+  if (wv)
+    for (int t = 0; t < views; ++t) {
+      const float w = wv[t];
+      if (!(isfinite(w) && w >= 0.f)) c.bad = true;
+    }
+  if (c.bad) return c;
+  long long d = 0;
+#pragma unroll 1
+  for (int i = 0; i < views; ++i)
+#pragma unroll 1
+    for (int j = i + 1; j < views; ++j)
+#pragma unroll 1
+      for (int k = 0; k < 2; ++k, ++d) {
+        const int s = k ? j : i, q = k ? i : j;
+        const double w = cons_weight(wv, s, q);
+        if (!(w > 0.0)) continue;
+        const float2 pr = P[d * batch];
+        double m[9], c0, c1, c2;
+        const bool ok = cons_rot(R + s * 9, m);
+        if (!(ok && isfinite(pr.x) && isfinite(pr.y))) {
+          c.bad = true;
+          continue;
+        }
+        cons_head_vec(m, (double)pr.x, (double)pr.y, c0, c1, c2);
+        c.h0 = fma(w, c0, c.h0);
+        c.h1 = fma(w, c1, c.h1);
+        c.h2 = fma(w, c2, c.h2);
+        c.W += w;
+      }
+  if (!(c.W > 0.0)) c.bad = true;
+  return c;
+}
+__global__ __launch_bounds__(256) void gaze_consensus_fwd_kernel(const float *__restrict__ preds, const float *__restrict__ rot,
+                                                                 const float *__restrict__ weights, int iters, int views, int batch,
+                                                                 float *__restrict__ head, float *__restrict__ views_out,
+                                                                 float *__restrict__ stats) {
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (item >= (long long)iters * batch) return;
+  const int it = (int)(item / batch), b = (int)(item - (long long)it * batch);
+  const int dirs = views * (views - 1);
+  const float2 *P = (const float2 *)preds + (long long)it * dirs * batch + b;
+  const float *R = rot + (long long)b * views * 9, *wv = weights ? weights + (long long)b * views : nullptr;
+  float2 *VO = (float2 *)views_out + (long long)it * views * batch + b;
+  const float nanf_ = __builtin_nanf("");
+  const ConsSum c = cons_sum(P, R, wv, views, batch);
+  const double n = sqrt(dot3_d(c.h0, c.h1, c.h2, c.h0, c.h1, c.h2));
+  if (c.bad || !(n > 1e-4 * c.W)) {           // degenerate: NaN everywhere
+    head[3 * item] = head[3 * item + 1] = head[3 * item + 2] = nanf_;
+    for (int t = 0; t < views; ++t) VO[(long long)t * batch] = make_float2(nanf_, nanf_);
+    if (stats) stats[2 * item] = stats[2 * item + 1] = nanf_;
+    return;
+  }
+  const double e0 = c.h0 / n, e1 = c.h1 / n, e2 = c.h2 / n;
+  head[3 * item] = (float)e0;
+  head[3 * item + 1] = (float)e1;
+  head[3 * item + 2] = (float)e2;
+#pragma unroll 1
+  for (int t = 0; t < views; ++t) {           // every view gets the consensus in its own frame, whatever its weight
+    double m[9];
+    float2 o = make_float2(nanf_, nanf_);
+    if (cons_rot(R + t * 9, m)) {
+      const double u0 = dot3_d(m[0], m[1], m[2], e0, e1, e2), u1 = dot3_d(m[3], m[4], m[5], e0, e1, e2),
+                   u2 = dot3_d(m[6], m[7], m[8], e0, e1, e2);
+      o = make_float2((float)asin(fmin(fmax(u1, -1.0), 1.0)), (float)atan2(u0, u2));
+    }
+    VO[(long long)t * batch] = o;
+  }
+  if (!stats) return;
+  double acc = 0.0;
+  long long d = 0;
+#pragma unroll 1
+  for (int i = 0; i < views; ++i)
+#pragma unroll 1
+    for (int j = i + 1; j < views; ++j)
+#pragma unroll 1
+      for (int k = 0; k < 2; ++k, ++d) {
+        const int s = k ? j : i, q = k ? i : j;
+        const double w = cons_weight(wv, s, q);
+        if (!(w > 0.0)) continue;
+        const float2 pr = P[d * batch];
+        double m[9], c0, c1, c2;
+        cons_rot(R + s * 9, m);
+        cons_head_vec(m, (double)pr.x, (double)pr.y, c0, c1, c2);
+        acc = fma(w, acos(fmin(fmax(dot3_d(e0, e1, e2, c0, c1, c2), -1.0), 1.0)), acc);
+      }
+  stats[2 * item] = (float)(n / c.W);
+  stats[2 * item + 1] = (float)(acc * (180.0 / 3.14159265358979323846) / c.W);
+}
+__global__ __launch_bounds__(256) void gaze_consensus_bwd_kernel(const float *__restrict__ dviews, const float *__restrict__ preds,
+                                                                 const float *__restrict__ rot, const float *__restrict__ weights,
+                                                                 int iters, int views, int batch, float *__restrict__ dpreds) {
+  const long long item = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (item >= (long long)iters * batch) return;
+  const int it = (int)(item / batch), b = (int)(item - (long long)it * batch);
+  const int dirs = views * (views - 1);
+  const float2 *P = (const float2 *)preds + (long long)it * dirs * batch + b;
+  float2 *DP = (float2 *)dpreds + (long long)it * dirs * batch + b;
+  const float *R = rot + (long long)b * views * 9, *wv = weights ? weights + (long long)b * views : nullptr;
+  const float2 *DV = (const float2 *)dviews + (long long)it * views * batch + b;
+  const ConsSum c = cons_sum(P, R, wv, views, batch);
+  const double n = sqrt(dot3_d(c.h0, c.h1, c.h2, c.h0, c.h1, c.h2));
+  const bool degenerate = c.bad || !(n > 1e-4 * c.W);
+  double g0 = 0.0, g1 = 0.0, g2 = 0.0;        // the gradient on h
+  if (!degenerate) {
+    const double e0 = c.h0 / n, e1 = c.h1 / n, e2 = c.h2 / n;
+    double a0 = 0.0, a1 = 0.0, a2 = 0.0;      // the gradient on the unit vector: sum over the targets of rot[t]^T g_t
+#pragma unroll 1
+    for (int t = 0; t < views; ++t) {
+      double m[9];
+      if (!cons_rot(R + t * 9, m)) continue;  // its forward row is NaN: no gradient
+      const double u0 = dot3_d(m[0], m[1], m[2], e0, e1, e2), u1 = dot3_d(m[3], m[4], m[5], e0, e1, e2),
+                   u2 = dot3_d(m[6], m[7], m[8], e0, e1, e2);
+      const double r2 = fma(u0, u0, u2 * u2), s1 = u1 * u1;
+      if (r2 == 0.0 || s1 >= 1.0) continue;
+      const float2 dv = DV[(long long)t * batch];
+      const double dpitch = (double)dv.x, dyaw = (double)dv.y;
+      const double t0 = dyaw * u2 / r2, t1 = dpitch / sqrt(1.0 - s1), t2 = -dyaw * u0 / r2;
+      a0 += dot3_d(m[0], m[3], m[6], t0, t1, t2);
+      a1 += dot3_d(m[1], m[4], m[7], t0, t1, t2);
+      a2 += dot3_d(m[2], m[5], m[8], t0, t1, t2);
+    }
+    const double ae = dot3_d(a0, a1, a2, e0, e1, e2);
+    g0 = (a0 - ae * e0) / n;
+    g1 = (a1 - ae * e1) / n;
+    g2 = (a2 - ae * e2) / n;
+  }
+  long long d = 0;
+#pragma unroll 1
+  for (int i = 0; i < views; ++i)
+#pragma unroll 1
+    for (int j = i + 1; j < views; ++j)
+#pragma unroll 1
+      for (int k = 0; k < 2; ++k, ++d) {
+        const int s = k ? j : i, q = k ? i : j;
+        float2 o = make_float2(0.f, 0.f);     // every row is written: inactive rows and degenerate items are exactly 0
+        const double w = degenerate ? 0.0 : cons_weight(wv, s, q);
+        if (w > 0.0) {
+          const float2 pr = P[d * batch];
+          double m[9];
+          cons_rot(R + s * 9, m);
+          const double v0 = w * dot3_d(m[0], m[1], m[2], g0, g1, g2), v1 = w * dot3_d(m[3], m[4], m[5], g0, g1, g2),
+                       v2 = w * dot3_d(m[6], m[7], m[8], g0, g1, g2);
+          const double p = (double)pr.x, y = (double)pr.y, sp = sin(p), cp = cos(p), sy = sin(y), cy = cos(y);
+          o = make_float2((float)dot3_d(v0, v1, v2, -sp * sy, cp, -sp * cy), (float)(cp * fma(v0, cy, -v2 * sy)));
+        }
+        DP[d * batch] = o;
+      }
+}
+
 // Adam with its step counter and learning rate on the DEVICE (a captured step replays with nothing from the host):
 // adam_tick_kernel advances state = {step, bias correction 1, sqrt(bias correction 2)} (one thread), adam_dev_kernel is
 // adam_kernel reading lr from hyper[0] and the corrections from state.
@@ -1470,6 +1656,47 @@ int mvg_gaze_error_update(const float *preds, const float *gt, int iters, int di
   hipLaunchKernelGGL(gaze_error_update_kernel, dim3((unsigned)(iters * dirs)), dim3(256), 0, st, preds, gt, dirs, batch, record, err_out,
                      (long long)capacity);
   return check_launch("gaze_error_update");
+}
+
+// (the checks the two consensus entry points share, before the first HIP call; rows of two floats move as 8-byte vectors)
+static int consensus_check(const char *who, int iters, int views, int batch, const void *rows0, const void *rows1) {
+  MVG_REQUIRE(views >= 2 && views <= 8, "%s: views must be 2..8 (got %d)", who, views);
+  MVG_REQUIRE(iters >= 1 && batch >= 1, "%s: iters and batch must be >= 1 (got %d, %d)", who, iters, batch);
+  MVG_REQUIRE((int64_t)iters * batch <= INT32_MAX, "%s: iters * batch = %lld items exceed one grid", who,
+              (long long)iters * batch);
+  MVG_REQUIRE(((uintptr_t)rows0 | (uintptr_t)rows1) % 8 == 0, "%s: the (pitch, yaw) buffers must be 8-byte aligned", who);
+  return 0;
+}
+
+int mvg_gaze_consensus_fwd(const float *preds, const float *rot, const float *weights, int iters, int views, int batch, float *head,
+                           float *views_out, float *stats, void *stream) {
+  MVG_REQUIRE(preds, "gaze_consensus_fwd: null preds");
+  MVG_REQUIRE(rot, "gaze_consensus_fwd: null rot");
+  MVG_REQUIRE(head, "gaze_consensus_fwd: null head");
+  MVG_REQUIRE(views_out, "gaze_consensus_fwd: null views_out");
+  if (int e = consensus_check("gaze_consensus_fwd", iters, views, batch, preds, views_out)) return e;
+  hipStream_t st = (hipStream_t)stream;
+  const double items = (double)iters * batch, dirs = (double)views * (views - 1);
+  ProfScope ps(MVG_K_LOSS, st, 0.0, items * (8.0 * dirs + 8.0 * views + 12.0 + (stats ? 8.0 : 0.0)) + batch * views * (36.0 + (weights ? 4.0 : 0.0)));
+  hipLaunchKernelGGL(gaze_consensus_fwd_kernel, dim3((unsigned)ceil_div((int64_t)iters * batch, 256)), dim3(256), 0, st, preds, rot, weights,
+                     iters, views, batch, head, views_out, stats);
+  return check_launch("gaze_consensus_fwd");
+}
+
+int mvg_gaze_consensus_bwd(const float *dviews, const float *preds, const float *rot, const float *weights, int iters, int views,
+                           int batch, float *dpreds, void *stream) {
+  MVG_REQUIRE(dviews, "gaze_consensus_bwd: null dviews");
+  MVG_REQUIRE(preds, "gaze_consensus_bwd: null preds");
+  MVG_REQUIRE(rot, "gaze_consensus_bwd: null rot");
+  MVG_REQUIRE(dpreds, "gaze_consensus_bwd: null dpreds");
+  if (int e = consensus_check("gaze_consensus_bwd", iters, views, batch, preds, dpreds)) return e;
+  MVG_REQUIRE((uintptr_t)dviews % 8 == 0, "gaze_consensus_bwd: the (pitch, yaw) buffers must be 8-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  const double items = (double)iters * batch, dirs = (double)views * (views - 1);
+  ProfScope ps(MVG_K_LOSS, st, 0.0, items * (16.0 * dirs + 8.0 * views) + batch * views * (36.0 + (weights ? 4.0 : 0.0)));
+  hipLaunchKernelGGL(gaze_consensus_bwd_kernel, dim3((unsigned)ceil_div((int64_t)iters * batch, 256)), dim3(256), 0, st, dviews, preds, rot,
+                     weights, iters, views, batch, dpreds);
+  return check_launch("gaze_consensus_bwd");
 }
 
 int mvg_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev, float *state3,

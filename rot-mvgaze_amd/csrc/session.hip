@@ -297,7 +297,11 @@ int mvg_session_forward(mvg_session *s, const void *const *host_view_ptrs, const
   }
   for (const SStep &t : s->plan.steps)
     if (int e = run_step(s, a, t, stream)) return e;
-  if (s->err_record)      // mvg_session_set_error_record: the gaze error meter over this forward's preds (not a step of the plan)
+  if (s->cons_views)      // mvg_session_set_consensus: one gaze per sample from this forward's preds and rot (not a step of the plan)
+    if (int e = mvg_gaze_consensus_fwd(preds, rot, s->cons_weights, s->cfg.num_iter, s->cfg.views, s->cfg.batch, s->cons_head, s->cons_views,
+                                       s->cons_stats, stream))
+      return e;
+  if (s->err_record)     // mvg_session_set_error_record: the gaze error meter over this forward's preds (not a step of the plan)
     return mvg_gaze_error_update(preds, s->err_gt, s->cfg.num_iter, s->plan.dirs, s->cfg.batch, s->err_record, s->err_out, s->err_capacity,
                                  stream);
   return 0;

@@ -1004,7 +1004,7 @@ int64_t mvg_session_tensor_numel(const mvg_session *s, int i) {
 
 size_t mvg_session_workspace_bytes(const mvg_session *s) { return s ? (size_t)s->plan.workspace_bytes : 0; }
 
-int mvg_session_launches(const mvg_session *s) { return s ? (int)s->plan.steps.size() + (s->err_record ? 1 : 0) : -1; }
+int mvg_session_launches(const mvg_session *s) { return s ? (int)s->plan.steps.size() + (s->err_record ? 1 : 0) + (s->cons_views ? 1 : 0) : -1; }
 
 int mvg_session_compute(const mvg_session *s) { return s ? s->plan.compute : -1; }
 
@@ -1052,6 +1052,22 @@ int mvg_session_set_error_record(mvg_session *s, const float *gt_dev, double *re
   s->err_record = record_dev;
   s->err_out = record_dev ? err_out : nullptr;
   s->err_capacity = record_dev ? capacity : 0;
+  return 0;
+}
+
+int mvg_session_set_consensus(mvg_session *s, const float *weights_dev, float *head, float *views_out, float *stats) {
+  if (!s) {
+    mvg::set_error("session_set_consensus: null session");
+    return 2;
+  }
+  if (views_out && !head) {
+    mvg::set_error("session_set_consensus: a consensus needs the head buffer with views_out");
+    return 2;
+  }
+  s->cons_weights = views_out ? weights_dev : nullptr;
+  s->cons_head = views_out ? head : nullptr;
+  s->cons_views = views_out;
+  s->cons_stats = views_out ? stats : nullptr;
   return 0;
 }
 

@@ -110,4 +110,9 @@ struct mvg_session {
   double *err_record = nullptr;
   float *err_out = nullptr;
   int64_t err_capacity = 0;
+  // mvg_session_set_consensus: what mvg_gaze_consensus_fwd takes after the last step; cons_views null = no consensus launch
+  const float *cons_weights = nullptr;
+  float *cons_head = nullptr;
+  float *cons_views = nullptr;
+  float *cons_stats = nullptr;
 };

@@ -216,3 +216,26 @@ class MultiViewIterationLoss(AbstractLoss):
         dw = [(self._rel_weight if d % 2 == 0 else self._rel_weight * self._reference_decay) / npairs
               for d in range(D)]
         return _FusedIterLossFn.apply(preds, gt_dir, iw, dw)
+
+
+class MultiViewConsensusLoss(AbstractLoss):
+    """The angular loss of the consensus gaze: ``sum_it w_it * (weight / V) * sum_t mean_b theta(views[it, t], gt[:, t])`` over
+    ``out["consensus"]["views"]`` of ``forward_multiview(..., consensus=True)`` and gt [B,V,2], with IterationLoss's iteration
+    weights; the caller adds it to ``MultiViewIterationLoss``.  The fused loss launch with one "direction" per view; the gradient
+    reaches the pair predictions through ``consensus.gaze_consensus``.
+
+    Precondition: every sample has an active contribution and every view a label (targets cannot be masked).  A degenerate
+    sample has a NaN consensus and makes the loss NaN; ``optim.Adam(skip_nonfinite=True)`` then skips that step."""
+
+    def __init__(self, weight: float = 0.01, iter_decay: float = 0.5, additional_decay: Optional[float] = None):
+        super().__init__()
+        self._weight, self._iter_decay, self._addtional_decay = weight, iter_decay, additional_decay
+
+    def forward(self, out: Dict[str, Any], gt: Tensor) -> Tensor:
+        cons = out.get("consensus")
+        if cons is None:
+            raise ValueError("MultiViewConsensusLoss: the dict holds no 'consensus' (forward_multiview(..., consensus=True))")
+        views = cons["views"]
+        I, V = views.shape[0], views.shape[1]
+        gt_dir = gt.to(torch.float32).transpose(0, 1)          # [V,B,2]: "direction" t is view t
+        return _FusedIterLossFn.apply(views, gt_dir, iteration_weights(I, self._iter_decay, self._addtional_decay), [self._weight / V] * V)

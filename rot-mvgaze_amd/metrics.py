@@ -49,6 +49,7 @@ class AngularErrorMeter:
       ``update(data)``       the dict ``FeatRotationSymm.forward`` returned (``_mvg_preds``, ``gt_gaze``, ``gt_gaze_1``);
       ``update(out, gt)``    the dict of ``forward_multiview`` and gt ``[B,V,2]``;
       ``update(pred, gt)``   device tensors ``[N,2]`` (one cell).
+    ``update_consensus(out, gt)`` (a meter with ``dirs = V``) takes the consensus gaze of ``forward_multiview(..., consensus=True)``.
     Inside a captured step the eager warm-up steps of ``GraphedStep`` count like any other update (the capture pass itself runs
     nothing): call ``reset()`` after building the graph (stream-ordered, so it lands before the first replay)."""
 
@@ -98,6 +99,26 @@ class AngularErrorMeter:
         g = gt_dir.detach().to(torch.float32).contiguous()
         with torch.cuda.device(p.device):
             ops.gaze_error_update(p, g, I, D, B, self.record, self.err_out, self.capacity)
+
+    def update_consensus(self, out: Dict[str, Any], gt: Tensor) -> None:
+        """For a meter made with ``dirs = V``: adds the errors of the consensus gaze (``out["consensus"]["views"]`` [I,V,B,2] of
+        ``forward_multiview(..., consensus=True)``) against gt [B,V,2] - cell (it, t) is view t.  One ``mvg_gaze_error_update``;
+        a degenerate sample (NaN consensus) counts in ``nonfinite``."""
+        cons = out.get("consensus") if isinstance(out, dict) else None
+        if cons is None:
+            raise ValueError("AngularErrorMeter.update_consensus: the dict holds no 'consensus' (forward_multiview(..., consensus=True))")
+        views = cons["views"]
+        if not (isinstance(views, Tensor) and views.is_cuda and isinstance(gt, Tensor) and gt.is_cuda):
+            raise RuntimeError("AngularErrorMeter: the MI355X path needs device tensors (no CPU fallback)")
+        I, V, B = views.shape[0], views.shape[1], views.shape[2]
+        if (I, V) != (self.num_iter, self.dirs) or tuple(gt.shape) != (B, V, 2):
+            raise ValueError(f"AngularErrorMeter: made for {self.num_iter} iterations x {self.dirs} views, got consensus views "
+                             f"{tuple(views.shape)} and labels {tuple(gt.shape)}")
+        self._ensure(views.device)
+        p = views.detach().to(torch.float32).contiguous()
+        g = gt.detach().to(torch.float32).transpose(0, 1).contiguous()
+        with torch.cuda.device(p.device):
+            ops.gaze_error_update(p, g, I, V, B, self.record, self.err_out, self.capacity)
 
     def reset(self) -> None:
         """Back to the empty record (a stream-ordered fill; the stored per-sample errors are trimmed by the counters)."""

@@ -398,9 +398,14 @@ class MultiViewGaze(nn.Module):
         lifted, feats, preds = _HeadFn.apply(self, img_feat, rot, *self._head_params)
         return img_feat, lifted, feats, preds
 
-    def forward_multiview(self, img: Tensor, rot: Tensor) -> Dict[str, Any]:
+    def forward_multiview(self, img: Tensor, rot: Tensor, consensus: bool = False, view_weights: Optional[Tensor] = None) -> Dict[str, Any]:
         """img [B,V,3,H,W] (or a list of V tensors [B,3,H,W]), rot [B,V,3,3].  Output: per-view ``img_feat`` /
-        ``initial_rot_feat`` and per-pair dicts shaped like the reference's two-view output."""
+        ``initial_rot_feat`` and per-pair dicts shaped like the reference's two-view output.
+
+        consensus=True adds ``out["consensus"]``: one gaze per sample from all directed pairs (``consensus.gaze_consensus``, one
+        more launch; view_weights [B,V] or None: per-view confidence, 0 = the view is missing) - ``head`` [I,B,3], ``views``
+        [I,V,B,2], ``resultant`` / ``spread`` [I,B] and ``pred_gaze`` [B,V,2], the output iteration's consensus in every view's
+        frame.  With the default nothing is added and nothing else is launched."""
         if isinstance(img, (list, tuple)):
             imgs = list(img)                       # V tensors [B,3,H,W] (already one tensor per view)
             V = len(imgs)
@@ -420,6 +425,13 @@ class MultiViewGaze(nn.Module):
                 out["pairs"][(i, j)] = pd
                 p += 1
         out["pred_gaze"] = preds[self._output_index, 0]
+        if consensus:
+            from .consensus import gaze_consensus
+            head, views, stats = gaze_consensus(preds, rot, view_weights, stats=True)
+            out["consensus"] = {"head": head, "views": views, "resultant": stats[..., 0], "spread": stats[..., 1],
+                                "pred_gaze": views[self._output_index].transpose(0, 1)}
+        elif view_weights is not None:
+            raise ValueError("forward_multiview: view_weights go with consensus=True")
         return out
 
 

@@ -1065,6 +1065,34 @@ def gaze_error_update(preds, gt, iters, dirs, batch, record, err_out=None, capac
           "gaze_error_update")
 
 
+def _consensus_shapes(preds, rot, weights, iters, views, batch):
+    dirs = views * (views - 1)
+    assert preds.dtype == torch.float32 and preds.is_contiguous() and preds.numel() == iters * dirs * batch * 2
+    assert rot.dtype == torch.float32 and rot.is_contiguous() and rot.numel() == batch * views * 9
+    assert weights is None or (weights.dtype == torch.float32 and weights.is_contiguous() and weights.numel() == batch * views)
+
+
+def gaze_consensus_fwd(preds, rot, weights, iters, views, batch, head, views_out, stats=None):
+    """head [iters][batch][3], views_out [iters][views][batch][2] (and stats [iters][batch][2]: resultant length, mean
+    disagreement in degrees) <- the consensus gaze of preds [iters][views*(views-1)][batch][2] under rot [batch][views][3][3] and
+    the per-view weights [batch][views] (None: all 1).  One launch, no sync; the definition is at mvg_gaze_consensus_fwd."""
+    _consensus_shapes(preds, rot, weights, iters, views, batch)
+    for t, n in ((head, 3 * iters * batch), (views_out, 2 * iters * views * batch), (stats, 2 * iters * batch)):
+        assert t is None or (t.dtype == torch.float32 and t.is_contiguous() and t.numel() == n)
+    check(lib().mvg_gaze_consensus_fwd(_p(preds), _p(rot), _p(weights), iters, views, batch, _p(head), _p(views_out), _p(stats), _s()),
+          "gaze_consensus_fwd")
+
+
+def gaze_consensus_bwd(dviews, preds, rot, weights, iters, views, batch, dpreds):
+    """dpreds [iters][views*(views-1)][batch][2] <- the gradient of gaze_consensus_fwd's views_out (dviews, its shape) on preds;
+    every row is written (inactive rows and degenerate items 0).  One launch, no sync."""
+    _consensus_shapes(preds, rot, weights, iters, views, batch)
+    assert dviews.dtype == torch.float32 and dviews.is_contiguous() and dviews.numel() == 2 * iters * views * batch
+    assert dpreds.dtype == torch.float32 and dpreds.is_contiguous() and dpreds.numel() == preds.numel()
+    check(lib().mvg_gaze_consensus_bwd(_p(dviews), _p(preds), _p(rot), _p(weights), iters, views, batch, _p(dpreds), _s()),
+          "gaze_consensus_bwd")
+
+
 def adam_step_segments(param, grad, exp_avg, exp_avg_sq, segments):
     """The Adam step over ``segments`` of the arenas only: (begin, end, lr, beta1, beta2, eps, weight_decay, step) records -
     element ranges sorted by begin, disjoint, aligned to 4 - each with its own hyper-parameters and step count

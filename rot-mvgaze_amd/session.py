@@ -91,6 +91,8 @@ class InferenceSession:
             check(lib().mvg_session_set_range_record(h, C.c_void_p(self._range_record.data_ptr())), "session_set_range_record")
         self.meter = None
         self._gt: Optional[Tensor] = None
+        self.consensus = None                       # bind_consensus: the static consensus outputs, or None
+        self._cons_weights: Optional[Tensor] = None
         if meter is not None:
             self.bind_meter(meter)
         self.refresh()
@@ -116,6 +118,38 @@ class InferenceSession:
                                                      meter.capacity), "session_set_error_record")
             self.meter = meter
         self.launches = int(lib().mvg_session_launches(self._h))
+
+    # ---------------------------------------------------------------- consensus gaze
+    def bind_consensus(self, weights: Optional[Tensor] = None, stats: bool = False, enable: bool = True) -> None:
+        """Every ``run`` also leaves the consensus gaze of its own ``preds`` and ``rot`` (``mvg_session_set_consensus``: one more
+        launch after the plan's last step, same four outputs, still no synchronisation) in ``session.consensus``: static tensors
+        ``{"head" [I,B,3], "views" [I,V,B,2]}`` and with ``stats=True`` ``"stats"`` [I,B,2] (resultant length, mean disagreement
+        in degrees).  weights: a static fp32 ``[B,V]`` device tensor the caller refills before each ``run`` (None: all views count
+        1).  ``enable=False`` (or ``unbind_consensus()``) detaches: the plain forward again.  Host only: the library stores four
+        pointers."""
+        if self._h is None:
+            raise RuntimeError("InferenceSession is closed")
+        if not enable:
+            check(lib().mvg_session_set_consensus(self._h, None, None, None, None), "session_set_consensus")
+            self.consensus, self._cons_weights = None, None
+        else:
+            I, V, B = self.num_iter, self.views, self.batch
+            if weights is not None and (tuple(weights.shape) != (B, V) or weights.dtype != torch.float32 or weights.device != self.device
+                                        or not weights.is_contiguous()):
+                raise ValueError(f"InferenceSession.bind_consensus: weights must be a contiguous fp32 tensor of shape {(B, V)} on {self.device}")
+            with torch.cuda.device(self.device):
+                mk = lambda *s: torch.empty(*s, dtype=torch.float32, device=self.device)
+                cons = {"head": mk(I, B, 3), "views": mk(I, V, B, 2)}
+                if stats:
+                    cons["stats"] = mk(I, B, 2)
+            check(lib().mvg_session_set_consensus(self._h, C.c_void_p(weights.data_ptr()) if weights is not None else None,
+                                                  C.c_void_p(cons["head"].data_ptr()), C.c_void_p(cons["views"].data_ptr()),
+                                                  C.c_void_p(cons["stats"].data_ptr()) if stats else None), "session_set_consensus")
+            self.consensus, self._cons_weights = cons, weights
+        self.launches = int(lib().mvg_session_launches(self._h))
+
+    def unbind_consensus(self) -> None:
+        self.bind_consensus(enable=False)
 
     # ---------------------------------------------------------------- weights
     def refresh(self) -> None:
@@ -215,6 +249,7 @@ class InferenceSession:
             self._workspace = None
             self._range_record = None
             self.meter = self._gt = None
+            self.consensus = self._cons_weights = None
 
     def __del__(self):
         try:
