@@ -6,7 +6,7 @@ import sys
 from concurrent.futures import ThreadPoolExecutor
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-SOURCES = ["api.hip", "conv_igemm.hip", "conv_bf16.hip", "conv_split.hip", "bn.hip", "pool.hip", "fusion.hip", "pair_index.cpp", "session.hip",
+SOURCES = ["api.hip", "conv_igemm.hip", "conv_bf16.hip", "conv_split.hip", "bn.hip", "pool.hip", "fusion.hip", "adam.hip", "pair_index.cpp", "session.hip",
            "session_plan.cpp"]
 LIB = os.path.join(HERE, "librotmvgaze_hip.so")
 FLAGS = ["--offload-arch=gfx950", "-O3", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-function", "-Wno-unused-value", "-Wno-unused-result",

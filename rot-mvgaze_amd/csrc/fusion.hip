@@ -439,104 +439,6 @@ __global__ __launch_bounds__(256) void axpby_kernel(const float *__restrict__ x,
   for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) y[i] = a * x[i] + (b != 0.f ? b * y[i] : 0.f);
 }
 
-// ---- Adam (torch.optim.Adam semantics: coupled L2 weight decay, bias correction) over flat arenas --
-// trainer.py:54 optim.Adam(params, lr, weight_decay=1e-6); one launch updates every parameter.
-// The update of one element, stated once for adam_kernel, adam_dev_kernel and adam_segments_kernel.
-__device__ __forceinline__ void adam1(float &p, float g, float &m, float &v, float b1, float b2, float eps, float wd,
-                                      float step_size, float bc2_sqrt) {
-  const float gr = g + wd * p;
-  m = b1 * m + (1.f - b1) * gr;
-  v = b2 * v + (1.f - b2) * gr * gr;
-  const float denom = sqrtf(v) / bc2_sqrt + eps;
-  p = p - step_size * (m / denom);
-}
-// ... and of the four elements of one 16-byte slot: three loads + a gradient load, three stores
-__device__ __forceinline__ void adam4(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
-                                      float4 *__restrict__ v, long long i, float b1, float b2, float eps, float wd,
-                                      float step_size, float bc2_sqrt) {
-  float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
-  adam1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, wd, step_size, bc2_sqrt);
-  adam1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, wd, step_size, bc2_sqrt);
-  adam1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, wd, step_size, bc2_sqrt);
-  adam1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, wd, step_size, bc2_sqrt);
-  p[i] = pp;
-  m[i] = mm;
-  v[i] = vv;
-}
-
-__global__ __launch_bounds__(256) void adam_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
-                                                   float4 *__restrict__ m, float4 *__restrict__ v, long long n4, float lr,
-                                                   float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-  const long long stride = (long long)gridDim.x * 256;
-  const float step_size = lr / bc1;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
-    adam4(p, g, m, v, i, b1, b2, eps, wd, step_size, bc2_sqrt);
-}
-
-// Adam over SEGMENTS of the arenas (parameter groups, parameters without a gradient: optim.Adam): up to
-// MVG_ADAM_MAX_SEGMENTS element ranges, each with its own hyper-parameters and bias corrections, travel BY VALUE in the
-// kernel arguments - no device table, nothing a later step could overwrite under a launch still in flight.  The grid-stride
-// index runs over the segments laid end to end (16-byte slots): a lane finds its segment by counting the prefix ends at or
-// below its index and adds that segment's offset to reach the arena slot.  Nothing outside the segments is read or written.
-struct AdamSegments {
-  long long end4[MVG_ADAM_MAX_SEGMENTS];      // prefix ends in the concatenated index space; unused entries = the total
-  long long shift4[MVG_ADAM_MAX_SEGMENTS];    // arena slot = concatenated index + shift4[segment]
-  float lr[MVG_ADAM_MAX_SEGMENTS], bc1[MVG_ADAM_MAX_SEGMENTS], b1[MVG_ADAM_MAX_SEGMENTS], b2[MVG_ADAM_MAX_SEGMENTS],
-      eps[MVG_ADAM_MAX_SEGMENTS], wd[MVG_ADAM_MAX_SEGMENTS], bc2_sqrt[MVG_ADAM_MAX_SEGMENTS];
-};
-__global__ __launch_bounds__(256) void adam_segments_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
-                                                            float4 *__restrict__ m, float4 *__restrict__ v, AdamSegments t) {
-  const long long stride = (long long)gridDim.x * 256;
-  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
-    // (lr / bc1 on the device, in float, as adam_kernel forms it: the same bits for the same hyper-parameters)
-    adam4(p, g, m, v, i + t.shift4[k], t.b1[k], t.b2[k], t.eps[k], t.wd[k], t.lr[k] / t.bc1[k], t.bc2_sqrt[k]);
-  }
-}
-
-// DECOUPLED weight decay (torch.optim.AdamW): the parameter is shrunk by f = 1 - lr * wd and the moments see the gradient alone.
-// The update of one element, stated once for adamw_kernel, adamw_dev_kernel and the decoupled segments of the _ex kernels.
-// lr in f is the plain learning rate (not lr / bc1); f is formed here, on the device, in float, by every form - host-lr forms
-// included - so all forms give the same bits for the same hyper-parameters, as they do for lr / bc1.
-// Which products are fused is WRITTEN here, not left to the compiler: q - step_size * x has two products, and contracted the
-// other way round (p * f fused, the step rounded on its own) the element would differ from adam1's at wd = 0.  The fused
-// multiply-adds are the ones the compiler forms in adam1 (m: (1 - b1) * g fused, b1 * m rounded; v: g * ((1 - b2) * g) fused,
-// b2 * v rounded; p: the step fused), q = p * f is rounded on its own, f is one fused multiply-add: with wd = 0, f = 1, q = p and
-// the element is adam1's in every bit - and every form runs these operations whatever kernel they are inlined into.
-__device__ __forceinline__ float adamw_factor(float lr, float wd) { return __fmaf_rn(-lr, wd, 1.f); }
-__device__ __forceinline__ void adamw1(float &p, float g, float &m, float &v, float b1, float b2, float eps, float f,
-                                       float step_size, float bc2_sqrt) {
-  const float q = p * f;
-  m = __fmaf_rn(1.f - b1, g, b1 * m);
-  v = __fmaf_rn(g, (1.f - b2) * g, b2 * v);
-  const float denom = sqrtf(v) / bc2_sqrt + eps;
-  p = __fmaf_rn(-step_size, m / denom, q);
-}
-__device__ __forceinline__ void adamw4(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
-                                       float4 *__restrict__ v, long long i, float b1, float b2, float eps, float f,
-                                       float step_size, float bc2_sqrt) {
-  float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
-  adamw1(pp.x, gg.x, mm.x, vv.x, b1, b2, eps, f, step_size, bc2_sqrt);
-  adamw1(pp.y, gg.y, mm.y, vv.y, b1, b2, eps, f, step_size, bc2_sqrt);
-  adamw1(pp.z, gg.z, mm.z, vv.z, b1, b2, eps, f, step_size, bc2_sqrt);
-  adamw1(pp.w, gg.w, mm.w, vv.w, b1, b2, eps, f, step_size, bc2_sqrt);
-  p[i] = pp;
-  m[i] = mm;
-  v[i] = vv;
-}
-// adam_kernel in decoupled mode
-__global__ __launch_bounds__(256) void adamw_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
-                                                    float4 *__restrict__ m, float4 *__restrict__ v, long long n4, float lr,
-                                                    float b1, float b2, float eps, float wd, float bc1, float bc2_sqrt) {
-  const long long stride = (long long)gridDim.x * 256;
-  const float step_size = lr / bc1, f = adamw_factor(lr, wd);
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
-    adamw4(p, g, m, v, i, b1, b2, eps, f, step_size, bc2_sqrt);
-}
-
 // ---- skinny linear (out_features <= 4): the Linear(512 -> 2) of the gaze head ------------------
 // fwd: one wave per row.
 __global__ __launch_bounds__(256) void skinny_fwd_kernel(const float *__restrict__ x, const float *__restrict__ w,
@@ -989,259 +891,6 @@ __global__ __launch_bounds__(256) void gaze_consensus_bwd_kernel(const float *__
       }
 }
 
-// Adam with its step counter and learning rate on the DEVICE (a captured step replays with nothing from the host):
-// adam_tick_kernel advances state = {step, bias correction 1, sqrt(bias correction 2)} (one thread), adam_dev_kernel is
-// adam_kernel reading lr from hyper[0] and the corrections from state.
-// (the advance of one state row, stated once for adam_tick_kernel and adam_tick_segments_kernel)
-__device__ __forceinline__ void adam_tick1(float *__restrict__ state, float b1, float b2) {
-  const float step = state[0] + 1.f;
-  state[0] = step;
-  state[1] = (float)(1.0 - pow((double)b1, (double)step));
-  state[2] = (float)sqrt(1.0 - pow((double)b2, (double)step));
-}
-__global__ void adam_tick_kernel(float *__restrict__ state, float b1, float b2) {
-  if (threadIdx.x != 0 || blockIdx.x != 0) return;
-  adam_tick1(state, b1, b2);
-}
-__global__ __launch_bounds__(256) void adam_dev_kernel(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
-                                                       float4 *__restrict__ v, long long n4, const float *__restrict__ lr_dev,
-                                                       const float *__restrict__ state, float b1, float b2, float eps, float wd) {
-  const long long stride = (long long)gridDim.x * 256;
-  const float step_size = lr_dev[0] / state[1], bc2_sqrt = state[2];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
-    adam4(p, g, m, v, i, b1, b2, eps, wd, step_size, bc2_sqrt);
-}
-
-// The segmented step with its learning rates and step counters on the DEVICE (a captured fine-tuning step): the segments'
-// bounds and constants travel by value as in adam_segments_kernel, but a segment's learning rate is lr_dev[lr_index] (one float
-// per parameter group, written by the host between replays) and its bias corrections are its row of state =
-// {step, 1 - beta1^step, sqrt(1 - beta2^step)}, advanced by adam_tick_segments_kernel in front of the update: lane k < count
-// advances row k with segment k's betas, every row exactly once.
-struct AdamTicks {
-  float b1[MVG_ADAM_MAX_SEGMENTS], b2[MVG_ADAM_MAX_SEGMENTS];
-  int count;
-};
-__global__ void adam_tick_segments_kernel(float *__restrict__ state, AdamTicks t) {
-  const int k = threadIdx.x;
-  if (blockIdx.x != 0 || k >= t.count || k >= MVG_ADAM_MAX_SEGMENTS) return;
-  adam_tick1(state + 3 * k, t.b1[k], t.b2[k]);
-}
-struct AdamSegmentsDev {
-  long long end4[MVG_ADAM_MAX_SEGMENTS];      // as AdamSegments
-  long long shift4[MVG_ADAM_MAX_SEGMENTS];
-  int lr_index[MVG_ADAM_MAX_SEGMENTS];        // into lr_dev
-  float b1[MVG_ADAM_MAX_SEGMENTS], b2[MVG_ADAM_MAX_SEGMENTS], eps[MVG_ADAM_MAX_SEGMENTS], wd[MVG_ADAM_MAX_SEGMENTS];
-};
-__global__ __launch_bounds__(256) void adam_segments_dev_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
-                                                                float4 *__restrict__ m, float4 *__restrict__ v,
-                                                                const float *__restrict__ lr_dev, const float *__restrict__ state,
-                                                                AdamSegmentsDev t) {
-  const long long stride = (long long)gridDim.x * 256;
-  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
-    // (lr / bc1 in float, as adam_dev_kernel forms it: the same bits for the same device scalars)
-    adam4(p, g, m, v, i + t.shift4[k], t.b1[k], t.b2[k], t.eps[k], t.wd[k], lr_dev[t.lr_index[k]] / state[3 * k + 1], state[3 * k + 2]);
-  }
-}
-
-// ---- global-norm gradient clipping and the non-finite guard of the segmented steps (optim.Adam(max_grad_norm, skip_nonfinite))
-// One read of the segments' gradients leaves clip4 = {norm, coef, skipped, skipped_total} on the device; the clipped forms of
-// the two segmented updates multiply the gradient by coef as they load it and, like the tick, return at once when skipped is
-// set - a captured replay clips and skips with nothing from the host, and the gradient arena is never rewritten.
-//
-// grad_sumsq_segments_kernel: sum of squares over the segments laid end to end (AdamSegments' addressing: nothing outside a
-// segment is read), float4 loads, grid-stride.  Accumulated in DOUBLE: the square of a float is exact there and a finite fp32
-// gradient cannot overflow the sum (3.4e38^2 * 1e9 < 1.8e308), so the sum is non-finite exactly when an element is.  Waves
-// first, then the four waves through LDS; every workgroup stores one partial - no atomics, a fixed order for a fixed grid.
-struct GradSegments {
-  long long end4[MVG_ADAM_MAX_SEGMENTS];      // as AdamSegments
-  long long shift4[MVG_ADAM_MAX_SEGMENTS];
-};
-__global__ __launch_bounds__(256) void grad_sumsq_segments_kernel(const float4 *__restrict__ g, GradSegments t,
-                                                                  double *__restrict__ partial) {
-  __shared__ double sh[4];
-  const long long stride = (long long)gridDim.x * 256;
-  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
-  double a0 = 0.0, a1 = 0.0, a2 = 0.0, a3 = 0.0;
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
-    const float4 x = g[i + t.shift4[k]];
-    a0 += (double)x.x * (double)x.x;
-    a1 += (double)x.y * (double)x.y;
-    a2 += (double)x.z * (double)x.z;
-    a3 += (double)x.w * (double)x.w;
-  }
-  const double local = wave_sum_d((a0 + a1) + (a2 + a3));
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x == 0) partial[blockIdx.x] = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-}
-
-// One workgroup merges the `count` partials of all chunk launches in a fixed order (lane l takes l, l + 256, ... in index
-// order, then waves, then the four waves) and writes the record.  coef is torch.nn.utils.clip_grad_norm_'s
-// min(1, max_norm / (norm + 1e-6)), formed in double; max_norm <= 0: no clipping (coef = 1), the guard only.  A non-finite
-// sum with the guard on: skipped = 1 and coef = 0; with it off, the coefficient torch's formula gives (NaN for a NaN norm, 0
-// for an infinite one).  skipped_total is the one field read before it is written: replays count their skips in it.
-__global__ __launch_bounds__(256) void grad_clip_finalize_kernel(const double *__restrict__ partial, int count, float max_norm,
-                                                                 int skip_nonfinite, float *__restrict__ clip4) {
-  __shared__ double sh[4];
-  double local = 0.0;
-  for (int i = threadIdx.x; i < count; i += 256) local += partial[i];
-  local = wave_sum_d(local);
-  if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = local;
-  __syncthreads();
-  if (threadIdx.x != 0) return;
-  const double sum = (sh[0] + sh[1]) + (sh[2] + sh[3]);
-  const double norm = sqrt(sum);
-  const bool finite = sum - sum == 0.0;                    // false for inf and NaN
-  float coef = 1.f;
-  if (max_norm > 0.f) {
-    const double c = (double)max_norm / (norm + 1e-6);
-    coef = (float)(c > 1.0 ? 1.0 : c);                     // (a NaN passes through, as torch.clamp(max=1) lets it)
-  }
-  const float skipped = skip_nonfinite && !finite ? 1.f : 0.f;
-  clip4[0] = (float)norm;
-  clip4[1] = skipped != 0.f ? 0.f : coef;
-  clip4[2] = skipped;
-  clip4[3] = clip4[3] + skipped;
-}
-
-// adam4 with the gradient multiplied by coef as it is loaded.  The product is rounded to fp32 on its own - never contracted
-// into adam1's wd * p fma - so a clipped step equals, bit for bit, the unclipped one on a gradient torch scaled in fp32.
-__device__ __forceinline__ float clip_mul(float g, float coef) {
-#pragma clang fp contract(off)
-  return __fmul_rn(g, coef);
-}
-__device__ __forceinline__ void adam4_clip(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
-                                           float4 *__restrict__ v, long long i, float coef, float b1, float b2, float eps, float wd,
-                                           float step_size, float bc2_sqrt) {
-  float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
-  adam1(pp.x, clip_mul(gg.x, coef), mm.x, vv.x, b1, b2, eps, wd, step_size, bc2_sqrt);
-  adam1(pp.y, clip_mul(gg.y, coef), mm.y, vv.y, b1, b2, eps, wd, step_size, bc2_sqrt);
-  adam1(pp.z, clip_mul(gg.z, coef), mm.z, vv.z, b1, b2, eps, wd, step_size, bc2_sqrt);
-  adam1(pp.w, clip_mul(gg.w, coef), mm.w, vv.w, b1, b2, eps, wd, step_size, bc2_sqrt);
-  p[i] = pp;
-  m[i] = mm;
-  v[i] = vv;
-}
-// The clipped forms: adam_segments_kernel / adam_tick_segments_kernel / adam_segments_dev_kernel reading the record first.
-__global__ __launch_bounds__(256) void adam_segments_clip_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
-                                                                 float4 *__restrict__ m, float4 *__restrict__ v,
-                                                                 const float *__restrict__ clip4, AdamSegments t) {
-  const float coef = clip4[1];
-  if (clip4[2] != 0.f) return;
-  const long long stride = (long long)gridDim.x * 256;
-  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
-    adam4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], t.wd[k], t.lr[k] / t.bc1[k], t.bc2_sqrt[k]);
-  }
-}
-__global__ void adam_tick_segments_clip_kernel(float *__restrict__ state, const float *__restrict__ clip4, AdamTicks t) {
-  const int k = threadIdx.x;
-  if (blockIdx.x != 0 || k >= t.count || k >= MVG_ADAM_MAX_SEGMENTS || clip4[2] != 0.f) return;
-  adam_tick1(state + 3 * k, t.b1[k], t.b2[k]);
-}
-__global__ __launch_bounds__(256) void adam_segments_dev_clip_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
-                                                                     float4 *__restrict__ m, float4 *__restrict__ v,
-                                                                     const float *__restrict__ lr_dev, const float *__restrict__ state,
-                                                                     const float *__restrict__ clip4, AdamSegmentsDev t) {
-  const float coef = clip4[1];
-  if (clip4[2] != 0.f) return;
-  const long long stride = (long long)gridDim.x * 256;
-  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
-    adam4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], t.wd[k], lr_dev[t.lr_index[k]] / state[3 * k + 1],
-               state[3 * k + 2]);
-  }
-}
-
-// ---- the decoupled mode of the device-lr and segmented forms (optim.AdamW, optim.Adam(decoupled_weight_decay=True))
-// adam_dev_kernel in decoupled mode: the same state row (adam_tick_kernel advances it), f from the device learning rate.
-__global__ __launch_bounds__(256) void adamw_dev_kernel(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
-                                                        float4 *__restrict__ v, long long n4, const float *__restrict__ lr_dev,
-                                                        const float *__restrict__ state, float b1, float b2, float eps, float wd) {
-  const long long stride = (long long)gridDim.x * 256;
-  const float lr = lr_dev[0];
-  const float step_size = lr / state[1], bc2_sqrt = state[2], f = adamw_factor(lr, wd);
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride)
-    adamw4(p, g, m, v, i, b1, b2, eps, f, step_size, bc2_sqrt);
-}
-// adamw4 with the gradient multiplied by coef as it is loaded (adam4_clip's rule: the product rounded on its own)
-__device__ __forceinline__ void adamw4_clip(float4 *__restrict__ p, const float4 *__restrict__ g, float4 *__restrict__ m,
-                                            float4 *__restrict__ v, long long i, float coef, float b1, float b2, float eps, float f,
-                                            float step_size, float bc2_sqrt) {
-  float4 pp = p[i], gg = g[i], mm = m[i], vv = v[i];
-  adamw1(pp.x, clip_mul(gg.x, coef), mm.x, vv.x, b1, b2, eps, f, step_size, bc2_sqrt);
-  adamw1(pp.y, clip_mul(gg.y, coef), mm.y, vv.y, b1, b2, eps, f, step_size, bc2_sqrt);
-  adamw1(pp.z, clip_mul(gg.z, coef), mm.z, vv.z, b1, b2, eps, f, step_size, bc2_sqrt);
-  adamw1(pp.w, clip_mul(gg.w, coef), mm.w, vv.w, b1, b2, eps, f, step_size, bc2_sqrt);
-  p[i] = pp;
-  m[i] = mm;
-  v[i] = vv;
-}
-// The segmented kernels with a MODE per segment, by value like wd: decoupled[k] != 0 runs adamw1 on segment k, 0 runs adam1 - one
-// launch may hold both side by side (a segment is a run of whole 16-byte slots, so a wave changes mode at a segment's border
-// only).  clip4 may be null: coef = 1 (g * 1 is g in every bit) and no guard; otherwise the record is read as the clipped
-// kernels read it.  The coupled segments run adam4_clip as adam_segments_clip_kernel does.
-struct AdamModes {
-  int decoupled[MVG_ADAM_MAX_SEGMENTS];
-};
-__global__ __launch_bounds__(256) void adam_segments_ex_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
-                                                               float4 *__restrict__ m, float4 *__restrict__ v,
-                                                               const float *__restrict__ clip4, AdamSegments t, AdamModes md) {
-  float coef = 1.f;
-  if (clip4) {
-    coef = clip4[1];
-    if (clip4[2] != 0.f) return;
-  }
-  const long long stride = (long long)gridDim.x * 256;
-  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
-    if (md.decoupled[k])
-      adamw4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], adamw_factor(t.lr[k], t.wd[k]), t.lr[k] / t.bc1[k],
-                  t.bc2_sqrt[k]);
-    else
-      adam4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], t.wd[k], t.lr[k] / t.bc1[k], t.bc2_sqrt[k]);
-  }
-}
-__global__ __launch_bounds__(256) void adam_segments_dev_ex_kernel(float4 *__restrict__ p, const float4 *__restrict__ g,
-                                                                   float4 *__restrict__ m, float4 *__restrict__ v,
-                                                                   const float *__restrict__ lr_dev, const float *__restrict__ state,
-                                                                   const float *__restrict__ clip4, AdamSegmentsDev t, AdamModes md) {
-  float coef = 1.f;
-  if (clip4) {
-    coef = clip4[1];
-    if (clip4[2] != 0.f) return;
-  }
-  const long long stride = (long long)gridDim.x * 256;
-  const long long total = t.end4[MVG_ADAM_MAX_SEGMENTS - 1];
-  for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < total; i += stride) {
-    int k = 0;
-#pragma unroll
-    for (int j = 0; j < MVG_ADAM_MAX_SEGMENTS - 1; ++j) k += i >= t.end4[j];
-    const float lr = lr_dev[t.lr_index[k]];
-    if (md.decoupled[k])
-      adamw4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], adamw_factor(lr, t.wd[k]), lr / state[3 * k + 1],
-                  state[3 * k + 2]);
-    else
-      adam4_clip(p, g, m, v, i + t.shift4[k], coef, t.b1[k], t.b2[k], t.eps[k], t.wd[k], lr / state[3 * k + 1], state[3 * k + 2]);
-  }
-}
-
 }  // namespace mvg
 
 using namespace mvg;
@@ -1378,206 +1027,6 @@ int mvg_axpby(const float *x, float *y, float a, float b, int64_t n, void *strea
   return check_launch("axpby");
 }
 
-int mvg_adam_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float beta1,
-                  float beta2, float eps, float weight_decay, int step, void *stream) {
-  MVG_REQUIRE(n % 4 == 0 && step >= 1, "adam: n %% 4 != 0 or step < 1");
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * (double)n);
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  long long blocks = (n / 4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(adam_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
-                     (float4 *)exp_avg, (float4 *)exp_avg_sq, (long long)(n / 4), lr, beta1, beta2, eps, weight_decay,
-                     (float)bc1, (float)sqrt(bc2));
-  return check_launch("adam_step");
-}
-
-// mvg_adam_step in decoupled mode: the same checks, corrections and grid, adamw_kernel
-int mvg_adamw_step(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, float lr, float beta1,
-                   float beta2, float eps, float weight_decay, int step, void *stream) {
-  MVG_REQUIRE(n % 4 == 0 && step >= 1, "adamw: n %% 4 != 0 or step < 1");
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * (double)n);
-  const double bc1 = 1.0 - pow((double)beta1, (double)step);
-  const double bc2 = 1.0 - pow((double)beta2, (double)step);
-  long long blocks = (n / 4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(adamw_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
-                     (float4 *)exp_avg, (float4 *)exp_avg_sq, (long long)(n / 4), lr, beta1, beta2, eps, weight_decay,
-                     (float)bc1, (float)sqrt(bc2));
-  return check_launch("adamw_step");
-}
-
-// The mode rule of the _ex entry points, checked with the segment rules before the first launch.
-static int check_modes(const char *what, const int32_t *host_decoupled, int n_segments) {
-  MVG_REQUIRE(host_decoupled, "%s: null host_decoupled", what);
-  for (int i = 0; i < n_segments; ++i)
-    MVG_REQUIRE(host_decoupled[i] == 0 || host_decoupled[i] == 1, "%s: segment %d has mode %d (0: coupled, 1: decoupled)", what, i,
-                (int)host_decoupled[i]);
-  return 0;
-}
-
-// The segment rules of every segmented entry point, checked before its first launch: aligned to 4, inside [0, n), non-empty,
-// sorted by begin, disjoint.  *active receives the elements the segments hold.
-static int check_segments(const char *what, int64_t n, const int64_t *host_bounds, int n_segments, double *active) {
-  *active = 0.0;
-  for (int i = 0; i < n_segments; ++i) {
-    const int64_t b = host_bounds[2 * i], e = host_bounds[2 * i + 1];
-    MVG_REQUIRE(b % 4 == 0 && e % 4 == 0, "%s: segment %d [%lld, %lld) is not aligned to 4 elements", what, i, (long long)b, (long long)e);
-    MVG_REQUIRE(b >= 0 && e <= n, "%s: segment %d [%lld, %lld) is outside the arena of %lld elements", what, i, (long long)b, (long long)e,
-                (long long)n);
-    MVG_REQUIRE(b < e, "%s: segment %d [%lld, %lld) is empty or reversed", what, i, (long long)b, (long long)e);
-    if (i > 0) {
-      MVG_REQUIRE(b >= host_bounds[2 * i - 2], "%s: segment %d begins before segment %d (unsorted)", what, i, i - 1);
-      MVG_REQUIRE(b >= host_bounds[2 * i - 1], "%s: segment %d overlaps segment %d", what, i, i - 1);
-    }
-    *active += (double)(e - b);
-  }
-  return 0;
-}
-
-// mvg_adam_step_segments (clip4 == nullptr: its launches as they always were), mvg_adam_step_segments_clip and, with ex set,
-// mvg_adam_step_segments_ex (a mode per segment in host_decoupled, clip4 nullable: adam_segments_ex_kernel)
-static int adam_step_segments_launch(const char *what, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                                     const int64_t *host_bounds, const float *host_hyper, const int32_t *host_steps, int n_segments,
-                                     const float *clip4, void *stream, bool ex = false, const int32_t *host_decoupled = nullptr) {
-  MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && host_bounds && host_hyper && host_steps && n % 4 == 0 && n_segments >= 1,
-              "%s: null argument, n %% 4 != 0 or no segment", what);
-  // every segment is checked before the first launch: a rejected call has updated nothing
-  double active = 0.0;
-  if (int rc = check_segments(what, n, host_bounds, n_segments, &active)) return rc;
-  for (int i = 0; i < n_segments; ++i)
-    MVG_REQUIRE(host_steps[i] >= 1, "%s: segment %d has step %d < 1", what, i, (int)host_steps[i]);
-  if (ex)
-    if (int rc = check_modes(what, host_decoupled, n_segments)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * active);
-  for (int s0 = 0; s0 < n_segments; s0 += MVG_ADAM_MAX_SEGMENTS) {
-    const int cnt = n_segments - s0 < MVG_ADAM_MAX_SEGMENTS ? n_segments - s0 : MVG_ADAM_MAX_SEGMENTS;
-    AdamSegments t;
-    AdamModes md;
-    memset(&t, 0, sizeof(t));
-    memset(&md, 0, sizeof(md));
-    long long total = 0;
-    for (int k = 0; k < MVG_ADAM_MAX_SEGMENTS; ++k) {
-      const int i = s0 + (k < cnt ? k : cnt - 1);          // (unused entries repeat the last segment: never selected)
-      const float *h = host_hyper + 5 * i;
-      if (k < cnt) {
-        t.shift4[k] = host_bounds[2 * i] / 4 - total;
-        total += (host_bounds[2 * i + 1] - host_bounds[2 * i]) / 4;
-      } else {
-        t.shift4[k] = t.shift4[cnt - 1];
-      }
-      t.end4[k] = total;
-      t.lr[k] = h[0];
-      t.b1[k] = h[1];
-      t.b2[k] = h[2];
-      t.eps[k] = h[3];
-      t.wd[k] = h[4];
-      t.bc1[k] = (float)(1.0 - pow((double)h[1], (double)host_steps[i]));
-      t.bc2_sqrt[k] = (float)sqrt(1.0 - pow((double)h[2], (double)host_steps[i]));
-      if (ex) md.decoupled[k] = host_decoupled[i];
-    }
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (ex)
-      hipLaunchKernelGGL(adam_segments_ex_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
-                         (float4 *)exp_avg, (float4 *)exp_avg_sq, clip4, t, md);
-    else if (clip4)
-      hipLaunchKernelGGL(adam_segments_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
-                         (float4 *)exp_avg, (float4 *)exp_avg_sq, clip4, t);
-    else
-      hipLaunchKernelGGL(adam_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
-                         (float4 *)exp_avg, (float4 *)exp_avg_sq, t);
-    if (check_launch(what)) return 1;
-  }
-  return 0;
-}
-
-int mvg_adam_step_segments(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
-                           const float *host_hyper, const int32_t *host_steps, int n_segments, void *stream) {
-  return adam_step_segments_launch("adam_step_segments", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper, host_steps,
-                                   n_segments, nullptr, stream);
-}
-
-int mvg_adam_step_segments_clip(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
-                                const float *host_hyper, const int32_t *host_steps, int n_segments, const float *clip4_dev, void *stream) {
-  MVG_REQUIRE(clip4_dev, "adam_step_segments_clip: null clip4 record");
-  return adam_step_segments_launch("adam_step_segments_clip", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper, host_steps,
-                                   n_segments, clip4_dev, stream);
-}
-
-int mvg_adam_step_segments_ex(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
-                              const float *host_hyper, const int32_t *host_steps, const int32_t *host_decoupled, int n_segments,
-                              const float *clip4_dev, void *stream) {
-  return adam_step_segments_launch("adam_step_segments_ex", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper, host_steps,
-                                   n_segments, clip4_dev, stream, true, host_decoupled);
-}
-
-// The grid of one partial-sum launch over `total4` 16-byte slots: eight workgroups per CU the planners may use, at most.
-static long long grad_norm_grid(long long total4, int cus) {
-  const long long cap = 8LL * cus, blocks = (total4 + 255) / 256;
-  return blocks < cap ? (blocks < 1 ? 1 : blocks) : cap;
-}
-
-int64_t mvg_grad_norm_workspace_bytes(int n_segments) {
-  if (n_segments < 1) {
-    set_error("grad_norm_workspace_bytes: no segment");
-    return -1;
-  }
-  int cus = mvg_device_cus();                              // (every CU: what compute_cus() can at most answer)
-  if (cus <= 0) cus = 256;
-  const int64_t chunks = (n_segments + MVG_ADAM_MAX_SEGMENTS - 1) / MVG_ADAM_MAX_SEGMENTS;
-  return chunks * 8 * cus * (int64_t)sizeof(double);
-}
-
-int mvg_grad_norm_segments(const float *grad, int64_t n, const int64_t *host_bounds, int n_segments, float max_norm, int skip_nonfinite,
-                           void *ws, int64_t ws_bytes, float *clip4_dev, void *stream) {
-  MVG_REQUIRE(grad && host_bounds && ws && clip4_dev, "grad_norm_segments: null argument (grad, host_bounds, ws or clip4)");
-  MVG_REQUIRE(n % 4 == 0 && n_segments >= 1, "grad_norm_segments: n %% 4 != 0 or no segment");
-  MVG_REQUIRE(max_norm == max_norm, "grad_norm_segments: max_norm is NaN");
-  double active = 0.0;
-  if (int rc = check_segments("grad_norm_segments", n, host_bounds, n_segments, &active)) return rc;
-  // the grids of all chunk launches, before the first of them: their partials lie end to end in the workspace
-  const int cus = compute_cus();
-  long long partials = 0;
-  for (int s0 = 0; s0 < n_segments; s0 += MVG_ADAM_MAX_SEGMENTS) {
-    long long total = 0;
-    for (int i = s0; i < n_segments && i < s0 + MVG_ADAM_MAX_SEGMENTS; ++i) total += (host_bounds[2 * i + 1] - host_bounds[2 * i]) / 4;
-    partials += grad_norm_grid(total, cus);
-  }
-  MVG_REQUIRE(ws_bytes >= partials * (long long)sizeof(double) && partials < (1LL << 30),
-              "grad_norm_segments: workspace of %lld bytes is too small for %lld partial sums (mvg_grad_norm_workspace_bytes)",
-              (long long)ws_bytes, partials);
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(MVG_K_ELEMENTWISE, st, 2.0 * active, 4.0 * active);
-  long long at = 0;
-  for (int s0 = 0; s0 < n_segments; s0 += MVG_ADAM_MAX_SEGMENTS) {
-    const int cnt = n_segments - s0 < MVG_ADAM_MAX_SEGMENTS ? n_segments - s0 : MVG_ADAM_MAX_SEGMENTS;
-    GradSegments t;
-    memset(&t, 0, sizeof(t));
-    long long total = 0;
-    for (int k = 0; k < MVG_ADAM_MAX_SEGMENTS; ++k) {
-      const int i = s0 + k;
-      if (k < cnt) {
-        t.shift4[k] = host_bounds[2 * i] / 4 - total;
-        total += (host_bounds[2 * i + 1] - host_bounds[2 * i]) / 4;
-      } else {
-        t.shift4[k] = t.shift4[cnt - 1];                  // (unused entries repeat the last segment: never selected)
-      }
-      t.end4[k] = total;
-    }
-    const long long blocks = grad_norm_grid(total, cus);
-    hipLaunchKernelGGL(grad_sumsq_segments_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (const float4 *)grad, t, (double *)ws + at);
-    if (check_launch("grad_norm_segments")) return 1;
-    at += blocks;
-  }
-  hipLaunchKernelGGL(grad_clip_finalize_kernel, dim3(1), dim3(256), 0, st, (const double *)ws, (int)partials, max_norm,
-                     skip_nonfinite != 0, clip4_dev);
-  return check_launch("grad_clip_finalize");
-}
-
 int mvg_absmax_multi(const float *const *host_ptrs, const int64_t *host_counts, float *const *host_out_slots, int n, void *stream) {
   MVG_REQUIRE(host_ptrs && host_counts && host_out_slots && n >= 1 && n <= 8, "absmax_multi: 1..8 tensors");
   AbsMaxItems it;
@@ -1697,125 +1146,6 @@ int mvg_gaze_consensus_bwd(const float *dviews, const float *preds, const float 
   hipLaunchKernelGGL(gaze_consensus_bwd_kernel, dim3((unsigned)ceil_div((int64_t)iters * batch, 256)), dim3(256), 0, st, dviews, preds, rot,
                      weights, iters, views, batch, dpreds);
   return check_launch("gaze_consensus_bwd");
-}
-
-int mvg_adam_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev, float *state3,
-                      float beta1, float beta2, float eps, float weight_decay, void *stream) {
-  MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && lr_dev && state3 && n % 4 == 0, "adam_step_dev: null argument or n %% 4 != 0");
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * (double)n);
-  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st, state3, beta1, beta2);
-  if (check_launch("adam_tick")) return 1;
-  long long blocks = (n / 4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(adam_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad, (float4 *)exp_avg,
-                     (float4 *)exp_avg_sq, (long long)(n / 4), lr_dev, state3, beta1, beta2, eps, weight_decay);
-  return check_launch("adam_step_dev");
-}
-
-// mvg_adam_step_dev in decoupled mode: the same tick on the same state3, adamw_dev_kernel
-int mvg_adamw_step_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const float *lr_dev, float *state3,
-                       float beta1, float beta2, float eps, float weight_decay, void *stream) {
-  MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && lr_dev && state3 && n % 4 == 0, "adamw_step_dev: null argument or n %% 4 != 0");
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * (double)n);
-  hipLaunchKernelGGL(adam_tick_kernel, dim3(1), dim3(64), 0, st, state3, beta1, beta2);
-  if (check_launch("adam_tick")) return 1;
-  long long blocks = (n / 4 + 255) / 256;
-  if (blocks > 8192) blocks = 8192;
-  hipLaunchKernelGGL(adamw_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad, (float4 *)exp_avg,
-                     (float4 *)exp_avg_sq, (long long)(n / 4), lr_dev, state3, beta1, beta2, eps, weight_decay);
-  return check_launch("adamw_step_dev");
-}
-
-// mvg_adam_step_segments_dev (clip4 == nullptr: its launches as they always were), mvg_adam_step_segments_dev_clip and, with ex
-// set, mvg_adam_step_segments_dev_ex (a mode per segment, clip4 nullable: the same ticks, adam_segments_dev_ex_kernel)
-static int adam_step_segments_dev_launch(const char *what, float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n,
-                                         const int64_t *host_bounds, const float *host_hyper, const int32_t *host_lr_index, int n_segments,
-                                         const float *lr_dev, int n_lr, float *state3_dev, const float *clip4, void *stream,
-                                         bool ex = false, const int32_t *host_decoupled = nullptr) {
-  MVG_REQUIRE(param && grad && exp_avg && exp_avg_sq && host_bounds && host_hyper && host_lr_index && lr_dev && state3_dev,
-              "%s: null argument", what);
-  MVG_REQUIRE(n % 4 == 0 && n_segments >= 1 && n_lr >= 1, "%s: n %% 4 != 0, no segment or no learning rate", what);
-  // every segment is checked before the first launch (the tick included): a rejected call has advanced and updated nothing
-  double active = 0.0;
-  if (int rc = check_segments(what, n, host_bounds, n_segments, &active)) return rc;
-  for (int i = 0; i < n_segments; ++i)
-    MVG_REQUIRE(host_lr_index[i] >= 0 && host_lr_index[i] < n_lr, "%s: segment %d has lr index %d outside [0, %d)", what, i,
-                (int)host_lr_index[i], n_lr);
-  if (ex)
-    if (int rc = check_modes(what, host_decoupled, n_segments)) return rc;
-  hipStream_t st = (hipStream_t)stream;
-  ProfScope ps(MVG_K_ELEMENTWISE, st, 0.0, 28.0 * active);
-  for (int s0 = 0; s0 < n_segments; s0 += MVG_ADAM_MAX_SEGMENTS) {
-    const int cnt = n_segments - s0 < MVG_ADAM_MAX_SEGMENTS ? n_segments - s0 : MVG_ADAM_MAX_SEGMENTS;
-    AdamTicks ticks;
-    AdamSegmentsDev t;
-    AdamModes md;
-    memset(&ticks, 0, sizeof(ticks));
-    memset(&t, 0, sizeof(t));
-    memset(&md, 0, sizeof(md));
-    ticks.count = cnt;
-    long long total = 0;
-    for (int k = 0; k < MVG_ADAM_MAX_SEGMENTS; ++k) {
-      const int i = s0 + (k < cnt ? k : cnt - 1);          // (unused entries repeat the last segment: never selected)
-      const float *h = host_hyper + 4 * i;
-      if (k < cnt) {
-        t.shift4[k] = host_bounds[2 * i] / 4 - total;
-        total += (host_bounds[2 * i + 1] - host_bounds[2 * i]) / 4;
-      } else {
-        t.shift4[k] = t.shift4[cnt - 1];
-      }
-      t.end4[k] = total;
-      t.lr_index[k] = host_lr_index[i];
-      ticks.b1[k] = t.b1[k] = h[0];
-      ticks.b2[k] = t.b2[k] = h[1];
-      t.eps[k] = h[2];
-      t.wd[k] = h[3];
-      if (ex) md.decoupled[k] = host_decoupled[i];
-    }
-    float *rows = state3_dev + 3 * (size_t)s0;             // this launch's rows of the table
-    if (clip4)
-      hipLaunchKernelGGL(adam_tick_segments_clip_kernel, dim3(1), dim3(64), 0, st, rows, clip4, ticks);
-    else
-      hipLaunchKernelGGL(adam_tick_segments_kernel, dim3(1), dim3(64), 0, st, rows, ticks);
-    if (check_launch("adam_tick_segments")) return 1;
-    long long blocks = (total + 255) / 256;
-    if (blocks > 8192) blocks = 8192;
-    if (ex)
-      hipLaunchKernelGGL(adam_segments_dev_ex_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
-                         (float4 *)exp_avg, (float4 *)exp_avg_sq, lr_dev, (const float *)rows, clip4, t, md);
-    else if (clip4)
-      hipLaunchKernelGGL(adam_segments_dev_clip_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
-                         (float4 *)exp_avg, (float4 *)exp_avg_sq, lr_dev, (const float *)rows, clip4, t);
-    else
-      hipLaunchKernelGGL(adam_segments_dev_kernel, dim3((unsigned)blocks), dim3(256), 0, st, (float4 *)param, (const float4 *)grad,
-                         (float4 *)exp_avg, (float4 *)exp_avg_sq, lr_dev, (const float *)rows, t);
-    if (check_launch(what)) return 1;
-  }
-  return 0;
-}
-
-int mvg_adam_step_segments_dev(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
-                               const float *host_hyper, const int32_t *host_lr_index, int n_segments, const float *lr_dev, int n_lr,
-                               float *state3_dev, void *stream) {
-  return adam_step_segments_dev_launch("adam_step_segments_dev", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper, host_lr_index,
-                                       n_segments, lr_dev, n_lr, state3_dev, nullptr, stream);
-}
-
-int mvg_adam_step_segments_dev_clip(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
-                                    const float *host_hyper, const int32_t *host_lr_index, int n_segments, const float *lr_dev, int n_lr,
-                                    float *state3_dev, const float *clip4_dev, void *stream) {
-  MVG_REQUIRE(clip4_dev, "adam_step_segments_dev_clip: null clip4 record");
-  return adam_step_segments_dev_launch("adam_step_segments_dev_clip", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper,
-                                       host_lr_index, n_segments, lr_dev, n_lr, state3_dev, clip4_dev, stream);
-}
-
-int mvg_adam_step_segments_dev_ex(float *param, const float *grad, float *exp_avg, float *exp_avg_sq, int64_t n, const int64_t *host_bounds,
-                                  const float *host_hyper, const int32_t *host_lr_index, const int32_t *host_decoupled, int n_segments,
-                                  const float *lr_dev, int n_lr, float *state3_dev, const float *clip4_dev, void *stream) {
-  return adam_step_segments_dev_launch("adam_step_segments_dev_ex", param, grad, exp_avg, exp_avg_sq, n, host_bounds, host_hyper,
-                                       host_lr_index, n_segments, lr_dev, n_lr, state3_dev, clip4_dev, stream, true, host_decoupled);
 }
 
 int mvg_linear_skinny_fwd(const float *x, const float *w, const float *bias, float *y, int rows, int k, int nout,

@@ -970,13 +970,17 @@ def linear_skinny_bwd(dy, x, w, mask, dx, dw, db, rows, k, nout, accumulate=Fals
                                       int(accumulate), _p(dx_absmax), _s()), "linear_skinny_bwd")
 
 
-def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step):
-    check(lib().mvg_adam_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, beta1, beta2, eps,
-                              weight_decay, step, _s()), "adam_step")
+def _adam_call(name, param, grad, exp_avg, exp_avg_sq, *args):
+    """mvg_<name> on the four arenas, ``args`` between their element count and the stream."""
+    check(getattr(lib(), "mvg_" + name)(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), *args, _s()), name)
     # the kernel wrote the parameters (and the moments) through raw pointers: tell autograd's version counters, which
     # the views of the arena share (saved-tensor checks, and the inference path's cache of split weights, rely on them)
     for t in (param, exp_avg, exp_avg_sq):
         torch.autograd.graph.increment_version(t)
+
+
+def adam_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step):
+    _adam_call("adam_step", param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step)
 
 
 def gaze_angular_loss(pred, gt, n, row_weight, loss, accumulate=False, dpred=None, theta=None):
@@ -1093,34 +1097,6 @@ def gaze_consensus_bwd(dviews, preds, rot, weights, iters, views, batch, dpreds)
           "gaze_consensus_bwd")
 
 
-def adam_step_segments(param, grad, exp_avg, exp_avg_sq, segments):
-    """The Adam step over ``segments`` of the arenas only: (begin, end, lr, beta1, beta2, eps, weight_decay, step) records -
-    element ranges sorted by begin, disjoint, aligned to 4 - each with its own hyper-parameters and step count
-    (mvg_adam_step_segments: MVG_ADAM_MAX_SEGMENTS per launch, by value).  Nothing outside the segments is touched."""
-    n = len(segments)
-    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
-    hyper = (C.c_float * (5 * n))(*[float(v) for s in segments for v in s[2:7]])
-    steps = (C.c_int32 * n)(*[int(s[7]) for s in segments])
-    check(lib().mvg_adam_step_segments(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, steps, n, _s()),
-          "adam_step_segments")
-
-
-def adam_step_segments_dev(param, grad, exp_avg, exp_avg_sq, segments, lr_dev, state3):
-    """``adam_step_segments`` with the learning rates and step counters on the device: (begin, end, lr_index, beta1, beta2, eps,
-    weight_decay) records, ``lr_dev`` one float per parameter group, ``state3`` one row {step, 1 - beta1^step,
-    sqrt(1 - beta2^step)} per segment, advanced on the device in front of the update (mvg_adam_step_segments_dev)."""
-    n = len(segments)
-    if state3 is not None and (state3.dim() != 2 or tuple(state3.shape) != (n, 3) or not state3.is_contiguous()):
-        raise ValueError(f"adam_step_segments_dev: state3 must be a contiguous [{n}, 3] table, one row per segment")
-    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
-    index = (C.c_int32 * n)(*[int(s[2]) for s in segments])
-    hyper = (C.c_float * (4 * n))(*[float(v) for s in segments for v in s[3:7]])
-    check(lib().mvg_adam_step_segments_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, index, n,
-                                           _p(lr_dev), 0 if lr_dev is None else lr_dev.numel(), _p(state3), _s()), "adam_step_segments_dev")
-    for t in (param, exp_avg, exp_avg_sq):
-        torch.autograd.graph.increment_version(t)
-
-
 _grad_norm_ws = {}    # device index -> the uint8 workspace of grad_norm_segments (partial sums; uses are ordered by the stream)
 
 
@@ -1162,98 +1138,87 @@ def grad_norm_segments(grad, bounds, max_norm, skip_nonfinite, clip4, ws=None):
                                        _s()), "grad_norm_segments")
 
 
+def _segment_tables(what, segments, dev=False, state3=None, ex=False):
+    """The host tables of a segmented step from its records, in the order the entry points take them: bounds, hyper, the steps
+    (host records: begin, end, lr, beta1, beta2, eps, weight_decay, step) or the lr indices (``dev`` records: begin, end, lr_index,
+    beta1, beta2, eps, weight_decay; ``state3`` must hold one row per record), the modes (``ex``: one more item per record, 0 / False
+    coupled or 1 / True decoupled - anything else is refused here, before any launch, as the library refuses it) and the count."""
+    n, at = len(segments), 7 if dev else 8
+    modes = []
+    for i, s in enumerate(segments if ex else ()):
+        if len(s) != at + 1 or isinstance(s[at], float) or s[at] not in (0, 1):
+            raise ValueError(f"{what}: segment {i} needs {at + 1} items, the last its mode 0 (coupled) or 1 (decoupled): {s!r}")
+        modes.append(int(s[at]))
+    if dev and state3 is not None and (state3.dim() != 2 or tuple(state3.shape) != (n, 3) or not state3.is_contiguous()):
+        raise ValueError(f"{what}: state3 must be a contiguous [{n}, 3] table, one row per segment")
+    first = 3 if dev else 2                                 # hyper: items first .. 6 of a record
+    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
+    hyper = (C.c_float * ((7 - first) * n))(*[float(v) for s in segments for v in s[first:7]])
+    ints = (C.c_int32 * n)(*[int(s[2 if dev else 7]) for s in segments])
+    return [bounds, hyper, ints] + ([(C.c_int32 * n)(*modes)] if ex else []) + [n]
+
+
+def _lr_table(lr_dev):
+    return _p(lr_dev), 0 if lr_dev is None else lr_dev.numel()
+
+
+def adam_step_segments(param, grad, exp_avg, exp_avg_sq, segments):
+    """The Adam step over ``segments`` of the arenas only: (begin, end, lr, beta1, beta2, eps, weight_decay, step) records -
+    element ranges sorted by begin, disjoint, aligned to 4 - each with its own hyper-parameters and step count
+    (mvg_adam_step_segments: MVG_ADAM_MAX_SEGMENTS per launch, by value).  Nothing outside the segments is touched."""
+    _adam_call("adam_step_segments", param, grad, exp_avg, exp_avg_sq, *_segment_tables("adam_step_segments", segments))
+
+
+def adam_step_segments_dev(param, grad, exp_avg, exp_avg_sq, segments, lr_dev, state3):
+    """``adam_step_segments`` with the learning rates and step counters on the device: (begin, end, lr_index, beta1, beta2, eps,
+    weight_decay) records, ``lr_dev`` one float per parameter group, ``state3`` one row {step, 1 - beta1^step,
+    sqrt(1 - beta2^step)} per segment, advanced on the device in front of the update (mvg_adam_step_segments_dev)."""
+    _adam_call("adam_step_segments_dev", param, grad, exp_avg, exp_avg_sq,
+               *_segment_tables("adam_step_segments_dev", segments, True, state3), *_lr_table(lr_dev), _p(state3))
+
+
 def adam_step_segments_clip(param, grad, exp_avg, exp_avg_sq, segments, clip4):
     """``adam_step_segments`` with the gradient multiplied by clip4's coefficient as it is loaded, and nothing touched when
     clip4's skipped flag is set (mvg_adam_step_segments_clip; clip4 as grad_norm_segments left it)."""
-    n = len(segments)
-    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
-    hyper = (C.c_float * (5 * n))(*[float(v) for s in segments for v in s[2:7]])
-    steps = (C.c_int32 * n)(*[int(s[7]) for s in segments])
-    check(lib().mvg_adam_step_segments_clip(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, steps, n,
-                                            _p(clip4), _s()), "adam_step_segments_clip")
-    for t in (param, exp_avg, exp_avg_sq):
-        torch.autograd.graph.increment_version(t)
+    _adam_call("adam_step_segments_clip", param, grad, exp_avg, exp_avg_sq, *_segment_tables("adam_step_segments_clip", segments),
+               _p(clip4))
 
 
 def adam_step_segments_dev_clip(param, grad, exp_avg, exp_avg_sq, segments, lr_dev, state3, clip4):
     """``adam_step_segments_dev`` reading clip4: the clipped update, and neither tick nor update when its skipped flag is set
     (mvg_adam_step_segments_dev_clip)."""
-    n = len(segments)
-    if state3 is not None and (state3.dim() != 2 or tuple(state3.shape) != (n, 3) or not state3.is_contiguous()):
-        raise ValueError(f"adam_step_segments_dev_clip: state3 must be a contiguous [{n}, 3] table, one row per segment")
-    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
-    index = (C.c_int32 * n)(*[int(s[2]) for s in segments])
-    hyper = (C.c_float * (4 * n))(*[float(v) for s in segments for v in s[3:7]])
-    check(lib().mvg_adam_step_segments_dev_clip(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, index, n,
-                                                _p(lr_dev), 0 if lr_dev is None else lr_dev.numel(), _p(state3), _p(clip4), _s()),
-          "adam_step_segments_dev_clip")
-    for t in (param, exp_avg, exp_avg_sq):
-        torch.autograd.graph.increment_version(t)
+    _adam_call("adam_step_segments_dev_clip", param, grad, exp_avg, exp_avg_sq,
+               *_segment_tables("adam_step_segments_dev_clip", segments, True, state3), *_lr_table(lr_dev), _p(state3), _p(clip4))
 
 
 def adam_step_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, state3, beta1, beta2, eps, weight_decay):
-    check(lib().mvg_adam_step_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(lr_dev), _p(state3), beta1, beta2, eps,
-                                  weight_decay, _s()), "adam_step_dev")
-    for t in (param, exp_avg, exp_avg_sq):
-        torch.autograd.graph.increment_version(t)
+    _adam_call("adam_step_dev", param, grad, exp_avg, exp_avg_sq, _p(lr_dev), _p(state3), beta1, beta2, eps, weight_decay)
 
 
 # ---- decoupled weight decay (torch.optim.AdamW): p shrunk by 1 - lr * weight_decay, the moments from the gradient alone
 def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step):
     """``adam_step`` in decoupled mode (mvg_adamw_step)."""
-    check(lib().mvg_adamw_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, beta1, beta2, eps,
-                               weight_decay, step, _s()), "adamw_step")
+    _adam_call("adamw_step", param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step)
 
 
 def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, lr_dev, state3, beta1, beta2, eps, weight_decay):
     """``adam_step_dev`` in decoupled mode: the same tick on the same state3 (mvg_adamw_step_dev)."""
-    check(lib().mvg_adamw_step_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(lr_dev), _p(state3), beta1, beta2, eps,
-                                   weight_decay, _s()), "adamw_step_dev")
-    for t in (param, exp_avg, exp_avg_sq):
-        torch.autograd.graph.increment_version(t)
-
-
-def _segment_modes(what, segments, at):
-    """The int32 modes of the _ex wrappers from item ``at`` of each record: 0 (False) coupled, 1 (True) decoupled; anything else is
-    refused here, before any launch (the library refuses it as well)."""
-    modes = []
-    for i, s in enumerate(segments):
-        if len(s) != at + 1 or isinstance(s[at], float) or s[at] not in (0, 1):
-            raise ValueError(f"{what}: segment {i} needs {at + 1} items, the last its mode 0 (coupled) or 1 (decoupled): {s!r}")
-        modes.append(int(s[at]))
-    return (C.c_int32 * len(segments))(*modes)
+    _adam_call("adamw_step_dev", param, grad, exp_avg, exp_avg_sq, _p(lr_dev), _p(state3), beta1, beta2, eps, weight_decay)
 
 
 def adam_step_segments_ex(param, grad, exp_avg, exp_avg_sq, segments, clip4=None):
     """``adam_step_segments`` with a mode per segment: (begin, end, lr, beta1, beta2, eps, weight_decay, step, decoupled) records,
     coupled and decoupled ones side by side in one launch.  clip4 None: no clipping, no guard; otherwise as
     ``adam_step_segments_clip`` (mvg_adam_step_segments_ex)."""
-    n = len(segments)
-    modes = _segment_modes("adam_step_segments_ex", segments, 8)
-    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
-    hyper = (C.c_float * (5 * n))(*[float(v) for s in segments for v in s[2:7]])
-    steps = (C.c_int32 * n)(*[int(s[7]) for s in segments])
-    check(lib().mvg_adam_step_segments_ex(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, steps, modes, n,
-                                          _p(clip4), _s()), "adam_step_segments_ex")
-    for t in (param, exp_avg, exp_avg_sq):
-        torch.autograd.graph.increment_version(t)
+    _adam_call("adam_step_segments_ex", param, grad, exp_avg, exp_avg_sq,
+               *_segment_tables("adam_step_segments_ex", segments, ex=True), _p(clip4))
 
 
 def adam_step_segments_dev_ex(param, grad, exp_avg, exp_avg_sq, segments, lr_dev, state3, clip4=None):
     """``adam_step_segments_dev`` with a mode per segment: (begin, end, lr_index, beta1, beta2, eps, weight_decay, decoupled)
     records.  clip4 None: no clipping, no guard; otherwise as ``adam_step_segments_dev_clip`` (mvg_adam_step_segments_dev_ex)."""
-    n = len(segments)
-    modes = _segment_modes("adam_step_segments_dev_ex", segments, 7)
-    if state3 is not None and (state3.dim() != 2 or tuple(state3.shape) != (n, 3) or not state3.is_contiguous()):
-        raise ValueError(f"adam_step_segments_dev_ex: state3 must be a contiguous [{n}, 3] table, one row per segment")
-    bounds = (C.c_int64 * (2 * n))(*[int(v) for s in segments for v in s[0:2]])
-    index = (C.c_int32 * n)(*[int(s[2]) for s in segments])
-    hyper = (C.c_float * (4 * n))(*[float(v) for s in segments for v in s[3:7]])
-    check(lib().mvg_adam_step_segments_dev_ex(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), bounds, hyper, index, modes, n,
-                                              _p(lr_dev), 0 if lr_dev is None else lr_dev.numel(), _p(state3), _p(clip4), _s()),
-          "adam_step_segments_dev_ex")
-    for t in (param, exp_avg, exp_avg_sq):
-        torch.autograd.graph.increment_version(t)
+    _adam_call("adam_step_segments_dev_ex", param, grad, exp_avg, exp_avg_sq,
+               *_segment_tables("adam_step_segments_dev_ex", segments, True, state3, ex=True), *_lr_table(lr_dev), _p(state3), _p(clip4))
 
 
 # ---------------------------------------------------------------- profiling

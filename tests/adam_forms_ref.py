@@ -1,6 +1,6 @@
 """The float64 reference of ONE Adam step (torch.optim.Adam: coupled L2 weight decay, bias correction, no amsgrad) on flat arrays,
 its per-element error units, and the case table of tests/test_adam_forms_gpu.py (checked without a GPU in
-tests/test_adam_forms_cpu.py).  Every Adam entry point of csrc/fusion.hip (adam1 / adam4 / adam_tick1) is held to this one statement.
+tests/test_adam_forms_cpu.py).  Every Adam entry point of csrc/adam.hip (adam_elem / adam_slot / adam_tick1) is held to this one statement.
 
     lr, b1, b2, eps, wd, coef   rounded to float32 first: the values the C ABI carries
     g      = float32(g * coef) for the clipped forms, rounded on its own (clip_mul)
@@ -47,7 +47,7 @@ HYPER = [
 ]
 SCALES = (1.0, 1e-4, 0.0)
 SIZES = (4, 8, 1020, 4100)
-BIG_N = 8192 * 256 * 4 + 512                      # past adam_kernel's / adam_dev_kernel's grid cap: the grid-stride loop's second pass
+BIG_N = 8192 * 256 * 4 + 512                      # past the flat update kernels' grid cap: the grid-stride loop's second pass
 BIG = {"adam_step": (1, 0), "adam_step_dev": (5, 1)}          # entry -> (hyper, scale index) of its one BIG_N case
 
 
@@ -113,7 +113,7 @@ MUTATIONS = ("decoupled_weight_decay", "eps_inside_bc2_division", "bc2_from_doub
 
 
 def float32_restatement(p, g, m, v, lr, b1, b2, eps, wd, step, coef=None):
-    """adam1 as csrc/fusion.hip writes it, every operation rounded to float32 on its own (NumPy: no fused multiply-add); the bias
+    """adam_elem's coupled branch as csrc/adam.hip writes it, every operation rounded to float32 on its own (NumPy: no fused multiply-add); the bias
     corrections from double pow rounded to float32 as the launchers and adam_tick1 form them.  For tests/test_adam_forms_cpu.py."""
     F = np.float32
     p, g, m, v = (np.asarray(a, dtype=F) for a in (p, g, m, v))

@@ -1,7 +1,7 @@
 """The float64 reference of ONE Adam step with DECOUPLED weight decay (torch.optim.AdamW; no amsgrad) on flat arrays, its per-element
 error units and the bars of tests/test_adamw_forms_gpu.py and tests/test_adamw_optim_gpu.py (checked without a GPU in
 tests/test_adamw_forms_cpu.py).  The case table, the inputs, `Arena`, `units` and the coupled reference are adam_forms_ref's,
-imported and never copied; every decoupled entry point of csrc/fusion.hip (adamw1 / adamw4 / adamw_factor) is held to this one
+imported and never copied; every decoupled entry point of csrc/adam.hip (adam_elem<true> / adam_slot / adamw_factor) is held to this one
 statement.
 
     lr, b1, b2, eps, wd, coef   rounded to float32 first: the values the C ABI carries
@@ -84,7 +84,7 @@ def reference(p, g, m, v, lr, b1, b2, eps, wd, step, coef=None, skipped=False, m
 
 
 def float32_restatement(p, g, m, v, lr, b1, b2, eps, wd, step, coef=None):
-    """adamw1 as csrc/fusion.hip writes it, every operation rounded to float32 on its own (NumPy: no fused multiply-add); the bias
+    """adam_elem's decoupled branch as csrc/adam.hip writes it, every operation rounded to float32 on its own (NumPy: no fused multiply-add); the bias
     corrections from double pow rounded to float32 as the launchers and adam_tick1 form them.  For tests/test_adamw_forms_cpu.py."""
     F = np.float32
     p, g, m, v = (np.asarray(a, dtype=F) for a in (p, g, m, v))

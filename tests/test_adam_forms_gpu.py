@@ -1,4 +1,4 @@
-"""Every Adam entry point of csrc/fusion.hip called directly (ops.*) and held, element by element, to the float64 statement of one
+"""Every Adam entry point of csrc/adam.hip called directly (ops.*) and held, element by element, to the float64 statement of one
 torch.optim.Adam step in tests/adam_forms_ref.py - the parameter, both moments and, for the device forms, the state rows their tick
 kernels advance.  Runs on an MI355X only; the reference, its units, the bars and the case table are checked without a GPU in
 tests/test_adam_forms_cpu.py.
@@ -30,11 +30,11 @@ Measured on an MI355X (every line: profiles/adam_forms_errors.txt), smallest .. 
   mvg_adam_step_segments_dev_clip  (coef 0.37 and 1)     1.03 .. 1.887  12  0.79 .. 1.958   8   0.77 .. 1.468   8   1.1e-07 .. 3.2e-03
   mvg_adam_step, 20 teacher-forced steps                 1.59 .. 1.897  12  1.17 .. 1.937   8   0.96 .. 1.179   8   6.4e-05 .. 5.9e-04
   mvg_adam_step_segments_dev, 20 teacher-forced steps    1.50 .. 1.865  12  1.06 .. 1.952   8   0.89 .. 1.150   8   1.7e-04 .. 9.8e-03
-  adam_tick_kernel / adam_tick_segments_kernel / adam_tick_segments_clip_kernel: 37 / 201 / 282 rows, every bc1 and sqrt(bc2) the
+  adam_tick_kernel / adam_tick_segments_kernel without a record / with one: 37 / 201 / 282 rows, every bc1 and sqrt(bc2) the
   float32 nearest to the float64 value (0 ulp; the bar is 1), every count exact
 The kernel sits at the float32 restatement's own level (2.9 / 2.0 / 1.8 units on the CPU) and below it on m, where the compiler
 contracts b1 * m + (1 - b1) * g_r into a fused multiply-add.  The segmented forms print the same figures as each other - they run
-the same adam1 on the same bits - and the unclipped ones the same as the clipped ones at coef = 1.  The step max-rel column is what
+the same adam_elem on the same bits - and the unclipped ones the same as the clipped ones at coef = 1.  The step max-rel column is what
 the parameter-relative anchor never saw; it is large (1e-3) only where the largest step of a segment is itself small against |p|,
 i.e. where it measures the rounding of p' - the units account for that, the column does not.
 The sub-normal case: (1 - b2) g^2 = 1e-42 is kept, not flushed, on all 1020 elements; |p'| reaches 0.99999998 of its bound."""

@@ -2,7 +2,7 @@
 its step counters / bias corrections (one row per segment) on the device.
 
 Reference for every slice: ops.adam_step_dev (mvg_adam_step_dev) on clones of that slice, with a one-element lr_dev and a one-row
-state3 holding the same starting count.  Both run the same device arithmetic (adam_tick1, adam1 / adam4), so the bar is
+state3 holding the same starting count.  Both run the same device arithmetic (adam_tick1, adam_elem / adam_slot), so the bar is
 torch.equal - on the parameter, both moments and the state rows.  Outside the segments the int32 views are unchanged.  Shapes are
 the ones tests/test_finetune_gpu.py found necessary for mvg_adam_step_segments."""
 import numpy as np

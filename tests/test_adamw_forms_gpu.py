@@ -1,4 +1,4 @@
-"""Every entry point of decoupled weight decay in csrc/fusion.hip called directly (ops.*) and held, element by element, to the
+"""Every entry point of decoupled weight decay in csrc/adam.hip called directly (ops.*) and held, element by element, to the
 float64 statement of one torch.optim.AdamW step in tests/adamw_forms_ref.py - the parameter, both moments and, for the device
 forms, the state rows their tick kernels advance.  Runs on an MI355X only; the reference, its units, the bars and the table's
 sensitivity are checked without a GPU in tests/test_adamw_forms_cpu.py.
@@ -30,7 +30,7 @@ Measured on an MI355X (every line: profiles/adamw_forms_errors.txt), smallest ..
   mvg_adam_step_segments_ex      NULL record (15)        0.97 .. 1.79  8     0.79 .. 1.89   8     0.49 .. 1.18   7     1.1e-07 .. 1.4e-03
   mvg_adam_step_segments_ex      coef 0.37 and 1 (30)    0.97 .. 1.87  8     0.79 .. 1.96   8     0.49 .. 1.18   7     1.1e-07 .. 3.2e-03
   mvg_adam_step_segments_ex      mixed modes (6)         0.89 .. 1.67  8     1.36 .. 1.83   8     0.75 .. 0.99   7     1.4e-07 .. 1.0e-04
-  mvg_adam_step_segments_dev_ex  the same 51 cases: the same figures in every digit (the same adamw1 on the same bits)
+  mvg_adam_step_segments_dev_ex  the same 51 cases: the same figures in every digit (the same adam_elem<true> on the same bits)
   mvg_adamw_step, 20 teacher-forced steps                0.95 .. 1.90  8     0.60 .. 1.94   8     0.90 .. 1.13   7     2.7e-04 .. 1.9e-03
   mvg_adam_step_segments_dev_ex, 20 teacher-forced steps 0.94 .. 1.84  8     0.58 .. 1.93   8     0.91 .. 1.13   7     4.1e-04 .. 9.8e-03
   the ticks: 108 lines of rows, every bc1 and sqrt(bc2) the float32 nearest to the float64 value (0 ulp; the bar is 1), every count exact
@@ -431,3 +431,32 @@ def test_twenty_teacher_forced_steps_of_adam_step_segments_dev_ex():
         for got, old in zip((p, m, v), (arena.p, arena.m, arena.v)):
             fails.check(same_bits(down(got)[mask], old[mask]), f"{case}: something outside the segments changed")
     fails.done()
+
+
+# ---------------------------------------------------------------- the version counters, every wrapper
+WRAPPERS = ["adam_step", "adamw_step", "adam_step_dev", "adamw_step_dev", "adam_step_segments", "adam_step_segments_clip",
+            "adam_step_segments_ex", "adam_step_segments_dev", "adam_step_segments_dev_clip", "adam_step_segments_dev_ex"]
+
+
+@pytest.mark.parametrize("entry", WRAPPERS)
+def test_every_wrapper_bumps_the_version_counters_of_what_the_kernel_wrote(entry):
+    """The kernels write param, exp_avg and exp_avg_sq through raw pointers; autograd's saved-tensor checks and the inference
+    path's cache of split weights learn of it from the version counters alone, so every ops wrapper must raise all three."""
+    lr, b1, b2, eps, wd = 1e-3, 0.9, 0.999, 1e-8, 1e-2
+    p, g, m, v = (torch.full((64,), x, device=dev()) for x in (0.5, 0.25, 0.0, 0.0))
+    before = [t._version for t in (p, m, v)]
+    segmented, on_dev, ex = "segments" in entry, "_dev" in entry, entry.endswith("_ex")
+    bounds = [(0, 16), (32, 48)]
+    args = []
+    if segmented:
+        args.append([(b, e) + ((0, b1, b2, eps, wd) if on_dev else (lr, b1, b2, eps, wd, 1)) + ((k,) if ex else ()) for k, (b, e) in enumerate(bounds)])
+    if on_dev:
+        args += [up(np.array([lr], dtype=np.float32)), torch.zeros((2, 3) if segmented else (3,), device=dev())]
+    if not segmented:
+        args += [b1, b2, eps, wd] if on_dev else [lr, b1, b2, eps, wd, 1]
+    if ex or entry.endswith("_clip"):
+        args.append(up(np.array([0.0, 1.0, 0.0, 0.0], dtype=np.float32)))
+    getattr(ops, entry)(p, g, m, v, *args)
+    torch.cuda.synchronize()
+    assert all(t._version > was for t, was in zip((p, m, v), before)), (entry, before, [t._version for t in (p, m, v)])
+    assert bool((p != 0.5).any()) and bool((m != 0).any())              # (the call did run its update)

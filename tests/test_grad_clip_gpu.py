@@ -5,7 +5,7 @@ float32: within ONE float32 ulp - the kernel's double sum over <= 1e8 exact squa
 inside a float32 ulp (6e-8 .. 1.2e-7), so after sqrt and the division the two doubles can round to different floats only across
 one rounding boundary.  The clipped updates against the EXISTING ops.adam_step_segments / adam_step_segments_dev on clones whose
 gradient torch first multiplied by the recorded coefficient in fp32 (g.mul(coef)): torch.equal on parameters, both moments and the
-state rows - the clipped kernels round the product to fp32 on its own and then run the same adam1.  Everything outside the
+state rows - the clipped kernels round the product to fp32 on its own and then run the same adam_elem.  Everything outside the
 segments: unchanged as int32.  Kernel-level arenas, segment shapes and RNG are those of tests/test_adam_segments_dev_gpu.py."""
 import numpy as np
 import pytest
